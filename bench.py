@@ -8,7 +8,14 @@ GPU, pose read-back included.  The grid stays resident in HBM.  `value` is a SIN
 one robot's scans are strictly sequential (the next ray cast needs this push), so it is 1 / (time of one scan).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg1|cfg2|cfg3] [--scene room|pillars|comb]
-                  [--mode slam|push] [--storage f64|q32] [--robots R]
+                  [--mode slam|push] [--storage f64|q32] [--robots R] [--full] [--dump-outputs DIR]
+
+  A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs of its own: the CPU
+  baseline, the comparison passes (value_repeat, value_lookahead, value_async_mapping), the registration's spread pass and the
+  stream-bandwidth measurement (roofline.peak_measured); --no-cpu-baseline / --no-second-pass / --no-stream drop them again.
+  --dump-outputs DIR writes what the last timed step left to a caller as DIR/<name>.npy (float64): every robot's report (pose,
+  T, rms, counters) and the grid (tile flags and _initWeight in full, tsd, weight and whether tsd is known -- NaN in the grid,
+  0 in the file -- of a fixed seeded sample of cells); every value finite.
 
   The next scan is announced to the localiser (a replay knows it): its ingest, copy and tables run while the current scan is being
   registered (tsd_scan_stage); --no-lookahead turns that off.
@@ -62,6 +69,9 @@ PROFILE_TAG = "r6"              # profiles/<tag>_<workload>_*: the committed roc
 STREAM_DOUBLES = 48 << 20    # tsd_measure_stream: 2 arrays x 48 Mi doubles = 768 MiB footprint (3x the 256 MiB Infinity Cache)
 CPU_REPEATS = 3              # cpu_baseline: passes per thread count (the median is reported)
 STAGES = ("raycast", "icp", "push_classify", "push_update", "push_halo")
+DUMP_SAMPLE_CELLS = 1 << 21  # --dump-outputs: cells of the grid's tsd / weight sampled (3 x 16 MiB as float64 with tsd's mask)
+DUMP_SEED = 20261016         # --dump-outputs: seed of that sample
+DUMP_MAX_BYTES = 64 << 20    # --dump-outputs: bound on all arrays together
 
 
 def workload_key(cfg: str, scene: str, mode: str, storage: str) -> str:
@@ -215,6 +225,36 @@ def cpu_baseline(cfg_name: str, scene: str, mode: str, n_multi: int):
 
 
 # ------------------------------------------------------------------------------------------------ timing helpers
+def grid_outputs(grid) -> dict:
+    """The grid as a caller finds it after the last timed step: per tile the init flag and _initWeight in full, tsd and weight of
+    DUMP_SAMPLE_CELLS cells drawn once with a fixed seed (the same cells for the same grid size in every run).  A cell no scan has
+    reached holds tsd NaN (the reference's "no distance yet"): grid_tsd_sample carries 0 there and grid_tsd_sample_known 0, so
+    that every array is finite."""
+    init, iw, tsd, w = grid.download_tiles()
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.unique(rng.integers(0, tsd.size, min(DUMP_SAMPLE_CELLS, tsd.size)))
+    tsd_s = tsd.reshape(-1)[idx]
+    known = ~np.isnan(tsd_s)
+    return {"grid_tile_init": init.astype(np.float64), "grid_tile_init_weight": iw,
+            "grid_tsd_sample": np.where(known, tsd_s, 0.0), "grid_tsd_sample_known": known.astype(np.float64),
+            "grid_weight_sample": w.reshape(-1)[idx]}
+
+
+def write_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as <path>/<name>.npy in float64; refuses a value that is not finite and more than DUMP_MAX_BYTES
+    in all."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    bad = [k for k, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise SystemExit(f"bench.py: --dump-outputs: not finite: {', '.join(bad)}")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def stage_table(grid, steps):
     """Mean dispatch duration of every stage kernel from the events sampled in the timed region, and its share of a
     step (launches per step x mean duration)."""
@@ -270,6 +310,11 @@ def main():
                     help="`value` with the facade's async_mapping = 1 (the push beside the next registration, the next ray cast one "
                          "push behind: the reference's own ThreadMapping is asynchronous); default: strict order, and the "
                          "asynchronous rate as value_async_mapping")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the CPU baseline, the comparison passes, the spread pass and the "
+                         "stream-bandwidth measurement (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (reports, a seeded sample of the grid) as DIR/<name>.npy")
     ap.add_argument("--launch-check", action="store_true",
                     help="multi-rank plumbing only (no GPU work): the ranks rendezvous over gloo, sum their ranks, rank 0 prints "
                          "{launch_check, world_size}.  With --gpus N and no launcher this goes through the self-launch path.")
@@ -341,6 +386,9 @@ def main():
         out = run_slam(args, gc, geo, scene, K, W, every, every_upd, every_icp, device, rank, local_rank, world_size, use_dist, dist, torch,
                        facade, multigpu, synth)
     rc = 0
+    dump = out.pop("_dump", None)
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, dump)
     if rank == 0:
         st, pushes, upd_ms, upd_launches = out.pop("_stats")
         stream_best, stream_mean = out.pop("_stream")
@@ -405,7 +453,7 @@ def main():
                 "sum_avg_launch_ms": t_push,
                 "achieved": bytes_per_launch / (t_push * 1e-3) / 1e9, "frac": bytes_per_launch / (t_push * 1e-3) / 1e9 / HBM_PEAK_GBS,
                 "of": "the same algorithmic bytes over the summed average durations of the push's kernels (sampled dispatches)"}
-        if not args.no_cpu_baseline and args.robots == 1 and not args.registration_mode:
+        if args.full and not args.no_cpu_baseline and args.robots == 1 and not args.registration_mode:
             # (rank 0 only, whatever N: one robot's workload on this box's host cores; the other ranks wait at the closing barrier)
             # (its own sample size: the bound is CPU seconds -- ~10 s over the whole sweep at cfg 2 -- not the GPU leg's K)
             line["cpu_baseline"] = cpu_baseline(args.config, scene, mode, args.cpu_scans or (12 if args.config == "cfg3" else 100))
@@ -522,7 +570,8 @@ def run_push(args, gc, geo, scene, K, W, every, every_upd, device, capi, synth):
     stages = stage_table(grid, K)
     st, pushes = grid.push_stats_total()
     grid.profile(False)
-    stream = grid.measure_stream(STREAM_DOUBLES, 5) if not args.no_stream else (None, None)
+    dump = grid_outputs(grid) if args.dump_outputs else None
+    stream = grid.measure_stream(STREAM_DOUBLES, 5) if (args.full and not args.no_stream) else (None, None)
     if args.calibrate:
         grid.calibrate_rmw(CALIB_DOUBLES, 3)
     for _ in range(args.occupancy):
@@ -537,7 +586,7 @@ def run_push(args, gc, geo, scene, K, W, every, every_upd, device, capi, synth):
         "pushes_in_timed_region": pushes, "cells_updated_per_push": st["cells_updated"] / max(pushes, 1),
         "cells_visited_per_push": st["cells_visited"] / max(pushes, 1),
         "tiles_updated_per_push": st["tiles_update"] / max(pushes, 1),
-        "_stats": (st, pushes, upd_ms, upd_launches), "_stream": stream,
+        "_stats": (st, pushes, upd_ms, upd_launches), "_stream": stream, "_dump": dump,
     }
     grid.close()
     return out
@@ -554,7 +603,8 @@ def run_slam(args, gc, geo, scene, K, W, every, every_upd, every_icp, device, ra
     lanes = synth.free_lanes(world, R, 0.06 * leg, clearance=0.6) if R > 1 else [(float(world.start[0]), float(world.start[1]))]
     poses, scans = [], []
     for r in range(R):
-        p = synth.trajectory(world, 1 + W + max(K, SPREAD_STEPS if R == 1 else K), leg=leg)
+        # (the spread pass of --full replays SPREAD_STEPS scans; the poses of a shorter trajectory are its first ones)
+        p = synth.trajectory(world, 1 + W + max(K, SPREAD_STEPS if (R == 1 and args.full) else K), leg=leg)
         p[:, 1] += lanes[r][1] - world.start[1]
         poses.append(p); scans.append(synth.scans_for(world, geo, p))
     scans32 = [np.ascontiguousarray(np.stack(sc), dtype=np.float32) for sc in scans]
@@ -581,14 +631,14 @@ def run_slam(args, gc, geo, scene, K, W, every, every_upd, every_icp, device, ra
         params["registration_mode"] = args.registration_mode
         params["tsdpdf_seed"] = 20261003
 
-    def one_pass(lookahead: bool, full: bool, async_mapping: bool = False, K=K, every_icp_dispatch: bool = False):
-        """init + W warm-up scans + K timed scans on a fresh node; `full`: with the occupancy merge (N > 1), the stage table and
-        everything else the line reports; otherwise just the rate (the comparison passes).  every_icp_dispatch: HIP events around EVERY
+    def one_pass(lookahead: bool, main_pass: bool, async_mapping: bool = False, K=K, every_icp_dispatch: bool = False):
+        """init + W warm-up scans + K timed scans on a fresh node; `main_pass`: with the occupancy merge (N > 1), the stage table
+        and everything else the line reports; otherwise just the rate (the comparison passes of --full).  every_icp_dispatch: HIP events around EVERY
         registration of the region, returned as samples (the spread pass: its rate is not reported, the events cost stream time)."""
         node = facade.SlamNode(dict(params, async_mapping=1) if async_mapping else params, device=device, synchronous=True)
         grid = node.grid()
         merger = None
-        if use_dist and full:
+        if use_dist and main_pass:
             # the merge itself is the C ABI of include/tsd_comm.h (extraction kernels + ncclAllReduce(int8, max) on the grid's
             # stream); torch.distributed only carries the communicator's unique id to the ranks
             ids = [multigpu.NativeOccupancyMerger.new_id() if rank == 0 else None]
@@ -662,7 +712,7 @@ def run_slam(args, gc, geo, scene, K, W, every, every_upd, every_icp, device, ra
         else:
             grid.profile(True, kernels=f"push_update:{every_upd},icp:{every_icp},all/{every}")      # HIP events on every n-th dispatch of each kernel
         grid.profile_reset()
-        if dist is not None and full:
+        if dist is not None and main_pass:
             torch.cuda.synchronize()
             dist.barrier()
         b0 = node.batch_stats()
@@ -673,7 +723,7 @@ def run_slam(args, gc, geo, scene, K, W, every, every_upd, every_icp, device, ra
         occ_calls = [0]
         occ_stop = threading.Event()
         occ_thread = None
-        if args.occupancy_every_ms > 0 and full:
+        if args.occupancy_every_ms > 0 and main_pass:
             def map_thread():
                 while not occ_stop.wait(args.occupancy_every_ms * 1e-3):
                     grid.occupancy(False, 2)
@@ -695,10 +745,10 @@ def run_slam(args, gc, geo, scene, K, W, every, every_upd, every_icp, device, ra
         elapsed = time.perf_counter() - t0
         if merger is not None:
             grid.sync(); merger.wait()    # (nothing left to wait for: the library's own bookkeeping of the merge's events)
-        if dist is not None and full:
+        if dist is not None and main_pass:
             dist.barrier()
         pygc.enable()
-        if not full:
+        if not main_pass:
             samples = grid.profile_samples("icp") if every_icp_dispatch else None
             grid.profile(False)
             node.close()
@@ -711,9 +761,10 @@ def run_slam(args, gc, geo, scene, K, W, every, every_upd, every_icp, device, ra
         bstats = (b1[0] - b0[0], b1[1] - b0[1])
         st, pushes = grid.push_stats_total()
         grid.profile(False)
-        errs = []
+        errs, finals = [], []
         for r in range(R):
             final = node.report(robot=r)
+            finals.append(final)
             errs.append(math.hypot(final["pose"][0, 2] - poses[r][W + K, 0], final["pose"][1, 2] - poses[r][W + K, 1]))    # (the last scan processed)
 
         ranks = None
@@ -728,7 +779,13 @@ def run_slam(args, gc, geo, scene, K, W, every, every_upd, every_icp, device, ra
             t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}" if args.pg_backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        stream = grid.measure_stream(STREAM_DOUBLES, 5) if (rank == 0 and not args.no_stream) else (None, None)
+        dump = None
+        if args.dump_outputs and rank == 0:
+            # what the caller of the last timed step holds: every robot's report and the grid its push left
+            dump = {"pose": np.stack([f["pose"] for f in finals]), "T": np.stack([f["T"] for f in finals]),
+                    "report": np.array([[f[k] for k in facade.REPORT_FIELDS] for f in finals], dtype=np.float64)}
+            dump.update(grid_outputs(grid))
+        stream = grid.measure_stream(STREAM_DOUBLES, 5) if (rank == 0 and args.full and not args.no_stream) else (None, None)
         if args.calibrate:
             grid.calibrate_rmw(CALIB_DOUBLES, 3)
         pdf_ms, pdf_n = grid.profile_get("tsdpdf")
@@ -781,7 +838,7 @@ def run_slam(args, gc, geo, scene, K, W, every, every_upd, every_icp, device, ra
             "cells_visited_per_push": st["cells_visited"] / max(pushes, 1),
             "tiles_updated_per_push": st["tiles_update"] / max(pushes, 1),
             "tracking_error_m": max(errs),
-            "_stats": (st, pushes, upd_ms, upd_launches), "_stream": stream, "_ranks": ranks,
+            "_stats": (st, pushes, upd_ms, upd_launches), "_stream": stream, "_ranks": ranks, "_dump": dump,
         }
         if args.occupancy_every_ms > 0:
             out["occupancy_calls_in_timed_region"] = occ_calls[0]
@@ -799,7 +856,7 @@ def run_slam(args, gc, geo, scene, K, W, every, every_upd, every_icp, device, ra
     out = one_pass(args.lookahead, True, args.async_mapping and R == 1)
     out["config"]["mapping"] = ("asynchronous: the push runs beside the next registration, the next ray cast is one push behind"
                                 if (args.async_mapping and R == 1) else "strict: the next ray cast sees this scan's push")
-    if R == 1 and not use_dist and not args.no_second_pass:
+    if R == 1 and not use_dist and args.full and not args.no_second_pass:
         # `value` is the rate a live scanner's subscriber gets: scan k+1 is handed over when scan k's result has been seen (it never has the
         # next LaserScan queued; the reference's localiser takes the newest scan, ThreadLocalize.cpp:319-332).  Beside it, each the
         # median of three passes on fresh nodes with its spread (one pass of 20 scans on a fresh node is not a number -- VERDICT r3):

@@ -9,6 +9,7 @@ both loops with work still queued (ThreadSLAM.cpp:19-33).  Built twice: -fsaniti
 -fsanitize=address,undefined (lifetime of the queued sensor copies, leaks at shutdown)."""
 import math
 import os
+import platform
 import shutil
 import subprocess
 
@@ -35,6 +36,17 @@ def _build(tmp, tag, flags):
     return exe
 
 
+def _no_aslr():
+    """The command prefix that starts ONE process without address-space randomisation (setarch -R: that process's personality),
+    or [] where it is not available.  GCC 11's ThreadSanitizer expects the executable and its libraries where a kernel with 28
+    bits of mmap randomisation puts them; with more (vm.mmap_rnd_bits = 32) it stops before main with "FATAL: ThreadSanitizer:
+    unexpected memory mapping"."""
+    s = shutil.which("setarch")
+    if s and subprocess.run([s, platform.machine(), "-R", "true"], capture_output=True).returncode == 0:
+        return [s, platform.machine(), "-R"]
+    return []
+
+
 @pytest.mark.parametrize("tag,flags,env", [
     ("tsan", ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=0 exitcode=66 second_deadlock_stack=1"}),
     ("asan", ["-fsanitize=address,undefined"], {"ASAN_OPTIONS": "detect_leaks=1 exitcode=67", "UBSAN_OPTIONS": "print_stacktrace=1 halt_on_error=1"}),
@@ -43,7 +55,7 @@ def test_thread_contract_under_sanitizer(tmp_path, tag, flags, env):
     if not (shutil.which("g++") and shutil.which("gcc")):
         pytest.skip("no host compiler")
     exe = _build(str(tmp_path), tag, flags)
-    r = subprocess.run([exe], env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
+    r = subprocess.run(_no_aslr() + [exe], env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
     out = r.stdout + r.stderr
     assert "Sanitizer" not in out, out[-4000:]               # no report of either sanitizer
     assert r.returncode == 0, out[-4000:]
