@@ -197,6 +197,36 @@ int tsd_tsdpdf_match(tsd_ctx* ctx, const double pose33[9], const double* model_x
                      const int* draws_subsample, const int* draws_control, const int* draws_trials,
                      tsd_tsdpdf_result* result);
 
+/* ---- pre-registration (registration_mode 2) ------------------------------------------------------------- */
+/* obvious::PDFMatching(trials, epsThresh, sizeControlSet, zhit, zphi, zshort, zmax, zrand, percentagePointsInC, rangemax,
+ * sigphi, sighit, lamshort, maxAngleDiff, maxAnglePenalty) (PDFMatching.cpp:9-40; ThreadLocalize.cpp:185-187) and the
+ * arguments of its match() that are not point sets (ThreadLocalize.cpp:547) */
+typedef struct {
+  int    trials;                  /* "trials" */
+  int    size_control_set;        /* "sizeControlSet" */
+  double eps_thresh;              /* "epsThresh"; only sets _scaleDistance, which match() never reads */
+  double zhit, zphi, zshort, zmax, zrand;   /* mixture weights of probabilityOfTwoSingleScans (PDFMatching.cpp:435-487) */
+  double percentage_points_in_c;  /* "percentagePointsInC": share of the control set that has to be in view (:373) */
+  double rangemax;                /* "rangemax" */
+  double sigphi, sighit, lamshort;
+  double max_angle_diff;          /* "maxAngleDiff", degrees: a control point is in view within this of a model beam (:227, :339) */
+  double max_angle_penalty;       /* "maxAnglePenalty"; match() never reads it */
+  double phi_max;                 /* deg2rad("ransac_phi_max"), capped at pi/2 inside (:159) */
+  double ang_res;                 /* sensor->getAngularResolution() */
+} tsd_pdfmatch_params;
+/* obvious::PDFMatching::match(M, maskM, NULL, S, maskS, phiMax, transMax, resolution) (PDFMatching.cpp:47-432): the same
+ * beam-indexed inputs and rand() streams as tsd_tsdpdf_match (the front end is shared), no grid and no sensor pose: the
+ * control set is scored in the sensor frame against the model's polar angles and ranges.  T is TBest (identity on the
+ * reference's early returns: too few points, too few valid points, resolution <= 1e-6); `probability` is the winning
+ * product, counts as in tsd_tsdpdf_result.  Scoring and arg-max run on the device. */
+int tsd_pdf_match(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m, const double* scene_xy_2B,
+                  const uint8_t* mask_s, int beams, const tsd_pdfmatch_params* params, const int* draws_subsample,
+                  const int* draws_control, const int* draws_trials, tsd_tsdpdf_result* result);
+/* TEST HOOK: the last tsd_pdf_match's per-candidate values in candidate order (the reference's serial trial / i order):
+ * the product over the control set before the field-of-view gate and the field-of-view count.  Copies min(n, cap) entries
+ * and returns n (0 when the last pre-registration call on this context scored nothing or was a tsd_tsdpdf_match). */
+int tsd_debug_pdf_match_scores(tsd_ctx* ctx, double* prob_ungated, int* fov, int cap);
+
 /* ---- fused scan: ThreadLocalize::eventLoop + ThreadMapping push without a host round trip ------------ */
 /* Device-resident mirror of one robot's obvious::SensorPolar2D (pose, world / local ray maps) and of
  * ThreadLocalize's pose bookkeeping (_lastPose).  Several sensors may share one grid context

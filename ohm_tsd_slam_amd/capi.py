@@ -80,6 +80,21 @@ class TsdPdfResult(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class PdfMatchParams(C.Structure):
+    """tsd_pdfmatch_params"""
+    _fields_ = [("trials", C.c_int), ("size_control_set", C.c_int), ("eps_thresh", C.c_double), ("zhit", C.c_double),
+                ("zphi", C.c_double), ("zshort", C.c_double), ("zmax", C.c_double), ("zrand", C.c_double),
+                ("percentage_points_in_c", C.c_double), ("rangemax", C.c_double), ("sigphi", C.c_double), ("sighit", C.c_double),
+                ("lamshort", C.c_double), ("max_angle_diff", C.c_double), ("max_angle_penalty", C.c_double), ("phi_max", C.c_double),
+                ("ang_res", C.c_double)]
+
+
+# the node's defaults for registration_mode 2 (ThreadLocalize.cpp:105-128): PdfMatchParams fields -> value
+PDFMATCH_DEFAULTS = dict(trials=100, size_control_set=140, eps_thresh=0.15, zhit=0.45, zphi=0.0, zshort=0.25, zmax=0.05, zrand=0.25,
+                         percentage_points_in_c=0.9, rangemax=20.0, sigphi=3.141592653589793 / 180.0 * 3, sighit=0.2,
+                         lamshort=0.08, max_angle_diff=3.0, max_angle_penalty=0.5)
+
+
 class IcpResult(C.Structure):
     _fields_ = [
         ("T", C.c_double * 9),
@@ -170,6 +185,9 @@ ABI = {
     "tsd_icp_trace": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "tsd_tsdpdf_match": (C.c_int, [C.c_void_p, _dp, _dp, _u8p, _dp, _u8p, C.c_int, C.POINTER(TsdPdfParams), _ip, _ip, _ip,
                                    C.POINTER(TsdPdfResult)]),
+    "tsd_pdf_match": (C.c_int, [C.c_void_p, _dp, _u8p, _dp, _u8p, C.c_int, C.POINTER(PdfMatchParams), _ip, _ip, _ip,
+                                C.POINTER(TsdPdfResult)]),
+    "tsd_debug_pdf_match_scores": (C.c_int, [C.c_void_p, _dp, _ip, C.c_int]),
     "tsd_scan_preregister": (C.c_int, [C.c_void_p, C.POINTER(TsdPdfParams), _dp, _u8p, _ip, _ip, _ip]),
     "tsd_scan_preregistration_result": (C.c_int, [C.c_void_p, C.POINTER(TsdPdfResult)]),
     "tsd_sensor_set_async_mapping": (C.c_int, [C.c_void_p, C.c_int]),
@@ -222,7 +240,8 @@ def load_library(path: str | None = None):
     # the ctypes mirrors of the public structs must have the library's layout
     for cname, mirror in (("tsd_push_stats", PushStats), ("tsd_icp_params", IcpParams), ("tsd_icp_result", IcpResult),
                           ("tsd_gate_params", GateParams), ("tsd_scan_result", ScanResult), ("tsd_grid_digest_t", GridDigest),
-                          ("tsd_tsdpdf_params", TsdPdfParams), ("tsd_tsdpdf_result", TsdPdfResult)):
+                          ("tsd_tsdpdf_params", TsdPdfParams), ("tsd_tsdpdf_result", TsdPdfResult),
+                          ("tsd_pdfmatch_params", PdfMatchParams)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -358,6 +377,30 @@ class TsdGridDevice:
         self._check(rc, "tsd_tsdpdf_match")
         return dict(T=np.array(r.T[:]).reshape(3, 3), prob=r.probability, idx=r.idx_model, i=r.idx_scene,
                     candidates=r.candidates, valid_model=r.valid_model, valid_scene=r.valid_scene, control=r.control_points)
+
+    def pdf_match(self, model_xy, mask_m, scene_xy, mask_s, phi_max, ang_res, draws_sub, draws_ctrl, draws_trials, **kw) -> dict:
+        """obvious::PDFMatching::match with the rand() draws as inputs (tsd_pdf_match); `kw` overrides PDFMATCH_DEFAULTS"""
+        M, S = _f64(model_xy).reshape(-1), _f64(scene_xy).reshape(-1)
+        n = M.size // 2
+        mM, mS = np.ascontiguousarray(mask_m, dtype=np.uint8), np.ascontiguousarray(mask_s, dtype=np.uint8)
+        ds, dc, dt = (np.ascontiguousarray(x, dtype=np.int32) for x in (draws_sub, draws_ctrl, draws_trials))
+        v = dict(PDFMATCH_DEFAULTS, **kw)
+        assert ds.size >= n and dc.size >= v["size_control_set"] and dt.size >= v["trials"]
+        prm = PdfMatchParams(phi_max=phi_max, ang_res=ang_res, **v)
+        r = TsdPdfResult()
+        rc = self.lib.tsd_pdf_match(self.h, _d(M), _u8(mM), _d(S), _u8(mS), n, C.byref(prm), ds.ctypes.data_as(_ip),
+                                    dc.ctypes.data_as(_ip), dt.ctypes.data_as(_ip), C.byref(r))
+        self._check(rc, "tsd_pdf_match")
+        return dict(T=np.array(r.T[:]).reshape(3, 3), prob=r.probability, idx=r.idx_model, i=r.idx_scene,
+                    candidates=r.candidates, valid_model=r.valid_model, valid_scene=r.valid_scene, control=r.control_points)
+
+    def debug_pdf_match_scores(self):
+        """TEST HOOK: the last pdf_match's ungated products and field-of-view counts, in candidate order"""
+        n = self.lib.tsd_debug_pdf_match_scores(self.h, None, None, 0)
+        self._check(min(n, 0), "tsd_debug_pdf_match_scores")
+        p, f = np.zeros(max(n, 1)), np.zeros(max(n, 1), dtype=np.int32)
+        self.lib.tsd_debug_pdf_match_scores(self.h, _d(p), f.ctypes.data_as(_ip), n)
+        return p[:n], f[:n]
 
     def icp(self, model_xy, scene_xy, pose, params: IcpParams, model_normals_xy=None) -> IcpOut:
         m = _f64(model_xy).reshape(-1)

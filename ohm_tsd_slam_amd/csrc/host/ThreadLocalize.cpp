@@ -81,6 +81,8 @@ ThreadLocalize::ThreadLocalize(obvious::TsdGrid* grid, ThreadMapping* mapper, co
   _regMode     = (int)node->get_parameter(_robotName + "registration_mode").as_int();
   _ranPhiMax   = node->get_parameter(_robotName + "ransac_phi_max").as_double();
   _preMatcher.reset();
+  _pdfMatcher.reset();
+  std::memset(&_preResult, 0, sizeof(_preResult));
   switch(_regMode)
   {
   case 0:   // ICP: no instance needed
@@ -92,10 +94,30 @@ ThreadLocalize::ThreadLocalize(obvious::TsdGrid* grid, ThreadMapping* mapper, co
                                                    node->get_parameter("zrand").as_double()));
     _preMatcher->setSeed((long)param(node, _robotName + "tsdpdf_seed", -1).as_int());   // addition: reproducible draws for tests
     break;
+  case 2:   // PDF (ThreadLocalize.cpp:185-187): PDFMatching(trials, epsThresh, sizeControlSet, zhit, ..., maxAnglePenalty)
+    if(!obvious::PDFMatching::available())
+    {
+      std::fprintf(stderr, "Localizer(%s): registration mode 2 (PDFMatching pre-registration): the device library has no "
+                           "tsd_pdf_match; using default = ICP.\n", _nameSpace.c_str());
+      _regMode = 0;
+      break;
+    }
+    _pdfMatcher.reset(new obvious::PDFMatching(*grid, (unsigned)node->get_parameter("trials").as_int(),
+                                               node->get_parameter("epsThresh").as_double(),
+                                               (unsigned)node->get_parameter("sizeControlSet").as_int(),
+                                               node->get_parameter("zhit").as_double(), node->get_parameter("zphi").as_double(),
+                                               node->get_parameter("zshort").as_double(), node->get_parameter("zmax").as_double(),
+                                               node->get_parameter("zrand").as_double(),
+                                               node->get_parameter("percentagePointsInC").as_double(),
+                                               node->get_parameter("rangemax").as_double(), node->get_parameter("sigphi").as_double(),
+                                               node->get_parameter("sighit").as_double(), node->get_parameter("lamshort").as_double(),
+                                               node->get_parameter("maxAngleDiff").as_double(),
+                                               node->get_parameter("maxAnglePenalty").as_double()));
+    _pdfMatcher->setSeed((long)param(node, _robotName + "tsdpdf_seed", -1).as_int());   // addition: reproducible draws for tests
+    break;
   case 1:   // EXP: RandomNormalMatching
-  case 2:   // PDF: PDFMatching
-    std::fprintf(stderr, "Localizer(%s): registration mode %d (RandomNormalMatching / PDFMatching pre-registration) is not part of "
-                         "the GPU hot path (SURVEY 2: out of scope); using default = ICP.\n", _nameSpace.c_str(), _regMode);
+    std::fprintf(stderr, "Localizer(%s): registration mode 1 (RandomNormalMatching pre-registration) is not part of "
+                         "the GPU hot path (out of scope); using default = ICP.\n", _nameSpace.c_str());
     _regMode = 0;
     break;
   default:  // ThreadLocalize.cpp:188-190
@@ -301,7 +323,9 @@ void ThreadLocalize::processScan(const std::vector<float>& ranges, const builtin
   // this robot has the fused path to itself; the reference's own call structure otherwise (and with TSD_MODE3_UNFUSED set: A/B)
   static const bool mode3Unfused = std::getenv("TSD_MODE3_UNFUSED") != nullptr;
   // (several robots on one grid: the batched dispatcher runs the pre-registration behind its batch's ray casts; the split scan does not)
-  if(_regMode == 3 && _preMatcher && (mode3Unfused || !_preFusedOk || !_fused || !_sensor->deviceHandle() || (_concurrent && !_grid.batcher())))
+  // (registration_mode 2: always the reference's call structure, the matcher's host part between the ray cast and the registration)
+  if((_regMode == 3 && _preMatcher && (mode3Unfused || !_preFusedOk || !_fused || !_sensor->deviceHandle() || (_concurrent && !_grid.batcher()))) ||
+     (_regMode == 2 && _pdfMatcher))
   {
     processScanPreRegistered(rep);
     return;
@@ -386,8 +410,20 @@ void ThreadLocalize::processScanPreRegistered(ScanReport& rep)
   g_m3.lap(1);
   // doRegistration, case TSD: T = _TSD_PDFMatcher->match(sensor->getTransformation(), M, _maskM, NULL, S, _maskS,
   //                                                      deg2rad(_ranPhiMax), _trnsMax, sensor->getAngularResolution())
-  obvious::Matrix Tpre = _preMatcher->match(_sensor->getTransformation(), _modelCoords.data(), maskM, nullptr, _scene.data(), maskS,
-                                            n, _ranPhiMax * M_PI / 180.0, _trnsMax, _sensor->getAngularResolution());
+  //                 case PDF: T = _PDFMatcher->match(M, _maskM, NULL, S, _maskS, deg2rad(_ranPhiMax), _trnsMax,
+  //                                                  sensor->getAngularResolution())  (ThreadLocalize.cpp:545-553)
+  obvious::Matrix Tpre(3, 3);
+  if(_regMode == 2)
+    Tpre = _pdfMatcher->match(_modelCoords.data(), maskM, nullptr, _scene.data(), maskS, n, _ranPhiMax * M_PI / 180.0, _trnsMax,
+                              _sensor->getAngularResolution());
+  else
+    Tpre = _preMatcher->match(_sensor->getTransformation(), _modelCoords.data(), maskM, nullptr, _scene.data(), maskS,
+                              n, _ranPhiMax * M_PI / 180.0, _trnsMax, _sensor->getAngularResolution());
+  {
+    std::lock_guard<std::mutex> lk(_reportMutex);
+    _preResult = _regMode == 2 ? _pdfMatcher->lastResult() : _preMatcher->lastResult();
+    _havePreResult = true;
+  }
   g_m3.lap(2);
   tsd_icp_params p = _icpParams;
   Tpre.getData(p.t_init);
@@ -409,6 +445,15 @@ void ThreadLocalize::processScanPreRegistered(ScanReport& rep)
   g_m3.lap(3);
   finishScan(rep, res);
   g_m3.lap(4); g_m3.scan();
+}
+
+bool ThreadLocalize::lastPreregistration(tsd_tsdpdf_result* out)
+{
+  std::lock_guard<std::mutex> lk(_reportMutex);
+  if(!_havePreResult)
+    return false;
+  *out = _preResult;
+  return true;
 }
 
 // what follows the registration (ThreadLocalize.cpp:381-406): gate, Sensor::transform, pose / tf, push decision

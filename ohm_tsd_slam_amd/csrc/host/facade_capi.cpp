@@ -272,6 +272,19 @@ void tsd_node_report(tsd_node* n, int robot, double* out28)
   out28[26] = r.noModel; out28[27] = r.initialised; out28[28] = (double)r.stampNs;
 }
 
+// the robot's last pre-registration (registration_mode 2 / unfused 3): T[9], probability, idx_model, idx_scene, candidates,
+// valid_model, valid_scene, control_points.  Returns 0 if there was none.
+int tsd_node_preregistration(tsd_node* n, int robot, double* out16)
+{
+  tsd_tsdpdf_result r;
+  if(!n->localizers[robot]->lastPreregistration(&r))
+    return 0;
+  std::memcpy(out16, r.T, sizeof(r.T));
+  out16[9] = r.probability; out16[10] = r.idx_model; out16[11] = r.idx_scene; out16[12] = r.candidates;
+  out16[13] = r.valid_model; out16[14] = r.valid_scene; out16[15] = r.control_points;
+  return 1;
+}
+
 // last PoseStamped on <node>/<robot/>estimated_pose: x, y, z, qx, qy, qz, qw, publish count
 void tsd_node_pose_msg(tsd_node* n, int robot, double* out8)
 {

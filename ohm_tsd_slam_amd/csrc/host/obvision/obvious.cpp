@@ -1,5 +1,10 @@
 // obvious.cpp -- host-side sensor model and the device-grid handle (see obvious.h).
 #include "obvious.h"
+
+// tsd_pdf_match is referenced WEAKLY: host builds that link this file against a device library without registration_mode 2 (the
+// CPU thread-contract test links a recording stand-in of the C ABI) still link; PDFMatching::available() then says false and
+// ThreadLocalize falls back to ICP with a warning.
+#pragma weak tsd_pdf_match
 #include <cstdlib>
 #include <ctime>
 
@@ -581,20 +586,26 @@ TSD_PDFMatching::TSD_PDFMatching(TsdGrid& grid, unsigned int trials, double epsT
   std::memset(&_last, 0, sizeof(_last));
 }
 
-void TSD_PDFMatching::drawStreams(unsigned int points, std::vector<int>& dSub, std::vector<int>& dCtrl, std::vector<int>& dTrials)
+void drawRandomMatchingStreams(long seed, unsigned long& calls, unsigned int points, unsigned int sizeControlSet, unsigned int trials,
+                               std::vector<int>& dSub, std::vector<int>& dCtrl, std::vector<int>& dTrials)
 {
   // the three rand() streams, in the reference's call order.  (Seeded -- tests only --: srand + the draws as ONE step under a process-
   // wide lock, so that several robots' localiser threads each get their own reproducible sequence; unseeded it is the reference's
   // plain rand(), whose interleaving between threads is as unspecified as in the reference.)
   static std::mutex seededDraws;
   std::unique_lock<std::mutex> lk(seededDraws, std::defer_lock);
-  if (_seed >= 0) { lk.lock(); std::srand((unsigned)(_seed + (long)_calls)); }
-  _calls++;
-  dSub.assign(points, 0); dCtrl.assign(_sizeControlSet > 0 ? _sizeControlSet : 1, 0); dTrials.assign(_trials > 0 ? _trials : 1, 0);
+  if (seed >= 0) { lk.lock(); std::srand((unsigned)(seed + (long)calls)); }
+  calls++;
+  dSub.assign(points, 0); dCtrl.assign(sizeControlSet > 0 ? sizeControlSet : 1, 0); dTrials.assign(trials > 0 ? trials : 1, 0);
   for (auto& v : dSub) v = std::rand();                      // RandomMatching::subsampleMask (RandomMatching.cpp:183)
   for (auto& v : dCtrl) v = std::rand();                     // RandomMatching::pickControlSet (:65)
-  if (_seed < 0) std::srand((unsigned)time(NULL));           // TSD_PDFMatching.cpp:184
-  for (auto& v : dTrials) v = std::rand();                   // TSD_PDFMatching.cpp:190
+  if (seed < 0) std::srand((unsigned)time(NULL));            // TSD_PDFMatching.cpp:184, PDFMatching.cpp:173
+  for (auto& v : dTrials) v = std::rand();                   // TSD_PDFMatching.cpp:190, PDFMatching.cpp:215
+}
+
+void TSD_PDFMatching::drawStreams(unsigned int points, std::vector<int>& dSub, std::vector<int>& dCtrl, std::vector<int>& dTrials)
+{
+  drawRandomMatchingStreams(_seed, _calls, points, _sizeControlSet, _trials, dSub, dCtrl, dTrials);
 }
 
 tsd_tsdpdf_params TSD_PDFMatching::params(double phiMax, double resolution) const
@@ -624,6 +635,56 @@ Matrix TSD_PDFMatching::match(Matrix TSensor, const double* M, const bool* maskM
   }
   if (rc != TSD_OK) {
     std::fprintf(stderr, "TSD_PDFMatching::match failed (%d): %s\n", rc, tsd_last_error(_grid.context()));
+    return TBest;
+  }
+  TBest.setData(_last.T);
+  return TBest;
+}
+
+// --------------------------------------------------------------------------------------- PDFMatching
+PDFMatching::PDFMatching(TsdGrid& grid, unsigned int trials, double epsThresh, unsigned int sizeControlSet, double zhit, double zphi,
+                         double zshort, double zmax, double zrand, double percentagePointsInC, double rangemax, double sigphi,
+                         double sighit, double lamshort, double maxAngleDiff, double maxAnglePenalty)
+    : _grid(grid), _seed(-1), _calls(0)
+{
+  std::memset(&_prm, 0, sizeof(_prm));
+  _prm.trials = (int)trials; _prm.size_control_set = (int)sizeControlSet; _prm.eps_thresh = epsThresh;
+  _prm.zhit = zhit; _prm.zphi = zphi; _prm.zshort = zshort; _prm.zmax = zmax; _prm.zrand = zrand;
+  _prm.percentage_points_in_c = percentagePointsInC; _prm.rangemax = rangemax; _prm.sigphi = sigphi; _prm.sighit = sighit;
+  _prm.lamshort = lamshort; _prm.max_angle_diff = maxAngleDiff; _prm.max_angle_penalty = maxAnglePenalty;
+  std::memset(&_last, 0, sizeof(_last));
+}
+
+bool PDFMatching::available()
+{
+  return tsd_pdf_match != nullptr;
+}
+
+tsd_pdfmatch_params PDFMatching::params(double phiMax, double resolution) const
+{
+  tsd_pdfmatch_params prm = _prm;
+  prm.phi_max = phiMax; prm.ang_res = resolution;
+  return prm;
+}
+
+Matrix PDFMatching::match(const double* M, const bool* maskM, const double* /*NM*/, const double* S, const bool* maskS,
+                          unsigned int points, double phiMax, const double /*transMax*/, const double resolution)
+{
+  Matrix TBest(3, 3);
+  TBest.setIdentity();
+  std::memset(&_last, 0, sizeof(_last));
+  if (!available()) return TBest;
+  std::vector<int> dSub, dCtrl, dTrials;
+  drawRandomMatchingStreams(_seed, _calls, points, (unsigned)_prm.size_control_set, (unsigned)_prm.trials, dSub, dCtrl, dTrials);
+  const tsd_pdfmatch_params prm = params(phiMax, resolution);
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(_grid.mutex());
+    rc = tsd_pdf_match(_grid.context(), M, reinterpret_cast<const uint8_t*>(maskM), S, reinterpret_cast<const uint8_t*>(maskS),
+                       (int)points, &prm, dSub.data(), dCtrl.data(), dTrials.data(), &_last);
+  }
+  if (rc != TSD_OK) {
+    std::fprintf(stderr, "PDFMatching::match failed (%d): %s\n", rc, tsd_last_error(_grid.context()));
     return TBest;
   }
   TBest.setData(_last.T);

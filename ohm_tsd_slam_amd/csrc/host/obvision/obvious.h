@@ -250,4 +250,37 @@ private:
   tsd_tsdpdf_result _last;
 };
 
+/** the three rand() streams of one RandomMatching-based match() call, in the reference's call order (RandomMatching.cpp:183,
+ *  :65; TSD_PDFMatching.cpp:184-190 = PDFMatching.cpp:173-215).  seed >= 0 (tests): srand(seed + calls) first; `calls` counts. */
+void drawRandomMatchingStreams(long seed, unsigned long& calls, unsigned int points, unsigned int sizeControlSet, unsigned int trials,
+                               std::vector<int>& dSub, std::vector<int>& dCtrl, std::vector<int>& dTrials);
+
+// obvious::PDFMatching (registration/ransacMatching/PDFMatching.{h,cpp}) on obvious::RandomMatching: the pre-registration of
+// registration_mode 2.  The reference constructor's 15 arguments behind the grid whose device runs it; match() as the reference's
+// plus the number of points.  The front end is TSD_PDFMatching's, the scoring runs on the device (tsd_pdf_match), the rand()
+// streams are drawn here exactly as TSD_PDFMatching draws them.
+class PDFMatching
+{
+public:
+  PDFMatching(TsdGrid& grid, unsigned int trials, double epsThresh, unsigned int sizeControlSet, double zhit, double zphi,
+              double zshort, double zmax, double zrand, double percentagePointsInC, double rangemax, double sigphi, double sighit,
+              double lamshort, double maxAngleDiff, double maxAnglePenalty);
+  virtual ~PDFMatching() {}
+  /** whether the device library provides tsd_pdf_match (a host build linked against a library without it has none) */
+  static bool available();
+  Matrix match(const double* M, const bool* maskM, const double* NM, const double* S, const bool* maskS, unsigned int points,
+               double phiMax = M_PI / 4.0, const double transMax = 1.5, const double resolution = 0.0);
+  /** addition (tests): as TSD_PDFMatching::setSeed */
+  void setSeed(long seed) { _seed = seed; }
+  const tsd_tsdpdf_result& lastResult() const { return _last; }
+  /** the parameters of match() as the C ABI takes them */
+  tsd_pdfmatch_params params(double phiMax, double resolution) const;
+private:
+  TsdGrid& _grid;
+  tsd_pdfmatch_params _prm;
+  long _seed;
+  unsigned long _calls;
+  tsd_tsdpdf_result _last;
+};
+
 }  // namespace obvious

@@ -243,6 +243,9 @@ struct tsd_ctx {
 
   // TSD_PDF pre-registration (tsdpdf.hip): one device + one pinned staging buffer, grown on demand
   char* d_pdf = nullptr; char* h_pdf = nullptr; size_t pdf_bytes = 0;
+  // registration_mode 2 (pdfmatch.hip): where the last tsd_pdf_match left its per-candidate values in d_pdf (tsd_debug_pdf_match_scores);
+  // any later pre-registration call on this context reuses the buffer and clears the count
+  int pdfm_dbg_n = 0; size_t pdfm_dbg_off_u = 0, pdfm_dbg_off_fov = 0;
 
   // occupancy
   int8_t* d_occ = nullptr;       // persistent map (ThreadGrid::_occGridContent)

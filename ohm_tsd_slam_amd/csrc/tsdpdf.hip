@@ -36,6 +36,7 @@
 #include <mutex>
 #include <vector>
 #include "tsdpdf_device.hpp"
+#include "pdf_front.hpp"
 
 namespace tsd {
 
@@ -178,6 +179,11 @@ k_pdf_argmax(const double* __restrict__ prob, const PdfCandidate* __restrict__ c
              PdfHeader* __restrict__ host_hdr, PdfResult* __restrict__ host_res)
 {
   pdf_argmax_body(prob, cand, n_cand, M, S, out, hdr, host_hdr, host_res);
+}
+void launch_pdf_argmax(hipStream_t stream, const double* prob, const PdfCandidate* cand, int n_cand, const double* M, const double* S,
+                       PdfResult* out)
+{
+  hipLaunchKernelGGL(k_pdf_argmax, dim3(1), dim3(1024), 0, stream, prob, cand, n_cand, M, S, out, nullptr, nullptr, nullptr);
 }
 struct PdfArgmaxBatch { PdfArgmaxEntry e[PDF_BATCH_BYVAL]; };
 __global__ void __launch_bounds__(1024)
@@ -692,33 +698,18 @@ static void calc_normals(const double* M, int points, std::vector<double>& N, co
   }
 }
 
-}  // namespace tsd
-
-using namespace tsd;
-
-extern "C" int tsd_tsdpdf_match(tsd_ctx* ctx, const double pose33[9], const double* model_xy_2B, const uint8_t* mask_m,
-                                const double* scene_xy_2B, const uint8_t* mask_s, int beams, const tsd_tsdpdf_params* prm,
-                                const int* draws_subsample, const int* draws_control, const int* draws_trials,
-                                tsd_tsdpdf_result* result)
+int pdf_front_end(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m, const double* scene_xy_2B, const uint8_t* mask_s,
+                  int beams, int trials_cfg, int size_control_set, double phi_max_in, double ang_res, const int* draws_subsample,
+                  const int* draws_control, const int* draws_trials, PdfExtraBytes extra, PdfLap& lap, tsd_tsdpdf_result* result,
+                  PdfFrontEnd& fe, bool host_normals_call)
 {
-  if (!ctx || !pose33 || !model_xy_2B || !mask_m || !scene_xy_2B || !mask_s || !prm || !draws_subsample || !draws_control ||
-      !draws_trials || !result)
-    return TSD_E_ARG;
-  if (beams < 1 || beams > TSD_MAX_BEAMS || prm->size_control_set < 0 || prm->size_control_set > PDF_MAX_CONTROL || prm->trials < 0)
-    return set_error(ctx, TSD_E_CAPACITY, "tsd_tsdpdf_match: beams / control set out of range", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;     // (the scoring reads the grid: behind a push still on the push stream)
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // TSD_MODE3_TIMING=1: the host phases of this call (printed every 100 calls)
-  static const bool timing = std::getenv("TSD_MODE3_TIMING") != nullptr;
-  static double t_acc[6]; static int t_calls;
-  auto t_last = std::chrono::steady_clock::now();
-  auto lap = [&](int i) { if (!timing) return; const auto now = std::chrono::steady_clock::now(); t_acc[i] += std::chrono::duration<double, std::micro>(now - t_last).count(); t_last = now; };
   const int n = beams;
   const int SR = 10 / 2;                                   // _pcaSearchRange / 2 (TSD_PDFMatching.cpp:18)
   for (int i = 0; i < 9; i++) result->T[i] = (i % 4 == 0) ? 1.0 : 0.0;     // TBest.setIdentity()
   result->probability = 0.0; result->idx_model = -1; result->idx_scene = -1; result->candidates = 0;
   result->valid_model = 0; result->valid_scene = 0; result->control_points = 0; result->reserved = 0;
+  fe.n = n; fe.stage = PdfFrontEnd::FEW_POINTS;
+  ctx->pdfm_dbg_n = 0;                                     // (tsd_debug_pdf_match_scores: the buffer is about to be reused)
   if (n < 3) return TSD_OK;                                // "Model and scene contain too less points" (:53-57)
   const double* M = model_xy_2B; const double* S = scene_xy_2B;
 
@@ -734,19 +725,23 @@ extern "C" int tsd_tsdpdf_match(tsd_ctx* ctx, const double pose33[9], const doub
     const int thresh = (int)(1000.0 - probability * 1000.0 + 0.5);
     for (int i = 0; i < n; i++) if ((draws_subsample[i] % 1000) < thresh) mSp[i] = 0;
   }
-  const bool res_ok = prm->ang_res > 1e-6;                 // (reported where the reference does, behind the point-count exits: :171-175)
-  const double phi_max = std::min(prm->phi_max, M_PI * 0.5);
-  int span = res_ok ? (int)std::floor(phi_max / prm->ang_res) : n;
+  const bool res_ok = ang_res > 1e-6;                      // (reported where the reference does, behind the point-count exits: :171-175)
+  const double phi_max = std::min(phi_max_in, M_PI * 0.5);
+  int span = res_ok ? (int)std::floor(phi_max / ang_res) : n;
   if (span > n) span = n;
-  // device buffer: [M | S | mask_in M, S | mask_io M, S | phi M, S | control | candidates | pose | prob | result]; the candidate
-  // list is sized for its upper bound (trials x (2 span) scene points) because the normals come back before it is known
-  const size_t max_cand = (size_t)std::max(prm->trials, 0) * (size_t)std::min(2 * span + 1, n) + 1;
+  fe.phi_max = phi_max; fe.span = span;
+  // device buffer: [M | S | mask_in M, S | mask_io M, S | phi M, S | control | candidates | pose | prob | result | extra]; the
+  // candidate list is sized for its upper bound (trials x (2 span) scene points) because the normals come back before it is known
+  const size_t max_cand = (size_t)std::max(trials_cfg, 0) * (size_t)std::min(2 * span + 1, n) + 1;
   const size_t bM = (size_t)n * 16, bMask = ((size_t)n + 15) & ~(size_t)15, bPhi = (size_t)n * 8;
-  const size_t bC = (size_t)std::max(prm->size_control_set, 1) * 16, bK = max_cand * sizeof(PdfCandidate), bP = 80;
+  const size_t bC = (size_t)std::max(size_control_set, 1) * 16, bK = max_cand * sizeof(PdfCandidate), bP = 80;
   const size_t off_S = bM, off_mi = 2 * bM, off_mo = off_mi + 2 * bMask, off_phi = off_mo + 2 * bMask;
   const size_t off_C = off_phi + 2 * bPhi, off_K = off_C + bC, off_P = off_K + ((bK + 15) & ~(size_t)15);
   const size_t off_prob = off_P + bP, off_res = off_prob + max_cand * sizeof(double);
-  const size_t total = off_res + sizeof(PdfResult);
+  const size_t off_extra = (off_res + sizeof(PdfResult) + 15) & ~(size_t)15;
+  const size_t total = extra ? off_extra + extra(n, max_cand) : off_res + sizeof(PdfResult);
+  fe.max_cand = max_cand; fe.bC = bC;
+  fe.off_S = off_S; fe.off_C = off_C; fe.off_K = off_K; fe.off_P = off_P; fe.off_prob = off_prob; fe.off_res = off_res; fe.off_extra = off_extra;
   if (total > ctx->pdf_bytes) {
     TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->d_pdf) hipFree(ctx->d_pdf);
@@ -759,9 +754,10 @@ extern "C" int tsd_tsdpdf_match(tsd_ctx* ctx, const double pose33[9], const doub
   }
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));          // (the pinned buffer of a previous call is free)
   char* h = ctx->h_pdf; char* d = ctx->d_pdf;
-  static const bool host_normals = std::getenv("TSD_PDF_HOST_NORMALS") != nullptr;     // A/B and cross-check: the host restatement
+  fe.h = h; fe.d = d;
+  static const bool host_normals_env = std::getenv("TSD_PDF_HOST_NORMALS") != nullptr;     // A/B and cross-check: the host restatement
   std::memcpy(h, M, bM); std::memcpy(h + off_S, S, bM);
-  if (host_normals) {
+  if (host_normals_env || host_normals_call) {
     std::vector<double> NM(2 * (size_t)n, 0.0), NS(2 * (size_t)n, 0.0);
     calc_normals(M, n, NM, mask_m, mMp, SR);
     for (int i = 0; i < n; i++) phiM[i] = mMp[i] ? std::atan2(NM[2 * i + 1], NM[2 * i]) : -1e6;     // calcPhi (:155-174)
@@ -789,13 +785,15 @@ extern "C" int tsd_tsdpdf_match(tsd_ctx* ctx, const double pose33[9], const doub
     std::memcpy(phiM.data(), h + off_phi, bPhi); std::memcpy(phiS.data(), h + off_phi + bPhi, bPhi);
     lap(0);
   }
-  std::vector<int> idxM, idxS;
+  std::vector<int>& idxM = fe.idxM; std::vector<int>& idxS = fe.idxS;
+  idxM.clear(); idxS.clear();
   for (int i = SR; i < n - SR; i++) if (mMp[i]) idxM.push_back(i);                                // extractSamples (:41-50)
   for (int i = SR; i < n - SR; i++) if (mSp[i]) idxS.push_back(i);
   // ---- control set (:106-118, RandomMatching::pickControlSet :52-80)
-  int nC = prm->size_control_set;
+  int nC = size_control_set;
   if ((int)idxS.size() < nC) nC = (int)idxS.size();
-  std::vector<double> control(2 * (size_t)std::max(nC, 1));
+  std::vector<double>& control = fe.control;
+  control.assign(2 * (size_t)std::max(nC, 1), 0.0);
   {
     std::vector<int> tmp = idxS;
     for (int k = 0; k < nC; k++) {
@@ -805,14 +803,19 @@ extern "C" int tsd_tsdpdf_match(tsd_ctx* ctx, const double pose33[9], const doub
       control[2 * k] = S[2 * idx]; control[2 * k + 1] = S[2 * idx + 1];
     }
   }
+  fe.nC = nC;
   lap(1);
   result->valid_model = (int)idxM.size(); result->valid_scene = (int)idxS.size(); result->control_points = nC;
+  fe.stage = PdfFrontEnd::FEW_VALID;
   if (idxS.size() < 3 || idxM.size() < 3) return TSD_OK;   // "Too less valid points" (:129-139): identity
-  int trials = prm->trials;
+  int trials = trials_cfg;
   if ((int)idxM.size() < trials) trials = (int)idxM.size();
-  if (!res_ok) return set_error(ctx, TSD_E_ARG, "tsd_tsdpdf_match: resolution not properly set", hipSuccess);   // :171-175
+  fe.trials = trials;
+  fe.stage = PdfFrontEnd::NO_RESOLUTION;
+  if (!res_ok) return TSD_OK;                              // :171-175 (each mode reports it in its own way)
   // ---- candidates in the reference's serial order (:185-215)
-  std::vector<PdfCandidate> cand;
+  std::vector<PdfCandidate>& cand = fe.cand;
+  cand.clear();
   {
     std::vector<int> tmp = idxM;
     for (int trial = 0; trial < trials; trial++) {
@@ -830,36 +833,71 @@ extern "C" int tsd_tsdpdf_match(tsd_ctx* ctx, const double pose33[9], const doub
     }
   }
   result->candidates = (int)cand.size();
+  fe.stage = PdfFrontEnd::NO_CANDIDATES;
   if (cand.empty()) return TSD_OK;
-  if (cand.size() > max_cand) return set_error(ctx, TSD_E_CAPACITY, "tsd_tsdpdf_match: candidate bound", hipSuccess);
+  if (cand.size() > max_cand) return set_error(ctx, TSD_E_CAPACITY, "pdf_front_end: candidate bound", hipSuccess);
+  fe.stage = PdfFrontEnd::SCORE;
   lap(2);
+  return TSD_OK;
+}
+
+}  // namespace tsd
+
+using namespace tsd;
+
+extern "C" int tsd_tsdpdf_match(tsd_ctx* ctx, const double pose33[9], const double* model_xy_2B, const uint8_t* mask_m,
+                                const double* scene_xy_2B, const uint8_t* mask_s, int beams, const tsd_tsdpdf_params* prm,
+                                const int* draws_subsample, const int* draws_control, const int* draws_trials,
+                                tsd_tsdpdf_result* result)
+{
+  if (!ctx || !pose33 || !model_xy_2B || !mask_m || !scene_xy_2B || !mask_s || !prm || !draws_subsample || !draws_control ||
+      !draws_trials || !result)
+    return TSD_E_ARG;
+  if (beams < 1 || beams > TSD_MAX_BEAMS || prm->size_control_set < 0 || prm->size_control_set > PDF_MAX_CONTROL || prm->trials < 0)
+    return set_error(ctx, TSD_E_CAPACITY, "tsd_tsdpdf_match: beams / control set out of range", hipSuccess);
+  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (int rcd_ = drain_async_push(ctx)) return rcd_;     // (the scoring reads the grid: behind a push still on the push stream)
+  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  // TSD_MODE3_TIMING=1: the host phases of this call (printed every 100 calls)
+  static const bool timing = std::getenv("TSD_MODE3_TIMING") != nullptr;
+  static double t_acc[6]; static int t_calls;
+  PdfLap lap; lap.on = timing; lap.acc = t_acc;
+  PdfFrontEnd fe;
+  if (int rc = pdf_front_end(ctx, model_xy_2B, mask_m, scene_xy_2B, mask_s, beams, prm->trials, prm->size_control_set, prm->phi_max,
+                             prm->ang_res, draws_subsample, draws_control, draws_trials, nullptr, lap, result, fe))
+    return rc;
+  if (fe.stage == PdfFrontEnd::NO_RESOLUTION) return set_error(ctx, TSD_E_ARG, "tsd_tsdpdf_match: resolution not properly set", hipSuccess);   // :171-175
+  if (fe.stage != PdfFrontEnd::SCORE) return TSD_OK;
+  char* h = fe.h; char* d = fe.d;
+  const int nC = fe.nC;
+  const std::vector<PdfCandidate>& cand = fe.cand;
 
   // ---- device: score + arg-max
   const size_t bKu = cand.size() * sizeof(PdfCandidate);
-  std::memcpy(h + off_C, control.data(), (size_t)nC * 16);
-  std::memcpy(h + off_K, cand.data(), bKu); std::memcpy(h + off_P, pose33, 9 * sizeof(double));
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d + off_C, h + off_C, bC + bKu, hipMemcpyHostToDevice, ctx->stream));
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d + off_P, h + off_P, bP, hipMemcpyHostToDevice, ctx->stream));
+  std::memcpy(h + fe.off_C, fe.control.data(), (size_t)nC * 16);
+  std::memcpy(h + fe.off_K, cand.data(), bKu); std::memcpy(h + fe.off_P, pose33, 9 * sizeof(double));
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d + fe.off_C, h + fe.off_C, fe.bC + bKu, hipMemcpyHostToDevice, ctx->stream));
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d + fe.off_P, h + fe.off_P, 80, hipMemcpyHostToDevice, ctx->stream));
   lap(3);
   {
     ScopedKernelTimer t(ctx, "tsdpdf", true);
     const int nc = (int)cand.size();
-    hipLaunchKernelGGL(k_pdf_score, dim3((nc + PDF_WAVES - 1) / PDF_WAVES), dim3(64 * PDF_WAVES), 0, ctx->stream, ctx->grid, reinterpret_cast<const double*>(d + off_P),
-                       reinterpret_cast<const double*>(d), reinterpret_cast<const double*>(d + off_S),
-                       reinterpret_cast<const double2*>(d + off_C), nC, reinterpret_cast<const PdfCandidate*>(d + off_K), nc,
-                       prm->zrand, reinterpret_cast<double*>(d + off_prob), nullptr, nc, nC > 0 ? nC : 1);
-    hipLaunchKernelGGL(k_pdf_argmax, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const double*>(d + off_prob),
-                       reinterpret_cast<const PdfCandidate*>(d + off_K), nc, reinterpret_cast<const double*>(d),
-                       reinterpret_cast<const double*>(d + off_S), reinterpret_cast<PdfResult*>(d + off_res), nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(k_pdf_score, dim3((nc + PDF_WAVES - 1) / PDF_WAVES), dim3(64 * PDF_WAVES), 0, ctx->stream, ctx->grid, reinterpret_cast<const double*>(d + fe.off_P),
+                       reinterpret_cast<const double*>(d), reinterpret_cast<const double*>(d + fe.off_S),
+                       reinterpret_cast<const double2*>(d + fe.off_C), nC, reinterpret_cast<const PdfCandidate*>(d + fe.off_K), nc,
+                       prm->zrand, reinterpret_cast<double*>(d + fe.off_prob), nullptr, nc, nC > 0 ? nC : 1);
+    hipLaunchKernelGGL(k_pdf_argmax, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const double*>(d + fe.off_prob),
+                       reinterpret_cast<const PdfCandidate*>(d + fe.off_K), nc, reinterpret_cast<const double*>(d),
+                       reinterpret_cast<const double*>(d + fe.off_S), reinterpret_cast<PdfResult*>(d + fe.off_res), nullptr, nullptr, nullptr);
   }
   TSD_HIP_CHECK(ctx, hipGetLastError());
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(h + off_res, d + off_res, sizeof(PdfResult), hipMemcpyDeviceToHost, ctx->stream));
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(h + fe.off_res, d + fe.off_res, sizeof(PdfResult), hipMemcpyDeviceToHost, ctx->stream));
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   lap(4);
   if (timing && ++t_calls % 100 == 0)
     std::fprintf(stderr, "tsd_tsdpdf_match, us per call: normals of both sets (%s) %.1f | lists + control set %.1f | candidates (%d) %.1f | staging + H2D issue %.1f | kernels + D2H %.1f\n",
-                 host_normals ? "host" : "device", t_acc[0] / t_calls, t_acc[1] / t_calls, (int)cand.size(), t_acc[2] / t_calls, t_acc[3] / t_calls, t_acc[4] / t_calls);
-  const PdfResult* r = reinterpret_cast<const PdfResult*>(h + off_res);
+                 std::getenv("TSD_PDF_HOST_NORMALS") ? "host" : "device", t_acc[0] / t_calls, t_acc[1] / t_calls, (int)cand.size(), t_acc[2] / t_calls, t_acc[3] / t_calls, t_acc[4] / t_calls);
+  const PdfResult* r = reinterpret_cast<const PdfResult*>(h + fe.off_res);
   std::memcpy(result->T, r->T, sizeof(r->T));
   result->probability = r->prob; result->idx_model = r->idx; result->idx_scene = r->i;
   return TSD_OK;

@@ -33,6 +33,7 @@ HOST_ABI = {
     "tsd_node_processed": (C.c_ulonglong, [C.c_void_p, C.c_int]),
     "tsd_node_report": (None, [C.c_void_p, C.c_int, _dp]),
     "tsd_node_pose_msg": (None, [C.c_void_p, C.c_int, _dp]),
+    "tsd_node_preregistration": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "tsd_node_pose_topic": (C.c_char_p, [C.c_void_p, C.c_int]),
     "tsd_node_tf_msg": (None, [C.c_void_p, C.c_int, _dp, C.c_char_p, C.c_int]),
     "tsd_node_set_transform": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, _dp, _dp]),
@@ -188,6 +189,14 @@ class SlamNode:
             out[k] = int(buf[19 + i])
         out["stamp_ns"] = int(buf[28])
         return out
+
+    def preregistration(self, robot: int = 0) -> dict | None:
+        """the robot's last pre-registration (registration_mode 2; mode 3 where it ran unfused), None if there was none"""
+        buf = np.zeros(16)
+        if not self.lib.tsd_node_preregistration(self.h, robot, buf.ctypes.data_as(_dp)):
+            return None
+        return dict(T=buf[:9].reshape(3, 3).copy(), prob=float(buf[9]), idx=int(buf[10]), i=int(buf[11]), candidates=int(buf[12]),
+                    valid_model=int(buf[13]), valid_scene=int(buf[14]), control=int(buf[15]))
 
     def pose_msg(self, robot: int = 0) -> dict:
         buf = np.zeros(8)

@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""registration_mode 2 (PDFMatching pre-registration + ICP) through the C++ façade at cfg 2 with a fixed seed: scans per second of
+the synchronous node, the pre-registration's phases in us per match (tsd_pdf_match's own timing, TSD_MODE2_TIMING: normals, host
+lists, staging, and the device's model arrays / scoring / arg-max by HIP events) and, for comparison, the plain-C restatement of
+PDFMatching::match (tests/pdfmatch_restate.c, one thread) in ms per match on the same inputs.
+
+    python tools/mode2_rate.py [--scans N] [--warmup W]
+"""
+import argparse
+import math
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+os.environ.setdefault("TSD_MODE2_TIMING", "1")        # (read once, at the first tsd_pdf_match)
+
+import numpy as np  # noqa: E402
+
+from ohm_tsd_slam_amd import capi, facade, synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scans", type=int, default=400)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--seed", type=int, default=4711)
+    a = ap.parse_args()
+    gc, geo, scene = synth.CONFIGS["cfg2"]
+    world = synth.World(scene, gc)
+    n = a.warmup + a.scans
+    scans = synth.scans_for(world, geo, synth.trajectory(world, n))
+    params = facade.node_params(gc, geo)
+    params.update({"registration_mode": 2, "tsdpdf_seed": a.seed})
+    node = facade.SlamNode(params, synchronous=True)
+    for k in range(a.warmup):
+        node.laser(scans[k], geo.angle_min, geo.angle_increment)
+    sys.stderr.flush()
+    t0 = time.perf_counter()
+    for k in range(a.warmup, n):
+        node.laser(scans[k], geo.angle_min, geo.angle_increment)
+    dt = time.perf_counter() - t0
+    sys.stderr.flush()
+    pr = node.preregistration()
+    rep = node.report()
+    e = math.hypot(rep["pose"][0, 2] - synth.trajectory(world, n)[-1, 0], rep["pose"][1, 2] - synth.trajectory(world, n)[-1, 1])
+    print(f"mode 2, cfg 2 ({geo.beams} beams), {a.scans} scans after {a.warmup}: {a.scans / dt:.0f} scans/s ({1e6 * dt / a.scans:.1f} us per scan), "
+          f"last pre-registration: {pr['candidates']} candidates, {pr['control']} control points, {pr['valid_model']} model points; "
+          f"tracking error {e:.4f} m", flush=True)
+    # the restatement, single-threaded, on the last scan's inputs as the facade's ray cast gives them
+    from tests import pdfmatch_ref as R
+    from tests import helpers as H
+    from oracle import pyoracle as O
+    O.build()
+    with tempfile.TemporaryDirectory() as tmp:
+        rs = R.Restatement(R.build(tmp))
+        g = node.grid()
+        pose = rep["pose"]
+        rl, rw = H.world_rays(O, geo, pose, gc.cell_size)
+        co, no, mo, cnt = g.raycast(pose, rw, H.MIN_RANGE, H.MAX_RANGE)
+        data, mask = O.ingest_f32(scans[-1], H.MAX_RANGE, geo.angle_increment)
+        sc, ms, _ = O.scene_from_scan(rl, data, mask)
+        rng = np.random.default_rng(a.seed)
+        ds, dc, dt_ = (rng.integers(0, 2 ** 31 - 1, k) for k in (geo.beams, 140, 100))
+        phi = 30.0 * math.pi / 180.0
+        reps = 5
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            rr = rs.match(co, mo, sc, ms, phi, geo.angle_increment, ds, dc, dt_)
+        tr = (time.perf_counter() - t0) / reps
+        dg = capi.TsdGridDevice(9, 0.05, 0.15)
+        for _ in range(3):
+            rh = dg.pdf_match(co, mo, sc, ms, phi, geo.angle_increment, ds, dc, dt_)
+        t0 = time.perf_counter()
+        for _ in range(50):
+            rh = dg.pdf_match(co, mo, sc, ms, phi, geo.angle_increment, ds, dc, dt_)
+        th = (time.perf_counter() - t0) / 50
+        same = (rh["candidates"], rh["idx"], rh["i"]) == (rr["candidates"], rr["idx"], rr["i"])
+        print(f"one match on the last scan's inputs ({rr['candidates']} candidates): restatement {1e3 * tr:.1f} ms (one CPU thread), "
+              f"tsd_pdf_match {1e6 * th:.1f} us end to end; same winner: {same}", flush=True)
+        dg.close()
+    node.close()
+
+
+if __name__ == "__main__":
+    main()
