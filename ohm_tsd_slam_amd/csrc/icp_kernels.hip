@@ -1651,16 +1651,7 @@ static int launch_icp_shape_est(tsd_ctx* ctx, const IcpArgs& a, int n, int cap, 
   const bool ptl = a.estimator == TSD_ESTIMATOR_POINT_TO_LINE;
   const size_t lds = icp_lds_bytes_for(cap, T, ptl) + ICP_TL_BYTES;
   if (lds > 160u * 1024u) return set_error(ctx, TSD_E_CAPACITY, "registration does not fit the LDS of one CU (point-to-line: model normals too)", hipSuccess);
-  {
-    // the attribute is per device: remembered per context (and kernel instantiation), not per process
-    std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
-    size_t& configured = ctx->lds_configured[reinterpret_cast<const void*>(k_icp<R, MAXT, PTL>)];
-    if (lds > configured) {
-      TSD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_icp<R, MAXT, PTL>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured = lds;
-    }
-  }
+  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp<R, MAXT, PTL>), lds)) return rc;
   ScopedKernelTimer t(ctx, "icp");
   const LaunchTarget* tg = launch_target();       // concurrent multi-robot path: the sensor's own stream and buffers
   // the per-iteration record (tsd_icp_trace) is kept by tsd_icp / tsd_localize; the fused scan has no reader for it and skips
@@ -1679,14 +1670,7 @@ static int launch_icp_shape_est(tsd_ctx* ctx, const IcpArgs& a, int n, int cap, 
   if (pre) {
     // fused registration_mode 3, the node's shape (icp_pre_supported): the arg-max rides as the launch's first workgroup
     if (!(R == 3 && MAXT == 512 && !PTL && cap == 1088 && T == 512) || !post.st) return set_error(ctx, TSD_E_ARG, "launch_icp: the arg-max can only ride with the node's registration shape", hipSuccess);
-    {
-      std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
-      size_t& configured = ctx->lds_configured[reinterpret_cast<const void*>(k_icp_pre<3, 512, 1088, 512>)];
-      if (lds > configured) {
-        TSD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_icp_pre<3, 512, 1088, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured = lds;
-      }
-    }
+    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp_pre<3, 512, 1088, 512>), lds)) return rc;
     // (the launch's own completion is the event a pre-registration armed AHEAD waits for before it overwrites the inputs; a timed
     // dispatch needs its stop event for the timer: a marker behind it then)
     hipEvent_t stop = t.b ? t.b : pre->done;
@@ -1699,14 +1683,7 @@ static int launch_icp_shape_est(tsd_ctx* ctx, const IcpArgs& a, int n, int cap, 
     return TSD_OK;
   }
   if (R == 3 && MAXT == 512 && !PTL && cap == 1088 && T == 512) {
-    {
-      std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
-      size_t& configured = ctx->lds_configured[reinterpret_cast<const void*>(k_icp<3, 512, false, 1088, 512>)];
-      if (lds > configured) {
-        TSD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_icp<3, 512, false, 1088, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured = lds;
-      }
-    }
+    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp<3, 512, false, 1088, 512>), lds)) return rc;
     hipExtLaunchKernelGGL((k_icp<3, 512, false, 1088, 512>), dim3(1 + sa.helpers), dim3(T), lds, launch_stream(ctx), t.a, t.b, 0, a, P_dev, cap, ctx->d_model, ctx->d_scene,
                      ctx->d_morig, ctx->d_start, tg && tg->coords ? tg->coords : ctx->d_coords, tg && tg->mask_m ? tg->mask_m : ctx->d_mask_m,
                      d_rays_local ? d_rays_local : ctx->d_rays_local, d_ranges ? d_ranges : ctx->d_ranges,
@@ -1769,14 +1746,7 @@ static int launch_icp_pairs_shape(tsd_ctx* ctx, const IcpArgs& a, int n, int cap
   if (T > MAXT) return set_error(ctx, TSD_E_CAPACITY, "icp workgroup shape", hipSuccess);
   const size_t lds = icp_lds_bytes_for(cap, T, false);
   if (lds > 160u * 1024u) return set_error(ctx, TSD_E_CAPACITY, "registration does not fit the LDS of one CU", hipSuccess);
-  {
-    std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
-    size_t& configured = ctx->lds_configured[reinterpret_cast<const void*>(k_icp_pairs<R, MAXT>)];
-    if (lds > configured) {
-      TSD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_icp_pairs<R, MAXT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured = lds;
-    }
-  }
+  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp_pairs<R, MAXT>), lds)) return rc;
   hipLaunchKernelGGL((k_icp_pairs<R, MAXT>), dim3(1), dim3(T), lds, ctx->stream, a, cap, ctx->d_model, ctx->d_scene, ctx->d_morig, ctx->d_start,
                      ctx->d_icp_res, ctx->d_icp_trace, d_pairs);
   TSD_HIP_CHECK(ctx, hipGetLastError());
@@ -1801,26 +1771,10 @@ static int launch_icp_batch_shape(tsd_ctx* ctx, hipStream_t stream, const IcpBat
   if (T > MAXT) return set_error(ctx, TSD_E_CAPACITY, "icp workgroup shape", hipSuccess);
   const size_t lds = icp_lds_bytes_for(cap, T, PTL);
   if (lds > 160u * 1024u) return set_error(ctx, TSD_E_CAPACITY, "registration does not fit the LDS of one CU", hipSuccess);
-  {
-    std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
-    size_t& configured = ctx->lds_configured[reinterpret_cast<const void*>(k_icp_batch<R, MAXT, PTL>)];
-    if (lds > configured) {
-      TSD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_icp_batch<R, MAXT, PTL>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured = lds;
-    }
-  }
+  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp_batch<R, MAXT, PTL>), lds)) return rc;
   ScopedKernelTimer t(ctx, "icp");
   if (R == 3 && MAXT == 512 && !PTL && cap == 1088 && T == 512) {        // (the default scanner's shape: compile-time LDS layout, see launch_icp_shape_est)
-    {
-      std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
-      size_t& configured = ctx->lds_configured[reinterpret_cast<const void*>(k_icp_batch<3, 512, false, 1088, 512>)];
-      if (lds > configured) {
-        TSD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_icp_batch<3, 512, false, 1088, 512>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured = lds;
-      }
-    }
+    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp_batch<3, 512, false, 1088, 512>), lds)) return rc;
     hipExtLaunchKernelGGL((k_icp_batch<3, 512, false, 1088, 512>), dim3(n * (1 + helpers)), dim3(T), lds, stream, t.a, t.b, 0, d_entries, cap, n);
     TSD_HIP_CHECK(ctx, hipGetLastError());
     return TSD_OK;

@@ -1,6 +1,8 @@
 // push_device.hpp -- what the push kernels share (push_kernels.hip: one scan into the grid; push_multi.hip: the scans of a batch of robots
 // into the grid in one pass per tile): the per-tile records, the range-query tables' layout, tile geometry, the correctly rounded
-// square root / quotient, addTsd, the work-list constants and records, and the fp32 beam estimate of the update kernels.
+// square root / quotient, addTsd, the work-list constants and records, isInRange of a tile and its update record, the phases of the
+// update kernels per cell (fp32 beam estimate, candidate test, compaction, fix-up, signed distance, increaseEmptiness) and the
+// launch window of a push.
 #pragma once
 #include "tsd_ctx.hpp"
 #include <climits>
@@ -338,6 +340,233 @@ __device__ __forceinline__ CellClass classify_cell(const TileA& t, float dxc, fl
   }
 }
 
+// ---- TsdGridComponent::isInRange (TsdGridComponent.cpp:43-124) of tile p by one lane QUAD (k_push_classify, k_mp_classify) -------------
+// Range cull, four corner back-projections (one per lane of the quad: `corner` = lane & 3), the two beam-range tests as O(1) table
+// look-ups.  The quad's four lanes return the same values.
+constexpr int ACT_NONE = 0, ACT_EMPTY = 1, ACT_UPDATE = 2;
+struct TileRange {
+  bool pass;            // the range cull let the tile through
+  int action;           // ACT_EMPTY: increaseEmptiness (isInRange then returns false); ACT_UPDATE: the scan updates the tile's cells
+  uint32_t win;         // beams the cells of the tile can project to: lo | hi << 16
+  uint32_t far_flag;    // LIST_FAR / LIST_INTERIOR of the tile's list entry
+  double pw;            // partition weight (ACT_UPDATE)
+  double cx, cy;        // the tile's centroid (ACT_UPDATE)
+  double2 bd0;          // direction of boundary jb0 = max(lo - 1, 0) of a far tile, 0 of a near one
+};
+__device__ __forceinline__ TileRange tile_in_range(const GridDev& g, const PushArgs& a, const RmqView& rv, int p, int corner)
+{
+  TileRange r;
+  r.pass = false; r.action = ACT_NONE; r.win = (uint32_t)(a.beams - 1) << 16; r.far_flag = 0u;
+  r.pw = 0.0; r.cx = 0.0; r.cy = 0.0; r.bd0 = make_double2(1.0, 0.0);
+  double e[4][2], cx, cy, rad;
+  tile_geometry(g, p, e, cx, cy, rad);
+  // euklideanDistance<obfloat>(pos, _centroid, 2) (mathbase.h:369-378)
+  double sqr = 0.0;
+  { const double t0 = a.trx - cx; sqr += t0 * t0; const double t1 = a.try_ - cy; sqr += t1 * t1; }
+  const double distance = sqrt(sqr);
+  const double closest = distance - rad - g.max_trunc;
+  const double farthest = distance + rad + g.max_trunc;
+  if (closest > a.max_range || farthest < a.min_range) return r;
+  r.pass = true;
+  bool all_vis = true, any_vis = false;
+  int lo = 0, hi = 0;
+  {
+    const int k = corner;
+    const double ex = (k & 1) ? e[1][0] : e[0][0], ey = (k & 2) ? e[2][1] : e[0][1];
+    int ik = backproject(a.Pi, ex, ey, a.phi_min, a.ang_res_inv, a.phi_lower, a.phi_upper);
+    if (ik == -1) { ik = a.beams - 1; all_vis = false; }
+    else if (ik == -2) { ik = 0; all_vis = false; }
+    else any_vis = true;
+    // minmaxArray<int> (mathbase.h:55-64) over the four corners = minimum and maximum over the quad's lanes
+    lo = ik; hi = ik;
+  }
+  // (the whole quad is here or nowhere: the range cull above depends on the tile only)
+#pragma unroll
+  for (int m = 1; m <= 2; m <<= 1) {
+    const int lo2 = __shfl_xor(lo, m, 64), hi2 = __shfl_xor(hi, m, 64);
+    const int av2 = __shfl_xor((int)all_vis, m, 64), an2 = __shfl_xor((int)any_vis, m, 64);
+    lo = lo2 < lo ? lo2 : lo; hi = hi2 > hi ? hi2 : hi;
+    all_vis = all_vis && av2 != 0; any_vis = any_vis || an2 != 0;
+  }
+  // (requested here, next to the table look-ups below, used when the record is written)
+  r.bd0 = rv.bdir[(distance > 3.0 * rad && lo > 1) ? lo - 1 : 0];
+  if (any_vis) {
+    const int len = hi - lo + 1;
+    const int k = 31 - __clz(len);                                         // floor(log2(len))
+    const unsigned short* tm = rv.tmax + (size_t)k * rv.Bp;
+    const unsigned short* tn = rv.tmin + (size_t)k * rv.Bp;
+    const int j2 = hi - (1 << k) + 1;
+    const unsigned short n0 = ld_pinned(&rv.inf[lo]), n1 = ld_pinned(&rv.inf[hi + 1]);     // (issued with the index look-ups, used last)
+    const unsigned short i0 = tm[lo], i1 = tm[j2], i2 = tn[lo], i3 = tn[j2];
+    const double amax = fmax(rv.A[i0], rv.A[i1]);
+    const double bmin = fmin(rv.Bv[i2], rv.Bv[i3]);
+    const bool has_inf = n1 != n0;
+    const bool visible = amax > closest;
+    const bool empty = (bmin > farthest) && (!has_inf || distance < a.low_refl);
+    if (visible) r.action = (all_vis && empty) ? ACT_EMPTY : ACT_UPDATE;
+  }
+  // The cell centres of a tile lie inside the quadrilateral of the four corner points; seen from a sensor
+  // well outside of it the extreme angles are those of corners, so every cell projects into [lo, hi]
+  // (corners outside the field of view were mapped to its ends above).
+  if (distance > 3.0 * rad) {
+    r.win = (uint32_t)lo | ((uint32_t)hi << 16); r.far_flag = LIST_FAR;
+    // angular diameter of a far tile < 2 asin(1/3) = 0.68 rad; a tile that straddles the cut of a full-circle sensor has its
+    // corner indices at both ends of the scan instead
+    if (all_vis && lo >= 1 && hi <= a.beams - 2 && (double)(hi - lo) <= 0.7 * a.ang_res_inv + 2.0) r.far_flag |= LIST_INTERIOR;
+  }
+  if (r.action == ACT_UPDATE) {
+    // partition weight (TsdGrid.cpp:239-243): ((maxRange - min(distance to the centroid, maxRange)) / maxRange)^2.
+    // `distance` above is that distance bit for bit ((a - b)^2 == (b - a)^2, 0.0 + x == x), so the per-tile
+    // square root and division are done once here instead of by every thread of the update workgroup.
+    double dc = distance;
+    if (dc > a.max_range) dc = a.max_range;
+    r.pw = (a.max_range - dc) / a.max_range;
+    r.pw *= r.pw;
+    r.cx = cx; r.cy = cy;
+  }
+  return r;
+}
+
+// The list record of an UPDATE tile (PushListAux) from its isInRange; `entry` is its list word, iw / flag what the update kernel takes
+// for the tile's _initWeight and flag word
+__device__ __forceinline__ PushListAuxBody make_update_record(const GridDev& g, const PushArgs& a, uint32_t entry, const TileRange& tr,
+                                                              double iw, uint32_t flag)
+{
+  PushListAuxBody x;
+  x.entry = entry; x.win = tr.win; x.pw = 0.01 * tr.pw;
+  // the linear forms of the update's phase A (see PushListAux): fp64 here, once per tile, instead of fp32 in every lane there
+  const double lcx = a.Pi[0] * tr.cx + a.Pi[1] * tr.cy + a.Pi[2], lcy = a.Pi[3] * tr.cx + a.Pi[4] * tr.cy + a.Pi[5];
+  const double axx = a.Pi[0] * g.cs, axy = a.Pi[1] * g.cs, ayx = a.Pi[3] * g.cs, ayy = a.Pi[4] * g.cs;
+  x.A = (float)(lcx * ayx - lcy * axx); x.B = (float)(lcx * ayy - lcy * axy);
+  x.C = (float)(lcx * axx + lcy * ayx); x.D = (float)(lcx * axy + lcy * ayy);
+  x.lc2 = (float)(lcx * lcx + lcy * lcy);
+  x.lcx = (float)lcx; x.lcy = (float)lcy;
+  x.th_c = atan2_estimate(x.lcy, x.lcx);
+  x.iw = iw; x.flag = flag;
+  x.jb0 = (tr.win & 0xFFFFu) > 0u ? (tr.win & 0xFFFFu) - 1u : 0u;
+  x.bd = tr.bd0;
+  return x;
+}
+
+// ---- phase A of the update kernels (k_push_update, k_mp_update) for the UPD_CPT cells of a thread: cell k = (ix, iy0 + 8 k) of the
+// tile, c0 + UPDATE_BLOCK k in the tile's storage, offset (dxc, iy0 + 8 k - 16) cells from its centroid
+struct CellsA {
+  int idx[UPD_CPT];                               // beam (or boundary, undecided cells)
+  float d2f[UPD_CPT];                             // fp32 squared sensor distance
+  float lim[UPD_CPT];                             // the limit of its beam (cell_limits)
+  bool uns[UPD_CPT], in[UPD_CPT], cand[UPD_CPT];  // undecided / decided inside the field of view / candidate (lane masks)
+};
+// the beam classification of the cells from the tile's record x
+__device__ __forceinline__ void classify_cells(TileA ta, const PushListAuxBody& x, float dxc, unsigned iy0, CellsA& c)
+{
+  ta.A = x.A; ta.B = x.B; ta.C = x.C; ta.D = x.D; ta.lc2 = x.lc2; ta.th_c = x.th_c; ta.lcx = x.lcx; ta.lcy = x.lcy;
+  const bool far = (x.entry & LIST_FAR) != 0u;
+  const bool interior = (x.entry & LIST_INTERIOR) != 0u;
+  const float pA = dxc * ta.A, pC = fmaf(dxc, ta.C, ta.lc2), qx = fmaf(ta.cs2 * dxc, dxc, -ta.lc2);
+  const float vc = fmaf(ta.th_c - ta.phi_min, ta.inv_res, 0.5f);
+#pragma unroll
+  for (int k = 0; k < UPD_CPT; k++) {
+    const float dyc = (float)(iy0 + 8u * (unsigned)k) - 16.0f;
+    CellClass cc;
+    if (interior) cc = classify_cell<true, true>(ta, dxc, dyc, pA, pC, qx, vc, c.d2f[k]);
+    else if (far) cc = classify_cell<true, false>(ta, dxc, dyc, pA, pC, qx, vc, c.d2f[k]);
+    else          cc = classify_cell<false, false>(ta, dxc, dyc, pA, pC, qx, vc, c.d2f[k]);
+    c.idx[k] = cc.j; c.uns[k] = cc.uns; c.in[k] = !cc.uns && !cc.out;
+  }
+}
+// The beams' limits from LDS (lim[j] = beam_limit of beam j, ta.wlo <= j <= ta.whi), the four reads in flight together.  A decided
+// beam outside the staged window -- possible only through rounding at the window's ends -- joins the undecided cells (boundary = the
+// beam: the exact test names it again, and that path reads any beam)
+__device__ __forceinline__ void cell_limits(const TileA& ta, const float* lim, CellsA& c)
+{
+#pragma unroll
+  for (int k = 0; k < UPD_CPT; k++) {
+    const int il = min(max(c.idx[k], ta.wlo), ta.whi);
+    c.lim[k] = lim[il];
+    if (c.in[k] && il != c.idx[k]) { c.in[k] = false; c.uns[k] = true; }
+  }
+}
+// the candidate test of cell k: decided inside the field of view and not beyond its beam's limit
+__device__ __forceinline__ bool is_candidate(const CellsA& c, int k) { return c.in[k] && !(c.d2f[k] > c.lim[k]); }
+// Compaction: ONE LDS atomic per wave on `cnt` (candidates | undecided << 32) for its cells of all four strips -- the candidates go to
+// the front of the tile's list, the undecided cells (cell | boundary << 10) to its back (list[UPD_CAND_MAX - 1 - u]); the fix-up and
+// the exact part settle those, densely, behind the barrier
+__device__ __forceinline__ void compact_cells(const CellsA& c, int c0, int lane, unsigned long long* cnt, uint32_t* list)
+{
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  unsigned long long bc[UPD_CPT], bu[UPD_CPT];
+  unsigned nc = 0u, nu = 0u;
+#pragma unroll
+  for (int k = 0; k < UPD_CPT; k++) { bc[k] = __ballot(c.cand[k]); bu[k] = __ballot(c.uns[k]); nc += (unsigned)__popcll(bc[k]); nu += (unsigned)__popcll(bu[k]); }
+  unsigned base = 0u, ub = 0u;
+  if (nc | nu) {
+    unsigned long long got = 0ull;
+    if (lane == 0) got = atomicAdd(cnt, (unsigned long long)nc | ((unsigned long long)nu << 32));
+    base = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)got);
+    ub = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(got >> 32));
+  }
+#pragma unroll
+  for (int k = 0; k < UPD_CPT; k++) {
+    const uint32_t e = (uint32_t)(c0 + UPDATE_BLOCK * k) | ((uint32_t)c.idx[k] << 10);
+    if (c.cand[k]) list[base + (unsigned)__popcll(bc[k] & lt)] = e;
+    if (bu[k] && c.uns[k]) list[(unsigned)(UPD_CAND_MAX - 1) - (ub + (unsigned)__popcll(bu[k] & lt))] = e;
+    base += (unsigned)__popcll(bc[k]); ub += (unsigned)__popcll(bu[k]);
+  }
+}
+
+// ---- fix-up of one undecided cell (centre (ccx, ccy), boundary jbq of phase A): the side of the boundary direction beta_jbq the cell's
+// fp64 sensor-frame vector lies on -- the sign of |l| sin(angle - beta) = bx ly - by lx, good to 1e-16 where the reference's own
+// rounding chain is good to 1e-15 -- names the reference's beam unless |sin| < 1e-11; those cells, and cells at the +-pi cut (jbq =
+// IDX_CUT), take the reference's formulation itself (backproject_cold).  The boundary's direction is the record's beta_jb0 (bd) turned
+// by (jbq - jb0) * res -- rot[] -- or, beyond that table, bdir[jbq].  index: the reference's beam, < 0 for none; l2 = |l|^2.
+struct UndecidedBeam { int index; bool cold; double l2; };
+__device__ __forceinline__ UndecidedBeam resolve_undecided(const PushArgs& a, const PushArgs* a_dev, unsigned jb0, double2 bd,
+                                                           const double2* rot, const double2* bdir, double ccx, double ccy, int jbq)
+{
+  // PoseInv * (x, y, 1)^T as SensorPolar2D::backProject forms it (dgemm order)
+  double lx = 0.0, ly = 0.0;
+  lx += a.Pi[0] * ccx; lx += a.Pi[1] * ccy; lx += a.Pi[2] * 1.0;
+  ly += a.Pi[3] * ccx; ly += a.Pi[4] * ccy; ly += a.Pi[5] * 1.0;
+  UndecidedBeam b;
+  b.index = -1;
+  b.cold = jbq == IDX_CUT;
+  b.l2 = lx * lx + ly * ly;
+  if (!b.cold) {
+    const int kr = jbq - (int)jb0;
+    double2 bj;
+    if (__builtin_expect(kr >= 0 && kr < ROT_N, 1)) { const double2 rc = rot[kr]; bj.x = bd.x * rc.x - bd.y * rc.y; bj.y = bd.y * rc.x + bd.x * rc.y; }
+    else bj = bdir[jbq];
+    const double cr = bj.x * ly - bj.y * lx;                  // |l| sin(angle - beta_jb)
+    if (cr * cr > 1e-22 * b.l2) {
+      // beyond the boundary (phi > beta): beam jb, or past phi_upper (-1); before it: beam jb - 1, or before phi_lower (-2 -> negative)
+      b.index = cr > 0.0 ? (jbq < a.beams ? jbq : -1) : jbq - 1;
+    } else b.cold = true;
+  }
+  if (__builtin_expect(__any(b.cold), 0)) {
+    // within 1e-11 rad of a boundary, or at the cut: the reference's own formulation decides (fp64 atan2, bound checks, round)
+    if (b.cold) b.index = backproject_cold(a_dev, ccx, ccy);
+  }
+  return b;
+}
+
+// ---- the exact part, per cell
+// The signed distance of a cell `dist` from the sensor to the reading r of its beam (TsdGrid.cpp:253-268): false where addTsd leaves
+// the cell (an infinite reading at or beyond lowReflectivityRange; sd < -maxTruncation)
+__device__ __forceinline__ bool cell_signed_distance(double r, double dist, double low_refl, double max_trunc, double& sd)
+{
+  sd = 0.0;
+  bool ok = false;
+  if (!isinf(r)) { sd = r - dist; ok = true; }
+  else if (dist < low_refl) { sd = max_trunc; ok = true; }
+  return ok && sd >= -max_trunc;
+}
+// TsdGridPartition::increaseEmptiness (TsdGridPartition.cpp:136-164) of one cell of a materialised tile; the average uses the NEW weight
+__device__ __forceinline__ void empty_cell(double& t, double& w)
+{
+  if (isnan(t)) { w += 1.0; t = 1.0; }
+  else { w = fmin(w + 1, MAX_WEIGHT); t = (t * (w - 1.0) + 1.0) / w; }
+}
+
 // ---- TsdGrid::propagateBorders (TsdGrid.cpp:372-427), incremental form, for ONE listed tile by ONE wave --------------------------------
 // The tile's own halo from R / U / UR and the halos of L / D / DL that mirror its first column / row / cell.  Equal to the reference's
 // full sweep by induction (untouched pairs are already consistent).  Every lane has up to three copy jobs (source cell -> destination
@@ -428,6 +657,25 @@ __device__ __forceinline__ void halo_bookkeeping(unsigned long long* __restrict_
     const double sx = a_dev->trx, sy = a_dev->try_;
     if (!(fabs(sx - cx) <= slack && fabs(sy - cy) <= slack)) pushes[1] += 1ull;
   }
+}
+
+// The launch window of a push (host): a tile passes the range cull of isInRange only if its centre is within max_range + radius +
+// max_trunc of the sensor (TsdGridComponent.cpp:52-60), and the sensor is within `slack` of (cx, cy).  Clamped to the grid; the whole
+// grid where the reach is not finite.
+inline TileBox push_tile_window(const GridDev& g, double cx, double cy, double max_range, double slack)
+{
+  const double tile = TILE_DIM * g.cs;
+  const double reach = max_range + 0.75 * tile + g.max_trunc + slack + g.cs;      // radius = sqrt(2)/2 tile < 0.75 tile
+  const double last = (double)(g.PX - 1);
+  const double fx0 = floor((cx - reach) / tile) - 1.0, fy0 = floor((cy - reach) / tile) - 1.0;
+  const double fx1 = floor((cx + reach) / tile) + 1.0, fy1 = floor((cy + reach) / tile) + 1.0;
+  TileBox b;
+  if (!(reach < 1e300) || !(fx0 == fx0)) { b.x0 = 0; b.y0 = 0; b.x1 = g.PX - 1; b.y1 = g.PX - 1; }
+  else {
+    b.x0 = (int)fmax(0.0, fmin(last, fx0)); b.y0 = (int)fmax(0.0, fmin(last, fy0));
+    b.x1 = (int)fmax(0.0, fmin(last, fx1)); b.y1 = (int)fmax(0.0, fmin(last, fy1));
+  }
+  return b;
 }
 
 // per-tile values the exact part (phase C) and the tile's record need; two tiles are in flight per workgroup

@@ -131,7 +131,7 @@ k_push_classify(GridDev g, const PushArgs* __restrict__ a_dev, const char* __res
   }
   const bool in_window = t < ntx * nty;
   const int p = in_window ? (ty0 + t / ntx) * g.PX + tx0 + t % ntx : 0;
-  uint32_t rec = 0u, kind = 0u, far_flag = 0u;
+  uint32_t rec = 0u, kind = 0u;
   // the tile's state, requested before anything else: it travels in the list record of an UPDATE tile (k_push_update then needs no
   // dependent read for it) and decides the increaseEmptiness case below
   // (unconditional reads -- p is 0 outside the window: the compiler waits for a predicated read on the spot, and this kernel is a
@@ -148,81 +148,13 @@ k_push_classify(GridDev g, const PushArgs* __restrict__ a_dev, const char* __res
     nbr = ((hL && nL) ? 2u : 0u) | ((hD && nD) ? 4u : 0u) | ((hL && hD && nDL) ? 8u : 0u);
   }
   const double t_iw = ld_pinned(&g.init_weight[p]);
-  double pw = 0.0;
-  double tcx = 0.0, tcy = 0.0;                               // the tile's centroid (UPDATE tiles)
-  uint32_t win = (uint32_t)(a.beams - 1) << 16;              // beams the cells of the tile can project to: lo | hi << 16
-  double2 bd0 = make_double2(1.0, 0.0);                      // direction of boundary jb0 = max(lo - 1, 0) of a far tile, 0 of a near one
+  TileRange tr{};                                           // (read for UPDATE tiles only)
   if (in_window && a.enabled) {
-    double e[4][2], cx, cy, rad;
-    tile_geometry(g, p, e, cx, cy, rad);
-    // euklideanDistance<obfloat>(pos, _centroid, 2) (mathbase.h:369-378)
-    double sqr = 0.0;
-    { const double t0 = a.trx - cx; sqr += t0 * t0; const double t1 = a.try_ - cy; sqr += t1 * t1; }
-    const double distance = sqrt(sqr);
-    const double closest = distance - rad - g.max_trunc;
-    const double farthest = distance + rad + g.max_trunc;
-    if (!(closest > a.max_range || farthest < a.min_range)) {
+    tr = tile_in_range(g, a, rmq_view(const_cast<char*>(rmq_buf), a.beams), p, corner);
+    if (tr.pass) {
       rec = REC_RANGE_PASS;
-      bool all_vis = true, any_vis = false;
-      int lo = 0, hi = 0;
-      {
-        const int k = corner;
-        const double ex = (k & 1) ? e[1][0] : e[0][0], ey = (k & 2) ? e[2][1] : e[0][1];
-        int ik = backproject(a.Pi, ex, ey, a.phi_min, a.ang_res_inv, a.phi_lower, a.phi_upper);
-        if (ik == -1) { ik = a.beams - 1; all_vis = false; }
-        else if (ik == -2) { ik = 0; all_vis = false; }
-        else any_vis = true;
-        // minmaxArray<int> (mathbase.h:55-64) over the four corners = minimum and maximum over the quad's lanes
-        lo = ik; hi = ik;
-      }
-      // (the whole quad is here or nowhere: the range cull above depends on the tile only)
-#pragma unroll
-      for (int m = 1; m <= 2; m <<= 1) {
-        const int lo2 = __shfl_xor(lo, m, 64), hi2 = __shfl_xor(hi, m, 64);
-        const int av2 = __shfl_xor((int)all_vis, m, 64), an2 = __shfl_xor((int)any_vis, m, 64);
-        lo = lo2 < lo ? lo2 : lo; hi = hi2 > hi ? hi2 : hi;
-        all_vis = all_vis && av2 != 0; any_vis = any_vis || an2 != 0;
-      }
-      // (requested here, next to the table look-ups below, used when the record is written)
-      bd0 = rmq_view(const_cast<char*>(rmq_buf), a.beams).bdir[(distance > 3.0 * rad && lo > 1) ? lo - 1 : 0];
-      int action = 0;
-      if (any_vis) {
-        const RmqView rv = rmq_view(const_cast<char*>(rmq_buf), a.beams);
-        const int len = hi - lo + 1;
-        const int k = 31 - __clz(len);                                         // floor(log2(len))
-        const unsigned short* tm = rv.tmax + (size_t)k * rv.Bp;
-        const unsigned short* tn = rv.tmin + (size_t)k * rv.Bp;
-        const int j2 = hi - (1 << k) + 1;
-        const unsigned short n0 = ld_pinned(&rv.inf[lo]), n1 = ld_pinned(&rv.inf[hi + 1]);     // (issued with the index look-ups, used last)
-        const unsigned short i0 = tm[lo], i1 = tm[j2], i2 = tn[lo], i3 = tn[j2];
-        const double amax = fmax(rv.A[i0], rv.A[i1]);
-        const double bmin = fmin(rv.Bv[i2], rv.Bv[i3]);
-        const bool has_inf = n1 != n0;
-        const bool visible = amax > closest;
-        const bool empty = (bmin > farthest) && (!has_inf || distance < a.low_refl);
-        if (visible) action = (all_vis && empty) ? 1 : 2;
-      }
-      // The cell centres of a tile lie inside the quadrilateral of the four corner points; seen from a sensor
-      // well outside of it the extreme angles are those of corners, so every cell projects into [lo, hi]
-      // (corners outside the field of view were mapped to its ends above).
-      if (distance > 3.0 * rad) {
-        win = (uint32_t)lo | ((uint32_t)hi << 16); far_flag = LIST_FAR;
-        // angular diameter of a far tile < 2 asin(1/3) = 0.68 rad; a tile that straddles the cut of a full-circle sensor has its
-        // corner indices at both ends of the scan instead
-        if (all_vis && lo >= 1 && hi <= a.beams - 2 && (double)(hi - lo) <= 0.7 * a.ang_res_inv + 2.0) far_flag |= LIST_INTERIOR;
-      }
-      if (action == 2) {
-        kind = KIND_UPDATE;
-        // partition weight (TsdGrid.cpp:239-243): ((maxRange - min(distance to the centroid, maxRange)) / maxRange)^2.
-        // `distance` above is that distance bit for bit ((a - b)^2 == (b - a)^2, 0.0 + x == x), so the per-tile
-        // square root and division are done once here instead of by every thread of the update workgroup.
-        double dc = distance;
-        if (dc > a.max_range) dc = a.max_range;
-        pw = (a.max_range - dc) / a.max_range;
-        pw *= pw;
-        tcx = cx; tcy = cy;
-      }
-      else if (action == 1) {
+      if (tr.action == ACT_UPDATE) kind = KIND_UPDATE;
+      else if (tr.action == ACT_EMPTY) {
         // TsdGridPartition::increaseEmptiness (TsdGridPartition.cpp:136-164), isInRange then returns false
         if (t_flag) kind = KIND_EMPTY;
         else {
@@ -261,27 +193,14 @@ k_push_classify(GridDev g, const PushArgs* __restrict__ a_dev, const char* __res
     unsigned int base_u = s_base[0], base_o = s_base[1], base_h = s_base[2];
     for (int w = 0; w < wave; w++) { base_u += s_wu[w]; base_o += s_wo[w]; base_h += s_wh[w]; }
     const unsigned long long lt = (1ull << lane) - 1ull;
-    const uint32_t word = (uint32_t)p | far_flag | (kind << KIND_SHIFT);
+    const uint32_t word = (uint32_t)p | tr.far_flag | (kind << KIND_SHIFT);
     if (kind != 0u && kind != KIND_UPDATE) list[(unsigned)g.tiles - 1u - (base_o + (unsigned)__popcll(ob & lt))] = word;
     if (kind == KIND_UPDATE && (t_flag == 0 || t_dirty != 0)) list_h[base_h + (unsigned)__popcll(hb & lt)] = word;
     if (kind == KIND_UPDATE) {
       const unsigned int slot = base_u + (unsigned)__popcll(ub & lt);
       list[slot] = word;
-      PushListAuxBody x;
-      x.entry = word; x.win = win; x.pw = 0.01 * pw;
-      // the linear forms of k_push_update's phase A (see PushListAux): fp64 here, once per tile, instead of fp32 in every lane there
-      const double lcx = a.Pi[0] * tcx + a.Pi[1] * tcy + a.Pi[2], lcy = a.Pi[3] * tcx + a.Pi[4] * tcy + a.Pi[5];
-      const double axx = a.Pi[0] * g.cs, axy = a.Pi[1] * g.cs, ayx = a.Pi[3] * g.cs, ayy = a.Pi[4] * g.cs;
-      x.A = (float)(lcx * ayx - lcy * axx); x.B = (float)(lcx * ayy - lcy * axy);
-      x.C = (float)(lcx * axx + lcy * ayx); x.D = (float)(lcx * axy + lcy * ayy);
-      x.lc2 = (float)(lcx * lcx + lcy * lcy);
-      x.lcx = (float)lcx; x.lcy = (float)lcy;
-      x.th_c = atan2_estimate(x.lcy, x.lcx);
-      x.iw = t_iw; x.flag = t_flag;
-      x.flag |= nbr;               // bit 0: the tile's _initialized; bits 1 / 2 / 3: left / lower / diagonal neighbour holds data
-      x.jb0 = (win & 0xFFFFu) > 0u ? (win & 0xFFFFu) - 1u : 0u;
-      x.bd = bd0;
-      static_cast<PushListAuxBody&>(list_aux[slot]) = x;
+      // flag bit 0: the tile's _initialized; bits 1 / 2 / 3: left / lower / diagonal neighbour holds data
+      static_cast<PushListAuxBody&>(list_aux[slot]) = make_update_record(g, a, word, tr, t_iw, (uint32_t)t_flag | nbr);
     }
   }
 }
@@ -436,7 +355,6 @@ k_push_update(GridDev g, const PushArgs* __restrict__ a_dev, const double* __res
     lds_barrier();                     // scan staged, counters zeroed, first tickets in place
     PSTAMP(0);
 
-    const unsigned long long lt = (1ull << lane) - 1ull;
     const unsigned ix = (unsigned)tid & 31u, iy0 = (unsigned)tid >> 5;
     const int c0 = (int)(iy0 * 32u + ix);                                  // phase A: cell k of this thread is c0 + 256 k = (ix, iy0 + 8 k)
     const float dxc = (float)ix - 16.0f;
@@ -454,71 +372,28 @@ k_push_update(GridDev g, const PushArgs* __restrict__ a_dev, const double* __res
         const double dw = cc - (col ? a.trx : a.try_);
         s_d2[(n & 1u) * 2 * TILE_DIM + tid] = dw * dw;
       }
-      ta.A = x.A; ta.B = x.B; ta.C = x.C; ta.D = x.D; ta.lc2 = x.lc2; ta.th_c = x.th_c; ta.lcx = x.lcx; ta.lcy = x.lcy;
-      const bool far = (x.entry & LIST_FAR) != 0u;
-      const bool interior = (x.entry & LIST_INTERIOR) != 0u;
-      const float pA = dxc * ta.A, pC = fmaf(dxc, ta.C, ta.lc2), qx = fmaf(ta.cs2 * dxc, dxc, -ta.lc2);
-      const float vc = fmaf(ta.th_c - ta.phi_min, ta.inv_res, 0.5f);
-      int idx[UPD_CPT]; float d2f[UPD_CPT];      // beam (or boundary, undecided cells) and fp32 squared distance of cell k
-      bool uns[UPD_CPT], in[UPD_CPT];            // undecided / decided inside the field of view (lane masks)
-#pragma unroll
-      for (int k = 0; k < UPD_CPT; k++) {
-        const float dyc = (float)(iy0 + 8u * (unsigned)k) - 16.0f;
-        CellClass cc;
-        if (interior) cc = classify_cell<true, true>(ta, dxc, dyc, pA, pC, qx, vc, d2f[k]);
-        else if (far) cc = classify_cell<true, false>(ta, dxc, dyc, pA, pC, qx, vc, d2f[k]);
-        else          cc = classify_cell<false, false>(ta, dxc, dyc, pA, pC, qx, vc, d2f[k]);
-        idx[k] = cc.j; uns[k] = cc.uns; in[k] = !cc.uns && !cc.out;
-      }
+      CellsA cs;
+      classify_cells(ta, x, dxc, iy0, cs);
       PSTAMP(6);     // (sub-phase: d2 table, setup, classification)
-      // the beams' limits from LDS, the four reads in flight together.  A decided beam outside the staged window -- possible only
-      // through rounding at the window's ends -- joins the undecided cells (boundary = the beam: the exact test names it again, and
-      // that path reads any beam)
-      float lim[UPD_CPT];
+      cell_limits(ta, s_lim, cs);
 #pragma unroll
       for (int k = 0; k < UPD_CPT; k++) {
-        const int il = min(max(idx[k], wlo), whi);
-        lim[k] = s_lim[il];
-        if (in[k] && il != idx[k]) { in[k] = false; uns[k] = true; }
-      }
-      bool cand[UPD_CPT];
-#pragma unroll
-      for (int k = 0; k < UPD_CPT; k++) {
-        cand[k] = in[k] && !(d2f[k] > lim[k]);
+        cs.cand[k] = is_candidate(cs, k);
         // a freshly materialised tile: cells that addTsd will not touch get the init value here
-        if (tc.fresh && !cand[k] && !uns[k]) st_cell(tc.T, tc.W, c0 + UPDATE_BLOCK * k, t_init, tc.iw);
+        if (tc.fresh && !cs.cand[k] && !cs.uns[k]) st_cell(tc.T, tc.W, c0 + UPDATE_BLOCK * k, t_init, tc.iw);
 #ifdef TSD_PUSH_VERIFY_INDEX   // diagnostic build: every decided cell against the exact formulation
         {
           const double ccx = ((double)(x0 + ix) + 0.5) * g.cs, ccy = ((double)(y0 + iy0 + 8u * (unsigned)k) + 0.5) * g.cs;
           const int ex = backproject(a.Pi, ccx, ccy, a.phi_min, a.ang_res_inv, a.phi_lower, a.phi_upper);
-          const int index = in[k] ? idx[k] : -1;
-          if (!uns[k] && (index < 0 ? ex >= 0 : ex != index)) atomicAdd(reinterpret_cast<unsigned long long*>(dbg + 1000), 1ull);
-          if (uns[k]) atomicAdd(reinterpret_cast<unsigned long long*>(dbg + 1001), 1ull);
+          const int index = cs.in[k] ? cs.idx[k] : -1;
+          if (!cs.uns[k] && (index < 0 ? ex >= 0 : ex != index)) atomicAdd(reinterpret_cast<unsigned long long*>(dbg + 1000), 1ull);
+          if (cs.uns[k]) atomicAdd(reinterpret_cast<unsigned long long*>(dbg + 1001), 1ull);
           atomicAdd(reinterpret_cast<unsigned long long*>(dbg + 1002), 1ull);
         }
 #endif
       }
       PSTAMP(7);     // (sub-phase: limits, candidate test, fresh stores)
-      // compaction: ONE LDS atomic per wave for its cells of all four strips -- the candidates go to the front of the tile's list, the
-      // undecided cells (cell | boundary << 10) to its back; the exact part settles those, densely, behind the barrier
-      unsigned long long bc[UPD_CPT], bu[UPD_CPT];
-      unsigned nc = 0u, nu = 0u;
-#pragma unroll
-      for (int k = 0; k < UPD_CPT; k++) { bc[k] = __ballot(cand[k]); bu[k] = __ballot(uns[k]); nc += (unsigned)__popcll(bc[k]); nu += (unsigned)__popcll(bu[k]); }
-      unsigned base = 0u, ub = 0u;
-      if (nc | nu) {
-        unsigned long long got = 0ull;
-        if (lane == 0) got = atomicAdd(cnt, (unsigned long long)nc | ((unsigned long long)nu << 32));
-        base = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)got);
-        ub = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(got >> 32));
-      }
-#pragma unroll
-      for (int k = 0; k < UPD_CPT; k++) {
-        const uint32_t e = (uint32_t)(c0 + UPDATE_BLOCK * k) | ((uint32_t)idx[k] << 10);
-        if (cand[k]) cand_list[base + (unsigned)__popcll(bc[k] & lt)] = e;
-        if (bu[k] && uns[k]) cand_list[(unsigned)(UPD_CAND_MAX - 1) - (ub + (unsigned)__popcll(bu[k] & lt))] = e;
-        base += (unsigned)__popcll(bc[k]); ub += (unsigned)__popcll(bu[k]);
-      }
+      compact_cells(cs, c0, lane, cnt, cand_list);
       PSTAMP(8);     // (sub-phase: compaction)
       if (tc.fresh) {
         // halo cells of a freshly materialised tile keep the init value until k_push_halo
@@ -565,44 +440,21 @@ k_push_update(GridDev g, const PushArgs* __restrict__ a_dev, const double* __res
       const double t_init = (tcur.iw > 0.0) ? 1.0 : __builtin_nan("");
       // ---- fix-up of the tile's undecided cells (~4 % of the cells: one partly filled wave per tile), one lane each, in place: entry
       // n_cand + u of the exact part below lives at list[1023 - u] and is settled here BY THE THREAD THAT WILL READ IT there (an LDS
-      // hand-off inside one lane: no barrier).  The side of the boundary direction beta_jb the cell's fp64 sensor-frame vector lies on
-      // -- the sign of |l| sin(angle - beta) = bx ly - by lx -- names the reference's beam unless |sin| < 1e-11.
+      // hand-off inside one lane: no barrier).  resolve_undecided names the cell's beam.
       for (unsigned u = ((unsigned)tid - n_cand) & (unsigned)(UPDATE_BLOCK - 1); u < n_uns; u += UPDATE_BLOCK) {
         const uint32_t e = cand_list[(unsigned)(UPD_CAND_MAX - 1) - u];
         const int c = (int)(e & 1023u);
         const int jbq = (int)(e >> 10);
         const double ccx = ((double)(x0 + ((unsigned)c & 31u)) + 0.5) * g.cs;   // TsdGridPartition.cpp:127-128
         const double ccy = ((double)(y0 + ((unsigned)c >> 5)) + 0.5) * g.cs;
-        // PoseInv * (x, y, 1)^T as SensorPolar2D::backProject forms it (dgemm order)
-        double lx = 0.0, ly = 0.0;
-        lx += a.Pi[0] * ccx; lx += a.Pi[1] * ccy; lx += a.Pi[2] * 1.0;
-        ly += a.Pi[3] * ccx; ly += a.Pi[4] * ccy; ly += a.Pi[5] * 1.0;
-        int index = -1;
-        bool hard = jbq == IDX_CUT;
-        const double l2 = lx * lx + ly * ly;
-        if (!hard) {
-          // the boundary's direction: beta_jb0 (from the tile's record) turned by (jb - jb0) * res -- a table in LDS; near tiles see the
-          // whole scan: the global table
-          const int kr = jbq - (int)xc.jb0;
-          const double2 bdc = bd_unpack(xc_v);
-          double2 bd;
-          if (__builtin_expect(kr >= 0 && kr < ROT_N, 1)) { const double2 rc = s_rot[kr]; bd.x = bdc.x * rc.x - bdc.y * rc.y; bd.y = bdc.y * rc.x + bdc.x * rc.y; }
-          else bd = bdir[jbq];
-          const double cr = bd.x * ly - bd.y * lx;                  // |l| sin(angle - beta_jb)
-          if (cr * cr > 1e-22 * l2) {
-            // beyond the boundary (phi > beta): beam jb, or past phi_upper (-1); before it: beam jb - 1, or before phi_lower (-2 -> negative)
-            index = cr > 0.0 ? (jbq < a.beams ? jbq : -1) : jbq - 1;
-          } else hard = true;
-        }
-        if (__builtin_expect(__any(hard), 0)) {
-          // within 1e-11 rad of a boundary, or at the cut: the reference's own formulation decides (fp64 atan2, bound checks, round)
-          if (hard) index = backproject_cold(a_dev, ccx, ccy);
-        }
+        // (near tiles see the whole scan: beyond the LDS rotation table, the global boundary table)
+        const UndecidedBeam beam = resolve_undecided(a, a_dev, xc.jb0, bd_unpack(xc_v), s_rot, bdir, ccx, ccy, jbq);
+        const int index = beam.index;
 #ifdef TSD_PUSH_VERIFY_INDEX
         {
           const int ex = backproject(a.Pi, ccx, ccy, a.phi_min, a.ang_res_inv, a.phi_lower, a.phi_upper);
           if (index < 0 ? ex >= 0 : ex != index) atomicAdd(reinterpret_cast<unsigned long long*>(dbg + 1003), 1ull);
-          if (hard) atomicAdd(reinterpret_cast<unsigned long long*>(dbg + 1004), 1ull);
+          if (beam.cold) atomicAdd(reinterpret_cast<unsigned long long*>(dbg + 1004), 1ull);
         }
 #endif
         bool cand = false;
@@ -611,7 +463,7 @@ k_push_update(GridDev g, const PushArgs* __restrict__ a_dev, const double* __res
           float lm = s_lim[il];
           asm volatile("" : "+v"(lm));
           if (__builtin_expect(il != index, 0)) { lm = beam_limit(ranges[index], (unsigned)mask[index], ta.mt, ta.low2); asm volatile("" : "+v"(lm)); }
-          cand = !((float)l2 > lm * 1.00001f);         // (|l|^2 from the fp64 vector here: within 1e-7 of phase A's fp32 form; the margin covers it)
+          cand = !((float)beam.l2 > lm * 1.00001f);      // (|l|^2 from the fp64 vector here: within 1e-7 of phase A's fp32 form; the margin covers it)
         }
         if (tcur.fresh && !cand) st_cell(tcur.T, tcur.W, c, t_init, tcur.iw);
         cand_list[(unsigned)(UPD_CAND_MAX - 1) - u] = cand ? ((uint32_t)c | ((uint32_t)index << 10)) : 0xFFFFFFFFu;
@@ -655,11 +507,10 @@ k_push_update(GridDev g, const PushArgs* __restrict__ a_dev, const double* __res
 #pragma unroll
             for (int jj = 0; jj < UPD_CB; jj++) asm volatile("" : "+v"(tv[jj]), "+v"(wv[jj]));
           }
-          double sd = 0.0; bool ok = false;
-          if (!isinf(r)) { sd = r - dist; ok = true; }
-          else if (dist < a.low_refl) { sd = max_trunc; ok = true; }
+          double sd;
+          const bool hit = cell_signed_distance(r, dist, a.low_refl, max_trunc, sd);
           bool touched = false;
-          if (on && ok && sd >= -max_trunc) touched = add_tsd(tv[j], wv[j], sd, w_meas, max_trunc, inv_max_trunc);
+          if (on && hit) touched = add_tsd(tv[j], wv[j], sd, w_meas, max_trunc, inv_max_trunc);
           n_upd += (unsigned)__popcll(__ballot(touched));
           if (touched && tv[j] < 0.0) wrote_neg |= neg_bit((unsigned)c & 31u, (unsigned)c >> 5);
           if (on && (touched || tcur.fresh)) st_cell(tcur.T, tcur.W, c, tv[j], wv[j]);
@@ -737,8 +588,7 @@ k_push_update(GridDev g, const PushArgs* __restrict__ a_dev, const double* __res
     w_cell_t* __restrict__ W = g.weight + (size_t)p * TILE_STRIDE;
     for (int i = tid; i < TILE_CELLS; i += UPDATE_BLOCK) {      // (interior, halo column, halo row: offsets 0..1088)
       double t = ld_tsd(T + i), w = ld_w(W + i);
-      if (isnan(t)) { w += 1.0; t = 1.0; }
-      else { w = fmin(w + 1, MAX_WEIGHT); t = (t * (w - 1.0) + 1.0) / w; }
+      empty_cell(t, w);
       st_cell(T, W, i, t, w);
     }
     if (tid == 0) { tile_rec[p] = REC_RANGE_PASS | REC_EMPTIED_INIT | REC_LISTED; atomicAdd(&tile_totals[(size_t)p * TOT_FIELDS + 5], 1u); }
@@ -977,15 +827,11 @@ int launch_push_tables(tsd_ctx* ctx, hipStream_t stream, int beams, const double
 {
   const size_t bp = (size_t)((beams + 3) & ~3);
   const size_t lds = 2 * bp * sizeof(double) + 4 * bp * 2 + 64;
-  std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
-  if (lds > ctx->tables_lds_configured) {     // the attribute is per device: remembered per context, not per process
-    TSD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_push_tables),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ctx->tables_lds_configured = lds;
-  }
+  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_push_tables), lds)) return rc;
   char* rmq;
   if (launch_target() && launch_target()->rmq) rmq = launch_target()->rmq;       // concurrent multi-robot path: the sensor's own (double) buffer
   else {
+    std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
     ctx->rmq_slot ^= 1;                                  // the push that may still be running keeps its tables
     ctx->d_rmq = ctx->d_rmq2[ctx->rmq_slot];
     rmq = ctx->d_rmq;
@@ -1000,15 +846,7 @@ int launch_push_tables_batch(tsd_ctx* ctx, hipStream_t stream, const TablesBatch
 {
   const size_t bp = (size_t)((max_beams + 3) & ~3);
   const size_t lds = 2 * bp * sizeof(double) + 4 * bp * 2 + 64;
-  {
-    std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
-    size_t& configured = ctx->lds_configured[reinterpret_cast<const void*>(k_push_tables_batch)];
-    if (lds > configured) {
-      TSD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_push_tables_batch),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured = lds;
-    }
-  }
+  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_push_tables_batch), lds)) return rc;
   hipLaunchKernelGGL(k_push_tables_batch, dim3(n), dim3(1024), lds, stream, d_entries);
   TSD_HIP_CHECK(ctx, hipGetLastError());
   return TSD_OK;
@@ -1024,23 +862,9 @@ int launch_push(tsd_ctx* ctx, const PushArgs& a, double cx, double cy, double sl
   char* const rmq = (launch_target() && launch_target()->rmq) ? launch_target()->rmq : ctx->d_rmq;
   if (!d_ranges) d_ranges = ctx->d_ranges;
   if (!d_mask) d_mask = ctx->d_mask;
-  // Tile window: a tile passes the range cull of isInRange only if its centre is within
-  // max_range + radius + max_trunc of the sensor (TsdGridComponent.cpp:52-60); the sensor is within `slack`
-  // of (cx, cy).  The window also covers the previous push (its records are rewritten) and whatever
-  // freeFootprint touched since.  sensor max_range comes from the by-value args or the attached sensor.
-  TileBox box;
-  {
-    const double tile = TILE_DIM * g.cs;
-    const double reach = a.max_range + 0.75 * tile + g.max_trunc + slack + g.cs;      // radius = sqrt(2)/2 tile < 0.75 tile
-    const double last = (double)(g.PX - 1);
-    const double fx0 = floor((cx - reach) / tile) - 1.0, fy0 = floor((cy - reach) / tile) - 1.0;
-    const double fx1 = floor((cx + reach) / tile) + 1.0, fy1 = floor((cy + reach) / tile) + 1.0;
-    if (!(reach < 1e300) || !(fx0 == fx0)) { box.x0 = 0; box.y0 = 0; box.x1 = g.PX - 1; box.y1 = g.PX - 1; }
-    else {
-      box.x0 = (int)fmax(0.0, fmin(last, fx0)); box.y0 = (int)fmax(0.0, fmin(last, fy0));
-      box.x1 = (int)fmax(0.0, fmin(last, fx1)); box.y1 = (int)fmax(0.0, fmin(last, fy1));
-    }
-  }
+  // Tile window (push_tile_window), sensor max_range from the by-value args or the attached sensor.  The window also covers the
+  // previous push (its records are rewritten) and whatever freeFootprint touched since.
+  TileBox box = push_tile_window(g, cx, cy, a.max_range, slack);
   const TileBox cur = box;
   box.add(ctx->box_prev);
   box.add(ctx->box_dirty);

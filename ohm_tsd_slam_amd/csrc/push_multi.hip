@@ -13,8 +13,8 @@
 // pass over the tiles the batch touched, after all of them, gives the halos the serial pushes leave.  tests/test_gpu_batch.py and
 // tools/fuzz_batch.py compare the grids cell for cell (halo included) with the oracle's serial pushes.
 //
-//   k_mp_classify   block y = robot: isInRange for every tile of the batch's window (the union of the robots' windows), the same
-//                   arithmetic as k_push_classify; per (tile, robot) the decision and the 128-byte record of the update's beam
+//   k_mp_classify   block y = robot: isInRange for every tile of the batch's window (the union of the robots' windows), with
+//                   k_push_classify's tile_in_range; per (tile, robot) the decision and the 128-byte record of the update's beam
 //                   estimate, per tile a 64-bit mask of who updates / who empties; first arrival lists the tile
 //   k_mp_update     one workgroup per listed tile: the tile's 33 x 33 cells into LDS once, then robot after robot -- stage the robot's
 //                   scan window, phase A (fp32 beam estimate, candidates compacted), fix-up of the undecided cells, the exact part on
@@ -59,69 +59,13 @@ k_mp_classify(GridDev g, MultiPushArgs mp, uint32_t* __restrict__ tile_rec, cons
     if (blockIdx.x == 0 && threadIdx.x == 0) { cnt[parity ^ 1] = 0u; cnt[2 + (parity ^ 1)] = 0u; }
   }
   const uint8_t t_dirty = ld_pinned(&dirty[p]);
-  uint32_t kind = 0u, far_flag = 0u;
-  double pw = 0.0, tcx = 0.0, tcy = 0.0;
-  uint32_t win = (uint32_t)(a.beams - 1) << 16;
-  double2 bd0 = make_double2(1.0, 0.0);
+  uint32_t kind = 0u;
+  TileRange tr{};                                           // (read for UPDATE tiles only)
   if (in_window && a.enabled) {
-    // TsdGridComponent::isInRange (TsdGridComponent.cpp:43-124): range cull, four corner back-projections (one lane each), the two
-    // beam-range tests as table look-ups -- k_push_classify's statements
-    double e[4][2], cx, cy, rad;
-    tile_geometry(g, p, e, cx, cy, rad);
-    double sqr = 0.0;
-    { const double t0 = a.trx - cx; sqr += t0 * t0; const double t1 = a.try_ - cy; sqr += t1 * t1; }
-    const double distance = sqrt(sqr);
-    const double closest = distance - rad - g.max_trunc;
-    const double farthest = distance + rad + g.max_trunc;
-    if (!(closest > a.max_range || farthest < a.min_range)) {
-      bool all_vis = true, any_vis = false;
-      int lo = 0, hi = 0;
-      {
-        const int k = corner;
-        const double ex = (k & 1) ? e[1][0] : e[0][0], ey = (k & 2) ? e[2][1] : e[0][1];
-        int ik = backproject(a.Pi, ex, ey, a.phi_min, a.ang_res_inv, a.phi_lower, a.phi_upper);
-        if (ik == -1) { ik = a.beams - 1; all_vis = false; }
-        else if (ik == -2) { ik = 0; all_vis = false; }
-        else any_vis = true;
-        lo = ik; hi = ik;
-      }
-#pragma unroll
-      for (int m = 1; m <= 2; m <<= 1) {
-        const int lo2 = __shfl_xor(lo, m, 64), hi2 = __shfl_xor(hi, m, 64);
-        const int av2 = __shfl_xor((int)all_vis, m, 64), an2 = __shfl_xor((int)any_vis, m, 64);
-        lo = lo2 < lo ? lo2 : lo; hi = hi2 > hi ? hi2 : hi;
-        all_vis = all_vis && av2 != 0; any_vis = any_vis || an2 != 0;
-      }
-      const RmqView rv = rmq_view(const_cast<char*>(rb.rmq), a.beams);
-      bd0 = rv.bdir[(distance > 3.0 * rad && lo > 1) ? lo - 1 : 0];
-      int action = 0;
-      if (any_vis) {
-        const int len = hi - lo + 1;
-        const int k = 31 - __clz(len);
-        const unsigned short* tm = rv.tmax + (size_t)k * rv.Bp;
-        const unsigned short* tn = rv.tmin + (size_t)k * rv.Bp;
-        const int j2 = hi - (1 << k) + 1;
-        const unsigned short n0 = ld_pinned(&rv.inf[lo]), n1 = ld_pinned(&rv.inf[hi + 1]);
-        const unsigned short i0 = tm[lo], i1 = tm[j2], i2 = tn[lo], i3 = tn[j2];
-        const double amax = fmax(rv.A[i0], rv.A[i1]);
-        const double bmin = fmin(rv.Bv[i2], rv.Bv[i3]);
-        const bool has_inf = n1 != n0;
-        const bool visible = amax > closest;
-        const bool empty = (bmin > farthest) && (!has_inf || distance < a.low_refl);
-        if (visible) action = (all_vis && empty) ? 1 : 2;
-      }
-      if (distance > 3.0 * rad) {
-        win = (uint32_t)lo | ((uint32_t)hi << 16); far_flag = LIST_FAR;
-        if (all_vis && lo >= 1 && hi <= a.beams - 2 && (double)(hi - lo) <= 0.7 * a.ang_res_inv + 2.0) far_flag |= LIST_INTERIOR;
-      }
-      if (action == 2) {
-        kind = KIND_UPDATE;
-        double dc = distance;
-        if (dc > a.max_range) dc = a.max_range;
-        pw = (a.max_range - dc) / a.max_range;
-        pw *= pw;
-        tcx = cx; tcy = cy;
-      } else if (action == 1) kind = KIND_EMPTY;
+    tr = tile_in_range(g, a, rmq_view(const_cast<char*>(rb.rmq), a.beams), p, corner);
+    if (tr.pass) {
+      if (tr.action == ACT_UPDATE) kind = KIND_UPDATE;
+      else if (tr.action == ACT_EMPTY) kind = KIND_EMPTY;
       if (owner) atomicAdd(&tile_totals[(size_t)p * TOT_FIELDS + 1], 1u);
     }
   }
@@ -129,19 +73,9 @@ k_mp_classify(GridDev g, MultiPushArgs mp, uint32_t* __restrict__ tile_rec, cons
   if (owner && in_window) {
     unsigned long long bits = 0ull;
     if (kind == KIND_UPDATE) {
-      PushListAuxBody x;
-      x.entry = (uint32_t)p | far_flag | (kind << KIND_SHIFT); x.win = win; x.pw = 0.01 * pw;
-      const double lcx = a.Pi[0] * tcx + a.Pi[1] * tcy + a.Pi[2], lcy = a.Pi[3] * tcx + a.Pi[4] * tcy + a.Pi[5];
-      const double axx = a.Pi[0] * g.cs, axy = a.Pi[1] * g.cs, ayx = a.Pi[3] * g.cs, ayy = a.Pi[4] * g.cs;
-      x.A = (float)(lcx * ayx - lcy * axx); x.B = (float)(lcx * ayy - lcy * axy);
-      x.C = (float)(lcx * axx + lcy * ayx); x.D = (float)(lcx * axy + lcy * ayy);
-      x.lc2 = (float)(lcx * lcx + lcy * lcy);
-      x.lcx = (float)lcx; x.lcy = (float)lcy;
-      x.th_c = atan2_estimate(x.lcy, x.lcx);
-      x.iw = 0.0; x.flag = 0u;                 // (the tile's state is the update kernel's business here)
-      x.jb0 = (win & 0xFFFFu) > 0u ? (win & 0xFFFFu) - 1u : 0u;
-      x.bd = bd0;
-      static_cast<PushListAuxBody&>(rec[(size_t)t * MP_MAX_ROBOTS + r]) = x;
+      // (the tile's state is the update kernel's business here)
+      static_cast<PushListAuxBody&>(rec[(size_t)t * MP_MAX_ROBOTS + r]) =
+          make_update_record(g, a, (uint32_t)p | tr.far_flag | (kind << KIND_SHIFT), tr, 0.0, 0u);
       bits = 1ull << r;
     } else if (kind == KIND_EMPTY) bits = 1ull << (MP_EMPTY_SHIFT + r);
     if (r == 0 && t_dirty != 0) bits |= MP_DIRTY;
@@ -166,6 +100,7 @@ k_mp_classify(GridDev g, MultiPushArgs mp, uint32_t* __restrict__ tile_rec, cons
 
 // ------------------------------------------------------------------------------------------------------------------------------
 constexpr int MP_BLOCK = 256;
+static_assert(MP_BLOCK == UPDATE_BLOCK, "phase A (push_device.hpp) lays the cells of a tile out over UPDATE_BLOCK threads");
 constexpr int MP_ARG_DOUBLES = (sizeof(PushArgs) + 7) / 8;
 __host__ __device__ inline size_t mp_update_lds_bytes(int beams)
 {
@@ -204,7 +139,6 @@ k_mp_update(GridDev g, MultiPushArgs mp, uint32_t* __restrict__ tile_totals, uns
   const int tid = threadIdx.x, lane = tid & 63;
   const unsigned int n_list = cnt[parity];
   const double max_trunc = g.max_trunc, inv_max_trunc = 1.0 / max_trunc;
-  const unsigned long long lt = (1ull << lane) - 1ull;
   const unsigned ix = (unsigned)tid & 31u, iy0 = (unsigned)tid >> 5;
   const int c0 = (int)(iy0 * 32u + ix);
   const float dxc = (float)ix - 16.0f;
@@ -292,8 +226,7 @@ k_mp_update(GridDev g, MultiPushArgs mp, uint32_t* __restrict__ tile_totals, uns
           __syncthreads();
           for (int i = tid; i < TILE_CELLS; i += MP_BLOCK) {
             double tv = s_t[i], wv = s_w[i];
-            if (isnan(tv)) { wv += 1.0; tv = 1.0; }
-            else { wv = fmin(wv + 1, MAX_WEIGHT); tv = (tv * (wv - 1.0) + 1.0) / wv; }
+            empty_cell(tv, wv);
             s_t[i] = tv; s_w[i] = wv;
           }
           changed = true; st_emp_i++;
@@ -340,57 +273,20 @@ k_mp_update(GridDev g, MultiPushArgs mp, uint32_t* __restrict__ tile_totals, uns
         const double dw = cc - (col ? a.trx : a.try_);
         s_d2[tid] = dw * dw;
       }
-      // ---- phase A (fp32): the beam estimate of every cell, candidates compacted (k_push_update's, see push_device.hpp)
+      // ---- phase A (fp32): the beam estimate of every cell, candidates compacted
       TileA ta;
       ta.phi_min = (float)a.phi_min; ta.inv_res = (float)a.ang_res_inv; ta.beams = a.beams;
       ta.mt = mtf; ta.low2 = low2f;
       ta.axx = (float)(a.Pi[0] * g.cs); ta.axy = (float)(a.Pi[1] * g.cs); ta.ayx = (float)(a.Pi[3] * g.cs); ta.ayy = (float)(a.Pi[4] * g.cs);
       ta.cs2 = (float)(g.cs * g.cs);
       ta.wlo = wlo; ta.whi = whi;
-      ta.A = x.A; ta.B = x.B; ta.C = x.C; ta.D = x.D; ta.lc2 = x.lc2; ta.th_c = x.th_c; ta.lcx = x.lcx; ta.lcy = x.lcy;
-      const bool far = (x.entry & LIST_FAR) != 0u, interior = (x.entry & LIST_INTERIOR) != 0u;
-      const float pA = dxc * ta.A, pC = fmaf(dxc, ta.C, ta.lc2), qx = fmaf(ta.cs2 * dxc, dxc, -ta.lc2);
-      const float vc = fmaf(ta.th_c - ta.phi_min, ta.inv_res, 0.5f);
-      int idx[UPD_CPT]; float d2f[UPD_CPT];
-      bool uns[UPD_CPT], in[UPD_CPT];
-#pragma unroll
-      for (int k = 0; k < UPD_CPT; k++) {
-        const float dyc = (float)(iy0 + 8u * (unsigned)k) - 16.0f;
-        CellClass cc;
-        if (interior) cc = classify_cell<true, true>(ta, dxc, dyc, pA, pC, qx, vc, d2f[k]);
-        else if (far) cc = classify_cell<true, false>(ta, dxc, dyc, pA, pC, qx, vc, d2f[k]);
-        else          cc = classify_cell<false, false>(ta, dxc, dyc, pA, pC, qx, vc, d2f[k]);
-        idx[k] = cc.j; uns[k] = cc.uns; in[k] = !cc.uns && !cc.out;
-      }
+      CellsA cs;
+      classify_cells(ta, x, dxc, iy0, cs);
       lds_barrier();                       // the windows, the distance tables and (a fresh tile) the init values are in LDS
-      float lim[UPD_CPT];
+      cell_limits(ta, s_lim + pb, cs);
 #pragma unroll
-      for (int k = 0; k < UPD_CPT; k++) {
-        const int il = min(max(idx[k], wlo), whi);
-        lim[k] = s_lim[pb + il];
-        if (in[k] && il != idx[k]) { in[k] = false; uns[k] = true; }
-      }
-      bool cand[UPD_CPT];
-#pragma unroll
-      for (int k = 0; k < UPD_CPT; k++) cand[k] = in[k] && !(d2f[k] > lim[k]);
-      unsigned long long bc[UPD_CPT], bu[UPD_CPT];
-      unsigned nc = 0u, nu = 0u;
-#pragma unroll
-      for (int k = 0; k < UPD_CPT; k++) { bc[k] = __ballot(cand[k]); bu[k] = __ballot(uns[k]); nc += (unsigned)__popcll(bc[k]); nu += (unsigned)__popcll(bu[k]); }
-      unsigned base = 0u, ub = 0u;
-      if (nc | nu) {
-        unsigned long long got = 0ull;
-        if (lane == 0) got = atomicAdd(&s_cu, (unsigned long long)nc | ((unsigned long long)nu << 32));
-        base = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)got);
-        ub = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(got >> 32));
-      }
-#pragma unroll
-      for (int k = 0; k < UPD_CPT; k++) {
-        const uint32_t e = (uint32_t)(c0 + MP_BLOCK * k) | ((uint32_t)idx[k] << 10);
-        if (cand[k]) s_cand[base + (unsigned)__popcll(bc[k] & lt)] = e;
-        if (bu[k] && uns[k]) s_cand[(unsigned)(UPD_CAND_MAX - 1) - (ub + (unsigned)__popcll(bu[k] & lt))] = e;
-        base += (unsigned)__popcll(bc[k]); ub += (unsigned)__popcll(bu[k]);
-      }
+      for (int k = 0; k < UPD_CPT; k++) cs.cand[k] = is_candidate(cs, k);
+      compact_cells(cs, c0, lane, &s_cu, s_cand);
       lds_barrier();
       const unsigned long long cu = s_cu;
       const unsigned n_cand = (unsigned)cu, n_uns = (unsigned)(cu >> 32);
@@ -403,33 +299,15 @@ k_mp_update(GridDev g, MultiPushArgs mp, uint32_t* __restrict__ tile_totals, uns
         const int jbq = (int)(e >> 10);
         const double ccx = ((double)(x0 + ((unsigned)c & 31u)) + 0.5) * g.cs;
         const double ccy = ((double)(y0 + ((unsigned)c >> 5)) + 0.5) * g.cs;
-        double lx = 0.0, ly = 0.0;
-        lx += a.Pi[0] * ccx; lx += a.Pi[1] * ccy; lx += a.Pi[2] * 1.0;
-        ly += a.Pi[3] * ccx; ly += a.Pi[4] * ccy; ly += a.Pi[5] * 1.0;
-        int index = -1;
-        bool hard = jbq == IDX_CUT;
-        const double l2 = lx * lx + ly * ly;
-        if (!hard) {
-          const int kr = jbq - (int)x.jb0;
-          const double2 bdc = x.bd;
-          double2 bd;
-          if (__builtin_expect(kr >= 0 && kr < ROT_N, 1)) {
-            const double2 rc = own_rot ? rmq_view(const_cast<char*>(rb.rmq), a.beams).rot[kr] : s_rot[kr];
-            bd.x = bdc.x * rc.x - bdc.y * rc.y; bd.y = bdc.y * rc.x + bdc.x * rc.y;
-          } else bd = rmq_view(const_cast<char*>(rb.rmq), a.beams).bdir[jbq];
-          const double cr = bd.x * ly - bd.y * lx;                  // |l| sin(angle - beta_jb)
-          if (cr * cr > 1e-22 * l2) index = cr > 0.0 ? (jbq < a.beams ? jbq : -1) : jbq - 1;
-          else hard = true;
-        }
-        if (__builtin_expect(__any(hard), 0)) {
-          if (hard) index = backproject_cold(rb.args, ccx, ccy);
-        }
+        const RmqView rv = rmq_view(const_cast<char*>(rb.rmq), a.beams);
+        const UndecidedBeam beam = resolve_undecided(a, rb.args, x.jb0, x.bd, own_rot ? rv.rot : s_rot, rv.bdir, ccx, ccy, jbq);
+        const int index = beam.index;
         bool cd = false;
         if (index >= 0) {
           const int il = min(max(index, wlo), whi);
           float lm = s_lim[pb + il];
           if (__builtin_expect(il != index, 0)) lm = beam_limit(rb.ranges[index], (unsigned)rb.mask[index], mtf, low2f);
-          cd = !((float)l2 > lm * 1.00001f);
+          cd = !((float)beam.l2 > lm * 1.00001f);
         }
         s_cand[(unsigned)(UPD_CAND_MAX - 1) - u] = cd ? ((uint32_t)c | ((uint32_t)index << 10)) : 0xFFFFFFFFu;
       }
@@ -446,12 +324,11 @@ k_mp_update(GridDev g, MultiPushArgs mp, uint32_t* __restrict__ tile_totals, uns
         double rg = s_ranges[pb + il];
         if (__builtin_expect(il != index, 0)) rg = rb.ranges[index];
         const double dist = sqrt_normal(s_d2[c & 31] + s_d2[TILE_DIM + (c >> 5)]);
-        double sd = 0.0; bool ok = false;
-        if (!isinf(rg)) { sd = rg - dist; ok = true; }
-        else if (dist < a.low_refl) { sd = max_trunc; ok = true; }
+        double sd;
+        const bool hit = cell_signed_distance(rg, dist, a.low_refl, max_trunc, sd);
         double tv = s_t[c], wv = s_w[c];
         bool touched = false;
-        if (on && ok && sd >= -max_trunc) touched = add_tsd(tv, wv, sd, w_meas, max_trunc, inv_max_trunc);
+        if (on && hit) touched = add_tsd(tv, wv, sd, w_meas, max_trunc, inv_max_trunc);
         n_upd += (unsigned)__popcll(__ballot(touched));
         if (touched) { s_t[c] = tv; s_w[c] = wv; if (tv < 0.0) wrote_neg |= neg_bit((unsigned)c & 31u, (unsigned)c >> 5); }
       }
@@ -553,19 +430,7 @@ int launch_push_multi(tsd_ctx* ctx, hipStream_t stream, int n, const PushArgs* c
   for (int i = 0; i < n; i++) {
     mp.r[i] = MultiPushRobot{a_dev[i], d_ranges[i], d_mask[i], d_rmq[i], cx[i], cy[i], slack[i] + g.cs};
     if (beams[i] > max_beams) max_beams = beams[i];
-    // the robot's own window (launch_push's rule): a tile passes the range cull only within max_range + radius + max_trunc of the sensor
-    const double tile = TILE_DIM * g.cs;
-    const double reach = max_range[i] + 0.75 * tile + g.max_trunc + slack[i] + g.cs;
-    const double last = (double)(g.PX - 1);
-    const double fx0 = floor((cx[i] - reach) / tile) - 1.0, fy0 = floor((cy[i] - reach) / tile) - 1.0;
-    const double fx1 = floor((cx[i] + reach) / tile) + 1.0, fy1 = floor((cy[i] + reach) / tile) + 1.0;
-    TileBox b;
-    if (!(reach < 1e300) || !(fx0 == fx0)) { b.x0 = 0; b.y0 = 0; b.x1 = g.PX - 1; b.y1 = g.PX - 1; }
-    else {
-      b.x0 = (int)fmax(0.0, fmin(last, fx0)); b.y0 = (int)fmax(0.0, fmin(last, fy0));
-      b.x1 = (int)fmax(0.0, fmin(last, fx1)); b.y1 = (int)fmax(0.0, fmin(last, fy1));
-    }
-    box.add(b);
+    box.add(push_tile_window(g, cx[i], cy[i], max_range[i], slack[i]));          // the robot's own window
   }
   const TileBox cur = box;
   box.add(ctx->box_prev);
@@ -603,14 +468,7 @@ int launch_push_multi(tsd_ctx* ctx, hipStream_t stream, int n, const PushArgs* c
   }
   TSD_HIP_CHECK(ctx, hipGetLastError());
   const size_t lds = mp_update_lds_bytes(max_beams);
-  {
-    std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
-    size_t& configured = ctx->lds_configured[reinterpret_cast<const void*>(k_mp_update)];
-    if (lds > configured) {
-      TSD_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(k_mp_update), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      configured = lds;
-    }
-  }
+  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_mp_update), lds)) return rc;
   int per_cu = (int)((160u * 1024u) / (lds + 256));
   if (per_cu > 4) per_cu = 4;
   if (per_cu < 1) per_cu = 1;

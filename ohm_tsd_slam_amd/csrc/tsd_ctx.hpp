@@ -185,8 +185,7 @@ struct tsd_ctx {
   char* d_rmq = nullptr;                     // range-query tables of the current scan (k_push_tables): one of d_rmq2
   char* d_rmq2[2] = {nullptr, nullptr};      // (the next scan's tables are built while the current push still reads its own)
   int rmq_slot = 0;
-  size_t tables_lds_configured = 0;          // dynamic LDS k_push_tables was configured for on this context's device
-  std::map<const void*, size_t> lds_configured;   // the same for the k_icp instantiations
+  std::map<const void*, size_t> lds_configured;   // dynamic LDS every kernel was configured for on this context's device (ensure_dynamic_lds)
   hipEvent_t ev_h2d = nullptr;               // fused scan: the scan's copy (side stream) is complete
   uint32_t* d_tile_rec = nullptr;            // [tiles] what the last push did to every tile
   uint8_t* d_dirty = nullptr;                // [tiles] written by freeFootprint since the last push
@@ -396,6 +395,19 @@ struct TargetScope {
     hipError_t _e = (call);                                                          \
     if (_e != hipSuccess) return tsd::set_error((ctx), TSD_E_HIP, #call, _e);        \
   } while (0)
+
+// Raises a kernel's dynamic-LDS limit to `bytes` where it is below.  The attribute is per device: remembered per context (and kernel
+// instantiation), not per process.
+inline int ensure_dynamic_lds(tsd_ctx* ctx, const void* kernel, size_t bytes)
+{
+  std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
+  size_t& configured = ctx->lds_configured[kernel];
+  if (bytes > configured) {
+    TSD_HIP_CHECK(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    configured = bytes;
+  }
+  return TSD_OK;
+}
 
 // Event-timed launch.  Default: the two events are handed to hipExtLaunchKernelGGL, which stamps them with the
 // dispatch's own begin / end (the duration rocprofv3 reports, free of the gaps between stream operations).

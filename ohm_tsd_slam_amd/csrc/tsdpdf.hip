@@ -1055,25 +1055,14 @@ static int pre_inputs_ready(tsd_ctx* ctx, tsd_sensor* s, hipStream_t stream)
   }
   return TSD_OK;
 }
-static int pre_configure_lds(tsd_ctx* ctx, const void* kernel, size_t prep_lds)
-{
-  // (k_pdf_prepare's static LDS is ~33 KB; beyond ~3 000 beams the dynamic part needs the attribute)
-  std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
-  size_t& configured = ctx->lds_configured[kernel];
-  if (prep_lds > configured) {
-    TSD_HIP_CHECK(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds));
-    configured = prep_lds;
-  }
-  return TSD_OK;
-}
-
 int launch_preregistration(tsd_ctx* ctx, tsd_sensor* s, hipStream_t stream, const double* d_coords, const uint8_t* d_mask_m,
                            const double* d_pose6, const double** tinit_dev, hipEvent_t before_score, IcpPreLaunch* fold)
 {
   const tsd_sensor::PreLayout& L = s->pre;
   if (int rc = pre_inputs_ready(ctx, s, stream)) return rc;
   const PreLaunch pl = pre_launch_args(s, d_coords, d_mask_m, d_pose6);
-  if (int rc = pre_configure_lds(ctx, reinterpret_cast<const void*>(k_pdf_prepare), pl.prep_lds)) return rc;
+  // (k_pdf_prepare's static LDS is ~33 KB; beyond ~3 000 beams the dynamic part needs the attribute)
+  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_pdf_prepare), pl.prep_lds)) return rc;
   {
     ScopedKernelTimer t(ctx, "tsdpdf", true);
     hipLaunchKernelGGL(k_pdf_normals, dim3((2 * L.n + 255) / 256, 2), dim3(256), 0, stream, pl.normals.set0, pl.normals.set1, L.n, pl.normals.sr);
@@ -1122,7 +1111,7 @@ int launch_preregistration_batch(tsd_ctx* ctx, hipStream_t stream, tsd_sensor* c
       s->pre_done_valid = false;              // (no event of this sensor's own behind the batched arg-max; batches are armed between scans)
       s->pre_res_off_hdr = s->pre.off_hdr; s->pre_res_off_res = s->pre.off_res;
     }
-    if (int rc = pre_configure_lds(ctx, reinterpret_cast<const void*>(k_pdf_prepare_batch), max_lds)) return rc;
+    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_pdf_prepare_batch), max_lds)) return rc;
     // (the scoring strides a fixed grid over each robot's candidates: a share of the single launch's grid per robot keeps the
     // batch's workgroups at about that launch's number)
     const int blocks = std::max(64, std::min(max_blocks, PDF_SCORE_GRID / std::max(1, m / 2)));
