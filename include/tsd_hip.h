@@ -227,6 +227,44 @@ int tsd_pdf_match(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m
  * and returns n (0 when the last pre-registration call on this context scored nothing or was a tsd_tsdpdf_match). */
 int tsd_debug_pdf_match_scores(tsd_ctx* ctx, double* prob_ungated, int* fov, int cap);
 
+/* ---- pre-registration (registration_mode 1) ------------------------------------------------------------- */
+/* obvious::RandomNormalMatching(trials, epsThresh, sizeControlSet) (RandomNormalMatching.cpp:19-28; ThreadLocalize.cpp:183:
+ * the shared "trials", "epsThresh", "sizeControlSet", not the ransac_* ones) and the arguments of its match() that are not
+ * point sets (ThreadLocalize.cpp:537) */
+typedef struct {
+  int    trials;                  /* "trials" */
+  int    size_control_set;        /* "sizeControlSet" */
+  double eps_thresh;              /* "epsThresh": _scaleDistance = 1 / (epsThresh * epsThresh) */
+  double phi_max;                 /* deg2rad("ransac_phi_max"), capped at pi/2 inside (:190) */
+  double ang_res;                 /* sensor->getAngularResolution() */
+} tsd_rnmatch_params;
+typedef struct {
+  double T[9];                  /* TBest, 3x3 row-major (identity when no candidate was accepted) */
+  double ratio;                 /* bestRatio = cntMatch / maxCntMatch of the winner (0 if none) */
+  double err_sum;               /* bestErr: the winner's errSum (1e12 if none) */
+  int32_t cnt_match, max_cnt_match;   /* the winner's counts (0 if none) */
+  int32_t idx_model, idx_scene; /* the winning pair (beam indices), -1 if none */
+  int32_t candidates;           /* (trial, i) pairs scored */
+  int32_t valid_model, valid_scene, control_points;   /* idxMValid.size(), idxSValid.size(), Control->getCols() */
+  int32_t reserved[2];
+} tsd_rnmatch_result;
+/* obvious::RandomNormalMatching::match(M, maskM, NULL, S, maskS, phiMax, transMax, resolution)
+ * (RandomNormalMatching.cpp:67-395): the same beam-indexed inputs and rand() streams as tsd_pdf_match (the front end is
+ * shared).  Each candidate carries the control set through T and rates it by the exact nearest valid model point (L2, ties to
+ * the lowest position in idxMValid) and the normal consensus; the winner is Kuehn's rating folded in the reference's serial
+ * (trial, i) order (:344-359).  T is TBest (identity on the reference's early returns and when nothing is accepted).  Scoring
+ * and selection run on the device. */
+int tsd_rn_match(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m, const double* scene_xy_2B,
+                 const uint8_t* mask_s, int beams, const tsd_rnmatch_params* params, const int* draws_subsample,
+                 const int* draws_control, const int* draws_trials, tsd_rnmatch_result* result);
+/* TEST HOOK: the last tsd_rn_match's per-candidate values in candidate order: cntMatch (before the cntMatchThresh test),
+ * maxCntMatch (control points in view) and errSum.  Copies min(n, cap) entries and returns n (0 when the last
+ * pre-registration call on this context scored nothing or was not a tsd_rn_match). */
+int tsd_debug_rn_match_scores(tsd_ctx* ctx, int* cnt, int* max_cnt, double* err_sum, int cap);
+/* TEST HOOK: the device selection of tsd_rn_match on given arrays of n candidates (serial order): the index of the winner
+ * of Kuehn's rating among those with cnt > thresh in *winner (-1 if none).  Returns TSD_OK. */
+int tsd_debug_rn_select(tsd_ctx* ctx, const int* cnt, const int* max_cnt, const double* err_sum, int n, int thresh, int* winner);
+
 /* ---- fused scan: ThreadLocalize::eventLoop + ThreadMapping push without a host round trip ------------ */
 /* Device-resident mirror of one robot's obvious::SensorPolar2D (pose, world / local ray maps) and of
  * ThreadLocalize's pose bookkeeping (_lastPose).  Several sensors may share one grid context

@@ -95,6 +95,23 @@ PDFMATCH_DEFAULTS = dict(trials=100, size_control_set=140, eps_thresh=0.15, zhit
                          lamshort=0.08, max_angle_diff=3.0, max_angle_penalty=0.5)
 
 
+class RnMatchParams(C.Structure):
+    """tsd_rnmatch_params"""
+    _fields_ = [("trials", C.c_int), ("size_control_set", C.c_int), ("eps_thresh", C.c_double), ("phi_max", C.c_double),
+                ("ang_res", C.c_double)]
+
+
+class RnMatchResult(C.Structure):
+    """tsd_rnmatch_result"""
+    _fields_ = [("T", C.c_double * 9), ("ratio", C.c_double), ("err_sum", C.c_double), ("cnt_match", C.c_int32),
+                ("max_cnt_match", C.c_int32), ("idx_model", C.c_int32), ("idx_scene", C.c_int32), ("candidates", C.c_int32),
+                ("valid_model", C.c_int32), ("valid_scene", C.c_int32), ("control_points", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# the node's defaults for registration_mode 1 (ThreadLocalize.cpp:105-107, :183): RnMatchParams fields -> value
+RNMATCH_DEFAULTS = dict(trials=100, size_control_set=140, eps_thresh=0.15)
+
+
 class IcpResult(C.Structure):
     _fields_ = [
         ("T", C.c_double * 9),
@@ -188,6 +205,10 @@ ABI = {
     "tsd_pdf_match": (C.c_int, [C.c_void_p, _dp, _u8p, _dp, _u8p, C.c_int, C.POINTER(PdfMatchParams), _ip, _ip, _ip,
                                 C.POINTER(TsdPdfResult)]),
     "tsd_debug_pdf_match_scores": (C.c_int, [C.c_void_p, _dp, _ip, C.c_int]),
+    "tsd_rn_match": (C.c_int, [C.c_void_p, _dp, _u8p, _dp, _u8p, C.c_int, C.POINTER(RnMatchParams), _ip, _ip, _ip,
+                               C.POINTER(RnMatchResult)]),
+    "tsd_debug_rn_match_scores": (C.c_int, [C.c_void_p, _ip, _ip, _dp, C.c_int]),
+    "tsd_debug_rn_select": (C.c_int, [C.c_void_p, _ip, _ip, _dp, C.c_int, C.c_int, _ip]),
     "tsd_scan_preregister": (C.c_int, [C.c_void_p, C.POINTER(TsdPdfParams), _dp, _u8p, _ip, _ip, _ip]),
     "tsd_scan_preregistration_result": (C.c_int, [C.c_void_p, C.POINTER(TsdPdfResult)]),
     "tsd_sensor_set_async_mapping": (C.c_int, [C.c_void_p, C.c_int]),
@@ -241,7 +262,8 @@ def load_library(path: str | None = None):
     for cname, mirror in (("tsd_push_stats", PushStats), ("tsd_icp_params", IcpParams), ("tsd_icp_result", IcpResult),
                           ("tsd_gate_params", GateParams), ("tsd_scan_result", ScanResult), ("tsd_grid_digest_t", GridDigest),
                           ("tsd_tsdpdf_params", TsdPdfParams), ("tsd_tsdpdf_result", TsdPdfResult),
-                          ("tsd_pdfmatch_params", PdfMatchParams)):
+                          ("tsd_pdfmatch_params", PdfMatchParams), ("tsd_rnmatch_params", RnMatchParams),
+                          ("tsd_rnmatch_result", RnMatchResult)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -401,6 +423,42 @@ class TsdGridDevice:
         p, f = np.zeros(max(n, 1)), np.zeros(max(n, 1), dtype=np.int32)
         self.lib.tsd_debug_pdf_match_scores(self.h, _d(p), f.ctypes.data_as(_ip), n)
         return p[:n], f[:n]
+
+    def rn_match(self, model_xy, mask_m, scene_xy, mask_s, phi_max, ang_res, draws_sub, draws_ctrl, draws_trials, **kw) -> dict:
+        """obvious::RandomNormalMatching::match with the rand() draws as inputs (tsd_rn_match); `kw` overrides RNMATCH_DEFAULTS"""
+        M, S = _f64(model_xy).reshape(-1), _f64(scene_xy).reshape(-1)
+        n = M.size // 2
+        mM, mS = np.ascontiguousarray(mask_m, dtype=np.uint8), np.ascontiguousarray(mask_s, dtype=np.uint8)
+        ds, dc, dt = (np.ascontiguousarray(x, dtype=np.int32) for x in (draws_sub, draws_ctrl, draws_trials))
+        v = dict(RNMATCH_DEFAULTS, **kw)
+        assert ds.size >= n and dc.size >= v["size_control_set"] and dt.size >= v["trials"]
+        prm = RnMatchParams(phi_max=phi_max, ang_res=ang_res, **v)
+        r = RnMatchResult()
+        rc = self.lib.tsd_rn_match(self.h, _d(M), _u8(mM), _d(S), _u8(mS), n, C.byref(prm), ds.ctypes.data_as(_ip),
+                                   dc.ctypes.data_as(_ip), dt.ctypes.data_as(_ip), C.byref(r))
+        self._check(rc, "tsd_rn_match")
+        return dict(T=np.array(r.T[:]).reshape(3, 3), ratio=r.ratio, err_sum=r.err_sum, cnt=r.cnt_match, max_cnt=r.max_cnt_match,
+                    idx=r.idx_model, i=r.idx_scene, candidates=r.candidates, valid_model=r.valid_model, valid_scene=r.valid_scene,
+                    control=r.control_points)
+
+    def debug_rn_match_scores(self):
+        """TEST HOOK: the last rn_match's cntMatch, maxCntMatch and errSum per candidate, in candidate order"""
+        n = self.lib.tsd_debug_rn_match_scores(self.h, None, None, None, 0)
+        self._check(min(n, 0), "tsd_debug_rn_match_scores")
+        c, m, e = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1))
+        self.lib.tsd_debug_rn_match_scores(self.h, c.ctypes.data_as(_ip), m.ctypes.data_as(_ip), _d(e), n)
+        return c[:n], m[:n], e[:n]
+
+    def debug_rn_select(self, cnt, max_cnt, err_sum, thresh) -> int:
+        """TEST HOOK: the device selection of rn_match (Kuehn's rating in serial order) on given arrays: the winner's index or -1"""
+        c, m = np.ascontiguousarray(cnt, dtype=np.int32), np.ascontiguousarray(max_cnt, dtype=np.int32)
+        e = _f64(err_sum).reshape(-1)
+        assert c.size == m.size == e.size
+        w = C.c_int(-2)
+        rc = self.lib.tsd_debug_rn_select(self.h, c.ctypes.data_as(_ip), m.ctypes.data_as(_ip), _d(e), int(c.size), int(thresh),
+                                          C.byref(w))
+        self._check(rc, "tsd_debug_rn_select")
+        return w.value
 
     def icp(self, model_xy, scene_xy, pose, params: IcpParams, model_normals_xy=None) -> IcpOut:
         m = _f64(model_xy).reshape(-1)

@@ -82,6 +82,7 @@ ThreadLocalize::ThreadLocalize(obvious::TsdGrid* grid, ThreadMapping* mapper, co
   _ranPhiMax   = node->get_parameter(_robotName + "ransac_phi_max").as_double();
   _preMatcher.reset();
   _pdfMatcher.reset();
+  _rnMatcher.reset();
   std::memset(&_preResult, 0, sizeof(_preResult));
   switch(_regMode)
   {
@@ -115,10 +116,19 @@ ThreadLocalize::ThreadLocalize(obvious::TsdGrid* grid, ThreadMapping* mapper, co
                                                node->get_parameter("maxAnglePenalty").as_double()));
     _pdfMatcher->setSeed((long)param(node, _robotName + "tsdpdf_seed", -1).as_int());   // addition: reproducible draws for tests
     break;
-  case 1:   // EXP: RandomNormalMatching
-    std::fprintf(stderr, "Localizer(%s): registration mode 1 (RandomNormalMatching pre-registration) is not part of "
-                         "the GPU hot path (out of scope); using default = ICP.\n", _nameSpace.c_str());
-    _regMode = 0;
+  case 1:   // EXP (ThreadLocalize.cpp:181-183): RandomNormalMatching(trials, epsThresh, sizeControlSet) -- the shared parameters, not
+            // the ransac_* ones
+    if(!obvious::RandomNormalMatching::available())
+    {
+      std::fprintf(stderr, "Localizer(%s): registration mode 1 (RandomNormalMatching pre-registration): the device library has no "
+                           "tsd_rn_match; using default = ICP.\n", _nameSpace.c_str());
+      _regMode = 0;
+      break;
+    }
+    _rnMatcher.reset(new obvious::RandomNormalMatching(*grid, (unsigned)node->get_parameter("trials").as_int(),
+                                                       node->get_parameter("epsThresh").as_double(),
+                                                       (unsigned)node->get_parameter("sizeControlSet").as_int()));
+    _rnMatcher->setSeed((long)param(node, _robotName + "tsdpdf_seed", -1).as_int());   // addition: reproducible draws for tests
     break;
   default:  // ThreadLocalize.cpp:188-190
     std::fprintf(stderr, "Localizer(%s): Unknown registration mode %d use default = ICP.\n", _nameSpace.c_str(), _regMode);
@@ -325,7 +335,7 @@ void ThreadLocalize::processScan(const std::vector<float>& ranges, const builtin
   // (several robots on one grid: the batched dispatcher runs the pre-registration behind its batch's ray casts; the split scan does not)
   // (registration_mode 2: always the reference's call structure, the matcher's host part between the ray cast and the registration)
   if((_regMode == 3 && _preMatcher && (mode3Unfused || !_preFusedOk || !_fused || !_sensor->deviceHandle() || (_concurrent && !_grid.batcher()))) ||
-     (_regMode == 2 && _pdfMatcher))
+     (_regMode == 2 && _pdfMatcher) || (_regMode == 1 && _rnMatcher))
   {
     processScanPreRegistered(rep);
     return;
@@ -412,8 +422,22 @@ void ThreadLocalize::processScanPreRegistered(ScanReport& rep)
   //                                                      deg2rad(_ranPhiMax), _trnsMax, sensor->getAngularResolution())
   //                 case PDF: T = _PDFMatcher->match(M, _maskM, NULL, S, _maskS, deg2rad(_ranPhiMax), _trnsMax,
   //                                                  sensor->getAngularResolution())  (ThreadLocalize.cpp:545-553)
+  //                 case EXP: T = _RandomNormalMatcher->match(M, _maskM, NULL, S, _maskS, deg2rad(_ranPhiMax), _trnsMax,
+  //                                                           sensor->getAngularResolution())  (ThreadLocalize.cpp:537-545)
   obvious::Matrix Tpre(3, 3);
-  if(_regMode == 2)
+  tsd_tsdpdf_result pre;
+  std::memset(&pre, 0, sizeof(pre));
+  if(_regMode == 1)
+  {
+    Tpre = _rnMatcher->match(_modelCoords.data(), maskM, nullptr, _scene.data(), maskS, n, _ranPhiMax * M_PI / 180.0, _trnsMax,
+                             _sensor->getAngularResolution());
+    // reported in the common record: bestRatio in the probability slot
+    const tsd_rnmatch_result& r = _rnMatcher->lastResult();
+    std::memcpy(pre.T, r.T, sizeof(pre.T));
+    pre.probability = r.ratio; pre.idx_model = r.idx_model; pre.idx_scene = r.idx_scene; pre.candidates = r.candidates;
+    pre.valid_model = r.valid_model; pre.valid_scene = r.valid_scene; pre.control_points = r.control_points;
+  }
+  else if(_regMode == 2)
     Tpre = _pdfMatcher->match(_modelCoords.data(), maskM, nullptr, _scene.data(), maskS, n, _ranPhiMax * M_PI / 180.0, _trnsMax,
                               _sensor->getAngularResolution());
   else
@@ -421,7 +445,7 @@ void ThreadLocalize::processScanPreRegistered(ScanReport& rep)
                               n, _ranPhiMax * M_PI / 180.0, _trnsMax, _sensor->getAngularResolution());
   {
     std::lock_guard<std::mutex> lk(_reportMutex);
-    _preResult = _regMode == 2 ? _pdfMatcher->lastResult() : _preMatcher->lastResult();
+    _preResult = _regMode == 1 ? pre : _regMode == 2 ? _pdfMatcher->lastResult() : _preMatcher->lastResult();
     _havePreResult = true;
   }
   g_m3.lap(2);

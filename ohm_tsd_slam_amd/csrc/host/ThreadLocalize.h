@@ -2,9 +2,9 @@
 // ThreadLocalize (src/ThreadLocalize.h:73-104): same constructor, same laserCallBack entry point, same
 // parameters, topic and message content.  The arithmetic of eventLoop (ray cast, ICP) runs on the GPU
 // through obvious::TsdGrid::localize; scan ingest, gates and pose bookkeeping stay on the host.
-// registration_mode 0 (ICP only), 2 (PDFMatching pre-registration + ICP) and 3 (TSD_PDF pre-registration + ICP, what
-// config/single-laser.yaml ships) are implemented; mode 1 (RandomNormalMatching: out of scope) falls back to 0 with a warning,
-// as the reference does for unknown modes (ThreadLocalize.cpp:188-190).
+// registration_mode 0 (ICP only), 1 (RandomNormalMatching pre-registration + ICP), 2 (PDFMatching pre-registration + ICP) and
+// 3 (TSD_PDF pre-registration + ICP, what config/single-laser.yaml ships) are implemented; unknown modes fall back to 0 with a
+// warning, as in the reference (ThreadLocalize.cpp:188-190).
 #pragma once
 #include <deque>
 #include <memory>
@@ -56,8 +56,8 @@ public:
   };
   ScanReport lastReport();
   uint64_t processedScans();
-  /** the last pre-registration of the reference's call structure (registration_mode 2, and mode 3 where it runs unfused); false if
-   *  there was none */
+  /** the last pre-registration of the reference's call structure (registration_modes 1 and 2, and mode 3 where it runs unfused;
+   *  mode 1 reports bestRatio as the probability); false if there was none */
   bool lastPreregistration(tsd_tsdpdf_result* out);
   /** nothing queued and nothing being processed */
   bool idle();
@@ -104,6 +104,7 @@ private:
   double _ranPhiMax;
   std::unique_ptr<obvious::TSD_PDFMatching> _preMatcher;      // _TSD_PDFMatcher (ThreadLocalize.h)
   std::unique_ptr<obvious::PDFMatching> _pdfMatcher;          // _PDFMatcher (ThreadLocalize.h)
+  std::unique_ptr<obvious::RandomNormalMatching> _rnMatcher;  // _RandomNormalMatcher (ThreadLocalize.h)
   tsd_tsdpdf_result _preResult;                               // (guarded by _reportMutex)
   bool _havePreResult = false;
   std::vector<double> _modelCoords, _modelNormals, _scene;     // beam-indexed buffers of the event loop (:342-350)

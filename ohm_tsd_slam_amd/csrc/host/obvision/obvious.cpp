@@ -1,10 +1,11 @@
 // obvious.cpp -- host-side sensor model and the device-grid handle (see obvious.h).
 #include "obvious.h"
 
-// tsd_pdf_match is referenced WEAKLY: host builds that link this file against a device library without registration_mode 2 (the
-// CPU thread-contract test links a recording stand-in of the C ABI) still link; PDFMatching::available() then says false and
-// ThreadLocalize falls back to ICP with a warning.
+// tsd_pdf_match and tsd_rn_match are referenced WEAKLY: host builds that link this file against a device library without
+// registration_modes 2 and 1 (the CPU thread-contract test links a recording stand-in of the C ABI) still link;
+// PDFMatching::available() / RandomNormalMatching::available() then say false and ThreadLocalize falls back to ICP with a warning.
 #pragma weak tsd_pdf_match
+#pragma weak tsd_rn_match
 #include <cstdlib>
 #include <ctime>
 
@@ -685,6 +686,53 @@ Matrix PDFMatching::match(const double* M, const bool* maskM, const double* /*NM
   }
   if (rc != TSD_OK) {
     std::fprintf(stderr, "PDFMatching::match failed (%d): %s\n", rc, tsd_last_error(_grid.context()));
+    return TBest;
+  }
+  TBest.setData(_last.T);
+  return TBest;
+}
+
+// --------------------------------------------------------------------------------------- RandomNormalMatching
+RandomNormalMatching::RandomNormalMatching(TsdGrid& grid, unsigned int trials, double epsThresh, unsigned int sizeControlSet)
+    : _grid(grid), _seed(-1), _calls(0)
+{
+  std::memset(&_prm, 0, sizeof(_prm));
+  _prm.trials = (int)trials; _prm.size_control_set = (int)sizeControlSet; _prm.eps_thresh = epsThresh;
+  std::memset(&_last, 0, sizeof(_last));
+}
+
+bool RandomNormalMatching::available()
+{
+  return tsd_rn_match != nullptr;
+}
+
+tsd_rnmatch_params RandomNormalMatching::params(double phiMax, double resolution) const
+{
+  tsd_rnmatch_params prm = _prm;
+  prm.phi_max = phiMax; prm.ang_res = resolution;
+  return prm;
+}
+
+Matrix RandomNormalMatching::match(const double* M, const bool* maskM, const double* /*NM*/, const double* S, const bool* maskS,
+                                   unsigned int points, double phiMax, const double /*transMax*/, const double resolution)
+{
+  Matrix TBest(3, 3);
+  TBest.setIdentity();
+  std::memset(&_last, 0, sizeof(_last));
+  if (!available()) return TBest;
+  std::vector<int> dSub, dCtrl, dTrials;
+  // the same three streams as PDFMatching: subsampleMask, pickControlSet, srand(time(NULL)) + the trial picks
+  // (RandomNormalMatching.cpp:133, :144, :203, :233)
+  drawRandomMatchingStreams(_seed, _calls, points, (unsigned)_prm.size_control_set, (unsigned)_prm.trials, dSub, dCtrl, dTrials);
+  const tsd_rnmatch_params prm = params(phiMax, resolution);
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(_grid.mutex());
+    rc = tsd_rn_match(_grid.context(), M, reinterpret_cast<const uint8_t*>(maskM), S, reinterpret_cast<const uint8_t*>(maskS),
+                      (int)points, &prm, dSub.data(), dCtrl.data(), dTrials.data(), &_last);
+  }
+  if (rc != TSD_OK) {
+    std::fprintf(stderr, "RandomNormalMatching::match failed (%d): %s\n", rc, tsd_last_error(_grid.context()));
     return TBest;
   }
   TBest.setData(_last.T);

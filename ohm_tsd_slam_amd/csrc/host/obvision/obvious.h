@@ -283,4 +283,30 @@ private:
   tsd_tsdpdf_result _last;
 };
 
+// obvious::RandomNormalMatching (registration/ransacMatching/RandomNormalMatching.{h,cpp}) on obvious::RandomMatching: the
+// pre-registration of registration_mode 1.  The reference constructor's three arguments behind the grid whose device runs it; match() as
+// the reference's plus the number of points.  The front end is PDFMatching's, the scoring and the selection run on the device
+// (tsd_rn_match), the rand() streams are drawn here exactly as PDFMatching draws them.
+class RandomNormalMatching
+{
+public:
+  RandomNormalMatching(TsdGrid& grid, unsigned int trials = 50, double epsThresh = 0.15, unsigned int sizeControlSet = 180);
+  virtual ~RandomNormalMatching() {}
+  /** whether the device library provides tsd_rn_match (a host build linked against a library without it has none) */
+  static bool available();
+  Matrix match(const double* M, const bool* maskM, const double* NM, const double* S, const bool* maskS, unsigned int points,
+               double phiMax = M_PI / 4.0, const double transMax = 1.5, const double resolution = 0.0);
+  /** addition (tests): as TSD_PDFMatching::setSeed */
+  void setSeed(long seed) { _seed = seed; }
+  const tsd_rnmatch_result& lastResult() const { return _last; }
+  /** the parameters of match() as the C ABI takes them */
+  tsd_rnmatch_params params(double phiMax, double resolution) const;
+private:
+  TsdGrid& _grid;
+  tsd_rnmatch_params _prm;
+  long _seed;
+  unsigned long _calls;
+  tsd_rnmatch_result _last;
+};
+
 }  // namespace obvious

@@ -32,6 +32,8 @@ struct PdfFrontEnd {
   double phi_max = 0.0;                    // min(phiMax, pi/2)
   std::vector<int> idxM, idxS;             // extractSamples of both sets (ascending beam indices)
   std::vector<double> control;             // the control set, nC x 2
+  std::vector<int> idxControl;             // the control set's scene indices (pickControlSet's idxControl)
+  std::vector<double> phiM, phiS;          // calcPhi of both sets' normals, beam-indexed (-1e6 where masked)
   std::vector<PdfCandidate> cand;          // in the reference's serial order
   size_t max_cand = 0;                     // the candidate list's allocation (entries)
   // ctx->h_pdf / ctx->d_pdf: [M | S | masks | angles | control | candidates | pose | prob | result | extra]

@@ -245,6 +245,8 @@ struct tsd_ctx {
   // registration_mode 2 (pdfmatch.hip): where the last tsd_pdf_match left its per-candidate values in d_pdf (tsd_debug_pdf_match_scores);
   // any later pre-registration call on this context reuses the buffer and clears the count
   int pdfm_dbg_n = 0; size_t pdfm_dbg_off_u = 0, pdfm_dbg_off_fov = 0;
+  // registration_mode 1 (rnmatch.hip): the same for the last tsd_rn_match (tsd_debug_rn_match_scores)
+  int rnm_dbg_n = 0; size_t rnm_dbg_off_cnt = 0, rnm_dbg_off_max = 0, rnm_dbg_off_err = 0;
 
   // occupancy
   int8_t* d_occ = nullptr;       // persistent map (ThreadGrid::_occGridContent)

@@ -710,11 +710,13 @@ int pdf_front_end(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m
   result->valid_model = 0; result->valid_scene = 0; result->control_points = 0; result->reserved = 0;
   fe.n = n; fe.stage = PdfFrontEnd::FEW_POINTS;
   ctx->pdfm_dbg_n = 0;                                     // (tsd_debug_pdf_match_scores: the buffer is about to be reused)
+  ctx->rnm_dbg_n = 0;                                      // (tsd_debug_rn_match_scores: the same)
   if (n < 3) return TSD_OK;                                // "Model and scene contain too less points" (:53-57)
   const double* M = model_xy_2B; const double* S = scene_xy_2B;
 
   // ---- masks, then the normals of both sets (:63-102)
-  std::vector<double> phiM((size_t)n), phiS((size_t)n);
+  std::vector<double>& phiM = fe.phiM; std::vector<double>& phiS = fe.phiS;
+  phiM.assign((size_t)n, 0.0); phiS.assign((size_t)n, 0.0);
   std::vector<uint8_t> mMp(mask_m, mask_m + n), mSp(mask_s, mask_s + n);
   unsigned valid = 0;
   for (int i = 0; i < n; i++) if (mSp[i]) valid++;
@@ -794,12 +796,14 @@ int pdf_front_end(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m
   if ((int)idxS.size() < nC) nC = (int)idxS.size();
   std::vector<double>& control = fe.control;
   control.assign(2 * (size_t)std::max(nC, 1), 0.0);
+  fe.idxControl.assign((size_t)std::max(nC, 0), 0);
   {
     std::vector<int> tmp = idxS;
     for (int k = 0; k < nC; k++) {
       const unsigned r = (unsigned)draws_control[k] % (unsigned)tmp.size();
       const int idx = tmp[r];
       tmp.erase(tmp.begin() + r);
+      fe.idxControl[k] = idx;
       control[2 * k] = S[2 * idx]; control[2 * k + 1] = S[2 * idx + 1];
     }
   }

@@ -191,7 +191,8 @@ class SlamNode:
         return out
 
     def preregistration(self, robot: int = 0) -> dict | None:
-        """the robot's last pre-registration (registration_mode 2; mode 3 where it ran unfused), None if there was none"""
+        """the robot's last pre-registration (registration_modes 1 and 2; mode 3 where it ran unfused), None if there was none.
+        `prob` is the winning probability in modes 2 and 3 and bestRatio (cntMatch / maxCntMatch of the winner) in mode 1."""
         buf = np.zeros(16)
         if not self.lib.tsd_node_preregistration(self.h, robot, buf.ctypes.data_as(_dp)):
             return None
