@@ -428,6 +428,23 @@ int tsd_occupancy_dev_async(tsd_ctx* ctx, void* occ_dev, int inflate, int inflat
  * image ThreadGrid publishes with every occupancy map (ThreadGrid.cpp:119-131).  Host buffer of 3*width*height. */
 int tsd_color_image(tsd_ctx* ctx, uint8_t* rgb_host, unsigned int width, unsigned int height);
 
+/* ThreadGrid's publication (ThreadGrid.cpp:72-131) as one asynchronous frame: the occupancy map of tsd_occupancy (same rules, same
+ * persistent map, int8 cells*cells) and, unless rgb_host is NULL, the image of tsd_color_image(cells, cells) (RGB8, 3*cells*cells
+ * bytes), built from one read of each tile.  begin returns once the work is enqueued: the frame reflects every push enqueued on the
+ * context before the call, and its copies to the host leave on a stream of their own, so the scans enqueued after it do not wait for
+ * them.  The host buffers must stay valid until tsd_map_frame_wait returns; pinned buffers (tsd_host_alloc) keep begin from blocking.
+ * One frame may be in flight per context: a second begin fails with TSD_E_ARG.  wait blocks until the frame is on the host and
+ * gives its surface count (calcCoords' mapSize / 2). */
+typedef struct {
+  int32_t inflate;              /* use_object_inflation */
+  int32_t inflate_factor;       /* object_inflation_factor */
+} tsd_map_params;
+int tsd_map_frame_begin(tsd_ctx* ctx, const tsd_map_params* params, int8_t* occ_host, uint8_t* rgb_host);
+int tsd_map_frame_wait(tsd_ctx* ctx, int* n_surface);
+/* page-locked host memory for the frame buffers (NULL on failure), and its release */
+void* tsd_host_alloc(uint64_t bytes);
+void tsd_host_free(void* p);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the ctx stream.  Kernel names: "push_classify", "push_update",
  * "push_halo", "raycast", "icp", "occupancy", "tsdpdf". */

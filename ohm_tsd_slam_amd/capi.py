@@ -101,6 +101,11 @@ class RnMatchParams(C.Structure):
                 ("ang_res", C.c_double)]
 
 
+class MapParams(C.Structure):
+    """tsd_map_params"""
+    _fields_ = [("inflate", C.c_int32), ("inflate_factor", C.c_int32)]
+
+
 class RnMatchResult(C.Structure):
     """tsd_rnmatch_result"""
     _fields_ = [("T", C.c_double * 9), ("ratio", C.c_double), ("err_sum", C.c_double), ("cnt_match", C.c_int32),
@@ -217,6 +222,10 @@ ABI = {
     "tsd_debug_sensor_scan_path": (C.c_int, [C.c_void_p]),
     "tsd_debug_set_push_multi": (C.c_int, [C.c_void_p, C.c_int]),
     "tsd_color_image": (C.c_int, [C.c_void_p, _u8p, C.c_uint, C.c_uint]),
+    "tsd_map_frame_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsd_map_frame_wait": (C.c_int, [C.c_void_p, _ip]),
+    "tsd_host_alloc": (C.c_void_p, [C.c_uint64]),
+    "tsd_host_free": (None, [C.c_void_p]),
     "tsd_store_grid_text": (C.c_int, [C.c_void_p, C.c_char_p]),
     "tsd_load_grid_text": (C.c_int, [C.c_void_p, C.c_char_p]),
     "tsd_download_tiles": (C.c_int, [C.c_void_p, _u8p, _dp, _dp, _dp]),
@@ -263,7 +272,7 @@ def load_library(path: str | None = None):
                           ("tsd_gate_params", GateParams), ("tsd_scan_result", ScanResult), ("tsd_grid_digest_t", GridDigest),
                           ("tsd_tsdpdf_params", TsdPdfParams), ("tsd_tsdpdf_result", TsdPdfResult),
                           ("tsd_pdfmatch_params", PdfMatchParams), ("tsd_rnmatch_params", RnMatchParams),
-                          ("tsd_rnmatch_result", RnMatchResult)):
+                          ("tsd_rnmatch_result", RnMatchResult), ("tsd_map_params", MapParams)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -329,6 +338,9 @@ class TsdGridDevice:
         if getattr(self, "h", None):
             self.lib.tsd_destroy(self.h)
             self.h = None
+        for ptr in getattr(self, "_frame_bufs", {}).values():
+            self.lib.tsd_host_free(ptr)
+        self._frame_bufs = {}
 
     def __del__(self):
         try:
@@ -573,6 +585,40 @@ class TsdGridDevice:
         img = np.zeros((height, width, 3), dtype=np.uint8)
         self._check(self.lib.tsd_color_image(self.h, img.ctypes.data_as(_u8p), width, height), "tsd_color_image")
         return img
+
+    def _pinned(self, name, nbytes):
+        """a page-locked host buffer kept by the wrapper (tsd_host_alloc), as a numpy view"""
+        bufs = self.__dict__.setdefault("_frame_bufs", {})
+        if name not in bufs:
+            ptr = self.lib.tsd_host_alloc(nbytes)
+            if not ptr:
+                raise TsdError(f"tsd_host_alloc({nbytes}) failed")
+            bufs[name] = ptr
+        return np.ctypeslib.as_array(C.cast(bufs[name], _u8p), shape=(nbytes,))
+
+    def map_frame_begin(self, inflate=False, factor=2, image=True):
+        """tsd_map_frame_begin into the wrapper's pinned buffers: returns once the frame is enqueued"""
+        n = self.cells * self.cells
+        prm = MapParams(int(bool(inflate)), int(factor))
+        occ = self._pinned("occ", n)
+        rgb = self._pinned("rgb", 3 * n) if image else None
+        self._check(self.lib.tsd_map_frame_begin(self.h, C.byref(prm), occ.ctypes.data, None if rgb is None else rgb.ctypes.data),
+                    "tsd_map_frame_begin")
+        self._frame_image = bool(image)          # (only once begun: a refused begin leaves the frame in flight as it was)
+
+    def map_frame_wait(self):
+        """tsd_map_frame_wait: (occ (cells, cells) int8, rgb (cells, cells, 3) uint8 or None, n_surface), copied out of the pinned buffers"""
+        ns = C.c_int(0)
+        self._check(self.lib.tsd_map_frame_wait(self.h, C.byref(ns)), "tsd_map_frame_wait")
+        n = self.cells * self.cells
+        occ = self._pinned("occ", n).view(np.int8).reshape(self.cells, self.cells).copy()
+        rgb = self._pinned("rgb", 3 * n).reshape(self.cells, self.cells, 3).copy() if self._frame_image else None
+        return occ, rgb, ns.value
+
+    def map_frame(self, inflate=False, factor=2, image=True):
+        """ThreadGrid's publication in one frame (tsd_map_frame_begin + _wait): (occ, rgb or None, n_surface)"""
+        self.map_frame_begin(inflate, factor, image)
+        return self.map_frame_wait()
 
     def push_stats_total(self, reset=False):
         st = PushStats()

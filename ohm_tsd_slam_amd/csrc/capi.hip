@@ -467,6 +467,10 @@ void tsd_destroy(tsd_ctx* ctx)
   if (ctx->stream_io) { hipStreamSynchronize(ctx->stream_io); hipStreamDestroy(ctx->stream_io); }
   if (ctx->ev_io) hipEventDestroy(ctx->ev_io);
   if (ctx->d_img) hipFree(ctx->d_img);
+  if (ctx->d_frame) hipFree(ctx->d_frame);
+  if (ctx->h_frame_count) hipHostFree(ctx->h_frame_count);
+  if (ctx->ev_frame) hipEventDestroy(ctx->ev_frame);
+  if (ctx->ev_frame_done) hipEventDestroy(ctx->ev_frame_done);
   if (ctx->d_pdf) hipFree(ctx->d_pdf);
   if (ctx->h_pdf) hipHostFree(ctx->h_pdf);
   if (ctx->stream) hipStreamDestroy(ctx->stream);

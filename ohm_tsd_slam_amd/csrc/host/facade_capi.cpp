@@ -1,8 +1,9 @@
 // facade_capi.cpp -- a flat C surface over the C++ facade so that the Python test / bench drivers can
-// exercise ThreadLocalize / ThreadMapping exactly as SlamNode wires them (SlamNode.cpp:27-129): one
-// TsdGrid, one ThreadMapping, N ThreadLocalize sharing them, laser callbacks per robot.
+// exercise ThreadLocalize / ThreadMapping / ThreadGrid exactly as SlamNode wires them (SlamNode.cpp:27-129): one
+// TsdGrid, one ThreadMapping, one ThreadGrid woken every occ_grid_time_interval, N ThreadLocalize sharing them, laser callbacks per robot.
 #include <atomic>
 #include <chrono>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -11,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "ThreadGrid.h"
 #include "ThreadLocalize.h"
 #include "ThreadMapping.h"
 
@@ -21,6 +23,12 @@ struct tsd_node
   std::shared_ptr<rclcpp::Node> node;
   obvious::TsdGrid* grid = nullptr;
   ThreadMapping* mapping = nullptr;
+  ThreadGrid* gridThread = nullptr;
+  // SlamNode::_timer (SlamNode.cpp:128, :154-157): wakes the ThreadGrid every occ_grid_time_interval
+  std::thread timer;
+  std::mutex timerMutex;
+  std::condition_variable timerCond;
+  bool timerStop = false;
   std::vector<ThreadLocalize*> localizers;
   std::vector<uint64_t> submitted;
   bool synchronous = false;
@@ -54,8 +62,7 @@ static void declare_node_parameters(const std::shared_ptr<rclcpp::Node>& node)
   node->declare_parameter("truncation_radius", 3);
   node->declare_parameter("occ_grid_time_interval", 2.0);
   node->declare_parameter("tf_map_frame", std::string("map"));
-  // ThreadGrid's (ThreadGrid.cpp:42-47): the occupancy thread itself is out of scope, its extraction kernels (row N1) take
-  // these as arguments; declared so that the shipped YAMLs (config/single-laser.yaml) load as they are
+  // ThreadGrid's (ThreadGrid.cpp:42-47), declared here once: ThreadGrid reads them
   node->declare_parameter("pub_tsd_color_map", true);
   node->declare_parameter("object_inflation_factor", 2);
   node->declare_parameter("use_object_inflation", false);
@@ -121,6 +128,7 @@ int tsd_node_initialize(tsd_node* n, int device)
     return TSD_E_NODEVICE;
   n->grid->setMaxTruncation(truncationRadius * cellSize);
   n->mapping = new ThreadMapping(n->grid);
+  n->gridThread = new ThreadGrid(n->grid, node, xOffset, yOffset);
   if(robotNbr == 1)
   {
     n->localizers.push_back(new ThreadLocalize(n->grid, n->mapping, node, "", xOffset, yOffset));
@@ -136,6 +144,20 @@ int tsd_node_initialize(tsd_node* n, int device)
     }
   }
   n->submitted.assign(n->localizers.size(), 0);
+  const double interval = node->get_parameter("occ_grid_time_interval").as_double();
+  if(interval > 0.0)
+  {
+    const auto period = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::duration<double>(interval));
+    n->timer = std::thread([n, period] {
+      std::unique_lock<std::mutex> lk(n->timerMutex);
+      auto next = std::chrono::steady_clock::now() + period;
+      while(!n->timerCond.wait_until(lk, next, [n] { return n->timerStop; }))
+      {
+        n->gridThread->unblock();            // SlamNode::timedGridPub
+        next += period;
+      }
+    });
+  }
   // several robots on one grid: their scans go through the grid's dispatcher as batched launches (TSD_NO_BATCH: the split
   // scan on one stream per robot instead; TSD_BATCH_SLOTS: batch slots used in turn, default 2 -- A/B switches for measurements)
   if(n->localizers.size() > 1 && !std::getenv("TSD_NO_CONCURRENT") && !std::getenv("TSD_NO_BATCH"))
@@ -322,13 +344,72 @@ int tsd_node_set_transform(tsd_node* n, int robot, const char* parent, const cha
   return n->localizers[robot]->tfBuffer()->setTransform(t, "tsd_node_set_transform", true) ? 0 : -1;
 }
 
+// ThreadGrid: one publication now, on the caller's thread (what a timer wake-up does); TSD_OK or the frame's error
+int tsd_node_publish_map(tsd_node* n)
+{
+  if(!n || !n->gridThread)
+    return TSD_E_ARG;
+  return n->gridThread->publish();
+}
+
+unsigned long long tsd_node_map_frames(tsd_node* n) { return (n && n->gridThread) ? n->gridThread->frames() : 0; }
+
+// an OccupancyGrid as flat values: resolution, width, height, origin x, y, z, qx, qy, qz, qw, stamp [ns], map_load_time [ns]
+// (12 doubles); data (width * height) when data_out is given; header.frame_id into frame_id
+static void map_out(const nav_msgs::msg::OccupancyGrid& m, int8_t* data_out, double* out12, char* frame_id, int cap)
+{
+  auto ns = [](const builtin_interfaces::msg::Time& t) { return (double)t.sec * 1e9 + (double)t.nanosec; };
+  out12[0] = m.info.resolution; out12[1] = m.info.width; out12[2] = m.info.height;
+  out12[3] = m.info.origin.position.x; out12[4] = m.info.origin.position.y; out12[5] = m.info.origin.position.z;
+  out12[6] = m.info.origin.orientation.x; out12[7] = m.info.origin.orientation.y; out12[8] = m.info.origin.orientation.z;
+  out12[9] = m.info.origin.orientation.w; out12[10] = ns(m.header.stamp); out12[11] = ns(m.info.map_load_time);
+  if(data_out && !m.data.empty())
+    std::memcpy(data_out, m.data.data(), m.data.size());
+  if(frame_id && cap > 0)
+    std::snprintf(frame_id, (size_t)cap, "%s", m.header.frame_id.c_str());
+}
+
+// last message on <node>/map (map_out layout); returns the publish count
+unsigned long long tsd_node_map_msg(tsd_node* n, int8_t* data_out, double* out12, char* frame_id, int cap)
+{
+  auto pub = n->gridThread->gridPublisher();
+  map_out(pub->last(), data_out, out12, frame_id, cap);
+  return pub->count();
+}
+
+// <node>/get_map (ThreadGrid::getMapServCallBack): the last map with a fresh stamp (map_out layout); 1 if the service answered
+int tsd_node_get_map(tsd_node* n, int8_t* data_out, double* out12, char* frame_id, int cap)
+{
+  auto req = std::make_shared<nav_msgs::srv::GetMap::Request>();
+  auto res = std::make_shared<nav_msgs::srv::GetMap::Response>();
+  if(!n->gridThread->getMapServCallBack(req, res))
+    return 0;
+  map_out(res->map, data_out, out12, frame_id, cap);
+  return 1;
+}
+
+// last message on <node>/map/image: height, width, step, is_bigendian, stamp [ns] (5 doubles); data (step * height) when
+// data_out is given; "encoding|frame_id" into text.  Returns the publish count.
+unsigned long long tsd_node_map_image_msg(tsd_node* n, uint8_t* data_out, double* out5, char* text, int cap)
+{
+  auto pub = n->gridThread->imagePublisher();
+  const sensor_msgs::msg::Image m = pub->last();
+  out5[0] = m.height; out5[1] = m.width; out5[2] = m.step; out5[3] = m.is_bigendian;
+  out5[4] = (double)m.header.stamp.sec * 1e9 + (double)m.header.stamp.nanosec;
+  if(data_out && !m.data.empty())
+    std::memcpy(data_out, m.data.data(), m.data.size());
+  if(text && cap > 0)
+    std::snprintf(text, (size_t)cap, "%s|%s", m.encoding.c_str(), m.header.frame_id.c_str());
+  return pub->count();
+}
+
 tsd_ctx* tsd_node_grid_ctx(tsd_node* n) { return n->grid ? n->grid->context() : nullptr; }
 // the facade's grid mutex (obvious::TsdGrid::mutex()): whoever talks to the context through the raw tsd_* ABI while the
 // node's worker threads may be running takes it around each call, like the facade's own classes do
 void tsd_node_grid_lock(tsd_node* n) { if(n && n->grid) n->grid->mutex().lock(); }
 void tsd_node_grid_unlock(tsd_node* n) { if(n && n->grid) n->grid->mutex().unlock(); }
 
-// SlamNode::~SlamNode shutdown order (SlamNode.cpp:131-152): terminate + join every thread
+// SlamNode::~SlamNode shutdown order (SlamNode.cpp:131-152): localisers, then ThreadGrid (its timer first), then the mapper
 void tsd_node_destroy(tsd_node* n)
 {
   if(!n)
@@ -338,6 +419,21 @@ void tsd_node_destroy(tsd_node* n)
     l->terminateThread();
     while(!l->alive(1)) {}
     delete l;
+  }
+  if(n->timer.joinable())
+  {
+    {
+      std::lock_guard<std::mutex> lk(n->timerMutex);
+      n->timerStop = true;
+    }
+    n->timerCond.notify_all();
+    n->timer.join();
+  }
+  if(n->gridThread)
+  {
+    n->gridThread->terminateThread();
+    while(!n->gridThread->alive(1)) {}
+    delete n->gridThread;
   }
   if(n->mapping)
   {

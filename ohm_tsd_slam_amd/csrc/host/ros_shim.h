@@ -1,4 +1,4 @@
-// ros_shim.h -- the slice of the ROS 2 API that ThreadLocalize / ThreadMapping touch
+// ros_shim.h -- the slice of the ROS 2 API that ThreadLocalize / ThreadMapping / ThreadGrid touch
 // (SURVEY Appendix D).  With rclcpp available the real headers are used; on boxes without ROS
 // (this image, the GPU box) a plain-C++ stand-in with the same spelling is compiled instead:
 // parameters are a string-keyed map, publishers keep the last message and a counter, the tf
@@ -17,12 +17,17 @@
 #include <tf2_ros/buffer.h>
 #include <tf2/LinearMath/Transform.h>
 #include <tf2_geometry_msgs/tf2_geometry_msgs.hpp>
+#include <nav_msgs/msg/occupancy_grid.hpp>
+#include <nav_msgs/srv/get_map.hpp>
+#include <sensor_msgs/msg/image.hpp>
+#include <sensor_msgs/image_encodings.hpp>
 #else
 #define OHM_TSD_SLAM_HAVE_ROS 0
 #include <chrono>
 #include <cstdint>
 #include <map>
 #include <cmath>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -56,7 +61,56 @@ struct Transform { Vector3 translation; Quaternion rotation; };
 struct TransformStamped { std_msgs::msg::Header header; std::string child_frame_id; Transform transform; };
 } }
 
+// ThreadGrid's messages and service (ThreadGrid.cpp:16-142): nav_msgs/OccupancyGrid, sensor_msgs/Image, nav_msgs/GetMap
+namespace nav_msgs { namespace msg {
+struct MapMetaData {
+  builtin_interfaces::msg::Time map_load_time;
+  float resolution = 0.f;
+  uint32_t width = 0, height = 0;
+  geometry_msgs::msg::Pose origin;
+};
+struct OccupancyGrid { std_msgs::msg::Header header; MapMetaData info; std::vector<int8_t> data; };
+} namespace srv {
+struct GetMap {
+  struct Request {};
+  struct Response { nav_msgs::msg::OccupancyGrid map; };
+};
+} }
+namespace sensor_msgs { namespace msg {
+struct Image {
+  std_msgs::msg::Header header;
+  uint32_t height = 0, width = 0;
+  std::string encoding;
+  uint8_t is_bigendian = 0;
+  uint32_t step = 0;
+  std::vector<uint8_t> data;
+};
+} namespace image_encodings {
+static const std::string RGB8 = "rgb8";
+} }
+
 namespace rclcpp {
+
+// QoS settings are accepted and ignored (a stand-in publisher has no transport)
+struct QoS {
+  explicit QoS(size_t /*depth*/) {}
+  QoS& reliable() { return *this; }
+  QoS& best_effort() { return *this; }
+  QoS& transient_local() { return *this; }
+};
+
+// a service keeps its callback; call() is what a client's request does
+template <class SrvT>
+class Service {
+public:
+  using Callback = std::function<bool(const std::shared_ptr<typename SrvT::Request>, std::shared_ptr<typename SrvT::Response>)>;
+  Service(std::string name, Callback cb) : _name(std::move(name)), _cb(std::move(cb)) {}
+  bool call(const std::shared_ptr<typename SrvT::Request>& req, std::shared_ptr<typename SrvT::Response>& res) { return _cb(req, res); }
+  const std::string& name() const { return _name; }
+private:
+  std::string _name;
+  Callback _cb;
+};
 
 struct Time { int64_t ns = 0; operator builtin_interfaces::msg::Time() const { return {(int32_t)(ns / 1000000000LL), (uint32_t)(ns % 1000000000LL)}; } };
 struct Clock {
@@ -121,6 +175,14 @@ public:
   template <class MsgT>
   std::shared_ptr<Publisher<MsgT>> create_publisher(const std::string& topic, int /*qos*/ = 1) {
     return std::make_shared<Publisher<MsgT>>(topic);
+  }
+  template <class MsgT>
+  std::shared_ptr<Publisher<MsgT>> create_publisher(const std::string& topic, const QoS&) {
+    return std::make_shared<Publisher<MsgT>>(topic);
+  }
+  template <class SrvT, class CallbackT>
+  std::shared_ptr<Service<SrvT>> create_service(const std::string& name, CallbackT&& cb) {
+    return std::make_shared<Service<SrvT>>(name, typename Service<SrvT>::Callback(std::forward<CallbackT>(cb)));
   }
 private:
   static Parameter::Value to_value(bool v) { return v; }

@@ -257,6 +257,12 @@ struct tsd_ctx {
   int8_t* d_occ_out = nullptr;   // tsd_occupancy's device staging (allocated on first use, kept)
   hipStream_t stream_io = nullptr; hipEvent_t ev_io = nullptr;   // ... and the stream its copy to the host leaves on (created on first use)
   uint8_t* d_img = nullptr; size_t img_bytes = 0;   // tsd_color_image's (coordinate tables + image), grown on demand
+  // ThreadGrid's publication (tsd_map_frame_begin / _wait, map_publish.hip): at most one frame in flight
+  char* d_frame = nullptr; size_t frame_bytes = 0;  // device staging: coordinate tables, surface count, map, image (kept, grown on demand)
+  int* h_frame_count = nullptr;                     // pinned: the frame's surface count
+  hipEvent_t ev_frame = nullptr;                    // on `stream`: the frame's kernels are done
+  hipEvent_t ev_frame_done = nullptr;               // on stream_io: the frame's copies to the host are done
+  bool frame_inflight = false;
 
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;
@@ -486,6 +492,10 @@ IcpSeedArgs icp_batch_seed_args(const tsd_ctx* ctx, void* buf, int beams, int ba
 int launch_calibrate(tsd_ctx* ctx, double* t, double* w, size_t n);
 int launch_occupancy(tsd_ctx* ctx, int8_t* d_out, int inflate, int inflate_factor);
 size_t occ_heads_bytes();
+// the list heads of the next extraction (cur) and the set it clears for the one after (next)
+struct OccHeads { unsigned int* cur; unsigned int* next; };
+OccHeads next_occ_heads(tsd_ctx* ctx);
+int launch_occ_mark(tsd_ctx* ctx, int8_t* d_out, int* d_count, int inflate, int inflate_factor, const unsigned int* heads);
 int launch_color_image(tsd_ctx* ctx, const double* d_px, const double* d_py, unsigned width, unsigned height, uint8_t* d_image);
 size_t icp_lds_bytes();
 

@@ -41,6 +41,11 @@ HOST_ABI = {
     "tsd_node_play": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_fp), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_longlong, C.c_longlong]),
     "tsd_node_batch_stats": (None, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "tsd_node_grid_ctx": (C.c_void_p, [C.c_void_p]),
+    "tsd_node_publish_map": (C.c_int, [C.c_void_p]),
+    "tsd_node_map_frames": (C.c_ulonglong, [C.c_void_p]),
+    "tsd_node_map_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
+    "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
+    "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_grid_lock": (None, [C.c_void_p]),
     "tsd_node_grid_unlock": (None, [C.c_void_p]),
     "tsd_node_destroy": (None, [C.c_void_p]),
@@ -221,6 +226,53 @@ class SlamNode:
         rc = self.lib.tsd_node_set_transform(self.h, robot, parent.encode(), child.encode(), t.ctypes.data_as(_dp), q.ctypes.data_as(_dp))
         if rc != 0:
             raise ValueError("tsd_node_set_transform refused %s -> %s" % (parent, child))
+
+    # ---- ThreadGrid (ThreadGrid.cpp:16-142): <node>/map, <node>/map/image, <node>/get_map
+    def publish_map(self):
+        """one ThreadGrid publication now, on the caller's thread (what every occ_grid_time_interval wake-up does)"""
+        rc = self.lib.tsd_node_publish_map(self.h)
+        if rc != 0:
+            raise capi.TsdError(f"tsd_node_publish_map failed ({rc})")
+
+    def map_frames(self) -> int:
+        """ThreadGrid publications so far (timer wake-ups and publish_map())"""
+        return int(self.lib.tsd_node_map_frames(self.h))
+
+    def _map_dict(self, fn):
+        info = np.zeros(12)
+        frame = C.create_string_buffer(256)
+        fn(None, info.ctypes.data_as(_dp), frame, 256)
+        data = np.zeros(int(info[1]) * int(info[2]), dtype=np.int8)
+        ret = fn(data.ctypes.data, info.ctypes.data_as(_dp), frame, 256)
+        return ret, {"resolution": float(info[0]), "width": int(info[1]), "height": int(info[2]),
+                     "origin_position": info[3:6].copy(), "origin_orientation_xyzw": info[6:10].copy(),
+                     "stamp_ns": int(info[10]), "map_load_time_ns": int(info[11]), "frame_id": frame.value.decode(),
+                     "data": data.reshape(int(info[2]), int(info[1]))}
+
+    def map_msg(self) -> dict:
+        """the last nav_msgs/OccupancyGrid on <node>/map (data as (height, width) int8) and its publish count"""
+        n, m = self._map_dict(lambda d, i, f, c: self.lib.tsd_node_map_msg(self.h, d, i, f, c))
+        m["count"] = int(n)
+        return m
+
+    def get_map(self) -> dict:
+        """the get_map service's answer: the last map with a fresh stamp"""
+        ok, m = self._map_dict(lambda d, i, f, c: self.lib.tsd_node_get_map(self.h, d, i, f, c))
+        if not ok:
+            raise capi.TsdError("get_map refused")
+        return m
+
+    def map_image_msg(self) -> dict:
+        """the last sensor_msgs/Image on <node>/map/image (data as (height, width, 3) uint8) and its publish count"""
+        info = np.zeros(5)
+        text = C.create_string_buffer(256)
+        self.lib.tsd_node_map_image_msg(self.h, None, info.ctypes.data_as(_dp), text, 256)
+        h, w, step = int(info[0]), int(info[1]), int(info[2])
+        data = np.zeros(step * h, dtype=np.uint8)
+        n = self.lib.tsd_node_map_image_msg(self.h, data.ctypes.data, info.ctypes.data_as(_dp), text, 256)
+        enc, frame = text.value.decode().split("|")
+        return {"height": h, "width": w, "step": step, "is_bigendian": int(info[3]), "stamp_ns": int(info[4]),
+                "encoding": enc, "frame_id": frame, "data": data.reshape(h, w, 3) if h and w else data, "count": int(n)}
 
     def grid(self) -> "GridView":
         return GridView(self.lib.tsd_node_grid_ctx(self.h), self)
