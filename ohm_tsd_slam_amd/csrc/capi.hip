@@ -158,6 +158,36 @@ void fill_icp_args(IcpArgs& a, const double pose33[9], const tsd_icp_params* p)
   a.Tinit_dev = nullptr;
 }
 
+IcpArgs sensor_icp_args(const tsd_sensor* s, const tsd_icp_params* p)
+{
+  IcpArgs a; std::memset(&a, 0, sizeof(a));
+  const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  fill_icp_args(a, ident, p);
+  a.beams = s->beams; a.ccw = s->ccw ? 1 : 0;
+  return a;
+}
+ScanPostArgs sensor_post_args(const tsd_sensor* s, unsigned long long seq, const tsd_gate_params& gates)
+{
+  const GridDev& g = s->ctx->grid;
+  ScanPostArgs sp; std::memset(&sp, 0, sizeof(sp));
+  sp.st = s->d_state; sp.rays = s->d_rays; sp.out = s->d_result; sp.seq = seq; sp.beams = s->beams;
+  sp.gmin_x = g.min_x; sp.gmax_x = g.max_x; sp.gmin_y = g.min_y; sp.gmax_y = g.max_y;
+  sp.gates = GateArgs{gates.reg_trs_max, gates.reg_sin_rot_max, gates.trs_min, gates.rot_min};
+  return sp;
+}
+PushArgs sensor_push_launch_args(const tsd_sensor* s)
+{
+  PushArgs pa; std::memset(&pa, 0, sizeof(pa));
+  pa.beams = s->beams; pa.max_range = s->max_range;
+  return pa;
+}
+RaycastArgs sensor_raycast_launch_args(const tsd_sensor* s)
+{
+  RaycastArgs ra; std::memset(&ra, 0, sizeof(ra));
+  ra.beams = s->beams;
+  return ra;
+}
+
 void fill_raycast_args(const tsd_ctx* ctx, RaycastArgs& a, const double pose33[9], int beams,
                               double min_range, double max_range)
 {
@@ -245,12 +275,9 @@ bool host_saw_event(hipEvent_t ev, int us)
   }
 }
 
-ConcTiming g_conc_timing;
-ConcTiming g_scan_timing;      // the same for tsd_scan (one robot): where the host time of a scan goes
-ConcTiming g_stage_timing;     // ... and of the staging of a scan (acquire, host copy, hipMemcpyAsync, records, tables)
-unsigned long long g_scan_lap_max[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-unsigned long long g_scan_lap_max_at[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-unsigned long long g_scan_last_return = 0;
+LapTimes g_conc_timing;
+LapTimes g_scan_timing;
+LapTimes g_stage_timing;
 
 // every grid WRITE enqueued on the context's stream goes behind the ray casts the concurrent multi-robot path has in
 // flight on the sensors' own streams (no-op without such sensors)
@@ -260,13 +287,13 @@ int wait_for_readers(tsd_ctx* ctx)
   // for: earlier ones are ordered through that write already.  A sensor whose thread has taken its ticket but not yet
   // issued the event record (a few microseconds) is waited for on the host.
   for (tsd_sensor* t : ctx->sensors) {
-    if (!t->rc_event_valid || t->rc_ticket <= ctx->last_push_ticket) continue;
-    while (!__atomic_load_n(&t->rc_recorded, __ATOMIC_ACQUIRE)) {
+    if (!t->split.rc_event_valid || t->split.rc_ticket <= ctx->last_push_ticket) continue;
+    while (!__atomic_load_n(&t->split.rc_recorded, __ATOMIC_ACQUIRE)) {
 #if defined(__x86_64__)
       __builtin_ia32_pause();
 #endif
     }
-    TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, t->ev_rc_done, 0));
+    TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, t->split.ev_rc_done, 0));
   }
   // (the ray casts of the batched path run on the context's stream itself: ordered by it)
   ctx->last_push_ticket = ctx->ticket;
@@ -411,36 +438,31 @@ tsd_ctx* tsd_create(int device, int map_size_log2, double cell_size, double max_
   return ctx;
 }
 
+// TSD_CONC_TIMING: one accumulator's laps, averaged per call (and, `longest`, each lap's longest single one with the call it was seen in)
+static void print_laps(const LapTimes& t, const char* head, const char* const* names, int laps, bool longest)
+{
+  if (!t.on || !t.n) return;
+  const double n = (double)t.n;
+  fprintf(stderr, head, n);
+  for (int i = 0; i < laps; i++) fprintf(stderr, " %s %.1f", names[i], 1e-3 * (double)t.ns[i] / n);
+  if (longest) fprintf(stderr, "\nTSD_CONC_TIMING longest single lap (us @ call):");
+  for (int i = 0; longest && i < laps; i++) fprintf(stderr, " %s %.0f @%llu", names[i], 1e-3 * (double)t.max[i], t.max_at[i].load());
+  fprintf(stderr, "\n");
+}
+
 void tsd_destroy(tsd_ctx* ctx)
 {
   if (!ctx) return;
-  if (g_stage_timing.on && g_stage_timing.n) {
-    const double n = (double)g_stage_timing.n;
-    static const char* names[8] = {"acquire", "host copy", "hipMemcpyAsync", "records", "tables launch", "-", "-", "-"};
-    fprintf(stderr, "TSD_CONC_TIMING stagings %.0f; host us each:", n);
-    for (int i = 0; i < 5; i++) fprintf(stderr, " %s %.1f", names[i], 1e-3 * (double)g_stage_timing.ns[i] / n);
-    fprintf(stderr, "\n");
-  }
-  if (g_scan_timing.on && g_scan_timing.n) {
-    const double n = (double)g_scan_timing.n;
-    static const char* names[8] = {"caller (between calls)", "stage+copy+tables", "ray cast", "wait copy + icp launch", "push launches", "next ray cast", "wait result", "result"};
-    fprintf(stderr, "TSD_CONC_TIMING tsd_scan calls %.0f; host us per scan:", n);
-    for (int i = 0; i < 8; i++) fprintf(stderr, " %s %.1f", names[i], 1e-3 * (double)g_scan_timing.ns[i] / n);
-    fprintf(stderr, "\nTSD_CONC_TIMING longest single lap (us @ call):");
-    for (int i = 0; i < 8; i++) fprintf(stderr, " %s %.0f @%llu", names[i], 1e-3 * (double)g_scan_lap_max[i], g_scan_lap_max_at[i]);
-    fprintf(stderr, "\n");
-  }
-  if (g_conc_timing.on && g_conc_timing.n) {
-    const double n = (double)g_conc_timing.n;
-    static const char* names[8] = {"begin:copy+tables", "begin:lock", "begin:ordered", "begin:raycast+icp", "wait", "finish:lock", "finish:push", "finish:result"};
-    fprintf(stderr, "TSD_CONC_TIMING scans %.0f; host us per scan:", n);
-    for (int i = 0; i < 8; i++) fprintf(stderr, " %s %.1f", names[i], 1e-3 * (double)g_conc_timing.ns[i] / n);
-    fprintf(stderr, "\n");
-  }
+  static const char* const stage_laps[5] = {"acquire", "host copy", "hipMemcpyAsync", "records", "tables launch"};
+  static const char* const scan_laps[8] = {"caller (between calls)", "stage+copy+tables", "ray cast", "wait copy + icp launch", "push launches", "next ray cast", "wait result", "result"};
+  static const char* const conc_laps[8] = {"begin:copy+tables", "begin:lock", "begin:ordered", "begin:raycast+icp", "wait", "finish:lock", "finish:push", "finish:result"};
+  print_laps(g_stage_timing, "TSD_CONC_TIMING stagings %.0f; host us each:", stage_laps, 5, false);
+  print_laps(g_scan_timing, "TSD_CONC_TIMING tsd_scan calls %.0f; host us per scan:", scan_laps, 8, true);
+  print_laps(g_conc_timing, "TSD_CONC_TIMING scans %.0f; host us per scan:", conc_laps, 8, false);
   hipSetDevice(ctx->device);
   // sensors and batch slots that outlive their grid are detached: their own destroy calls then only free what is theirs
   for (tsd_batch* bt : ctx->batches) { if (bt->stream) hipStreamSynchronize(bt->stream); bt->ctx = nullptr; }
-  for (tsd_sensor* sn : ctx->sensors) { if (sn->stream) hipStreamSynchronize(sn->stream); sn->ctx = nullptr; }
+  for (tsd_sensor* sn : ctx->sensors) { if (sn->split.stream) hipStreamSynchronize(sn->split.stream); sn->ctx = nullptr; }
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
   drain_timers(ctx);
   GridDev& g = ctx->grid;

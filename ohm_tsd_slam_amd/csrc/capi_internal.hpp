@@ -34,37 +34,37 @@ inline unsigned long long now_ns()
   return (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// TSD_CONC_TIMING=1: host time spent inside the split-scan calls (wall clock, summed over all threads), printed by
-// tsd_destroy.  Diagnostic only.
-struct ConcTiming {
-  std::atomic<unsigned long long> ns[8];
-  std::atomic<unsigned long long> n;
+// TSD_CONC_TIMING=1: host time spent inside the scan calls, lap by lap (wall clock, summed over all threads), printed by
+// tsd_destroy.  Diagnostic only: unset, a lap is one test of `on` and no clock read.
+struct LapTimes {
+  std::atomic<unsigned long long> ns[8], max[8], max_at[8];   // per lap: sum, the longest single one and the call it was seen in
+  std::atomic<unsigned long long> n;                          // calls
+  unsigned long long last_return = 0;                         // (g_scan_timing: when the previous tsd_scan_collect returned)
   bool on;
-  ConcTiming() : on(getenv("TSD_CONC_TIMING") != nullptr) { for (auto& v : ns) v = 0; n = 0; }
+  LapTimes() : on(getenv("TSD_CONC_TIMING") != nullptr) { for (int i = 0; i < 8; i++) ns[i] = max[i] = max_at[i] = 0; n = 0; }
 };
-extern ConcTiming g_conc_timing;
-extern ConcTiming g_scan_timing;      // the same for tsd_scan (one robot): where the host time of a scan goes
-extern ConcTiming g_stage_timing;     // ... and of the staging of a scan (acquire, host copy, hipMemcpyAsync, records, tables)
-struct ConcLap {
+extern LapTimes g_conc_timing;       // the split scan (tsd_scan_begin / _wait / _finish)
+extern LapTimes g_scan_timing;       // tsd_scan (one robot): where the host time of a scan goes
+extern LapTimes g_stage_timing;      // ... and of the staging of a scan (acquire, host copy, hipMemcpyAsync, records, tables)
+struct Lap {
+  LapTimes& acc;
   unsigned long long t;
-  ConcLap() : t(g_conc_timing.on ? now_ns() : 0) {}
-  void lap(int i) { if (g_conc_timing.on) { const unsigned long long u = now_ns(); g_conc_timing.ns[i] += u - t; t = u; } }
-};
-extern unsigned long long g_scan_lap_max[8];
-extern unsigned long long g_scan_lap_max_at[8];
-struct ScanLap {
-  unsigned long long t;
-  ScanLap() : t(g_scan_timing.on ? now_ns() : 0) {}
+  explicit Lap(LapTimes& a) : acc(a), t(a.on ? now_ns() : 0) {}
   void lap(int i)
   {
-    if (!g_scan_timing.on) return;
-    const unsigned long long u = now_ns();
-    g_scan_timing.ns[i] += u - t;
-    if (u - t > g_scan_lap_max[i]) { g_scan_lap_max[i] = u - t; g_scan_lap_max_at[i] = (unsigned long long)g_scan_timing.n; }
-    t = u;
+    if (!acc.on) return;
+    const unsigned long long u = now_ns(), d = u - t;
+    acc.ns[i] += d; t = u;
+    if (d > acc.max[i]) { acc.max[i] = d; acc.max_at[i] = acc.n.load(); }
   }
 };
-extern unsigned long long g_scan_last_return;
 
+// What a scan's kernels are given, derived from its sensor (zeroed first: the bytes that reach the device are defined ones).
+// sensor_post_args leaves push_copy / publish_done, which are what differs between the scan paths, to the caller; the launch-sizing
+// arguments carry what a launcher needs on the host (the rest is read on the device, from the sensor's state).
+IcpArgs sensor_icp_args(const tsd_sensor* s, const tsd_icp_params* p);
+ScanPostArgs sensor_post_args(const tsd_sensor* s, unsigned long long seq, const tsd_gate_params& gates);
+PushArgs sensor_push_launch_args(const tsd_sensor* s);          // beams: LDS size of the launch; max_range: its tile window
+RaycastArgs sensor_raycast_launch_args(const tsd_sensor* s);    // beams: grid size of the launch
 
 }  // namespace tsd

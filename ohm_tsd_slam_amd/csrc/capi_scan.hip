@@ -10,6 +10,28 @@
 
 using namespace tsd;
 
+// Waits on the host until `arrived()` says yes: spins with pause (`nudge(spins)` after every miss is the caller's), and after
+// 4 000 000 spins -- about a tenth of a second: something is wrong -- falls back to a real wait for `stream` and asks once more.
+// false: it never arrived (*e_sync: what the stream's synchronisation said).
+template <class Arrived, class Nudge>
+static bool wait_arrival(Arrived arrived, hipStream_t stream, Nudge nudge, hipError_t* e_sync = nullptr)
+{
+  unsigned long long spins = 0;
+  while (!arrived()) {
+    nudge(++spins);
+    if (spins > 4000000ull) {
+      const hipError_t e = hipStreamSynchronize(stream);
+      if (e_sync) *e_sync = e;
+      return e == hipSuccess && arrived();
+    }
+#if defined(__x86_64__)
+    __builtin_ia32_pause();
+#endif
+  }
+  return true;
+}
+static void no_nudge(unsigned long long) {}
+
 extern "C" {
 // ---------------------------------------------------------------------------------- fused scan path
 // Can this process store into fine-grained device memory of `device` through the PCIe BAR, and does a kernel launched right behind the
@@ -38,7 +60,6 @@ static int bar_verify_mode()
   static const int mode = [] { const char* e = std::getenv("TSD_SCAN_BAR_VERIFY"); return e && (*e == '1' || *e == '2') ? *e - '0' : 0; }();
   return mode;
 }
-static bool bar_verify_requested() { return bar_verify_mode() != 0; }
 static bool host_writes_device_memory(tsd_ctx* ctx)
 {
   const int device = ctx->device;
@@ -52,7 +73,7 @@ static bool host_writes_device_memory(tsd_ctx* ctx)
   if (const char* e = std::getenv("TSD_SCAN_PINNED")) if (*e == '1') return false;
   int large_bar = 0;
   if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device) != hipSuccess || !large_bar) { (void)hipGetLastError(); return false; }
-  constexpr int kWords = (TSD_MAX_BEAMS * 10 + 64 + 7) / 8;      // a scan buffer's size
+  constexpr int kWords = (int)((scan_alloc_bytes(TSD_MAX_BEAMS) + 7) / 8);      // a scan buffer's size
   constexpr int kRounds = 6;
   unsigned long long* p = nullptr;
   unsigned long long* d_out = nullptr;
@@ -100,18 +121,18 @@ tsd_sensor* tsd_sensor_create(tsd_ctx* ctx, int beams, double ang_res, double ph
   if (host_writes_device_memory(ctx)) {
     s->scan_bar = true;
     for (int i = 0; i < 3; i++)
-      if (hipExtMallocWithFlags((void**)&s->d_scan2[i], nb * 10 + 64, hipDeviceMallocFinegrained) != hipSuccess) { (void)hipGetLastError(); s->scan_bar = false; }
+      if (hipExtMallocWithFlags((void**)&s->d_scan2[i], scan_alloc_bytes(beams), hipDeviceMallocFinegrained) != hipSuccess) { (void)hipGetLastError(); s->scan_bar = false; }
     if (!s->scan_bar) for (int i = 0; i < 3; i++) { if (s->d_scan2[i]) hipFree(s->d_scan2[i]); s->d_scan2[i] = nullptr; }
-    if (s->scan_bar && bar_verify_requested()) {
-      A(hipHostMalloc((void**)&s->h_bar_mismatch, 64, hipHostMallocMapped | hipHostMallocCoherent));
-      if (ok) { *s->h_bar_mismatch = 0; A(hipHostGetDevicePointer((void**)&s->d_bar_mismatch, s->h_bar_mismatch, 0)); }
+    if (s->scan_bar && bar_verify_mode() != 0) {
+      A(hipHostMalloc((void**)&s->fused.h_bar_mismatch, 64, hipHostMallocMapped | hipHostMallocCoherent));
+      if (ok) { *s->fused.h_bar_mismatch = 0; A(hipHostGetDevicePointer((void**)&s->fused.d_bar_mismatch, s->fused.h_bar_mismatch, 0)); }
     }
   }
-  if (!s->scan_bar) for (int i = 0; i < 3; i++) A(hipMalloc(&s->d_scan2[i], nb * 10 + 64));
+  if (!s->scan_bar) for (int i = 0; i < 3; i++) A(hipMalloc(&s->d_scan2[i], scan_alloc_bytes(beams)));
   for (int i = 0; i < 3; i++) {
-    A(hipHostMalloc(&s->h_scan3[i], nb * 10 + 64, hipHostMallocMapped));
-    if (ok) A(hipHostGetDevicePointer((void**)&s->hd_scan3[i], s->h_scan3[i], 0));
-    A(hipEventCreateWithFlags(&s->ev_scan_copy[i], hipEventDisableTiming));
+    A(hipHostMalloc(&s->fused.h_scan3[i], scan_alloc_bytes(beams), hipHostMallocMapped));
+    if (ok) A(hipHostGetDevicePointer((void**)&s->fused.hd_scan3[i], s->fused.h_scan3[i], 0));
+    A(hipEventCreateWithFlags(&s->fused.ev_scan_copy[i], hipEventDisableTiming));
   }
   // the scan result is written by the kernel straight into coherent pinned host memory
   s->h_result = new (std::nothrow) ScanResultDev();
@@ -123,6 +144,38 @@ tsd_sensor* tsd_sensor_create(tsd_ctx* ctx, int beams, double ang_res, double ph
   return s;
 }
 
+// What each owner in tsd_sensor holds is released in one place (pointers that were never set are null).
+static void release_async(tsd_sensor* s)
+{
+  tsd_ctx* ctx = s->ctx;
+  if (s->async.d_push_slot) { if (ctx && ctx->stream_push) hipStreamSynchronize(ctx->stream_push); hipFree(s->async.d_push_slot); }
+  for (hipEvent_t e : s->async.ev_slot_push) {
+    if (!e) continue;
+    if (ctx && ctx->ev_async_push == e) {      // (the push stream was drained above)
+      if (ctx->async_pending) hipStreamWaitEvent(ctx->stream, e, 0);
+      ctx->async_pending = false; ctx->ev_async_push = nullptr;
+    }
+    hipEventDestroy(e);
+  }
+}
+static void release(tsd_sensor::Split& p)
+{
+  for (hipEvent_t e : {p.ev_rc_done, p.ev_icp_done}) if (e) hipEventDestroy(e);
+  if (p.stream) hipStreamDestroy(p.stream);
+  hipFree(p.d_coords); hipFree(p.d_normals); hipFree(p.d_mask_m); hipFree(p.d_icp_res); hipFree(p.d_icp_seed); hipFree(p.d_icp_trace);
+  for (char* h : p.h_stage2) if (h) hipHostFree(h);
+}
+static void release(tsd_sensor::Pre& p)
+{
+  for (hipEvent_t e : {p.ev, p.ev_done}) if (e) hipEventDestroy(e);
+  hipFree(p.d); hipFree(p.d_flag);
+  if (p.h) hipHostFree(p.h);
+}
+static void release(tsd_sensor::Fused& f)
+{
+  for (int i = 0; i < 3; i++) { if (f.h_scan3[i]) hipHostFree(f.h_scan3[i]); if (f.ev_scan_copy[i]) hipEventDestroy(f.ev_scan_copy[i]); }
+  if (f.h_bar_mismatch) hipHostFree(f.h_bar_mismatch);
+}
 void tsd_sensor_destroy(tsd_sensor* s)
 {
   if (!s) return;
@@ -131,31 +184,12 @@ void tsd_sensor_destroy(tsd_sensor* s)
     auto& v = s->ctx->sensors;
     v.erase(std::remove(v.begin(), v.end(), s), v.end());
   }
-  if (s->stream) hipStreamSynchronize(s->stream);
-  for (hipEvent_t e : {s->ev_rc_done, s->ev_icp_done}) if (e) hipEventDestroy(e);
-  if (s->stream) hipStreamDestroy(s->stream);
-  hipFree(s->d_coords); hipFree(s->d_normals); hipFree(s->d_mask_m); hipFree(s->d_icp_res); hipFree(s->d_icp_seed); hipFree(s->d_icp_trace);
-  if (s->ev_pre) hipEventDestroy(s->ev_pre);
-  if (s->ev_pre_done) hipEventDestroy(s->ev_pre_done);
-  if (s->d_push_slot) { if (s->ctx && s->ctx->stream_push) hipStreamSynchronize(s->ctx->stream_push); hipFree(s->d_push_slot); }
-  for (int i = 0; i < 3; i++)
-    if (s->ev_slot_push[i]) {
-      if (s->ctx && s->ctx->ev_async_push == s->ev_slot_push[i]) {      // (the push stream was drained above)
-        if (s->ctx->async_pending) hipStreamWaitEvent(s->ctx->stream, s->ev_slot_push[i], 0);
-        s->ctx->async_pending = false; s->ctx->ev_async_push = nullptr;
-      }
-      hipEventDestroy(s->ev_slot_push[i]);
-    }
-  if (s->d_pre) hipFree(s->d_pre);
-  if (s->d_pre_flag) hipFree(s->d_pre_flag);
-  if (s->h_pre) hipHostFree(s->h_pre);
-  hipFree(s->d_rmq2[0]); hipFree(s->d_rmq2[1]); hipFree(s->d_rmq2[2]);
-  for (int i = 0; i < 3; i++) { if (s->h_scan3[i]) hipHostFree(s->h_scan3[i]); if (s->ev_scan_copy[i]) hipEventDestroy(s->ev_scan_copy[i]); }
-  if (s->h_stage2[0]) hipHostFree(s->h_stage2[0]);
-  if (s->h_stage2[1]) hipHostFree(s->h_stage2[1]);
-  hipFree(s->d_state); hipFree(s->d_rays); hipFree(s->d_rays_local); hipFree(s->d_scan2[0]); hipFree(s->d_scan2[1]); hipFree(s->d_scan2[2]);
+  if (s->split.stream) hipStreamSynchronize(s->split.stream);
+  release_async(s);
+  release(s->split); release(s->pre); release(s->fused);
+  for (int i = 0; i < 3; i++) { hipFree(s->d_rmq2[i]); hipFree(s->d_scan2[i]); }
+  hipFree(s->d_state); hipFree(s->d_rays); hipFree(s->d_rays_local);
   hipHostFree(s->h_rwords); delete s->h_result;
-  if (s->h_bar_mismatch) hipHostFree(s->h_bar_mismatch);
   delete s;
 }
 
@@ -219,6 +253,17 @@ static bool scan_result_arrived(tsd_sensor* s, unsigned long long seq)
   return true;
 }
 
+// The record that arrived last (s->h_result) as the caller's tsd_scan_result.  reserved == 0: the registration ran, and the host's
+// mirror of the sensor position follows it.
+static void deliver_result(tsd_sensor* s, tsd_scan_result* r, int reserved)
+{
+  const ScanResultDev* h = s->h_result;
+  copy_icp_result(&h->icp, &r->icp);
+  for (int i = 0; i < 9; i++) r->pose[i] = h->pose[i];
+  r->reg_error = h->reg_error; r->pushed = h->pushed; r->no_model = h->no_model; r->reserved = reserved;
+  if (reserved == 0) { s->pos[0] = r->pose[2]; s->pos[1] = r->pose[5]; }
+}
+
 // A scan comes in two steps.  scan_stage_host: the caller's arrays into the sensor's scan buffer -- device memory that the host stores
 // into through the PCIe BAR (tsd_sensor::scan_bar), or a pinned host buffer where that mapping is missing (the three scan / table
 // buffers are used in turn).  scan_stage_device: the range-query tables of this scan's push on the side stream (and, pinned mode, the
@@ -227,93 +272,74 @@ static bool scan_result_arrived(tsd_sensor* s, unsigned long long seq)
 static int scan_stage_host(tsd_sensor* s, const double* ranges, const uint8_t* mask, const uint8_t* mask_push)
 {
   tsd_ctx* ctx = s->ctx;
-  const size_t nb = (size_t)s->beams;
   if (int rc = sensor_conc_init(s, false)) return rc;       // (the sensor's own table buffers)
-  unsigned long long tl = g_stage_timing.on ? now_ns() : 0;
-  auto LAP = [&](int i) { if (g_stage_timing.on) { const unsigned long long u = now_ns(); g_stage_timing.ns[i] += u - tl; tl = u; } };
-  // three buffers in turn (see tsd_sensor::stage_slot): the push that read this one three scans ago is done -- and so is the device
+  Lap lap(g_stage_timing);
+  // three buffers in turn (see tsd_sensor::Fused::stage_slot): the push that read this one three scans ago is done -- and so is the device
   // copy out of the pinned buffer, which that push was ordered behind; its event is looked at all the same (one query)
-  const int sslot = s->stage_slot;
-  s->stage_slot = (s->stage_slot + 1) % 3;
-  if (s->scan_copy_valid[sslot]) { TSD_HIP_CHECK(ctx, hipEventSynchronize(s->ev_scan_copy[sslot])); s->scan_copy_valid[sslot] = false; }
+  const int sslot = s->fused.stage_slot;
+  s->fused.stage_slot = (s->fused.stage_slot + 1) % 3;
+  if (s->fused.scan_copy_valid[sslot]) { TSD_HIP_CHECK(ctx, hipEventSynchronize(s->fused.ev_scan_copy[sslot])); s->fused.scan_copy_valid[sslot] = false; }
   // (the host writes the device buffer itself: with asynchronous mapping the push that last read it has to be SEEN done first)
-  if (s->scan_bar && s->slot_push_valid[sslot]) { TSD_HIP_CHECK(ctx, hipEventSynchronize(s->ev_slot_push[sslot])); s->slot_push_valid[sslot] = false; }
-  LAP(0);
-  char* h = s->scan_bar ? s->d_scan2[sslot] : s->h_scan3[sslot];
-  std::memcpy(h, ranges, nb * 8);
-  std::memcpy(h + nb * 8, mask, nb);
-  std::memcpy(h + nb * 9, mask_push ? mask_push : mask, nb);
+  if (s->scan_bar && s->async.slot_push_valid[sslot]) { TSD_HIP_CHECK(ctx, hipEventSynchronize(s->async.ev_slot_push[sslot])); s->async.slot_push_valid[sslot] = false; }
+  lap.lap(0);
+  scan_pack(s->scan_bar ? s->d_scan2[sslot] : s->fused.h_scan3[sslot], s->beams, ranges, mask, mask_push);
 #if defined(__x86_64__)
   if (s->scan_bar) _mm_sfence();              // (write-combined stores: on their way before any launch that reads them)
 #endif
-  if (s->d_bar_mismatch) {                    // (debug: the pinned copy the device compares the scan buffer with, launch_bar_verify)
-    std::memcpy(s->h_scan3[sslot], ranges, nb * 8);
-    std::memcpy(s->h_scan3[sslot] + nb * 8, mask, nb);
-    std::memcpy(s->h_scan3[sslot] + nb * 9, mask_push ? mask_push : mask, nb);
-    if (bar_verify_mode() == 2) s->h_scan3[sslot][nb * 4] ^= 0x40;
+  if (s->fused.d_bar_mismatch) {                    // (debug: the pinned copy the device compares the scan buffer with, launch_bar_verify)
+    scan_pack(s->fused.h_scan3[sslot], s->beams, ranges, mask, mask_push);
+    if (bar_verify_mode() == 2) s->fused.h_scan3[sslot][(size_t)s->beams * 4] ^= 0x40;
   }
-  LAP(1);
-  char* d_scan = s->d_scan2[sslot];
-  s->st_ranges = reinterpret_cast<const double*>(d_scan);
-  s->st_mask = reinterpret_cast<const uint8_t*>(d_scan + nb * 8);
-  s->st_mask_push = reinterpret_cast<const uint8_t*>(d_scan + nb * 9);
-  s->st_h_ranges = s->scan_bar ? s->st_ranges : reinterpret_cast<const double*>(s->hd_scan3[sslot]);
-  s->st_h_mask = s->scan_bar ? s->st_mask : reinterpret_cast<const uint8_t*>(s->hd_scan3[sslot] + nb * 8);
-  s->st_rmq = s->d_rmq2[sslot]; s->st_slot = sslot;
-  s->st_device_done = false;
-  s->staged = true;
+  lap.lap(1);
+  s->fused.scan = scan_view(s->d_scan2[sslot], s->beams);
+  s->fused.h_scan = s->scan_bar ? s->fused.scan : scan_view(s->fused.hd_scan3[sslot], s->beams);
+  s->fused.rmq = s->d_rmq2[sslot]; s->fused.slot = sslot;
+  s->fused.device_done = false;
+  s->fused.staged = true;
   return TSD_OK;
 }
 
 static int scan_stage_device(tsd_sensor* s)
 {
   tsd_ctx* ctx = s->ctx;
-  const size_t nb = (size_t)s->beams;
-  const int sslot = s->st_slot;
-  unsigned long long tl = g_stage_timing.on ? now_ns() : 0;
-  auto LAP = [&](int i) { if (g_stage_timing.on) { const unsigned long long u = now_ns(); g_stage_timing.ns[i] += u - tl; tl = u; } };
+  const int sslot = s->fused.slot;
+  Lap lap(g_stage_timing);
   // Asynchronous mapping: the push that last read this buffer (three scans back) ran on the push stream beside a registration, and
   // nothing the host has seen since is ordered behind it -- the copy and the tables below wait for that push's own event (done long
-  // ago in practice: one query; the stream-side wait is the fall-back).  Strict order: see tsd_sensor::stage_slot.
-  if (s->slot_push_valid[sslot]) {
-    if (!host_saw_event(s->ev_slot_push[sslot], 0)) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, s->ev_slot_push[sslot], 0));
-    else s->slot_push_valid[sslot] = false;
+  // ago in practice: one query; the stream-side wait is the fall-back).  Strict order: see tsd_sensor::Fused::stage_slot.
+  if (s->async.slot_push_valid[sslot]) {
+    if (!host_saw_event(s->async.ev_slot_push[sslot], 0)) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, s->async.ev_slot_push[sslot], 0));
+    else s->async.slot_push_valid[sslot] = false;
   }
   if (!s->scan_bar) {
-    TSD_HIP_CHECK(ctx, hipMemcpyAsync(s->d_scan2[sslot], s->h_scan3[sslot], nb * 10, hipMemcpyHostToDevice, ctx->stream2));
-    LAP(2);
-    TSD_HIP_CHECK(ctx, hipEventRecord(s->ev_scan_copy[sslot], ctx->stream2));
-    s->scan_copy_valid[sslot] = true;
+    TSD_HIP_CHECK(ctx, hipMemcpyAsync(s->d_scan2[sslot], s->fused.h_scan3[sslot], scan_bytes(s->beams), hipMemcpyHostToDevice, ctx->stream2));
+    lap.lap(2);
+    TSD_HIP_CHECK(ctx, hipEventRecord(s->fused.ev_scan_copy[sslot], ctx->stream2));
+    s->fused.scan_copy_valid[sslot] = true;
     TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_h2d, ctx->stream2));
-    LAP(3);
+    lap.lap(3);
   }
   LaunchTarget tg;
-  tg.rmq = s->st_rmq;
+  tg.rmq = s->fused.rmq;
   TargetScope scope(ctx, &tg);
-  int rc = launch_push_tables(ctx, ctx->stream2, s->beams, s->st_ranges, s->st_mask_push, s->phi_min, s->ang_res);
+  int rc = launch_push_tables(ctx, ctx->stream2, s->beams, s->fused.scan.ranges, s->fused.scan.mask_push, s->phi_min, s->ang_res);
   if (rc != TSD_OK) return rc;
   TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_tables, ctx->stream2));
   // make sure the side stream's commands are on their way now: with more streams in the process than hardware queues (a
   // communicator's, a framework's) the runtime was seen to hold them back until the next synchronisation, and the
   // registration that waits for this copy with them (a 40 ms stall once in ~200 scans)
   (void)hipStreamQuery(ctx->stream2);
-  LAP(4);
+  lap.lap(4);
   if (g_stage_timing.on) g_stage_timing.n++;
-  s->st_device_done = true;
+  s->fused.device_done = true;
   return TSD_OK;
-}
-
-static int scan_stage_impl(tsd_sensor* s, const double* ranges, const uint8_t* mask, const uint8_t* mask_push)
-{
-  if (int rc = scan_stage_host(s, ranges, mask, mask_push)) return rc;
-  return scan_stage_device(s);
 }
 
 int tsd_sensor_set_async_mapping(tsd_sensor* s, int on)
 {
   if (!s || !s->ctx) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
-  if (s->submitted) return set_error(ctx, TSD_E_ARG, "tsd_sensor_set_async_mapping: a scan is in flight", hipSuccess);
+  if (s->fused.submitted) return set_error(ctx, TSD_E_ARG, "tsd_sensor_set_async_mapping: a scan is in flight", hipSuccess);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (int rcd_ = drain_async_push(ctx)) return rcd_;
   if (on) {
@@ -321,15 +347,15 @@ int tsd_sensor_set_async_mapping(tsd_sensor* s, int on)
     // (both events order kernels of ONE device against each other: no system-scope fence when they complete)
     if (!ctx->ev_async_rc) TSD_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_async_rc, hipEventDisableTiming | hipEventDisableSystemFence));
     // "the push of the scan that used scan / table buffer i is done": one event per buffer, so that the staging of a later scan
-    // into that buffer can be ordered behind the push that last read it (scan_stage_impl); ctx->ev_async_push is the newest of them
+    // into that buffer can be ordered behind the push that last read it (scan_stage_host, scan_stage_device); ctx->ev_async_push is the newest of them
     for (int i = 0; i < 3; i++)
-      if (!s->ev_slot_push[i]) TSD_HIP_CHECK(ctx, hipEventCreateWithFlags(&s->ev_slot_push[i], hipEventDisableTiming | hipEventDisableSystemFence));
-    if (!s->d_push_slot) TSD_HIP_CHECK(ctx, hipMalloc(&s->d_push_slot, 2 * sizeof(tsd::PushArgs)));
+      if (!s->async.ev_slot_push[i]) TSD_HIP_CHECK(ctx, hipEventCreateWithFlags(&s->async.ev_slot_push[i], hipEventDisableTiming | hipEventDisableSystemFence));
+    if (!s->async.d_push_slot) TSD_HIP_CHECK(ctx, hipMalloc(&s->async.d_push_slot, 2 * sizeof(tsd::PushArgs)));
   }
-  s->async_mapping = on != 0;
+  s->async.mapping = on != 0;
   // a ray cast enqueued ahead by the previous scan saw (strict) or did not see (asynchronous) that scan's push: the next scan of the
   // other kind casts again
-  s->rc_pending = false;
+  s->fused.rc_pending = false;
   return TSD_OK;
 }
 
@@ -350,7 +376,7 @@ int tsd_debug_set_icp_helpers(tsd_ctx* ctx, int on)
 int tsd_debug_sensor_scan_path(const tsd_sensor* s)
 {
   if (!s) return TSD_E_ARG;
-  return s->scan_bar ? (s->d_bar_mismatch ? 2 : 1) : 0;
+  return s->scan_bar ? (s->fused.d_bar_mismatch ? 2 : 1) : 0;
 }
 
 int tsd_debug_set_push_multi(tsd_ctx* ctx, int on)
@@ -365,9 +391,10 @@ int tsd_scan_stage(tsd_sensor* s, const double* ranges, const uint8_t* mask, con
   if (!s || !s->ctx || !ranges || !mask) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
   if (!s->posed) return set_error(ctx, TSD_E_ARG, "tsd_scan_stage before tsd_sensor_set_pose", hipSuccess);
-  if (s->staged) return set_error(ctx, TSD_E_ARG, "tsd_scan_stage: a staged scan is waiting for tsd_scan_submit already", hipSuccess);
+  if (s->fused.staged) return set_error(ctx, TSD_E_ARG, "tsd_scan_stage: a staged scan is waiting for tsd_scan_submit already", hipSuccess);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  return scan_stage_impl(s, ranges, mask, mask_push);
+  if (int rc = scan_stage_host(s, ranges, mask, mask_push)) return rc;
+  return scan_stage_device(s);
 }
 
 int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, const uint8_t* mask_push,
@@ -376,14 +403,14 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
   if (!s || !s->ctx || !params || !gates || (ranges && !mask)) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
   if (!s->posed) return set_error(ctx, TSD_E_ARG, "tsd_scan before tsd_sensor_set_pose", hipSuccess);
-  if (s->submitted) return set_error(ctx, TSD_E_ARG, "tsd_scan_submit: the previous scan was not collected", hipSuccess);
-  if (!ranges && !s->staged) return set_error(ctx, TSD_E_ARG, "tsd_scan_submit without a scan (none given, none staged)", hipSuccess);
+  if (s->fused.submitted) return set_error(ctx, TSD_E_ARG, "tsd_scan_submit: the previous scan was not collected", hipSuccess);
+  if (!ranges && !s->fused.staged) return set_error(ctx, TSD_E_ARG, "tsd_scan_submit without a scan (none given, none staged)", hipSuccess);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  ScanLap lap;
-  if (g_scan_timing.on && g_scan_last_return) {
-    const unsigned long long gap = lap.t - g_scan_last_return;
+  Lap lap(g_scan_timing);
+  if (g_scan_timing.on && g_scan_timing.last_return) {
+    const unsigned long long gap = lap.t - g_scan_timing.last_return;
     if (gap < 1000000ull) g_scan_timing.ns[0] += gap;   // (one-off pauses of the caller excluded from the average)
-    if (gap > g_scan_lap_max[0] && g_scan_timing.n > 8) { g_scan_lap_max[0] = gap; g_scan_lap_max_at[0] = (unsigned long long)g_scan_timing.n; }
+    if (gap > g_scan_timing.max[0] && g_scan_timing.n > 8) { g_scan_timing.max[0] = gap; g_scan_timing.max_at[0] = g_scan_timing.n.load(); }
   }
   const bool staged_ahead = ranges == nullptr;
   if (ranges) {
@@ -391,53 +418,46 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     // three-buffer rotation is only safe when it advances once per scan (the buffer two rotations back may still be read by the
     // push of the previous scan, which is ordered behind nothing the host has seen).  The new copy and tables follow the dropped
     // ones on the side stream (pinned mode), and nothing else ever read the dropped data.
-    if (s->staged) {
-      s->stage_slot = s->st_slot;
+    if (s->fused.staged) {
+      s->fused.stage_slot = s->fused.slot;
       // (BAR mode: the host is about to store into that buffer itself -- the dropped scan's tables kernel on the side stream, which
       // reads it, has to be SEEN done first; pinned mode orders the new copy behind it on the side stream)
-      if (s->scan_bar && s->st_device_done) TSD_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev_tables));
+      if (s->scan_bar && s->fused.device_done) TSD_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev_tables));
     }
-    s->staged = false;
+    s->fused.staged = false;
     int rcs = scan_stage_host(s, ranges, mask, mask_push);
     if (rcs != TSD_OK) return rcs;
   }
-  s->staged = false;
+  s->fused.staged = false;
   // A scan that came with this call is in the scan buffer (device memory the host stored into, or the pinned buffer) and its tables are
   // not built yet: its registration reads it from there, and the tables (pinned mode: the device copy first) are enqueued BEHIND the
   // registration's launch -- the host's work on them no longer sits between the result of the
   // previous scan and this launch (the main stream ran dry for ~10 us per scan there; the push needs them 100+ us from now).
-  const bool icp_from_host = !s->st_device_done;
-  const double* d_ranges = s->st_ranges;
-  const uint8_t* d_mask = s->st_mask;
-  const uint8_t* d_mask_push = s->st_mask_push;
+  const bool icp_from_host = !s->fused.device_done;
+  const ScanView scan = s->fused.scan;
   int rc = TSD_OK;
   lap.lap(1);
 
   // The ray cast needs nothing from the scan (its pose arguments were left on the device by the previous
   // registration), so the previous tsd_scan enqueued it right behind its push; it is launched here only if
   // something touched the grid, the sensor or the context's ray-cast outputs since.
-  RaycastArgs ra;
-  std::memset(&ra, 0, sizeof(ra));
-  ra.beams = s->beams;                                   // grid size of the launch; the rest is read on the device
-  if (!(s->rc_pending && s->rc_epoch == ctx->epoch)) {
+  const RaycastArgs ra = sensor_raycast_launch_args(s);
+  if (!(s->fused.rc_pending && s->fused.rc_epoch == ctx->epoch)) {
     if (int rcd_ = drain_async_push(ctx)) return rcd_;     // (asynchronous mapping: a push still on the push stream comes first)
     rc = launch_raycast(ctx, ra, &s->d_state->rc, s->d_rays);
     if (rc != TSD_OK) return rc;
   }
-  s->rc_pending = false;
+  s->fused.rc_pending = false;
   lap.lap(2);
-  IcpArgs ia;
-  const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  fill_icp_args(ia, ident, params);
-  ia.beams = s->beams; ia.ccw = s->ccw ? 1 : 0;
+  IcpArgs ia = sensor_icp_args(s, params);
   // registration_mode 3: the pre-registration armed by tsd_scan_preregister runs here, between the ray cast and the registration,
   // whose Tinit it leaves on the device
-  s->pre_ran = false;
+  s->pre.ran = false;
   IcpPreLaunch prel;
   std::memset(&prel, 0, sizeof(prel));
   bool fold_argmax = false;
-  if (s->pre_armed) {
-    s->pre_armed = false;
+  if (s->pre.armed) {
+    s->pre.armed = false;
     // (asynchronous mapping: the SCORING reads the grid -- the previous scan's push, still on the push stream, has to land first; the
     // normals and the list building ahead of it do not, and run beside that push.  The order is then ray cast, previous push,
     // pre-registration, registration: still one of the reference's interleavings)
@@ -450,42 +470,35 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     rc = launch_preregistration(ctx, s, launch_stream(ctx), tgp && tgp->coords ? tgp->coords : ctx->d_coords,
                                 tgp && tgp->mask_m ? tgp->mask_m : ctx->d_mask_m, s->d_state->icpP, &ia.Tinit_dev, before_score, fold_argmax ? &prel : nullptr);
     if (rc != TSD_OK) return rc;
-    s->pre_ran = true;
+    s->pre.ran = true;
   }
   // the gates, Sensor::transform and the push decision run as the epilogue of the registration kernel
   const unsigned long long seq = ++s->seq;
-  ScanPostArgs sp;
-  std::memset(&sp, 0, sizeof(sp));
-  sp.st = s->d_state; sp.rays = s->d_rays; sp.out = s->d_result; sp.seq = seq; sp.beams = s->beams;
-  sp.gmin_x = ctx->grid.min_x; sp.gmax_x = ctx->grid.max_x; sp.gmin_y = ctx->grid.min_y; sp.gmax_y = ctx->grid.max_y;
-  sp.gates = GateArgs{gates->reg_trs_max, gates->reg_sin_rot_max, gates->trs_min, gates->rot_min};
-  const bool async_map = s->async_mapping && s->d_push_slot != nullptr;
-  tsd::PushArgs* const push_slot = async_map ? s->d_push_slot + (seq & 1ull) : nullptr;
+  ScanPostArgs sp = sensor_post_args(s, seq, *gates);
+  const bool async_map = s->async.mapping && s->async.d_push_slot != nullptr;
+  tsd::PushArgs* const push_slot = async_map ? s->async.d_push_slot + (seq & 1ull) : nullptr;
   sp.push_copy = push_slot;
   // The ray cast did not need the scan, the registration does.  The copy is short and the ray cast long, so the
   // host waits for the copy itself (a few microseconds, the device is busy meanwhile) instead of putting a
   // cross-stream barrier between the two kernels; the barrier is the fall-back.  (A scan staged ahead was copied
   // during the previous registration: nothing to wait for.)
-  if (s->d_bar_mismatch) {
-    hipLaunchKernelGGL(k_bar_verify, dim3(4), dim3(256), 0, ctx->stream, reinterpret_cast<const unsigned char*>(s->d_scan2[s->st_slot]),
-                       reinterpret_cast<const unsigned char*>(s->hd_scan3[s->st_slot]), (int)((size_t)s->beams * 10), s->d_bar_mismatch);
+  if (s->fused.d_bar_mismatch) {
+    hipLaunchKernelGGL(k_bar_verify, dim3(4), dim3(256), 0, ctx->stream, reinterpret_cast<const unsigned char*>(s->d_scan2[s->fused.slot]),
+                       reinterpret_cast<const unsigned char*>(s->fused.hd_scan3[s->fused.slot]), (int)scan_bytes(s->beams), s->fused.d_bar_mismatch);
     TSD_HIP_CHECK(ctx, hipGetLastError());
   }
   if (icp_from_host) {
-    rc = launch_icp(ctx, ia, s->d_state->icpP, s->d_rays_local, s->st_h_ranges, s->st_h_mask, &sp, fold_argmax ? &prel : nullptr);
+    rc = launch_icp(ctx, ia, s->d_state->icpP, s->d_rays_local, s->fused.h_scan.ranges, s->fused.h_scan.mask, &sp, fold_argmax ? &prel : nullptr);
     if (rc != TSD_OK) return rc;
     rc = scan_stage_device(s);
     if (rc != TSD_OK) return rc;
   } else {
     if (!s->scan_bar && !host_saw_event(ctx->ev_h2d, staged_ahead ? 2 : 40)) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_h2d, 0));
-    rc = launch_icp(ctx, ia, s->d_state->icpP, s->d_rays_local, d_ranges, d_mask, &sp, fold_argmax ? &prel : nullptr);
+    rc = launch_icp(ctx, ia, s->d_state->icpP, s->d_rays_local, scan.ranges, scan.mask, &sp, fold_argmax ? &prel : nullptr);
     if (rc != TSD_OK) return rc;
   }
   lap.lap(3);
-  PushArgs pa;
-  std::memset(&pa, 0, sizeof(pa));
-  pa.beams = s->beams;                                   // LDS size of the launch
-  pa.max_range = s->max_range;                           // tile window of the launch (the rest is read on the device)
+  const PushArgs pa = sensor_push_launch_args(s);
   // TSD_HALO_KERNEL=1: the push's halo pass as a kernel of its own even here (the form every other path uses; A/B)
   static const bool halo_in_raycast = [] { const char* e = std::getenv("TSD_HALO_KERNEL"); return !(e && *e == '1'); }();
   HaloArgs halo;
@@ -495,11 +508,11 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     if (!host_saw_event(ctx->ev_tables, staged_ahead ? 2 : 60)) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_tables, 0));
     {
       LaunchTarget tg;
-      tg.rmq = s->st_rmq;                                  // this scan's tables (the sensor's own buffers)
+      tg.rmq = s->fused.rmq;                                  // this scan's tables (the sensor's own buffers)
       TargetScope scope(ctx, &tg);
       // the registration moves the sensor by at most the gate (a larger step is rejected: pose unchanged)
       // (the push's halo pass is left to the ray cast that follows it at once: k_raycast's prologue, raycast_kernels.hip)
-      rc = launch_push(ctx, pa, s->pos[0], s->pos[1], gates->reg_trs_max, &s->d_state->push, d_ranges, d_mask_push, nullptr, halo_in_raycast ? &halo : nullptr);
+      rc = launch_push(ctx, pa, s->pos[0], s->pos[1], gates->reg_trs_max, &s->d_state->push, scan.ranges, scan.mask_push, nullptr, halo_in_raycast ? &halo : nullptr);
     }
     if (rc != TSD_OK) return rc;
     ctx->epoch++;                                          // the grid changes
@@ -511,7 +524,7 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
       if (halo_in_raycast) (void)launch_push_halo(ctx, halo);      // (the grid's halos must not stay behind the push whatever happened to the ray cast)
       return rc;
     }
-    s->rc_pending = true; s->rc_epoch = ctx->epoch;
+    s->fused.rc_pending = true; s->fused.rc_epoch = ctx->epoch;
     lap.lap(5);
   } else {
     // Asynchronous mapping (the reference's ThreadMapping: queuePush returns at once and the push lands when the mapping thread gets
@@ -535,22 +548,22 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream_push, ctx->ev_tables, 0));
     {
       LaunchTarget tg;
-      tg.rmq = s->st_rmq;
+      tg.rmq = s->fused.rmq;
       TargetScope scope(ctx, &tg);
       if (ctx->debug_push_stall_us) launch_stall(ctx, ctx->stream_push, ctx->debug_push_stall_us);     // (tests: a push stream that lags)
-      rc = launch_push(ctx, pa, s->pos[0], s->pos[1], gates->reg_trs_max, push_slot, d_ranges, d_mask_push, ctx->stream_push);
+      rc = launch_push(ctx, pa, s->pos[0], s->pos[1], gates->reg_trs_max, push_slot, scan.ranges, scan.mask_push, ctx->stream_push);
     }
     if (rc != TSD_OK) return rc;
-    ctx->ev_async_push = s->ev_slot_push[s->st_slot];      // (st_slot: the buffers of the scan being submitted)
-    s->slot_push_valid[s->st_slot] = true;
+    ctx->ev_async_push = s->async.ev_slot_push[s->fused.slot];      // (fused.slot: the buffers of the scan being submitted)
+    s->async.slot_push_valid[s->fused.slot] = true;
     TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_async_push, ctx->stream_push));
     (void)hipStreamQuery(ctx->stream_push);
     ctx->async_pending = true;
     ctx->epoch++;                                          // the grid changes ...
-    s->rc_pending = true; s->rc_epoch = ctx->epoch;        // ... and the ray cast enqueued above is, by design, the one that does not see it
+    s->fused.rc_pending = true; s->fused.rc_epoch = ctx->epoch;        // ... and the ray cast enqueued above is, by design, the one that does not see it
     lap.lap(5);
   }
-  s->submitted = true;
+  s->fused.submitted = true;
   return TSD_OK;
 }
 
@@ -558,43 +571,29 @@ int tsd_scan_collect(tsd_sensor* s, tsd_scan_result* result)
 {
   if (!s || !s->ctx || !result) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
-  if (!s->submitted) return set_error(ctx, TSD_E_ARG, "tsd_scan_collect without tsd_scan_submit", hipSuccess);
-  s->submitted = false;
-  ScanLap lap;
+  if (!s->fused.submitted) return set_error(ctx, TSD_E_ARG, "tsd_scan_collect without tsd_scan_submit", hipSuccess);
+  s->fused.submitted = false;
+  Lap lap(g_scan_timing);
   const unsigned long long seq = s->seq;
   // The result is known once k_scan_post has run; the push kernels behind it only touch the grid, and
   // whatever the caller enqueues next is ordered behind them on the stream.  So the host does not wait for
   // the stream: it polls the sequence number and prepares the next scan while the push is still running.
-  {
-    unsigned long long spins = 0;
-    while (!scan_result_arrived(s, seq)) {
-      ++spins;
-      // A registration takes 0.15-0.3 ms.  Past that, nudge the runtime: with other streams in the process (a communicator's,
-      // a framework's) it was seen to sit on an enqueued launch until the next query / synchronisation of the stream -- a
-      // 40 ms stall at the same scan of every run (profiles/r2_dist_stall.txt); a stream query is a few microseconds.
-      if ((spins & 0x3FFFull) == 0) { (void)hipStreamQuery(ctx->stream); (void)hipStreamQuery(ctx->stream2); }
-      if (spins > 4000000ull) {            // ~ a tenth of a second: something is wrong, fall back to a real wait
-        TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (!scan_result_arrived(s, seq))
-          return set_error(ctx, TSD_E_HIP, "tsd_scan: result record never arrived", hipSuccess);
-        break;
-      }
-#if defined(__x86_64__)
-      __builtin_ia32_pause();
-#endif
-    }
-  }
+  hipError_t e_sync = hipSuccess;
+  const bool arrived = wait_arrival([&] { return scan_result_arrived(s, seq); }, ctx->stream, [&](unsigned long long spins) {
+    // A registration takes 0.15-0.3 ms.  Past that, nudge the runtime: with other streams in the process (a communicator's,
+    // a framework's) it was seen to sit on an enqueued launch until the next query / synchronisation of the stream -- a
+    // 40 ms stall at the same scan of every run (profiles/r2_dist_stall.txt); a stream query is a few microseconds.
+    if ((spins & 0x3FFFull) == 0) { (void)hipStreamQuery(ctx->stream); (void)hipStreamQuery(ctx->stream2); }
+  }, &e_sync);
+  if (e_sync != hipSuccess) return set_error(ctx, TSD_E_HIP, "hipStreamSynchronize(ctx->stream)", e_sync);
+  if (!arrived) return set_error(ctx, TSD_E_HIP, "tsd_scan: result record never arrived", hipSuccess);
   lap.lap(6);
-  if (s->h_bar_mismatch && __atomic_load_n(s->h_bar_mismatch, __ATOMIC_ACQUIRE) != 0)
+  if (s->fused.h_bar_mismatch && __atomic_load_n(s->fused.h_bar_mismatch, __ATOMIC_ACQUIRE) != 0)
     return set_error(ctx, TSD_E_HIP, "tsd_scan: the scan the host stored into device memory through the PCIe BAR is not what the device read "
                                      "(TSD_SCAN_BAR_VERIFY); run with TSD_SCAN_PINNED=1 on this platform", hipSuccess);
-  copy_icp_result(&s->h_result->icp, &result->icp);
-  for (int i = 0; i < 9; i++) result->pose[i] = s->h_result->pose[i];
-  s->pos[0] = result->pose[2]; s->pos[1] = result->pose[5];
-  result->reg_error = s->h_result->reg_error; result->pushed = s->h_result->pushed;
-  result->no_model = s->h_result->no_model; result->reserved = 0;
+  deliver_result(s, result, 0);
   lap.lap(7);
-  if (g_scan_timing.on) { g_scan_timing.n++; g_scan_last_return = now_ns(); }
+  if (g_scan_timing.on) { g_scan_timing.n++; g_scan_timing.last_return = now_ns(); }
   return TSD_OK;
 }
 
@@ -626,22 +625,22 @@ static int sensor_conc_init(tsd_sensor* s, bool own_stream)
   tsd_ctx* ctx = s->ctx;
   bool ok = true;
   auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
-  if (own_stream && !s->stream) {            // (a sensor that only ever runs in batches uses the batch's stream and events)
-    A(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&s->ev_rc_done, &s->ev_icp_done}) A(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  if (own_stream && !s->split.stream) {            // (a sensor that only ever runs in batches uses the batch's stream and events)
+    A(hipStreamCreateWithFlags(&s->split.stream, hipStreamNonBlocking));
+    for (hipEvent_t* e : {&s->split.ev_rc_done, &s->split.ev_icp_done}) A(hipEventCreateWithFlags(e, hipEventDisableTiming));
     if (!ok) return set_error(ctx, TSD_E_HIP, "tsd_scan_begin: per-sensor stream", hipGetLastError());
   }
-  if (s->conc_ready) return TSD_OK;
+  if (s->split.ready) return TSD_OK;
   const size_t nb = (size_t)s->beams;
-  A(hipMalloc(&s->d_coords, nb * 16)); A(hipMalloc(&s->d_normals, nb * 16)); A(hipMalloc(&s->d_mask_m, nb));
-  A(hipMalloc(&s->d_icp_res, sizeof(IcpResultDev))); A(hipMalloc(&s->d_icp_trace, sizeof(double) * TSD_ICP_TRACE_STRIDE * TSD_ICP_TRACE_MAX));
-  A(hipMalloc(&s->d_icp_seed, icp_seed_bytes(s->beams)));
+  A(hipMalloc(&s->split.d_coords, nb * 16)); A(hipMalloc(&s->split.d_normals, nb * 16)); A(hipMalloc(&s->split.d_mask_m, nb));
+  A(hipMalloc(&s->split.d_icp_res, sizeof(IcpResultDev))); A(hipMalloc(&s->split.d_icp_trace, sizeof(double) * TSD_ICP_TRACE_STRIDE * TSD_ICP_TRACE_MAX));
+  A(hipMalloc(&s->split.d_icp_seed, icp_seed_bytes(s->beams)));
   // (through the context's stream and waited for: a plain hipMemset would bring the NULL stream alive, see capi.hip)
-  if (ok) { A(hipMemsetAsync(s->d_icp_seed, 0, icp_seed_bytes(s->beams), ctx->stream)); A(hipStreamSynchronize(ctx->stream)); }
+  if (ok) { A(hipMemsetAsync(s->split.d_icp_seed, 0, icp_seed_bytes(s->beams), ctx->stream)); A(hipStreamSynchronize(ctx->stream)); }
   for (int i = 0; i < 3; i++) A(hipMalloc(&s->d_rmq2[i], push_rmq_bytes(s->beams)));
-  A(hipHostMalloc(&s->h_stage2[0], nb * 10 + 64, hipHostMallocDefault)); A(hipHostMalloc(&s->h_stage2[1], nb * 10 + 64, hipHostMallocDefault));
+  for (char*& h : s->split.h_stage2) A(hipHostMalloc(&h, scan_alloc_bytes(s->beams), hipHostMallocDefault));
   if (!ok) return set_error(ctx, TSD_E_HIP, "tsd_scan_begin: per-sensor streams / buffers", hipGetLastError());
-  s->conc_ready = true;
+  s->split.ready = true;
   return TSD_OK;
 }
 
@@ -651,34 +650,29 @@ int tsd_scan_begin(tsd_sensor* s, const double* ranges, const uint8_t* mask, con
   if (!s || !s->ctx || !ranges || !mask || !params || !gates) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
   if (!s->posed) return set_error(ctx, TSD_E_ARG, "tsd_scan_begin before tsd_sensor_set_pose", hipSuccess);
-  if (s->inflight) return set_error(ctx, TSD_E_ARG, "tsd_scan_begin: the previous scan of this sensor was not finished", hipSuccess);
+  if (s->split.inflight) return set_error(ctx, TSD_E_ARG, "tsd_scan_begin: the previous scan of this sensor was not finished", hipSuccess);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (int rcd_ = drain_async_push(ctx)) return rcd_;
   int rc = sensor_conc_init(s, true);
   if (rc != TSD_OK) return rc;
-  const size_t nb = (size_t)s->beams;
-  ConcLap lap;
+  Lap lap(g_conc_timing);
   // the scan: ranges | mask | mask_push through the sensor's own pinned buffer (the buffer two scans back is free: its
   // copy was waited for by that scan's registration)
-  char* h = s->h_stage2[s->scan_slot];
-  char* d_scan = s->d_scan2[s->scan_slot];
-  s->scan_slot ^= 1;
-  std::memcpy(h, ranges, nb * 8);
-  std::memcpy(h + nb * 8, mask, nb);
-  std::memcpy(h + nb * 9, mask_push ? mask_push : mask, nb);
+  char* h = s->split.h_stage2[s->split.scan_slot];
+  char* d_scan = s->d_scan2[s->split.scan_slot];
+  s->split.scan_slot ^= 1;
+  scan_pack(h, s->beams, ranges, mask, mask_push);
   // (copy and tables on the sensor's ONE stream, ahead of the ray cast: every further stream is one more candidate for
   // sharing a hardware queue with another robot's 0.17 ms registration -- HIP multiplexes streams onto a few in-order
   // hardware queues, GPU_MAX_HW_QUEUES -- and 17 us ahead of a 190 us chain is the cheaper price)
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d_scan, h, nb * 10, hipMemcpyHostToDevice, s->stream));
-  const double* d_ranges = reinterpret_cast<const double*>(d_scan);
-  const uint8_t* d_mask = reinterpret_cast<const uint8_t*>(d_scan + nb * 8);
-  const uint8_t* d_mask_push = reinterpret_cast<const uint8_t*>(d_scan + nb * 9);
-  s->rmq_slot ^= 1;                         // (the previous push of this sensor may still read its tables)
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d_scan, h, scan_bytes(s->beams), hipMemcpyHostToDevice, s->split.stream));
+  const ScanView scan = scan_view(d_scan, s->beams);
+  s->split.rmq_slot ^= 1;                         // (the previous push of this sensor may still read its tables)
   LaunchTarget tg;
-  tg.stream = s->stream; tg.coords = s->d_coords; tg.normals = s->d_normals; tg.mask_m = s->d_mask_m;
-  tg.icp_res = s->d_icp_res; tg.trace = s->d_icp_trace; tg.icp_seed = s->d_icp_seed; tg.icp_seed_points = s->beams; tg.rmq = s->d_rmq2[s->rmq_slot];
+  tg.stream = s->split.stream; tg.coords = s->split.d_coords; tg.normals = s->split.d_normals; tg.mask_m = s->split.d_mask_m;
+  tg.icp_res = s->split.d_icp_res; tg.trace = s->split.d_icp_trace; tg.icp_seed = s->split.d_icp_seed; tg.icp_seed_points = s->beams; tg.rmq = s->d_rmq2[s->split.rmq_slot];
   TargetScope scope(ctx, &tg);
-  rc = launch_push_tables(ctx, s->stream, s->beams, d_ranges, d_mask_push, s->phi_min, s->ang_res);
+  rc = launch_push_tables(ctx, s->split.stream, s->beams, scan.ranges, scan.mask_push, s->phi_min, s->ang_res);
   if (rc != TSD_OK) return rc;
   lap.lap(0);
   {
@@ -687,66 +681,44 @@ int tsd_scan_begin(tsd_sensor* s, const double* ranges, const uint8_t* mask, con
     std::lock_guard<std::mutex> lk(ctx->order_mutex);
     lap.lap(1);
     TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_grid, ctx->stream));
-    TSD_HIP_CHECK(ctx, hipStreamWaitEvent(s->stream, ctx->ev_grid, 0));
-    __atomic_store_n(&s->rc_recorded, 0, __ATOMIC_RELEASE);
-    s->rc_ticket = ++ctx->ticket;
-    s->rc_event_valid = true;
+    TSD_HIP_CHECK(ctx, hipStreamWaitEvent(s->split.stream, ctx->ev_grid, 0));
+    __atomic_store_n(&s->split.rc_recorded, 0, __ATOMIC_RELEASE);
+    s->split.rc_ticket = ++ctx->ticket;
+    s->split.rc_event_valid = true;
     lap.lap(2);
   }
-  RaycastArgs ra;
-  std::memset(&ra, 0, sizeof(ra));
-  ra.beams = s->beams;
-  rc = launch_raycast(ctx, ra, &s->d_state->rc, s->d_rays);
-  const hipError_t e_rc = hipEventRecord(s->ev_rc_done, s->stream);
-  __atomic_store_n(&s->rc_recorded, 1, __ATOMIC_RELEASE);      // (always: a writer may be spinning on it)
+  rc = launch_raycast(ctx, sensor_raycast_launch_args(s), &s->d_state->rc, s->d_rays);
+  const hipError_t e_rc = hipEventRecord(s->split.ev_rc_done, s->split.stream);
+  __atomic_store_n(&s->split.rc_recorded, 1, __ATOMIC_RELEASE);      // (always: a writer may be spinning on it)
   if (rc != TSD_OK) return rc;
   if (e_rc != hipSuccess) return set_error(ctx, TSD_E_HIP, "hipEventRecord(ev_rc_done)", e_rc);
-  s->rc_pending = false;
-  IcpArgs ia;
-  const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  fill_icp_args(ia, ident, params);
-  ia.beams = s->beams; ia.ccw = s->ccw ? 1 : 0;
-  const unsigned long long seq = ++s->seq;
-  ScanPostArgs sp;
-  std::memset(&sp, 0, sizeof(sp));
-  sp.st = s->d_state; sp.rays = s->d_rays; sp.out = s->d_result; sp.seq = seq; sp.beams = s->beams;
-  sp.gmin_x = ctx->grid.min_x; sp.gmax_x = ctx->grid.max_x; sp.gmin_y = ctx->grid.min_y; sp.gmax_y = ctx->grid.max_y;
-  sp.gates = GateArgs{gates->reg_trs_max, gates->reg_sin_rot_max, gates->trs_min, gates->rot_min};
-  rc = launch_icp(ctx, ia, s->d_state->icpP, s->d_rays_local, d_ranges, d_mask, &sp);
+  s->fused.rc_pending = false;
+  const ScanPostArgs sp = sensor_post_args(s, ++s->seq, *gates);
+  rc = launch_icp(ctx, sensor_icp_args(s, params), s->d_state->icpP, s->d_rays_local, scan.ranges, scan.mask, &sp);
   if (rc != TSD_OK) return rc;
-  TSD_HIP_CHECK(ctx, hipEventRecord(s->ev_icp_done, s->stream));
-  s->conc_gates = *gates; s->conc_ranges = d_ranges; s->conc_mask_push = d_mask_push;
-  s->inflight = true;
+  TSD_HIP_CHECK(ctx, hipEventRecord(s->split.ev_icp_done, s->split.stream));
+  s->split.gates = *gates; s->split.scan = scan;
+  s->split.inflight = true;
   lap.lap(3);
   return TSD_OK;
 }
 
 int tsd_scan_wait(tsd_sensor* s)
 {
-  if (!s || !s->inflight) return TSD_E_ARG;
-  unsigned long long spins = 0;
-  while (!scan_result_arrived(s, s->seq)) {
-    if (++spins > 4000000ull) {            // something is wrong: a real wait on the sensor's stream
-      if (hipStreamSynchronize(s->stream) != hipSuccess || !scan_result_arrived(s, s->seq)) return TSD_E_HIP;
-      break;
-    }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
-  }
-  return TSD_OK;
+  if (!s || !s->split.inflight) return TSD_E_ARG;
+  return wait_arrival([&] { return scan_result_arrived(s, s->seq); }, s->split.stream, no_nudge) ? TSD_OK : TSD_E_HIP;
 }
 
 int tsd_scan_finish(tsd_sensor* s, tsd_scan_result* result)
 {
-  if (!s || !s->ctx || !result || !s->inflight) return TSD_E_ARG;
+  if (!s || !s->ctx || !result || !s->split.inflight) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (int rcd_ = drain_async_push(ctx)) return rcd_;
-  ConcLap lap;
+  Lap lap(g_conc_timing);
   int rc = tsd_scan_wait(s);
   if (rc != TSD_OK) return set_error(ctx, TSD_E_HIP, "tsd_scan_finish: result record never arrived", hipSuccess);
-  s->inflight = false;
+  s->split.inflight = false;
   lap.lap(4);
   {
     // ORDERED SECTION: the push on the grid stream -- enqueued only now, when the registration has finished, so it
@@ -756,26 +728,18 @@ int tsd_scan_finish(tsd_sensor* s, tsd_scan_result* result)
     // the last grid write.
     std::lock_guard<std::mutex> lk_order(ctx->order_mutex);
     lap.lap(5);
-    TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, s->ev_icp_done, 0));
+    TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, s->split.ev_icp_done, 0));
     if (int rcw = wait_for_readers(ctx)) return rcw;
-    PushArgs pa;
-    std::memset(&pa, 0, sizeof(pa));
-    pa.beams = s->beams;
-    pa.max_range = s->max_range;
     LaunchTarget tg;
-    tg.rmq = s->d_rmq2[s->rmq_slot];
+    tg.rmq = s->d_rmq2[s->split.rmq_slot];
     TargetScope scope(ctx, &tg);
     // the registration moves the sensor by at most the gate (a larger step is rejected: pose unchanged)
-    rc = launch_push(ctx, pa, s->pos[0], s->pos[1], s->conc_gates.reg_trs_max, &s->d_state->push, s->conc_ranges, s->conc_mask_push);
+    rc = launch_push(ctx, sensor_push_launch_args(s), s->pos[0], s->pos[1], s->split.gates.reg_trs_max, &s->d_state->push, s->split.scan.ranges, s->split.scan.mask_push);
     if (rc != TSD_OK) return rc;
     ctx->epoch++;
     lap.lap(6);
   }
-  copy_icp_result(&s->h_result->icp, &result->icp);
-  for (int i = 0; i < 9; i++) result->pose[i] = s->h_result->pose[i];
-  s->pos[0] = result->pose[2]; s->pos[1] = result->pose[5];
-  result->reg_error = s->h_result->reg_error; result->pushed = s->h_result->pushed;
-  result->no_model = s->h_result->no_model; result->reserved = 0;
+  deliver_result(s, result, 0);
   lap.lap(7); g_conc_timing.n++;
   return TSD_OK;
 }
@@ -840,7 +804,7 @@ static void batch_abandon(tsd_batch* b, bool registration_launched)
   }
   if (b->stream) hipStreamSynchronize(b->stream);
   hipStreamSynchronize(ctx->stream);
-  for (tsd_sensor* s : b->sensors) if (s) s->inflight = false;
+  for (tsd_sensor* s : b->sensors) if (s) s->split.inflight = false;
   b->n = 0; b->push_enqueued = false;
 }
 
@@ -853,7 +817,7 @@ tsd_batch* tsd_batch_create(tsd_ctx* ctx, int max_scans)
   b->ctx = ctx; b->max_scans = max_scans;
   b->head_bytes = align64((size_t)max_scans * sizeof(IcpBatchEntry)) + align64((size_t)max_scans * sizeof(RaycastBatchEntry)) +
                   align64((size_t)max_scans * sizeof(TablesBatchEntry));
-  b->scan_bytes = align64((size_t)TSD_MAX_BEAMS * 10);
+  b->scan_bytes = align64(scan_bytes(TSD_MAX_BEAMS));
   const size_t bytes = b->head_bytes + (size_t)max_scans * b->scan_bytes;
   bool ok = true;
   auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
@@ -883,7 +847,7 @@ void tsd_batch_destroy(tsd_batch* b)
     auto& v = b->ctx->batches;
     v.erase(std::remove(v.begin(), v.end(), b), v.end());
   }
-  for (tsd_sensor* s : b->sensors) if (s) s->inflight = false;
+  for (tsd_sensor* s : b->sensors) if (s) s->split.inflight = false;
   for (hipEvent_t e : {b->ev_rc_done, b->ev_icp_done, b->ev_copy_done}) if (e) hipEventDestroy(e);
   if (b->stream) hipStreamDestroy(b->stream);
   if (b->h_stage) hipHostFree(b->h_stage);
@@ -913,7 +877,7 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
     tsd_sensor* s = sensors[i];
     if (!s || s->ctx != ctx || !ranges[i] || !mask[i]) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin: sensor / scan", hipSuccess);
     if (!s->posed) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin before tsd_sensor_set_pose", hipSuccess);
-    if (s->inflight) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin: a sensor has a scan in flight already", hipSuccess);
+    if (s->split.inflight) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin: a sensor has a scan in flight already", hipSuccess);
     for (int j = 0; j < i; j++) if (sensors[j] == s) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin: a sensor appears twice", hipSuccess);
   }
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -934,44 +898,34 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
   b->seqs.resize((size_t)n); b->gates.assign(gates, gates + n); b->scan_off.resize((size_t)n);
   size_t off = b->head_bytes;
   int max_beams = 0;
-  const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   for (int i = 0; i < n; i++) {
     tsd_sensor* s = sensors[i];
-    const size_t nb = (size_t)s->beams;
     if (s->beams > max_beams) max_beams = s->beams;
-    char* h = h_base + off;
-    std::memcpy(h, ranges[i], nb * 8);
-    std::memcpy(h + nb * 8, mask[i], nb);
-    std::memcpy(h + nb * 9, (mask_push && mask_push[i]) ? mask_push[i] : mask[i], nb);
-    const double* d_ranges = reinterpret_cast<const double*>(d_base + off);
-    const uint8_t* d_mask = reinterpret_cast<const uint8_t*>(d_base + off + nb * 8);
-    const uint8_t* d_mask_push = reinterpret_cast<const uint8_t*>(d_base + off + nb * 9);
+    scan_pack(h_base + off, s->beams, ranges[i], mask[i], mask_push ? mask_push[i] : nullptr);
+    const ScanView scan = scan_view(d_base + off, s->beams);
     b->scan_off[(size_t)i] = off;
-    off += align64(nb * 10);
-    s->rmq_slot ^= 1;                       // (the previous push of this sensor may still read its tables)
-    h_tb[i] = TablesBatchEntry{d_ranges, d_mask_push, s->d_rmq2[s->rmq_slot], s->phi_min, s->ang_res, s->beams, 0};
-    h_rc[i] = RaycastBatchEntry{&s->d_state->rc, s->d_rays, s->d_coords, s->d_normals, s->d_mask_m};
+    off += align64(scan_bytes(s->beams));
+    s->split.rmq_slot ^= 1;                       // (the previous push of this sensor may still read its tables)
+    h_tb[i] = TablesBatchEntry{scan.ranges, scan.mask_push, s->d_rmq2[s->split.rmq_slot], s->phi_min, s->ang_res, s->beams, 0};
+    h_rc[i] = RaycastBatchEntry{&s->d_state->rc, s->d_rays, s->split.d_coords, s->split.d_normals, s->split.d_mask_m};
     IcpBatchEntry& e = h_icp[i];
     std::memset(&e, 0, sizeof(e));
-    fill_icp_args(e.a, ident, &params[i]);
-    e.a.beams = s->beams; e.a.ccw = s->ccw ? 1 : 0;
+    e.a = sensor_icp_args(s, &params[i]);
     // registration_mode 3 (tsd_scan_preregister armed this sensor): the registration starts from the pre-registration's result, which
     // k_pdf_argmax leaves in the sensor's own buffer (the kernels go out below, behind the batch's ray casts)
-    if (s->pre_armed) e.a.Tinit_dev = reinterpret_cast<const double*>(s->d_pre + s->pre.off_res);
-    e.P_dev = s->d_state->icpP; e.coords = s->d_coords; e.mask_m = s->d_mask_m; e.rays_local = s->d_rays_local;
-    e.ranges = d_ranges; e.mask = d_mask; e.out = s->d_icp_res; e.trace = nullptr /* no reader in the fused path */; e.normals = s->d_normals;
+    if (s->pre.armed) e.a.Tinit_dev = reinterpret_cast<const double*>(s->pre.d + s->pre.layout.off_res);
+    e.P_dev = s->d_state->icpP; e.coords = s->split.d_coords; e.mask_m = s->split.d_mask_m; e.rays_local = s->d_rays_local;
+    e.ranges = scan.ranges; e.mask = scan.mask; e.out = s->split.d_icp_res; e.trace = nullptr /* no reader in the fused path */; e.normals = s->split.d_normals;
     const unsigned long long seq = ++s->seq;
     b->seqs[(size_t)i] = seq;
-    if (!s->pre_armed) s->pre_ran = false;                 // (tsd_scan_preregistration_result: this scan has none)
-    e.post.st = s->d_state; e.post.rays = s->d_rays; e.post.out = s->d_result; e.post.seq = seq; e.post.beams = s->beams;
-    e.post.gmin_x = ctx->grid.min_x; e.post.gmax_x = ctx->grid.max_x; e.post.gmin_y = ctx->grid.min_y; e.post.gmax_y = ctx->grid.max_y;
-    e.post.gates = GateArgs{gates[i].reg_trs_max, gates[i].reg_sin_rot_max, gates[i].trs_min, gates[i].rot_min};
+    if (!s->pre.armed) s->pre.ran = false;                 // (tsd_scan_preregistration_result: this scan has none)
+    e.post = sensor_post_args(s, seq, gates[i]);
     e.post.publish_done = 1;               // (tsd_batch_push gates this robot's push on it)
   }
   // (step 0's searches on helper workgroups: measured worth it for batches of up to four registrations -- +6 % scans/s at two per batch,
   // even at four, -2 to -10 % at eight, where forty more polling workgroups sit beside the ray casts)
   for (int i = 0; i < n; i++) {
-    h_icp[i].seed = icp_batch_seed_args(ctx, sensors[i]->d_icp_seed, sensors[i]->beams, max_beams);
+    h_icp[i].seed = icp_batch_seed_args(ctx, sensors[i]->split.d_icp_seed, sensors[i]->beams, max_beams);
     if (n > 4) h_icp[i].seed.helpers = 0;
   }
   // the registrations go out AHEAD of the ray casts and wait for the slot's flag on the device (where the probe allowed it).
@@ -979,7 +933,7 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
   // event instead: the pre-registration kernels sit between the ray casts and the registrations, on the grid's stream -- the scoring
   // reads the grid, like the ray casts, and takes its place between the pushes the same way.
   bool any_pre = false;
-  for (int i = 0; i < n; i++) any_pre |= sensors[i]->pre_armed;
+  for (int i = 0; i < n; i++) any_pre |= sensors[i]->pre.armed;
   const bool dev_wait = b->dev_wait && !any_pre;
   if (dev_wait) {
     b->rc_batches++;
@@ -1020,10 +974,10 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
       // model its ray cast just produced; all of them score against the grid as it is before any push of this batch
       // (four launches for all of them: launch_preregistration_batch)
       std::vector<tsd_sensor*> armed;
-      for (int i = 0; i < n; i++) if (sensors[i]->pre_armed) armed.push_back(sensors[i]);
+      for (int i = 0; i < n; i++) if (sensors[i]->pre.armed) armed.push_back(sensors[i]);
       rc = launch_preregistration_batch(ctx, ctx->stream, armed.data(), (int)armed.size());
       if (rc != TSD_OK) return FAIL(rc);
-      for (tsd_sensor* s : armed) { s->pre_armed = false; s->pre_ran = true; }
+      for (tsd_sensor* s : armed) { s->pre.armed = false; s->pre.ran = true; }
     }
     if (dev_wait) {
       rc = launch_set_flag(ctx, ctx->stream, b->d_rc_flag, b->rc_batches);
@@ -1039,7 +993,7 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
     icp_launched = true;
   }
   if (hipEventRecord(b->ev_icp_done, b->stream) != hipSuccess) return FAIL(set_error(ctx, TSD_E_HIP, "tsd_batch_begin: event", hipGetLastError()));
-  for (int i = 0; i < n; i++) { sensors[i]->inflight = true; sensors[i]->rc_pending = false; }
+  for (int i = 0; i < n; i++) { sensors[i]->split.inflight = true; sensors[i]->fused.rc_pending = false; }
   b->n = n; b->push_enqueued = false;
   return TSD_OK;
 }
@@ -1064,11 +1018,10 @@ int tsd_batch_push(tsd_batch* b)
     double cx[16], cy[16], sl[16], mr[16]; int bm[16];
     for (int i = 0; i < n; i++) {
       tsd_sensor* s = b->sensors[(size_t)i];
-      const size_t nb = (size_t)s->beams;
-      const char* d_scan = b->d_stage_cur + b->scan_off[(size_t)i];
+      const ScanView scan = scan_view(b->d_stage_cur + b->scan_off[(size_t)i], s->beams);
       seqp[i] = &s->d_state->done_seq; seqv[i] = b->seqs[(size_t)i]; pushp[i] = &s->d_state->push;
-      ap[i] = &s->d_state->push; rg[i] = reinterpret_cast<const double*>(d_scan); mk[i] = reinterpret_cast<const uint8_t*>(d_scan + nb * 9);
-      rq[i] = s->d_rmq2[s->rmq_slot];
+      ap[i] = &s->d_state->push; rg[i] = scan.ranges; mk[i] = scan.mask_push;
+      rq[i] = s->d_rmq2[s->split.rmq_slot];
       cx[i] = s->pos[0]; cy[i] = s->pos[1]; sl[i] = b->gates[(size_t)i].reg_trs_max; mr[i] = s->max_range; bm[i] = s->beams;
     }
     if (gate) { if (int rcg = launch_wait_seq_multi(ctx, n, seqp, seqv, pushp, b->d_gate_err, b->poll_bound)) return rcg; }
@@ -1082,19 +1035,14 @@ int tsd_batch_push(tsd_batch* b)
     // robot i's push starts when robot i's registration is done (its epilogue has left the push arguments and published the
     // scan's sequence number), not when the slowest registration of the batch is
     if (gate) { if (int rcg = launch_wait_seq(ctx, &s->d_state->done_seq, b->seqs[(size_t)i], &s->d_state->push, b->d_gate_err, b->poll_bound)) return rcg; }
-    const size_t nb = (size_t)s->beams;
-    PushArgs pa;
-    std::memset(&pa, 0, sizeof(pa));
-    pa.beams = s->beams;
-    pa.max_range = s->max_range;
     LaunchTarget tg;
-    tg.rmq = s->d_rmq2[s->rmq_slot];
+    tg.rmq = s->d_rmq2[s->split.rmq_slot];
     TargetScope scope(ctx, &tg);
-    const char* d_scan = b->d_stage_cur + b->scan_off[(size_t)i];
+    const ScanView scan = scan_view(b->d_stage_cur + b->scan_off[(size_t)i], s->beams);
     // the registration moves the sensor by at most the gate (a larger step is rejected: pose unchanged); s->pos is the
     // position after the previous scan, which the host has seen
-    int rc = launch_push(ctx, pa, s->pos[0], s->pos[1], b->gates[(size_t)i].reg_trs_max, &s->d_state->push,
-                         reinterpret_cast<const double*>(d_scan), reinterpret_cast<const uint8_t*>(d_scan + nb * 9));
+    int rc = launch_push(ctx, sensor_push_launch_args(s), s->pos[0], s->pos[1], b->gates[(size_t)i].reg_trs_max, &s->d_state->push,
+                         scan.ranges, scan.mask_push);
     if (rc != TSD_OK) return rc;
   }
   ctx->epoch++;
@@ -1115,32 +1063,19 @@ int tsd_batch_results(tsd_batch* b, tsd_scan_result* results)
   if (!b || !b->ctx || !results) return TSD_E_ARG;
   tsd_ctx* ctx = b->ctx;
   if (!b->n) return set_error(ctx, TSD_E_ARG, "tsd_batch_results without tsd_batch_begin", hipSuccess);
-  unsigned long long spins = 0;
-  while (tsd_batch_poll(b) != 1) {
-    if (++spins > 4000000ull) {              // something is wrong: a real wait on the batch's stream
-      if (hipStreamSynchronize(b->stream) != hipSuccess || tsd_batch_poll(b) != 1) {
-        batch_abandon(b, true);              // (the slot and its sensors are usable again; this batch's scans are lost)
-        return set_error(ctx, TSD_E_HIP, "tsd_batch_results: result records never arrived", hipSuccess);
-      }
-      break;
-    }
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#endif
+  if (!wait_arrival([&] { return tsd_batch_poll(b) == 1; }, b->stream, no_nudge)) {
+    batch_abandon(b, true);                // (the slot and its sensors are usable again; this batch's scans are lost)
+    return set_error(ctx, TSD_E_HIP, "tsd_batch_results: result records never arrived", hipSuccess);
   }
   int rc = tsd_batch_push(b);               // (no-op when the caller enqueued the pushes ahead of the results)
   if (rc != TSD_OK) { batch_abandon(b, true); return rc; }
   int failed = 0;
   for (int i = 0; i < b->n; i++) {
     tsd_sensor* s = b->sensors[(size_t)i];
-    tsd_scan_result* r = &results[i];
-    copy_icp_result(&s->h_result->icp, &r->icp);
-    for (int k = 0; k < 9; k++) r->pose[k] = s->h_result->pose[k];
-    r->reg_error = s->h_result->reg_error; r->pushed = s->h_result->pushed;
-    r->no_model = s->h_result->no_model; r->reserved = s->h_result->reserved;
-    if (r->reserved != 0) failed = r->reserved;       // this robot's registration never ran (k_icp_batch): flagged, pose untouched
-    else { s->pos[0] = r->pose[2]; s->pos[1] = r->pose[5]; }
-    s->inflight = false;
+    // reserved != 0: this robot's registration never ran (k_icp_batch): flagged to the caller, the sensor's position untouched
+    deliver_result(s, &results[i], s->h_result->reserved);
+    if (results[i].reserved != 0) failed = results[i].reserved;
+    s->split.inflight = false;
   }
   b->n = 0;
   if (failed) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <cstring>
 #include <string>
 #include <vector>
 #include <map>
@@ -153,6 +154,24 @@ constexpr int BATCH_FAIL_TIMEOUT = 1;    // its ray casts never reported done wi
 constexpr int BATCH_FAIL_ABORTED = 2;    // the host abandoned the batch
 constexpr unsigned int BATCH_POLL_BOUND = 1u << 21;   // ~2 s
 
+// A scan as it lies in every scan buffer (the sensors', the batches' staging): ranges[beams] | mask[beams] | mask_push[beams].
+struct ScanView { const double* ranges; const uint8_t* mask; const uint8_t* mask_push; };
+constexpr size_t scan_bytes(int beams) { return (size_t)beams * 10; }            // what a copy of a scan moves
+constexpr size_t scan_alloc_bytes(int beams) { return scan_bytes(beams) + 64; }   // what a buffer for one scan is allocated with
+inline ScanView scan_view(const char* base, int beams)
+{
+  const size_t nb = (size_t)beams;
+  return ScanView{reinterpret_cast<const double*>(base), reinterpret_cast<const uint8_t*>(base + nb * 8), reinterpret_cast<const uint8_t*>(base + nb * 9)};
+}
+// (a scan without a mask of its own for the push is pushed with the registration's)
+inline void scan_pack(char* dst, int beams, const double* ranges, const uint8_t* mask, const uint8_t* mask_push)
+{
+  const size_t nb = (size_t)beams;
+  std::memcpy(dst, ranges, nb * 8);
+  std::memcpy(dst + nb * 8, mask, nb);
+  std::memcpy(dst + nb * 9, mask_push ? mask_push : mask, nb);
+}
+
 constexpr size_t KERNEL_TIMER_SAMPLES = 65536;
 struct KernelTimer {
   double total_ms = 0.0;
@@ -273,7 +292,7 @@ struct tsd_ctx {
   std::vector<hipEvent_t> event_pool;
 };
 
-// device-resident sensor of one robot (tsd_sensor_* / tsd_scan in include/tsd_hip.h)
+// device-resident sensor of one robot (tsd_sensor_* / tsd_scan in include/tsd_hip.h): what every scan path uses, then one member per path
 struct tsd_sensor {
   tsd_ctx* ctx = nullptr;
   int beams = 0;
@@ -283,80 +302,97 @@ struct tsd_sensor {
   tsd::SensorDev* d_state = nullptr;
   double* d_rays = nullptr;        // [2*beams] world rays, normalised to the cell size
   double* d_rays_local = nullptr;  // [2*beams]
-  char* d_scan2[3] = {nullptr, nullptr, nullptr};   // ranges[beams] | mask[beams] | mask_push[beams], used in turn (split scan: 0 / 1)
-  // The same three scans in pinned host memory, where the caller's arrays are copied first.  A scan that was NOT staged ahead is read
-  // by its registration from here, over the host link (10 KB, requested at once at the top of k_icp): the registration is launched as
-  // soon as the scan is in this buffer, and the device copy + the push's range tables follow on the side stream beside it.
-  char* h_scan3[3] = {nullptr, nullptr, nullptr};
-  char* hd_scan3[3] = {nullptr, nullptr, nullptr};  // device addresses of h_scan3
-  hipEvent_t ev_scan_copy[3] = {nullptr, nullptr, nullptr};   // "the device copy out of h_scan3[i] is done" (before the host rewrites it)
-  bool scan_copy_valid[3] = {false, false, false};
-  const double* st_h_ranges = nullptr; const uint8_t* st_h_mask = nullptr;   // the staged scan's ranges / mask in h_scan3 (device addresses)
-  // Where the device's memory is mapped into the host's address space (large PCIe BAR: every MI300-class server), d_scan2[] is
-  // fine-grained device memory and the HOST writes a scan straight into it: no pinned copy, no device copy, and the registration reads
-  // its 10 KB from local memory (1 us) instead of over the host link (3.5-4 us at the top of every registration: tools/exp/bar.hip).
-  bool scan_bar = false;
-  unsigned int* h_bar_mismatch = nullptr;   // TSD_SCAN_BAR_VERIFY=1: bytes in which a scan's two copies differed on the device (pinned, coherent)
-  unsigned int* d_bar_mismatch = nullptr;   // ... its device address
-  bool st_device_done = false;     // the staged scan's device copy and tables are enqueued
-  int scan_slot = 0;
   tsd::ScanResultDev* h_result = nullptr;   // the last record that arrived, decoded (ordinary host memory)
   unsigned long long* h_rwords = nullptr;   // pinned, coherent: SCAN_RESULT_WORDS tagged words, written by the registration's epilogue
   tsd::ScanResultDev* d_result = nullptr;   // device address of h_rwords (ScanPostArgs::out)
   unsigned long long seq = 0;
   double pos[2] = {0, 0};          // host mirror of the sensor position (window of the push launches)
-  // tsd_scan_stage / _submit / _collect: the scan that is staged (copied, tables built) and not yet submitted
-  bool staged = false, submitted = false;
-  const double* st_ranges = nullptr; const uint8_t* st_mask = nullptr; const uint8_t* st_mask_push = nullptr;
-  char* st_rmq = nullptr; int st_slot = 0;
-  int stage_slot = 0;              // the scan / table buffers are used in turn, THREE of them: the scan staged ahead of scan k+2 goes
-                                   // where scan k was, and by then the host has seen the result of scan k+1, whose ray cast ran behind
-                                   // the push of scan k on the stream -- so that push is done without any event on the stream.
-                                   // That argument needs the STRICT order.  With asynchronous mapping ray cast k+1 runs behind push
-                                   // k-1 and push k beside registration k+1 on the push stream: the host has no proof that it is
-                                   // done, so the staging waits for the buffer's own push event (below).
-  hipEvent_t ev_slot_push[3] = {nullptr, nullptr, nullptr};   // asynchronous mapping: "the push that read buffer i is done"
-  bool slot_push_valid[3] = {false, false, false};            // ... recorded and not yet seen complete
+  // Shared by the fused and the split path: scan buffers (tsd::ScanView's layout), used in turn -- all three by the fused path
+  // (fused.stage_slot), 0 / 1 by the split path (split.scan_slot) -- and the range-query tables of a scan's push, in turn likewise
+  // (fused.stage_slot; split and batched path: 0 / 1 by split.rmq_slot).  The tables are allocated on first use (split.ready).
+  char* d_scan2[3] = {nullptr, nullptr, nullptr};
+  char* d_rmq2[3] = {nullptr, nullptr, nullptr};
+  // Where the device's memory is mapped into the host's address space (large PCIe BAR: every MI300-class server), d_scan2[] is
+  // fine-grained device memory and the HOST writes a scan straight into it: no pinned copy, no device copy, and the registration reads
+  // its 10 KB from local memory (1 us) instead of over the host link (3.5-4 us at the top of every registration: tools/exp/bar.hip).
+  bool scan_bar = false;
+
+  // tsd_scan_stage / _submit / _collect
+  struct Fused {
+    // The same three scans in pinned host memory, where the caller's arrays are copied first.  A scan that was NOT staged ahead is read
+    // by its registration from here, over the host link (10 KB, requested at once at the top of k_icp): the registration is launched as
+    // soon as the scan is in this buffer, and the device copy + the push's range tables follow on the side stream beside it.
+    char* h_scan3[3] = {nullptr, nullptr, nullptr};
+    char* hd_scan3[3] = {nullptr, nullptr, nullptr};  // device addresses of h_scan3
+    hipEvent_t ev_scan_copy[3] = {nullptr, nullptr, nullptr};   // "the device copy out of h_scan3[i] is done" (before the host rewrites it)
+    bool scan_copy_valid[3] = {false, false, false};
+    unsigned int* h_bar_mismatch = nullptr;   // TSD_SCAN_BAR_VERIFY=1: bytes in which a scan's two copies differed on the device (pinned, coherent)
+    unsigned int* d_bar_mismatch = nullptr;   // ... its device address
+    // the scan that is staged (copied, tables built) and not yet submitted
+    bool staged = false, submitted = false;
+    tsd::ScanView scan{};            // in d_scan2[slot]
+    tsd::ScanView h_scan{};          // its ranges / mask in h_scan3[slot] (device addresses; scan_bar: the same as `scan`)
+    char* rmq = nullptr; int slot = 0;
+    bool device_done = false;        // the staged scan's device copy and tables are enqueued
+    int stage_slot = 0;              // the scan / table buffers are used in turn, THREE of them: the scan staged ahead of scan k+2 goes
+                                     // where scan k was, and by then the host has seen the result of scan k+1, whose ray cast ran behind
+                                     // the push of scan k on the stream -- so that push is done without any event on the stream.
+                                     // That argument needs the STRICT order.  With asynchronous mapping ray cast k+1 runs behind push
+                                     // k-1 and push k beside registration k+1 on the push stream: the host has no proof that it is
+                                     // done, so the staging waits for the buffer's own push event (async.ev_slot_push).
+    bool rc_pending = false;         // the next scan's ray cast was enqueued behind this scan's push ...
+    unsigned long long rc_epoch = 0; // ... when the context was in this state
+  } fused;
+
+  // asynchronous mapping of the fused path (tsd_sensor_set_async_mapping)
+  struct Async {
+    bool mapping = false;
+    tsd::PushArgs* d_push_slot = nullptr;     // [2] push arguments by scan parity
+    hipEvent_t ev_slot_push[3] = {nullptr, nullptr, nullptr};   // "the push that read buffer i is done"
+    bool slot_push_valid[3] = {false, false, false};            // ... recorded and not yet seen complete
+  } async;
+
   // fused registration_mode 3 (tsd_scan_preregister, tsdpdf.hip): inputs of the pre-registration that the next tsd_scan_submit runs
   // on the device between its ray cast and its registration; one device + one pinned buffer, grown on demand
-  char* d_pre = nullptr; char* h_pre = nullptr; size_t pre_bytes = 0;
-  char* h_pre_dev = nullptr;                // h_pre as the device sees it (looked up once per allocation)
-  hipEvent_t ev_pre_done = nullptr;         // the in-flight scan's pre-registration kernels have read their inputs (the arg-max's own stop event)
-  bool pre_done_valid = false;
-  size_t pre_res_off_hdr = 0, pre_res_off_res = 0;      // where the collected scan's header / result are in h_pre (the layout may be re-armed meanwhile)
-  bool async_mapping = false;               // tsd_sensor_set_async_mapping
-  tsd::PushArgs* d_push_slot = nullptr;          // [2] push arguments by scan parity (asynchronous mapping)
-  hipEvent_t ev_pre = nullptr;              // the pre-registration's inputs are on the device (copied on the side stream by tsd_scan_preregister)
-  bool pre_copied = false;
-  bool pre_bar = false;       // d_pre is fine-grained device memory (tsd_sensor::scan_bar) ...
-  bool pre_direct = false;    // ... and the armed inputs were stored into it by the host: nothing to copy, nothing to wait for
-  bool pre_armed = false, pre_ran = false;
-  unsigned int* d_pre_flag = nullptr;        // k_icp_pre: the launch number of the last arg-max whose TBest stands (its own small allocation)
-  unsigned int pre_seq = 0;
   struct PreLayout {
     size_t off_S, off_ms, off_msp, off_dc, off_dt, in_bytes;             // inputs (host -> device each scan)
     size_t off_mo_m, off_mo_s, off_phi_m, off_phi_s, off_C, off_K, off_prob, off_hdr, off_res;
     int n, span, trials, size_control_set, max_cand;
     double phi_max, zrand;
-  } pre{};
-  bool rc_pending = false;         // the next scan's ray cast was enqueued behind this scan's push ...
-  unsigned long long rc_epoch = 0; // ... when the context was in this state
+  };
+  struct Pre {
+    char* d = nullptr; char* h = nullptr; size_t bytes = 0;
+    char* h_dev = nullptr;                    // `h` as the device sees it (looked up once per allocation)
+    hipEvent_t ev_done = nullptr;             // the in-flight scan's pre-registration kernels have read their inputs (the arg-max's own stop event)
+    bool done_valid = false;
+    size_t res_off_hdr = 0, res_off_res = 0;  // where the collected scan's header / result are in `h` (the layout may be re-armed meanwhile)
+    hipEvent_t ev = nullptr;                  // the pre-registration's inputs are on the device (copied on the side stream by tsd_scan_preregister)
+    bool copied = false;
+    bool bar = false;         // `d` is fine-grained device memory (tsd_sensor::scan_bar) ...
+    bool direct = false;      // ... and the armed inputs were stored into it by the host: nothing to copy, nothing to wait for
+    bool armed = false, ran = false;
+    unsigned int* d_flag = nullptr;           // k_icp_pre: the launch number of the last arg-max whose TBest stands (its own small allocation)
+    unsigned int seq = 0;
+    PreLayout layout{};
+  } pre;
 
-  // concurrent multi-robot path (tsd_scan_begin / tsd_scan_wait / tsd_scan_finish): ray cast + registration on the
-  // sensor's own stream into its own buffers, created on first use
-  bool conc_ready = false;
-  hipStream_t stream = nullptr;      // ONE stream per sensor: streams are multiplexed onto a few in-order hardware queues
-  hipEvent_t ev_rc_done = nullptr, ev_icp_done = nullptr;
-  bool rc_event_valid = false;     // ev_rc_done has been recorded at least once
-  unsigned long long rc_ticket = 0;            // ticket of the sensor's most recent ray cast ...
-  volatile int rc_recorded = 1;                // ... whose ev_rc_done record has been issued (by the sensor's own thread)
-  double* d_coords = nullptr; double* d_normals = nullptr; uint8_t* d_mask_m = nullptr;
-  tsd::IcpResultDev* d_icp_res = nullptr; double* d_icp_trace = nullptr; void* d_icp_seed = nullptr;
-  char* d_rmq2[3] = {nullptr, nullptr, nullptr}; int rmq_slot = 0;
-  char* h_stage2[2] = {nullptr, nullptr};   // pinned staging of the scan, alternating
-  bool inflight = false;           // begin() without finish()
-  tsd_gate_params conc_gates{};
-  const double* conc_ranges = nullptr; const uint8_t* conc_mask_push = nullptr;
+  // concurrent multi-robot path (tsd_scan_begin / tsd_scan_wait / tsd_scan_finish): ray cast + registration on the sensor's own stream
+  // into its own buffers, created on first use.  The batched path (tsd_batch_*) uses the buffers, `rmq_slot` and `inflight` as well.
+  struct Split {
+    bool ready = false;
+    hipStream_t stream = nullptr;      // ONE stream per sensor: streams are multiplexed onto a few in-order hardware queues
+    hipEvent_t ev_rc_done = nullptr, ev_icp_done = nullptr;
+    bool rc_event_valid = false;     // ev_rc_done has been recorded at least once
+    unsigned long long rc_ticket = 0;            // ticket of the sensor's most recent ray cast ...
+    volatile int rc_recorded = 1;                // ... whose ev_rc_done record has been issued (by the sensor's own thread)
+    double* d_coords = nullptr; double* d_normals = nullptr; uint8_t* d_mask_m = nullptr;
+    tsd::IcpResultDev* d_icp_res = nullptr; double* d_icp_trace = nullptr; void* d_icp_seed = nullptr;
+    int scan_slot = 0, rmq_slot = 0;
+    char* h_stage2[2] = {nullptr, nullptr};   // pinned staging of the scan, alternating
+    bool inflight = false;           // begin() without finish()
+    tsd_gate_params gates{};         // of the scan in flight, and where its push finds ranges / mask_push
+    tsd::ScanView scan{};
+  } split;
 };
 
 // one batch slot of the multi-robot path (tsd_batch_* in include/tsd_hip.h): its own stream, events and staging

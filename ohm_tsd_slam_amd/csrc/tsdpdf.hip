@@ -920,13 +920,13 @@ extern "C" int tsd_scan_preregister(tsd_sensor* s, const tsd_tsdpdf_params* prm,
   if (!(prm->ang_res > 1e-6)) return set_error(ctx, TSD_E_ARG, "tsd_scan_preregister: resolution not properly set", hipSuccess);
   // A scan of this sensor may be IN FLIGHT (submitted, not collected): the pre-registration of the scan after it is then armed ahead --
   // its inputs are copied behind that scan's own pre-registration kernels (which read the same device buffer), beside its registration.
-  const bool inflight = s->submitted;
-  if (s->inflight) return set_error(ctx, TSD_E_ARG, "tsd_scan_preregister: the sensor has a batched / split scan in flight (arm it between two scans)", hipSuccess);
+  const bool inflight = s->fused.submitted;
+  if (s->split.inflight) return set_error(ctx, TSD_E_ARG, "tsd_scan_preregister: the sensor has a batched / split scan in flight (arm it between two scans)", hipSuccess);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   // The last side-stream copy out of the pinned buffer has to have left it before the host rewrites it (and, BAR mode, before the host
   // stores into d_pre itself).  That copy belongs to the in-flight scan -- or to a pre-registration that was armed ahead while a scan
   // was in flight and is now being RE-armed without having been submitted: nothing the host has seen is ordered behind that one.
-  if (s->ev_pre && s->pre_copied && !s->pre_direct) TSD_HIP_CHECK(ctx, hipEventSynchronize(s->ev_pre));
+  if (s->pre.ev && s->pre.copied && !s->pre.direct) TSD_HIP_CHECK(ctx, hipEventSynchronize(s->pre.ev));
   tsd_sensor::PreLayout L{};
   L.n = n; L.trials = prm->trials; L.size_control_set = prm->size_control_set; L.zrand = prm->zrand;
   L.phi_max = std::min(prm->phi_max, M_PI * 0.5);
@@ -946,24 +946,24 @@ extern "C" int tsd_scan_preregister(tsd_sensor* s, const tsd_tsdpdf_params* prm,
   // The in-flight scan's arg-max writes its header and result into the PINNED buffer at the offsets of ITS layout (pre_res_off_*),
   // and tsd_scan_preregistration_result reads them there after the collect: a layout that needs new buffers, or whose inputs would
   // reach into those records, cannot be armed ahead -- the caller arms it after tsd_scan_collect.
-  if (inflight && s->pre_ran && (total > s->pre_bytes || L.in_bytes > s->pre_res_off_hdr))
+  if (inflight && s->pre.ran && (total > s->pre.bytes || L.in_bytes > s->pre.res_off_hdr))
     return set_error(ctx, TSD_E_ARG, "tsd_scan_preregister: a larger layout than the in-flight scan's cannot be armed ahead of its collect", hipSuccess);
-  if (total > s->pre_bytes) {
+  if (total > s->pre.bytes) {
     TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream2));      // (an armed, not yet submitted pre-registration's copy may still read the old buffer)
-    if (s->d_pre) hipFree(s->d_pre);
-    if (s->h_pre) hipHostFree(s->h_pre);
-    s->d_pre = nullptr; s->h_pre = nullptr; s->pre_bytes = 0;
-    s->pre_bar = false;
-    if (s->scan_bar && hipExtMallocWithFlags((void**)&s->d_pre, total, hipDeviceMallocFinegrained) == hipSuccess) s->pre_bar = true;
-    else { (void)hipGetLastError(); s->d_pre = nullptr; }
-    if (!s->pre_bar) TSD_HIP_CHECK(ctx, hipMalloc(&s->d_pre, total));
-    TSD_HIP_CHECK(ctx, hipHostMalloc(&s->h_pre, total, hipHostMallocDefault));
-    TSD_HIP_CHECK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&s->h_pre_dev), s->h_pre, 0));
-    s->pre_bytes = total;
+    if (s->pre.d) hipFree(s->pre.d);
+    if (s->pre.h) hipHostFree(s->pre.h);
+    s->pre.d = nullptr; s->pre.h = nullptr; s->pre.bytes = 0;
+    s->pre.bar = false;
+    if (s->scan_bar && hipExtMallocWithFlags((void**)&s->pre.d, total, hipDeviceMallocFinegrained) == hipSuccess) s->pre.bar = true;
+    else { (void)hipGetLastError(); s->pre.d = nullptr; }
+    if (!s->pre.bar) TSD_HIP_CHECK(ctx, hipMalloc(&s->pre.d, total));
+    TSD_HIP_CHECK(ctx, hipHostMalloc(&s->pre.h, total, hipHostMallocDefault));
+    TSD_HIP_CHECK(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&s->pre.h_dev), s->pre.h, 0));
+    s->pre.bytes = total;
   }
   // (the pinned buffer is free: the previous scan was collected, i.e. its copy from here and its read-back have completed)
-  char* h = s->h_pre;
+  char* h = s->pre.h;
   std::memcpy(h + L.off_S, scene_xy_2B, bM);
   std::memcpy(h + L.off_ms, mask_s, (size_t)n);
   uint8_t* mSp = reinterpret_cast<uint8_t*>(h + L.off_msp);
@@ -979,47 +979,47 @@ extern "C" int tsd_scan_preregister(tsd_sensor* s, const tsd_tsdpdf_params* prm,
   }
   std::memcpy(h + L.off_dc, draws_control, (size_t)prm->size_control_set * 4);
   std::memcpy(h + L.off_dt, draws_trials, (size_t)prm->trials * 4);
-  s->pre = L;
+  s->pre.layout = L;
   // The inputs go to the device NOW, on the side stream: the caller is between two scans -- the previous scan's push and this scan's ray
   // cast are still running on the main stream -- so the copy (6 us on a DMA engine + ~9 us until a kernel behind it on the same stream
   // starts) is off the scan's chain.  The previous scan's kernels that read d_pre ran ahead of its registration, which has ended (the
   // scan was collected).  TSD_PRE_COPY_MAIN=1: the copy at tsd_scan_submit, on the main stream (round 3's first form; A/B).
   static const bool copy_main = [] { const char* e = std::getenv("TSD_PRE_COPY_MAIN"); return e && *e == '1'; }();
-  s->pre_copied = false; s->pre_direct = false;
-  if (s->pre_bar && !inflight && !copy_main) {
+  s->pre.copied = false; s->pre.direct = false;
+  if (s->pre.bar && !inflight && !copy_main) {
     // the host stores the inputs into the device buffer itself (the previous scan was collected: nothing on the device reads it)
-    std::memcpy(s->d_pre, s->h_pre, L.in_bytes);
+    std::memcpy(s->pre.d, s->pre.h, L.in_bytes);
 #if defined(__x86_64__)
     _mm_sfence();
 #endif
-    s->pre_copied = true; s->pre_direct = true;
-    s->pre_armed = true;
+    s->pre.copied = true; s->pre.direct = true;
+    s->pre.armed = true;
     return TSD_OK;
   }
   if (copy_main && inflight) return set_error(ctx, TSD_E_ARG, "tsd_scan_preregister ahead of the collect needs the side-stream copy (TSD_PRE_COPY_MAIN is set)", hipSuccess);
   if (!copy_main) {
-    if (inflight && s->pre_done_valid) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, s->ev_pre_done, 0));
-    if (!s->ev_pre) TSD_HIP_CHECK(ctx, hipEventCreateWithFlags(&s->ev_pre, hipEventDisableTiming));
-    TSD_HIP_CHECK(ctx, hipMemcpyAsync(s->d_pre, s->h_pre, L.in_bytes, hipMemcpyHostToDevice, ctx->stream2));
-    TSD_HIP_CHECK(ctx, hipEventRecord(s->ev_pre, ctx->stream2));
+    if (inflight && s->pre.done_valid) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, s->pre.ev_done, 0));
+    if (!s->pre.ev) TSD_HIP_CHECK(ctx, hipEventCreateWithFlags(&s->pre.ev, hipEventDisableTiming));
+    TSD_HIP_CHECK(ctx, hipMemcpyAsync(s->pre.d, s->pre.h, L.in_bytes, hipMemcpyHostToDevice, ctx->stream2));
+    TSD_HIP_CHECK(ctx, hipEventRecord(s->pre.ev, ctx->stream2));
     (void)hipStreamQuery(ctx->stream2);
-    s->pre_copied = true;
+    s->pre.copied = true;
   }
-  s->pre_armed = true;
+  s->pre.armed = true;
   return TSD_OK;
 }
 
 namespace tsd {
-// the four kernels' arguments of one sensor's armed pre-registration (its layout in s->d_pre, the ray cast's outputs, the pose)
+// the four kernels' arguments of one sensor's armed pre-registration (its layout in s->pre.d, the ray cast's outputs, the pose)
 struct PreLaunch {
   PdfNormalsEntry normals; PdfPrepareArgs prepare; PdfScoreEntry score; PdfArgmaxEntry argmax;
   size_t prep_lds; int score_blocks;
 };
 static PreLaunch pre_launch_args(const tsd_sensor* s, const double* d_coords, const uint8_t* d_mask_m, const double* d_pose6)
 {
-  const tsd_sensor::PreLayout& L = s->pre;
-  char* d = s->d_pre;
-  char* h_dev = s->h_pre_dev;               // the pinned buffer as the device sees it (header + result are written there by k_pdf_argmax)
+  const tsd_sensor::PreLayout& L = s->pre.layout;
+  char* d = s->pre.d;
+  char* h_dev = s->pre.h_dev;               // the pinned buffer as the device sees it (header + result are written there by k_pdf_argmax)
   const int n = L.n, SR = 10 / 2;
   PreLaunch pl;
   pl.normals.set0 = PdfNormalsSet{d_coords, d_mask_m, d_mask_m, reinterpret_cast<uint8_t*>(d + L.off_mo_m), reinterpret_cast<double*>(d + L.off_phi_m)};
@@ -1051,18 +1051,18 @@ static PreLaunch pre_launch_args(const tsd_sensor* s, const double* d_coords, co
 // by event) or, where that was switched off, here
 static int pre_inputs_ready(tsd_ctx* ctx, tsd_sensor* s, hipStream_t stream)
 {
-  if (s->pre_direct) return TSD_OK;
-  if (!s->pre_copied) TSD_HIP_CHECK(ctx, hipMemcpyAsync(s->d_pre, s->h_pre, s->pre.in_bytes, hipMemcpyHostToDevice, stream));
-  else if (hipEventQuery(s->ev_pre) != hipSuccess) {
+  if (s->pre.direct) return TSD_OK;
+  if (!s->pre.copied) TSD_HIP_CHECK(ctx, hipMemcpyAsync(s->pre.d, s->pre.h, s->pre.layout.in_bytes, hipMemcpyHostToDevice, stream));
+  else if (hipEventQuery(s->pre.ev) != hipSuccess) {
     (void)hipGetLastError();                 // (hipErrorNotReady is sticky as "last error")
-    TSD_HIP_CHECK(ctx, hipStreamWaitEvent(stream, s->ev_pre, 0));
+    TSD_HIP_CHECK(ctx, hipStreamWaitEvent(stream, s->pre.ev, 0));
   }
   return TSD_OK;
 }
 int launch_preregistration(tsd_ctx* ctx, tsd_sensor* s, hipStream_t stream, const double* d_coords, const uint8_t* d_mask_m,
                            const double* d_pose6, const double** tinit_dev, hipEvent_t before_score, IcpPreLaunch* fold)
 {
-  const tsd_sensor::PreLayout& L = s->pre;
+  const tsd_sensor::PreLayout& L = s->pre.layout;
   if (int rc = pre_inputs_ready(ctx, s, stream)) return rc;
   const PreLaunch pl = pre_launch_args(s, d_coords, d_mask_m, d_pose6);
   // (k_pdf_prepare's static LDS is ~33 KB; beyond ~3 000 beams the dynamic part needs the attribute)
@@ -1077,28 +1077,28 @@ int launch_preregistration(tsd_ctx* ctx, tsd_sensor* s, hipStream_t stream, cons
                        pl.score.control, 0, pl.score.cand, 0, pl.score.zrand, pl.score.prob, pl.score.hdr, pl.score.max_cand, pl.score.control_alloc);
     // (the arg-max's own completion is the event a pre-registration armed AHEAD waits for before it overwrites the inputs: no marker
     // between this kernel and the registration)
-    if (!s->ev_pre_done) TSD_HIP_CHECK(ctx, hipEventCreateWithFlags(&s->ev_pre_done, hipEventDisableTiming | hipEventDisableSystemFence));
+    if (!s->pre.ev_done) TSD_HIP_CHECK(ctx, hipEventCreateWithFlags(&s->pre.ev_done, hipEventDisableTiming | hipEventDisableSystemFence));
     if (fold) {
       // the arg-max rides as the first workgroup of the registration's launch (k_icp_pre); its outcome is announced through a flag word
-      if (!s->d_pre_flag) {
-        TSD_HIP_CHECK(ctx, hipMalloc(&s->d_pre_flag, 128));
-        TSD_HIP_CHECK(ctx, hipMemsetAsync(s->d_pre_flag, 0, 128, stream));
+      if (!s->pre.d_flag) {
+        TSD_HIP_CHECK(ctx, hipMalloc(&s->pre.d_flag, 128));
+        TSD_HIP_CHECK(ctx, hipMemsetAsync(s->pre.d_flag, 0, 128, stream));
       }
-      if (++s->pre_seq == 0u) ++s->pre_seq;
-      fold->dev.am = pl.argmax; fold->dev.flag = s->d_pre_flag; fold->dev.seq = s->pre_seq; fold->done = s->ev_pre_done;
+      if (++s->pre.seq == 0u) ++s->pre.seq;
+      fold->dev.am = pl.argmax; fold->dev.flag = s->pre.d_flag; fold->dev.seq = s->pre.seq; fold->done = s->pre.ev_done;
     } else
-    hipExtLaunchKernelGGL(k_pdf_argmax, dim3(1), dim3(1024), 0, stream, nullptr, s->ev_pre_done, 0, pl.argmax.prob, pl.argmax.cand, pl.argmax.max_cand, pl.argmax.M,
+    hipExtLaunchKernelGGL(k_pdf_argmax, dim3(1), dim3(1024), 0, stream, nullptr, s->pre.ev_done, 0, pl.argmax.prob, pl.argmax.cand, pl.argmax.max_cand, pl.argmax.M,
                        pl.argmax.S, pl.argmax.out, pl.argmax.hdr, pl.argmax.host_hdr, pl.argmax.host_res);
-    s->pre_done_valid = true;
-    s->pre_res_off_hdr = L.off_hdr; s->pre_res_off_res = L.off_res;
+    s->pre.done_valid = true;
+    s->pre.res_off_hdr = L.off_hdr; s->pre.res_off_res = L.off_res;
   }
   TSD_HIP_CHECK(ctx, hipGetLastError());
-  *tinit_dev = reinterpret_cast<const double*>(s->d_pre + L.off_res);
+  *tinit_dev = reinterpret_cast<const double*>(s->pre.d + L.off_res);
   return TSD_OK;
 }
 
 // The armed pre-registrations of a batch's robots (tsd_batch_begin) in four launches instead of four per robot; each robot's result
-// lands where its own launch_preregistration would have put it (s->d_pre + off_res: the Tinit of its registration).
+// lands where its own launch_preregistration would have put it (s->pre.d + off_res: the Tinit of its registration).
 int launch_preregistration_batch(tsd_ctx* ctx, hipStream_t stream, tsd_sensor* const* sensors, int n)
 {
   for (int i0 = 0; i0 < n; i0 += PDF_BATCH_BYVAL) {
@@ -1109,11 +1109,11 @@ int launch_preregistration_batch(tsd_ctx* ctx, hipStream_t stream, tsd_sensor* c
     for (int i = 0; i < m; i++) {
       tsd_sensor* s = sensors[i0 + i];
       if (int rc = pre_inputs_ready(ctx, s, stream)) return rc;
-      const PreLaunch pl = pre_launch_args(s, s->d_coords, s->d_mask_m, s->d_state->icpP);
+      const PreLaunch pl = pre_launch_args(s, s->split.d_coords, s->split.d_mask_m, s->d_state->icpP);
       bn.e[i] = pl.normals; bp.e[i] = pl.prepare; bs.e[i] = pl.score; ba.e[i] = pl.argmax;
       max_points = std::max(max_points, pl.normals.points); max_blocks = std::max(max_blocks, pl.score_blocks); max_lds = std::max(max_lds, pl.prep_lds);
-      s->pre_done_valid = false;              // (no event of this sensor's own behind the batched arg-max; batches are armed between scans)
-      s->pre_res_off_hdr = s->pre.off_hdr; s->pre_res_off_res = s->pre.off_res;
+      s->pre.done_valid = false;              // (no event of this sensor's own behind the batched arg-max; batches are armed between scans)
+      s->pre.res_off_hdr = s->pre.layout.off_hdr; s->pre.res_off_res = s->pre.layout.off_res;
     }
     if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_pdf_prepare_batch), max_lds)) return rc;
     // (the scoring strides a fixed grid over each robot's candidates: a share of the single launch's grid per robot keeps the
@@ -1133,9 +1133,9 @@ int launch_preregistration_batch(tsd_ctx* ctx, hipStream_t stream, tsd_sensor* c
 extern "C" int tsd_scan_preregistration_result(tsd_sensor* s, tsd_tsdpdf_result* result)
 {
   if (!s || !s->ctx || !result) return TSD_E_ARG;
-  if (!s->pre_ran || s->submitted) return set_error(s->ctx, TSD_E_ARG, "tsd_scan_preregistration_result: no collected scan with a pre-registration", hipSuccess);
-  const PdfHeader* hd = reinterpret_cast<const PdfHeader*>(s->h_pre + s->pre_res_off_hdr);
-  const PdfResult* r = reinterpret_cast<const PdfResult*>(s->h_pre + s->pre_res_off_res);
+  if (!s->pre.ran || s->fused.submitted) return set_error(s->ctx, TSD_E_ARG, "tsd_scan_preregistration_result: no collected scan with a pre-registration", hipSuccess);
+  const PdfHeader* hd = reinterpret_cast<const PdfHeader*>(s->pre.h + s->pre.res_off_hdr);
+  const PdfResult* r = reinterpret_cast<const PdfResult*>(s->pre.h + s->pre.res_off_res);
   std::memcpy(result->T, r->T, sizeof(r->T));
   result->probability = r->prob; result->idx_model = r->idx; result->idx_scene = r->i;
   result->candidates = hd->identity ? 0 : hd->n_cand;
