@@ -396,37 +396,33 @@ class TsdGridDevice:
             p.use_t_init = 1
         return p
 
+    def _match(self, fn, lead, model_xy, mask_m, scene_xy, mask_s, prm, result, draws_sub, draws_ctrl, draws_trials) -> dict:
+        """the marshalling the three pre-registration calls share; the common record's fields of `result` as a dict"""
+        M, S = _f64(model_xy).reshape(-1), _f64(scene_xy).reshape(-1)
+        n = M.size // 2
+        mM, mS = np.ascontiguousarray(mask_m, dtype=np.uint8), np.ascontiguousarray(mask_s, dtype=np.uint8)
+        ds, dc, dt = (np.ascontiguousarray(x, dtype=np.int32) for x in (draws_sub, draws_ctrl, draws_trials))
+        assert ds.size >= n and dc.size >= prm.size_control_set and dt.size >= prm.trials
+        rc = getattr(self.lib, fn)(self.h, *lead, _d(M), _u8(mM), _d(S), _u8(mS), n, C.byref(prm), ds.ctypes.data_as(_ip),
+                                   dc.ctypes.data_as(_ip), dt.ctypes.data_as(_ip), C.byref(result))
+        self._check(rc, fn)
+        return dict(T=np.array(result.T[:]).reshape(3, 3), idx=result.idx_model, i=result.idx_scene, candidates=result.candidates,
+                    valid_model=result.valid_model, valid_scene=result.valid_scene, control=result.control_points)
+
     def tsdpdf_match(self, pose, model_xy, mask_m, scene_xy, mask_s, trials, size_control_set, zrand, phi_max, ang_res,
                      draws_sub, draws_ctrl, draws_trials, eps_thresh=0.15) -> dict:
         """obvious::TSD_PDFMatching::match with the rand() draws as inputs (tsd_tsdpdf_match)"""
-        M, S = _f64(model_xy).reshape(-1), _f64(scene_xy).reshape(-1)
-        n = M.size // 2
-        mM, mS = np.ascontiguousarray(mask_m, dtype=np.uint8), np.ascontiguousarray(mask_s, dtype=np.uint8)
-        ds, dc, dt = (np.ascontiguousarray(x, dtype=np.int32) for x in (draws_sub, draws_ctrl, draws_trials))
-        assert ds.size >= n and dc.size >= size_control_set and dt.size >= trials
-        prm = TsdPdfParams(trials, size_control_set, eps_thresh, zrand, phi_max, ang_res)
         r = TsdPdfResult()
-        rc = self.lib.tsd_tsdpdf_match(self.h, _d(_f64(pose).reshape(9)), _d(M), _u8(mM), _d(S), _u8(mS), n, C.byref(prm),
-                                       ds.ctypes.data_as(_ip), dc.ctypes.data_as(_ip), dt.ctypes.data_as(_ip), C.byref(r))
-        self._check(rc, "tsd_tsdpdf_match")
-        return dict(T=np.array(r.T[:]).reshape(3, 3), prob=r.probability, idx=r.idx_model, i=r.idx_scene,
-                    candidates=r.candidates, valid_model=r.valid_model, valid_scene=r.valid_scene, control=r.control_points)
+        return dict(self._match("tsd_tsdpdf_match", (_d(_f64(pose).reshape(9)),), model_xy, mask_m, scene_xy, mask_s,
+                                TsdPdfParams(trials, size_control_set, eps_thresh, zrand, phi_max, ang_res), r,
+                                draws_sub, draws_ctrl, draws_trials), prob=r.probability)
 
     def pdf_match(self, model_xy, mask_m, scene_xy, mask_s, phi_max, ang_res, draws_sub, draws_ctrl, draws_trials, **kw) -> dict:
         """obvious::PDFMatching::match with the rand() draws as inputs (tsd_pdf_match); `kw` overrides PDFMATCH_DEFAULTS"""
-        M, S = _f64(model_xy).reshape(-1), _f64(scene_xy).reshape(-1)
-        n = M.size // 2
-        mM, mS = np.ascontiguousarray(mask_m, dtype=np.uint8), np.ascontiguousarray(mask_s, dtype=np.uint8)
-        ds, dc, dt = (np.ascontiguousarray(x, dtype=np.int32) for x in (draws_sub, draws_ctrl, draws_trials))
-        v = dict(PDFMATCH_DEFAULTS, **kw)
-        assert ds.size >= n and dc.size >= v["size_control_set"] and dt.size >= v["trials"]
-        prm = PdfMatchParams(phi_max=phi_max, ang_res=ang_res, **v)
         r = TsdPdfResult()
-        rc = self.lib.tsd_pdf_match(self.h, _d(M), _u8(mM), _d(S), _u8(mS), n, C.byref(prm), ds.ctypes.data_as(_ip),
-                                    dc.ctypes.data_as(_ip), dt.ctypes.data_as(_ip), C.byref(r))
-        self._check(rc, "tsd_pdf_match")
-        return dict(T=np.array(r.T[:]).reshape(3, 3), prob=r.probability, idx=r.idx_model, i=r.idx_scene,
-                    candidates=r.candidates, valid_model=r.valid_model, valid_scene=r.valid_scene, control=r.control_points)
+        return dict(self._match("tsd_pdf_match", (), model_xy, mask_m, scene_xy, mask_s,
+                                PdfMatchParams(phi_max=phi_max, ang_res=ang_res, **dict(PDFMATCH_DEFAULTS, **kw)), r,
+                                draws_sub, draws_ctrl, draws_trials), prob=r.probability)
 
     def debug_pdf_match_scores(self):
         """TEST HOOK: the last pdf_match's ungated products and field-of-view counts, in candidate order"""
@@ -438,20 +434,11 @@ class TsdGridDevice:
 
     def rn_match(self, model_xy, mask_m, scene_xy, mask_s, phi_max, ang_res, draws_sub, draws_ctrl, draws_trials, **kw) -> dict:
         """obvious::RandomNormalMatching::match with the rand() draws as inputs (tsd_rn_match); `kw` overrides RNMATCH_DEFAULTS"""
-        M, S = _f64(model_xy).reshape(-1), _f64(scene_xy).reshape(-1)
-        n = M.size // 2
-        mM, mS = np.ascontiguousarray(mask_m, dtype=np.uint8), np.ascontiguousarray(mask_s, dtype=np.uint8)
-        ds, dc, dt = (np.ascontiguousarray(x, dtype=np.int32) for x in (draws_sub, draws_ctrl, draws_trials))
-        v = dict(RNMATCH_DEFAULTS, **kw)
-        assert ds.size >= n and dc.size >= v["size_control_set"] and dt.size >= v["trials"]
-        prm = RnMatchParams(phi_max=phi_max, ang_res=ang_res, **v)
         r = RnMatchResult()
-        rc = self.lib.tsd_rn_match(self.h, _d(M), _u8(mM), _d(S), _u8(mS), n, C.byref(prm), ds.ctypes.data_as(_ip),
-                                   dc.ctypes.data_as(_ip), dt.ctypes.data_as(_ip), C.byref(r))
-        self._check(rc, "tsd_rn_match")
-        return dict(T=np.array(r.T[:]).reshape(3, 3), ratio=r.ratio, err_sum=r.err_sum, cnt=r.cnt_match, max_cnt=r.max_cnt_match,
-                    idx=r.idx_model, i=r.idx_scene, candidates=r.candidates, valid_model=r.valid_model, valid_scene=r.valid_scene,
-                    control=r.control_points)
+        return dict(self._match("tsd_rn_match", (), model_xy, mask_m, scene_xy, mask_s,
+                                RnMatchParams(phi_max=phi_max, ang_res=ang_res, **dict(RNMATCH_DEFAULTS, **kw)), r,
+                                draws_sub, draws_ctrl, draws_trials),
+                    ratio=r.ratio, err_sum=r.err_sum, cnt=r.cnt_match, max_cnt=r.max_cnt_match)
 
     def debug_rn_match_scores(self):
         """TEST HOOK: the last rn_match's cntMatch, maxCntMatch and errSum per candidate, in candidate order"""

@@ -80,20 +80,18 @@ ThreadLocalize::ThreadLocalize(obvious::TsdGrid* grid, ThreadMapping* mapper, co
   _lasMinRange = node->get_parameter("laser_min_range").as_double();
   _regMode     = (int)node->get_parameter(_robotName + "registration_mode").as_int();
   _ranPhiMax   = node->get_parameter(_robotName + "ransac_phi_max").as_double();
-  _preMatcher.reset();
-  _pdfMatcher.reset();
-  _rnMatcher.reset();
+  _matcher.reset();
+  _tsdPdf = nullptr;
   std::memset(&_preResult, 0, sizeof(_preResult));
+  const auto trials = [&] { return (unsigned)node->get_parameter("trials").as_int(); };
+  const auto sizeControlSet = [&] { return (unsigned)node->get_parameter("sizeControlSet").as_int(); };
+  const auto dbl = [&](const char* name) { return node->get_parameter(name).as_double(); };
   switch(_regMode)
   {
   case 0:   // ICP: no instance needed
     break;
   case 3:   // TSD (ThreadLocalize.cpp:193): TSD_PDFMatching(_grid, trials, epsThresh, sizeControlSet, zrand)
-    _preMatcher.reset(new obvious::TSD_PDFMatching(*grid, (unsigned)node->get_parameter("trials").as_int(),
-                                                   node->get_parameter("epsThresh").as_double(),
-                                                   (unsigned)node->get_parameter("sizeControlSet").as_int(),
-                                                   node->get_parameter("zrand").as_double()));
-    _preMatcher->setSeed((long)param(node, _robotName + "tsdpdf_seed", -1).as_int());   // addition: reproducible draws for tests
+    _matcher.reset(_tsdPdf = new obvious::TSD_PDFMatching(*grid, trials(), dbl("epsThresh"), sizeControlSet(), dbl("zrand")));
     break;
   case 2:   // PDF (ThreadLocalize.cpp:185-187): PDFMatching(trials, epsThresh, sizeControlSet, zhit, ..., maxAnglePenalty)
     if(!obvious::PDFMatching::available())
@@ -103,18 +101,9 @@ ThreadLocalize::ThreadLocalize(obvious::TsdGrid* grid, ThreadMapping* mapper, co
       _regMode = 0;
       break;
     }
-    _pdfMatcher.reset(new obvious::PDFMatching(*grid, (unsigned)node->get_parameter("trials").as_int(),
-                                               node->get_parameter("epsThresh").as_double(),
-                                               (unsigned)node->get_parameter("sizeControlSet").as_int(),
-                                               node->get_parameter("zhit").as_double(), node->get_parameter("zphi").as_double(),
-                                               node->get_parameter("zshort").as_double(), node->get_parameter("zmax").as_double(),
-                                               node->get_parameter("zrand").as_double(),
-                                               node->get_parameter("percentagePointsInC").as_double(),
-                                               node->get_parameter("rangemax").as_double(), node->get_parameter("sigphi").as_double(),
-                                               node->get_parameter("sighit").as_double(), node->get_parameter("lamshort").as_double(),
-                                               node->get_parameter("maxAngleDiff").as_double(),
-                                               node->get_parameter("maxAnglePenalty").as_double()));
-    _pdfMatcher->setSeed((long)param(node, _robotName + "tsdpdf_seed", -1).as_int());   // addition: reproducible draws for tests
+    _matcher.reset(new obvious::PDFMatching(*grid, trials(), dbl("epsThresh"), sizeControlSet(), dbl("zhit"), dbl("zphi"), dbl("zshort"),
+                                            dbl("zmax"), dbl("zrand"), dbl("percentagePointsInC"), dbl("rangemax"), dbl("sigphi"),
+                                            dbl("sighit"), dbl("lamshort"), dbl("maxAngleDiff"), dbl("maxAnglePenalty")));
     break;
   case 1:   // EXP (ThreadLocalize.cpp:181-183): RandomNormalMatching(trials, epsThresh, sizeControlSet) -- the shared parameters, not
             // the ransac_* ones
@@ -125,15 +114,13 @@ ThreadLocalize::ThreadLocalize(obvious::TsdGrid* grid, ThreadMapping* mapper, co
       _regMode = 0;
       break;
     }
-    _rnMatcher.reset(new obvious::RandomNormalMatching(*grid, (unsigned)node->get_parameter("trials").as_int(),
-                                                       node->get_parameter("epsThresh").as_double(),
-                                                       (unsigned)node->get_parameter("sizeControlSet").as_int()));
-    _rnMatcher->setSeed((long)param(node, _robotName + "tsdpdf_seed", -1).as_int());   // addition: reproducible draws for tests
+    _matcher.reset(new obvious::RandomNormalMatching(*grid, trials(), dbl("epsThresh"), sizeControlSet()));
     break;
   default:  // ThreadLocalize.cpp:188-190
     std::fprintf(stderr, "Localizer(%s): Unknown registration mode %d use default = ICP.\n", _nameSpace.c_str(), _regMode);
     _regMode = 0;
   }
+  if(_matcher) _matcher->setSeed((long)param(node, _robotName + "tsdpdf_seed", -1).as_int());   // addition: reproducible draws for tests
 
   // ICP set-up (ThreadLocalize.cpp:211-225): DistanceFilter(max, min, icpIterations - 10), bounds filter
   // over the grid extent, maxRMS 0, max iterations == convergence counter == icpIterations
@@ -227,15 +214,38 @@ void ThreadLocalize::declareInitParameters(const std::shared_ptr<rclcpp::Node>& 
   (void)param(node, nameSpace + "footprint_x_offset", 0.28);
 }
 
-void ThreadLocalize::laserCallBack(const std::shared_ptr<sensor_msgs::msg::LaserScan> scan)
+void ThreadLocalize::clampRanges(sensor_msgs::msg::LaserScan& scan) const
 {
-  // the reference clamps in place through an aliased shared_ptr (Appendix B #15); copy instead
-  auto scanCopy = std::make_shared<sensor_msgs::msg::LaserScan>(*scan);
-  for(auto& iter : scanCopy->ranges)
+  for(auto& iter : scan.ranges)
   {
     if(iter < _lasMinRange)
       iter = 0.0;
   }
+}
+
+long long ThreadLocalize::stampNs(const builtin_interfaces::msg::Time& stamp)
+{
+  return (long long)stamp.sec * 1000000000LL + (long long)stamp.nanosec;
+}
+
+// a scan's outcome becomes the last report
+void ThreadLocalize::publish(const ScanReport& rep)
+{
+  std::lock_guard<std::mutex> lk(_reportMutex);
+  _report = rep; _processed++;
+}
+
+void ThreadLocalize::deviceError(int rc, const ScanReport& rep)
+{
+  std::fprintf(stderr, "Localizer(%s) device error %d\n", _nameSpace.c_str(), rc);
+  publish(rep);
+}
+
+void ThreadLocalize::laserCallBack(const std::shared_ptr<sensor_msgs::msg::LaserScan> scan)
+{
+  // the reference clamps in place through an aliased shared_ptr (Appendix B #15); copy instead
+  auto scanCopy = std::make_shared<sensor_msgs::msg::LaserScan>(*scan);
+  clampRanges(*scanCopy);
   if(!_initialized)
   {
     this->init(*scanCopy);
@@ -261,11 +271,7 @@ void ThreadLocalize::laserCallBack(const std::shared_ptr<sensor_msgs::msg::Laser
 void ThreadLocalize::announceNext(const std::shared_ptr<sensor_msgs::msg::LaserScan> scan)
 {
   auto copy = std::make_shared<sensor_msgs::msg::LaserScan>(*scan);
-  for(auto& iter : copy->ranges)
-  {
-    if(iter < _lasMinRange)
-      iter = 0.0;
-  }
+  clampRanges(*copy);
   if(_reverseScan)
     std::reverse(copy->ranges.begin(), copy->ranges.end());
   std::lock_guard<std::mutex> lk(_dataMutex);
@@ -307,7 +313,7 @@ void ThreadLocalize::processScan(const std::vector<float>& ranges, const builtin
   ScanReport rep;
   std::memset(&rep, 0, sizeof(rep));
   rep.initialised = true;
-  rep.stampNs = (long long)stamp.sec * 1000000000LL + (long long)stamp.nanosec;
+  rep.stampNs = stampNs(stamp);
   _stampLaserOld = _stampLaser;
   _stampLaser = stamp;
 
@@ -334,8 +340,7 @@ void ThreadLocalize::processScan(const std::vector<float>& ranges, const builtin
   static const bool mode3Unfused = std::getenv("TSD_MODE3_UNFUSED") != nullptr;
   // (several robots on one grid: the batched dispatcher runs the pre-registration behind its batch's ray casts; the split scan does not)
   // (registration_mode 2: always the reference's call structure, the matcher's host part between the ray cast and the registration)
-  if((_regMode == 3 && _preMatcher && (mode3Unfused || !_preFusedOk || !_fused || !_sensor->deviceHandle() || (_concurrent && !_grid.batcher()))) ||
-     (_regMode == 2 && _pdfMatcher) || (_regMode == 1 && _rnMatcher))
+  if(_matcher && (!_tsdPdf || mode3Unfused || !_preFusedOk || !_fused || !_sensor->deviceHandle() || (_concurrent && !_grid.batcher())))
   {
     processScanPreRegistered(rep);
     return;
@@ -353,9 +358,7 @@ void ThreadLocalize::processScan(const std::vector<float>& ranges, const builtin
   _sensor->getTransformation().getData(rep.pose);
   if(rc != TSD_OK)
   {
-    std::fprintf(stderr, "Localizer(%s) device error %d\n", _nameSpace.c_str(), rc);
-    std::lock_guard<std::mutex> lk(_reportMutex);
-    _report = rep; _processed++;
+    deviceError(rc, rep);
     return;
   }
   rep.validModel = res.n_model; rep.validScene = res.n_scene;
@@ -363,8 +366,7 @@ void ThreadLocalize::processScan(const std::vector<float>& ranges, const builtin
   {
     // "Raycasting found no coordinates" -> skip the scan (ThreadLocalize.cpp:354-358)
     rep.noModel = true;
-    std::lock_guard<std::mutex> lk(_reportMutex);
-    _report = rep; _processed++;
+    publish(rep);
     return;
   }
   finishScan(rep, res);
@@ -407,12 +409,15 @@ void ThreadLocalize::processScanPreRegistered(ScanReport& rep)
   g_m3.lap(0);
   _sensor->getTransformation().getData(rep.pose);
   rep.validModel = (int)validModelPoints;
-  if(rcR != TSD_OK || validModelPoints == 0)
+  if(rcR != TSD_OK)
   {
-    if(rcR != TSD_OK) std::fprintf(stderr, "Localizer(%s) device error %d\n", _nameSpace.c_str(), rcR);
-    rep.noModel = rcR == TSD_OK;
-    std::lock_guard<std::mutex> lk(_reportMutex);
-    _report = rep; _processed++;
+    deviceError(rcR, rep);
+    return;
+  }
+  if(validModelPoints == 0)
+  {
+    rep.noModel = true;
+    publish(rep);
     return;
   }
   const unsigned int validScenePoints = _sensor->dataToCartesianVectorMask(_scene.data(), maskS);
@@ -424,28 +429,12 @@ void ThreadLocalize::processScanPreRegistered(ScanReport& rep)
   //                                                  sensor->getAngularResolution())  (ThreadLocalize.cpp:545-553)
   //                 case EXP: T = _RandomNormalMatcher->match(M, _maskM, NULL, S, _maskS, deg2rad(_ranPhiMax), _trnsMax,
   //                                                           sensor->getAngularResolution())  (ThreadLocalize.cpp:537-545)
-  obvious::Matrix Tpre(3, 3);
-  tsd_tsdpdf_result pre;
-  std::memset(&pre, 0, sizeof(pre));
-  if(_regMode == 1)
-  {
-    Tpre = _rnMatcher->match(_modelCoords.data(), maskM, nullptr, _scene.data(), maskS, n, _ranPhiMax * M_PI / 180.0, _trnsMax,
-                             _sensor->getAngularResolution());
-    // reported in the common record: bestRatio in the probability slot
-    const tsd_rnmatch_result& r = _rnMatcher->lastResult();
-    std::memcpy(pre.T, r.T, sizeof(pre.T));
-    pre.probability = r.ratio; pre.idx_model = r.idx_model; pre.idx_scene = r.idx_scene; pre.candidates = r.candidates;
-    pre.valid_model = r.valid_model; pre.valid_scene = r.valid_scene; pre.control_points = r.control_points;
-  }
-  else if(_regMode == 2)
-    Tpre = _pdfMatcher->match(_modelCoords.data(), maskM, nullptr, _scene.data(), maskS, n, _ranPhiMax * M_PI / 180.0, _trnsMax,
-                              _sensor->getAngularResolution());
-  else
-    Tpre = _preMatcher->match(_sensor->getTransformation(), _modelCoords.data(), maskM, nullptr, _scene.data(), maskS,
-                              n, _ranPhiMax * M_PI / 180.0, _trnsMax, _sensor->getAngularResolution());
+  // (one virtual call: modes 1 and 2 ignore the sensor's pose; mode 1 reports bestRatio in the common record's probability slot)
+  obvious::Matrix Tpre = _matcher->match(_sensor->getTransformation(), _modelCoords.data(), maskM, nullptr, _scene.data(), maskS,
+                                         n, _ranPhiMax * M_PI / 180.0, _trnsMax, _sensor->getAngularResolution());
   {
     std::lock_guard<std::mutex> lk(_reportMutex);
-    _preResult = _regMode == 1 ? pre : _regMode == 2 ? _pdfMatcher->lastResult() : _preMatcher->lastResult();
+    _preResult = _matcher->lastResult();
     _havePreResult = true;
   }
   g_m3.lap(2);
@@ -461,9 +450,7 @@ void ThreadLocalize::processScanPreRegistered(ScanReport& rep)
   const int rc = _grid.localize(_sensor, p, &res);
   if(rc != TSD_OK)
   {
-    std::fprintf(stderr, "Localizer(%s) device error %d\n", _nameSpace.c_str(), rc);
-    std::lock_guard<std::mutex> lk(_reportMutex);
-    _report = rep; _processed++;
+    deviceError(rc, rep);
     return;
   }
   g_m3.lap(3);
@@ -511,8 +498,7 @@ void ThreadLocalize::finishScan(ScanReport& rep, const tsd_icp_result& res)
       rep.pushed = true;
     }
   }
-  std::lock_guard<std::mutex> lk(_reportMutex);
-  _report = rep; _processed++;
+  publish(rep);
 }
 
 // The event-loop body with the device doing everything between scan ingest and pose publication
@@ -526,111 +512,42 @@ void ThreadLocalize::processScanFused(ScanReport& rep)
   tsd_gate_params gates = {_trnsMax, _rotMax, TRNS_MIN, ROT_MIN};
   tsd_scan_result sr;
   std::memset(&sr, 0, sizeof(sr));
-  int rc;
+  // single robot: the scan may have been staged, and its pre-registration armed, while the previous scan registered
+  const bool useStaged = !_concurrent && _stagedValid;
+  const bool preStaged = _preStagedValid && useStaged;      // (a dropped staged scan takes its armed pre-registration along)
+  // ... but not its draws: they do not depend on the scan, and the scan that came instead uses the very same ones, so that a seeded
+  // sequence (tsdpdf_seed) stays one drawStreams() call per REGISTERED scan, as in the unfused path
+  if(!_concurrent)
+  {
+    if(_preStagedValid && !useStaged) _drawsReady = true;
+    _stagedValid = false;
+    _preStagedValid = false;
+  }
+  int rc = TSD_OK;
+  // arm: registration_mode 3's pre-registration for this scan.  Several robots on one grid: armed for this robot's scan of the batch,
+  // which runs it behind the batch's ray casts (tsd_batch_begin) -- fresh draws every time; single robot: the draws taken ahead.
+  if(_tsdPdf && !preStaged && (rc = armPreregistration(!_concurrent)) == TSD_E_CAPACITY)
+  {
+    // more trials / control points than the device-side list building holds in LDS: the reference's call structure instead,
+    // from this scan on (nothing was enqueued; the draws are consumed, like a match() that ran)
+    std::fprintf(stderr, "Localizer(%s): registration_mode 3 runs unfused (%s)\n", _nameSpace.c_str(), tsd_last_error(_grid.context()));
+    _preFusedOk = false;
+    processScanPreRegistered(rep);
+    return;
+  }
   if(_concurrent)
   {
-    // several robots on one grid: the grid's dispatcher batches the robots' scans (or the split scan)
-    rc = TSD_OK;
-    if(_regMode == 3 && _preMatcher && _preFusedOk && _grid.batcher())
-    {
-      // doRegistration, case TSD (ThreadLocalize.cpp:557-567), armed for this robot's scan of the batch: scene points + the three
-      // rand() streams from the host, everything else on the device behind the batch's ray casts (tsd_batch_begin)
-      const unsigned int n = _sensor->getRealMeasurementSize();
-      if(_scene.size() != 2 * (size_t)n) { _scene.assign(2 * (size_t)n, 0.0); _maskS.assign(n, 0); }
-      bool* maskS = reinterpret_cast<bool*>(_maskS.data());
-      _sensor->dataToCartesianVectorMask(_scene.data(), maskS);
-      _preMatcher->drawStreams(n, _dSub, _dCtrl, _dTrials);
-      rc = _grid.scanPreregister(_sensor, _preMatcher->params(_ranPhiMax * M_PI / 180.0, _sensor->getAngularResolution()), _scene.data(), maskS,
-                                 _dSub.data(), _dCtrl.data(), _dTrials.data());
-      if(rc == TSD_E_CAPACITY)
-      {
-        std::fprintf(stderr, "Localizer(%s): registration_mode 3 runs unfused (%s)\n", _nameSpace.c_str(), tsd_last_error(_grid.context()));
-        _preFusedOk = false;
-        processScanPreRegistered(rep);
-        return;
-      }
-    }
+    // the grid's dispatcher batches the robots' scans (or the split scan)
     if(rc == TSD_OK) rc = _grid.scanConcurrent(_sensor, maskPush.data(), _icpParams, gates, &sr);
   }
   else
   {
-    const bool useStaged = _stagedValid;
-    _stagedValid = false;
-    const bool preStaged = _preStagedValid && useStaged;      // (armed while the previous scan registered; a dropped staged scan takes it along)
-    // ... but not its draws: they do not depend on the scan, and the scan that came instead uses the very same ones, so that a seeded
-    // sequence (tsdpdf_seed) stays one drawStreams() call per REGISTERED scan, as in the unfused path
-    if(_preStagedValid && !useStaged) _drawsReady = true;
-    _preStagedValid = false;
-    rc = TSD_OK;
-    if(_regMode == 3 && _preMatcher && !preStaged)
-    {
-      // doRegistration, case TSD (ThreadLocalize.cpp:557-567): the scene points and the match's three rand() streams are all the
-      // pre-registration needs from the host; its model is the ray cast's output, on the device
-      const unsigned int n = _sensor->getRealMeasurementSize();
-      if(_scene.size() != 2 * (size_t)n) { _scene.assign(2 * (size_t)n, 0.0); _maskS.assign(n, 0); }
-      bool* maskS = reinterpret_cast<bool*>(_maskS.data());
-      _sensor->dataToCartesianVectorMask(_scene.data(), maskS);
-      // (the draws do not depend on the scan: they were taken from rand() while the previous scan registered -- same values, same
-      // order, as long as this localiser is the process's only rand() user, which it is in the reference's single-robot node too)
-      if(!_drawsReady || _dSub.size() != n) _preMatcher->drawStreams(n, _dSub, _dCtrl, _dTrials);
-      _drawsReady = false;
-      rc = _grid.scanPreregister(_sensor, _preMatcher->params(_ranPhiMax * M_PI / 180.0, _sensor->getAngularResolution()), _scene.data(), maskS,
-                                 _dSub.data(), _dCtrl.data(), _dTrials.data());
-      if(rc == TSD_E_CAPACITY)
-      {
-        // more trials / control points than the device-side list building holds in LDS: the reference's call structure instead,
-        // from this scan on (nothing was enqueued; the draws are consumed, like a match() that ran)
-        std::fprintf(stderr, "Localizer(%s): registration_mode 3 runs unfused (%s)\n", _nameSpace.c_str(), tsd_last_error(_grid.context()));
-        _preFusedOk = false;
-        processScanPreRegistered(rep);
-        return;
-      }
-    }
+    // submit, stage the next scan while the device registers this one, collect
     if(rc == TSD_OK) rc = _grid.scanSubmit(_sensor, useStaged, maskPush.data(), _icpParams, gates);
-    // the next scan, if it is known already: ingest + copy + tables while the device registers this one
-    std::shared_ptr<sensor_msgs::msg::LaserScan> next;
+    stageNextScan(rc == TSD_OK);
+    if(rc == TSD_OK && _tsdPdf && _preFusedOk && !_drawsReady && !_preStagedValid)
     {
-      std::lock_guard<std::mutex> lk(_dataMutex);
-      next.swap(_ahead);
-      if(!next && !_synchronous && !_laserData.empty())
-      {
-        // threaded mode: the newest scan that queued up meanwhile is what the event loop takes next -- unless a newer one
-        // still arrives, in which case the staged one is dropped like the reference drops it (ThreadLocalize.cpp:319-332)
-        next = std::make_shared<sensor_msgs::msg::LaserScan>(*_laserData.front());
-        if(_reverseScan)
-          std::reverse(next->ranges.begin(), next->ranges.end());
-      }
-    }
-    if(rc == TSD_OK && next && next->ranges.size() == _sensor->getRealMeasurementSize())
-    {
-      _sensor->setRealMeasurementData(next->ranges);
-      _sensor->setStandardMask();
-      std::vector<uint8_t> maskNext;
-      _sensor->maskForMapping(maskNext);
-      if(_grid.scanStage(_sensor, maskNext.data()) == TSD_OK)
-      {
-        _stagedValid = true;
-        _stagedStampNs = (long long)next->header.stamp.sec * 1000000000LL + (long long)next->header.stamp.nanosec;
-        _stagedRanges = next->ranges;
-        if(_regMode == 3 && _preMatcher && _preFusedOk)
-        {
-          // ... and its pre-registration: scene points, draws and the inputs' copy NOW, while the device registers this scan -- between
-          // two scans the host then only submits (the device was waiting for the host there: 40 us of host work per scan in mode 3)
-          const unsigned int n = _sensor->getRealMeasurementSize();
-          if(_scene.size() != 2 * (size_t)n) { _scene.assign(2 * (size_t)n, 0.0); _maskS.assign(n, 0); }
-          bool* maskS = reinterpret_cast<bool*>(_maskS.data());
-          _sensor->dataToCartesianVectorMask(_scene.data(), maskS);
-          if(!_drawsReady || _dSub.size() != n) _preMatcher->drawStreams(n, _dSub, _dCtrl, _dTrials);
-          _drawsReady = false;
-          if(_grid.scanPreregister(_sensor, _preMatcher->params(_ranPhiMax * M_PI / 180.0, _sensor->getAngularResolution()), _scene.data(), maskS,
-                                   _dSub.data(), _dCtrl.data(), _dTrials.data()) == TSD_OK)
-            _preStagedValid = true;
-        }
-      }
-    }
-    if(rc == TSD_OK && _regMode == 3 && _preMatcher && _preFusedOk && !_drawsReady && !_preStagedValid)
-    {
-      _preMatcher->drawStreams(_sensor->getRealMeasurementSize(), _dSub, _dCtrl, _dTrials);      // the next scan's, while the device is busy
+      _matcher->drawStreams(_sensor->getRealMeasurementSize(), _dSub, _dCtrl, _dTrials);      // the next scan's, while the device is busy
       _drawsReady = true;
     }
     if(rc == TSD_OK) rc = _grid.scanCollect(_sensor, &sr);
@@ -638,17 +555,14 @@ void ThreadLocalize::processScanFused(ScanReport& rep)
   _sensor->getTransformation().getData(rep.pose);
   if(rc != TSD_OK)
   {
-    std::fprintf(stderr, "Localizer(%s) device error %d\n", _nameSpace.c_str(), rc);
-    std::lock_guard<std::mutex> lk(_reportMutex);
-    _report = rep; _processed++;
+    deviceError(rc, rep);
     return;
   }
   rep.validModel = sr.icp.n_model; rep.validScene = sr.icp.n_scene;
   if(sr.no_model)
   {
     rep.noModel = true;
-    std::lock_guard<std::mutex> lk(_reportMutex);
-    _report = rep; _processed++;
+    publish(rep);
     return;
   }
   obvious::Matrix T(3, 3, sr.icp.T);
@@ -673,8 +587,56 @@ void ThreadLocalize::processScanFused(ScanReport& rep)
       rep.pushed = true;
     }
   }
-  std::lock_guard<std::mutex> lk(_reportMutex);
-  _report = rep; _processed++;
+  publish(rep);
+}
+
+// doRegistration, case TSD (ThreadLocalize.cpp:557-567) inside the fused scan: the scene points and the match's three rand() streams
+// are all the pre-registration needs from the host; its model is the ray cast's output, on the device.  reuseDraws: the draws do not
+// depend on the scan and may have been taken from rand() while the previous scan registered -- same values, same order, as long as
+// this localiser is the process's only rand() user, which it is in the reference's single-robot node too.
+int ThreadLocalize::armPreregistration(bool reuseDraws)
+{
+  const unsigned int n = _sensor->getRealMeasurementSize();
+  if(_scene.size() != 2 * (size_t)n) { _scene.assign(2 * (size_t)n, 0.0); _maskS.assign(n, 0); }
+  bool* maskS = reinterpret_cast<bool*>(_maskS.data());
+  _sensor->dataToCartesianVectorMask(_scene.data(), maskS);
+  if(!reuseDraws || !_drawsReady || _dSub.size() != n) _matcher->drawStreams(n, _dSub, _dCtrl, _dTrials);
+  _drawsReady = false;
+  return _grid.scanPreregister(_sensor, _tsdPdf->params(_ranPhiMax * M_PI / 180.0, _sensor->getAngularResolution()), _scene.data(), maskS,
+                               _dSub.data(), _dCtrl.data(), _dTrials.data());
+}
+
+// the next scan, if it is known already (taken from the queue either way): ingest + copy + tables while the device registers this one
+void ThreadLocalize::stageNextScan(bool submitted)
+{
+  std::shared_ptr<sensor_msgs::msg::LaserScan> next;
+  {
+    std::lock_guard<std::mutex> lk(_dataMutex);
+    next.swap(_ahead);
+    if(!next && !_synchronous && !_laserData.empty())
+    {
+      // threaded mode: the newest scan that queued up meanwhile is what the event loop takes next -- unless a newer one
+      // still arrives, in which case the staged one is dropped like the reference drops it (ThreadLocalize.cpp:319-332)
+      next = std::make_shared<sensor_msgs::msg::LaserScan>(*_laserData.front());
+      if(_reverseScan)
+        std::reverse(next->ranges.begin(), next->ranges.end());
+    }
+  }
+  if(!submitted || !next || next->ranges.size() != _sensor->getRealMeasurementSize())
+    return;
+  _sensor->setRealMeasurementData(next->ranges);
+  _sensor->setStandardMask();
+  std::vector<uint8_t> maskNext;
+  _sensor->maskForMapping(maskNext);
+  if(_grid.scanStage(_sensor, maskNext.data()) != TSD_OK)
+    return;
+  _stagedValid = true;
+  _stagedStampNs = stampNs(next->header.stamp);
+  _stagedRanges = next->ranges;
+  // ... and its pre-registration: scene points, draws and the inputs' copy NOW, while the device registers this scan -- between
+  // two scans the host then only submits (the device was waiting for the host there: 40 us of host work per scan in mode 3)
+  if(_tsdPdf && _preFusedOk && armPreregistration(true) == TSD_OK)
+    _preStagedValid = true;
 }
 
 void ThreadLocalize::init(const sensor_msgs::msg::LaserScan& scan)
@@ -738,7 +700,7 @@ void ThreadLocalize::init(const sensor_msgs::msg::LaserScan& scan)
     _sensor->getTransformation().getData(_report.pose);
     _report.T[0] = _report.T[4] = _report.T[8] = 1.0;
     _report.pushed = pushed; _report.initialised = true;
-    _report.stampNs = (long long)scan.header.stamp.sec * 1000000000LL + (long long)scan.header.stamp.nanosec;
+    _report.stampNs = stampNs(scan.header.stamp);
     _processed++;
   }
   this->unblock();

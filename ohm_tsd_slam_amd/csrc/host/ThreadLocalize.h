@@ -86,6 +86,12 @@ private:
   void processScanFused(ScanReport& rep);
   void processScanPreRegistered(ScanReport& rep);
   void finishScan(ScanReport& rep, const tsd_icp_result& res);
+  int armPreregistration(bool reuseDraws);
+  void stageNextScan(bool submitted);
+  void publish(const ScanReport& rep);
+  void deviceError(int rc, const ScanReport& rep);
+  void clampRanges(sensor_msgs::msg::LaserScan& scan) const;
+  static long long stampNs(const builtin_interfaces::msg::Time& stamp);
   void sendTransform(obvious::Matrix* T);
   void sendNanTransform();
 
@@ -102,9 +108,9 @@ private:
   double _trnsMax, _rotMax, _lasMinRange;
   int _regMode;
   double _ranPhiMax;
-  std::unique_ptr<obvious::TSD_PDFMatching> _preMatcher;      // _TSD_PDFMatcher (ThreadLocalize.h)
-  std::unique_ptr<obvious::PDFMatching> _pdfMatcher;          // _PDFMatcher (ThreadLocalize.h)
-  std::unique_ptr<obvious::RandomNormalMatching> _rnMatcher;  // _RandomNormalMatcher (ThreadLocalize.h)
+  // _RandomNormalMatcher / _PDFMatcher / _TSD_PDFMatcher (ThreadLocalize.h): the one the registration mode asks for, or none (ICP)
+  std::unique_ptr<obvious::RandomMatching> _matcher;
+  obvious::TSD_PDFMatching* _tsdPdf = nullptr;                // _matcher where it is mode 3's (the fused arming needs its params())
   tsd_tsdpdf_result _preResult;                               // (guarded by _reportMutex)
   bool _havePreResult = false;
   std::vector<double> _modelCoords, _modelNormals, _scene;     // beam-indexed buffers of the event loop (:342-350)

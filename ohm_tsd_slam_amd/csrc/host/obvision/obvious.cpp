@@ -580,33 +580,52 @@ void ScanBatcher::run()
   }
 }
 
-// --------------------------------------------------------------------------------------- TSD_PDFMatching
-TSD_PDFMatching::TSD_PDFMatching(TsdGrid& grid, unsigned int trials, double epsThresh, unsigned int sizeControlSet, double zrand)
-    : _grid(grid), _trials(trials), _sizeControlSet(sizeControlSet), _epsThresh(epsThresh), _zrand(zrand), _seed(-1), _calls(0)
+// --------------------------------------------------------------------------------------- RandomMatching
+RandomMatching::RandomMatching(TsdGrid& grid, unsigned int trials, unsigned int sizeControlSet)
+    : _grid(grid), _trials(trials), _sizeControlSet(sizeControlSet), _seed(-1), _calls(0)
 {
   std::memset(&_last, 0, sizeof(_last));
 }
 
-void drawRandomMatchingStreams(long seed, unsigned long& calls, unsigned int points, unsigned int sizeControlSet, unsigned int trials,
-                               std::vector<int>& dSub, std::vector<int>& dCtrl, std::vector<int>& dTrials)
+void RandomMatching::drawStreams(unsigned int points, std::vector<int>& dSub, std::vector<int>& dCtrl, std::vector<int>& dTrials)
 {
   // the three rand() streams, in the reference's call order.  (Seeded -- tests only --: srand + the draws as ONE step under a process-
   // wide lock, so that several robots' localiser threads each get their own reproducible sequence; unseeded it is the reference's
   // plain rand(), whose interleaving between threads is as unspecified as in the reference.)
   static std::mutex seededDraws;
   std::unique_lock<std::mutex> lk(seededDraws, std::defer_lock);
-  if (seed >= 0) { lk.lock(); std::srand((unsigned)(seed + (long)calls)); }
-  calls++;
-  dSub.assign(points, 0); dCtrl.assign(sizeControlSet > 0 ? sizeControlSet : 1, 0); dTrials.assign(trials > 0 ? trials : 1, 0);
+  if (_seed >= 0) { lk.lock(); std::srand((unsigned)(_seed + (long)_calls)); }
+  _calls++;
+  dSub.assign(points, 0); dCtrl.assign(_sizeControlSet > 0 ? _sizeControlSet : 1, 0); dTrials.assign(_trials > 0 ? _trials : 1, 0);
   for (auto& v : dSub) v = std::rand();                      // RandomMatching::subsampleMask (RandomMatching.cpp:183)
   for (auto& v : dCtrl) v = std::rand();                     // RandomMatching::pickControlSet (:65)
-  if (seed < 0) std::srand((unsigned)time(NULL));            // TSD_PDFMatching.cpp:184, PDFMatching.cpp:173
+  if (_seed < 0) std::srand((unsigned)time(NULL));           // TSD_PDFMatching.cpp:184, PDFMatching.cpp:173
   for (auto& v : dTrials) v = std::rand();                   // TSD_PDFMatching.cpp:190, PDFMatching.cpp:215
 }
 
-void TSD_PDFMatching::drawStreams(unsigned int points, std::vector<int>& dSub, std::vector<int>& dCtrl, std::vector<int>& dTrials)
+Matrix RandomMatching::run(const char* name, unsigned int points, const std::function<int(const int*, const int*, const int*)>& call)
 {
-  drawRandomMatchingStreams(_seed, _calls, points, _sizeControlSet, _trials, dSub, dCtrl, dTrials);
+  Matrix TBest(3, 3);
+  TBest.setIdentity();
+  std::vector<int> dSub, dCtrl, dTrials;
+  drawStreams(points, dSub, dCtrl, dTrials);
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(_grid.mutex());
+    rc = call(dSub.data(), dCtrl.data(), dTrials.data());
+  }
+  if (rc != TSD_OK) {
+    std::fprintf(stderr, "%s::match failed (%d): %s\n", name, rc, tsd_last_error(_grid.context()));
+    return TBest;
+  }
+  TBest.setData(_last.T);
+  return TBest;
+}
+
+// --------------------------------------------------------------------------------------- TSD_PDFMatching
+TSD_PDFMatching::TSD_PDFMatching(TsdGrid& grid, unsigned int trials, double epsThresh, unsigned int sizeControlSet, double zrand)
+    : RandomMatching(grid, trials, sizeControlSet), _epsThresh(epsThresh), _zrand(zrand)
+{
 }
 
 tsd_tsdpdf_params TSD_PDFMatching::params(double phiMax, double resolution) const
@@ -621,39 +640,26 @@ Matrix TSD_PDFMatching::match(Matrix TSensor, const double* M, const bool* maskM
                               const bool* maskS, unsigned int points, double phiMax, const double /*transMax*/,
                               const double resolution)
 {
-  Matrix TBest(3, 3);
-  TBest.setIdentity();
-  std::vector<int> dSub, dCtrl, dTrials;
-  drawStreams(points, dSub, dCtrl, dTrials);
   const tsd_tsdpdf_params prm = params(phiMax, resolution);
   double pose[9];
   TSensor.getData(pose);
-  int rc;
-  {
-    std::lock_guard<std::mutex> lk(_grid.mutex());
-    rc = tsd_tsdpdf_match(_grid.context(), pose, M, reinterpret_cast<const uint8_t*>(maskM), S,
-                          reinterpret_cast<const uint8_t*>(maskS), (int)points, &prm, dSub.data(), dCtrl.data(), dTrials.data(), &_last);
-  }
-  if (rc != TSD_OK) {
-    std::fprintf(stderr, "TSD_PDFMatching::match failed (%d): %s\n", rc, tsd_last_error(_grid.context()));
-    return TBest;
-  }
-  TBest.setData(_last.T);
-  return TBest;
+  return run("TSD_PDFMatching", points, [&](const int* dSub, const int* dCtrl, const int* dTrials) {
+    return tsd_tsdpdf_match(_grid.context(), pose, M, reinterpret_cast<const uint8_t*>(maskM), S,
+                            reinterpret_cast<const uint8_t*>(maskS), (int)points, &prm, dSub, dCtrl, dTrials, &_last);
+  });
 }
 
 // --------------------------------------------------------------------------------------- PDFMatching
 PDFMatching::PDFMatching(TsdGrid& grid, unsigned int trials, double epsThresh, unsigned int sizeControlSet, double zhit, double zphi,
                          double zshort, double zmax, double zrand, double percentagePointsInC, double rangemax, double sigphi,
                          double sighit, double lamshort, double maxAngleDiff, double maxAnglePenalty)
-    : _grid(grid), _seed(-1), _calls(0)
+    : RandomMatching(grid, trials, sizeControlSet)
 {
   std::memset(&_prm, 0, sizeof(_prm));
   _prm.trials = (int)trials; _prm.size_control_set = (int)sizeControlSet; _prm.eps_thresh = epsThresh;
   _prm.zhit = zhit; _prm.zphi = zphi; _prm.zshort = zshort; _prm.zmax = zmax; _prm.zrand = zrand;
   _prm.percentage_points_in_c = percentagePointsInC; _prm.rangemax = rangemax; _prm.sigphi = sigphi; _prm.sighit = sighit;
   _prm.lamshort = lamshort; _prm.max_angle_diff = maxAngleDiff; _prm.max_angle_penalty = maxAnglePenalty;
-  std::memset(&_last, 0, sizeof(_last));
 }
 
 bool PDFMatching::available()
@@ -671,34 +677,22 @@ tsd_pdfmatch_params PDFMatching::params(double phiMax, double resolution) const
 Matrix PDFMatching::match(const double* M, const bool* maskM, const double* /*NM*/, const double* S, const bool* maskS,
                           unsigned int points, double phiMax, const double /*transMax*/, const double resolution)
 {
-  Matrix TBest(3, 3);
-  TBest.setIdentity();
   std::memset(&_last, 0, sizeof(_last));
-  if (!available()) return TBest;
-  std::vector<int> dSub, dCtrl, dTrials;
-  drawRandomMatchingStreams(_seed, _calls, points, (unsigned)_prm.size_control_set, (unsigned)_prm.trials, dSub, dCtrl, dTrials);
+  if (!available()) { Matrix I(3, 3); I.setIdentity(); return I; }
   const tsd_pdfmatch_params prm = params(phiMax, resolution);
-  int rc;
-  {
-    std::lock_guard<std::mutex> lk(_grid.mutex());
-    rc = tsd_pdf_match(_grid.context(), M, reinterpret_cast<const uint8_t*>(maskM), S, reinterpret_cast<const uint8_t*>(maskS),
-                       (int)points, &prm, dSub.data(), dCtrl.data(), dTrials.data(), &_last);
-  }
-  if (rc != TSD_OK) {
-    std::fprintf(stderr, "PDFMatching::match failed (%d): %s\n", rc, tsd_last_error(_grid.context()));
-    return TBest;
-  }
-  TBest.setData(_last.T);
-  return TBest;
+  return run("PDFMatching", points, [&](const int* dSub, const int* dCtrl, const int* dTrials) {
+    return tsd_pdf_match(_grid.context(), M, reinterpret_cast<const uint8_t*>(maskM), S, reinterpret_cast<const uint8_t*>(maskS),
+                         (int)points, &prm, dSub, dCtrl, dTrials, &_last);
+  });
 }
 
 // --------------------------------------------------------------------------------------- RandomNormalMatching
 RandomNormalMatching::RandomNormalMatching(TsdGrid& grid, unsigned int trials, double epsThresh, unsigned int sizeControlSet)
-    : _grid(grid), _seed(-1), _calls(0)
+    : RandomMatching(grid, trials, sizeControlSet)
 {
   std::memset(&_prm, 0, sizeof(_prm));
   _prm.trials = (int)trials; _prm.size_control_set = (int)sizeControlSet; _prm.eps_thresh = epsThresh;
-  std::memset(&_last, 0, sizeof(_last));
+  std::memset(&_lastRn, 0, sizeof(_lastRn));
 }
 
 bool RandomNormalMatching::available()
@@ -716,27 +710,20 @@ tsd_rnmatch_params RandomNormalMatching::params(double phiMax, double resolution
 Matrix RandomNormalMatching::match(const double* M, const bool* maskM, const double* /*NM*/, const double* S, const bool* maskS,
                                    unsigned int points, double phiMax, const double /*transMax*/, const double resolution)
 {
-  Matrix TBest(3, 3);
-  TBest.setIdentity();
   std::memset(&_last, 0, sizeof(_last));
-  if (!available()) return TBest;
-  std::vector<int> dSub, dCtrl, dTrials;
-  // the same three streams as PDFMatching: subsampleMask, pickControlSet, srand(time(NULL)) + the trial picks
-  // (RandomNormalMatching.cpp:133, :144, :203, :233)
-  drawRandomMatchingStreams(_seed, _calls, points, (unsigned)_prm.size_control_set, (unsigned)_prm.trials, dSub, dCtrl, dTrials);
+  std::memset(&_lastRn, 0, sizeof(_lastRn));
+  if (!available()) { Matrix I(3, 3); I.setIdentity(); return I; }
   const tsd_rnmatch_params prm = params(phiMax, resolution);
-  int rc;
-  {
-    std::lock_guard<std::mutex> lk(_grid.mutex());
-    rc = tsd_rn_match(_grid.context(), M, reinterpret_cast<const uint8_t*>(maskM), S, reinterpret_cast<const uint8_t*>(maskS),
-                      (int)points, &prm, dSub.data(), dCtrl.data(), dTrials.data(), &_last);
-  }
-  if (rc != TSD_OK) {
-    std::fprintf(stderr, "RandomNormalMatching::match failed (%d): %s\n", rc, tsd_last_error(_grid.context()));
-    return TBest;
-  }
-  TBest.setData(_last.T);
-  return TBest;
+  return run("RandomNormalMatching", points, [&](const int* dSub, const int* dCtrl, const int* dTrials) {
+    const int rc = tsd_rn_match(_grid.context(), M, reinterpret_cast<const uint8_t*>(maskM), S, reinterpret_cast<const uint8_t*>(maskS),
+                                (int)points, &prm, dSub, dCtrl, dTrials, &_lastRn);
+    // the common record: bestRatio in the probability slot
+    const tsd_rnmatch_result& r = _lastRn;
+    std::memcpy(_last.T, r.T, sizeof(_last.T));
+    _last.probability = r.ratio; _last.idx_model = r.idx_model; _last.idx_scene = r.idx_scene; _last.candidates = r.candidates;
+    _last.valid_model = r.valid_model; _last.valid_scene = r.valid_scene; _last.control_points = r.control_points;
+    return rc;
+  });
 }
 
 }  // namespace obvious

@@ -12,6 +12,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -218,95 +219,98 @@ protected:
   bool _initialPushAccomplished;
 };
 
-// obvious::TSD_PDFMatching (registration/ransacMatching/TSD_PDFMatching.{h,cpp}) on obvious::RandomMatching: the
-// pre-registration of registration_mode 3.  Same constructor and match() signature as the reference; the scoring of
-// the candidates runs on the device (tsd_tsdpdf_match), the three rand() streams are drawn here, where the reference
-// draws them (RandomMatching.cpp:65, :183; TSD_PDFMatching.cpp:190).
-class TSD_PDFMatching
+// obvious::RandomMatching (registration/ransacMatching/RandomMatching.{h,cpp}): the base of the three pre-registrations, as in the
+// reference.  The matchers are one algorithm with three scoring rules; what they share on this side of the C ABI lives here: the grid
+// whose device runs them, trials / control-set size, the three rand() streams drawn where the reference draws them
+// (RandomMatching.cpp:65, :183; TSD_PDFMatching.cpp:190), the common result record and the call itself (run).
+class RandomMatching
 {
 public:
-  TSD_PDFMatching(TsdGrid& grid, unsigned int trials = 50, double epsThresh = 0.15, unsigned int sizeControlSet = 140,
-                  double zrand = 0.05);
-  virtual ~TSD_PDFMatching() {}
-  /** NM (model normals) is accepted for signature compatibility; ThreadLocalize passes NULL and the normals come from
-   *  the PCA of RandomMatching::calcNormals, as in the reference's call (ThreadLocalize.cpp:559) */
-  Matrix match(Matrix TSensor, const double* M, const bool* maskM, const double* NM, const double* S, const bool* maskS,
-               unsigned int points, double phiMax = M_PI / 4.0, const double transMax = 1.5, const double resolution = 0.0);
+  virtual ~RandomMatching() {}
+  /** one entry for every matcher, TSD_PDFMatching's argument list (PDFMatching and RandomNormalMatching ignore TSensor).  NM (model
+   *  normals) is accepted for signature compatibility; ThreadLocalize passes NULL and the normals come from the PCA of
+   *  RandomMatching::calcNormals, as in the reference's call (ThreadLocalize.cpp:559) */
+  virtual Matrix match(Matrix TSensor, const double* M, const bool* maskM, const double* NM, const double* S, const bool* maskS,
+                       unsigned int points, double phiMax, const double transMax, const double resolution) = 0;
   /** addition (tests): >= 0 makes the draws reproducible -- srand(seed + number of calls so far) before drawing; the
    *  default -1 keeps the reference's behaviour (srand(time(NULL)) before the trial picks, TSD_PDFMatching.cpp:184) */
   void setSeed(long seed) { _seed = seed; }
+  /** the last match() in the common record (RandomNormalMatching: bestRatio in the probability slot) */
   const tsd_tsdpdf_result& lastResult() const { return _last; }
   /** the three rand() streams of one match() call, drawn in the reference's order (RandomMatching.cpp:183, :65;
-   *  TSD_PDFMatching.cpp:184-190) -- what match() itself uses and what the fused scan hands to tsd_scan_preregister */
+   *  TSD_PDFMatching.cpp:184-190 = PDFMatching.cpp:173-215 = RandomNormalMatching.cpp:133-233) -- what match() itself uses and what
+   *  the fused scan hands to tsd_scan_preregister */
   void drawStreams(unsigned int points, std::vector<int>& dSub, std::vector<int>& dCtrl, std::vector<int>& dTrials);
-  /** the parameters of match() as the C ABI takes them */
-  tsd_tsdpdf_params params(double phiMax, double resolution) const;
-private:
+protected:
+  RandomMatching(TsdGrid& grid, unsigned int trials, unsigned int sizeControlSet);
+  /** a match(): draws the streams, makes the device call under the grid's mutex (call(dSub, dCtrl, dTrials) fills _last and returns
+   *  the C ABI's code), reports a failure as "<name>::match failed"; TBest = _last.T, or the identity after a failure */
+  Matrix run(const char* name, unsigned int points, const std::function<int(const int*, const int*, const int*)>& call);
   TsdGrid& _grid;
   unsigned int _trials, _sizeControlSet;
-  double _epsThresh, _zrand;
   long _seed;
   unsigned long _calls;
   tsd_tsdpdf_result _last;
 };
 
-/** the three rand() streams of one RandomMatching-based match() call, in the reference's call order (RandomMatching.cpp:183,
- *  :65; TSD_PDFMatching.cpp:184-190 = PDFMatching.cpp:173-215).  seed >= 0 (tests): srand(seed + calls) first; `calls` counts. */
-void drawRandomMatchingStreams(long seed, unsigned long& calls, unsigned int points, unsigned int sizeControlSet, unsigned int trials,
-                               std::vector<int>& dSub, std::vector<int>& dCtrl, std::vector<int>& dTrials);
+// obvious::TSD_PDFMatching (registration/ransacMatching/TSD_PDFMatching.{h,cpp}): the pre-registration of registration_mode 3.  Same
+// constructor and match() signature as the reference; the scoring of the candidates runs on the device (tsd_tsdpdf_match).
+class TSD_PDFMatching : public RandomMatching
+{
+public:
+  TSD_PDFMatching(TsdGrid& grid, unsigned int trials = 50, double epsThresh = 0.15, unsigned int sizeControlSet = 140,
+                  double zrand = 0.05);
+  Matrix match(Matrix TSensor, const double* M, const bool* maskM, const double* NM, const double* S, const bool* maskS,
+               unsigned int points, double phiMax = M_PI / 4.0, const double transMax = 1.5, const double resolution = 0.0) override;
+  /** the parameters of match() as the C ABI takes them */
+  tsd_tsdpdf_params params(double phiMax, double resolution) const;
+private:
+  double _epsThresh, _zrand;
+};
 
-// obvious::PDFMatching (registration/ransacMatching/PDFMatching.{h,cpp}) on obvious::RandomMatching: the pre-registration of
-// registration_mode 2.  The reference constructor's 15 arguments behind the grid whose device runs it; match() as the reference's
-// plus the number of points.  The front end is TSD_PDFMatching's, the scoring runs on the device (tsd_pdf_match), the rand()
-// streams are drawn here exactly as TSD_PDFMatching draws them.
-class PDFMatching
+// obvious::PDFMatching (registration/ransacMatching/PDFMatching.{h,cpp}): the pre-registration of registration_mode 2.  The reference
+// constructor's 15 arguments behind the grid whose device runs it; match() as the reference's plus the number of points.  The scoring
+// runs on the device (tsd_pdf_match).
+class PDFMatching : public RandomMatching
 {
 public:
   PDFMatching(TsdGrid& grid, unsigned int trials, double epsThresh, unsigned int sizeControlSet, double zhit, double zphi,
               double zshort, double zmax, double zrand, double percentagePointsInC, double rangemax, double sigphi, double sighit,
               double lamshort, double maxAngleDiff, double maxAnglePenalty);
-  virtual ~PDFMatching() {}
   /** whether the device library provides tsd_pdf_match (a host build linked against a library without it has none) */
   static bool available();
   Matrix match(const double* M, const bool* maskM, const double* NM, const double* S, const bool* maskS, unsigned int points,
                double phiMax = M_PI / 4.0, const double transMax = 1.5, const double resolution = 0.0);
-  /** addition (tests): as TSD_PDFMatching::setSeed */
-  void setSeed(long seed) { _seed = seed; }
-  const tsd_tsdpdf_result& lastResult() const { return _last; }
+  Matrix match(Matrix /*TSensor*/, const double* M, const bool* maskM, const double* NM, const double* S, const bool* maskS,
+               unsigned int points, double phiMax, const double transMax, const double resolution) override
+  { return match(M, maskM, NM, S, maskS, points, phiMax, transMax, resolution); }
   /** the parameters of match() as the C ABI takes them */
   tsd_pdfmatch_params params(double phiMax, double resolution) const;
 private:
-  TsdGrid& _grid;
   tsd_pdfmatch_params _prm;
-  long _seed;
-  unsigned long _calls;
-  tsd_tsdpdf_result _last;
 };
 
-// obvious::RandomNormalMatching (registration/ransacMatching/RandomNormalMatching.{h,cpp}) on obvious::RandomMatching: the
-// pre-registration of registration_mode 1.  The reference constructor's three arguments behind the grid whose device runs it; match() as
-// the reference's plus the number of points.  The front end is PDFMatching's, the scoring and the selection run on the device
-// (tsd_rn_match), the rand() streams are drawn here exactly as PDFMatching draws them.
-class RandomNormalMatching
+// obvious::RandomNormalMatching (registration/ransacMatching/RandomNormalMatching.{h,cpp}): the pre-registration of registration_mode
+// 1.  The reference constructor's three arguments behind the grid whose device runs it; match() as the reference's plus the number of
+// points.  The scoring and the selection run on the device (tsd_rn_match).
+class RandomNormalMatching : public RandomMatching
 {
 public:
   RandomNormalMatching(TsdGrid& grid, unsigned int trials = 50, double epsThresh = 0.15, unsigned int sizeControlSet = 180);
-  virtual ~RandomNormalMatching() {}
   /** whether the device library provides tsd_rn_match (a host build linked against a library without it has none) */
   static bool available();
   Matrix match(const double* M, const bool* maskM, const double* NM, const double* S, const bool* maskS, unsigned int points,
                double phiMax = M_PI / 4.0, const double transMax = 1.5, const double resolution = 0.0);
-  /** addition (tests): as TSD_PDFMatching::setSeed */
-  void setSeed(long seed) { _seed = seed; }
-  const tsd_rnmatch_result& lastResult() const { return _last; }
+  Matrix match(Matrix /*TSensor*/, const double* M, const bool* maskM, const double* NM, const double* S, const bool* maskS,
+               unsigned int points, double phiMax, const double transMax, const double resolution) override
+  { return match(M, maskM, NM, S, maskS, points, phiMax, transMax, resolution); }
+  /** the last match() in the mode's own record (ratio, errSum, cntMatch, maxCntMatch) */
+  const tsd_rnmatch_result& lastRating() const { return _lastRn; }
   /** the parameters of match() as the C ABI takes them */
   tsd_rnmatch_params params(double phiMax, double resolution) const;
 private:
-  TsdGrid& _grid;
   tsd_rnmatch_params _prm;
-  long _seed;
-  unsigned long _calls;
-  tsd_rnmatch_result _last;
+  tsd_rnmatch_result _lastRn;
 };
 
 }  // namespace obvious

@@ -37,7 +37,6 @@
 
 namespace tsd {
 
-constexpr int PDFM_MAX_CONTROL = 1024;     // = tsdpdf.hip's PDF_MAX_CONTROL (the front end's control set)
 constexpr int PDFM_WAVES = 4;              // candidates per workgroup and round
 constexpr int PDFM_GRID = 512;             // workgroups at most; their waves stride over the candidates (the model angles are staged once per workgroup)
 
@@ -154,10 +153,8 @@ k_pdfm_score(const double* __restrict__ M, const double* __restrict__ S, const d
     // cos(phi) / sin(phi) from the host (see the head of this file)
     const double2 cs = cos_sin[c];
     const double co = cs.x, si = cs.y;
-    const int ci = cd.ti & PDF_I_MASK;
-    const double sx = S[2 * ci], sy = S[2 * ci + 1];
-    const double T02 = M[2 * cd.idx] - (co * sx + (-si) * sy);
-    const double T12 = M[2 * cd.idx + 1] - (si * sx + co * sy);
+    int ci; double T02, T12;
+    pdf_candidate_T(M, S, cd.idx, cd.ti, co, si, ci, T02, T12);
     double prob = 1.0;
     int fov = 0;
     for (int s0 = 0; s0 < n_control; s0 += 64) {
@@ -167,9 +164,8 @@ k_pdfm_score(const double* __restrict__ M, const double* __restrict__ S, const d
       if (s < n_control) {
         // STemp = T * Control (:253; dgemm: k ascending from 0.0)
         const double2 cp = s_ctrl[s];
-        double cx = 0.0, cy = 0.0;
-        cx += co * cp.x; cx += (-si) * cp.y; cx += T02 * 1.0;
-        cy += si * cp.x; cy += co * cp.y; cy += T12 * 1.0;
+        double cx, cy;
+        pdf_transform_point(co, -si, T02, si, co, T12, cp.x, cp.y, cx, cy);
         const double angle = atan2(cy, cx);
         const double distance = sqrt(cx * cx + cy * cy);                // (:311; pow(., 2) as above)
         double minAngleDiff;
@@ -198,15 +194,16 @@ k_pdfm_score(const double* __restrict__ M, const double* __restrict__ S, const d
 using namespace tsd;
 
 namespace {
+constexpr int PDFM_DBG_MODE = 2;
 // behind the shared layout: [idxM | angles | (range, normaliser) | flag | ungated products | fov counts | (cos, sin) per candidate]
 struct PdfmLayout { size_t off_idx, off_ang, off_dn, off_flag, off_u, off_fov, off_cs, bytes; };
 PdfmLayout pdfm_layout(int n, size_t max_cand)
 {
-  auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  PdfCarve carve;
   PdfmLayout L;
-  L.off_idx = 0; L.off_ang = al((size_t)n * 4); L.off_dn = L.off_ang + al((size_t)n * 8); L.off_flag = L.off_dn + (size_t)n * 16;
-  L.off_u = L.off_flag + 16; L.off_fov = L.off_u + al(max_cand * 8); L.off_cs = L.off_fov + al(max_cand * 4);
-  L.bytes = L.off_cs + max_cand * 16;
+  L.off_idx = carve((size_t)n * 4); L.off_ang = carve((size_t)n * 8); L.off_dn = carve((size_t)n * 16); L.off_flag = carve(16);
+  L.off_u = carve(max_cand * 8); L.off_fov = carve(max_cand * 4); L.off_cs = carve(max_cand * 16);
+  L.bytes = carve.off;
   return L;
 }
 size_t pdfm_extra(int n, size_t max_cand) { return pdfm_layout(n, max_cand).bytes; }
@@ -216,25 +213,19 @@ extern "C" int tsd_pdf_match(tsd_ctx* ctx, const double* model_xy_2B, const uint
                              const uint8_t* mask_s, int beams, const tsd_pdfmatch_params* prm, const int* draws_subsample,
                              const int* draws_control, const int* draws_trials, tsd_tsdpdf_result* result)
 {
-  if (!ctx || !model_xy_2B || !mask_m || !scene_xy_2B || !mask_s || !prm || !draws_subsample || !draws_control || !draws_trials || !result)
-    return TSD_E_ARG;
-  if (beams < 1 || beams > TSD_MAX_BEAMS || prm->size_control_set < 0 || prm->size_control_set > PDFM_MAX_CONTROL || prm->trials < 0)
-    return set_error(ctx, TSD_E_CAPACITY, "tsd_pdf_match: beams / control set out of range", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // TSD_MODE2_TIMING=1: the phases of this call (printed every 100 calls)
-  static const bool timing = std::getenv("TSD_MODE2_TIMING") != nullptr;
-  static double t_acc[8]; static int t_calls;
-  PdfLap lap; lap.on = timing; lap.acc = t_acc;
+  if (int rc = pdf_check_match(ctx, {model_xy_2B, mask_m, scene_xy_2B, mask_s, draws_subsample, draws_control, draws_trials, result},
+                               beams, prm, "tsd_pdf_match: beams / control set out of range"))
+    return rc;
+  static PdfPhaseTimer tm("TSD_MODE2_TIMING");           // the phases of this call
   PdfFrontEnd fe;
   if (int rc = pdf_front_end(ctx, model_xy_2B, mask_m, scene_xy_2B, mask_s, beams, prm->trials, prm->size_control_set, prm->phi_max,
-                             prm->ang_res, draws_subsample, draws_control, draws_trials, pdfm_extra, lap, result, fe,
+                             prm->ang_res, draws_subsample, draws_control, draws_trials, pdfm_extra, tm, result, fe,
                              true /* the host's normals: see the head of this file */))
     return rc;
   if (fe.stage != PdfFrontEnd::SCORE) return TSD_OK;     // the reference's early returns: TBest = identity (:53-65, :134-144, :167-171)
-  char* h = fe.h; char* d = fe.d;
-  const int nC = fe.nC, nM = (int)fe.idxM.size(), nc = (int)fe.cand.size();
+  const int nC = fe.nC, nM = (int)fe.idxM.size(), nc = fe.n_cand();
   const PdfmLayout L = pdfm_layout(fe.n, fe.max_cand);
-  char* hx = h + fe.off_extra; char* dx = d + fe.off_extra;
+  char* hx = fe.h + fe.off_extra; char* dx = fe.d + fe.off_extra;
 
   PdfmParams p;
   p.zhit = prm->zhit; p.zphi = prm->zphi; p.zshort = prm->zshort; p.zmax = prm->zmax; p.zrand = prm->zrand;
@@ -245,75 +236,48 @@ extern "C" int tsd_pdf_match(tsd_ctx* ctx, const double* model_xy_2B, const uint
   const double sp2 = prm->sigphi * prm->sigphi;
   p.skip_phi = prm->zphi == 0.0 && std::isfinite(prm->sigphi) && std::isnormal(sp2) ? 1 : 0;
 
-  // ---- device: per-model-point arrays, score, arg-max
-  const size_t bKu = (size_t)nc * sizeof(PdfCandidate);
-  std::memcpy(h + fe.off_C, fe.control.data(), (size_t)nC * 16);
-  std::memcpy(h + fe.off_K, fe.cand.data(), bKu);
+  // ---- staging: the candidates with libm's cos / sin, the valid model indices, the cleared order flag
+  if (int rc = pdf_stage_candidates(ctx, fe, reinterpret_cast<double2*>(hx + L.off_cs))) return rc;
   std::memcpy(hx + L.off_idx, fe.idxM.data(), (size_t)nM * 4);
   std::memset(hx + L.off_flag, 0, 16);
-  double2* h_cs = reinterpret_cast<double2*>(hx + L.off_cs);
-  for (int c = 0; c < nc; c++) { const double phi = fe.cand[c].phi; h_cs[c] = make_double2(std::cos(phi), std::sin(phi)); }
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d + fe.off_C, h + fe.off_C, fe.bC + bKu, hipMemcpyHostToDevice, ctx->stream));
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(dx + L.off_idx, hx + L.off_idx, (size_t)nM * 4, hipMemcpyHostToDevice, ctx->stream));
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(dx + L.off_flag, hx + L.off_flag, 16, hipMemcpyHostToDevice, ctx->stream));
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(dx + L.off_cs, hx + L.off_cs, (size_t)nc * 16, hipMemcpyHostToDevice, ctx->stream));
-  lap(3);
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (timing)
-    for (auto& e : ev) TSD_HIP_CHECK(ctx, hipEventCreate(&e));
-  const double* dM = reinterpret_cast<const double*>(d);
-  const double* dS = reinterpret_cast<const double*>(d + fe.off_S);
+  tm.lap(3);
+  // ---- device: per-model-point arrays, score, arg-max
   double* d_ang = reinterpret_cast<double*>(dx + L.off_ang);
   double2* d_dn = reinterpret_cast<double2*>(dx + L.off_dn);
   int* d_flag = reinterpret_cast<int*>(dx + L.off_flag);
   {
     ScopedKernelTimer t(ctx, "tsdpdf", true);
-    if (timing) hipEventRecord(ev[0], ctx->stream);
-    hipLaunchKernelGGL(k_pdfm_model, dim3((nM + 255) / 256), dim3(256), 0, ctx->stream, dM, reinterpret_cast<const int*>(dx + L.off_idx), nM,
+    tm.mark(ctx->stream);
+    hipLaunchKernelGGL(k_pdfm_model, dim3((nM + 255) / 256), dim3(256), 0, ctx->stream, fe.dM(), reinterpret_cast<const int*>(dx + L.off_idx), nM,
                        prm->lamshort, d_ang, d_dn, d_flag);
-    if (timing) hipEventRecord(ev[1], ctx->stream);
+    tm.mark(ctx->stream);
     const size_t lds = (size_t)((nM + 1) & ~1) * 8 + (size_t)nC * 16;      // <= 32 KB + 16 KB
     const int blocks = std::min((nc + PDFM_WAVES - 1) / PDFM_WAVES, PDFM_GRID);
-    hipLaunchKernelGGL(k_pdfm_score, dim3(blocks), dim3(64 * PDFM_WAVES), lds, ctx->stream, dM, dS, d_ang, d_dn, d_flag, nM,
-                       reinterpret_cast<const double2*>(d + fe.off_C), nC, reinterpret_cast<const PdfCandidate*>(d + fe.off_K),
-                       reinterpret_cast<const double2*>(dx + L.off_cs), nc, p,
-                       reinterpret_cast<double*>(d + fe.off_prob), reinterpret_cast<double*>(dx + L.off_u), reinterpret_cast<int*>(dx + L.off_fov));
-    if (timing) hipEventRecord(ev[2], ctx->stream);
-    launch_pdf_argmax(ctx->stream, reinterpret_cast<const double*>(d + fe.off_prob), reinterpret_cast<const PdfCandidate*>(d + fe.off_K), nc,
-                      dM, dS, reinterpret_cast<PdfResult*>(d + fe.off_res));
-    if (timing) hipEventRecord(ev[3], ctx->stream);
+    hipLaunchKernelGGL(k_pdfm_score, dim3(blocks), dim3(64 * PDFM_WAVES), lds, ctx->stream, fe.dM(), fe.dS(), d_ang, d_dn, d_flag, nM,
+                       fe.dC(), nC, fe.dK(), reinterpret_cast<const double2*>(dx + L.off_cs), nc, p,
+                       fe.d_prob(), reinterpret_cast<double*>(dx + L.off_u), reinterpret_cast<int*>(dx + L.off_fov));
+    tm.mark(ctx->stream);
+    launch_pdf_argmax(ctx, fe);
+    tm.mark(ctx->stream);
   }
-  TSD_HIP_CHECK(ctx, hipGetLastError());
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(h + fe.off_res, d + fe.off_res, sizeof(PdfResult), hipMemcpyDeviceToHost, ctx->stream));
-  TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  lap(4);
-  if (timing) {
-    for (int i = 0; i < 3; i++) { float ms = 0.f; hipEventElapsedTime(&ms, ev[i], ev[i + 1]); t_acc[5 + i] += 1000.0 * ms; }
-    for (auto& e : ev) hipEventDestroy(e);
-    if (++t_calls % 100 == 0)
-      std::fprintf(stderr, "tsd_pdf_match, us per call: normals of both sets (host) %.1f | lists + control set %.1f | candidates (%d) %.1f | "
-                   "cos / sin + staging + H2D issue %.1f | kernels + D2H %.1f (model arrays %.1f | scoring %.1f | arg-max %.1f)\n",
-                   t_acc[0] / t_calls, t_acc[1] / t_calls, nc, t_acc[2] / t_calls, t_acc[3] / t_calls, t_acc[4] / t_calls,
-                   t_acc[5] / t_calls, t_acc[6] / t_calls, t_acc[7] / t_calls);
-  }
-  const PdfResult* r = reinterpret_cast<const PdfResult*>(h + fe.off_res);
-  std::memcpy(result->T, r->T, sizeof(r->T));
-  result->probability = r->prob; result->idx_model = r->idx; result->idx_scene = r->i;
-  ctx->pdfm_dbg_n = nc; ctx->pdfm_dbg_off_u = fe.off_extra + L.off_u; ctx->pdfm_dbg_off_fov = fe.off_extra + L.off_fov;
+  if (int rc = pdf_fetch_result(ctx, fe, result)) return rc;
+  tm.lap(4);
+  if (tm.due())
+    std::fprintf(stderr, "tsd_pdf_match, us per call: normals of both sets (host) %.1f | lists + control set %.1f | candidates (%d) %.1f | "
+                 "cos / sin + staging + H2D issue %.1f | kernels + D2H %.1f (model arrays %.1f | scoring %.1f | arg-max %.1f)\n",
+                 tm.us(0), tm.us(1), nc, tm.us(2), tm.us(3), tm.us(4), tm.us(5), tm.us(6), tm.us(7));
+  ctx->match_dbg.n = nc; ctx->match_dbg.mode = PDFM_DBG_MODE;
+  ctx->match_dbg.off[0] = fe.off_extra + L.off_u; ctx->match_dbg.off[1] = fe.off_extra + L.off_fov;
   return TSD_OK;
 }
 
 extern "C" int tsd_debug_pdf_match_scores(tsd_ctx* ctx, double* prob_ungated, int* fov, int cap)
 {
   if (!ctx || cap < 0 || (cap > 0 && (!prob_ungated || !fov))) return TSD_E_ARG;
-  const int n = ctx->pdfm_dbg_n;
-  if (n <= 0) return 0;
-  const int m = std::min(n, cap);
-  if (m > 0) {
-    TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    TSD_HIP_CHECK(ctx, hipMemcpy(prob_ungated, ctx->d_pdf + ctx->pdfm_dbg_off_u, (size_t)m * 8, hipMemcpyDeviceToHost));
-    TSD_HIP_CHECK(ctx, hipMemcpy(fov, ctx->d_pdf + ctx->pdfm_dbg_off_fov, (size_t)m * 4, hipMemcpyDeviceToHost));
-  }
-  return n;
+  void* const out[3] = {prob_ungated, fov, nullptr};
+  const int elem[3] = {8, 4, 0};
+  return pdf_debug_scores(ctx, PDFM_DBG_MODE, cap, out, elem);
 }

@@ -40,7 +40,6 @@
 
 namespace tsd {
 
-constexpr int RNM_MAX_CONTROL = 1024;     // = tsdpdf.hip's PDF_MAX_CONTROL (the front end's control set): 16 waves
 constexpr int RNM_GRID = 2048;            // workgroups at most; they stride over the candidates (the model is staged once per workgroup)
 constexpr double RNM_SCALE_ORIENTATION = 0.33;     // _scaleOrientation (RandomNormalMatching.cpp:22)
 
@@ -49,7 +48,7 @@ struct RnmResult { double T[9]; double ratio, err; int cnt, max_cnt, idx, i, win
 
 // One WORKGROUP per candidate, thread s on control point s (blockDim = 64 * ceil(nC / 64)).  Writes, per candidate, cntMatch (before the
 // cntMatchThresh test), maxCntMatch and errSum.
-__global__ void __launch_bounds__(RNM_MAX_CONTROL)
+__global__ void __launch_bounds__(PDF_MAX_CONTROL)
 k_rnm_score(const double2* __restrict__ mv_g, const double* __restrict__ phim_g, int nM, const double2* __restrict__ ctrl_g,
             const double* __restrict__ phic_g, int nC, const PdfCandidate* __restrict__ cand, const double2* __restrict__ cos_sin,
             int n_cand, const double* __restrict__ M, const double* __restrict__ S, double scale_d,
@@ -61,7 +60,7 @@ k_rnm_score(const double2* __restrict__ mv_g, const double* __restrict__ phim_g,
   double* s_phm = reinterpret_cast<double*>(s_c + nC);        // [nM] phiM[idxMValid[k]]
   double* s_phc = s_phm + nM;                                 // [nC] phiControl
   double* s_err = s_phc + nC;                                 // [nC] this candidate's err (0.0 out of view)
-  __shared__ int s_cnt[RNM_MAX_CONTROL / 64], s_max[RNM_MAX_CONTROL / 64];
+  __shared__ int s_cnt[PDF_MAX_CONTROL / 64], s_max[PDF_MAX_CONTROL / 64];
   for (int k = threadIdx.x; k < nM; k += blockDim.x) { s_m[k] = mv_g[k]; s_phm[k] = phim_g[k]; }
   for (int k = threadIdx.x; k < nC; k += blockDim.x) { s_c[k] = ctrl_g[k]; s_phc[k] = phic_g[k]; }
   __syncthreads();
@@ -74,17 +73,14 @@ k_rnm_score(const double2* __restrict__ mv_g, const double* __restrict__ phim_g,
     // T = TransformationMatrix33(phi, 0, 0) + translation (:257-263), with libm's cos(phi) / sin(phi) from the host
     const double2 cs = cos_sin[c];
     const double co = cs.x, si = cs.y;
-    const int ci = cd.ti & PDF_I_MASK;
-    const double sx = S[2 * ci], sy = S[2 * ci + 1];
-    const double T02 = M[2 * cd.idx] - (co * sx + (-si) * sy);
-    const double T12 = M[2 * cd.idx + 1] - (si * sx + co * sy);
+    int ci; double T02, T12;
+    pdf_candidate_T(M, S, cd.idx, cd.ti, co, si, ci, T02, T12);
     double cx = 0.0, cy = 0.0;
     bool in_view = false;
     if (s < nC) {
       // STemp = T * Control (:266; dgemm: k ascending from 0.0)
       const double2 cp = s_c[s];
-      cx += co * cp.x; cx += (-si) * cp.y; cx += T02 * 1.0;
-      cy += si * cp.x; cy += co * cp.y; cy += T12 * 1.0;
+      pdf_transform_point(co, -si, T02, si, co, T12, cp.x, cp.y, cx, cy);
       const double thetaControl = atan2(cy, cx);
       in_view = !(thetaControl > thetaBoundMax || thetaControl < thetaBoundMin);     // (:274)
     }
@@ -176,12 +172,9 @@ k_rnm_select(const int* __restrict__ cnt_g, const int* __restrict__ max_g, const
       const PdfCandidate cd = cand[win];
       const double2 cs = cos_sin[win];
       const double co = cs.x, si = cs.y;
-      const int ci = cd.ti & PDF_I_MASK;
-      const double sx = S[2 * ci], sy = S[2 * ci + 1];
       r.T[0] = co; r.T[1] = -si; r.T[3] = si; r.T[4] = co;
-      r.T[2] = M[2 * cd.idx] - (co * sx + (-si) * sy);
-      r.T[5] = M[2 * cd.idx + 1] - (si * sx + co * sy);
-      r.idx = cd.idx; r.i = ci;
+      pdf_candidate_T(M, S, cd.idx, cd.ti, co, si, r.i, r.T[2], r.T[5]);
+      r.idx = cd.idx;
     }
     *out = r;
   }
@@ -192,16 +185,16 @@ k_rnm_select(const int* __restrict__ cnt_g, const int* __restrict__ max_g, const
 using namespace tsd;
 
 namespace {
+constexpr int RNM_DBG_MODE = 1;
 // behind the shared layout: [model points | phiM | phiControl | (cos, sin) | cntMatch | maxCntMatch | errSum | result], per match
 struct RnmLayout { size_t off_mv, off_phm, off_phc, off_cs, off_cnt, off_max, off_err, off_res, bytes; };
 RnmLayout rnm_layout(int n, size_t max_cand)
 {
-  auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  PdfCarve carve;
   RnmLayout L;
-  L.off_mv = 0; L.off_phm = L.off_mv + (size_t)n * 16; L.off_phc = L.off_phm + al((size_t)n * 8);
-  L.off_cs = L.off_phc + al((size_t)n * 8); L.off_cnt = L.off_cs + max_cand * 16; L.off_max = L.off_cnt + al(max_cand * 4);
-  L.off_err = L.off_max + al(max_cand * 4); L.off_res = L.off_err + al(max_cand * 8);
-  L.bytes = L.off_res + sizeof(RnmResult);
+  L.off_mv = carve((size_t)n * 16); L.off_phm = carve((size_t)n * 8); L.off_phc = carve((size_t)n * 8); L.off_cs = carve(max_cand * 16);
+  L.off_cnt = carve(max_cand * 4); L.off_max = carve(max_cand * 4); L.off_err = carve(max_cand * 8); L.off_res = carve(sizeof(RnmResult));
+  L.bytes = carve.off;
   return L;
 }
 size_t rnm_extra(int n, size_t max_cand) { return rnm_layout(n, max_cand).bytes; }
@@ -211,20 +204,15 @@ extern "C" int tsd_rn_match(tsd_ctx* ctx, const double* model_xy_2B, const uint8
                             const uint8_t* mask_s, int beams, const tsd_rnmatch_params* prm, const int* draws_subsample,
                             const int* draws_control, const int* draws_trials, tsd_rnmatch_result* result)
 {
-  if (!ctx || !model_xy_2B || !mask_m || !scene_xy_2B || !mask_s || !prm || !draws_subsample || !draws_control || !draws_trials || !result)
-    return TSD_E_ARG;
-  if (beams < 1 || beams > TSD_MAX_BEAMS || prm->size_control_set < 0 || prm->size_control_set > RNM_MAX_CONTROL || prm->trials < 0)
-    return set_error(ctx, TSD_E_CAPACITY, "tsd_rn_match: beams / control set out of range", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // TSD_MODE1_TIMING=1: the phases of this call (printed every 100 calls)
-  static const bool timing = std::getenv("TSD_MODE1_TIMING") != nullptr;
-  static double t_acc[8]; static int t_calls;
-  PdfLap lap; lap.on = timing; lap.acc = t_acc;
+  if (int rc = pdf_check_match(ctx, {model_xy_2B, mask_m, scene_xy_2B, mask_s, draws_subsample, draws_control, draws_trials, result},
+                               beams, prm, "tsd_rn_match: beams / control set out of range"))
+    return rc;
+  static PdfPhaseTimer tm("TSD_MODE1_TIMING");           // the phases of this call
   std::memset(result, 0, sizeof(*result));
   tsd_tsdpdf_result fr;
   PdfFrontEnd fe;
   const int rc = pdf_front_end(ctx, model_xy_2B, mask_m, scene_xy_2B, mask_s, beams, prm->trials, prm->size_control_set, prm->phi_max,
-                               prm->ang_res, draws_subsample, draws_control, draws_trials, rnm_extra, lap, &fr, fe,
+                               prm->ang_res, draws_subsample, draws_control, draws_trials, rnm_extra, tm, &fr, fe,
                                true /* the host's normals, as mode 2 */);
   // the reference's early returns: TBest = identity (:82-92, :165-175, :192-201), counts as far as it gets
   std::memcpy(result->T, fr.T, sizeof(fr.T));
@@ -233,92 +221,66 @@ extern "C" int tsd_rn_match(tsd_ctx* ctx, const double* model_xy_2B, const uint8
   result->valid_model = fr.valid_model; result->valid_scene = fr.valid_scene; result->control_points = fr.control_points;
   if (rc) return rc;
   if (fe.stage != PdfFrontEnd::SCORE) return TSD_OK;
-  char* h = fe.h; char* d = fe.d;
-  const int nC = fe.nC, nM = (int)fe.idxM.size(), nc = (int)fe.cand.size();
+  const int nC = fe.nC, nM = (int)fe.idxM.size(), nc = fe.n_cand();
   const RnmLayout L = rnm_layout(fe.n, fe.max_cand);
-  char* hx = h + fe.off_extra; char* dx = d + fe.off_extra;
+  char* hx = fe.h + fe.off_extra; char* dx = fe.d + fe.off_extra;
 
   // ---- host staging: the valid model points and their normal angles (idxMValid order), the control set's angles
-  // (calcPhi(NControl, NULL, .) = phiS at the control points, :145-154), every candidate's cos / sin (libm)
+  // (calcPhi(NControl, NULL, .) = phiS at the control points, :145-154), the candidates with libm's cos / sin
   double2* h_mv = reinterpret_cast<double2*>(hx + L.off_mv);
   double* h_phm = reinterpret_cast<double*>(hx + L.off_phm);
   double* h_phc = reinterpret_cast<double*>(hx + L.off_phc);
-  double2* h_cs = reinterpret_cast<double2*>(hx + L.off_cs);
   for (int k = 0; k < nM; k++) {
     const int i = fe.idxM[k];
     h_mv[k] = make_double2(model_xy_2B[2 * i], model_xy_2B[2 * i + 1]);
     h_phm[k] = fe.phiM[i];
   }
   for (int s = 0; s < nC; s++) h_phc[s] = fe.phiS[fe.idxControl[s]];
-  for (int c = 0; c < nc; c++) { const double phi = fe.cand[c].phi; h_cs[c] = make_double2(std::cos(phi), std::sin(phi)); }
-  const size_t bKu = (size_t)nc * sizeof(PdfCandidate);
-  std::memcpy(h + fe.off_C, fe.control.data(), (size_t)nC * 16);
-  std::memcpy(h + fe.off_K, fe.cand.data(), bKu);
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d + fe.off_C, h + fe.off_C, fe.bC + bKu, hipMemcpyHostToDevice, ctx->stream));
+  if (int e = pdf_stage_candidates(ctx, fe, reinterpret_cast<double2*>(hx + L.off_cs))) return e;
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(dx, hx, L.off_cs + (size_t)nc * 16, hipMemcpyHostToDevice, ctx->stream));
-  lap(3);
+  tm.lap(3);
   const size_t lds = (size_t)nM * 24 + (size_t)nC * 32;       // <= 4 096 x 24 + 1 024 x 32 = 128 KB (160 KB per CU)
   if (int e = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_rnm_score), lds)) return e;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  if (timing)
-    for (auto& e : ev) TSD_HIP_CHECK(ctx, hipEventCreate(&e));
-  const double* dM = reinterpret_cast<const double*>(d);
-  const double* dS = reinterpret_cast<const double*>(d + fe.off_S);
-  const PdfCandidate* dK = reinterpret_cast<const PdfCandidate*>(d + fe.off_K);
+  // ---- device: score, select
   const double2* d_cs = reinterpret_cast<const double2*>(dx + L.off_cs);
   int* d_cnt = reinterpret_cast<int*>(dx + L.off_cnt);
   int* d_max = reinterpret_cast<int*>(dx + L.off_max);
   double* d_err = reinterpret_cast<double*>(dx + L.off_err);
-  RnmResult* d_res = reinterpret_cast<RnmResult*>(dx + L.off_res);
   const unsigned cntMatchThresh = (unsigned)nC / 3;          // (:152)
   {
     ScopedKernelTimer t(ctx, "tsdpdf", true);
-    if (timing) hipEventRecord(ev[0], ctx->stream);
+    tm.mark(ctx->stream);
     const int threads = 64 * std::max((nC + 63) / 64, 1);
     hipLaunchKernelGGL(k_rnm_score, dim3(std::min(nc, RNM_GRID)), dim3(threads), lds, ctx->stream,
                        reinterpret_cast<const double2*>(dx + L.off_mv), reinterpret_cast<const double*>(dx + L.off_phm), nM,
-                       reinterpret_cast<const double2*>(d + fe.off_C), reinterpret_cast<const double*>(dx + L.off_phc), nC, dK, d_cs, nc,
-                       dM, dS, 1.0 / (prm->eps_thresh * prm->eps_thresh) /* _scaleDistance (:21) */, d_cnt, d_max, d_err);
-    if (timing) hipEventRecord(ev[1], ctx->stream);
-    hipLaunchKernelGGL(k_rnm_select, dim3(1), dim3(64), 0, ctx->stream, d_cnt, d_max, d_err, nc, cntMatchThresh, dK, d_cs, dM, dS, d_res);
-    if (timing) hipEventRecord(ev[2], ctx->stream);
+                       fe.dC(), reinterpret_cast<const double*>(dx + L.off_phc), nC, fe.dK(), d_cs, nc,
+                       fe.dM(), fe.dS(), 1.0 / (prm->eps_thresh * prm->eps_thresh) /* _scaleDistance (:21) */, d_cnt, d_max, d_err);
+    tm.mark(ctx->stream);
+    hipLaunchKernelGGL(k_rnm_select, dim3(1), dim3(64), 0, ctx->stream, d_cnt, d_max, d_err, nc, cntMatchThresh, fe.dK(), d_cs, fe.dM(), fe.dS(),
+                       reinterpret_cast<RnmResult*>(dx + L.off_res));
+    tm.mark(ctx->stream);
   }
-  TSD_HIP_CHECK(ctx, hipGetLastError());
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(hx + L.off_res, dx + L.off_res, sizeof(RnmResult), hipMemcpyDeviceToHost, ctx->stream));
-  TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  lap(4);
-  if (timing) {
-    for (int i = 0; i < 2; i++) { float ms = 0.f; hipEventElapsedTime(&ms, ev[i], ev[i + 1]); t_acc[5 + i] += 1000.0 * ms; }
-    for (auto& e : ev) hipEventDestroy(e);
-    if (++t_calls % 100 == 0)
-      std::fprintf(stderr, "tsd_rn_match, us per call: normals of both sets (host) %.1f | lists + control set %.1f | candidates (%d) %.1f | "
-                   "cos / sin + staging + H2D issue %.1f | kernels + D2H %.1f (scoring %.1f | selection %.1f)\n",
-                   t_acc[0] / t_calls, t_acc[1] / t_calls, nc, t_acc[2] / t_calls, t_acc[3] / t_calls, t_acc[4] / t_calls,
-                   t_acc[5] / t_calls, t_acc[6] / t_calls);
-  }
+  if (int e = pdf_fetch(ctx, hx + L.off_res, dx + L.off_res, sizeof(RnmResult))) return e;
+  tm.lap(4);
+  if (tm.due())
+    std::fprintf(stderr, "tsd_rn_match, us per call: normals of both sets (host) %.1f | lists + control set %.1f | candidates (%d) %.1f | "
+                 "cos / sin + staging + H2D issue %.1f | kernels + D2H %.1f (scoring %.1f | selection %.1f)\n",
+                 tm.us(0), tm.us(1), nc, tm.us(2), tm.us(3), tm.us(4), tm.us(5), tm.us(6));
   const RnmResult* r = reinterpret_cast<const RnmResult*>(hx + L.off_res);
   std::memcpy(result->T, r->T, sizeof(r->T));
   result->ratio = r->ratio; result->err_sum = r->err; result->cnt_match = r->cnt; result->max_cnt_match = r->max_cnt;
   result->idx_model = r->idx; result->idx_scene = r->i;
-  ctx->rnm_dbg_n = nc; ctx->rnm_dbg_off_cnt = fe.off_extra + L.off_cnt; ctx->rnm_dbg_off_max = fe.off_extra + L.off_max;
-  ctx->rnm_dbg_off_err = fe.off_extra + L.off_err;
+  ctx->match_dbg.n = nc; ctx->match_dbg.mode = RNM_DBG_MODE;
+  ctx->match_dbg.off[0] = fe.off_extra + L.off_cnt; ctx->match_dbg.off[1] = fe.off_extra + L.off_max; ctx->match_dbg.off[2] = fe.off_extra + L.off_err;
   return TSD_OK;
 }
 
 extern "C" int tsd_debug_rn_match_scores(tsd_ctx* ctx, int* cnt, int* max_cnt, double* err_sum, int cap)
 {
   if (!ctx || cap < 0 || (cap > 0 && (!cnt || !max_cnt || !err_sum))) return TSD_E_ARG;
-  const int n = ctx->rnm_dbg_n;
-  if (n <= 0) return 0;
-  const int m = std::min(n, cap);
-  if (m > 0) {
-    TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    TSD_HIP_CHECK(ctx, hipMemcpy(cnt, ctx->d_pdf + ctx->rnm_dbg_off_cnt, (size_t)m * 4, hipMemcpyDeviceToHost));
-    TSD_HIP_CHECK(ctx, hipMemcpy(max_cnt, ctx->d_pdf + ctx->rnm_dbg_off_max, (size_t)m * 4, hipMemcpyDeviceToHost));
-    TSD_HIP_CHECK(ctx, hipMemcpy(err_sum, ctx->d_pdf + ctx->rnm_dbg_off_err, (size_t)m * 8, hipMemcpyDeviceToHost));
-  }
-  return n;
+  void* const out[3] = {cnt, max_cnt, err_sum};
+  const int elem[3] = {4, 4, 8};
+  return pdf_debug_scores(ctx, RNM_DBG_MODE, cap, out, elem);
 }
 
 extern "C" int tsd_debug_rn_select(tsd_ctx* ctx, const int* cnt, const int* max_cnt, const double* err_sum, int n, int thresh, int* winner)

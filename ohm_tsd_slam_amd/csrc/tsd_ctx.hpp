@@ -261,11 +261,10 @@ struct tsd_ctx {
 
   // TSD_PDF pre-registration (tsdpdf.hip): one device + one pinned staging buffer, grown on demand
   char* d_pdf = nullptr; char* h_pdf = nullptr; size_t pdf_bytes = 0;
-  // registration_mode 2 (pdfmatch.hip): where the last tsd_pdf_match left its per-candidate values in d_pdf (tsd_debug_pdf_match_scores);
-  // any later pre-registration call on this context reuses the buffer and clears the count
-  int pdfm_dbg_n = 0; size_t pdfm_dbg_off_u = 0, pdfm_dbg_off_fov = 0;
-  // registration_mode 1 (rnmatch.hip): the same for the last tsd_rn_match (tsd_debug_rn_match_scores)
-  int rnm_dbg_n = 0; size_t rnm_dbg_off_cnt = 0, rnm_dbg_off_max = 0, rnm_dbg_off_err = 0;
+  // where the last tsd_pdf_match (mode 2: ungated products, fov counts) / tsd_rn_match (mode 1: cntMatch, maxCntMatch, errSum) left its
+  // per-candidate arrays in d_pdf (tsd_debug_pdf_match_scores / tsd_debug_rn_match_scores); any later pre-registration call on this
+  // context reuses the buffer and clears the count
+  struct { int n = 0, mode = 0; size_t off[3] = {0, 0, 0}; } match_dbg;
 
   // occupancy
   int8_t* d_occ = nullptr;       // persistent map (ThreadGrid::_occGridContent)

@@ -40,7 +40,6 @@
 
 namespace tsd {
 
-constexpr int PDF_MAX_CONTROL = 1024;      // control points held in LDS (16 KB)
 constexpr int PDF_BATCH = 4;               // look-ups per LANE in flight together (64 x 4 control points per round)
 
 // One WAVE per candidate: probability of the control set under T(idx, i).  Lane l takes the control points l, l + 64, ...: their
@@ -88,10 +87,8 @@ pdf_score_body(const GridDev& g, const double* __restrict__ pose /* first two ro
   PdfCandidate cd; cd.idx = idx_rd; cd.ti = ti_rd; cd.phi = phi_rd;
   // T = MatrixFactory::TransformationMatrix33(phi, 0, 0) + translation (TSD_PDFMatching.cpp:217-223)
   const double co = cos(cd.phi), si = sin(cd.phi);
-  const int ci = cd.ti & PDF_I_MASK;
-  const double sx = S[2 * ci], sy = S[2 * ci + 1];
-  const double T02 = M[2 * cd.idx] - (co * sx + (-si) * sy);
-  const double T12 = M[2 * cd.idx + 1] - (si * sx + co * sy);
+  int ci; double T02, T12;
+  pdf_candidate_T(M, S, cd.idx, cd.ti, co, si, ci, T02, T12);
   // TMap = TSensor * T (3 x 3 dgemm: k ascending from 0.0)
   const double T[9] = {co, -si, T02, si, co, T12, 0.0, 0.0, 1.0};
   double TM[6];
@@ -119,9 +116,8 @@ pdf_score_body(const GridDev& g, const double* __restrict__ pose /* first two ro
       if (s0 + 64 * b >= n_control) continue;                // (wave-uniform)
       const double2 cp = make_double2(cpx[b], cpy[b]);
       // STemp = TMap * Control, Control column = (x, y, 1)
-      double cx = 0.0, cy = 0.0;
-      cx += TM[0] * cp.x; cx += TM[1] * cp.y; cx += TM[2] * 1.0;
-      cy += TM[3] * cp.x; cy += TM[4] * cp.y; cy += TM[5] * 1.0;
+      double cx, cy;
+      pdf_transform_point(TM[0], TM[1], TM[2], TM[3], TM[4], TM[5], cp.x, cp.y, cx, cy);
       int p = 0, lx = 0, ly = 0; double dx = 0.0, dy = 0.0;
       inside[b] = coord2cell(g, cx, cy, p, lx, ly, dx, dy);
       if (!inside[b]) { p = 0; lx = 0; ly = 0; }
@@ -180,10 +176,10 @@ k_pdf_argmax(const double* __restrict__ prob, const PdfCandidate* __restrict__ c
 {
   pdf_argmax_body(prob, cand, n_cand, M, S, out, hdr, host_hdr, host_res);
 }
-void launch_pdf_argmax(hipStream_t stream, const double* prob, const PdfCandidate* cand, int n_cand, const double* M, const double* S,
-                       PdfResult* out)
+void launch_pdf_argmax(tsd_ctx* ctx, const PdfFrontEnd& fe)
 {
-  hipLaunchKernelGGL(k_pdf_argmax, dim3(1), dim3(1024), 0, stream, prob, cand, n_cand, M, S, out, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(k_pdf_argmax, dim3(1), dim3(1024), 0, ctx->stream, fe.d_prob(), fe.dK(), fe.n_cand(), fe.dM(), fe.dS(), fe.d_res(),
+                     nullptr, nullptr, nullptr);
 }
 struct PdfArgmaxBatch { PdfArgmaxEntry e[PDF_BATCH_BYVAL]; };
 __global__ void __launch_bounds__(1024)
@@ -698,19 +694,48 @@ static void calc_normals(const double* M, int points, std::vector<double>& N, co
   }
 }
 
+// RandomMatching::subsampleMask (RandomMatching.cpp:176-189) with probability 180 / #valid, where the matchers call it (< 0.99)
+static void pdf_subsample_mask(uint8_t* mask, int n, const int* draws)
+{
+  unsigned valid = 0;
+  for (int i = 0; i < n; i++) if (mask[i]) valid++;
+  double probability = 180.0 / (double)valid;
+  if (probability >= 0.99) return;
+  if (probability > 1.0) probability = 1.0;
+  if (probability < 0.0) probability = 0.0;
+  const int thresh = (int)(1000.0 - probability * 1000.0 + 0.5);
+  for (int i = 0; i < n; i++) if ((draws[i] % 1000) < thresh) mask[i] = 0;
+}
+
+// phiMax capped at pi/2 and the window of +-span beams it allows (TSD_PDFMatching.cpp:163-175; no resolution: every beam); returns
+// the candidate list's upper bound, trials x (2 span + 1) scene points
+static size_t pdf_candidate_bound(double phi_max_in, double ang_res, int n, int trials_cfg, double& phi_max, int& span)
+{
+  phi_max = std::min(phi_max_in, M_PI * 0.5);
+  span = ang_res > 1e-6 ? (int)std::floor(phi_max / ang_res) : n;
+  if (span > n) span = n;
+  return (size_t)std::max(trials_cfg, 0) * (size_t)std::min(2 * span + 1, n) + 1;
+}
+
+static void pdf_fill_result(tsd_tsdpdf_result* result, const PdfResult* r)
+{
+  std::memcpy(result->T, r->T, sizeof(r->T));
+  result->probability = r->prob; result->idx_model = r->idx; result->idx_scene = r->i;
+}
+
 int pdf_front_end(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m, const double* scene_xy_2B, const uint8_t* mask_s,
                   int beams, int trials_cfg, int size_control_set, double phi_max_in, double ang_res, const int* draws_subsample,
-                  const int* draws_control, const int* draws_trials, PdfExtraBytes extra, PdfLap& lap, tsd_tsdpdf_result* result,
+                  const int* draws_control, const int* draws_trials, PdfExtraBytes extra, PdfPhaseTimer& tm, tsd_tsdpdf_result* result,
                   PdfFrontEnd& fe, bool host_normals_call)
 {
+  tm.start();
   const int n = beams;
   const int SR = 10 / 2;                                   // _pcaSearchRange / 2 (TSD_PDFMatching.cpp:18)
   for (int i = 0; i < 9; i++) result->T[i] = (i % 4 == 0) ? 1.0 : 0.0;     // TBest.setIdentity()
   result->probability = 0.0; result->idx_model = -1; result->idx_scene = -1; result->candidates = 0;
   result->valid_model = 0; result->valid_scene = 0; result->control_points = 0; result->reserved = 0;
   fe.n = n; fe.stage = PdfFrontEnd::FEW_POINTS;
-  ctx->pdfm_dbg_n = 0;                                     // (tsd_debug_pdf_match_scores: the buffer is about to be reused)
-  ctx->rnm_dbg_n = 0;                                      // (tsd_debug_rn_match_scores: the same)
+  ctx->match_dbg.n = 0;                                    // (tsd_debug_*_match_scores: the buffer is about to be reused)
   if (n < 3) return TSD_OK;                                // "Model and scene contain too less points" (:53-57)
   const double* M = model_xy_2B; const double* S = scene_xy_2B;
 
@@ -718,30 +743,21 @@ int pdf_front_end(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m
   std::vector<double>& phiM = fe.phiM; std::vector<double>& phiS = fe.phiS;
   phiM.assign((size_t)n, 0.0); phiS.assign((size_t)n, 0.0);
   std::vector<uint8_t> mMp(mask_m, mask_m + n), mSp(mask_s, mask_s + n);
-  unsigned valid = 0;
-  for (int i = 0; i < n; i++) if (mSp[i]) valid++;
-  double probability = 180.0 / (double)valid;
-  if (probability < 0.99) {                                // subsampleMask (RandomMatching.cpp:176-189)
-    if (probability > 1.0) probability = 1.0;
-    if (probability < 0.0) probability = 0.0;
-    const int thresh = (int)(1000.0 - probability * 1000.0 + 0.5);
-    for (int i = 0; i < n; i++) if ((draws_subsample[i] % 1000) < thresh) mSp[i] = 0;
-  }
+  pdf_subsample_mask(mSp.data(), n, draws_subsample);
   const bool res_ok = ang_res > 1e-6;                      // (reported where the reference does, behind the point-count exits: :171-175)
-  const double phi_max = std::min(phi_max_in, M_PI * 0.5);
-  int span = res_ok ? (int)std::floor(phi_max / ang_res) : n;
-  if (span > n) span = n;
-  fe.phi_max = phi_max; fe.span = span;
   // device buffer: [M | S | mask_in M, S | mask_io M, S | phi M, S | control | candidates | pose | prob | result | extra]; the
-  // candidate list is sized for its upper bound (trials x (2 span) scene points) because the normals come back before it is known
-  const size_t max_cand = (size_t)std::max(trials_cfg, 0) * (size_t)std::min(2 * span + 1, n) + 1;
-  const size_t bM = (size_t)n * 16, bMask = ((size_t)n + 15) & ~(size_t)15, bPhi = (size_t)n * 8;
-  const size_t bC = (size_t)std::max(size_control_set, 1) * 16, bK = max_cand * sizeof(PdfCandidate), bP = 80;
-  const size_t off_S = bM, off_mi = 2 * bM, off_mo = off_mi + 2 * bMask, off_phi = off_mo + 2 * bMask;
-  const size_t off_C = off_phi + 2 * bPhi, off_K = off_C + bC, off_P = off_K + ((bK + 15) & ~(size_t)15);
-  const size_t off_prob = off_P + bP, off_res = off_prob + max_cand * sizeof(double);
-  const size_t off_extra = (off_res + sizeof(PdfResult) + 15) & ~(size_t)15;
-  const size_t total = extra ? off_extra + extra(n, max_cand) : off_res + sizeof(PdfResult);
+  // candidate list is sized for its upper bound because the normals come back before it is known
+  const size_t max_cand = pdf_candidate_bound(phi_max_in, ang_res, n, trials_cfg, fe.phi_max, fe.span);
+  const double phi_max = fe.phi_max; const int span = fe.span;
+  const size_t bM = (size_t)n * 16, bMask = PdfCarve::al((size_t)n), bPhi = (size_t)n * 8;
+  const size_t bC = (size_t)std::max(size_control_set, 1) * 16;
+  PdfCarve carve;
+  carve(bM);
+  const size_t off_S = carve(bM), off_mi = carve(2 * bMask), off_mo = carve(2 * bMask), off_phi = carve(2 * bPhi);
+  const size_t off_C = carve(bC), off_K = carve(max_cand * sizeof(PdfCandidate)), off_P = carve(80);
+  const size_t off_prob = carve.exact(max_cand * sizeof(double)), off_res = carve.exact(sizeof(PdfResult));
+  const size_t off_extra = PdfCarve::al(carve.off);
+  const size_t total = extra ? off_extra + extra(n, max_cand) : carve.off;
   fe.max_cand = max_cand; fe.bC = bC;
   fe.off_S = off_S; fe.off_C = off_C; fe.off_K = off_K; fe.off_P = off_P; fe.off_prob = off_prob; fe.off_res = off_res; fe.off_extra = off_extra;
   if (total > ctx->pdf_bytes) {
@@ -763,7 +779,7 @@ int pdf_front_end(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m
     std::vector<double> NM(2 * (size_t)n, 0.0), NS(2 * (size_t)n, 0.0);
     calc_normals(M, n, NM, mask_m, mMp, SR);
     for (int i = 0; i < n; i++) phiM[i] = mMp[i] ? std::atan2(NM[2 * i + 1], NM[2 * i]) : -1e6;     // calcPhi (:155-174)
-    lap(0);
+    tm.lap(0);
     calc_normals(S, n, NS, mask_s, mSp, SR);
     for (int i = 0; i < n; i++) phiS[i] = mSp[i] ? std::atan2(NS[2 * i + 1], NS[2 * i]) : -1e6;
     TSD_HIP_CHECK(ctx, hipMemcpyAsync(d, h, 2 * bM, hipMemcpyHostToDevice, ctx->stream));
@@ -785,7 +801,7 @@ int pdf_front_end(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m
     TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(mMp.data(), h + off_mo, (size_t)n); std::memcpy(mSp.data(), h + off_mo + bMask, (size_t)n);
     std::memcpy(phiM.data(), h + off_phi, bPhi); std::memcpy(phiS.data(), h + off_phi + bPhi, bPhi);
-    lap(0);
+    tm.lap(0);
   }
   std::vector<int>& idxM = fe.idxM; std::vector<int>& idxS = fe.idxS;
   idxM.clear(); idxS.clear();
@@ -808,7 +824,7 @@ int pdf_front_end(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m
     }
   }
   fe.nC = nC;
-  lap(1);
+  tm.lap(1);
   result->valid_model = (int)idxM.size(); result->valid_scene = (int)idxS.size(); result->control_points = nC;
   fe.stage = PdfFrontEnd::FEW_VALID;
   if (idxS.size() < 3 || idxM.size() < 3) return TSD_OK;   // "Too less valid points" (:129-139): identity
@@ -841,8 +857,48 @@ int pdf_front_end(tsd_ctx* ctx, const double* model_xy_2B, const uint8_t* mask_m
   if (cand.empty()) return TSD_OK;
   if (cand.size() > max_cand) return set_error(ctx, TSD_E_CAPACITY, "pdf_front_end: candidate bound", hipSuccess);
   fe.stage = PdfFrontEnd::SCORE;
-  lap(2);
+  tm.lap(2);
   return TSD_OK;
+}
+
+int pdf_stage_candidates(tsd_ctx* ctx, const PdfFrontEnd& fe, double2* h_cos_sin)
+{
+  const size_t bKu = fe.cand.size() * sizeof(PdfCandidate);
+  std::memcpy(fe.h + fe.off_C, fe.control.data(), (size_t)fe.nC * 16);
+  std::memcpy(fe.h + fe.off_K, fe.cand.data(), bKu);
+  if (h_cos_sin)
+    for (size_t c = 0; c < fe.cand.size(); c++) { const double phi = fe.cand[c].phi; h_cos_sin[c] = make_double2(std::cos(phi), std::sin(phi)); }
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(fe.d + fe.off_C, fe.h + fe.off_C, fe.bC + bKu, hipMemcpyHostToDevice, ctx->stream));
+  return TSD_OK;
+}
+
+int pdf_fetch(tsd_ctx* ctx, void* h_rec, const void* d_rec, size_t bytes)
+{
+  TSD_HIP_CHECK(ctx, hipGetLastError());
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(h_rec, d_rec, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return TSD_OK;
+}
+
+int pdf_fetch_result(tsd_ctx* ctx, const PdfFrontEnd& fe, tsd_tsdpdf_result* result)
+{
+  if (int rc = pdf_fetch(ctx, fe.h + fe.off_res, fe.d + fe.off_res, sizeof(PdfResult))) return rc;
+  pdf_fill_result(result, reinterpret_cast<const PdfResult*>(fe.h + fe.off_res));
+  return TSD_OK;
+}
+
+int pdf_debug_scores(tsd_ctx* ctx, int mode, int cap, void* const out[3], const int elem[3])
+{
+  const int n = ctx->match_dbg.mode == mode ? ctx->match_dbg.n : 0;
+  if (n <= 0) return 0;
+  const int m = std::min(n, cap);
+  if (m > 0) {
+    TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int a = 0; a < 3 && elem[a]; a++)
+      TSD_HIP_CHECK(ctx, hipMemcpy(out[a], ctx->d_pdf + ctx->match_dbg.off[a], (size_t)m * elem[a], hipMemcpyDeviceToHost));
+  }
+  return n;
 }
 
 }  // namespace tsd
@@ -854,56 +910,37 @@ extern "C" int tsd_tsdpdf_match(tsd_ctx* ctx, const double pose33[9], const doub
                                 const int* draws_subsample, const int* draws_control, const int* draws_trials,
                                 tsd_tsdpdf_result* result)
 {
-  if (!ctx || !pose33 || !model_xy_2B || !mask_m || !scene_xy_2B || !mask_s || !prm || !draws_subsample || !draws_control ||
-      !draws_trials || !result)
-    return TSD_E_ARG;
-  if (beams < 1 || beams > TSD_MAX_BEAMS || prm->size_control_set < 0 || prm->size_control_set > PDF_MAX_CONTROL || prm->trials < 0)
-    return set_error(ctx, TSD_E_CAPACITY, "tsd_tsdpdf_match: beams / control set out of range", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (int rc = pdf_check_match(ctx, {pose33, model_xy_2B, mask_m, scene_xy_2B, mask_s, draws_subsample, draws_control, draws_trials, result},
+                               beams, prm, "tsd_tsdpdf_match: beams / control set out of range"))
+    return rc;
   if (int rcd_ = drain_async_push(ctx)) return rcd_;     // (the scoring reads the grid: behind a push still on the push stream)
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // TSD_MODE3_TIMING=1: the host phases of this call (printed every 100 calls)
-  static const bool timing = std::getenv("TSD_MODE3_TIMING") != nullptr;
-  static double t_acc[6]; static int t_calls;
-  PdfLap lap; lap.on = timing; lap.acc = t_acc;
+  static PdfPhaseTimer tm("TSD_MODE3_TIMING");           // the host phases of this call
   PdfFrontEnd fe;
   if (int rc = pdf_front_end(ctx, model_xy_2B, mask_m, scene_xy_2B, mask_s, beams, prm->trials, prm->size_control_set, prm->phi_max,
-                             prm->ang_res, draws_subsample, draws_control, draws_trials, nullptr, lap, result, fe))
+                             prm->ang_res, draws_subsample, draws_control, draws_trials, nullptr, tm, result, fe))
     return rc;
   if (fe.stage == PdfFrontEnd::NO_RESOLUTION) return set_error(ctx, TSD_E_ARG, "tsd_tsdpdf_match: resolution not properly set", hipSuccess);   // :171-175
   if (fe.stage != PdfFrontEnd::SCORE) return TSD_OK;
-  char* h = fe.h; char* d = fe.d;
-  const int nC = fe.nC;
-  const std::vector<PdfCandidate>& cand = fe.cand;
+  const int nC = fe.nC, nc = fe.n_cand();
 
   // ---- device: score + arg-max
-  const size_t bKu = cand.size() * sizeof(PdfCandidate);
-  std::memcpy(h + fe.off_C, fe.control.data(), (size_t)nC * 16);
-  std::memcpy(h + fe.off_K, cand.data(), bKu); std::memcpy(h + fe.off_P, pose33, 9 * sizeof(double));
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d + fe.off_C, h + fe.off_C, fe.bC + bKu, hipMemcpyHostToDevice, ctx->stream));
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d + fe.off_P, h + fe.off_P, 80, hipMemcpyHostToDevice, ctx->stream));
-  lap(3);
+  std::memcpy(fe.h + fe.off_P, pose33, 9 * sizeof(double));
+  if (int rc = pdf_stage_candidates(ctx, fe, nullptr)) return rc;
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(fe.d + fe.off_P, fe.h + fe.off_P, 80, hipMemcpyHostToDevice, ctx->stream));
+  tm.lap(3);
   {
     ScopedKernelTimer t(ctx, "tsdpdf", true);
-    const int nc = (int)cand.size();
-    hipLaunchKernelGGL(k_pdf_score, dim3((nc + PDF_WAVES - 1) / PDF_WAVES), dim3(64 * PDF_WAVES), 0, ctx->stream, ctx->grid, reinterpret_cast<const double*>(d + fe.off_P),
-                       reinterpret_cast<const double*>(d), reinterpret_cast<const double*>(d + fe.off_S),
-                       reinterpret_cast<const double2*>(d + fe.off_C), nC, reinterpret_cast<const PdfCandidate*>(d + fe.off_K), nc,
-                       prm->zrand, reinterpret_cast<double*>(d + fe.off_prob), nullptr, nc, nC > 0 ? nC : 1);
-    hipLaunchKernelGGL(k_pdf_argmax, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const double*>(d + fe.off_prob),
-                       reinterpret_cast<const PdfCandidate*>(d + fe.off_K), nc, reinterpret_cast<const double*>(d),
-                       reinterpret_cast<const double*>(d + fe.off_S), reinterpret_cast<PdfResult*>(d + fe.off_res), nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(k_pdf_score, dim3((nc + PDF_WAVES - 1) / PDF_WAVES), dim3(64 * PDF_WAVES), 0, ctx->stream, ctx->grid,
+                       reinterpret_cast<const double*>(fe.d + fe.off_P), fe.dM(), fe.dS(), fe.dC(), nC, fe.dK(), nc,
+                       prm->zrand, fe.d_prob(), nullptr, nc, nC > 0 ? nC : 1);
+    launch_pdf_argmax(ctx, fe);
   }
-  TSD_HIP_CHECK(ctx, hipGetLastError());
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(h + fe.off_res, d + fe.off_res, sizeof(PdfResult), hipMemcpyDeviceToHost, ctx->stream));
-  TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  lap(4);
-  if (timing && ++t_calls % 100 == 0)
+  if (int rc = pdf_fetch_result(ctx, fe, result)) return rc;
+  tm.lap(4);
+  if (tm.due())
     std::fprintf(stderr, "tsd_tsdpdf_match, us per call: normals of both sets (%s) %.1f | lists + control set %.1f | candidates (%d) %.1f | staging + H2D issue %.1f | kernels + D2H %.1f\n",
-                 std::getenv("TSD_PDF_HOST_NORMALS") ? "host" : "device", t_acc[0] / t_calls, t_acc[1] / t_calls, (int)cand.size(), t_acc[2] / t_calls, t_acc[3] / t_calls, t_acc[4] / t_calls);
-  const PdfResult* r = reinterpret_cast<const PdfResult*>(h + fe.off_res);
-  std::memcpy(result->T, r->T, sizeof(r->T));
-  result->probability = r->prob; result->idx_model = r->idx; result->idx_scene = r->i;
+                 std::getenv("TSD_PDF_HOST_NORMALS") ? "host" : "device", tm.us(0), tm.us(1), nc, tm.us(2), tm.us(3), tm.us(4));
   return TSD_OK;
 }
 
@@ -929,20 +966,16 @@ extern "C" int tsd_scan_preregister(tsd_sensor* s, const tsd_tsdpdf_params* prm,
   if (s->pre.ev && s->pre.copied && !s->pre.direct) TSD_HIP_CHECK(ctx, hipEventSynchronize(s->pre.ev));
   tsd_sensor::PreLayout L{};
   L.n = n; L.trials = prm->trials; L.size_control_set = prm->size_control_set; L.zrand = prm->zrand;
-  L.phi_max = std::min(prm->phi_max, M_PI * 0.5);
-  L.span = (int)std::floor(L.phi_max / prm->ang_res);
-  if (L.span > n) L.span = n;
-  L.max_cand = (int)std::min<size_t>((size_t)std::max(prm->trials, 0) * (size_t)std::min(2 * L.span + 1, n) + 1, (size_t)1 << 22);
-  const size_t bM = (size_t)n * 16, bMask = ((size_t)n + 15) & ~(size_t)15, bPhi = (size_t)n * 8;
-  auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  L.off_S = 0; L.off_ms = bM; L.off_msp = L.off_ms + bMask; L.off_dc = L.off_msp + bMask;
-  L.off_dt = L.off_dc + al((size_t)std::max(prm->size_control_set, 1) * 4);
-  L.in_bytes = L.off_dt + al((size_t)std::max(prm->trials, 1) * 4);
-  L.off_mo_m = L.in_bytes; L.off_mo_s = L.off_mo_m + bMask; L.off_phi_m = L.off_mo_s + bMask; L.off_phi_s = L.off_phi_m + bPhi;
-  L.off_C = L.off_phi_s + bPhi; L.off_K = L.off_C + al((size_t)std::max(prm->size_control_set, 1) * 16);
-  L.off_prob = L.off_K + al((size_t)L.max_cand * sizeof(PdfCandidate)); L.off_hdr = L.off_prob + al((size_t)L.max_cand * 8);
-  L.off_res = L.off_hdr + al(sizeof(PdfHeader));
-  const size_t total = L.off_res + al(sizeof(PdfResult));
+  L.max_cand = (int)std::min<size_t>(pdf_candidate_bound(prm->phi_max, prm->ang_res, n, prm->trials, L.phi_max, L.span), (size_t)1 << 22);
+  const size_t bM = (size_t)n * 16, bPhi = (size_t)n * 8, nCtrl = (size_t)std::max(prm->size_control_set, 1);
+  PdfCarve carve;
+  L.off_S = carve(bM); L.off_ms = carve((size_t)n); L.off_msp = carve((size_t)n); L.off_dc = carve(nCtrl * 4);
+  L.off_dt = carve((size_t)std::max(prm->trials, 1) * 4);
+  L.in_bytes = carve.off;
+  L.off_mo_m = carve((size_t)n); L.off_mo_s = carve((size_t)n); L.off_phi_m = carve.exact(bPhi); L.off_phi_s = carve.exact(bPhi);
+  L.off_C = carve(nCtrl * 16); L.off_K = carve((size_t)L.max_cand * sizeof(PdfCandidate));
+  L.off_prob = carve((size_t)L.max_cand * 8); L.off_hdr = carve(sizeof(PdfHeader)); L.off_res = carve(sizeof(PdfResult));
+  const size_t total = carve.off;
   // The in-flight scan's arg-max writes its header and result into the PINNED buffer at the offsets of ITS layout (pre_res_off_*),
   // and tsd_scan_preregistration_result reads them there after the collect: a layout that needs new buffers, or whose inputs would
   // reach into those records, cannot be armed ahead -- the caller arms it after tsd_scan_collect.
@@ -968,15 +1001,7 @@ extern "C" int tsd_scan_preregister(tsd_sensor* s, const tsd_tsdpdf_params* prm,
   std::memcpy(h + L.off_ms, mask_s, (size_t)n);
   uint8_t* mSp = reinterpret_cast<uint8_t*>(h + L.off_msp);
   std::memcpy(mSp, mask_s, (size_t)n);
-  unsigned valid = 0;
-  for (int i = 0; i < n; i++) if (mSp[i]) valid++;
-  double probability = 180.0 / (double)valid;
-  if (probability < 0.99) {                                // subsampleMask (RandomMatching.cpp:176-189)
-    if (probability > 1.0) probability = 1.0;
-    if (probability < 0.0) probability = 0.0;
-    const int thresh = (int)(1000.0 - probability * 1000.0 + 0.5);
-    for (int i = 0; i < n; i++) if ((draws_subsample[i] % 1000) < thresh) mSp[i] = 0;
-  }
+  pdf_subsample_mask(mSp, n, draws_subsample);
   std::memcpy(h + L.off_dc, draws_control, (size_t)prm->size_control_set * 4);
   std::memcpy(h + L.off_dt, draws_trials, (size_t)prm->trials * 4);
   s->pre.layout = L;
@@ -1136,8 +1161,7 @@ extern "C" int tsd_scan_preregistration_result(tsd_sensor* s, tsd_tsdpdf_result*
   if (!s->pre.ran || s->fused.submitted) return set_error(s->ctx, TSD_E_ARG, "tsd_scan_preregistration_result: no collected scan with a pre-registration", hipSuccess);
   const PdfHeader* hd = reinterpret_cast<const PdfHeader*>(s->pre.h + s->pre.res_off_hdr);
   const PdfResult* r = reinterpret_cast<const PdfResult*>(s->pre.h + s->pre.res_off_res);
-  std::memcpy(result->T, r->T, sizeof(r->T));
-  result->probability = r->prob; result->idx_model = r->idx; result->idx_scene = r->i;
+  pdf_fill_result(result, r);
   result->candidates = hd->identity ? 0 : hd->n_cand;
   result->valid_model = hd->n_model_valid; result->valid_scene = hd->n_scene_valid; result->control_points = hd->n_control;
   result->reserved = 0;

@@ -1,7 +1,9 @@
-// tsdpdf_device.hpp -- what the TSD_PDF pre-registration's kernels (tsdpdf.hip) and the registration kernel (icp_kernels.hip) share: the
-// candidate / header / result records and the arg-max over the scored candidates -- a kernel of its own (k_pdf_argmax) in the unfused
-// and batched paths, the FIRST WORKGROUP of the registration's launch in the fused scan (k_icp_pre: the registration needs Tinit only
-// ~2.5 us into its set-up, which is about what the arg-max takes).
+// tsdpdf_device.hpp -- what the kernels of the three pre-registrations (registration_mode 1 rnmatch.hip, 2 pdfmatch.hip, 3 tsdpdf.hip)
+// and the registration kernel (icp_kernels.hip) share: the candidate / header / result records, the candidate's rigid motion T(idx, i)
+// and a point under it (pdf_candidate_T, pdf_transform_point: ONE spelling of the operation order for every mode), and the arg-max
+// over the scored candidates -- a kernel of its own (k_pdf_argmax) in the unfused and batched paths, the FIRST WORKGROUP of the
+// registration's launch in the fused scan (k_icp_pre: the registration needs Tinit only ~2.5 us into its set-up, which is about what
+// the arg-max takes).
 #pragma once
 #include "tsd_ctx.hpp"
 #include "tsd_device.hpp"
@@ -13,6 +15,7 @@ namespace tsd {
 struct PdfCandidate { int idx, ti; double phi; };
 constexpr int PDF_I_BITS = 12, PDF_I_MASK = (1 << PDF_I_BITS) - 1;
 static_assert(TSD_MAX_BEAMS <= (1 << PDF_I_BITS), "scene index field of PdfCandidate::ti");
+constexpr int PDF_MAX_CONTROL = 1024;      // the front end's control set at most (mode 3 holds it in LDS: 16 KB; mode 1: one thread each)
 struct PdfResult { double T[9]; double prob; int idx, i, candidates, pad; };
 // what k_pdf_prepare (the fused scan's device-side list building) leaves for the scoring and arg-max kernels, which the host then
 // launches without knowing the counts
@@ -25,6 +28,33 @@ struct PdfArgmaxEntry { const double* prob; const PdfCandidate* cand; const doub
 // rows at `flag` (128 bytes)
 struct IcpPreArgs { PdfArgmaxEntry am; unsigned int* flag; unsigned int seq; };
 struct IcpPreLaunch { IcpPreArgs dev; hipEvent_t done; };        // (host side: + the event to record at the launch's completion)
+
+// T(idx, i) = TransformationMatrix33(phi, 0, 0) + the translation that moves scene point i onto model point idx
+// (TSD_PDFMatching.cpp:217-223 = PDFMatching.cpp:244-250 = RandomNormalMatching.cpp:257-263).  co / si are the caller's (device cos / sin
+// in mode 3 and the arg-max, the host's libm pair in modes 1 and 2: see the head of pdfmatch.hip).  By value: the arg-max requests the
+// winner's two points itself, ahead of the sine and cosine.
+__device__ __forceinline__ void pdf_candidate_T(double mx, double my, double sx, double sy, double co, double si, double& T02, double& T12)
+{
+  T02 = mx - (co * sx + (-si) * sy);
+  T12 = my - (si * sx + co * sy);
+}
+// ... from the candidate's (idx, ti) and the beam-indexed point sets; ci: its scene index
+__device__ __forceinline__ void pdf_candidate_T(const double* M, const double* S, int idx, int ti, double co,
+                                                double si, int& ci, double& T02, double& T12)
+{
+  ci = ti & PDF_I_MASK;
+  const double sx = S[2 * ci], sy = S[2 * ci + 1];
+  pdf_candidate_T(M[2 * idx], M[2 * idx + 1], sx, sy, co, si, T02, T12);
+}
+// STemp = T * (x, y, 1) for the two rows (a0 a1 a2), (b0 b1 b2) of T (dgemm: k ascending from 0.0)
+__device__ __forceinline__ void pdf_transform_point(double a0, double a1, double a2, double b0, double b1, double b2, double x, double y,
+                                                    double& cx, double& cy)
+{
+  double tx = 0.0, ty = 0.0;
+  tx += a0 * x; tx += a1 * y; tx += a2 * 1.0;
+  ty += b0 * x; ty += b1 * y; ty += b2 * 1.0;
+  cx = tx; cy = ty;
+}
 
 // wave reductions for the arg-max: DPP row shifts inside the 16-lane rows, the four row results through scalar registers
 __device__ __forceinline__ double pdf_wave_max_nonneg(double v)            // v >= 0 in every lane (lanes without a source read 0)
@@ -113,8 +143,7 @@ pdf_argmax_body(const double* __restrict__ prob, const PdfCandidate* __restrict_
       const double msx = ld_pinned(&M[2 * bidx]), msy = ld_pinned(&M[2 * bidx + 1]), ssx = ld_pinned(&S[2 * bci]), ssy = ld_pinned(&S[2 * bci + 1]);
       const double co = cos(bphi), si = sin(bphi);
       r.T[0] = co; r.T[1] = -si; r.T[3] = si; r.T[4] = co;
-      r.T[2] = msx - (co * ssx + (-si) * ssy);
-      r.T[5] = msy - (si * ssx + co * ssy);
+      pdf_candidate_T(msx, msy, ssx, ssy, co, si, r.T[2], r.T[5]);
       r.prob = gp; r.idx = bidx; r.i = bci;
     }
     *out = r;

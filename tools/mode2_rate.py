@@ -5,7 +5,10 @@ lists, staging, and the device's model arrays / scoring / arg-max by HIP events)
 PDFMatching::match (tests/pdfmatch_restate.c, one thread) in ms per match on the same inputs.  --mode 1: the same for
 registration_mode 1 (RandomNormalMatching: tsd_rn_match, TSD_MODE1_TIMING, scoring / selection; tests/rnmatch_restate.c).
 
-    python tools/mode2_rate.py [--mode {1,2}] [--scans N] [--warmup W]
+    python tools/mode2_rate.py [--mode {1,2}] [--scans N] [--warmup W] [--dump DIR]
+
+--dump DIR: every scan's pose and lastPreregistration record as raw float64 rows in DIR/mode<m>.bin (two builds with the same seed are
+compared bytewise) and nothing else: no timing lines, no restatement.
 """
 import argparse
 import math
@@ -28,8 +31,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--seed", type=int, default=4711)
     ap.add_argument("--mode", type=int, choices=(1, 2), default=2)
+    ap.add_argument("--dump", metavar="DIR", default=None)
     a = ap.parse_args()
-    os.environ.setdefault(f"TSD_MODE{a.mode}_TIMING", "1")      # (read once, at the first tsd_pdf_match / tsd_rn_match)
+    if not a.dump:
+        os.environ.setdefault(f"TSD_MODE{a.mode}_TIMING", "1")      # (read once, at the first tsd_pdf_match / tsd_rn_match)
     gc, geo, scene = synth.CONFIGS["cfg2"]
     world = synth.World(scene, gc)
     n = a.warmup + a.scans
@@ -37,6 +42,18 @@ def main():
     params = facade.node_params(gc, geo)
     params.update({"registration_mode": a.mode, "tsdpdf_seed": a.seed})
     node = facade.SlamNode(params, synchronous=True)
+    if a.dump:
+        rows = []
+        for k in range(n):
+            node.laser(scans[k], geo.angle_min, geo.angle_increment)
+            pr = node.preregistration() or dict(T=np.zeros((3, 3)), prob=0.0, idx=0, i=0, candidates=0, valid_model=0, valid_scene=0, control=0)
+            rows.append(np.concatenate([node.report()["pose"].ravel(), pr["T"].ravel(),
+                                        [pr[key] for key in ("prob", "idx", "i", "candidates", "valid_model", "valid_scene", "control")]]))
+        os.makedirs(a.dump, exist_ok=True)
+        np.asarray(rows, dtype=np.float64).tofile(os.path.join(a.dump, f"mode{a.mode}.bin"))
+        print(f"mode {a.mode}: {n} scans dumped to {a.dump}", flush=True)
+        node.close()
+        return
     for k in range(a.warmup):
         node.laser(scans[k], geo.angle_min, geo.angle_increment)
     sys.stderr.flush()
