@@ -417,7 +417,8 @@ int tsd_load_grid_text(tsd_ctx* ctx, const char* path);
 /* Occupancy map of ThreadGrid::eventLoop (ThreadGrid.cpp:72-118) built from
  * RayCastAxisAligned2D::calcCoords (RayCastAxisAligned2D.cpp:13-105): int8 cells*cells,
  * -1 unknown / 0 free / 100 occupied.  The map persists inside the ctx between calls like
- * ThreadGrid::_occGridContent.  The _dev form writes to a device pointer (e.g. a torch tensor that is
+ * ThreadGrid::_occGridContent: -1 at tsd_create, and cleared by nothing afterwards (tsd_reset, tsd_upload_tiles and
+ * tsd_load_grid_text replace the grid, not this map -- TsdGrid::reset does not touch ThreadGrid's copy either).  The _dev form writes to a device pointer (e.g. a torch tensor that is
  * then max-all-reduced over RCCL). */
 int tsd_occupancy(tsd_ctx* ctx, int8_t* occ_host, int inflate, int inflate_factor, int* n_surface);
 int tsd_occupancy_dev(tsd_ctx* ctx, void* occ_dev, int inflate, int inflate_factor);

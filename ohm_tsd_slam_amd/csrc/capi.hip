@@ -428,6 +428,9 @@ tsd_ctx* tsd_create(int device, int map_size_log2, double cell_size, double max_
   ctx->h_out_bytes = (size_t)TSD_MAX_BEAMS * (8 * 4 + 1) + 256;
   A(hipHostMalloc(&ctx->h_out, ctx->h_out_bytes, hipHostMallocDefault));
   A(hipMalloc(&ctx->d_occ, (size_t)g.N * g.N));
+  // -1 once, like ThreadGrid's constructor (ThreadGrid.cpp:27-28).  Nothing clears the persistent map afterwards: ThreadGrid never
+  // does, and TsdGrid::reset (tsd_reset below) does not reach into it.
+  if (ok) A(hipMemsetAsync(ctx->d_occ, 0xFF, (size_t)g.N * g.N, ctx->stream));
   A(hipMalloc(&ctx->d_occ_count, sizeof(int)));
   A(hipMalloc(&ctx->d_occ_heads, occ_heads_bytes()));
   A(hipMemsetAsync(ctx->d_occ_heads, 0, occ_heads_bytes(), ctx->stream));
@@ -519,7 +522,6 @@ int tsd_reset(tsd_ctx* ctx)
   TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_pushes, 0, 2 * sizeof(unsigned long long), ctx->stream));
   ctx->box_prev = TileBox{}; ctx->box_dirty = TileBox{};
   TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_list_cnt, 0, push_list_cnt_bytes(), ctx->stream));
-  TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_occ, 0xFF, (size_t)g.N * g.N, ctx->stream));   // -1 (ThreadGrid.cpp:27-28)
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return TSD_OK;
 }
