@@ -446,6 +446,49 @@ int tsd_map_frame_wait(tsd_ctx* ctx, int* n_surface);
 void* tsd_host_alloc(uint64_t bytes);
 void tsd_host_free(void* p);
 
+/* ---- same-device merge group: N grids of one process on ONE GPU, one merged occupancy map ------------------ */
+/* The one-GPU counterpart of include/tsd_comm.h (whose RCCL all-reduce needs one GPU per rank): n contexts of this process on one
+ * device, member i shifted by (cell_off_xy[2i], cell_off_xy[2i+1]) whole cells, merged by a local kernel into a width x height window.
+ * Member i's cell (x, y) lands in cell (x + ox_i, y + oy_i) of the offsets' frame; a merged cell is the SIGNED int8 maximum over the
+ * members that cover it (what ncclMax gives: occupied 100 > free 0 > unknown -1, and any other int8 value in its signed order), -1 where
+ * no member covers it; what falls outside the window is clipped.  width = height = 0: the window is the members' bounding box, and its
+ * corner (tsd_group_corner) is (min ox, min oy); an explicit window has its corner at (0, 0).  The members must be distinct contexts
+ * on one device with bit-equal cell sizes (their map sizes may differ), 1 <= n <= 64; anything else is refused before the first HIP
+ * call: tsd_group_create returns NULL with a message on stderr, the calls below return TSD_E_ARG.  Part of libtsd_hip.so: no RCCL.
+ *
+ * Nothing waits on the host before tsd_group_merge_wait.  tsd_group_merge_begin enqueues every member's extraction
+ * (tsd_occupancy_dev_async, into the group's buffer for that member) on that member's own stream; the group's own stream waits for
+ * them through events, runs the merge kernel and the copy to merged_host (width * height bytes, row = y; page-locked memory from
+ * tsd_host_alloc keeps the call from blocking; NULL: no copy).  A member's next extraction waits on the device for the merge that
+ * still reads its buffer.  One merge at a time per group: call tsd_group_merge_wait before the next begin if merged_host is reused.
+ * A caller that serialises each context with a lock of its own (the C++ facade) enqueues the members one by one with
+ * tsd_group_extract_begin, holding only that member's lock, and then calls tsd_group_merge_maps_begin(g, NULL, host).
+ * The contexts must outlive the group. */
+typedef struct tsd_group tsd_group;
+tsd_group*  tsd_group_create(int n, tsd_ctx* const* ctxs, const int32_t* cell_off_xy /* 2n, NULL = all 0 */,
+                             int width, int height /* 0, 0 = bounding box of the members */);
+void        tsd_group_destroy(tsd_group* g);
+int         tsd_group_size(const tsd_group* g);
+int         tsd_group_width(const tsd_group* g);
+int         tsd_group_height(const tsd_group* g);
+int         tsd_group_corner(const tsd_group* g, int32_t* x0, int32_t* y0);   /* the window's corner in the offsets' frame */
+const char* tsd_group_last_error(const tsd_group* g);
+int   tsd_group_merge_begin(tsd_group* g, const tsd_map_params* params, int8_t* merged_host);
+/* member i's extraction alone (ordered on its context's stream), for tsd_group_merge_maps_begin(g, NULL, ...) */
+int   tsd_group_extract_begin(tsd_group* g, int i, const tsd_map_params* params);
+/* the merge of maps the caller wrote: member_maps_dev[i] is member i's map on the device (cells_i * cells_i int8, row = y, 16-byte
+ * aligned, complete before the call), NULL = the group's own buffers (tsd_group_member_map_dev; extractions begun on them are waited for) */
+int   tsd_group_merge_maps_begin(tsd_group* g, const void* const* member_maps_dev, int8_t* merged_host);
+/* copy a host map (cells_i * cells_i bytes) into the group's buffer of member i, on the group's stream ahead of the next merge */
+int   tsd_group_member_map_upload(tsd_group* g, int i, const int8_t* map_host);
+int   tsd_group_merge_wait(tsd_group* g, int* n_occupied /* cells equal to 100 in the merged map; may be NULL */);
+void* tsd_group_map_dev(tsd_group* g);          /* merged map, width * height int8, row = y */
+void* tsd_group_member_map_dev(tsd_group* g, int i);
+/* what a merge costs, measured with HIP events when switched on: the members' extractions (summed over members) and the merge
+ * kernel; tsd_group_merge_times waits for the merges issued so far and returns the running totals since tsd_group_create */
+int   tsd_group_profile(tsd_group* g, int on);
+int   tsd_group_merge_times(tsd_group* g, double* extract_ms_total, double* merge_ms_total, int* merges);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the ctx stream.  Kernel names: "push_classify", "push_update",
  * "push_halo", "raycast", "icp", "occupancy", "tsdpdf". */

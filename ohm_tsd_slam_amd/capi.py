@@ -237,6 +237,22 @@ ABI = {
     "tsd_occupancy": (C.c_int, [C.c_void_p, _i8p, C.c_int, C.c_int, _ip]),
     "tsd_occupancy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "tsd_occupancy_dev_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "tsd_group_create": (C.c_void_p, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int]),
+    "tsd_group_destroy": (None, [C.c_void_p]),
+    "tsd_group_size": (C.c_int, [C.c_void_p]),
+    "tsd_group_width": (C.c_int, [C.c_void_p]),
+    "tsd_group_height": (C.c_int, [C.c_void_p]),
+    "tsd_group_corner": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tsd_group_last_error": (C.c_char_p, [C.c_void_p]),
+    "tsd_group_merge_begin": (C.c_int, [C.c_void_p, C.POINTER(MapParams), C.c_void_p]),
+    "tsd_group_extract_begin": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(MapParams)]),
+    "tsd_group_merge_maps_begin": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "tsd_group_member_map_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "tsd_group_merge_wait": (C.c_int, [C.c_void_p, _ip]),
+    "tsd_group_map_dev": (C.c_void_p, [C.c_void_p]),
+    "tsd_group_member_map_dev": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "tsd_group_profile": (C.c_int, [C.c_void_p, C.c_int]),
+    "tsd_group_merge_times": (C.c_int, [C.c_void_p, _dp, _dp, _ip]),
     "tsd_icp_pairs": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, C.c_int, _dp, C.POINTER(IcpParams), C.c_int, _ip, _ip, _ip]),
     "tsd_calibrate_rmw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
     "tsd_measure_stream": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),

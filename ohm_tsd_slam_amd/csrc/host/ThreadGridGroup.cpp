@@ -1,0 +1,163 @@
+#include "ThreadGridGroup.h"
+
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <stdexcept>
+
+namespace ohm_tsd_slam
+{
+
+bool ThreadGridGroup::cellOffset(double origin, double originRef, double cellSize, int32_t* cells)
+{
+  const double d = (origin - originRef) / cellSize;
+  const double r = std::round(d);
+  if(!(std::fabs(d - r) <= 1e-6) || std::fabs(r) > 16777216.0)
+    return false;
+  *cells = static_cast<int32_t>(r);
+  return true;
+}
+
+static double mapOrigin(obvious::TsdGrid* grid, unsigned int cells, double offset)
+{
+  // (ThreadGrid.cpp:28-29)
+  return -(static_cast<double>(cells) * static_cast<double>(grid->getCellSize()) * 0.5 + offset);
+}
+
+ThreadGridGroup::ThreadGridGroup(const std::shared_ptr<rclcpp::Node>& node, const std::vector<Member>& members):
+    ThreadSLAM(*members.at(0).grid),
+    _node(node),
+    _members(members),
+    _group(nullptr),
+    _occGrid(std::make_shared<nav_msgs::msg::OccupancyGrid>()),
+    _width(0),
+    _height(0),
+    _hOcc(nullptr),
+    _frames(0)
+{
+  const double cs = static_cast<double>(_grid.getCellSize());
+  // the merged window's origin is the smallest origin along each axis; every grid lies a whole number of cells from grid 0
+  std::vector<int32_t> off(2 * _members.size());
+  std::vector<tsd_ctx*> ctxs(_members.size());
+  const double ox0 = mapOrigin(_members[0].grid, _members[0].grid->getCellsX(), _members[0].xOffset);
+  const double oy0 = mapOrigin(_members[0].grid, _members[0].grid->getCellsY(), _members[0].yOffset);
+  double originX = ox0, originY = oy0;
+  for(size_t i = 0; i < _members.size(); i++)
+  {
+    obvious::TsdGrid* g = _members[i].grid;
+    ctxs[i] = g->context();
+    const double ox = mapOrigin(g, g->getCellsX(), _members[i].xOffset), oy = mapOrigin(g, g->getCellsY(), _members[i].yOffset);
+    if(!cellOffset(ox, ox0, cs, &off[2 * i]) || !cellOffset(oy, oy0, cs, &off[2 * i + 1]))
+    {
+      char text[256];
+      std::snprintf(text, sizeof(text), "ThreadGridGroup: the map origins of grid 0 (%.9g, %.9g) and grid %zu (%.9g, %.9g) do not differ by "
+                    "whole cells of %.9g m", ox0, oy0, i, ox, oy, cs);
+      throw std::invalid_argument(text);
+    }
+    if(ox < originX) originX = ox;
+    if(oy < originY) originY = oy;
+  }
+  _group = tsd_group_create(static_cast<int>(_members.size()), ctxs.data(), off.data(), 0, 0);
+  if(!_group)
+    throw std::invalid_argument("ThreadGridGroup: the device refused the group (one device, one cell size, at most 64 grids)");
+  _width = static_cast<unsigned int>(tsd_group_width(_group));
+  _height = static_cast<unsigned int>(tsd_group_height(_group));
+
+  _occGrid->info.resolution           = cs;
+  _occGrid->info.width                = _width;
+  _occGrid->info.height               = _height;
+  _occGrid->info.origin.orientation.w = 1.0;
+  _occGrid->info.origin.orientation.x = 0.0;
+  _occGrid->info.origin.orientation.y = 0.0;
+  _occGrid->info.origin.orientation.z = 0.0;
+  _occGrid->info.origin.position.x    = originX;
+  _occGrid->info.origin.position.y    = originY;
+  _occGrid->info.origin.position.z    = 0.0;
+  _occGrid->data.resize((size_t)_width * _height);
+
+  _occGrid->header.frame_id = node->get_parameter("tf_map_frame").as_string();
+  _objectInflation = node->get_parameter("use_object_inflation").as_bool();
+  _objInflateFactor = static_cast<unsigned int>(node->get_parameter("object_inflation_factor").as_int());
+
+  const std::string node_name = _node->get_name();
+  _gridPub = node->create_publisher<nav_msgs::msg::OccupancyGrid>(node_name + "/merged_map", rclcpp::QoS(1).reliable().transient_local());
+  _getMapServ = node->create_service<nav_msgs::srv::GetMap>(
+    node_name + "/get_merged_map",
+    std::bind(&ThreadGridGroup::getMapServCallBack, this, std::placeholders::_1, std::placeholders::_2));
+  startThread();
+}
+
+ThreadGridGroup::~ThreadGridGroup()
+{
+  terminateThread();
+  joinThread();
+  tsd_group_destroy(_group);
+  tsd_host_free(_hOcc);
+}
+
+uint64_t ThreadGridGroup::frames(void)
+{
+  std::lock_guard<std::mutex> lk(_msgMutex);
+  return _frames;
+}
+
+void ThreadGridGroup::eventLoop(void)
+{
+  while(_stayActive)
+  {
+    waitForWork();
+    if(!_stayActive)
+      break;
+    publish();
+  }
+}
+
+int ThreadGridGroup::publish(void)
+{
+  std::lock_guard<std::mutex> lk(_publishMutex);
+  const size_t cells = (size_t)_width * _height;
+  if(!_hOcc)
+    _hOcc = static_cast<int8_t*>(tsd_host_alloc(cells));
+  if(!_hOcc)
+    return TSD_E_ARG;
+  tsd_map_params prm;
+  prm.inflate = _objectInflation ? 1 : 0;
+  prm.inflate_factor = static_cast<int32_t>(_objInflateFactor);
+  for(size_t i = 0; i < _members.size(); i++)
+  {
+    // one grid's mutex at a time, and only while that grid's extraction is enqueued: the localisers go on while the maps are merged
+    std::lock_guard<std::mutex> g(_members[i].grid->mutex());
+    const int rc = tsd_group_extract_begin(_group, static_cast<int>(i), &prm);
+    if(rc != TSD_OK)
+      return rc;
+  }
+  int rc = tsd_group_merge_maps_begin(_group, nullptr, _hOcc);
+  if(rc != TSD_OK)
+    return rc;
+  rc = tsd_group_merge_wait(_group, nullptr);
+  if(rc != TSD_OK)
+    return rc;
+  nav_msgs::msg::OccupancyGrid msg;
+  {
+    std::lock_guard<std::mutex> m(_msgMutex);
+    _occGrid->header.stamp       = _node->get_clock()->now();
+    _occGrid->info.map_load_time = _node->get_clock()->now();
+    std::memcpy(_occGrid->data.data(), _hOcc, cells);
+    msg = *_occGrid;
+    _frames++;
+  }
+  _gridPub->publish(msg);
+  return TSD_OK;
+}
+
+bool ThreadGridGroup::getMapServCallBack(const std::shared_ptr<nav_msgs::srv::GetMap::Request>,
+                                         std::shared_ptr<nav_msgs::srv::GetMap::Response> res)
+{
+  std::lock_guard<std::mutex> m(_msgMutex);
+  res->map = *_occGrid;
+  res->map.header.stamp = _node->get_clock()->now();
+  _occGrid->info.map_load_time = _node->get_clock()->now();
+  return true;
+}
+
+} /* namespace ohm_tsd_slam */

@@ -1,0 +1,66 @@
+// ThreadGridGroup.h -- the merged-map worker of several grids on ONE GPU (not in the reference, whose robots share one TsdGrid): every
+// wake-up extracts each grid's occupancy map on that grid's own stream, merges them on the device (tsd_group_*: the signed maximum,
+// each grid shifted by the whole-cell difference of the map origins) and publishes one nav_msgs/OccupancyGrid on <node>/merged_map;
+// <node>/get_merged_map answers with the last one.  Across GPUs the merge is include/tsd_comm.h's; this one never maps RCCL.
+#pragma once
+#include <cstdint>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "ThreadSLAM.h"
+#include "ros_shim.h"
+
+namespace ohm_tsd_slam
+{
+
+class ThreadGridGroup : public ThreadSLAM
+{
+public:
+  struct Member
+  {
+    obvious::TsdGrid* grid;
+    double xOffset;       // the grid's x_offset / y_offset: its map origin is -(W / 2 + offset) (ThreadGrid.cpp:28-29)
+    double yOffset;
+  };
+
+  /** whole-cell offset of a map at `origin` relative to one at `originRef`; false unless within 1e-6 cells of an integer */
+  static bool cellOffset(double origin, double originRef, double cellSize, int32_t* cells);
+
+  /** throws std::invalid_argument when two grids' origins do not differ by whole cells (the message names them) or the device
+   *  refuses the group */
+  ThreadGridGroup(const std::shared_ptr<rclcpp::Node>& node, const std::vector<Member>& members);
+  virtual ~ThreadGridGroup();
+
+  /** one merge and publication on the caller's thread, what every wake-up of the event loop does.  TSD_OK or the error code. */
+  int publish(void);
+  /** merged maps published so far */
+  uint64_t frames(void);
+
+  std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }
+  std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> mapService() { return _getMapServ; }
+  bool getMapServCallBack(const std::shared_ptr<nav_msgs::srv::GetMap::Request> req,
+                          std::shared_ptr<nav_msgs::srv::GetMap::Response> res);
+
+protected:
+  virtual void eventLoop(void);
+
+private:
+  std::shared_ptr<rclcpp::Node> _node;
+  std::vector<Member> _members;
+  tsd_group* _group;
+  std::shared_ptr<nav_msgs::msg::OccupancyGrid> _occGrid;
+  std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> _getMapServ;
+  std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> _gridPub;
+  unsigned int _width;
+  unsigned int _height;
+  unsigned int _objInflateFactor;
+  bool _objectInflation;
+  int8_t* _hOcc;                 // page-locked landing buffer of the merged map
+  std::mutex _publishMutex;      // one merge at a time (event loop, publish())
+  std::mutex _msgMutex;          // _occGrid between a publication and the get_merged_map service
+  uint64_t _frames;
+};
+
+} /* namespace ohm_tsd_slam */

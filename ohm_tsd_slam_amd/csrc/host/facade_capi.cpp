@@ -13,10 +13,20 @@
 #include <vector>
 
 #include "ThreadGrid.h"
+#include "ThreadGridGroup.h"
 #include "ThreadLocalize.h"
 #include "ThreadMapping.h"
 
 using namespace ohm_tsd_slam;
+
+struct tsd_node;
+
+// several nodes' grids on one GPU and the worker that merges and publishes their maps (ThreadGridGroup); the nodes outlive it
+struct tsd_fleet
+{
+  std::vector<tsd_node*> nodes;
+  ThreadGridGroup* group = nullptr;
+};
 
 struct tsd_node
 {
@@ -401,6 +411,75 @@ unsigned long long tsd_node_map_image_msg(tsd_node* n, uint8_t* data_out, double
   if(text && cap > 0)
     std::snprintf(text, (size_t)cap, "%s|%s", m.encoding.c_str(), m.header.frame_id.c_str());
   return pub->count();
+}
+
+// ---- fleet: the merged map of several nodes' grids on one GPU (ThreadGridGroup) ----------------
+// The first node publishes (<node>/merged_map, <node>/get_merged_map; its inflation parameters apply); every node's x_offset /
+// y_offset places its grid.  NULL when the group is refused, with the reason in err.
+tsd_fleet* tsd_fleet_create(int n, tsd_node* const* nodes, char* err, int cap)
+{
+  auto refuse = [&](const char* what) -> tsd_fleet* {
+    if(err && cap > 0) std::snprintf(err, (size_t)cap, "%s", what);
+    return nullptr;
+  };
+  if(n < 1 || !nodes)
+    return refuse("tsd_fleet_create: no nodes");
+  std::vector<ThreadGridGroup::Member> members;
+  for(int i = 0; i < n; i++)
+  {
+    if(!nodes[i] || !nodes[i]->grid || !nodes[i]->grid->valid())
+      return refuse("tsd_fleet_create: a node is not initialised");
+    members.push_back({nodes[i]->grid, nodes[i]->node->get_parameter("x_offset").as_double(),
+                       nodes[i]->node->get_parameter("y_offset").as_double()});
+  }
+  tsd_fleet* f = new tsd_fleet();
+  f->nodes.assign(nodes, nodes + n);
+  try
+  {
+    f->group = new ThreadGridGroup(nodes[0]->node, members);
+  }
+  catch(const std::exception& e)
+  {
+    delete f;
+    return refuse(e.what());
+  }
+  return f;
+}
+
+void tsd_fleet_destroy(tsd_fleet* f)
+{
+  if(!f)
+    return;
+  if(f->group)
+  {
+    f->group->terminateThread();
+    while(!f->group->alive(1)) {}
+    delete f->group;
+  }
+  delete f;
+}
+
+// one merge and publication now, on the caller's thread (what a wake-up of the worker does); TSD_OK or the error
+int tsd_fleet_publish_merged(tsd_fleet* f) { return (f && f->group) ? f->group->publish() : TSD_E_ARG; }
+unsigned long long tsd_fleet_merged_frames(tsd_fleet* f) { return (f && f->group) ? f->group->frames() : 0; }
+
+// last message on <node>/merged_map (map_out layout); returns the publish count
+unsigned long long tsd_fleet_merged_map_msg(tsd_fleet* f, int8_t* data_out, double* out12, char* frame_id, int cap)
+{
+  auto pub = f->group->gridPublisher();
+  map_out(pub->last(), data_out, out12, frame_id, cap);
+  return pub->count();
+}
+
+// <node>/get_merged_map: the last merged map with a fresh stamp (map_out layout); 1 if the service answered
+int tsd_fleet_get_merged_map(tsd_fleet* f, int8_t* data_out, double* out12, char* frame_id, int cap)
+{
+  auto req = std::make_shared<nav_msgs::srv::GetMap::Request>();
+  auto res = std::make_shared<nav_msgs::srv::GetMap::Response>();
+  if(!f->group->getMapServCallBack(req, res))
+    return 0;
+  map_out(res->map, data_out, out12, frame_id, cap);
+  return 1;
 }
 
 tsd_ctx* tsd_node_grid_ctx(tsd_node* n) { return n->grid ? n->grid->context() : nullptr; }

@@ -49,6 +49,12 @@ HOST_ABI = {
     "tsd_node_grid_lock": (None, [C.c_void_p]),
     "tsd_node_grid_unlock": (None, [C.c_void_p]),
     "tsd_node_destroy": (None, [C.c_void_p]),
+    "tsd_fleet_create": (C.c_void_p, [C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
+    "tsd_fleet_destroy": (None, [C.c_void_p]),
+    "tsd_fleet_publish_merged": (C.c_int, [C.c_void_p]),
+    "tsd_fleet_merged_frames": (C.c_ulonglong, [C.c_void_p]),
+    "tsd_fleet_merged_map_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
+    "tsd_fleet_get_merged_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_host_sensor_ingest_f32": (None, [_fp, C.c_int, C.c_double, C.c_double, C.c_double, _dp, _u8p, C.c_int]),
     "tsd_host_sensor_chain": (None, [C.c_int, C.c_double, C.c_double, _dp, _dp, C.c_double, _fp, _dp, _dp, _dp,
                                      _dp, _u8p, _ip]),
@@ -238,7 +244,8 @@ class SlamNode:
         """ThreadGrid publications so far (timer wake-ups and publish_map())"""
         return int(self.lib.tsd_node_map_frames(self.h))
 
-    def _map_dict(self, fn):
+    @staticmethod
+    def _map_dict(fn):
         info = np.zeros(12)
         frame = C.create_string_buffer(256)
         fn(None, info.ctypes.data_as(_dp), frame, 256)
@@ -276,6 +283,54 @@ class SlamNode:
 
     def grid(self) -> "GridView":
         return GridView(self.lib.tsd_node_grid_ctx(self.h), self)
+
+
+class SlamFleet:
+    """Several :class:`SlamNode` s on ONE GPU, each with its own grid, and their merged map (``ThreadGridGroup``): every node's
+    ``x_offset`` / ``y_offset`` places its grid, offsets that do not differ by whole cells are refused.  The first node publishes
+    ``<node>/merged_map`` and answers ``<node>/get_merged_map``.  Close the fleet before its nodes."""
+
+    def __init__(self, nodes):
+        self.lib = load_library()
+        self.nodes = list(nodes)
+        hs = (C.c_void_p * max(len(self.nodes), 1))(*[n.h for n in self.nodes])
+        err = C.create_string_buffer(512)
+        self.h = self.lib.tsd_fleet_create(len(self.nodes), hs, err, 512)
+        if not self.h:
+            raise capi.TsdError(f"tsd_fleet_create refused: {err.value.decode()}")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tsd_fleet_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def publish_merged_map(self) -> dict:
+        """one merge and publication now, on the caller's thread; the published message (as ``merged_map_msg``)"""
+        rc = self.lib.tsd_fleet_publish_merged(self.h)
+        if rc != 0:
+            raise capi.TsdError(f"tsd_fleet_publish_merged failed ({rc})")
+        return self.merged_map_msg()
+
+    def merged_frames(self) -> int:
+        return int(self.lib.tsd_fleet_merged_frames(self.h))
+
+    def merged_map_msg(self) -> dict:
+        """the last nav_msgs/OccupancyGrid on <node>/merged_map (data as (height, width) int8) and its publish count"""
+        n, m = SlamNode._map_dict(lambda d, i, f, c: self.lib.tsd_fleet_merged_map_msg(self.h, d, i, f, c))
+        m["count"] = int(n)
+        return m
+
+    def get_merged_map(self) -> dict:
+        ok, m = SlamNode._map_dict(lambda d, i, f, c: self.lib.tsd_fleet_get_merged_map(self.h, d, i, f, c))
+        if not ok:
+            raise capi.TsdError("get_merged_map refused")
+        return m
 
 
 class GridView(capi.TsdGridDevice):

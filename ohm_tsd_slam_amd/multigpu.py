@@ -128,6 +128,116 @@ class NativeOccupancyMerger:
         return out.reshape(self.cells, self.cells)
 
 
+def cell_offset_from_origins(origin: float, origin_ref: float, cell_size: float, what: str = "origins") -> int:
+    """Whole-cell offset of a grid whose map origin (``-(W / 2 + offset)``, ThreadGrid.cpp:28-29) is ``origin`` relative to one at
+    ``origin_ref``.  A difference that is not within 1e-6 cells of an integer is refused: the merge shifts by whole cells."""
+    d = (float(origin) - float(origin_ref)) / float(cell_size)
+    r = round(d)
+    if abs(d - r) > 1e-6:
+        raise ValueError(f"{what}: the map origins differ by {d!r} cells, which is no whole number of cells")
+    return int(r)
+
+
+class LocalOccupancyGroup:
+    """The same-device merge group (``tsd_group_*``, in ``lib/libtsd_hip.so``: no RCCL): N grids of this process on ONE GPU, grid i
+    shifted by ``cell_offsets[i] = (ox, oy)`` whole cells, merged by a local kernel into one int8 map -- the signed maximum
+    :class:`NativeOccupancyMerger` gets from ``ncclAllReduce`` across GPUs.  ``width = height = 0``: the window is the members'
+    bounding box (``corner`` is its corner in the offsets' frame).  ``merge_async`` / ``merge_maps_async`` only enqueue; ``wait``
+    synchronises.  This is co-residency on one chip, never a scaling curve."""
+
+    def __init__(self, grids, cell_offsets=None, width: int = 0, height: int = 0):
+        self.lib = capi.load_library()
+        self.grids = list(grids)
+        n = len(self.grids)
+        hs = (C.c_void_p * max(n, 1))(*[g.h for g in self.grids])
+        offs = None
+        if cell_offsets is not None:
+            flat = [int(v) for xy in cell_offsets for v in xy]
+            if len(flat) != 2 * n:
+                raise capi.TsdError("cell_offsets: one (ox, oy) per grid")
+            offs = (C.c_int32 * max(2 * n, 1))(*flat)
+        self.h = self.lib.tsd_group_create(n, hs, offs, int(width), int(height))
+        if not self.h:
+            raise capi.TsdError("tsd_group_create refused the group (see stderr)")
+        self.width, self.height = self.lib.tsd_group_width(self.h), self.lib.tsd_group_height(self.h)
+        x0, y0 = C.c_int32(0), C.c_int32(0)
+        self.lib.tsd_group_corner(self.h, C.byref(x0), C.byref(y0))
+        self.corner = (x0.value, y0.value)
+        self._host = self.lib.tsd_host_alloc(self.width * self.height)
+        if not self._host:
+            self.close()
+            raise capi.TsdError("tsd_host_alloc failed")
+        self._n_occupied = 0
+        self._keep = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tsd_group_destroy(self.h)
+            self.h = None
+        if getattr(self, "_host", None):
+            self.lib.tsd_host_free(self._host)
+            self._host = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise capi.TsdError(f"{what} failed ({rc}): {self.lib.tsd_group_last_error(self.h).decode()}")
+
+    def merge_async(self, inflate: bool = False, inflate_factor: int = 2):
+        """every member's extraction on its own stream, the merge and the copy to the host behind them; nothing waits"""
+        prm = capi.MapParams(int(bool(inflate)), int(inflate_factor))
+        self._check(self.lib.tsd_group_merge_begin(self.h, C.byref(prm), self._host), "tsd_group_merge_begin")
+
+    def merge_maps_async(self, maps):
+        """the merge of given maps: per member a (cells, cells) int8 array (copied into the group's buffer) or a device address"""
+        assert len(maps) == len(self.grids)
+        ptrs, keep = [], []
+        for i, (m, g) in enumerate(zip(maps, self.grids)):
+            if isinstance(m, int):
+                ptrs.append(m)
+                continue
+            a = np.ascontiguousarray(m, dtype=np.int8)
+            assert a.size == g.cells * g.cells, f"member {i}: {a.size} bytes for a {g.cells}^2 grid"
+            keep.append(a)
+            self._check(self.lib.tsd_group_member_map_upload(self.h, i, a.ctypes.data), "tsd_group_member_map_upload")
+            ptrs.append(self.lib.tsd_group_member_map_dev(self.h, i))
+        self._keep = keep               # (the copies are asynchronous: the arrays live until wait())
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+        self._check(self.lib.tsd_group_merge_maps_begin(self.h, arr, self._host), "tsd_group_merge_maps_begin")
+
+    def wait(self) -> int:
+        n = C.c_int(0)
+        self._check(self.lib.tsd_group_merge_wait(self.h, C.byref(n)), "tsd_group_merge_wait")
+        self._keep = None
+        self._n_occupied = n.value
+        return n.value
+
+    @property
+    def n_occupied(self) -> int:
+        """cells equal to 100 in the merged map of the last ``wait`` (counted by the merge kernel)"""
+        return self._n_occupied
+
+    def merged(self) -> np.ndarray:
+        """waits; the merged map as (height, width) int8, row = y"""
+        self.wait()
+        buf = np.ctypeslib.as_array(C.cast(self._host, C.POINTER(C.c_int8)), shape=(self.height * self.width,))
+        return buf.reshape(self.height, self.width).copy()
+
+    def profile(self, on: bool = True):
+        self._check(self.lib.tsd_group_profile(self.h, int(on)), "tsd_group_profile")
+
+    def merge_times(self):
+        """(extraction ms summed over members, merge kernel ms, merges timed): totals while ``profile`` was on"""
+        a, b, n = C.c_double(), C.c_double(), C.c_int()
+        self._check(self.lib.tsd_group_merge_times(self.h, C.byref(a), C.byref(b), C.byref(n)), "tsd_group_merge_times")
+        return a.value, b.value, n.value
+
+
 def env_rank():
     """(rank, local_rank, world_size) as ``torch.distributed.run`` exports them."""
     return (int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0")),
