@@ -16,8 +16,6 @@
 
 namespace tsd {
 
-thread_local const LaunchTarget* g_launch_target = nullptr;
-
 int set_error(tsd_ctx* ctx, int code, const char* what, hipError_t e)
 {
   if (ctx) {
@@ -175,11 +173,9 @@ ScanPostArgs sensor_post_args(const tsd_sensor* s, unsigned long long seq, const
   sp.gates = GateArgs{gates.reg_trs_max, gates.reg_sin_rot_max, gates.trs_min, gates.rot_min};
   return sp;
 }
-PushArgs sensor_push_launch_args(const tsd_sensor* s)
+PushJob sensor_push_job(const tsd_sensor* s, const ScanView& scan, char* rmq, const tsd_gate_params& gates)
 {
-  PushArgs pa; std::memset(&pa, 0, sizeof(pa));
-  pa.beams = s->beams; pa.max_range = s->max_range;
-  return pa;
+  return PushJob{&s->d_state->push, scan.ranges, scan.mask_push, rmq, s->pos[0], s->pos[1], gates.reg_trs_max, s->beams, s->max_range};
 }
 RaycastArgs sensor_raycast_launch_args(const tsd_sensor* s)
 {
@@ -380,7 +376,6 @@ tsd_ctx* tsd_create(int device, int map_size_log2, double cell_size, double max_
   A(hipMalloc(&g.negmask, T * sizeof(unsigned long long)));
   A(hipMalloc(&ctx->d_rmq2[0], push_rmq_bytes(TSD_MAX_BEAMS)));
   A(hipMalloc(&ctx->d_rmq2[1], push_rmq_bytes(TSD_MAX_BEAMS)));
-  ctx->d_rmq = ctx->d_rmq2[0];
   A(hipEventCreateWithFlags(&ctx->ev_h2d, hipEventDisableTiming));
   A(hipMalloc(&ctx->d_tile_rec, T * sizeof(uint32_t)));
   A(hipMalloc(&ctx->d_dirty, T));
@@ -579,6 +574,14 @@ int tsd_free_footprint(tsd_ctx* ctx, const double center[2], double width, doubl
   return launch_free_footprint(ctx, minX, cx1, minY, cy1);
 }
 
+// The tables of an unfused push go into the context's two buffers in turn: the push that may still be running keeps its own.
+static char* next_ctx_tables(tsd_ctx* ctx)
+{
+  std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
+  ctx->rmq_slot ^= 1;
+  return ctx->d_rmq2[ctx->rmq_slot];
+}
+
 int tsd_push(tsd_ctx* ctx, const double pose33[9], const double* ranges, const uint8_t* mask,
              int beams, double ang_res, double phi_min, double max_range, double min_range,
              double low_refl_range, tsd_push_stats* stats)
@@ -612,9 +615,10 @@ int tsd_push(tsd_ctx* ctx, const double pose33[9], const double* ranges, const u
   std::lock_guard<std::mutex> lk_order(ctx->order_mutex);
   int rc = wait_for_readers(ctx);
   if (rc != TSD_OK) return rc;
-  rc = launch_push_tables(ctx, ctx->stream, beams, nullptr, nullptr, phi_min, ang_res);
+  const PushJob job{ctx->d_push_args, ctx->d_ranges, ctx->d_mask, next_ctx_tables(ctx), a.trx, a.try_, 0.0, beams, max_range};
+  rc = launch_push_tables(ctx, ctx->stream, beams, job.ranges, job.mask, job.rmq, phi_min, ang_res);
   if (rc != TSD_OK) return rc;
-  rc = launch_push(ctx, a, a.trx, a.try_, 0.0, ctx->d_push_args);
+  rc = launch_push(ctx, ctx->stream, job);
   if (rc != TSD_OK) return rc;
   if (stats) {
     rc = read_last_push_stats(ctx, stats);
@@ -639,7 +643,7 @@ int tsd_raycast(tsd_ctx* ctx, const double pose33[9], const double* rays_world_2
   std::memcpy(h, rays_world_2xB, (size_t)beams * 2 * sizeof(double));
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_rays, h, (size_t)beams * 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   TSD_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[s], ctx->stream));
-  int rc = launch_raycast(ctx, a);
+  int rc = launch_raycast(ctx, ctx_target(ctx), a, nullptr, ctx->d_rays);
   if (rc != TSD_OK) return rc;
   const size_t nb = (size_t)beams;
   char* o = ctx->h_out;
@@ -737,7 +741,7 @@ int tsd_icp_normals(tsd_ctx* ctx, const double* model_xy, const double* model_no
   std::vector<int> order;
   int rc = stage_icp_inputs(ctx, a, model_xy, model_normals_xy, n_model, scene_xy, n_scene, params->estimator == TSD_ESTIMATOR_POINT_TO_LINE, order);
   if (rc != TSD_OK) return rc;
-  rc = launch_icp(ctx, a);
+  rc = launch_icp(ctx, ctx_target(ctx), a, nullptr, ctx->d_rays_local, ctx->d_ranges, ctx->d_mask);
   if (rc != TSD_OK) return rc;
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_icp_res, ctx->d_icp_res, sizeof(IcpResultDev), hipMemcpyDeviceToHost, ctx->stream));
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -824,14 +828,14 @@ int tsd_localize(tsd_ctx* ctx, const double pose33[9], const double* rays_world_
 
   RaycastArgs ra;
   fill_raycast_args(ctx, ra, pose33, beams, min_range, max_range);
-  int rc = launch_raycast(ctx, ra);
+  int rc = launch_raycast(ctx, ctx_target(ctx), ra, nullptr, ctx->d_rays);
   if (rc != TSD_OK) return rc;
   IcpArgs ia;
   fill_icp_args(ia, pose33, params);
   ia.beams = beams;
   // beam order is counter-clockwise when consecutive local rays turn left (positive angle increment)
   ia.ccw = (beams < 2) || (rays_local_2xB[0] * rays_local_2xB[nb + 1] - rays_local_2xB[nb] * rays_local_2xB[1] >= 0.0);
-  rc = launch_icp(ctx, ia);
+  rc = launch_icp(ctx, ctx_target(ctx), ia, nullptr, ctx->d_rays_local, ctx->d_ranges, ctx->d_mask);
   if (rc != TSD_OK) return rc;
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_icp_res, ctx->d_icp_res, sizeof(IcpResultDev), hipMemcpyDeviceToHost, ctx->stream));
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));

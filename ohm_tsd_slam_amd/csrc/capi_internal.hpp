@@ -62,9 +62,11 @@ struct Lap {
 // What a scan's kernels are given, derived from its sensor (zeroed first: the bytes that reach the device are defined ones).
 // sensor_post_args leaves push_copy / publish_done, which are what differs between the scan paths, to the caller; the launch-sizing
 // arguments carry what a launcher needs on the host (the rest is read on the device, from the sensor's state).
+// sensor_push_job: the push of a scan of `s` that lies in `scan` and whose tables are in `rmq` -- every scan path's.  The host assumes
+// the sensor where it last saw it (s->pos); the registration moves it by at most the gate (a larger step is rejected: pose unchanged).
 IcpArgs sensor_icp_args(const tsd_sensor* s, const tsd_icp_params* p);
 ScanPostArgs sensor_post_args(const tsd_sensor* s, unsigned long long seq, const tsd_gate_params& gates);
-PushArgs sensor_push_launch_args(const tsd_sensor* s);          // beams: LDS size of the launch; max_range: its tile window
+PushJob sensor_push_job(const tsd_sensor* s, const ScanView& scan, char* rmq, const tsd_gate_params& gates);
 RaycastArgs sensor_raycast_launch_args(const tsd_sensor* s);    // beams: grid size of the launch
 
 }  // namespace tsd

@@ -319,10 +319,7 @@ static int scan_stage_device(tsd_sensor* s)
     TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_h2d, ctx->stream2));
     lap.lap(3);
   }
-  LaunchTarget tg;
-  tg.rmq = s->fused.rmq;
-  TargetScope scope(ctx, &tg);
-  int rc = launch_push_tables(ctx, ctx->stream2, s->beams, s->fused.scan.ranges, s->fused.scan.mask_push, s->phi_min, s->ang_res);
+  int rc = launch_push_tables(ctx, ctx->stream2, s->beams, s->fused.scan.ranges, s->fused.scan.mask_push, s->fused.rmq, s->phi_min, s->ang_res);
   if (rc != TSD_OK) return rc;
   TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_tables, ctx->stream2));
   // make sure the side stream's commands are on their way now: with more streams in the process than hardware queues (a
@@ -441,10 +438,11 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
   // The ray cast needs nothing from the scan (its pose arguments were left on the device by the previous
   // registration), so the previous tsd_scan enqueued it right behind its push; it is launched here only if
   // something touched the grid, the sensor or the context's ray-cast outputs since.
+  const LaunchTarget tg = ctx_target(ctx);
   const RaycastArgs ra = sensor_raycast_launch_args(s);
   if (!(s->fused.rc_pending && s->fused.rc_epoch == ctx->epoch)) {
     if (int rcd_ = drain_async_push(ctx)) return rcd_;     // (asynchronous mapping: a push still on the push stream comes first)
-    rc = launch_raycast(ctx, ra, &s->d_state->rc, s->d_rays);
+    rc = launch_raycast(ctx, tg, ra, &s->d_state->rc, s->d_rays);
     if (rc != TSD_OK) return rc;
   }
   s->fused.rc_pending = false;
@@ -463,12 +461,10 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     // pre-registration, registration: still one of the reference's interleavings)
     hipEvent_t before_score = nullptr;
     if (ctx->async_pending) { before_score = ctx->ev_async_push; ctx->async_pending = false; }
-    const LaunchTarget* tgp = launch_target();
     // (the node's registration shape: the arg-max rides with the registration's launch -- TSD_PDF_ARGMAX_KERNEL=1: as a kernel, A/B)
     static const bool argmax_kernel = [] { const char* e = std::getenv("TSD_PDF_ARGMAX_KERNEL"); return e && *e == '1'; }();
     fold_argmax = !argmax_kernel && icp_pre_supported(ctx, ia);
-    rc = launch_preregistration(ctx, s, launch_stream(ctx), tgp && tgp->coords ? tgp->coords : ctx->d_coords,
-                                tgp && tgp->mask_m ? tgp->mask_m : ctx->d_mask_m, s->d_state->icpP, &ia.Tinit_dev, before_score, fold_argmax ? &prel : nullptr);
+    rc = launch_preregistration(ctx, s, tg.stream, tg.coords, tg.mask_m, s->d_state->icpP, &ia.Tinit_dev, before_score, fold_argmax ? &prel : nullptr);
     if (rc != TSD_OK) return rc;
     s->pre.ran = true;
   }
@@ -488,17 +484,17 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     TSD_HIP_CHECK(ctx, hipGetLastError());
   }
   if (icp_from_host) {
-    rc = launch_icp(ctx, ia, s->d_state->icpP, s->d_rays_local, s->fused.h_scan.ranges, s->fused.h_scan.mask, &sp, fold_argmax ? &prel : nullptr);
+    rc = launch_icp(ctx, tg, ia, s->d_state->icpP, s->d_rays_local, s->fused.h_scan.ranges, s->fused.h_scan.mask, &sp, fold_argmax ? &prel : nullptr);
     if (rc != TSD_OK) return rc;
     rc = scan_stage_device(s);
     if (rc != TSD_OK) return rc;
   } else {
     if (!s->scan_bar && !host_saw_event(ctx->ev_h2d, staged_ahead ? 2 : 40)) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_h2d, 0));
-    rc = launch_icp(ctx, ia, s->d_state->icpP, s->d_rays_local, scan.ranges, scan.mask, &sp, fold_argmax ? &prel : nullptr);
+    rc = launch_icp(ctx, tg, ia, s->d_state->icpP, s->d_rays_local, scan.ranges, scan.mask, &sp, fold_argmax ? &prel : nullptr);
     if (rc != TSD_OK) return rc;
   }
   lap.lap(3);
-  const PushArgs pa = sensor_push_launch_args(s);
+  PushJob job = sensor_push_job(s, scan, s->fused.rmq, *gates);      // this scan's tables (the sensor's own buffers)
   // TSD_HALO_KERNEL=1: the push's halo pass as a kernel of its own even here (the form every other path uses; A/B)
   static const bool halo_in_raycast = [] { const char* e = std::getenv("TSD_HALO_KERNEL"); return !(e && *e == '1'); }();
   HaloArgs halo;
@@ -506,22 +502,16 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
   if (!async_map) {
     if (int rcd_ = drain_async_push(ctx)) return rcd_;   // (a push left on the push stream by an earlier, asynchronous scan)
     if (!host_saw_event(ctx->ev_tables, staged_ahead ? 2 : 60)) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_tables, 0));
-    {
-      LaunchTarget tg;
-      tg.rmq = s->fused.rmq;                                  // this scan's tables (the sensor's own buffers)
-      TargetScope scope(ctx, &tg);
-      // the registration moves the sensor by at most the gate (a larger step is rejected: pose unchanged)
-      // (the push's halo pass is left to the ray cast that follows it at once: k_raycast's prologue, raycast_kernels.hip)
-      rc = launch_push(ctx, pa, s->pos[0], s->pos[1], gates->reg_trs_max, &s->d_state->push, scan.ranges, scan.mask_push, nullptr, halo_in_raycast ? &halo : nullptr);
-    }
+    // (the push's halo pass is left to the ray cast that follows it at once: k_raycast's prologue, raycast_kernels.hip)
+    rc = launch_push(ctx, ctx->stream, job, halo_in_raycast ? &halo : nullptr);
     if (rc != TSD_OK) return rc;
     ctx->epoch++;                                          // the grid changes
     lap.lap(4);
     // the next scan's ray cast, right behind the push (see above): the host's work on the next scan no longer sits
     // between this push and that ray cast
-    rc = launch_raycast(ctx, ra, &s->d_state->rc, s->d_rays, halo_in_raycast ? &halo : nullptr);
+    rc = launch_raycast(ctx, tg, ra, &s->d_state->rc, s->d_rays, halo_in_raycast ? &halo : nullptr);
     if (rc != TSD_OK) {
-      if (halo_in_raycast) (void)launch_push_halo(ctx, halo);      // (the grid's halos must not stay behind the push whatever happened to the ray cast)
+      if (halo_in_raycast) (void)launch_push_halo(ctx, ctx->stream, halo);      // (the grid's halos must not stay behind the push whatever happened to the ray cast)
       return rc;
     }
     s->fused.rc_pending = true; s->fused.rc_epoch = ctx->epoch;
@@ -533,26 +523,16 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     // push stream.  Grid accesses stay ordered: ray cast (k+1) behind push (k-1) [first wait], push (k) behind ray cast (k+1)
     // [second wait]; the push reads its own copy of its arguments (the next registration's epilogue rewrites the sensor's).
     if (ctx->async_pending) { TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_async_push, 0)); ctx->async_pending = false; }
-    {
-      // (the event the push waits for is the ray cast's own completion -- a marker behind it would sit between the ray cast and the
-      // next registration)
-      LaunchTarget tgr;
-      tgr.rc_done = ctx->ev_async_rc;
-      TargetScope scope_r(ctx, &tgr);
-      rc = launch_raycast(ctx, ra, &s->d_state->rc, s->d_rays);
-      if (rc != TSD_OK) return rc;
-      if (!tgr.rc_done_used) TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_async_rc, ctx->stream));
-    }
+    // (the event the push waits for is the ray cast's own completion -- a marker behind it would sit between the ray cast and the
+    // next registration)
+    rc = launch_raycast(ctx, tg, ra, &s->d_state->rc, s->d_rays, nullptr, ctx->ev_async_rc);
+    if (rc != TSD_OK) return rc;
     lap.lap(4);
     TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream_push, ctx->ev_async_rc, 0));
     TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream_push, ctx->ev_tables, 0));
-    {
-      LaunchTarget tg;
-      tg.rmq = s->fused.rmq;
-      TargetScope scope(ctx, &tg);
-      if (ctx->debug_push_stall_us) launch_stall(ctx, ctx->stream_push, ctx->debug_push_stall_us);     // (tests: a push stream that lags)
-      rc = launch_push(ctx, pa, s->pos[0], s->pos[1], gates->reg_trs_max, push_slot, scan.ranges, scan.mask_push, ctx->stream_push);
-    }
+    if (ctx->debug_push_stall_us) launch_stall(ctx, ctx->stream_push, ctx->debug_push_stall_us);     // (tests: a push stream that lags)
+    job.a_dev = push_slot;                                 // (its own copy of the arguments, see above)
+    rc = launch_push(ctx, ctx->stream_push, job);
     if (rc != TSD_OK) return rc;
     ctx->ev_async_push = s->async.ev_slot_push[s->fused.slot];      // (fused.slot: the buffers of the scan being submitted)
     s->async.slot_push_valid[s->fused.slot] = true;
@@ -668,11 +648,8 @@ int tsd_scan_begin(tsd_sensor* s, const double* ranges, const uint8_t* mask, con
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(d_scan, h, scan_bytes(s->beams), hipMemcpyHostToDevice, s->split.stream));
   const ScanView scan = scan_view(d_scan, s->beams);
   s->split.rmq_slot ^= 1;                         // (the previous push of this sensor may still read its tables)
-  LaunchTarget tg;
-  tg.stream = s->split.stream; tg.coords = s->split.d_coords; tg.normals = s->split.d_normals; tg.mask_m = s->split.d_mask_m;
-  tg.icp_res = s->split.d_icp_res; tg.trace = s->split.d_icp_trace; tg.icp_seed = s->split.d_icp_seed; tg.icp_seed_points = s->beams; tg.rmq = s->d_rmq2[s->split.rmq_slot];
-  TargetScope scope(ctx, &tg);
-  rc = launch_push_tables(ctx, s->split.stream, s->beams, scan.ranges, scan.mask_push, s->phi_min, s->ang_res);
+  const LaunchTarget tg = sensor_target(s);      // ray cast and registration: the sensor's own stream and buffers
+  rc = launch_push_tables(ctx, tg.stream, s->beams, scan.ranges, scan.mask_push, s->d_rmq2[s->split.rmq_slot], s->phi_min, s->ang_res);
   if (rc != TSD_OK) return rc;
   lap.lap(0);
   {
@@ -687,14 +664,14 @@ int tsd_scan_begin(tsd_sensor* s, const double* ranges, const uint8_t* mask, con
     s->split.rc_event_valid = true;
     lap.lap(2);
   }
-  rc = launch_raycast(ctx, sensor_raycast_launch_args(s), &s->d_state->rc, s->d_rays);
+  rc = launch_raycast(ctx, tg, sensor_raycast_launch_args(s), &s->d_state->rc, s->d_rays);
   const hipError_t e_rc = hipEventRecord(s->split.ev_rc_done, s->split.stream);
   __atomic_store_n(&s->split.rc_recorded, 1, __ATOMIC_RELEASE);      // (always: a writer may be spinning on it)
   if (rc != TSD_OK) return rc;
   if (e_rc != hipSuccess) return set_error(ctx, TSD_E_HIP, "hipEventRecord(ev_rc_done)", e_rc);
   s->fused.rc_pending = false;
   const ScanPostArgs sp = sensor_post_args(s, ++s->seq, *gates);
-  rc = launch_icp(ctx, sensor_icp_args(s, params), s->d_state->icpP, s->d_rays_local, scan.ranges, scan.mask, &sp);
+  rc = launch_icp(ctx, tg, sensor_icp_args(s, params), s->d_state->icpP, s->d_rays_local, scan.ranges, scan.mask, &sp);
   if (rc != TSD_OK) return rc;
   TSD_HIP_CHECK(ctx, hipEventRecord(s->split.ev_icp_done, s->split.stream));
   s->split.gates = *gates; s->split.scan = scan;
@@ -730,11 +707,7 @@ int tsd_scan_finish(tsd_sensor* s, tsd_scan_result* result)
     lap.lap(5);
     TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, s->split.ev_icp_done, 0));
     if (int rcw = wait_for_readers(ctx)) return rcw;
-    LaunchTarget tg;
-    tg.rmq = s->d_rmq2[s->split.rmq_slot];
-    TargetScope scope(ctx, &tg);
-    // the registration moves the sensor by at most the gate (a larger step is rejected: pose unchanged)
-    rc = launch_push(ctx, sensor_push_launch_args(s), s->pos[0], s->pos[1], s->split.gates.reg_trs_max, &s->d_state->push, s->split.scan.ranges, s->split.scan.mask_push);
+    rc = launch_push(ctx, ctx->stream, sensor_push_job(s, s->split.scan, s->d_rmq2[s->split.rmq_slot], s->split.gates));
     if (rc != TSD_OK) return rc;
     ctx->epoch++;
     lap.lap(6);
@@ -1009,41 +982,31 @@ int tsd_batch_push(tsd_batch* b)
   const bool gate = b->dev_wait;                          // (else: the stream event for the whole batch's kernel)
   if (!gate) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_icp_done, 0));
   if (int rcw = wait_for_readers(ctx)) return rcw;
-  if (ctx->push_multi && b->n >= 2 && b->n <= push_multi_max_robots()) {
+  const int n = b->n;
+  PushJob jobs[TSD_BATCH_MAX_SCANS];
+  for (int i = 0; i < n; i++) {
+    tsd_sensor* s = b->sensors[(size_t)i];
+    // (s->pos: the position after the previous scan, which the host has seen)
+    jobs[i] = sensor_push_job(s, scan_view(b->d_stage_cur + b->scan_off[(size_t)i], s->beams), s->d_rmq2[s->split.rmq_slot], b->gates[(size_t)i]);
+  }
+  if (ctx->push_multi && n >= 2 && n <= push_multi_max_robots()) {
     // The robots' pushes in ONE pass per tile (push_multi.hip): every tile the batch touches is read and written once, each robot's
     // update applied in the batch's order -- the grid the serial pushes below leave, cell for cell.  One gate for all registrations.
-    const int n = b->n;
     const unsigned long long* seqp[16]; unsigned long long seqv[16]; PushArgs* pushp[16];
-    const PushArgs* ap[16]; const double* rg[16]; const uint8_t* mk[16]; const char* rq[16];
-    double cx[16], cy[16], sl[16], mr[16]; int bm[16];
     for (int i = 0; i < n; i++) {
       tsd_sensor* s = b->sensors[(size_t)i];
-      const ScanView scan = scan_view(b->d_stage_cur + b->scan_off[(size_t)i], s->beams);
       seqp[i] = &s->d_state->done_seq; seqv[i] = b->seqs[(size_t)i]; pushp[i] = &s->d_state->push;
-      ap[i] = &s->d_state->push; rg[i] = scan.ranges; mk[i] = scan.mask_push;
-      rq[i] = s->d_rmq2[s->split.rmq_slot];
-      cx[i] = s->pos[0]; cy[i] = s->pos[1]; sl[i] = b->gates[(size_t)i].reg_trs_max; mr[i] = s->max_range; bm[i] = s->beams;
     }
     if (gate) { if (int rcg = launch_wait_seq_multi(ctx, n, seqp, seqv, pushp, b->d_gate_err, b->poll_bound)) return rcg; }
-    if (int rc = launch_push_multi(ctx, ctx->stream, n, ap, rg, mk, rq, cx, cy, sl, bm, mr)) return rc;
-    ctx->epoch++;
-    b->push_enqueued = true;
-    return TSD_OK;
-  }
-  for (int i = 0; i < b->n; i++) {
-    tsd_sensor* s = b->sensors[(size_t)i];
-    // robot i's push starts when robot i's registration is done (its epilogue has left the push arguments and published the
-    // scan's sequence number), not when the slowest registration of the batch is
-    if (gate) { if (int rcg = launch_wait_seq(ctx, &s->d_state->done_seq, b->seqs[(size_t)i], &s->d_state->push, b->d_gate_err, b->poll_bound)) return rcg; }
-    LaunchTarget tg;
-    tg.rmq = s->d_rmq2[s->split.rmq_slot];
-    TargetScope scope(ctx, &tg);
-    const ScanView scan = scan_view(b->d_stage_cur + b->scan_off[(size_t)i], s->beams);
-    // the registration moves the sensor by at most the gate (a larger step is rejected: pose unchanged); s->pos is the
-    // position after the previous scan, which the host has seen
-    int rc = launch_push(ctx, sensor_push_launch_args(s), s->pos[0], s->pos[1], b->gates[(size_t)i].reg_trs_max, &s->d_state->push,
-                         scan.ranges, scan.mask_push);
-    if (rc != TSD_OK) return rc;
+    if (int rc = launch_push_multi(ctx, ctx->stream, n, jobs)) return rc;
+  } else {
+    for (int i = 0; i < n; i++) {
+      tsd_sensor* s = b->sensors[(size_t)i];
+      // robot i's push starts when robot i's registration is done (its epilogue has left the push arguments and published the
+      // scan's sequence number), not when the slowest registration of the batch is
+      if (gate) { if (int rcg = launch_wait_seq(ctx, &s->d_state->done_seq, b->seqs[(size_t)i], &s->d_state->push, b->d_gate_err, b->poll_bound)) return rcg; }
+      if (int rc = launch_push(ctx, ctx->stream, jobs[i])) return rc;
+    }
   }
   ctx->epoch++;
   b->push_enqueued = true;

@@ -1641,7 +1641,7 @@ static int icp_threads_for(int n, int R, int maxt)
 // workgroup shape: R scene points per thread, T threads.  One CU runs the whole registration and is
 // issue bound, so few waves (per-wave reduction / control cost paid once per SIMD) win.
 template <int R, int MAXT, bool PTL>
-static int launch_icp_shape_est(tsd_ctx* ctx, const IcpArgs& a, int n, int cap, const double* P_dev,
+static int launch_icp_shape_est(tsd_ctx* ctx, const LaunchTarget& tg, const IcpArgs& a, int n, int cap, const double* P_dev,
                             const double* d_rays_local, const double* d_ranges, const uint8_t* d_mask,
                             const ScanPostArgs& post, int force_T = 0, const IcpPreLaunch* pre = nullptr)
 {
@@ -1651,65 +1651,57 @@ static int launch_icp_shape_est(tsd_ctx* ctx, const IcpArgs& a, int n, int cap, 
   const bool ptl = a.estimator == TSD_ESTIMATOR_POINT_TO_LINE;
   const size_t lds = icp_lds_bytes_for(cap, T, ptl) + ICP_TL_BYTES;
   if (lds > 160u * 1024u) return set_error(ctx, TSD_E_CAPACITY, "registration does not fit the LDS of one CU (point-to-line: model normals too)", hipSuccess);
-  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp<R, MAXT, PTL>), lds)) return rc;
-  ScopedKernelTimer t(ctx, "icp");
-  const LaunchTarget* tg = launch_target();       // concurrent multi-robot path: the sensor's own stream and buffers
-  // the per-iteration record (tsd_icp_trace) is kept by tsd_icp / tsd_localize; the fused scan has no reader for it and skips
-  // the 64-byte store per step
-  double* trace_buf = tg && tg->trace ? tg->trace : ctx->d_icp_trace;
-  if (post.st) trace_buf = nullptr;
-#ifdef TSD_ICP_TIMELINE
-  if (post.st) trace_buf = ctx->d_icp_trace;     // (diagnostic build: the stamps of a fused scan's registration; no per-step record)
-#endif
-  const bool own_seed = tg && tg->icp_seed;
-  const IcpSeedArgs sa = icp_seed_args(own_seed ? tg->icp_seed : ctx->d_icp_seed, own_seed ? tg->icp_seed_points : TSD_MAX_ICP_POINTS,
-                                       icp_helpers_for(ctx, n, T));
   // The default scanner's shape (1081 beams: capacity 1088, 512 threads, closed form) has an instantiation of its own in which the
   // capacity and the thread count are compile-time constants: the twenty offsets of the LDS layout then cost no scalar registers
   // (spilled scalars of the loop 166 -> 56; -0.7 us per registration, profiles/r5_icp_helpers_ab.txt)
+  const bool node_shape = R == 3 && MAXT == 512 && !PTL && cap == 1088 && T == 512;
+  // fused registration_mode 3, the node's shape (icp_pre_supported): the arg-max rides as the launch's first workgroup
+  if (pre && (!node_shape || !post.st)) return set_error(ctx, TSD_E_ARG, "launch_icp: the arg-max can only ride with the node's registration shape", hipSuccess);
+  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp<R, MAXT, PTL>), lds)) return rc;
+  ScopedKernelTimer t(ctx, "icp");
+  // the per-iteration record (tsd_icp_trace) is kept by tsd_icp / tsd_localize; the fused scan has no reader for it and skips
+  // the 64-byte store per step
+  double* trace_buf = post.st ? nullptr : tg.trace;
+#ifdef TSD_ICP_TIMELINE
+  if (post.st) trace_buf = ctx->d_icp_trace;     // (diagnostic build: the stamps of a fused scan's registration; no per-step record)
+#endif
+  const IcpSeedArgs sa = icp_seed_args(tg.icp_seed, tg.icp_seed_points, icp_helpers_for(ctx, n, T));
   if (pre) {
-    // fused registration_mode 3, the node's shape (icp_pre_supported): the arg-max rides as the launch's first workgroup
-    if (!(R == 3 && MAXT == 512 && !PTL && cap == 1088 && T == 512) || !post.st) return set_error(ctx, TSD_E_ARG, "launch_icp: the arg-max can only ride with the node's registration shape", hipSuccess);
     if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp_pre<3, 512, 1088, 512>), lds)) return rc;
     // (the launch's own completion is the event a pre-registration armed AHEAD waits for before it overwrites the inputs; a timed
     // dispatch needs its stop event for the timer: a marker behind it then)
     hipEvent_t stop = t.b ? t.b : pre->done;
-    hipExtLaunchKernelGGL((k_icp_pre<3, 512, 1088, 512>), dim3(2 + sa.helpers), dim3(T), lds, launch_stream(ctx), t.a, stop, 0, a, P_dev, cap,
-                     tg && tg->coords ? tg->coords : ctx->d_coords, tg && tg->mask_m ? tg->mask_m : ctx->d_mask_m,
-                     d_rays_local ? d_rays_local : ctx->d_rays_local, d_ranges ? d_ranges : ctx->d_ranges,
-                     d_mask ? d_mask : ctx->d_mask, tg && tg->icp_res ? tg->icp_res : ctx->d_icp_res, trace_buf, post, sa, pre->dev);
+    hipExtLaunchKernelGGL((k_icp_pre<3, 512, 1088, 512>), dim3(2 + sa.helpers), dim3(T), lds, tg.stream, t.a, stop, 0, a, P_dev, cap,
+                     tg.coords, tg.mask_m, d_rays_local, d_ranges, d_mask, tg.icp_res, trace_buf, post, sa, pre->dev);
     TSD_HIP_CHECK(ctx, hipGetLastError());
-    if (t.b && pre->done) TSD_HIP_CHECK(ctx, hipEventRecord(pre->done, launch_stream(ctx)));
+    if (t.b && pre->done) TSD_HIP_CHECK(ctx, hipEventRecord(pre->done, tg.stream));
     return TSD_OK;
   }
-  if (R == 3 && MAXT == 512 && !PTL && cap == 1088 && T == 512) {
+  // (k_icp's argument list, once for the generic instantiation and the node's)
+  auto launch = [&](auto kernel) {
+    hipExtLaunchKernelGGL(kernel, dim3(1 + sa.helpers), dim3(T), lds, tg.stream, t.a, t.b, 0, a, P_dev, cap, ctx->d_model, ctx->d_scene,
+                     ctx->d_morig, ctx->d_start, tg.coords, tg.mask_m, d_rays_local, d_ranges, d_mask, tg.icp_res,
+                     trace_buf, post, ctx->d_mnormals, tg.normals, sa);
+  };
+  if (node_shape) {
     if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp<3, 512, false, 1088, 512>), lds)) return rc;
-    hipExtLaunchKernelGGL((k_icp<3, 512, false, 1088, 512>), dim3(1 + sa.helpers), dim3(T), lds, launch_stream(ctx), t.a, t.b, 0, a, P_dev, cap, ctx->d_model, ctx->d_scene,
-                     ctx->d_morig, ctx->d_start, tg && tg->coords ? tg->coords : ctx->d_coords, tg && tg->mask_m ? tg->mask_m : ctx->d_mask_m,
-                     d_rays_local ? d_rays_local : ctx->d_rays_local, d_ranges ? d_ranges : ctx->d_ranges,
-                     d_mask ? d_mask : ctx->d_mask, tg && tg->icp_res ? tg->icp_res : ctx->d_icp_res,
-                     trace_buf, post, ctx->d_mnormals, tg && tg->normals ? tg->normals : ctx->d_normals, sa);
-    TSD_HIP_CHECK(ctx, hipGetLastError());
-    return TSD_OK;
+    launch(k_icp<3, 512, false, 1088, 512>);
+  } else {
+    launch(k_icp<R, MAXT, PTL>);
   }
-  hipExtLaunchKernelGGL((k_icp<R, MAXT, PTL>), dim3(1 + sa.helpers), dim3(T), lds, launch_stream(ctx), t.a, t.b, 0, a, P_dev, cap, ctx->d_model, ctx->d_scene,
-                     ctx->d_morig, ctx->d_start, tg && tg->coords ? tg->coords : ctx->d_coords, tg && tg->mask_m ? tg->mask_m : ctx->d_mask_m,
-                     d_rays_local ? d_rays_local : ctx->d_rays_local, d_ranges ? d_ranges : ctx->d_ranges,
-                     d_mask ? d_mask : ctx->d_mask, tg && tg->icp_res ? tg->icp_res : ctx->d_icp_res,
-                     trace_buf, post, ctx->d_mnormals, tg && tg->normals ? tg->normals : ctx->d_normals, sa);
   TSD_HIP_CHECK(ctx, hipGetLastError());
   return TSD_OK;
 }
 
 template <int R, int MAXT>
-static int launch_icp_shape(tsd_ctx* ctx, const IcpArgs& a, int n, int cap, const double* P_dev,
+static int launch_icp_shape(tsd_ctx* ctx, const LaunchTarget& tg, const IcpArgs& a, int n, int cap, const double* P_dev,
                             const double* d_rays_local, const double* d_ranges, const uint8_t* d_mask,
                             const ScanPostArgs& post, int force_T = 0, const IcpPreLaunch* pre = nullptr)
 {
   // the estimator is a compile-time choice: the node's closed form does not pay for the other one's tenth sum
   if (a.estimator == TSD_ESTIMATOR_POINT_TO_LINE)
-    return launch_icp_shape_est<R, MAXT, true>(ctx, a, n, cap, P_dev, d_rays_local, d_ranges, d_mask, post, force_T, pre);
-  return launch_icp_shape_est<R, MAXT, false>(ctx, a, n, cap, P_dev, d_rays_local, d_ranges, d_mask, post, force_T, pre);
+    return launch_icp_shape_est<R, MAXT, true>(ctx, tg, a, n, cap, P_dev, d_rays_local, d_ranges, d_mask, post, force_T, pre);
+  return launch_icp_shape_est<R, MAXT, false>(ctx, tg, a, n, cap, P_dev, d_rays_local, d_ranges, d_mask, post, force_T, pre);
 }
 
 // can the pre-registration's arg-max ride with this registration's launch (k_icp_pre: the node's shape, closed form, fused scan)?
@@ -1719,7 +1711,7 @@ bool icp_pre_supported(const tsd_ctx* ctx, const IcpArgs& a)
   return icp_cap_for(a.beams) == 1088 && icp_threads_for(a.beams, 3, 512) == 512;
 }
 
-int launch_icp(tsd_ctx* ctx, const IcpArgs& a, const double* P_dev, const double* d_rays_local,
+int launch_icp(tsd_ctx* ctx, const LaunchTarget& tg, const IcpArgs& a, const double* P_dev, const double* d_rays_local,
                const double* d_ranges, const uint8_t* d_mask, const ScanPostArgs* post_in, const IcpPreLaunch* pre)
 {
   ScanPostArgs post;
@@ -1733,10 +1725,10 @@ int launch_icp(tsd_ctx* ctx, const IcpArgs& a, const double* P_dev, const double
   const int nthr = a.beams > 0 ? a.beams : a.n_scene;     // scene points decide the thread count
   // (round 3: the experimental shapes <2,576>, <5,512> and <5,256> are gone -- measured no faster in round 2, and the first spilled
   // 21-27 registers per lane; TSD_ICP_SHAPE=8 forces the 8-points-per-thread shape, TSD_ICP_SHAPE >= 64 a thread count of <3,512>)
-  if (ctx->icp_shape == 8) return launch_icp_shape<8, 256>(ctx, a, nthr, cap, P_dev, d_rays_local, d_ranges, d_mask, post);
+  if (ctx->icp_shape == 8) return launch_icp_shape<8, 256>(ctx, tg, a, nthr, cap, P_dev, d_rays_local, d_ranges, d_mask, post);
   if (pre && !icp_pre_supported(ctx, a)) return set_error(ctx, TSD_E_ARG, "launch_icp: the arg-max can only ride with the node's registration shape", hipSuccess);
-  if (nthr <= 3 * 512) return launch_icp_shape<3, 512>(ctx, a, nthr, cap, P_dev, d_rays_local, d_ranges, d_mask, post, ctx->icp_shape >= 64 ? ctx->icp_shape : 0, pre);
-  return launch_icp_shape<8, 256>(ctx, a, nthr, cap, P_dev, d_rays_local, d_ranges, d_mask, post);
+  if (nthr <= 3 * 512) return launch_icp_shape<3, 512>(ctx, tg, a, nthr, cap, P_dev, d_rays_local, d_ranges, d_mask, post, ctx->icp_shape >= 64 ? ctx->icp_shape : 0, pre);
+  return launch_icp_shape<8, 256>(ctx, tg, a, nthr, cap, P_dev, d_rays_local, d_ranges, d_mask, post);
 }
 
 template <int R, int MAXT>

@@ -822,22 +822,13 @@ size_t push_rmq_bytes(int beams) { return rmq_bytes(beams); }
 size_t push_list_aux_bytes() { return sizeof(PushListAux); }
 size_t push_list_cnt_bytes() { return 2 * CNT_WORDS * sizeof(unsigned int); }
 
-int launch_push_tables(tsd_ctx* ctx, hipStream_t stream, int beams, const double* d_ranges, const uint8_t* d_mask,
+int launch_push_tables(tsd_ctx* ctx, hipStream_t stream, int beams, const double* d_ranges, const uint8_t* d_mask, char* rmq,
                        double phi_min, double ang_res)
 {
   const size_t bp = (size_t)((beams + 3) & ~3);
   const size_t lds = 2 * bp * sizeof(double) + 4 * bp * 2 + 64;
   if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_push_tables), lds)) return rc;
-  char* rmq;
-  if (launch_target() && launch_target()->rmq) rmq = launch_target()->rmq;       // concurrent multi-robot path: the sensor's own (double) buffer
-  else {
-    std::lock_guard<std::mutex> lk_misc(ctx->misc_mutex);
-    ctx->rmq_slot ^= 1;                                  // the push that may still be running keeps its tables
-    ctx->d_rmq = ctx->d_rmq2[ctx->rmq_slot];
-    rmq = ctx->d_rmq;
-  }
-  hipLaunchKernelGGL(k_push_tables, dim3(1), dim3(1024), lds, stream, d_ranges ? d_ranges : ctx->d_ranges,
-                     d_mask ? d_mask : ctx->d_mask, beams, rmq, phi_min, ang_res);
+  hipLaunchKernelGGL(k_push_tables, dim3(1), dim3(1024), lds, stream, d_ranges, d_mask, beams, rmq, phi_min, ang_res);
   TSD_HIP_CHECK(ctx, hipGetLastError());
   return TSD_OK;
 }
@@ -852,19 +843,17 @@ int launch_push_tables_batch(tsd_ctx* ctx, hipStream_t stream, const TablesBatch
   return TSD_OK;
 }
 
-// the tables of this scan must already be in ctx->d_rmq (launch_push_tables, ordered before this)
-int launch_push(tsd_ctx* ctx, const PushArgs& a, double cx, double cy, double slack, const PushArgs* a_dev,
-                const double* d_ranges, const uint8_t* d_mask, hipStream_t stream_arg, HaloArgs* defer_halo)
+// the tables of this scan must already be in job.rmq (launch_push_tables, ordered before this)
+int launch_push(tsd_ctx* ctx, hipStream_t stream, const PushJob& job, HaloArgs* defer_halo)
 {
-  const hipStream_t stream = stream_arg ? stream_arg : ctx->stream;
   const GridDev& g = ctx->grid;
+  const PushArgs* const a_dev = job.a_dev;
   if (!a_dev) return set_error(ctx, TSD_E_ARG, "launch_push: the arguments must be on the device", hipSuccess);
-  char* const rmq = (launch_target() && launch_target()->rmq) ? launch_target()->rmq : ctx->d_rmq;
-  if (!d_ranges) d_ranges = ctx->d_ranges;
-  if (!d_mask) d_mask = ctx->d_mask;
-  // Tile window (push_tile_window), sensor max_range from the by-value args or the attached sensor.  The window also covers the
-  // previous push (its records are rewritten) and whatever freeFootprint touched since.
-  TileBox box = push_tile_window(g, cx, cy, a.max_range, slack);
+  char* const rmq = job.rmq;
+  const double cx = job.cx, cy = job.cy, slack = job.slack;
+  // Tile window (push_tile_window).  The window also covers the previous push (its records are rewritten) and whatever freeFootprint
+  // touched since.
+  TileBox box = push_tile_window(g, cx, cy, job.max_range, slack);
   const TileBox cur = box;
   box.add(ctx->box_prev);
   box.add(ctx->box_dirty);
@@ -888,15 +877,15 @@ int launch_push(tsd_ctx* ctx, const PushArgs& a, double cx, double cy, double sl
   // as many workgroups as are RESIDENT at once (UPDATE_WPS per compute unit), never more: every workgroup loops over the
   // list with that stride, and a second round of workgroups would start its whole share of the list when the first round is done
   int per_cu = UPDATE_WPS;
-  { const size_t lds_wg = update_lds_bytes(a.beams) + 64; const int by_lds = (int)((160u * 1024u) / lds_wg); if (by_lds < per_cu) per_cu = by_lds < 1 ? 1 : by_lds; }
+  { const size_t lds_wg = update_lds_bytes(job.beams) + 64; const int by_lds = (int)((160u * 1024u) / lds_wg); if (by_lds < per_cu) per_cu = by_lds < 1 ? 1 : by_lds; }
   const int resident = ctx->n_cus * per_cu;
   const int n_groups = n_window < resident ? n_window : resident;
   {
     ScopedKernelTimer t(ctx, "push_update");
-    size_t lds = update_lds_bytes(a.beams);
-    hipExtLaunchKernelGGL(k_push_update, dim3(n_groups), dim3(UPDATE_BLOCK), lds, stream, t.a, t.b, 0, g, a_dev, d_ranges, d_mask,
+    size_t lds = update_lds_bytes(job.beams);
+    hipExtLaunchKernelGGL(k_push_update, dim3(n_groups), dim3(UPDATE_BLOCK), lds, stream, t.a, t.b, 0, g, a_dev, job.ranges, job.mask,
                        ctx->d_tile_rec, ctx->d_tile_totals, ctx->d_list, reinterpret_cast<const PushListAux*>(ctx->d_list_aux), ctx->d_list_cnt, parity,
-                       rmq_view(rmq, a.beams).bdir, rmq_view(rmq, a.beams).rot, ctx->d_icp_trace);
+                       rmq_view(rmq, job.beams).bdir, rmq_view(rmq, job.beams).rot, ctx->d_icp_trace);
   }
   TSD_HIP_CHECK(ctx, hipGetLastError());
   HaloArgs h;
@@ -908,10 +897,10 @@ int launch_push(tsd_ctx* ctx, const PushArgs& a, double cx, double cy, double sl
     *defer_halo = h;
     return TSD_OK;
   }
-  return launch_push_halo(ctx, h, n_window, stream);
+  return launch_push_halo(ctx, stream, h, n_window);
 }
 
-int launch_push_halo(tsd_ctx* ctx, const HaloArgs& h, int n_window, hipStream_t stream)
+int launch_push_halo(tsd_ctx* ctx, hipStream_t stream, const HaloArgs& h, int n_window)
 {
   {
     ScopedKernelTimer t(ctx, "push_halo");
@@ -921,7 +910,7 @@ int launch_push_halo(tsd_ctx* ctx, const HaloArgs& h, int n_window, hipStream_t 
     constexpr int HALO_WAVES = 2048;
     if (n_window > ctx->grid.tiles) n_window = ctx->grid.tiles;        // (every wave reads its first list entry speculatively: stay inside the list)
     const int n_waves = n_window < HALO_WAVES ? (n_window < 1 ? 1 : n_window) : HALO_WAVES;
-    hipExtLaunchKernelGGL(k_push_halo, dim3((n_waves + 3) / 4), dim3(256), 0, stream ? stream : ctx->stream, t.a, t.b, 0, ctx->grid, h);
+    hipExtLaunchKernelGGL(k_push_halo, dim3((n_waves + 3) / 4), dim3(256), 0, stream, t.a, t.b, 0, ctx->grid, h);
   }
   TSD_HIP_CHECK(ctx, hipGetLastError());
   return TSD_OK;

@@ -417,8 +417,7 @@ k_mp_halo(GridDev g, MultiPushArgs mp, uint8_t* __restrict__ dirty, unsigned lon
 // ------------------------------------------------------------------------------------------------------------------------------
 // n robots' pushes in one pass (n <= MP_MAX_ROBOTS); every robot's range-query tables must be in its rmq buffer (ordered before this).
 int push_multi_max_robots() { return MP_MAX_ROBOTS; }
-int launch_push_multi(tsd_ctx* ctx, hipStream_t stream, int n, const PushArgs* const* a_dev, const double* const* d_ranges, const uint8_t* const* d_mask,
-                      const char* const* d_rmq, const double* cx, const double* cy, const double* slack, const int* beams, const double* max_range)
+int launch_push_multi(tsd_ctx* ctx, hipStream_t stream, int n, const PushJob* jobs)
 {
   if (n < 1 || n > MP_MAX_ROBOTS) return set_error(ctx, TSD_E_ARG, "launch_push_multi: robots", hipSuccess);
   const GridDev& g = ctx->grid;
@@ -428,9 +427,10 @@ int launch_push_multi(tsd_ctx* ctx, hipStream_t stream, int n, const PushArgs* c
   TileBox box;
   int max_beams = 1;
   for (int i = 0; i < n; i++) {
-    mp.r[i] = MultiPushRobot{a_dev[i], d_ranges[i], d_mask[i], d_rmq[i], cx[i], cy[i], slack[i] + g.cs};
-    if (beams[i] > max_beams) max_beams = beams[i];
-    box.add(push_tile_window(g, cx[i], cy[i], max_range[i], slack[i]));          // the robot's own window
+    const PushJob& j = jobs[i];
+    mp.r[i] = MultiPushRobot{j.a_dev, j.ranges, j.mask, j.rmq, j.cx, j.cy, j.slack + g.cs};
+    if (j.beams > max_beams) max_beams = j.beams;
+    box.add(push_tile_window(g, j.cx, j.cy, j.max_range, j.slack));          // the robot's own window
   }
   const TileBox cur = box;
   box.add(ctx->box_prev);

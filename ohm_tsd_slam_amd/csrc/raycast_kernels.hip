@@ -676,21 +676,20 @@ int launch_raycast_batch(tsd_ctx* ctx, hipStream_t stream, const RaycastBatchEnt
   return TSD_OK;
 }
 
-int launch_raycast(tsd_ctx* ctx, const RaycastArgs& a, const RaycastArgs* a_dev, const double* d_rays, const HaloArgs* halo)
+int launch_raycast(tsd_ctx* ctx, const LaunchTarget& tg, const RaycastArgs& a, const RaycastArgs* a_dev, const double* d_rays,
+                   const HaloArgs* halo, hipEvent_t done)
 {
   ScopedKernelTimer t(ctx, "raycast");
-  const LaunchTarget* tg = launch_target();       // concurrent multi-robot path: the sensor's own stream and output buffers
-  hipEvent_t stop = t.b;
-  if (tg && tg->rc_done && !t.b) { stop = tg->rc_done; const_cast<LaunchTarget*>(tg)->rc_done_used = true; }
-  if (halo)
-    hipExtLaunchKernelGGL(k_raycast_halo, dim3(a.beams + RC_HALO_WAVES), dim3(64), 0, launch_stream(ctx), t.a, stop, 0, ctx->grid, a, a_dev, d_rays ? d_rays : ctx->d_rays,
-                       tg && tg->coords ? tg->coords : ctx->d_coords, tg && tg->normals ? tg->normals : ctx->d_normals,
-                       tg && tg->mask_m ? tg->mask_m : ctx->d_mask_m, ctx->d_icp_trace, *halo);
-  else
-  hipExtLaunchKernelGGL(k_raycast, dim3(a.beams), dim3(64), 0, launch_stream(ctx), t.a, stop, 0, ctx->grid, a, a_dev, d_rays ? d_rays : ctx->d_rays,
-                     tg && tg->coords ? tg->coords : ctx->d_coords, tg && tg->normals ? tg->normals : ctx->d_normals,
-                     tg && tg->mask_m ? tg->mask_m : ctx->d_mask_m, ctx->d_icp_trace);
+  const hipEvent_t stop = t.b ? t.b : done;
+  // (k_raycast and k_raycast_halo: one argument list, the halo pass's arguments behind it)
+  auto launch = [&](auto kernel, int halo_waves, auto... halo_args) {
+    hipExtLaunchKernelGGL(kernel, dim3(a.beams + halo_waves), dim3(64), 0, tg.stream, t.a, stop, 0, ctx->grid, a, a_dev, d_rays,
+                          tg.coords, tg.normals, tg.mask_m, ctx->d_icp_trace, halo_args...);
+  };
+  if (halo) launch(k_raycast_halo, RC_HALO_WAVES, *halo);
+  else launch(k_raycast, 0);
   TSD_HIP_CHECK(ctx, hipGetLastError());
+  if (t.b && done) TSD_HIP_CHECK(ctx, hipEventRecord(done, tg.stream));
   return TSD_OK;
 }
 

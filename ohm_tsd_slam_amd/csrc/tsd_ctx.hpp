@@ -109,17 +109,23 @@ struct TileBox {
   }
 };
 
-// Where a ray cast / registration of the concurrent multi-robot path runs and writes (tsd_scan_begin / _finish): the
-// sensor's own stream and output buffers instead of the context's.  Set for the duration of the launches by the entry
-// point (calls on one context are serialised by the caller), nullptr otherwise.
+// Where a ray cast and a registration run and what they write: the context's own stream and buffers (ctx_target: the unfused entry
+// points and the fused scan) or a sensor's (sensor_target: tsd_scan_begin).  Always filled completely; launch_raycast and launch_icp
+// take it as an argument.
 struct LaunchTarget {
-  hipStream_t stream = nullptr;                                       // ray cast + registration
-  double* coords = nullptr; double* normals = nullptr; uint8_t* mask_m = nullptr;   // ray-cast outputs
-  IcpResultDev* icp_res = nullptr; double* trace = nullptr;
-  void* icp_seed = nullptr; int icp_seed_points = 0;                  // the registration's helper hand-off (icp_seed_bytes(points))
-  char* rmq = nullptr;                                                // range-query tables of the scan's push
-  hipEvent_t rc_done = nullptr;                                       // launch_raycast: completes with the ray cast itself (the kernel's own stop
-  bool rc_done_used = false;                                          // event: no marker behind it); used = false when the dispatch is being timed
+  hipStream_t stream;
+  double* coords; double* normals; uint8_t* mask_m;    // the ray cast's outputs = the registration's model
+  IcpResultDev* icp_res; double* trace;
+  void* icp_seed; int icp_seed_points;                 // the registration's helper hand-off (icp_seed_bytes(points))
+};
+
+// One push as the host describes it: the arguments on the device, the scan, its range-query tables (launch_push_tables, ordered before
+// the push), where the host knows the sensor to be (cx, cy) and how far the device-side pose may be from there (slack), and what sizes
+// the launches (beams: LDS; max_range: tile window).
+struct PushJob {
+  const PushArgs* a_dev; const double* ranges; const uint8_t* mask; char* rmq;
+  double cx, cy, slack;
+  int beams; double max_range;
 };
 
 // ---- batched scans (tsd_batch_*): one launch of each kernel for the robots of a batch; block (.., y) of the batched ray cast /
@@ -201,9 +207,8 @@ struct tsd_ctx {
   std::string err;
 
   // push state
-  char* d_rmq = nullptr;                     // range-query tables of the current scan (k_push_tables): one of d_rmq2
-  char* d_rmq2[2] = {nullptr, nullptr};      // (the next scan's tables are built while the current push still reads its own)
-  int rmq_slot = 0;
+  char* d_rmq2[2] = {nullptr, nullptr};      // range-query tables of an unfused tsd_push (k_push_tables), used in turn (next_ctx_tables):
+  int rmq_slot = 0;                          // the next scan's tables are built while the current push still reads its own
   std::map<const void*, size_t> lds_configured;   // dynamic LDS every kernel was configured for on this context's device (ensure_dynamic_lds)
   hipEvent_t ev_h2d = nullptr;               // fused scan: the scan's copy (side stream) is complete
   uint32_t* d_tile_rec = nullptr;            // [tiles] what the last push did to every tile
@@ -424,15 +429,15 @@ struct tsd_batch {
 namespace tsd {
 
 int set_error(tsd_ctx* ctx, int code, const char* what, hipError_t e);
-// launch target of the entry point that is enqueueing on THIS thread (the sensors' private streams are driven by their
-// own threads, outside the caller's grid lock)
-extern thread_local const LaunchTarget* g_launch_target;
-inline const LaunchTarget* launch_target() { return g_launch_target; }
-inline hipStream_t launch_stream(const tsd_ctx* c) { return (g_launch_target && g_launch_target->stream) ? g_launch_target->stream : c->stream; }
-struct TargetScope {
-  TargetScope(tsd_ctx*, const LaunchTarget* t) { g_launch_target = t; }
-  ~TargetScope() { g_launch_target = nullptr; }
-};
+inline LaunchTarget ctx_target(const tsd_ctx* c)
+{
+  return LaunchTarget{c->stream, c->d_coords, c->d_normals, c->d_mask_m, c->d_icp_res, c->d_icp_trace, c->d_icp_seed, TSD_MAX_ICP_POINTS};
+}
+inline LaunchTarget sensor_target(const tsd_sensor* s)    // (after sensor_conc_init(s, true))
+{
+  const tsd_sensor::Split& p = s->split;
+  return LaunchTarget{p.stream, p.d_coords, p.d_normals, p.d_mask_m, p.d_icp_res, p.d_icp_trace, p.d_icp_seed, s->beams};
+}
 #define TSD_HIP_CHECK(ctx, call)                                                     \
   do {                                                                               \
     hipError_t _e = (call);                                                          \
@@ -464,17 +469,15 @@ void drain_timers(tsd_ctx* ctx);
 int drain_async_push(tsd_ctx* ctx);          // asynchronous mapping: order the context's stream behind the push stream's last push (capi.hip)
 bool kernel_is_timed(const tsd_ctx* ctx, const char* name);
 
-// per-file launchers.  The *_dev pointers are the fused scan path: the kernels then read their pose
-// dependent arguments from the device-resident sensor state instead of the by-value copy.
-// (cx, cy) is where the host knows the sensor to be and `slack` how far the device-side pose may be from it
+// per-file launchers.  Which stream a kernel goes to and which buffers it reads and writes are arguments of the call; nothing is
+// defaulted below the entry points.  The *_dev pointers are the fused scan path: the kernels then read their pose dependent arguments
+// from the device-resident sensor state instead of the by-value copy.
 // defer_halo != nullptr: k_push_halo is NOT launched; *defer_halo receives its arguments for the ray cast that follows the push and
 // carries that pass in its prologue (launch_raycast(.., halo)) -- or for launch_push_halo() where no such ray cast follows
 struct HaloArgs;
-int launch_push(tsd_ctx* ctx, const PushArgs& a, double cx, double cy, double slack, const PushArgs* a_dev = nullptr,
-                const double* d_ranges = nullptr, const uint8_t* d_mask = nullptr, hipStream_t stream = nullptr /* nullptr: ctx->stream */,
-                HaloArgs* defer_halo = nullptr);
-int launch_push_halo(tsd_ctx* ctx, const HaloArgs& h, int n_window = 2048, hipStream_t stream = nullptr);
-int launch_push_tables(tsd_ctx* ctx, hipStream_t stream, int beams, const double* d_ranges, const uint8_t* d_mask,
+int launch_push(tsd_ctx* ctx, hipStream_t stream, const PushJob& job, HaloArgs* defer_halo = nullptr);
+int launch_push_halo(tsd_ctx* ctx, hipStream_t stream, const HaloArgs& h, int n_window = 2048);
+int launch_push_tables(tsd_ctx* ctx, hipStream_t stream, int beams, const double* d_ranges, const uint8_t* d_mask, char* rmq,
                        double phi_min, double ang_res);
 size_t push_rmq_bytes(int beams);
 size_t push_list_aux_bytes();
@@ -491,13 +494,15 @@ int launch_neg_scan(tsd_ctx* ctx);
 int launch_export_tiles(tsd_ctx* ctx, int t0, int n, double* d_t, double* d_w);
 int launch_import_tiles(tsd_ctx* ctx, int t0, int n, const double* d_t, const double* d_w);
 int launch_grid_digest(tsd_ctx* ctx, unsigned long long* d_out, double* d_sums);
-int launch_raycast(tsd_ctx* ctx, const RaycastArgs& a, const RaycastArgs* a_dev = nullptr, const double* d_rays = nullptr,
-                   const HaloArgs* halo = nullptr /* the push right ahead of this launch left its halo pass to it */);
+// halo: the push right ahead of this launch left its halo pass to it.  done: an event that completes with the ray cast itself (the
+// launch's own stop event: no marker behind it; a timed dispatch needs its stop event for the timer and records `done` behind it)
+int launch_raycast(tsd_ctx* ctx, const LaunchTarget& tg, const RaycastArgs& a, const RaycastArgs* a_dev, const double* d_rays,
+                   const HaloArgs* halo = nullptr, hipEvent_t done = nullptr);
 // pre: fused registration_mode 3 -- the pre-registration's arg-max rides as the first workgroup of the registration's launch (k_icp_pre;
 // only where icp_pre_supported() says so); pre->done is recorded when the launch has completed
 bool icp_pre_supported(const tsd_ctx* ctx, const IcpArgs& a);
-int launch_icp(tsd_ctx* ctx, const IcpArgs& a, const double* P_dev = nullptr, const double* d_rays_local = nullptr,
-               const double* d_ranges = nullptr, const uint8_t* d_mask = nullptr, const ScanPostArgs* post = nullptr, const IcpPreLaunch* pre = nullptr);
+int launch_icp(tsd_ctx* ctx, const LaunchTarget& tg, const IcpArgs& a, const double* P_dev, const double* d_rays_local,
+               const double* d_ranges, const uint8_t* d_mask, const ScanPostArgs* post = nullptr, const IcpPreLaunch* pre = nullptr);
 int launch_icp_pairs(tsd_ctx* ctx, const IcpArgs& a, int* d_pairs);
 int icp_pairs_cap(int n_model, int n_scene);
 int launch_scan_prepare(tsd_ctx* ctx, SensorDev* st);
@@ -517,8 +522,7 @@ int launch_raycast_batch_byval(tsd_ctx* ctx, hipStream_t stream, const RaycastBa
 int launch_push_tables_batch(tsd_ctx* ctx, hipStream_t stream, const TablesBatchEntry* d_entries, int n, int max_beams);
 int launch_icp_batch(tsd_ctx* ctx, hipStream_t stream, const IcpBatchEntry* host, const IcpBatchEntry* d_entries, int n);
 int push_multi_max_robots();
-int launch_push_multi(tsd_ctx* ctx, hipStream_t stream, int n, const PushArgs* const* a_dev, const double* const* d_ranges, const uint8_t* const* d_mask,
-                      const char* const* d_rmq, const double* cx, const double* cy, const double* slack, const int* beams, const double* max_range);
+int launch_push_multi(tsd_ctx* ctx, hipStream_t stream, int n, const PushJob* jobs);
 int launch_wait_seq_multi(tsd_ctx* ctx, int n, const unsigned long long* const* seq, const unsigned long long* value, PushArgs* const* push,
                           unsigned int* err_host, unsigned int poll_bound);
 size_t icp_seed_bytes(int points);
