@@ -489,9 +489,45 @@ void* tsd_group_member_map_dev(tsd_group* g, int i);
 int   tsd_group_profile(tsd_group* g, int on);
 int   tsd_group_merge_times(tsd_group* g, double* extract_ms_total, double* merge_ms_total, int* merges);
 
+/* ---- TSD-level fusion: the grids of several robots on ONE GPU fused into one grid ------------------------------- */
+/* dst becomes the grid that would have seen every member's scans: member i's cell (x, y) is dst's cell (x + ox_i, y + oy_i), offsets
+ * in whole cells, any integer in +-2^24 (no multiple of 32 is asked for); members are clipped to dst, what no member reaches becomes
+ * unknown, dst's previous content is discarded.  dst is an ordinary context afterwards: ray cast, localise, push, store, colour image.
+ *
+ * Contribution of member i at one of its cells: an initialised tile gives (tsd, weight) where tsd is not NaN and nothing where it is;
+ * an uninitialised tile with _initWeight > 0 (an "empty" tile, shorthand for tsd = 1, W = _initWeight: TsdGridPartition::init) gives
+ * (1.0, _initWeight); anything else gives nothing.  The fused cell, contributors in member order, fp64, no contraction:
+ *   none          (NaN, 0)
+ *   exactly one   (t, min(w, 32)), verbatim: fusing one grid at offset 0 is an identity
+ *   several       num = 0 + t1 w1 + t2 w2 + ..., den = 0 + w1 + w2 + ..., summed left to right; den > 0: (num / den, min(den, 32));
+ *                 den == 0 (cells freed by tsd_free_footprint): (t of the first contributor, 0)
+ * A dst tile is materialised when a member's initialised tile intersects its 32 x 32 cells; otherwise it stays unmaterialised when
+ * its 1024 fused cells are all equal (_initWeight = their weight, 0 for unknown) and is materialised with those cells when they are not
+ * (the empty tiles of members shifted by less than a tile).  _initWeight of a tile materialised by the first rule is that of the first
+ * member (member order, then source tile row by row) whose initialised tile intersects it, 0 by the second rule.  Every halo cell of a
+ * materialised tile holds the fused state of the grid cell it duplicates, (NaN, 0) beyond the grid's edge.  The ray cast's sign masks
+ * are rebuilt, the push bookkeeping is left as after tsd_reset.  Bit-exactness is claimed for fp64 cell storage.
+ *
+ * Refused with TSD_E_ARG before the first HIP call and with the grids untouched (tsd_last_error(dst) names the reason): n outside
+ * 1 .. 64, a NULL member, dst among the members, a member listed twice, members on another device than dst, a member whose cell size
+ * or max_truncation differs bitwise from dst's, an offset outside +-2^24.
+ *
+ * Everything runs behind events; the host waits for nothing before tsd_fuse_wait.  The kernel runs on dst's stream, behind whatever
+ * dst's own ordering asks for and behind every grid write the members have enqueued so far (the push stream of the asynchronous
+ * mapping included); what a member enqueues after the call runs behind the kernel.  The call holds the members' and dst's internal
+ * locks while it enqueues; a caller that serialises each context with a lock of its own holds those of all contexts involved for
+ * the duration of tsd_fuse_begin only.  tsd_destroy of a member or of dst with a fusion in flight is safe.  The counters: tiles of
+ * dst by representation, cells_valid = cells of dst with a fused value = cells_one_source + cells_many_sources (contributors). */
+typedef struct tsd_fuse_stats {
+  int64_t tiles_materialised, tiles_empty, cells_valid, cells_one_source, cells_many_sources;
+} tsd_fuse_stats;
+int tsd_fuse_begin(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell_off_xy /* 2n, NULL = 0 */);
+int tsd_fuse_wait(tsd_ctx* dst, tsd_fuse_stats* stats /* may be NULL */);
+int tsd_fuse(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell_off_xy, tsd_fuse_stats* stats);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the ctx stream.  Kernel names: "push_classify", "push_update",
- * "push_halo", "raycast", "icp", "occupancy", "tsdpdf". */
+ * "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse". */
 int tsd_profile_enable(tsd_ctx* ctx, int on);
 /* restrict timing to a comma separated list of kernel names, or "all"; a "/n" suffix times every n-th
  * launch only (two event records cost ~13 us of stream time per timed launch); a name may carry its own

@@ -106,6 +106,15 @@ class MapParams(C.Structure):
     _fields_ = [("inflate", C.c_int32), ("inflate_factor", C.c_int32)]
 
 
+class FuseStats(C.Structure):
+    """tsd_fuse_stats"""
+    _fields_ = [("tiles_materialised", C.c_int64), ("tiles_empty", C.c_int64), ("cells_valid", C.c_int64),
+                ("cells_one_source", C.c_int64), ("cells_many_sources", C.c_int64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class RnMatchResult(C.Structure):
     """tsd_rnmatch_result"""
     _fields_ = [("T", C.c_double * 9), ("ratio", C.c_double), ("err_sum", C.c_double), ("cnt_match", C.c_int32),
@@ -253,6 +262,9 @@ ABI = {
     "tsd_group_member_map_dev": (C.c_void_p, [C.c_void_p, C.c_int]),
     "tsd_group_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "tsd_group_merge_times": (C.c_int, [C.c_void_p, _dp, _dp, _ip]),
+    "tsd_fuse_begin": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "tsd_fuse_wait": (C.c_int, [C.c_void_p, C.POINTER(FuseStats)]),
+    "tsd_fuse": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(FuseStats)]),
     "tsd_icp_pairs": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, C.c_int, _dp, C.POINTER(IcpParams), C.c_int, _ip, _ip, _ip]),
     "tsd_calibrate_rmw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
     "tsd_measure_stream": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _dp, _dp]),
@@ -288,7 +300,8 @@ def load_library(path: str | None = None):
                           ("tsd_gate_params", GateParams), ("tsd_scan_result", ScanResult), ("tsd_grid_digest_t", GridDigest),
                           ("tsd_tsdpdf_params", TsdPdfParams), ("tsd_tsdpdf_result", TsdPdfResult),
                           ("tsd_pdfmatch_params", PdfMatchParams), ("tsd_rnmatch_params", RnMatchParams),
-                          ("tsd_rnmatch_result", RnMatchResult), ("tsd_map_params", MapParams)):
+                          ("tsd_rnmatch_result", RnMatchResult), ("tsd_map_params", MapParams),
+                          ("tsd_fuse_stats", FuseStats)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -588,6 +601,29 @@ class TsdGridDevice:
         img = np.zeros((height, width, 3), dtype=np.uint8)
         self._check(self.lib.tsd_color_image(self.h, img.ctypes.data_as(_u8p), width, height), "tsd_color_image")
         return img
+
+    def fuse_begin(self, members, offsets=None):
+        """tsd_fuse_begin: this grid becomes the TSD-level fusion of ``members`` (grids on the same GPU), member i shifted by
+        ``offsets[i]`` = (ox, oy) whole cells (None: all 0).  Returns once the fusion is enqueued."""
+        n = len(members)
+        hs = (C.c_void_p * max(n, 1))(*[m.h if m is not None else None for m in members])
+        off = None
+        if offsets is not None:
+            flat = [int(v) for o in offsets for v in o]
+            assert len(flat) == 2 * n
+            off = (C.c_int32 * max(2 * n, 1))(*flat)
+        self._check(self.lib.tsd_fuse_begin(self.h, n, hs, off), "tsd_fuse_begin")
+
+    def fuse_wait(self) -> dict:
+        """tsd_fuse_wait: blocks until the fusion begun last is done; its counters (tsd_fuse_stats)"""
+        st = FuseStats()
+        self._check(self.lib.tsd_fuse_wait(self.h, C.byref(st)), "tsd_fuse_wait")
+        return st.as_dict()
+
+    def fuse_from(self, members, offsets=None) -> dict:
+        """tsd_fuse: fuse_begin + fuse_wait"""
+        self.fuse_begin(members, offsets)
+        return self.fuse_wait()
 
     def _pinned(self, name, nbytes):
         """a page-locked host buffer kept by the wrapper (tsd_host_alloc), as a numpy view"""

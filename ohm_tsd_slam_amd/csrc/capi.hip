@@ -27,7 +27,7 @@ int set_error(tsd_ctx* ctx, int code, const char* what, hipError_t e)
   return code;
 }
 
-const char* const kKernelNames[] = {"push_classify", "push_update", "push_halo", "raycast", "icp", "occupancy", "tsdpdf"};
+const char* const kKernelNames[] = {"push_classify", "push_update", "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse"};
 
 bool kernel_is_timed(const tsd_ctx* ctx, const char* name)
 {
@@ -462,6 +462,8 @@ void tsd_destroy(tsd_ctx* ctx)
   for (tsd_batch* bt : ctx->batches) { if (bt->stream) hipStreamSynchronize(bt->stream); bt->ctx = nullptr; }
   for (tsd_sensor* sn : ctx->sensors) { if (sn->split.stream) hipStreamSynchronize(sn->split.stream); sn->ctx = nullptr; }
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
+  // (a fusion that reads this grid: the stream above has waited for it already; one that writes it ran on that stream)
+  if (ctx->ev_fuse_read) hipEventSynchronize(ctx->ev_fuse_read);
   drain_timers(ctx);
   GridDev& g = ctx->grid;
   hipFree(g.flags); hipFree(g.init_weight); hipFree(g.tsd); hipFree(g.weight); hipFree(g.negmask);
@@ -491,6 +493,9 @@ void tsd_destroy(tsd_ctx* ctx)
   if (ctx->h_frame_count) hipHostFree(ctx->h_frame_count);
   if (ctx->ev_frame) hipEventDestroy(ctx->ev_frame);
   if (ctx->ev_frame_done) hipEventDestroy(ctx->ev_frame_done);
+  if (ctx->d_fuse_stats) hipFree(ctx->d_fuse_stats);
+  if (ctx->h_fuse_stats) hipHostFree(ctx->h_fuse_stats);
+  for (hipEvent_t e : {ctx->ev_fuse_src, ctx->ev_fuse_src_push, ctx->ev_fuse_read}) if (e) hipEventDestroy(e);
   if (ctx->d_pdf) hipFree(ctx->d_pdf);
   if (ctx->h_pdf) hipHostFree(ctx->h_pdf);
   if (ctx->stream) hipStreamDestroy(ctx->stream);

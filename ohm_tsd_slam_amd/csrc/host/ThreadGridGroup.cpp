@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
+#include <vector>
 
 namespace ohm_tsd_slam
 {
@@ -57,6 +58,7 @@ ThreadGridGroup::ThreadGridGroup(const std::shared_ptr<rclcpp::Node>& node, cons
     if(ox < originX) originX = ox;
     if(oy < originY) originY = oy;
   }
+  _cellOff = off;
   _group = tsd_group_create(static_cast<int>(_members.size()), ctxs.data(), off.data(), 0, 0);
   if(!_group)
     throw std::invalid_argument("ThreadGridGroup: the device refused the group (one device, one cell size, at most 64 grids)");
@@ -148,6 +150,33 @@ int ThreadGridGroup::publish(void)
   }
   _gridPub->publish(msg);
   return TSD_OK;
+}
+
+int ThreadGridGroup::fuse(obvious::TsdGrid* dst)
+{
+  if(!dst || !dst->valid())
+    return TSD_E_ARG;
+  std::vector<tsd_ctx*> ctxs(_members.size());
+  for(size_t i = 0; i < _members.size(); i++)
+  {
+    if(_members[i].grid == dst)
+      return TSD_E_ARG;
+    ctxs[i] = _members[i].grid->context();
+  }
+  int rc;
+  {
+    // every grid involved, and only while the fusion is enqueued: the localisers go on while it runs
+    std::vector<std::unique_lock<std::mutex>> held;
+    held.reserve(_members.size() + 1);
+    for(size_t i = 0; i < _members.size(); i++)
+      held.emplace_back(_members[i].grid->mutex());
+    held.emplace_back(dst->mutex());
+    rc = tsd_fuse_begin(dst->context(), static_cast<int>(ctxs.size()), ctxs.data(), _cellOff.data());
+  }
+  if(rc != TSD_OK)
+    return rc;
+  std::lock_guard<std::mutex> g(dst->mutex());
+  return tsd_fuse_wait(dst->context(), nullptr);
 }
 
 bool ThreadGridGroup::getMapServCallBack(const std::shared_ptr<nav_msgs::srv::GetMap::Request>,

@@ -38,6 +38,13 @@ public:
   /** merged maps published so far */
   uint64_t frames(void);
 
+  /** TSD-level fusion of the members' grids into `dst` (tsd_fuse_*), on the caller's thread: `dst` lies where grid 0 lies and
+   *  member i is shifted by the whole-cell distance of its map origin from grid 0's, the offsets of the occupancy merge.  `dst`
+   *  (same cell size and truncation as the members, not one of them) is an ordinary grid afterwards.  The fusion must not run
+   *  beside a grid write of a member enqueued in between, so the mutexes of ALL grids involved are held while it is enqueued -- in
+   *  member order, then dst's; nothing else holds two grids -- and none of the members' while it runs.  TSD_OK or the error code. */
+  int fuse(obvious::TsdGrid* dst);
+
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }
   std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> mapService() { return _getMapServ; }
   bool getMapServCallBack(const std::shared_ptr<nav_msgs::srv::GetMap::Request> req,
@@ -50,6 +57,7 @@ private:
   std::shared_ptr<rclcpp::Node> _node;
   std::vector<Member> _members;
   tsd_group* _group;
+  std::vector<int32_t> _cellOff;   // (x, y) per member: whole cells from grid 0's map origin
   std::shared_ptr<nav_msgs::msg::OccupancyGrid> _occGrid;
   std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> _getMapServ;
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> _gridPub;

@@ -26,6 +26,7 @@ struct tsd_fleet
 {
   std::vector<tsd_node*> nodes;
   ThreadGridGroup* group = nullptr;
+  obvious::TsdGrid* fused = nullptr;      // the fleet's own grid: the TSD-level fusion of the nodes' grids (created by the first fusion)
 };
 
 struct tsd_node
@@ -456,7 +457,60 @@ void tsd_fleet_destroy(tsd_fleet* f)
     while(!f->group->alive(1)) {}
     delete f->group;
   }
+  delete f->fused;
   delete f;
+}
+
+// TSD-level fusion of the nodes' grids (ThreadGridGroup::fuse) into a grid the fleet owns: as large as node 0's and where node 0's
+// lies.  Returns its context (an ordinary grid: ray cast, localise, push, store, colour image), NULL on failure with the code in *rc.
+tsd_ctx* tsd_fleet_fuse_tsd(tsd_fleet* f, int* rc)
+{
+  int dummy;
+  if(!rc)
+    rc = &dummy;
+  *rc = TSD_E_ARG;
+  if(!f || !f->group || f->nodes.empty())
+    return nullptr;
+  obvious::TsdGrid* g0 = f->nodes[0]->grid;
+  if(!f->fused)
+  {
+    int log2 = 0;
+    while((1u << log2) < g0->getCellsX())
+      log2++;
+    f->fused = new obvious::TsdGrid(g0->getCellSize(), obvious::LAYOUT_32x32, static_cast<obvious::EnumTsdGridLayout>(log2),
+                                    tsd_device(g0->context()));
+    if(!f->fused->valid())
+    {
+      delete f->fused;
+      f->fused = nullptr;
+      *rc = TSD_E_NODEVICE;
+      return nullptr;
+    }
+  }
+  f->fused->setMaxTruncation(g0->getMaxTruncation());
+  *rc = f->group->fuse(f->fused);
+  return *rc == TSD_OK ? f->fused->context() : nullptr;
+}
+
+void tsd_fleet_fused_lock(tsd_fleet* f) { if(f && f->fused) f->fused->mutex().lock(); }
+void tsd_fleet_fused_unlock(tsd_fleet* f) { if(f && f->fused) f->fused->mutex().unlock(); }
+
+// the colour image of the fused grid as ThreadGrid would publish it (sensor_msgs/Image, rgb8, one pixel per cell): tsd_node_map_image_msg's
+// layout; data_out NULL: the sizes only.  TSD_OK or the error code (TSD_E_ARG before the first fusion).
+int tsd_fleet_fused_image_msg(tsd_fleet* f, uint8_t* data_out, double* out5, char* text, int cap)
+{
+  if(!f || !f->fused || !out5)
+    return TSD_E_ARG;
+  const unsigned int w = f->fused->getCellsX(), h = f->fused->getCellsY();
+  out5[0] = h; out5[1] = w; out5[2] = 3.0 * w; out5[3] = 0.0;
+  const builtin_interfaces::msg::Time now = f->nodes[0]->node->get_clock()->now();
+  out5[4] = (double)now.sec * 1e9 + (double)now.nanosec;
+  if(text && cap > 0)
+    std::snprintf(text, (size_t)cap, "%s|%s", sensor_msgs::image_encodings::RGB8.c_str(), "map");
+  if(!data_out)
+    return TSD_OK;
+  std::lock_guard<std::mutex> g(f->fused->mutex());
+  return tsd_color_image(f->fused->context(), data_out, w, h);
 }
 
 // one merge and publication now, on the caller's thread (what a wake-up of the worker does); TSD_OK or the error

@@ -286,6 +286,12 @@ struct tsd_ctx {
   hipEvent_t ev_frame = nullptr;                    // on `stream`: the frame's kernels are done
   hipEvent_t ev_frame_done = nullptr;               // on stream_io: the frame's copies to the host are done
   bool frame_inflight = false;
+  // TSD-level fusion (fuse.hip).  As the destination: the kernel's sharded counters and their pinned copy.  As a member: events of its
+  // own -- "every grid write enqueued so far" on its stream / its push stream, "the fusion that read this grid last is done" (recorded
+  // on the destination's stream; the member's streams wait for it at once) -- all created on first use
+  unsigned long long* d_fuse_stats = nullptr; unsigned long long* h_fuse_stats = nullptr;
+  bool fuse_begun = false;
+  hipEvent_t ev_fuse_src = nullptr, ev_fuse_src_push = nullptr, ev_fuse_read = nullptr;
 
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;

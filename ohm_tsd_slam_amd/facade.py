@@ -55,6 +55,10 @@ HOST_ABI = {
     "tsd_fleet_merged_frames": (C.c_ulonglong, [C.c_void_p]),
     "tsd_fleet_merged_map_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_fleet_get_merged_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
+    "tsd_fleet_fuse_tsd": (C.c_void_p, [C.c_void_p, _ip]),
+    "tsd_fleet_fused_lock": (None, [C.c_void_p]),
+    "tsd_fleet_fused_unlock": (None, [C.c_void_p]),
+    "tsd_fleet_fused_image_msg": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_host_sensor_ingest_f32": (None, [_fp, C.c_int, C.c_double, C.c_double, C.c_double, _dp, _u8p, C.c_int]),
     "tsd_host_sensor_chain": (None, [C.c_int, C.c_double, C.c_double, _dp, _dp, C.c_double, _fp, _dp, _dp, _dp,
                                      _dp, _u8p, _ip]),
@@ -331,6 +335,47 @@ class SlamFleet:
         if not ok:
             raise capi.TsdError("get_merged_map refused")
         return m
+
+    def fuse_tsd(self) -> "GridView":
+        """TSD-level fusion of the nodes' grids (``ThreadGridGroup::fuse``) into a grid the fleet owns -- as large as node 0's,
+        placed where node 0's lies, every other grid shifted by the whole-cell distance of its map origin.  The view is an
+        ordinary grid (ray cast, localise, push, store, colour image) and stays valid until the fleet is closed; every call
+        fuses anew."""
+        rc = C.c_int(0)
+        ctx = self.lib.tsd_fleet_fuse_tsd(self.h, C.byref(rc))
+        if not ctx:
+            raise capi.TsdError(f"tsd_fleet_fuse_tsd failed ({rc.value})")
+        return GridView(ctx, _FusedLock(self))
+
+    def fused_image_msg(self) -> dict:
+        """the colour image of the fused grid (after ``fuse_tsd``) as a sensor_msgs/Image: ``map_image_msg``'s fields"""
+        info = np.zeros(5)
+        text = C.create_string_buffer(256)
+        rc = self.lib.tsd_fleet_fused_image_msg(self.h, None, info.ctypes.data_as(_dp), text, 256)
+        if rc != 0:
+            raise capi.TsdError(f"tsd_fleet_fused_image_msg failed ({rc}): no fused grid yet?")
+        h, w, step = int(info[0]), int(info[1]), int(info[2])
+        data = np.zeros(step * h, dtype=np.uint8)
+        rc = self.lib.tsd_fleet_fused_image_msg(self.h, data.ctypes.data, info.ctypes.data_as(_dp), text, 256)
+        if rc != 0:
+            raise capi.TsdError(f"tsd_fleet_fused_image_msg failed ({rc})")
+        enc, frame = text.value.decode().split("|")
+        return {"height": h, "width": w, "step": step, "is_bigendian": int(info[3]), "stamp_ns": int(info[4]),
+                "encoding": enc, "frame_id": frame, "data": data.reshape(h, w, 3)}
+
+
+class _FusedLock:
+    """what GridView asks of a node, for the fleet's fused grid: its mutex"""
+
+    def __init__(self, fleet):
+        self.h = fleet.h
+        self.lib = _FusedLib(fleet.lib)
+
+
+class _FusedLib:
+    def __init__(self, lib):
+        self.tsd_node_grid_lock = lib.tsd_fleet_fused_lock
+        self.tsd_node_grid_unlock = lib.tsd_fleet_fused_unlock
 
 
 class GridView(capi.TsdGridDevice):
