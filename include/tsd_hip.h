@@ -442,6 +442,21 @@ typedef struct {
 } tsd_map_params;
 int tsd_map_frame_begin(tsd_ctx* ctx, const tsd_map_params* params, int8_t* occ_host, uint8_t* rgb_host);
 int tsd_map_frame_wait(tsd_ctx* ctx, int* n_surface);
+/* The same frame as a windowed update, the form rviz and nav2's static layer take on <map>_updates (map_msgs/OccupancyGridUpdate): only
+ * the rectangle that can differ from the context's previous frame or update is recomputed on the device and copied to the host.
+ * occ_host / rgb_host are the caller's FULL buffers (cells*cells, 3*cells*cells); the window's rows and columns alone are written
+ * into them, so a caller that passes the same buffers every time always holds the full current frame (what ThreadGrid.cpp:72-131
+ * rebuilds from scratch).  *win is that rectangle in cells; width == 0: nothing was pushed or freed since the previous frame, nothing
+ * is enqueued and wait returns at once.  The window is the whole map where no previous frame can be built on: the first call, a
+ * staging that was replaced (the image switched on), other inflation parameters than the previous frame's, inflate_factor > 31, a
+ * grid rewritten wholesale since (tsd_reset, tsd_upload_tiles, tsd_load_grid_text, tsd_set_max_truncation, a tsd_fuse destination),
+ * a previous frame that ended in an error.  tsd_map_frame_begin counts as the previous frame as well.  Ordering, the one frame in
+ * flight and the buffers' lifetime are tsd_map_frame_begin's; n_surface counts the marks made by this update's tiles only. */
+typedef struct {
+  int32_t x, y, width, height;  /* cells; width == 0: nothing changed */
+} tsd_map_window;
+int tsd_map_update_begin(tsd_ctx* ctx, const tsd_map_params* params, int8_t* occ_host, uint8_t* rgb_host, tsd_map_window* win);
+int tsd_map_update_wait(tsd_ctx* ctx, int* n_surface);
 /* page-locked host memory for the frame buffers (NULL on failure), and its release */
 void* tsd_host_alloc(uint64_t bytes);
 void tsd_host_free(void* p);

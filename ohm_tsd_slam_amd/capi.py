@@ -106,6 +106,14 @@ class MapParams(C.Structure):
     _fields_ = [("inflate", C.c_int32), ("inflate_factor", C.c_int32)]
 
 
+class MapWindow(C.Structure):
+    """tsd_map_window"""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
+
+    def as_tuple(self):
+        return (int(self.x), int(self.y), int(self.width), int(self.height))
+
+
 class FuseStats(C.Structure):
     """tsd_fuse_stats"""
     _fields_ = [("tiles_materialised", C.c_int64), ("tiles_empty", C.c_int64), ("cells_valid", C.c_int64),
@@ -233,6 +241,8 @@ ABI = {
     "tsd_color_image": (C.c_int, [C.c_void_p, _u8p, C.c_uint, C.c_uint]),
     "tsd_map_frame_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsd_map_frame_wait": (C.c_int, [C.c_void_p, _ip]),
+    "tsd_map_update_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsd_map_update_wait": (C.c_int, [C.c_void_p, _ip]),
     "tsd_host_alloc": (C.c_void_p, [C.c_uint64]),
     "tsd_host_free": (None, [C.c_void_p]),
     "tsd_store_grid_text": (C.c_int, [C.c_void_p, C.c_char_p]),
@@ -301,7 +311,7 @@ def load_library(path: str | None = None):
                           ("tsd_tsdpdf_params", TsdPdfParams), ("tsd_tsdpdf_result", TsdPdfResult),
                           ("tsd_pdfmatch_params", PdfMatchParams), ("tsd_rnmatch_params", RnMatchParams),
                           ("tsd_rnmatch_result", RnMatchResult), ("tsd_map_params", MapParams),
-                          ("tsd_fuse_stats", FuseStats)):
+                          ("tsd_fuse_stats", FuseStats), ("tsd_map_window", MapWindow)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -658,6 +668,43 @@ class TsdGridDevice:
         """ThreadGrid's publication in one frame (tsd_map_frame_begin + _wait): (occ, rgb or None, n_surface)"""
         self.map_frame_begin(inflate, factor, image)
         return self.map_frame_wait()
+
+    def map_update_begin(self, inflate=False, factor=2, image=True, occ=None, rgb=None):
+        """tsd_map_update_begin: the windowed form of map_frame_begin.  Returns the window (x, y, width, height) in cells once the
+        update is enqueued; width 0: nothing changed.  The window's rows and columns are written into the wrapper's pinned buffers --
+        the ones map_frame uses, so they always hold the full current frame -- or into ``occ`` (cells, cells) int8 / ``rgb``
+        (cells, cells, 3) uint8 where the caller hands in full C-contiguous buffers of its own (which must live until the wait)."""
+        n = self.cells * self.cells
+        prm = MapParams(int(bool(inflate)), int(factor))
+        if occ is None:
+            occ = self._pinned("occ", n)
+            rgb = self._pinned("rgb", 3 * n) if image else None
+        else:
+            assert occ.dtype == np.int8 and occ.size == n and occ.flags.c_contiguous
+            assert not image or (rgb is not None and rgb.dtype == np.uint8 and rgb.size == 3 * n and rgb.flags.c_contiguous)
+            rgb = rgb if image else None
+        win = MapWindow()
+        self._check(self.lib.tsd_map_update_begin(self.h, C.byref(prm), occ.ctypes.data, None if rgb is None else rgb.ctypes.data,
+                                                  C.byref(win)), "tsd_map_update_begin")
+        self._update_bufs = (occ, rgb)           # (kept alive until the wait)
+        return win.as_tuple()
+
+    def map_update_wait(self):
+        """tsd_map_update_wait: (occ, rgb or None, n_surface) -- copies of the full buffers the update was written into, n_surface
+        the marks made by the update's tiles"""
+        ns = C.c_int(0)
+        self._check(self.lib.tsd_map_update_wait(self.h, C.byref(ns)), "tsd_map_update_wait")
+        occ, rgb = self._update_bufs
+        self._update_bufs = None
+        occ = occ.view(np.int8).reshape(self.cells, self.cells).copy()
+        rgb = None if rgb is None else rgb.reshape(self.cells, self.cells, 3).copy()
+        return occ, rgb, ns.value
+
+    def map_update(self, inflate=False, factor=2, image=True, occ=None, rgb=None):
+        """tsd_map_update_begin + _wait: (window, occ, rgb or None, n_surface)"""
+        win = self.map_update_begin(inflate, factor, image, occ, rgb)
+        o, r, ns = self.map_update_wait()
+        return win, o, r, ns
 
     def push_stats_total(self, reset=False):
         st = PushStats()

@@ -521,6 +521,7 @@ int tsd_reset(tsd_ctx* ctx)
   TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_tile_totals, 0, T * 8 * sizeof(uint32_t), ctx->stream));
   TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_pushes, 0, 2 * sizeof(unsigned long long), ctx->stream));
   ctx->box_prev = TileBox{}; ctx->box_dirty = TileBox{};
+  ctx->frame_prev_valid = false;          // (the next tsd_map_update_begin takes a full frame)
   TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_list_cnt, 0, push_list_cnt_bytes(), ctx->stream));
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return TSD_OK;
@@ -533,6 +534,7 @@ int tsd_set_max_truncation(tsd_ctx* ctx, double val)
   // TsdGrid::setMaxTruncation (TsdGrid.cpp:206-215): at least 2 x cell size
   if (val < 2 * ctx->grid.cs) val = 2 * ctx->grid.cs;
   ctx->grid.max_trunc = val;
+  ctx->frame_prev_valid = false;          // (the next tsd_map_update_begin takes a full frame)
   return TSD_OK;
 }
 

@@ -101,6 +101,7 @@ int tsd_upload_tiles(tsd_ctx* ctx, const uint8_t* initialized, const double* ini
   {
     TileBox all; all.x0 = 0; all.y0 = 0; all.x1 = g.PX - 1; all.y1 = g.PX - 1;
     ctx->box_dirty.add(all);
+    ctx->frame_prev_valid = false;        // (the next tsd_map_update_begin takes a full frame)
   }
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return TSD_OK;
@@ -145,6 +146,7 @@ int tsd_abi_sizeof(const char* n)
   TSD_SZ(tsd_push_stats); TSD_SZ(tsd_icp_params); TSD_SZ(tsd_icp_result); TSD_SZ(tsd_gate_params); TSD_SZ(tsd_scan_result);
   TSD_SZ(tsd_grid_digest_t); TSD_SZ(tsd_tsdpdf_params); TSD_SZ(tsd_tsdpdf_result);
   TSD_SZ(tsd_pdfmatch_params); TSD_SZ(tsd_rnmatch_params); TSD_SZ(tsd_rnmatch_result); TSD_SZ(tsd_map_params); TSD_SZ(tsd_fuse_stats);
+  TSD_SZ(tsd_map_window);
 #undef TSD_SZ
   return 0;
 }

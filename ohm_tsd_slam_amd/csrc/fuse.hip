@@ -274,6 +274,7 @@ int tsd_fuse_begin(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell
   TSD_HIP_CHECK(dst, hipMemsetAsync(dst->d_pushes, 0, 2 * sizeof(unsigned long long), dst->stream));
   TSD_HIP_CHECK(dst, hipMemsetAsync(dst->d_list_cnt, 0, push_list_cnt_bytes(), dst->stream));
   dst->box_prev = TileBox{}; dst->box_dirty = TileBox{};
+  dst->frame_prev_valid = false;          // (the next tsd_map_update_begin takes a full frame)
   TSD_HIP_CHECK(dst, hipMemsetAsync(dst->d_fuse_stats, 0, kFuseStatBytes, dst->stream));
   if (int rc = launch_fuse(dst, a)) return rc;
   for (int i = 0; i < n; i++) {

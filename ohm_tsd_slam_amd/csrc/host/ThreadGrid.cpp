@@ -15,7 +15,8 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
     _cellSize(grid->getCellSize()),
     _hOcc(nullptr),
     _hRgb(nullptr),
-    _frames(0)
+    _frames(0),
+    _updates(0)
 {
   // (ThreadGrid.cpp:16-40)
   _occGrid->info.resolution           = static_cast<double>(_grid.getCellSize());
@@ -37,9 +38,21 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
   _objectInflation = node->get_parameter("use_object_inflation").as_bool();
   _objInflateFactor = static_cast<unsigned int>(node->get_parameter("object_inflation_factor").as_int());
 
+  // not in the reference: declared here, with the worker it belongs to (a launch file's or YAML's value is kept)
+#if OHM_TSD_SLAM_HAVE_ROS
+  if(!node->has_parameter("publish_map_updates"))
+    node->declare_parameter<bool>("publish_map_updates", false);
+#else
+  node->declare_parameter("publish_map_updates", false);
+#endif
+  _publishUpdates = node->get_parameter("publish_map_updates").as_bool();
+
   const std::string node_name = _node->get_name();
   _gridPub = node->create_publisher<nav_msgs::msg::OccupancyGrid>(node_name + "/map", rclcpp::QoS(1).reliable().transient_local());
   _pubColorImage = node->create_publisher<sensor_msgs::msg::Image>(node_name + "/map/image", rclcpp::QoS(1).best_effort());
+  if(_publishUpdates)
+    _updatePub = node->create_publisher<map_msgs::msg::OccupancyGridUpdate>(node_name + "/map_updates",
+                                                                            rclcpp::QoS(10).reliable().durability_volatile());
   _getMapServ = node->create_service<nav_msgs::srv::GetMap>(
     node_name + "/get_map",
     std::bind(&ThreadGrid::getMapServCallBack, this, std::placeholders::_1, std::placeholders::_2));
@@ -64,6 +77,18 @@ uint64_t ThreadGrid::frames(void)
 {
   std::lock_guard<std::mutex> lk(_msgMutex);
   return _frames;
+}
+
+uint64_t ThreadGrid::updates(void)
+{
+  std::lock_guard<std::mutex> lk(_msgMutex);
+  return _updates;
+}
+
+map_msgs::msg::OccupancyGridUpdate ThreadGrid::lastUpdate(void)
+{
+  std::lock_guard<std::mutex> lk(_msgMutex);
+  return _lastUpdate;
 }
 
 void ThreadGrid::eventLoop(void)
@@ -92,18 +117,23 @@ int ThreadGrid::publish(void)
   tsd_map_params prm;
   prm.inflate = _objectInflation ? 1 : 0;
   prm.inflate_factor = static_cast<int32_t>(_objInflateFactor);
+  tsd_map_window win = {0, 0, 0, 0};
   int rc;
   {
     // the grid's mutex only while the frame is enqueued: the localisers go on while it is computed and copied
     std::lock_guard<std::mutex> g(_grid.mutex());
-    rc = tsd_map_frame_begin(ctx, &prm, _hOcc, _hRgb);
+    rc = _publishUpdates ? tsd_map_update_begin(ctx, &prm, _hOcc, _hRgb, &win) : tsd_map_frame_begin(ctx, &prm, _hOcc, _hRgb);
   }
   if(rc != TSD_OK)
     return rc;
-  int mapSize2 = 0;          // calcCoords' mapSize / 2
-  rc = tsd_map_frame_wait(ctx, &mapSize2);
+  int mapSize2 = 0;          // calcCoords' mapSize / 2 (of an update: of the window's tiles)
+  rc = _publishUpdates ? tsd_map_update_wait(ctx, &mapSize2) : tsd_map_frame_wait(ctx, &mapSize2);
   if(rc != TSD_OK)
     return rc;
+  if(_publishUpdates && win.width == 0)      // nothing was pushed since the last publication
+    return TSD_OK;
+  if(_publishUpdates && !((size_t)win.width == _width && (size_t)win.height == _height))
+    return publishUpdate(win);
   if(mapSize2 == 0)
   {
 #if OHM_TSD_SLAM_HAVE_ROS
@@ -128,6 +158,43 @@ int ThreadGrid::publish(void)
   _image.width = msg.info.width;
   _image.encoding = sensor_msgs::image_encodings::RGB8;
   std::memcpy(_image.data.data(), _hRgb, 3 * cells);
+  _pubColorImage->publish(_image);
+  return TSD_OK;
+}
+
+// a windowed frame: _hOcc / _hRgb hold the full current frame, of which the window's rows are new
+int ThreadGrid::publishUpdate(const tsd_map_window& win)
+{
+  map_msgs::msg::OccupancyGridUpdate upd;
+  upd.x = win.x;
+  upd.y = win.y;
+  upd.width = static_cast<uint32_t>(win.width);
+  upd.height = static_cast<uint32_t>(win.height);
+  upd.data.resize((size_t)win.width * win.height);
+  {
+    std::lock_guard<std::mutex> m(_msgMutex);
+    _occGrid->header.stamp = _node->get_clock()->now();
+    upd.header = _occGrid->header;
+    for(int32_t r = 0; r < win.height; r++)
+    {
+      const size_t o = (size_t)(win.y + r) * _width + (size_t)win.x;
+      std::memcpy(_occGrid->data.data() + o, _hOcc + o, (size_t)win.width);
+      std::memcpy(upd.data.data() + (size_t)r * win.width, _hOcc + o, (size_t)win.width);
+    }
+    _lastUpdate = upd;
+    _updates++;
+  }
+  _updatePub->publish(upd);
+  // the image stays a full message (ThreadGrid.cpp:120-131), patched by the window's rows
+  _image.header.stamp = upd.header.stamp;
+  _image.height = _height;
+  _image.width = _width;
+  _image.encoding = sensor_msgs::image_encodings::RGB8;
+  for(int32_t r = 0; r < win.height; r++)
+  {
+    const size_t o = 3 * ((size_t)(win.y + r) * _width + (size_t)win.x);
+    std::memcpy(_image.data.data() + o, _hRgb + o, 3 * (size_t)win.width);
+  }
   _pubColorImage->publish(_image);
   return TSD_OK;
 }

@@ -1,6 +1,9 @@
 // ThreadGrid.h -- the occupancy-grid worker; public surface of the reference's ThreadGrid (src/ThreadGrid.h:24-129,
 // src/ThreadGrid.cpp).  Every wake-up publishes one frame of the device (tsd_map_frame_begin / _wait: the occupancy map and the
 // colour image from one pass over the tiles) on <node>/map and <node>/map/image; <node>/get_map answers with the last map.
+// With the parameter publish_map_updates (not in the reference; default false) only the first publication, and every one the device
+// cannot take as a window, is a full map: the others are windowed frames (tsd_map_update_begin / _wait) published as
+// map_msgs/OccupancyGridUpdate on <node>/map_updates, the form rviz and nav2's static layer listen for.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -23,9 +26,15 @@ public:
   int publish(void);
   /** frames published so far */
   uint64_t frames(void);
+  /** update messages published so far (publish_map_updates) */
+  uint64_t updates(void);
 
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }
   std::shared_ptr<rclcpp::Publisher<sensor_msgs::msg::Image>> imagePublisher() { return _pubColorImage; }
+  /** <node>/map_updates; nullptr unless publish_map_updates is set */
+  std::shared_ptr<rclcpp::Publisher<map_msgs::msg::OccupancyGridUpdate>> updatePublisher() { return _updatePub; }
+  /** the last update message (width 0 before the first one) */
+  map_msgs::msg::OccupancyGridUpdate lastUpdate(void);
   std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> mapService() { return _getMapServ; }
 
   /** the get_map service (ThreadGrid.cpp:135-142): the last map with a fresh stamp */
@@ -36,12 +45,18 @@ protected:
   virtual void eventLoop(void);
 
 private:
+  int publishUpdate(const tsd_map_window& win);
+
+private:
   std::shared_ptr<rclcpp::Node> _node;
   std::shared_ptr<nav_msgs::msg::OccupancyGrid> _occGrid;
   sensor_msgs::msg::Image _image;
   std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> _getMapServ;
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> _gridPub;
   std::shared_ptr<rclcpp::Publisher<sensor_msgs::msg::Image>> _pubColorImage;
+  std::shared_ptr<rclcpp::Publisher<map_msgs::msg::OccupancyGridUpdate>> _updatePub;
+  map_msgs::msg::OccupancyGridUpdate _lastUpdate;     // (kept here: a real publisher does not keep its messages)
+  bool _publishUpdates;
   unsigned int _width;
   unsigned int _height;
   double _cellSize;
@@ -53,6 +68,7 @@ private:
   std::mutex _publishMutex;      // one publication at a time (event loop, publish())
   std::mutex _msgMutex;          // _occGrid between a publication and the get_map service
   uint64_t _frames;
+  uint64_t _updates;
 };
 
 } /* namespace ohm_tsd_slam */

@@ -365,6 +365,24 @@ int tsd_node_publish_map(tsd_node* n)
 
 unsigned long long tsd_node_map_frames(tsd_node* n) { return (n && n->gridThread) ? n->gridThread->frames() : 0; }
 
+unsigned long long tsd_node_map_updates(tsd_node* n) { return (n && n->gridThread) ? n->gridThread->updates() : 0; }
+
+// last message on <node>/map_updates: x, y, width, height, stamp [ns] (5 doubles); data (width * height) when data_out is given;
+// header.frame_id into frame_id.  Returns the number of update messages so far.
+unsigned long long tsd_node_map_update_msg(tsd_node* n, int8_t* data_out, double* out5, char* frame_id, int cap)
+{
+  if(!n || !n->gridThread || !out5)
+    return 0;
+  const map_msgs::msg::OccupancyGridUpdate m = n->gridThread->lastUpdate();
+  out5[0] = m.x; out5[1] = m.y; out5[2] = m.width; out5[3] = m.height;
+  out5[4] = (double)m.header.stamp.sec * 1e9 + (double)m.header.stamp.nanosec;
+  if(data_out && !m.data.empty())
+    std::memcpy(data_out, m.data.data(), m.data.size());
+  if(frame_id && cap > 0)
+    std::snprintf(frame_id, (size_t)cap, "%s", m.header.frame_id.c_str());
+  return n->gridThread->updates();
+}
+
 // an OccupancyGrid as flat values: resolution, width, height, origin x, y, z, qx, qy, qz, qw, stamp [ns], map_load_time [ns]
 // (12 doubles); data (width * height) when data_out is given; header.frame_id into frame_id
 static void map_out(const nav_msgs::msg::OccupancyGrid& m, int8_t* data_out, double* out12, char* frame_id, int cap)

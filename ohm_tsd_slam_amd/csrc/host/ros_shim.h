@@ -21,6 +21,7 @@
 #include <nav_msgs/srv/get_map.hpp>
 #include <sensor_msgs/msg/image.hpp>
 #include <sensor_msgs/image_encodings.hpp>
+#include <map_msgs/msg/occupancy_grid_update.hpp>
 #else
 #define OHM_TSD_SLAM_HAVE_ROS 0
 #include <chrono>
@@ -76,6 +77,10 @@ struct GetMap {
   struct Response { nav_msgs::msg::OccupancyGrid map; };
 };
 } }
+// the incremental form of the map on <map>_updates (map_msgs/OccupancyGridUpdate): a rectangle of cells, row-major
+namespace map_msgs { namespace msg {
+struct OccupancyGridUpdate { std_msgs::msg::Header header; int32_t x = 0, y = 0; uint32_t width = 0, height = 0; std::vector<int8_t> data; };
+} }
 namespace sensor_msgs { namespace msg {
 struct Image {
   std_msgs::msg::Header header;
@@ -97,6 +102,7 @@ struct QoS {
   QoS& reliable() { return *this; }
   QoS& best_effort() { return *this; }
   QoS& transient_local() { return *this; }
+  QoS& durability_volatile() { return *this; }
 };
 
 // a service keeps its callback; call() is what a client's request does

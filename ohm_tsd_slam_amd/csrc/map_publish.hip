@@ -23,12 +23,14 @@ struct FrameTables {
   unsigned width, height;
 };
 
+// one workgroup's part of a frame: tile p's cells and, with kImage, the image dwords it owns
 template <bool kImage>
-__global__ void __launch_bounds__(256)
-k_map_frame(GridDev g, int8_t* __restrict__ content, int8_t* __restrict__ out, unsigned int* __restrict__ heads, uint32_t* __restrict__ list,
-            unsigned int* __restrict__ heads_next, int* __restrict__ count, FrameTables tab, uint8_t* __restrict__ image)
+__device__ __forceinline__ void map_frame_tile(const GridDev& g, int p, int8_t* __restrict__ content, int8_t* __restrict__ out,
+                                               unsigned int* __restrict__ heads, uint32_t* __restrict__ list,
+                                               unsigned int* __restrict__ heads_next, int* __restrict__ count, const FrameTables& tab,
+                                               uint8_t* __restrict__ image)
 {
-  const int p = blockIdx.x, PX = g.PX;
+  const int PX = g.PX;
   const int X = p % PX, Y = p / PX;
   const bool own_init = g.flags[p] != 0;
   const int lx0 = (threadIdx.x & 7) * 4, ly = threadIdx.x >> 3;
@@ -71,7 +73,51 @@ k_map_frame(GridDev g, int8_t* __restrict__ content, int8_t* __restrict__ out, u
       img4[(size_t)h * row_dw + d] = word;
     }
   }
-  occ_cells_tile(g, content, out, heads, list, heads_next, count, [&](const tsd_cell_t*) { return occ_bits4(t0, t1, t2, t3); });
+  occ_cells_tile(g, p, content, out, heads, list, heads_next, count, [&](const tsd_cell_t*) { return occ_bits4(t0, t1, t2, t3); });
+}
+
+template <bool kImage>
+__global__ void __launch_bounds__(256)
+k_map_frame(GridDev g, int8_t* __restrict__ content, int8_t* __restrict__ out, unsigned int* __restrict__ heads, uint32_t* __restrict__ list,
+            unsigned int* __restrict__ heads_next, int* __restrict__ count, FrameTables tab, uint8_t* __restrict__ image)
+{
+  map_frame_tile<kImage>(g, (int)blockIdx.x, content, out, heads, list, heads_next, count, tab, image);
+}
+
+// The windowed frame (tsd_map_update_begin).  u: the tiles that may differ from the previous frame, grown by the reach of a mark
+// (window_growth); m: u grown by that reach again.  One workgroup per tile of m.  A tile of u is redone as k_map_frame does it: the
+// persistent map and the staged map of its cells are rewritten -- which also erases every mark a changed tile can have left there --
+// and so are its image dwords.  Every processed, initialised tile of m goes on k_occ_mark's list: the marks of u's own tiles, and
+// those that the tiles around u drop into it, are made again; what such a tile marks outside u is there already (marks are
+// idempotent).  The staged map then equals a full frame's byte for byte.
+struct FrameWindow { int ux0, uy0, ux1, uy1, mx0, my0, mnx; };
+
+template <bool kImage>
+__global__ void __launch_bounds__(256)
+k_map_frame_window(GridDev g, int8_t* __restrict__ content, int8_t* __restrict__ out, unsigned int* __restrict__ heads,
+                   uint32_t* __restrict__ list, unsigned int* __restrict__ heads_next, int* __restrict__ count, FrameTables tab,
+                   uint8_t* __restrict__ image, FrameWindow w)
+{
+  const int X = w.mx0 + (int)blockIdx.x % w.mnx, Y = w.my0 + (int)blockIdx.x / w.mnx;
+  const int p = Y * g.PX + X;
+  if (X >= w.ux0 && X <= w.ux1 && Y >= w.uy0 && Y <= w.uy1) {
+    map_frame_tile<kImage>(g, p, content, out, heads, list, heads_next, count, tab, image);
+    return;
+  }
+  occ_launch_clear(heads_next, count);
+  if (threadIdx.x == 0 && tile_processed(X, Y, g.PX) && g.flags[p] != 0) occ_list_tile(g, p, heads, list);
+}
+
+// tiles a mark can land away from the tile that makes it: factor + 1 cells with inflation (the mark's cell is at most one past the
+// tile's 32, the square reaches `factor` further), one cell without
+static int window_growth(int inflate, int factor) { return inflate ? (factor + 1 + TILE_DIM - 1) / TILE_DIM : 1; }
+
+static TileBox grow_box(const TileBox& b, int by, int PX)
+{
+  TileBox r;
+  r.x0 = std::max(0, b.x0 - by); r.y0 = std::max(0, b.y0 - by);
+  r.x1 = std::min(PX - 1, b.x1 + by); r.y1 = std::min(PX - 1, b.y1 + by);
+  return r;
 }
 
 // one axis of coord2Cell on the host (tsd_device.hpp): the cell index, < 0 or >= N where it fails
@@ -102,6 +148,7 @@ static int ensure_frame_staging(tsd_ctx* ctx, bool image)
   // (a frame's staging is only replaced between frames: the last one's copies are done, tsd_map_frame_wait has seen them)
   if (ctx->d_frame) hipFree(ctx->d_frame);
   ctx->d_frame = nullptr; ctx->frame_bytes = 0;
+  ctx->frame_prev_valid = false;          // (a windowed frame has nothing to build on)
   TSD_HIP_CHECK(ctx, hipMalloc(&ctx->d_frame, need));
   // px / py exactly as the reference accumulates them (TsdGrid.cpp:433-486), then the tile ranges of the monotone tables
   std::vector<char> h(tab_bytes - 256);
@@ -128,23 +175,30 @@ static int ensure_frame_staging(tsd_ctx* ctx, bool image)
   return TSD_OK;
 }
 
-}  // namespace tsd
-
-using namespace tsd;
-
-extern "C" {
-
-int tsd_map_frame_begin(tsd_ctx* ctx, const tsd_map_params* prm, int8_t* occ_host, uint8_t* rgb_host)
+// tsd_map_frame_begin (win == nullptr) and tsd_map_update_begin: the whole map, or -- where the staging holds the previous frame of the
+// same parameters and the grid was not rewritten wholesale since -- the window around ctx->box_frame
+static int frame_begin(tsd_ctx* ctx, const tsd_map_params* prm, int8_t* occ_host, uint8_t* rgb_host, tsd_map_window* win, const char* who)
 {
   if (!ctx || !prm || !occ_host) return TSD_E_ARG;
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (ctx->frame_inflight) return set_error(ctx, TSD_E_ARG, "tsd_map_frame_begin: a frame is in flight (tsd_map_frame_wait first)", hipSuccess);
+  if (ctx->frame_inflight) return set_error(ctx, TSD_E_ARG, (std::string(who) + ": a frame is in flight (tsd_map_frame_wait first)").c_str(), hipSuccess);
   if (int rcd_ = drain_async_push(ctx)) return rcd_;
   std::lock_guard<std::mutex> lk_order(ctx->order_mutex);
   const bool image = rgb_host != nullptr;
   if (int rc = ensure_frame_staging(ctx, image)) return rc;
   const GridDev& g = ctx->grid;
   const size_t N = (size_t)g.N, PX = (size_t)g.PX, cells = N * N;
+  const int inflate = prm->inflate ? 1 : 0, factor = prm->inflate_factor;
+  // (with factor > 31 a mark at u + factor > N spills into the next row, far from any window: DESIGN 3.4)
+  const bool windowed = win && ctx->frame_prev_valid && (!image || ctx->frame_prev_image) && ctx->frame_prev_inflate == inflate &&
+                        (!inflate || (ctx->frame_prev_factor == factor && factor >= 0 && factor <= 31));
+  if (windowed && ctx->box_frame.empty()) {
+    win->x = win->y = win->width = win->height = 0;
+    *ctx->h_frame_count = 0;
+    ctx->frame_empty = true; ctx->frame_inflight = true;
+    return TSD_OK;
+  }
+  ctx->frame_prev_valid = false;            // (until this one is enqueued completely)
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t tab_bytes = up(256 + 2 * N * sizeof(double) + 2 * (PX + 1) * sizeof(int));
   int* d_count = reinterpret_cast<int*>(ctx->d_frame);
@@ -159,35 +213,94 @@ int tsd_map_frame_begin(tsd_ctx* ctx, const tsd_map_params* prm, int8_t* occ_hos
   // every push enqueued before this call is ahead of the frame on the grid's stream: the fused scan's deferred halo pass runs in the ray
   // cast that the same tsd_scan_submit enqueues behind its push, the batched push enqueues its own, an asynchronous push was drained above
   const OccHeads hd = next_occ_heads(ctx);
-  if (image)
-    hipLaunchKernelGGL(k_map_frame<true>, dim3(g.tiles), dim3(256), 0, ctx->stream, g, ctx->d_occ, d_occ, hd.cur, ctx->d_occ_list,
-                       hd.next, d_count, tab, d_img);
-  else
-    hipLaunchKernelGGL(k_map_frame<false>, dim3(g.tiles), dim3(256), 0, ctx->stream, g, ctx->d_occ, d_occ, hd.cur, ctx->d_occ_list,
-                       hd.next, d_count, tab, nullptr);
-  TSD_HIP_CHECK(ctx, hipGetLastError());
-  if (int rc = launch_occ_mark(ctx, d_occ, d_count, prm->inflate, prm->inflate_factor, hd.cur)) return rc;
+  TileBox u; u.x0 = 0; u.y0 = 0; u.x1 = (int)PX - 1; u.y1 = (int)PX - 1;
+  if (windowed) {
+    const int grow = window_growth(inflate, factor);
+    u = grow_box(ctx->box_frame, grow, (int)PX);
+    const TileBox m = grow_box(u, grow, (int)PX);
+    const FrameWindow fw{u.x0, u.y0, u.x1, u.y1, m.x0, m.y0, m.x1 - m.x0 + 1};
+    const int n_m = fw.mnx * (m.y1 - m.y0 + 1);
+    if (image)
+      hipLaunchKernelGGL(k_map_frame_window<true>, dim3(n_m), dim3(256), 0, ctx->stream, g, ctx->d_occ, d_occ, hd.cur, ctx->d_occ_list,
+                         hd.next, d_count, tab, d_img, fw);
+    else
+      hipLaunchKernelGGL(k_map_frame_window<false>, dim3(n_m), dim3(256), 0, ctx->stream, g, ctx->d_occ, d_occ, hd.cur, ctx->d_occ_list,
+                         hd.next, d_count, tab, nullptr, fw);
+    TSD_HIP_CHECK(ctx, hipGetLastError());
+    if (int rc = launch_occ_mark(ctx, d_occ, d_count, inflate, factor, hd.cur, n_m)) return rc;
+  } else {
+    if (image)
+      hipLaunchKernelGGL(k_map_frame<true>, dim3(g.tiles), dim3(256), 0, ctx->stream, g, ctx->d_occ, d_occ, hd.cur, ctx->d_occ_list,
+                         hd.next, d_count, tab, d_img);
+    else
+      hipLaunchKernelGGL(k_map_frame<false>, dim3(g.tiles), dim3(256), 0, ctx->stream, g, ctx->d_occ, d_occ, hd.cur, ctx->d_occ_list,
+                         hd.next, d_count, tab, nullptr);
+    TSD_HIP_CHECK(ctx, hipGetLastError());
+    if (int rc = launch_occ_mark(ctx, d_occ, d_count, prm->inflate, prm->inflate_factor, hd.cur)) return rc;
+  }
   // The copies leave on stream_io behind the kernels' event: the grid's stream goes on with the next scans at once.
   TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_frame, ctx->stream));
   TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream_io, ctx->ev_frame, 0));
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_frame_count, d_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream_io));
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(occ_host, d_occ, cells, hipMemcpyDeviceToHost, ctx->stream_io));
-  if (image) TSD_HIP_CHECK(ctx, hipMemcpyAsync(rgb_host, d_img, 3 * cells, hipMemcpyDeviceToHost, ctx->stream_io));
+  if (windowed) {
+    // The window's rows and columns only.  Pixel and cell grids coincide up to one pixel at a tile border (the pixel coordinates are
+    // accumulated), and the tiles that changed lie a whole tile inside u wherever u was not clipped by the grid's edge: the pixels of
+    // u's cell rectangle hold every pixel that can differ.  Its rows start on a dword (32 cells = 96 bytes).
+    const size_t x = (size_t)u.x0 * TILE_DIM, y = (size_t)u.y0 * TILE_DIM;
+    const size_t w = (size_t)(u.x1 - u.x0 + 1) * TILE_DIM, h = (size_t)(u.y1 - u.y0 + 1) * TILE_DIM;
+    const size_t o = y * N + x;
+    TSD_HIP_CHECK(ctx, hipMemcpy2DAsync(occ_host + o, N, d_occ + o, N, w, h, hipMemcpyDeviceToHost, ctx->stream_io));
+    if (image) TSD_HIP_CHECK(ctx, hipMemcpy2DAsync(rgb_host + 3 * o, 3 * N, d_img + 3 * o, 3 * N, 3 * w, h, hipMemcpyDeviceToHost, ctx->stream_io));
+  } else {
+    TSD_HIP_CHECK(ctx, hipMemcpyAsync(occ_host, d_occ, cells, hipMemcpyDeviceToHost, ctx->stream_io));
+    if (image) TSD_HIP_CHECK(ctx, hipMemcpyAsync(rgb_host, d_img, 3 * cells, hipMemcpyDeviceToHost, ctx->stream_io));
+  }
   TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_frame_done, ctx->stream_io));
-  ctx->frame_inflight = true;
+  if (win) {
+    win->x = u.x0 * TILE_DIM; win->y = u.y0 * TILE_DIM;
+    win->width = (u.x1 - u.x0 + 1) * TILE_DIM; win->height = (u.y1 - u.y0 + 1) * TILE_DIM;
+  }
+  ctx->box_frame = TileBox{};
+  ctx->frame_prev_valid = true; ctx->frame_prev_image = image;
+  ctx->frame_prev_inflate = inflate; ctx->frame_prev_factor = factor;
+  ctx->frame_empty = false; ctx->frame_inflight = true;
   return TSD_OK;
 }
 
-int tsd_map_frame_wait(tsd_ctx* ctx, int* n_surface)
+static int frame_wait(tsd_ctx* ctx, int* n_surface, const char* who)
 {
   if (!ctx) return TSD_E_ARG;
-  if (!ctx->frame_inflight) return set_error(ctx, TSD_E_ARG, "tsd_map_frame_wait: no frame in flight", hipSuccess);
-  const hipError_t e = hipEventSynchronize(ctx->ev_frame_done);
+  if (!ctx->frame_inflight) return set_error(ctx, TSD_E_ARG, (std::string(who) + ": no frame in flight").c_str(), hipSuccess);
   ctx->frame_inflight = false;
-  if (e != hipSuccess) return set_error(ctx, TSD_E_HIP, "tsd_map_frame_wait", e);
+  if (!ctx->frame_empty) {
+    const hipError_t e = hipEventSynchronize(ctx->ev_frame_done);
+    if (e != hipSuccess) { ctx->frame_prev_valid = false; return set_error(ctx, TSD_E_HIP, who, e); }
+  }
+  ctx->frame_empty = false;
   if (n_surface) *n_surface = *ctx->h_frame_count;
   return TSD_OK;
 }
+
+}  // namespace tsd
+
+using namespace tsd;
+
+extern "C" {
+
+int tsd_map_frame_begin(tsd_ctx* ctx, const tsd_map_params* prm, int8_t* occ_host, uint8_t* rgb_host)
+{
+  return frame_begin(ctx, prm, occ_host, rgb_host, nullptr, "tsd_map_frame_begin");
+}
+
+int tsd_map_frame_wait(tsd_ctx* ctx, int* n_surface) { return frame_wait(ctx, n_surface, "tsd_map_frame_wait"); }
+
+int tsd_map_update_begin(tsd_ctx* ctx, const tsd_map_params* prm, int8_t* occ_host, uint8_t* rgb_host, tsd_map_window* win)
+{
+  if (!win) return TSD_E_ARG;
+  return frame_begin(ctx, prm, occ_host, rgb_host, win, "tsd_map_update_begin");
+}
+
+int tsd_map_update_wait(tsd_ctx* ctx, int* n_surface) { return frame_wait(ctx, n_surface, "tsd_map_update_wait"); }
 
 void* tsd_host_alloc(uint64_t bytes)
 {

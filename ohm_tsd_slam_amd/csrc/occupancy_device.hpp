@@ -1,5 +1,5 @@
 // occupancy_device.hpp -- the per-tile rules of ThreadGrid's two outputs, shared by the extraction kernels of occupancy_kernels.hip
-// (k_occ_cells, k_color_image) and the one-pass publication of map_publish.hip (k_map_frame).
+// (k_occ_cells, k_color_image) and the one-pass publication of map_publish.hip (k_map_frame, k_map_frame_window).
 #pragma once
 #include "tsd_ctx.hpp"
 
@@ -28,21 +28,33 @@ __device__ __forceinline__ uint32_t occ_bits4(double t0, double t1, double t2, d
   return (t0 > 0.0 ? 0u : 0xFFu) | (t1 > 0.0 ? 0u : 0xFF00u) | (t2 > 0.0 ? 0u : 0xFF0000u) | (t3 > 0.0 ? 0u : 0xFF000000u);
 }
 
-// k_occ_cells for workgroup p = tile p, one lane per 4 consecutive cells of a row (256 lanes): the map is read and written 4 bytes per
-// lane (16-byte aligned rows).  A tile nobody writes (most of the grid) only forwards the persistent map to the output.
-// own_bits(t) gives the lane's 4 map bytes of a processed, initialised tile (t: its 4 interior cells); it is called only for such a tile.
-template <class OwnBits>
-__device__ __forceinline__ void occ_cells_tile(const GridDev& g, int8_t* __restrict__ content, int8_t* __restrict__ out,
-                                               unsigned int* __restrict__ heads, uint32_t* __restrict__ list,
-                                               unsigned int* __restrict__ heads_next, int* __restrict__ count, OwnBits own_bits)
+// This extraction's mark counter and the NEXT extraction's list heads are cleared by the launch's first workgroup -- the heads come in
+// two sets used in turn -- instead of by two memset launches ahead of every extraction.
+__device__ __forceinline__ void occ_launch_clear(unsigned int* __restrict__ heads_next, int* __restrict__ count)
 {
-  // (this extraction's mark counter and the NEXT extraction's list heads are cleared from here -- the heads come in two sets used in
-  // turn -- instead of by two memset launches ahead of every extraction)
   if (blockIdx.x == 0) {
     if (threadIdx.x == 0) *count = 0;
     if (threadIdx.x < OCC_SHARDS) heads_next[threadIdx.x * OCC_HEAD_STRIDE] = 0u;
   }
-  const int p = blockIdx.x;
+}
+
+// puts tile p (processed and initialised) on k_occ_mark's work list; one lane of the tile's workgroup calls it
+__device__ __forceinline__ void occ_list_tile(const GridDev& g, int p, unsigned int* __restrict__ heads, uint32_t* __restrict__ list)
+{
+  const unsigned sh = (unsigned)p % OCC_SHARDS, cap = ((unsigned)g.tiles + OCC_SHARDS - 1) / OCC_SHARDS;
+  list[sh * cap + atomicAdd(&heads[sh * OCC_HEAD_STRIDE], 1u)] = (uint32_t)p;
+}
+
+// k_occ_cells for one workgroup and tile p (the full-map kernels: p = blockIdx.x; the windowed frame: a tile of its box), one lane per
+// 4 consecutive cells of a row (256 lanes): the map is read and written 4 bytes per lane (16-byte aligned rows).  A tile nobody writes
+// (most of the grid) only forwards the persistent map to the output.
+// own_bits(t) gives the lane's 4 map bytes of a processed, initialised tile (t: its 4 interior cells); it is called only for such a tile.
+template <class OwnBits>
+__device__ __forceinline__ void occ_cells_tile(const GridDev& g, int p, int8_t* __restrict__ content, int8_t* __restrict__ out,
+                                               unsigned int* __restrict__ heads, uint32_t* __restrict__ list,
+                                               unsigned int* __restrict__ heads_next, int* __restrict__ count, OwnBits own_bits)
+{
+  occ_launch_clear(heads_next, count);
   const int PX = g.PX;
   const int X = p % PX, Y = p / PX;
   const bool own_proc = tile_processed(X, Y, PX);
@@ -56,10 +68,7 @@ __device__ __forceinline__ void occ_cells_tile(const GridDev& g, int8_t* __restr
   uint32_t* c4 = reinterpret_cast<uint32_t*>(content + gi);
   uint32_t* o4 = reinterpret_cast<uint32_t*>(out + gi);
   if (own_proc && own_init) {
-    if (threadIdx.x == 0) {
-      const unsigned sh = (unsigned)p % OCC_SHARDS, cap = ((unsigned)g.tiles + OCC_SHARDS - 1) / OCC_SHARDS;
-      list[sh * cap + atomicAdd(&heads[sh * OCC_HEAD_STRIDE], 1u)] = (uint32_t)p;
-    }
+    if (threadIdx.x == 0) occ_list_tile(g, p, heads, list);
     const uint32_t v = own_bits(g.tsd + (size_t)p * TILE_STRIDE + ly * TILE_DIM + lx0);     // interior row, 4 cells
     *c4 = v; *o4 = v;
     return;

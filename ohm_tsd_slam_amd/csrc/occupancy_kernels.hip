@@ -19,7 +19,7 @@ __global__ void __launch_bounds__(256)
 k_occ_cells(GridDev g, int8_t* __restrict__ content, int8_t* __restrict__ out, unsigned int* __restrict__ heads, uint32_t* __restrict__ list,
             unsigned int* __restrict__ heads_next, int* __restrict__ count)
 {
-  occ_cells_tile(g, content, out, heads, list, heads_next, count, [](const tsd_cell_t* t) {
+  occ_cells_tile(g, (int)blockIdx.x, content, out, heads, list, heads_next, count, [](const tsd_cell_t* t) {
     return occ_bits4(ld_tsd(t), ld_tsd(t + 1), ld_tsd(t + 2), ld_tsd(t + 3));
   });
 }
@@ -154,12 +154,14 @@ OccHeads next_occ_heads(tsd_ctx* ctx)
   return h;
 }
 
-int launch_occ_mark(tsd_ctx* ctx, int8_t* d_out, int* d_count, int inflate, int inflate_factor, const unsigned int* heads)
+// max_tiles: an upper bound of the list's length where the caller has one (the windowed frame: the tiles of its box), < 0: the grid's
+int launch_occ_mark(tsd_ctx* ctx, int8_t* d_out, int* d_count, int inflate, int inflate_factor, const unsigned int* heads, int max_tiles)
 {
   // (measured at cfg 2, maps of 40 / 200 scans: 2 048 workgroups 9.3 / 12.3 us, 1 024: 10.5 / 12.6, 512: 14.1 / 17.7, 256: 21.9 / 28.2 --
   //  a tile is a ~5 us chain of dependent round trips, so as many of them side by side as there are)
   constexpr int OCC_MARK_GROUPS = 2048;
-  const int mark_groups = ctx->grid.tiles < OCC_MARK_GROUPS ? ((ctx->grid.tiles + OCC_SHARDS - 1) / OCC_SHARDS) * OCC_SHARDS : OCC_MARK_GROUPS;   // a multiple of the shards
+  const int n_tiles = max_tiles >= 0 && max_tiles < ctx->grid.tiles ? (max_tiles < 1 ? 1 : max_tiles) : ctx->grid.tiles;
+  const int mark_groups = n_tiles < OCC_MARK_GROUPS ? ((n_tiles + OCC_SHARDS - 1) / OCC_SHARDS) * OCC_SHARDS : OCC_MARK_GROUPS;   // a multiple of the shards
   hipLaunchKernelGGL(k_occ_mark, dim3(mark_groups), dim3(256), 0, ctx->stream, ctx->grid, d_out,
                      d_count, inflate, inflate_factor, heads, ctx->d_occ_list);
   TSD_HIP_CHECK(ctx, hipGetLastError());

@@ -815,6 +815,7 @@ int launch_free_footprint(tsd_ctx* ctx, unsigned minX, unsigned maxX, unsigned m
   TSD_HIP_CHECK(ctx, hipGetLastError());
   TileBox b; b.x0 = (int)tx0; b.y0 = (int)ty0; b.x1 = (int)tx1; b.y1 = (int)ty1;
   ctx->box_dirty.add(b);             // the next push refreshes the halos there
+  ctx->box_frame.add(b);             // ... and the next windowed frame covers them (tsd_map_update_begin)
   return TSD_OK;
 }
 
@@ -858,6 +859,7 @@ int launch_push(tsd_ctx* ctx, hipStream_t stream, const PushJob& job, HaloArgs* 
   box.add(ctx->box_prev);
   box.add(ctx->box_dirty);
   ctx->box_prev = cur; ctx->box_dirty = TileBox{};
+  ctx->box_frame.add(box);           // (counted whether or not the device-side gate lets the push run)
   const int ntx = box.x1 - box.x0 + 1, nty = box.y1 - box.y0 + 1;
   const int parity = (int)(ctx->push_parity & 1u);
   ctx->push_parity++;

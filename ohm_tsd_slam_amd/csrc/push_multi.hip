@@ -436,6 +436,7 @@ int launch_push_multi(tsd_ctx* ctx, hipStream_t stream, int n, const PushJob* jo
   box.add(ctx->box_prev);
   box.add(ctx->box_dirty);
   ctx->box_prev = cur; ctx->box_dirty = TileBox{};
+  ctx->box_frame.add(box);           // (counted whether or not the device-side gates let the pushes run)
   mp.tx0 = box.x0; mp.ty0 = box.y0; mp.ntx = box.x1 - box.x0 + 1; mp.nty = box.y1 - box.y0 + 1;
   const size_t n_window = (size_t)mp.ntx * (size_t)mp.nty;
   // per-window-tile state of this path: the masks (zero between batches: every listed tile's workgroup gives its word back), the

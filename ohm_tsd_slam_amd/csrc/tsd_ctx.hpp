@@ -286,6 +286,13 @@ struct tsd_ctx {
   hipEvent_t ev_frame = nullptr;                    // on `stream`: the frame's kernels are done
   hipEvent_t ev_frame_done = nullptr;               // on stream_io: the frame's copies to the host are done
   bool frame_inflight = false;
+  // The windowed frame (tsd_map_update_begin).  box_frame: the tiles anything may have written since the last frame or update was
+  // enqueued (every push's launch window, freeFootprint's box).  frame_prev_valid: the staging holds a complete frame taken with
+  // frame_prev_inflate / _factor (and its image, frame_prev_image) of the grid as box_frame describes it; cleared by whatever rewrites
+  // the grid wholesale, by a new staging and by a frame that ended in an error.
+  tsd::TileBox box_frame{};
+  bool frame_prev_valid = false, frame_prev_image = false, frame_empty = false;
+  int frame_prev_inflate = 0, frame_prev_factor = 0;
   // TSD-level fusion (fuse.hip).  As the destination: the kernel's sharded counters and their pinned copy.  As a member: events of its
   // own -- "every grid write enqueued so far" on its stream / its push stream, "the fusion that read this grid last is done" (recorded
   // on the destination's stream; the member's streams wait for it at once) -- all created on first use
@@ -540,7 +547,7 @@ size_t occ_heads_bytes();
 // the list heads of the next extraction (cur) and the set it clears for the one after (next)
 struct OccHeads { unsigned int* cur; unsigned int* next; };
 OccHeads next_occ_heads(tsd_ctx* ctx);
-int launch_occ_mark(tsd_ctx* ctx, int8_t* d_out, int* d_count, int inflate, int inflate_factor, const unsigned int* heads);
+int launch_occ_mark(tsd_ctx* ctx, int8_t* d_out, int* d_count, int inflate, int inflate_factor, const unsigned int* heads, int max_tiles = -1);
 int launch_color_image(tsd_ctx* ctx, const double* d_px, const double* d_py, unsigned width, unsigned height, uint8_t* d_image);
 size_t icp_lds_bytes();
 

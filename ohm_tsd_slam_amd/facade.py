@@ -43,6 +43,8 @@ HOST_ABI = {
     "tsd_node_grid_ctx": (C.c_void_p, [C.c_void_p]),
     "tsd_node_publish_map": (C.c_int, [C.c_void_p]),
     "tsd_node_map_frames": (C.c_ulonglong, [C.c_void_p]),
+    "tsd_node_map_updates": (C.c_ulonglong, [C.c_void_p]),
+    "tsd_node_map_update_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
@@ -272,6 +274,21 @@ class SlamNode:
         if not ok:
             raise capi.TsdError("get_map refused")
         return m
+
+    def map_updates(self) -> int:
+        """map_msgs/OccupancyGridUpdate messages on <node>/map_updates so far (parameter publish_map_updates)"""
+        return int(self.lib.tsd_node_map_updates(self.h))
+
+    def map_update_msg(self) -> dict:
+        """the last map_msgs/OccupancyGridUpdate on <node>/map_updates (data as (height, width) int8) and the number published"""
+        info = np.zeros(5)
+        frame = C.create_string_buffer(256)
+        self.lib.tsd_node_map_update_msg(self.h, None, info.ctypes.data_as(_dp), frame, 256)
+        w, h = int(info[2]), int(info[3])
+        data = np.zeros(w * h, dtype=np.int8)
+        n = self.lib.tsd_node_map_update_msg(self.h, data.ctypes.data, info.ctypes.data_as(_dp), frame, 256)
+        return {"x": int(info[0]), "y": int(info[1]), "width": w, "height": h, "stamp_ns": int(info[4]),
+                "frame_id": frame.value.decode(), "data": data.reshape(h, w), "count": int(n)}
 
     def map_image_msg(self) -> dict:
         """the last sensor_msgs/Image on <node>/map/image (data as (height, width, 3) uint8) and its publish count"""
