@@ -165,6 +165,78 @@ int tsd_localize(tsd_ctx* ctx, const double pose33[9], const double* rays_world_
                  double min_range, double max_range, const tsd_icp_params* params,
                  tsd_icp_result* result);
 
+/* ---- relocalisation: where in this grid was this scan taken? ------------------------------------------------ */
+#define TSD_RELOC_MAX_PEAKS      64          /* start poses handed to the refinement at most */
+#define TSD_RELOC_MAX_CANDIDATES (1 << 26)   /* nx * ny * ntheta at most: a 256 MiB score volume */
+#define TSD_RELOC_MAX_REACH      4           /* grid widths a lattice position may lie outside the grid, and a scan point from the sensor */
+/* The pose lattice of the search and what is done with its peaks.  Candidate (ix, iy, k) stands for the sensor pose at
+ * (x0 + (double)ix * step_xy, y0 + (double)iy * step_xy) turned by rotation k; its index is idx = (k * ny + iy) * nx + ix. */
+typedef struct {
+  double  x0, y0, step_xy;      /* world coordinates of node (0, 0) and the node spacing (> 0), metres.  Every node within
+                                 * TSD_RELOC_MAX_REACH grid widths of the grid's square (TSD_E_ARG beyond): the cell index of a carried
+                                 * point then fits an int */
+  int32_t nx, ny, ntheta;       /* nodes per axis, each >= 1; nx * ny * ntheta <= TSD_RELOC_MAX_CANDIDATES (TSD_E_CAPACITY beyond) */
+  int32_t theta_wraps;          /* != 0: the rotations cover the full circle, k = 0 and k = ntheta - 1 are neighbours */
+  const double* cos_sin;        /* [2 * ntheta]: cos, sin of rotation k at [2k], [2k + 1].  NULL: the host fills the table with libm's
+                                 * cos / sin of theta0 + (double)k * dtheta (dtheta finite and != 0, else TSD_E_ARG).  The device never
+                                 * computes a sine: a restatement on the same table is bit-comparable */
+  double  theta0, dtheta;       /* read with cos_sin == NULL only */
+  int32_t K;                    /* peaks to refine, 1 .. TSD_RELOC_MAX_PEAKS */
+  int32_t min_pairs;            /* found = the winner's pairs >= min_pairs (>= 0) */
+} tsd_reloc_params;
+typedef struct {
+  int32_t  found;               /* the winner's registration ended with at least min_pairs pairs (0 without a peak) */
+  int32_t  winner_idx;          /* candidate index of the winning peak, -1 when the search found no peak */
+  double   pose33[9];           /* found: winner's coarse pose * T, 3x3 row-major (the sensor pose of the scan); NaN otherwise */
+  double   coarse_x, coarse_y, coarse_cos, coarse_sin;   /* the winning peak's lattice pose (NaN without a peak) */
+  uint32_t winner_score;        /* its score (0 without a peak) */
+  int32_t  n_peaks;             /* peaks the search returned, <= K */
+  int32_t  n_refined;           /* ... of which were refined (all of them unless a registration call failed) */
+  int32_t  reserved;
+  tsd_icp_result icp;           /* the winner's registration, as tsd_localize fills it (zero without a peak) */
+  double   search_ms, refine_ms;/* tsd_profile_enable(ctx, 1): stream time of the search (scores + peaks) and of the refinement's
+                                 * launches and copies, from HIP events around them; 0 otherwise */
+} tsd_reloc_result;
+/* Global localisation of one scan in the grid as it is: a dense search over the pose lattice, then the registration from its best peaks.
+ *
+ * Score of a candidate (k_reloc_score; fp64 in the written order, no contraction): with t = its position and (c, s) its rotation, 0 unless
+ * TsdGrid::interpolateBilinear (TsdGrid.h:284-304) at t succeeds with a value > 0 (the sensor stands in seen free space; nothing else is
+ * looked up otherwise).  Else the sum over the P points (px, py) of 1048576 - (uint32)rint(fabs(v) * 1048576.0), v the look-up at
+ * ((c*px - s*py) + t.x, (s*px + c*py) + t.y), over the look-ups that succeed (outside the grid, uninitialised tile, NaN: 0).  A sum of
+ * integers in uint32: independent of the order of summation.  The cells are taken to hold what a push writes, |tsd| <= 1 (or NaN): a term
+ * is then 0 .. 2^20 and the sum of TSD_MAX_ICP_POINTS of them fits.  For cells of |tsd| >= 4096, which only tsd_upload_tiles can leave,
+ * the conversion to uint32 is undefined and the score is unspecified; nothing else is affected.
+ * Peaks (k_reloc_peaks): a candidate with score > 0 that beats each of its up to 26 lattice neighbours n (k wraps when theta_wraps):
+ * score > score_n, or score == score_n and idx < idx_n.  The K best by score descending, then idx ascending.
+ * Refinement: for each peak in that order the unfused localisation of tsd_localize from the peak's pose [[c, -s, tx], [s, c, ty], [0, 0, 1]]
+ * with rays_world = R * rays_local (Sensor::transform, Sensor.cpp:50-55: (0 + c*x) + (-s)*y, (0 + s*x) + c*y) scaled by cellSize
+ * (Sensor::getNormalizedRayMap, Sensor.cpp:36-48) and icp_params as given.  The winner is IcpMultiInitIterator's
+ * (IcpMultiInitIterator.cpp:26-38): strictly more pairs replace the best so far, so the earlier peak keeps a tie.  pose33 = coarse * T.
+ *
+ * points_xy: the P valid scan points in the sensor frame (x0 y0 x1 y1 ..), what Sensor::dataToCartesianVectorMask leaves after the
+ * mask's compaction; 1 <= P (TSD_E_ARG) <= TSD_MAX_ICP_POINTS (TSD_E_CAPACITY), each coordinate finite and within TSD_RELOC_MAX_REACH grid
+ * widths of the sensor (TSD_E_ARG).  rays_local_2xB / ranges / mask / beams /
+ * min_range / max_range / icp_params: the scan as tsd_localize takes it.  The search only reads the grid: no cell, no tile flag, none of the
+ * push or map-publication bookkeeping and no sensor is touched; the refinement uses the context's ray-cast and registration buffers like
+ * tsd_localize.  Refused with TSD_E_ARG while a scan of this context is in flight (tsd_scan_submit / tsd_scan_begin / tsd_batch_begin without
+ * their collect): it is not ordered against one silently.  Waits for its result.  Every argument is checked before the context is
+ * touched: a refused call allocates nothing.
+ * Memory: the score volume (4 bytes per candidate) stays with the context for the next search and for tsd_debug_reloc_scores as long as it
+ * holds at most 2^23 candidates (32 MiB); a larger one is freed before the call returns.  tsd_destroy frees what is kept. */
+int tsd_relocalize(tsd_ctx* ctx, const tsd_reloc_params* params, const double* points_xy, int P, const double* rays_local_2xB,
+                   const double* ranges, const uint8_t* mask, int beams, double min_range, double max_range,
+                   const tsd_icp_params* icp_params, tsd_reloc_result* result);
+/* TEST HOOK: the score volume of the last tsd_relocalize of this context, scores[idx].  Copies min(n, cap) entries and returns
+ * n = nx * ny * ntheta of that search: 0 before the first one and after a search of more than 2^23 candidates, whose volume is not
+ * kept.  TSD_E_ARG without a context, TSD_E_HIP when the copy fails. */
+int tsd_debug_reloc_scores(tsd_ctx* ctx, uint32_t* scores, int cap);
+/* TEST HOOK: the device's peak selection on a given volume scores[(k * ny + iy) * nx + ix]: the K (1 .. TSD_RELOC_MAX_PEAKS) best peaks in
+ * idx_out / score_out [K], their number in *n_out.  Leaves the volume of the last search alone.  TSD_OK; TSD_E_ARG for a null
+ * pointer, a shape below 1, K outside its range or a scan of the context in flight (as tsd_relocalize); TSD_E_CAPACITY for a volume
+ * above TSD_RELOC_MAX_CANDIDATES; TSD_E_HIP when an allocation, a copy or a launch fails. */
+int tsd_debug_reloc_peaks(tsd_ctx* ctx, const uint32_t* scores, int nx, int ny, int ntheta, int theta_wraps, int K,
+                          int32_t* idx_out, uint32_t* score_out, int* n_out);
+
 /* ---- pre-registration (registration_mode 3) ------------------------------------------------------------- */
 /* obvious::TSD_PDFMatching(grid, trials, epsThresh, sizeControlSet, zrand) (TSD_PDFMatching.cpp:6-26; ThreadLocalize.cpp:193)
  * and the arguments of its match() that are not point sets (ThreadLocalize.cpp:559) */

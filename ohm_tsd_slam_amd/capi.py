@@ -167,6 +167,25 @@ class ScanResult(C.Structure):
                 ("no_model", C.c_int32), ("reserved", C.c_int32)]
 
 
+RELOC_MAX_PEAKS = 64
+RELOC_MAX_CANDIDATES = 1 << 26
+
+
+class RelocParams(C.Structure):
+    """tsd_reloc_params"""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("step_xy", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("ntheta", C.c_int32), ("theta_wraps", C.c_int32), ("cos_sin", C.POINTER(C.c_double)), ("theta0", C.c_double),
+                ("dtheta", C.c_double), ("K", C.c_int32), ("min_pairs", C.c_int32)]
+
+
+class RelocResult(C.Structure):
+    """tsd_reloc_result"""
+    _fields_ = [("found", C.c_int32), ("winner_idx", C.c_int32), ("pose33", C.c_double * 9), ("coarse_x", C.c_double),
+                ("coarse_y", C.c_double), ("coarse_cos", C.c_double), ("coarse_sin", C.c_double), ("winner_score", C.c_uint32),
+                ("n_peaks", C.c_int32), ("n_refined", C.c_int32), ("reserved", C.c_int32), ("icp", IcpResult),
+                ("search_ms", C.c_double), ("refine_ms", C.c_double)]
+
+
 # every symbol include/tsd_hip.h declares: name -> (restype, argtypes)
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
@@ -231,6 +250,11 @@ ABI = {
                                C.POINTER(RnMatchResult)]),
     "tsd_debug_rn_match_scores": (C.c_int, [C.c_void_p, _ip, _ip, _dp, C.c_int]),
     "tsd_debug_rn_select": (C.c_int, [C.c_void_p, _ip, _ip, _dp, C.c_int, C.c_int, _ip]),
+    "tsd_relocalize": (C.c_int, [C.c_void_p, C.POINTER(RelocParams), _dp, C.c_int, _dp, _dp, _u8p, C.c_int, C.c_double, C.c_double,
+                                 C.POINTER(IcpParams), C.POINTER(RelocResult)]),
+    "tsd_debug_reloc_scores": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),
+    "tsd_debug_reloc_peaks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _ip]),
     "tsd_scan_preregister": (C.c_int, [C.c_void_p, C.POINTER(TsdPdfParams), _dp, _u8p, _ip, _ip, _ip]),
     "tsd_scan_preregistration_result": (C.c_int, [C.c_void_p, C.POINTER(TsdPdfResult)]),
     "tsd_sensor_set_async_mapping": (C.c_int, [C.c_void_p, C.c_int]),
@@ -311,7 +335,8 @@ def load_library(path: str | None = None):
                           ("tsd_tsdpdf_params", TsdPdfParams), ("tsd_tsdpdf_result", TsdPdfResult),
                           ("tsd_pdfmatch_params", PdfMatchParams), ("tsd_rnmatch_params", RnMatchParams),
                           ("tsd_rnmatch_result", RnMatchResult), ("tsd_map_params", MapParams),
-                          ("tsd_fuse_stats", FuseStats), ("tsd_map_window", MapWindow)):
+                          ("tsd_fuse_stats", FuseStats), ("tsd_map_window", MapWindow), ("tsd_reloc_params", RelocParams),
+                          ("tsd_reloc_result", RelocResult)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -522,6 +547,51 @@ class TsdGridDevice:
                                    max_range, C.byref(params), C.byref(r))
         self._check(rc, "tsd_localize")
         return IcpOut(np.array(r.T[:]).reshape(3, 3), r.rms, r.pairs, r.iterations, r.state, r.n_model, r.n_scene, seeded=r.reserved)
+
+    def relocalize(self, points_xy, rays_local, ranges, mask, min_range, max_range, params: IcpParams, x0, y0, step_xy, nx, ny,
+                   ntheta, theta0=0.0, dtheta=0.0, cos_sin=None, theta_wraps=False, K=16, min_pairs=0) -> dict:
+        """tsd_relocalize: search the pose lattice (x0 + ix * step_xy, y0 + iy * step_xy, rotation k of ``cos_sin`` -- (ntheta, 2)
+        cos / sin -- or of theta0 + k * dtheta) for the scan whose valid points in the sensor frame are ``points_xy`` (P, 2), refine the
+        K best peaks with the registration of ``localize`` and keep the one with the most pairs.  Raises TsdError with the C code in
+        ``.args`` text on a refused call."""
+        pts, rl, rg = _f64(points_xy).reshape(-1), _f64(rays_local), _f64(ranges)
+        mk = np.ascontiguousarray(mask, dtype=np.uint8)
+        tab = None if cos_sin is None else _f64(cos_sin).reshape(-1)
+        assert tab is None or tab.size == 2 * ntheta
+        prm = RelocParams(float(x0), float(y0), float(step_xy), int(nx), int(ny), int(ntheta), int(bool(theta_wraps)),
+                          None if tab is None else _d(tab), float(theta0), float(dtheta), int(K), int(min_pairs))
+        r = RelocResult()
+        rc = self.lib.tsd_relocalize(self.h, C.byref(prm), _d(pts), pts.size // 2, _d(rl), _d(rg), _u8(mk), rg.size, min_range,
+                                     max_range, C.byref(params), C.byref(r))
+        self.last_rc = rc
+        self._check(rc, "tsd_relocalize")
+        i = r.icp
+        return dict(found=bool(r.found), pose=np.array(r.pose33[:]).reshape(3, 3), idx=int(r.winner_idx), score=int(r.winner_score),
+                    coarse=(r.coarse_x, r.coarse_y, r.coarse_cos, r.coarse_sin), n_peaks=int(r.n_peaks), n_refined=int(r.n_refined),
+                    icp=IcpOut(np.array(i.T[:]).reshape(3, 3), i.rms, i.pairs, i.iterations, i.state, i.n_model, i.n_scene,
+                               seeded=i.reserved),
+                    search_ms=r.search_ms, refine_ms=r.refine_ms)
+
+    def debug_reloc_scores(self) -> np.ndarray:
+        """TEST HOOK: the score volume of the last relocalize, uint32 [nx * ny * ntheta] in candidate order (empty before the first search and
+        after one of more than 2^23 candidates, whose volume the context does not keep)"""
+        n = self.lib.tsd_debug_reloc_scores(self.h, None, 0)
+        self._check(min(n, 0), "tsd_debug_reloc_scores")
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        self._check(min(self.lib.tsd_debug_reloc_scores(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n), 0), "tsd_debug_reloc_scores")
+        return out[:n]
+
+    def debug_reloc_peaks(self, scores, shape, wraps, K):
+        """TEST HOOK: the device's peak selection on a volume ``scores`` of ``shape`` = (ntheta, ny, nx): (idx, score) of the K best
+        peaks, score descending then idx ascending"""
+        nt, ny, nx = (int(v) for v in shape)
+        vol = np.ascontiguousarray(scores, dtype=np.uint32).reshape(-1)
+        assert vol.size == nt * ny * nx
+        idx, sc, n = np.zeros(RELOC_MAX_PEAKS, dtype=np.int32), np.zeros(RELOC_MAX_PEAKS, dtype=np.uint32), C.c_int(0)
+        rc = self.lib.tsd_debug_reloc_peaks(self.h, vol.ctypes.data_as(C.POINTER(C.c_uint32)), nx, ny, nt, int(bool(wraps)), int(K),
+                                            idx.ctypes.data_as(C.POINTER(C.c_int32)), sc.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n))
+        self._check(rc, "tsd_debug_reloc_peaks")
+        return idx[:n.value].copy(), sc[:n.value].copy()
 
     def set_icp_helpers(self, on: bool):
         """test hook: off = every registration does its first step's searches itself (same results, tsd_debug_set_icp_helpers)"""

@@ -498,6 +498,7 @@ void tsd_destroy(tsd_ctx* ctx)
   for (hipEvent_t e : {ctx->ev_fuse_src, ctx->ev_fuse_src_push, ctx->ev_fuse_read}) if (e) hipEventDestroy(e);
   if (ctx->d_pdf) hipFree(ctx->d_pdf);
   if (ctx->h_pdf) hipHostFree(ctx->h_pdf);
+  reloc_free(ctx);
   if (ctx->stream) hipStreamDestroy(ctx->stream);
   delete ctx;
 }

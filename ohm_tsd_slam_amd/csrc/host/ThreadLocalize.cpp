@@ -639,7 +639,43 @@ void ThreadLocalize::stageNextScan(bool submitted)
     _preStagedValid = true;
 }
 
-void ThreadLocalize::init(const sensor_msgs::msg::LaserScan& scan)
+bool ThreadLocalize::startAt(const double pose33[9], const sensor_msgs::msg::LaserScan& scan)
+{
+  if(!idle() || _mapper.pending() != 0)            // (a queued push still carries the pose the localiser is leaving)
+    return false;
+  if(!_initialized)
+  {
+    auto scanCopy = std::make_shared<sensor_msgs::msg::LaserScan>(scan);
+    clampRanges(*scanCopy);
+    this->init(*scanCopy, pose33);
+    _stampLaserOld = scan.header.stamp;
+    return true;
+  }
+  obvious::Matrix T(3, 3);
+  T.setData(pose33);
+  _sensor->resetPose();
+  _sensor->transform(&T);
+  _haveLastPose = false;
+  _stagedValid = false; _preStagedValid = false;
+  {
+    std::lock_guard<std::mutex> lk(_dataMutex);
+    _ahead.reset();
+  }
+  if(_sensor->deviceHandle() && _grid.attachSensor(_sensor) != TSD_OK)
+    return false;
+  // the report of a start, as init leaves it: the last scan's registration verdict does not describe the new pose
+  std::lock_guard<std::mutex> lk(_reportMutex);
+  const long long stamp = _report.stampNs;
+  std::memset(&_report, 0, sizeof(_report));
+  _sensor->getTransformation().getData(_report.pose);
+  _report.T[0] = _report.T[4] = _report.T[8] = 1.0;
+  _report.initialised = true;
+  _report.stampNs = stamp;
+  return true;
+}
+
+// pose33 != nullptr (startAt): that sensor pose instead of the configured start pose, no freeFootprint, no initial push
+void ThreadLocalize::init(const sensor_msgs::msg::LaserScan& scan, const double* pose33)
 {
   // per-robot parameters (ThreadLocalize.cpp:424-442)
   declareInitParameters(_node, _nameSpace);
@@ -660,7 +696,7 @@ void ThreadLocalize::init(const sensor_msgs::msg::LaserScan& scan)
                   std::sin(phi),  std::cos(phi), startY,
                   0,              0,             1};
   obvious::Matrix Tinit(3, 3);
-  Tinit.setData(tf);
+  Tinit.setData(pose33 ? pose33 : tf);
 
   double inc       = scan.angle_increment;
   double angle_min = scan.angle_min;
@@ -677,10 +713,12 @@ void ThreadLocalize::init(const sensor_msgs::msg::LaserScan& scan)
   _sensor->setStandardMask();
   _sensor->transform(&Tinit);
   double t[2] = {startX + footPrintXoffset, startY};
-  if(!_grid.freeFootprint(t, footPrintWidth, footPrintHeight))
+  if(!pose33 && !_grid.freeFootprint(t, footPrintWidth, footPrintHeight))
     std::fprintf(stderr, "Localizer (%s) warning! Footprint could not be freed!\n", _nameSpace.c_str());
   bool pushed = false;
-  if(!_mapper.initialized())
+  if(pose33)
+    _mapper.markInitialized();
+  else if(!_mapper.initialized())
   {
     _mapper.initPush(_sensor);
     pushed = true;

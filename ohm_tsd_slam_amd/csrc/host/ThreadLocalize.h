@@ -49,6 +49,13 @@ public:
    *  ingests it and stages it on the device while the current registration runs (tsd_scan_stage).  The following
    *  laserCallBack with the same stamp then starts from the staged data. */
   void announceNext(const std::shared_ptr<sensor_msgs::msg::LaserScan> scan);
+  /** start or re-seat the localiser at a known sensor pose (3x3 row-major), e.g. the result of a relocalisation in a stored map.
+   *  Fresh localiser: what init does with `scan` as the first scan, but at pose33 instead of the configured start pose, WITHOUT
+   *  freeFootprint and WITHOUT the initial push; the mapper is marked initialised, so the map in the grid is not overwritten.
+   *  Running localiser: the sensor pose is re-seated (host sensor and its device twin, _lastPose forgotten) between two scans;
+   *  `scan` is not used, and lastReport() reads like after a start: the new pose, T = identity, no verdict of the scan before.
+   *  False when scans are queued or being processed, or a push of the mapper is still queued.  Nothing is registered or pushed by the call. */
+  bool startAt(const double pose33[9], const sensor_msgs::msg::LaserScan& scan);
   struct ScanReport {
     double pose[9]; double T[9]; double rms; int pairs; int iterations; int icpState;
     int validModel; int validScene; bool regError; bool pushed; bool noModel; bool initialised;
@@ -81,7 +88,7 @@ protected:
   virtual void eventLoop(void);
 
 private:
-  void init(const sensor_msgs::msg::LaserScan& scan);
+  void init(const sensor_msgs::msg::LaserScan& scan, const double* pose33 = nullptr);
   void processScan(const std::vector<float>& rangesIn, const builtin_interfaces::msg::Time& stamp);
   void processScanFused(ScanReport& rep);
   void processScanPreRegistered(ScanReport& rep);

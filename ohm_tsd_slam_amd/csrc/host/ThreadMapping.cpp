@@ -44,6 +44,12 @@ void ThreadMapping::initPush(obvious::SensorPolar2D* sensor)
   _initialized = true;
 }
 
+void ThreadMapping::markInitialized(void)
+{
+  std::lock_guard<std::mutex> lk(_pushMutex);
+  _initialized = true;
+}
+
 void ThreadMapping::eventLoop(void)
 {
   while(_stayActive)

@@ -20,6 +20,8 @@ public:
   bool initialized(void);
   /** one synchronous TsdGrid::push on the caller's thread (ThreadMapping.cpp:32-41) */
   void initPush(obvious::SensorPolar2D* sensor);
+  /** the grid holds a map already (loaded, fused): no localiser's first scan is pushed at its start pose (addition) */
+  void markInitialized(void);
   /** number of queued sensors (test / drain helper; not in the reference) */
   size_t pending(void);
 

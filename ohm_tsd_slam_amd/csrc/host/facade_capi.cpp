@@ -215,6 +215,22 @@ int tsd_node_laser(tsd_node* n, int robot, const float* ranges, int count, doubl
   return TSD_OK;
 }
 
+// ThreadLocalize::startAt: start (first call: `ranges` is the first scan) or re-seat the robot's localiser at the sensor pose pose33
+// without touching the map.  TSD_E_ARG while scans of the robot are queued or being processed, or a push is queued at the mapper.
+int tsd_node_start_at(tsd_node* n, int robot, const double* pose33, const float* ranges, int count, double angle_min,
+                      double angle_increment, long long stamp_ns)
+{
+  if(!n || robot < 0 || robot >= (int)n->localizers.size() || !pose33 || !ranges || count < 1)
+    return TSD_E_ARG;
+  sensor_msgs::msg::LaserScan scan;
+  scan.ranges.assign(ranges, ranges + count);
+  scan.angle_min = (float)angle_min;
+  scan.angle_increment = (float)angle_increment;
+  scan.header.stamp.sec = (int32_t)(stamp_ns / 1000000000LL);
+  scan.header.stamp.nanosec = (uint32_t)(stamp_ns % 1000000000LL);
+  return n->localizers[robot]->startAt(pose33, scan) ? TSD_OK : TSD_E_ARG;
+}
+
 // the scan that tsd_node_laser will deliver NEXT (ThreadLocalize::announceNext): known ahead in a replay, or queued
 int tsd_node_laser_ahead(tsd_node* n, int robot, const float* ranges, int count, double angle_min, double angle_increment,
                          long long stamp_ns)

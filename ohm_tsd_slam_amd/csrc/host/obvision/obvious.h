@@ -67,6 +67,8 @@ public:
   void transform(Matrix* T);                    // Sensor.cpp:50-60
   Matrix getTransformation() const { return _T; }
   void setTransformation(const Matrix& T) { _T = T; }
+  /** a fresh sensor's pose state (addition): identity transformation, untransformed rays of norm 1; data and mask are kept */
+  void resetPose() { _T = Matrix(3, 3); _T.setIdentity(); _rays = _raysLocal; _rayNorm = 1.0; }
   void getPosition(double* tr) const { tr[0] = _T(0, 2); tr[1] = _T(1, 2); }   // Sensor.cpp:114-118
 
   double getMaximumRange() const { return _maxRange; }

@@ -300,6 +300,17 @@ struct tsd_ctx {
   bool fuse_begun = false;
   hipEvent_t ev_fuse_src = nullptr, ev_fuse_src_push = nullptr, ev_fuse_read = nullptr;
 
+  // relocalisation (reloc.hip): the scan points, the rotation table, the score volume of the last search, the per-workgroup and merged
+  // peak keys; one device block each, grown on demand, and the pinned copy of the merged keys + their count
+  struct Reloc {
+    double* d_points = nullptr;              // [2 * TSD_MAX_ICP_POINTS] x0 y0 x1 y1 ..
+    double* d_cos_sin = nullptr; size_t rot_cap = 0;
+    uint32_t* d_scores = nullptr; size_t score_cap = 0;
+    unsigned long long* d_keys = nullptr;    // [(RELOC_PEAK_GRID + 1) * 64 + 1]: per-workgroup keys, merged keys, count
+    unsigned long long* h_keys = nullptr;    // pinned [64 + 1]
+    int nx = 0, ny = 0, ntheta = 0;          // shape of the volume in d_scores (0: no search yet)
+  } reloc;
+
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;
   unsigned profile_every = 1;   // time every n-th launch of a selected kernel ("name/n" in tsd_profile_select)
@@ -541,6 +552,7 @@ int launch_wait_seq_multi(tsd_ctx* ctx, int n, const unsigned long long* const* 
 size_t icp_seed_bytes(int points);
 IcpSeedArgs icp_batch_seed_args(const tsd_ctx* ctx, void* buf, int beams, int batch_beams);
 
+void reloc_free(tsd_ctx* ctx);               // reloc.hip: releases tsd_ctx::reloc (tsd_destroy)
 int launch_calibrate(tsd_ctx* ctx, double* t, double* w, size_t n);
 int launch_occupancy(tsd_ctx* ctx, int8_t* d_out, int inflate, int inflate_factor);
 size_t occ_heads_bytes();

@@ -29,6 +29,7 @@ HOST_ABI = {
     "tsd_node_set_synchronous": (None, [C.c_void_p, C.c_int]),
     "tsd_node_set_fused": (None, [C.c_void_p, C.c_int]),
     "tsd_node_laser": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, C.c_double, C.c_double, C.c_longlong]),
+    "tsd_node_start_at": (C.c_int, [C.c_void_p, C.c_int, _dp, _fp, C.c_int, C.c_double, C.c_double, C.c_longlong]),
     "tsd_node_wait_idle": (C.c_int, [C.c_void_p, C.c_int]),
     "tsd_node_processed": (C.c_ulonglong, [C.c_void_p, C.c_int]),
     "tsd_node_report": (None, [C.c_void_p, C.c_int, _dp]),
@@ -146,6 +147,22 @@ class SlamNode:
             self.h = None
             raise capi.TsdError(f"tsd_node_initialize failed ({rc}): no usable GPU; the hot path has no CPU fall-back")
         self._stamp = 0
+        self._params, self._name, self._declared = dict(params), name, None
+
+    def robot_parameters(self, robot: int = 0) -> dict:
+        """What the robot's localiser reads from the node's parameters -- ThreadLocalize's constructor (laser_min_range, icp_iterations,
+        dist_filter_max / _min) and ThreadLocalize::init (max_range, min_range) -- as set for this node or as declared by default."""
+        if self._declared is None:
+            self._declared = {k: v for k, (_, v) in declared_parameters(self._params, self._name).items()}
+        d = self._declared
+        prefix = ""
+        if d["robot_nbr"] > 1:
+            prefix = d[f"robot_{robot}/name"]
+            prefix += "" if prefix.endswith("/") or not prefix else "/"
+        out = {"laser_min_range": d["laser_min_range"]}
+        out.update({k: d[prefix + k] for k in ("icp_iterations", "dist_filter_max", "dist_filter_min")})
+        out.update({k: d[f"{self._name}/{prefix}{k}"] for k in ("max_range", "min_range")})
+        return out
 
     def close(self):
         if getattr(self, "h", None):
@@ -174,6 +191,51 @@ class SlamNode:
         rc = self.lib.tsd_node_laser(self.h, robot, r.ctypes.data_as(_fp), r.size, angle_min, angle_increment, stamp_ns)
         if rc != 0:
             raise capi.TsdError(f"tsd_node_laser failed ({rc})")
+
+    def start_at(self, pose, ranges_f32, angle_min, angle_increment, robot: int = 0, stamp_ns: int | None = None):
+        """ThreadLocalize::startAt: start the robot's localiser at the sensor pose ``pose`` (3 x 3) with ``ranges_f32`` as its first scan
+        -- no freeFootprint, no initial push: the map in the grid stays as it is -- or re-seat a running one there."""
+        r = np.ascontiguousarray(ranges_f32, dtype=np.float32)
+        p = np.ascontiguousarray(pose, dtype=np.float64).reshape(9)
+        if stamp_ns is None:
+            self._stamp += 25_000_000
+            stamp_ns = self._stamp
+        rc = self.lib.tsd_node_start_at(self.h, robot, p.ctypes.data_as(_dp), r.ctypes.data_as(_fp), r.size, angle_min,
+                                        angle_increment, stamp_ns)
+        if rc != 0:
+            raise capi.TsdError(f"tsd_node_start_at failed ({rc}): scans of the robot are still queued or being processed")
+
+    def relocalize(self, ranges_f32, angle_min, angle_increment, x0, y0, step_xy, nx, ny, ntheta, theta0=0.0, dtheta=0.0,
+                   cos_sin=None, theta_wraps=False, K=16, min_pairs=0, robot: int = 0) -> dict:
+        """Find the scan in the grid's map and, when found, start (or re-seat) the robot's localiser there: the scan is ingested the
+        way laserCallBack and SensorPolar2D do it, ``TsdGridDevice.relocalize`` searches the lattice and refines its peaks, and
+        ``start_at`` takes the pose.  The ranges' limits and the registration's parameters are the robot's own, read from the node's
+        parameters (``robot_parameters``).  Returns relocalize's dict."""
+        prm = self.robot_parameters(robot)
+        max_range, min_range = prm["max_range"], prm["min_range"]
+        r = np.array(ranges_f32, dtype=np.float32)
+        r[r < prm["laser_min_range"]] = 0.0                                # ThreadLocalize::clampRanges
+        n = r.size
+        scan_geometry = (angle_min, angle_increment)                       # (start_at takes the scan as the driver delivered it)
+        if angle_increment < 0.0 and angle_min > 0:                        # clockwise scanner (ThreadLocalize.cpp:491-497)
+            r, angle_min, angle_increment = r[::-1].copy(), -angle_min, -angle_increment
+        data, mask = np.zeros(n), np.zeros(n, dtype=np.uint8)
+        self.lib.tsd_host_sensor_ingest_f32(r.ctypes.data_as(_fp), n, angle_increment, angle_min, max_range, data.ctypes.data_as(_dp),
+                                            mask.ctypes.data_as(_u8p), 0)
+        eye = np.eye(3).reshape(9)
+        pose, rays, rays_local, scene = np.zeros(9), np.zeros(2 * n), np.zeros(2 * n), np.zeros(2 * n)
+        smask, valid = np.zeros(n, dtype=np.uint8), C.c_int(0)
+        self.lib.tsd_host_sensor_chain(n, angle_increment, angle_min, eye.ctypes.data_as(_dp), eye.ctypes.data_as(_dp), 1.0,
+                                       r.ctypes.data_as(_fp), pose.ctypes.data_as(_dp), rays.ctypes.data_as(_dp),
+                                       rays_local.ctypes.data_as(_dp), scene.ctypes.data_as(_dp), smask.ctypes.data_as(_u8p), C.byref(valid))
+        points = scene.reshape(-1, 2)[smask.astype(bool)]
+        g = self.grid()
+        icp = g.icp_params(prm["icp_iterations"], prm["dist_filter_max"], prm["dist_filter_min"])
+        out = g.relocalize(points, rays_local, data, mask, min_range, max_range, icp, x0, y0, step_xy, nx, ny, ntheta, theta0=theta0,
+                           dtheta=dtheta, cos_sin=cos_sin, theta_wraps=theta_wraps, K=K, min_pairs=min_pairs)
+        if out["found"]:
+            self.start_at(out["pose"], ranges_f32, *scan_geometry, robot=robot)
+        return out
 
     def play(self, scans, first: int, count: int, angle_min, angle_increment):
         """Replay scans[r][first:first+count] of every robot r from one native publisher thread per robot (`rosbag play`):
@@ -402,7 +464,8 @@ class GridView(capi.TsdGridDevice):
 
     _LOCKED = ("reset", "sync", "free_footprint", "push", "raycast", "icp", "localize", "icp_trace", "download_tile_state",
                "download_tiles", "upload_tiles", "digest", "occupancy", "occupancy_into", "calibrate_rmw", "profile", "store_text",
-               "load_text", "color_image", "push_stats_total", "profile_reset", "profile_get", "profile_spread", "profile_samples", "tsdpdf_match")
+               "load_text", "color_image", "push_stats_total", "profile_reset", "profile_get", "profile_spread", "profile_samples", "tsdpdf_match",
+               "relocalize", "debug_reloc_scores", "debug_reloc_peaks")
 
     def __init__(self, ctx, node=None):  # noqa: D401 - does not call the base constructor on purpose
         self.lib = capi.load_library()
