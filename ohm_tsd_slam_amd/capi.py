@@ -422,6 +422,12 @@ class TsdGridDevice:
     def sync(self):
         self._check(self.lib.tsd_sync(self.h), "tsd_sync")
 
+    def set_max_truncation(self, val) -> float:
+        """TsdGrid::setMaxTruncation on the live grid (tsd_set_max_truncation): the truncation the context reports afterwards."""
+        self._check(self.lib.tsd_set_max_truncation(self.h, float(val)), "tsd_set_max_truncation")
+        self.max_trunc = self.lib.tsd_max_truncation(self.h)
+        return self.max_trunc
+
     def free_footprint(self, center, width, height) -> bool:
         c = _f64(center)
         rc = self.lib.tsd_free_footprint(self.h, _d(c), float(width), float(height))

@@ -102,6 +102,8 @@ def lib():
         for n in ("ora_grid_max_trunc", "ora_grid_max_x"):
             getattr(L, n).argtypes = [C.c_void_p]
             getattr(L, n).restype = C.c_double
+        L.ora_grid_set_max_trunc.argtypes = [C.c_void_p, C.c_double]
+        L.ora_grid_set_max_trunc.restype = None
         L.ora_free_footprint.argtypes = [C.c_void_p, _dp, C.c_double, C.c_double]
         L.ora_grid_dump.argtypes = [C.c_void_p, _u8p, _dp, _dp, _dp]
         L.ora_grid_load.argtypes = [C.c_void_p, _u8p, _dp, _dp, _dp]
@@ -231,6 +233,12 @@ class Grid:
             self.close()
         except Exception:
             pass
+
+    def set_max_truncation(self, val) -> float:
+        """TsdGrid::setMaxTruncation on the live grid: the truncation the grid reports afterwards."""
+        self.L.ora_grid_set_max_trunc(self.h, float(val))
+        self.max_trunc = self.L.ora_grid_max_trunc(self.h)
+        return self.max_trunc
 
     def store_text(self, path) -> bool:
         """TsdGrid::storeGrid: the reference's text format."""

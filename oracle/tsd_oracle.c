@@ -281,6 +281,13 @@ int ora_grid_tiles(const ora_grid* g) { return g->tiles; }
 double ora_grid_max_trunc(const ora_grid* g) { return g->max_trunc; }
 double ora_grid_max_x(const ora_grid* g) { return g->max_x; }
 
+/* TsdGrid::setMaxTruncation (TsdGrid.cpp:206-215) on a live grid: the clamp, nothing else is touched */
+void ora_grid_set_max_trunc(ora_grid* g, double val)
+{
+  if (val < 2 * g->cs) val = 2 * g->cs;
+  g->max_trunc = val;
+}
+
 /* TsdGridPartition::init (TsdGridPartition.cpp:88-134) */
 static void tile_init(ora_grid* g, int p)
 {

@@ -90,6 +90,7 @@ void      ora_grid_destroy(ora_grid* g);
 int       ora_grid_cells(const ora_grid* g);
 int       ora_grid_tiles(const ora_grid* g);
 double    ora_grid_max_trunc(const ora_grid* g);
+void      ora_grid_set_max_trunc(ora_grid* g, double val);   /* TsdGrid::setMaxTruncation (:206-215) */
 double    ora_grid_max_x(const ora_grid* g);
 int       ora_free_footprint(ora_grid* g, const double center[2], double width, double height);
 void      ora_grid_tile_state(const ora_grid* g, uint8_t* initialized, double* init_weight);

@@ -2,7 +2,9 @@
 """Randomised check of the ORACLE itself (CPU only, no GPU, test infrastructure): the independent NumPy / pure-Python re-derivations of
 tests/test_cpu_oracle_properties.py -- one push into an empty grid for every cell, the ray march with bilinear look-ups and normals, the
 closed-form and point-to-line estimators on the first step's pair list -- against oracle/tsd_oracle.c on random grids, scenes, scanners, poses and spoiled scans
-instead of the two or three fixed cases of the test suite.  usage: python3 tools/fuzz_oracle.py [cases] [first_seed]"""
+instead of the two or three fixed cases of the test suite.  "params": the truncation radius (1-40 cells, non-integers included),
+max_range (3-30 m), min_range (0.001-3 m) and low_reflectivity_range (0-12 m) are drawn per case as well, from a generator of their own:
+without it the cases of a seed are what they always were.  usage: python3 tools/fuzz_oracle.py [cases] [first_seed] [params]"""
 import math, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,6 +16,7 @@ import tests.test_cpu_oracle_properties as P
 O.build()
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+draw_params = len(sys.argv) > 3 and sys.argv[3] == "params"
 t0 = time.time()
 tot = dict(pushes=0, cells=0, beams=0, hits=0)
 for case in range(n_cases):
@@ -29,9 +32,19 @@ for case in range(n_cases):
         fov = math.radians(float(rng.uniform(60.0, 340.0)))
         geo = synth.ScanGeometry(nb, float(rng.uniform(-math.pi, math.pi - fov)) if fov < 2 * math.pi - 0.2 else -0.5 * fov, fov / (nb - 1))
     gc = synth.GridConfig(map_log2, cs)
+    max_range, min_range, low_refl = 30.0, 0.001, 2.0
+    if draw_params:
+        prng = np.random.default_rng([seed, 0x706172616D])
+        trunc = float(prng.integers(1, 41)) if prng.random() < 0.5 else float(prng.uniform(1.0, 40.0))
+        gc = synth.GridConfig(map_log2, cs, trunc)
+        max_range, min_range, low_refl = float(prng.uniform(3.0, 30.0)), float(prng.uniform(0.001, 3.0)), float(prng.uniform(0.0, 12.0))
+        if prng.random() < 0.2:
+            low_refl = 0.0
     world = synth.World(scene, gc)
     W = gc.cells * cs
     tag = f"seed {seed}: 2^{map_log2} cells @ {cs} m, {scene}, {geo.beams} beams from {geo.angle_min:.3f} rad"
+    if draw_params:
+        tag += f", truncation {gc.truncation_radius:.4g} cells, ranges {max_range:.3f} / {min_range:.3f} / {low_refl:.3f}"
     try:
         # ---- one push into an empty grid, every cell
         x = world.start[0] + rng.uniform(-0.1, 0.1) * W; y = world.start[1] + rng.uniform(-0.1, 0.1) * W; yaw = rng.uniform(-math.pi, math.pi)
@@ -40,11 +53,11 @@ for case in range(n_cases):
         if rng.random() < 0.5:
             for val in (0.0, np.nan, 45.0):
                 r32[rng.integers(0, len(r32), rng.integers(0, max(2, len(r32) // 40)))] = val
-        data, mask = O.ingest_f32(r32, 30.0, geo.angle_increment)
+        data, mask = O.ingest_f32(r32, max_range, geo.angle_increment)
         g = O.Grid(gc.map_size_log2, gc.cell_size, gc.max_trunc)
-        st = g.push(pose, data, mask, geo.angle_increment, geo.angle_min, 30.0, 0.001, 2.0)
+        st = g.push(pose, data, mask, geo.angle_increment, geo.angle_min, max_range, min_range, low_refl)
         init, iw, tsd, w = g.dump()
-        e_tsd, e_w, e_upd = P.numpy_push_from_empty(gc, geo, pose, data, mask, 30.0, 2.0)
+        e_tsd, e_w, e_upd = P.numpy_push_from_empty(gc, geo, pose, data, mask, max_range, low_refl)
         PX = gc.cells // 32
         n_upd = 0; edge = 0
         for p in np.nonzero(init)[0]:
@@ -63,16 +76,16 @@ for case in range(n_cases):
         # ---- ray cast (after two more pushes), beam by beam in pure Python: a sample of the beams
         for k in range(2):
             x2 = x + rng.uniform(-0.3, 0.3); y2 = y + rng.uniform(-0.3, 0.3); yaw2 = yaw + rng.uniform(-0.2, 0.2)
-            d2, m2 = O.ingest_f32(world.scan(x2, y2, yaw2, geo), 30.0, geo.angle_increment)
-            g.push(synth.pose_matrix(x2, y2, yaw2), d2, m2, geo.angle_increment, geo.angle_min, 30.0, 0.001, 2.0)
+            d2, m2 = O.ingest_f32(world.scan(x2, y2, yaw2, geo), max_range, geo.angle_increment)
+            g.push(synth.pose_matrix(x2, y2, yaw2), d2, m2, geo.angle_increment, geo.angle_min, max_range, min_range, low_refl)
         dump = g.dump()
         xr = x + rng.uniform(-0.3, 0.3); yr = y + rng.uniform(-0.3, 0.3); yawr = yaw + rng.uniform(-0.3, 0.3)
         poser = synth.pose_matrix(xr, yr, yawr)
         rl, rw = H.world_rays(O, geo, poser, gc.cell_size)
-        co, no, mo, cnt = g.raycast(poser, rw, 0.001, 30.0)
+        co, no, mo, cnt = g.raycast(poser, rw, min_range, max_range)
         Pi = np.linalg.inv(poser)
         for b in rng.choice(geo.beams, min(geo.beams, 60), replace=False):
-            hit, cx, cy = P._np_raycast_beam(gc, dump, (poser[0, 2], poser[1, 2]), (rw[b], rw[geo.beams + b]), 0.001, 30.0)
+            hit, cx, cy = P._np_raycast_beam(gc, dump, (poser[0, 2], poser[1, 2]), (rw[b], rw[geo.beams + b]), min_range, max_range)
             n = None
             if hit:
                 vals = [P._np_bilinear(gc, dump, cx + dx, cy + dy) for dx, dy in ((cs, 0), (-cs, 0), (0, cs), (0, -cs))]
@@ -94,7 +107,7 @@ for case in range(n_cases):
         # PointToLine2DEstimator (normal equations by np.linalg.solve) against Tlast of the oracle's first iteration
         M = co.reshape(-1, 2)[mo.astype(bool)]; Nn = no.reshape(-1, 2)[mo.astype(bool)]
         dxy = rng.uniform(-0.06, 0.06, 2); dya = rng.uniform(-0.02, 0.02)
-        d3, m3 = O.ingest_f32(world.scan(xr + dxy[0], yr + dxy[1], yawr + dya, geo), 30.0, geo.angle_increment)
+        d3, m3 = O.ingest_f32(world.scan(xr + dxy[0], yr + dxy[1], yawr + dya, geo), max_range, geo.angle_increment)
         sc, ms, _ = O.scene_from_scan(rl, d3, m3)
         S = sc.reshape(-1, 2)[ms.astype(bool)]
         bnd = (0.0, g.max_x, 0.0, g.max_x)

@@ -5,7 +5,9 @@ readings sprinkled in, then per case: pushes (stats + every cell), ray casts (hi
 (pairs / iterations / state exact, T 1e-9), occupancy maps (byte-exact).  Stops at the first mismatch and prints the seed.
 "hard": poses anywhere in the grid, at its edges and outside of it, any heading; registrations from up to 0.5 m / 0.2 rad away (few
 pairs, dropped points, not-matchable results) and with the point-to-line estimator.
-usage (GPU box): python3 tools/fuzz_parity.py [cases] [first_seed] [hard|easy] [big]"""
+"params" (in place of "big"): the truncation radius (1-40 cells, non-integers included), max_range (3-30 m), min_range (0.001-3 m) and
+low_reflectivity_range (0-12 m) are drawn per case too, from a generator of their own: without it the cases of a seed stay what they were.
+usage (GPU box): python3 tools/fuzz_parity.py [cases] [first_seed] [hard|easy] [big|params]"""
 import math, os, sys, tempfile, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,6 +19,7 @@ O.build()
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 hard = len(sys.argv) > 3 and sys.argv[3] == "hard"
+draw_params = len(sys.argv) > 4 and sys.argv[4] == "params"
 t_start = time.time()
 tot = dict(pushes=0, raycasts=0, icps=0, occs=0, files=0)
 
@@ -51,6 +54,14 @@ for case in range(n_cases):
         # of more than 12 288 tiles) and several tiles per workgroup on the full device
         map_log2, cs = 12, 0.01
     gc = synth.GridConfig(map_log2, cs)
+    MAX_RANGE, MIN_RANGE, LOW_REFL = H.MAX_RANGE, H.MIN_RANGE, H.LOW_REFL
+    if draw_params:
+        prng = np.random.default_rng([seed, 0x706172616D])
+        trunc = float(prng.integers(1, 41)) if prng.random() < 0.5 else float(prng.uniform(1.0, 40.0))
+        gc = synth.GridConfig(map_log2, cs, trunc)
+        MAX_RANGE, MIN_RANGE, LOW_REFL = float(prng.uniform(3.0, 30.0)), float(prng.uniform(0.001, 3.0)), float(prng.uniform(0.0, 12.0))
+        if prng.random() < 0.2:
+            LOW_REFL = 0.0
     world = synth.World(scene, gc)
     W = gc.cells * cs
     # a device that shows only a few compute units (TSD_DEBUG_N_CUS, read when the context is created): the update kernel's workgroups
@@ -63,6 +74,8 @@ for case in range(n_cases):
     dg = capi.TsdGridDevice(gc.map_size_log2, gc.cell_size, gc.max_trunc)
     content = np.full(gc.cells * gc.cells, -1, dtype=np.int8)
     tag = f"seed {seed}: 2^{map_log2} cells @ {cs} m, {scene}, {geo.beams} beams" + (f", {os.environ['TSD_DEBUG_N_CUS']} compute units" if "TSD_DEBUG_N_CUS" in os.environ else "")
+    if draw_params:
+        tag += f", truncation {gc.truncation_radius:.4g} cells, ranges {MAX_RANGE:.3f} / {MIN_RANGE:.3f} / {LOW_REFL:.3f}"
     try:
         # a cluster of poses around a random point of the free space near the start (pushes must overlap for the registration to work)
         x0 = world.start[0] + rng.uniform(-0.15, 0.15) * min(W, 20.0)
@@ -89,9 +102,9 @@ for case in range(n_cases):
             r32 = world.scan(x, y, yaw, geo)
             if rng.random() < 0.6:
                 r32 = spoil(rng, r32)
-            data, mask = O.ingest_f32(r32, H.MAX_RANGE, geo.angle_increment)
-            so = og.push(pose, data, mask, geo.angle_increment, geo.angle_min, H.MAX_RANGE, H.MIN_RANGE, H.LOW_REFL)
-            sd = dg.push(pose, data, mask, geo.angle_increment, geo.angle_min, H.MAX_RANGE, H.MIN_RANGE, H.LOW_REFL)
+            data, mask = O.ingest_f32(r32, MAX_RANGE, geo.angle_increment)
+            so = og.push(pose, data, mask, geo.angle_increment, geo.angle_min, MAX_RANGE, MIN_RANGE, LOW_REFL)
+            sd = dg.push(pose, data, mask, geo.angle_increment, geo.angle_min, MAX_RANGE, MIN_RANGE, LOW_REFL)
             if exact_pose:
                 # The cell whose centre is the sensor position to within rounding has no direction: PoseInv * centre is ~1e-15 of noise
                 # (the oracle's LU inverse and the library's differ in the last bit), and atan2 of noise names an arbitrary beam.  Any
@@ -162,8 +175,8 @@ for case in range(n_cases):
                 yaw = round(yaw / qa) * qa
             pose = synth.pose_matrix(x, y, yaw)
             rl, rw = H.world_rays(O, geo, pose, gc.cell_size)
-            co, no_, mo, cnt_o = og.raycast(pose, rw, H.MIN_RANGE, H.MAX_RANGE)
-            cd, nd_, md, cnt_d = dg.raycast(pose, rw, H.MIN_RANGE, H.MAX_RANGE)
+            co, no_, mo, cnt_o = og.raycast(pose, rw, MIN_RANGE, MAX_RANGE)
+            cd, nd_, md, cnt_d = dg.raycast(pose, rw, MIN_RANGE, MAX_RANGE)
             assert np.array_equal(mo, md), f"ray cast {k}: hit masks differ at beams {np.nonzero(mo != md)[0][:10]}"
             sel = np.repeat(mo.astype(bool), 2)
             if sel.any():
@@ -176,7 +189,7 @@ for case in range(n_cases):
             r32 = world.scan(x + dxy[0], y + dxy[1], yaw + dyaw, geo)
             if rng.random() < 0.5:
                 r32 = spoil(rng, r32)
-            data, mask = O.ingest_f32(r32, H.MAX_RANGE, geo.angle_increment)
+            data, mask = O.ingest_f32(r32, MAX_RANGE, geo.angle_increment)
             scn, ms, _ = O.scene_from_scan(rl, data, mask)
             M = co.reshape(-1, 2)[mo.astype(bool)]
             S = scn.reshape(-1, 2)[ms.astype(bool)]
