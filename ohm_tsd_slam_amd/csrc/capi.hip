@@ -307,6 +307,20 @@ int drain_async_push(tsd_ctx* ctx)
   return TSD_OK;
 }
 
+// What the push keeps per tile and per run -- dirty flags, last records, totals, push counts, list counters -- as a fresh grid has
+// them, on the context's stream; the ledger forgets the pushes along with them.
+int reset_push_bookkeeping(tsd_ctx* ctx)
+{
+  const size_t T = (size_t)ctx->grid.tiles;
+  TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_dirty, 0, T, ctx->stream));
+  TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_tile_rec, 0, T * sizeof(uint32_t), ctx->stream));
+  TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_tile_totals, 0, T * 8 * sizeof(uint32_t), ctx->stream));
+  TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_pushes, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_list_cnt, 0, push_list_cnt_bytes(), ctx->stream));
+  ctx->ledger.grid_reset();
+  return TSD_OK;
+}
+
 }  // namespace tsd
 
 using namespace tsd;
@@ -505,37 +519,27 @@ void tsd_destroy(tsd_ctx* ctx)
 
 int tsd_reset(tsd_ctx* ctx)
 {
-  if (ctx) ctx->epoch++;                  // (invalidates ray casts enqueued ahead of their scan)
   if (!ctx) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
-  std::lock_guard<std::mutex> lk_order(ctx->order_mutex);
-  if (int rcw = wait_for_readers(ctx)) return rcw;
+  if (int rc = enter(ctx)) return rc;
+  WriterScope w(ctx); if (w.rc) return w.rc;
   GridDev& g = ctx->grid;
   const size_t T = (size_t)g.tiles;
   // cells are materialised lazily (flags == 0 means "no cell storage yet", TsdGridPartition.cpp:88)
   TSD_HIP_CHECK(ctx, hipMemsetAsync(g.flags, 0, T, ctx->stream));
   TSD_HIP_CHECK(ctx, hipMemsetAsync(g.init_weight, 0, T * sizeof(double), ctx->stream));
-  TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_dirty, 0, T, ctx->stream));
   TSD_HIP_CHECK(ctx, hipMemsetAsync(g.negmask, 0, T * sizeof(unsigned long long), ctx->stream));
-  TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_tile_rec, 0, T * sizeof(uint32_t), ctx->stream));
-  TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_tile_totals, 0, T * 8 * sizeof(uint32_t), ctx->stream));
-  TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_pushes, 0, 2 * sizeof(unsigned long long), ctx->stream));
-  ctx->box_prev = TileBox{}; ctx->box_dirty = TileBox{};
-  ctx->frame_prev_valid = false;          // (the next tsd_map_update_begin takes a full frame)
-  TSD_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_list_cnt, 0, push_list_cnt_bytes(), ctx->stream));
+  if (int rc = reset_push_bookkeeping(ctx)) return rc;
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return TSD_OK;
 }
 
 int tsd_set_max_truncation(tsd_ctx* ctx, double val)
 {
-  if (ctx) ctx->epoch++;                  // (invalidates ray casts enqueued ahead of their scan)
   if (!ctx) return TSD_E_ARG;
   // TsdGrid::setMaxTruncation (TsdGrid.cpp:206-215): at least 2 x cell size
   if (val < 2 * ctx->grid.cs) val = 2 * ctx->grid.cs;
   ctx->grid.max_trunc = val;
-  ctx->frame_prev_valid = false;          // (the next tsd_map_update_begin takes a full frame)
+  ctx->ledger.grid_rewritten();
   return TSD_OK;
 }
 
@@ -562,10 +566,8 @@ double tsd_max_y(const tsd_ctx* ctx) { return ctx ? ctx->grid.max_y : 0.0; }
 
 int tsd_free_footprint(tsd_ctx* ctx, const double center[2], double width, double height)
 {
-  if (ctx) ctx->epoch++;                  // (invalidates ray casts enqueued ahead of their scan)
   if (!ctx || !center) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   const GridDev& g = ctx->grid;
   // TsdGrid.cpp:611-622
   const unsigned minX = static_cast<unsigned>((center[0] - width * 0.5) / g.cs + 0.5);
@@ -575,8 +577,7 @@ int tsd_free_footprint(tsd_ctx* ctx, const double center[2], double width, doubl
   const unsigned N = (unsigned)g.N;
   if (minX > N || maxX > N || minY > N || maxY > N)
     return set_error(ctx, TSD_E_BOUNDS, "freeFootprint: indices out of bounds", hipSuccess);
-  std::lock_guard<std::mutex> lk_order(ctx->order_mutex);
-  if (int rcw = wait_for_readers(ctx)) return rcw;
+  WriterScope w(ctx); if (w.rc) return w.rc;
   // cells == N would index past the last tile in the reference (undefined there); clamp
   const unsigned cx1 = maxX > N ? N : maxX, cy1 = maxY > N ? N : maxY;
   return launch_free_footprint(ctx, minX, cx1, minY, cy1);
@@ -594,11 +595,9 @@ int tsd_push(tsd_ctx* ctx, const double pose33[9], const double* ranges, const u
              int beams, double ang_res, double phi_min, double max_range, double min_range,
              double low_refl_range, tsd_push_stats* stats)
 {
-  if (ctx) ctx->epoch++;                  // (invalidates ray casts enqueued ahead of their scan)
   if (!ctx || !pose33 || !ranges || !mask) return TSD_E_ARG;
   if (beams < 1 || beams > TSD_MAX_BEAMS) return set_error(ctx, TSD_E_CAPACITY, "beams out of range", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   PushArgs a;
   double Pi[9];
   mat3_inv(pose33, Pi);
@@ -620,11 +619,9 @@ int tsd_push(tsd_ctx* ctx, const double pose33[9], const double* ranges, const u
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_push_args, h + (size_t)TSD_MAX_BEAMS * 9, sizeof(a), hipMemcpyHostToDevice, ctx->stream));
   TSD_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[s], ctx->stream));
 
-  std::lock_guard<std::mutex> lk_order(ctx->order_mutex);
-  int rc = wait_for_readers(ctx);
-  if (rc != TSD_OK) return rc;
+  WriterScope w(ctx); if (w.rc) return w.rc;
   const PushJob job{ctx->d_push_args, ctx->d_ranges, ctx->d_mask, next_ctx_tables(ctx), a.trx, a.try_, 0.0, beams, max_range};
-  rc = launch_push_tables(ctx, ctx->stream, beams, job.ranges, job.mask, job.rmq, phi_min, ang_res);
+  int rc = launch_push_tables(ctx, ctx->stream, beams, job.ranges, job.mask, job.rmq, phi_min, ang_res);
   if (rc != TSD_OK) return rc;
   rc = launch_push(ctx, ctx->stream, job);
   if (rc != TSD_OK) return rc;
@@ -639,11 +636,10 @@ int tsd_raycast(tsd_ctx* ctx, const double pose33[9], const double* rays_world_2
                 double min_range, double max_range, double* coords_2B, double* normals_2B,
                 uint8_t* mask_B, int* n_valid)
 {
-  if (ctx) ctx->epoch++;                  // (invalidates ray casts enqueued ahead of their scan)
   if (!ctx || !pose33 || !rays_world_2xB || !coords_2B || !normals_2B || !mask_B) return TSD_E_ARG;
   if (beams < 1 || beams > TSD_MAX_BEAMS) return set_error(ctx, TSD_E_CAPACITY, "beams out of range", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
+  ctx->ledger.outputs_overwritten();
   RaycastArgs a;
   fill_raycast_args(ctx, a, pose33, beams, min_range, max_range);
   int s;
@@ -732,7 +728,6 @@ int tsd_icp_normals(tsd_ctx* ctx, const double* model_xy, const double* model_no
                     const double* scene_xy, int n_scene, const double pose33[9], const tsd_icp_params* params,
                     tsd_icp_result* result)
 {
-  if (ctx) ctx->epoch++;                  // (invalidates ray casts enqueued ahead of their scan)
   if (!ctx || !pose33 || !params || !result || n_model < 0 || n_scene < 0) return TSD_E_ARG;
   if (params->estimator != TSD_ESTIMATOR_CLOSED_FORM && params->estimator != TSD_ESTIMATOR_POINT_TO_LINE)
     return set_error(ctx, TSD_E_ARG, "tsd_icp_params.estimator", hipSuccess);
@@ -741,8 +736,8 @@ int tsd_icp_normals(tsd_ctx* ctx, const double* model_xy, const double* model_no
   if ((n_model > 0 && !model_xy) || (n_scene > 0 && !scene_xy)) return TSD_E_ARG;
   if (n_model > TSD_MAX_ICP_POINTS || n_scene > TSD_MAX_ICP_POINTS)
     return set_error(ctx, TSD_E_CAPACITY, "icp points > TSD_MAX_ICP_POINTS", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
+  ctx->ledger.outputs_overwritten();
   IcpArgs a;
   fill_icp_args(a, pose33, params);
   a.n_model = n_model; a.n_scene = n_scene; a.beams = 0;
@@ -760,14 +755,13 @@ int tsd_icp_normals(tsd_ctx* ctx, const double* model_xy, const double* model_no
 int tsd_icp_pairs(tsd_ctx* ctx, const double* model_xy, int n_model, const double* scene_xy, int n_scene, const double pose33[9],
                   const tsd_icp_params* params, int calls, int* n_pairs, int* model_idx, int* scene_idx)
 {
-  if (ctx) ctx->epoch++;
   if (!ctx || !pose33 || !params || !n_pairs || !model_idx || !scene_idx || n_model < 1 || n_scene < 1 || !model_xy || !scene_xy) return TSD_E_ARG;
   if (calls < 1 || calls > TSD_ICP_TRACE_MAX) return set_error(ctx, TSD_E_ARG, "tsd_icp_pairs: calls out of range", hipSuccess);
   if (params->estimator != TSD_ESTIMATOR_CLOSED_FORM) return set_error(ctx, TSD_E_ARG, "tsd_icp_pairs: closed-form instantiation only", hipSuccess);
   if (n_model > TSD_MAX_ICP_POINTS || n_scene > TSD_MAX_ICP_POINTS)
     return set_error(ctx, TSD_E_CAPACITY, "icp points > TSD_MAX_ICP_POINTS", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
+  ctx->ledger.outputs_overwritten();
   IcpArgs a;
   fill_icp_args(a, pose33, params);        // (the threshold schedule comes from params->iterations, like the node's DistanceFilter)
   a.n_model = n_model; a.n_scene = n_scene; a.beams = 0;
@@ -811,12 +805,11 @@ int tsd_localize(tsd_ctx* ctx, const double pose33[9], const double* rays_world_
                  double min_range, double max_range, const tsd_icp_params* params,
                  tsd_icp_result* result)
 {
-  if (ctx) ctx->epoch++;                  // (invalidates ray casts enqueued ahead of their scan)
   if (!ctx || !pose33 || !rays_world_2xB || !rays_local_2xB || !ranges || !mask || !params || !result) return TSD_E_ARG;
   if (beams < 1 || beams > TSD_MAX_BEAMS || beams > TSD_MAX_ICP_POINTS)
     return set_error(ctx, TSD_E_CAPACITY, "beams out of range for fused localize", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
+  ctx->ledger.outputs_overwritten();
   const size_t nb = (size_t)beams;
   int s;
   char* h = stage_acquire(ctx, &s);
@@ -854,8 +847,7 @@ int tsd_localize(tsd_ctx* ctx, const double pose33[9], const double* rays_world_
 int tsd_icp_trace(tsd_ctx* ctx, double* out, int max_iters)
 {
   if (!ctx || !out || max_iters < 0) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   const int n = max_iters < 2 * TSD_ICP_TRACE_MAX ? max_iters : 2 * TSD_ICP_TRACE_MAX;     // (rows beyond TSD_ICP_TRACE_MAX: diagnostic builds' scratch)
   // (every copy of this library goes through the context's own stream: a plain hipMemcpy / hipMemset brings the NULL stream
   // alive, and that stream takes one of the few hardware queues the scan / batch streams are mapped onto -- DESIGN 5)

@@ -28,6 +28,18 @@ int read_last_push_stats(tsd_ctx* ctx, tsd_push_stats* out);
 int read_total_stats(tsd_ctx* ctx, tsd_push_stats* out, int64_t* pushes, bool reset);
 bool host_saw_event(hipEvent_t ev, int us);         // true once `ev` has completed; polls for at most ~`us` microseconds
 int wait_for_readers(tsd_ctx* ctx);                 // grid writes on the context's stream go behind the ray casts of the split path
+int reset_push_bookkeeping(tsd_ctx* ctx);           // the push's per-tile records, totals and counters as a fresh grid has them (capi.hip)
+
+// The top of an entry point that enqueues on the context's stream: the context's device, and behind a push that asynchronous
+// mapping left on the push stream.  `if (int rc = enter(ctx)) return rc;`
+inline int enter(tsd_ctx* ctx) { TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device)); return drain_async_push(ctx); }
+// The ordered section of an entry point that writes the grid: holds ctx->order_mutex (held = true: the caller holds it already,
+// tsd_fuse_begin with several contexts') and has put the context's stream behind the split path's ray casts in flight.
+// `WriterScope w(ctx); if (w.rc) return w.rc;`
+struct WriterScope {
+  std::unique_lock<std::mutex> lk; int rc;
+  explicit WriterScope(tsd_ctx* ctx, bool held = false) : lk(ctx->order_mutex, std::defer_lock) { if (!held) lk.lock(); rc = wait_for_readers(ctx); }
+};
 
 inline unsigned long long now_ns()
 {

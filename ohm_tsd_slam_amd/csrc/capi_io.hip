@@ -9,8 +9,7 @@ extern "C" {
 int tsd_download_tile_state(tsd_ctx* ctx, uint8_t* initialized, double* init_weight)
 {
   if (!ctx || !initialized || !init_weight) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   const size_t T = (size_t)ctx->grid.tiles;
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(initialized, ctx->grid.flags, T, hipMemcpyDeviceToHost, ctx->stream));
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(init_weight, ctx->grid.init_weight, T * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -59,15 +58,17 @@ int tsd_download_tiles(tsd_ctx* ctx, uint8_t* initialized, double* init_weight, 
 int tsd_upload_tiles(tsd_ctx* ctx, const uint8_t* initialized, const double* init_weight,
                      const double* tsd_in, const double* weight_in)
 {
-  if (ctx) ctx->epoch++;                  // (invalidates ray casts enqueued ahead of their scan)
   if (!ctx || !initialized || !init_weight || !tsd_in || !weight_in) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
-  std::lock_guard<std::mutex> lk_order(ctx->order_mutex);
-  if (int rcw = wait_for_readers(ctx)) return rcw;
+  if (int rc = enter(ctx)) return rc;
+  WriterScope w(ctx); if (w.rc) return w.rc;
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   const GridDev& g = ctx->grid;
   const size_t T = (size_t)g.tiles;
+  // The halos come as they are given (the text format does not store them: NaN): nothing says they agree with the neighbours' edge
+  // cells, which the incremental propagateBorders of the push relies on for the tiles it does not touch.  Every tile that holds data is
+  // marked like a freeFootprint write (d_dirty below): the next push refreshes the halos around all of them -- the reference's full
+  // sweep after its first push (TsdGrid.cpp:372-427).
+  { TileBox all; all.x0 = 0; all.y0 = 0; all.x1 = g.PX - 1; all.y1 = g.PX - 1; ctx->ledger.grid_uploaded(all); }
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(g.flags, initialized, T, hipMemcpyHostToDevice, ctx->stream));
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(g.init_weight, init_weight, T * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -93,16 +94,7 @@ int tsd_upload_tiles(tsd_ctx* ctx, const uint8_t* initialized, const double* ini
   if (rc != TSD_OK) return rc;
   rc = launch_neg_scan(ctx);              // which tiles can show a sign change to the ray cast
   if (rc != TSD_OK) return rc;
-  // The halos came as they were given (the text format does not store them: NaN): nothing says they agree with the neighbours' edge
-  // cells, which the incremental propagateBorders of the push relies on for the tiles it does not touch.  Every tile that holds data is
-  // marked like a freeFootprint write: the next push refreshes the halos around all of them -- the reference's full sweep after its
-  // first push (TsdGrid.cpp:372-427).
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_dirty, initialized, T, hipMemcpyHostToDevice, ctx->stream));
-  {
-    TileBox all; all.x0 = 0; all.y0 = 0; all.x1 = g.PX - 1; all.y1 = g.PX - 1;
-    ctx->box_dirty.add(all);
-    ctx->frame_prev_valid = false;        // (the next tsd_map_update_begin takes a full frame)
-  }
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return TSD_OK;
 }
@@ -110,8 +102,7 @@ int tsd_upload_tiles(tsd_ctx* ctx, const uint8_t* initialized, const double* ini
 int tsd_grid_digest(tsd_ctx* ctx, tsd_grid_digest_t* out)
 {
   if (!ctx || !out) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   const size_t T = (size_t)ctx->grid.tiles;
   unsigned long long* d_o = nullptr; double* d_s = nullptr;
   TSD_HIP_CHECK(ctx, hipMalloc(&d_o, T * 2 * sizeof(unsigned long long)));
@@ -243,8 +234,7 @@ int tsd_load_grid_text(tsd_ctx* ctx, const char* path)
 int tsd_occupancy_dev_async(tsd_ctx* ctx, void* occ_dev, int inflate, int inflate_factor)
 {
   if (!ctx || !occ_dev) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   return launch_occupancy(ctx, static_cast<int8_t*>(occ_dev), inflate, inflate_factor);
 }
 
@@ -259,8 +249,7 @@ int tsd_occupancy_dev(tsd_ctx* ctx, void* occ_dev, int inflate, int inflate_fact
 int tsd_color_image(tsd_ctx* ctx, uint8_t* rgb_host, unsigned int width, unsigned int height)
 {
   if (!ctx || !rgb_host || width == 0 || height == 0) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   // px / py exactly as the reference accumulates them (TsdGrid.cpp:433-486): start at 0, += step per pixel
   std::vector<double> pq((size_t)width + height);
   const double stepW = ctx->grid.max_x / (double)width, stepH = ctx->grid.max_y / (double)height;
@@ -290,8 +279,7 @@ int tsd_color_image(tsd_ctx* ctx, uint8_t* rgb_host, unsigned int width, unsigne
 int tsd_occupancy(tsd_ctx* ctx, int8_t* occ_host, int inflate, int inflate_factor, int* n_surface)
 {
   if (!ctx || !occ_host) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   const size_t cells = (size_t)ctx->grid.N * ctx->grid.N;
   if (!ctx->d_occ_out) TSD_HIP_CHECK(ctx, hipMalloc(&ctx->d_occ_out, cells));      // once per context (see tsd_color_image)
   // The map leaves on a stream of its own behind the extraction kernels' event: 16 MiB at 4096^2 are ~0.7 ms of PCIe, and on the grid's
@@ -319,8 +307,7 @@ int tsd_occupancy(tsd_ctx* ctx, int8_t* occ_host, int inflate, int inflate_facto
 int tsd_calibrate_rmw(tsd_ctx* ctx, int64_t n_doubles, int reps)
 {
   if (!ctx || n_doubles <= 0 || reps <= 0) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   double *t = nullptr, *w = nullptr;
   TSD_HIP_CHECK(ctx, hipMalloc(&t, (size_t)n_doubles * sizeof(double)));
   hipError_t e = hipMalloc(&w, (size_t)n_doubles * sizeof(double));
@@ -337,8 +324,7 @@ int tsd_calibrate_rmw(tsd_ctx* ctx, int64_t n_doubles, int reps)
 int tsd_measure_stream(tsd_ctx* ctx, int64_t n_doubles, int reps, double* gbs_best, double* gbs_mean)
 {
   if (!ctx || n_doubles <= 0 || reps <= 0 || reps > 64) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   double *t = nullptr, *w = nullptr;
   const size_t bytes = (size_t)n_doubles * sizeof(double);
   TSD_HIP_CHECK(ctx, hipMalloc(&t, bytes));
@@ -464,8 +450,7 @@ int tsd_profile_get_samples(tsd_ctx* ctx, const char* kernel, float* ms_out, int
 int tsd_push_stats_total(tsd_ctx* ctx, tsd_push_stats* total, int64_t* pushes, int reset)
 {
   if (!ctx) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   return read_total_stats(ctx, total, pushes, reset != 0);
 }
 

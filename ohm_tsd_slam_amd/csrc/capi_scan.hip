@@ -196,11 +196,10 @@ void tsd_sensor_destroy(tsd_sensor* s)
 int tsd_sensor_set_pose(tsd_sensor* s, const double pose33[9], const double* rays_world_2xB,
                         const double* rays_local_2xB)
 {
-  if (s && s->ctx) s->ctx->epoch++;
   if (!s || !s->ctx || !pose33 || !rays_world_2xB || !rays_local_2xB) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
+  ctx->ledger.outputs_overwritten();
   const size_t nb = (size_t)s->beams;
   SensorDev st;
   std::memset(&st, 0, sizeof(st));
@@ -337,8 +336,7 @@ int tsd_sensor_set_async_mapping(tsd_sensor* s, int on)
   if (!s || !s->ctx) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
   if (s->fused.submitted) return set_error(ctx, TSD_E_ARG, "tsd_sensor_set_async_mapping: a scan is in flight", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   if (on) {
     if (!ctx->stream_push) TSD_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->stream_push, hipStreamNonBlocking));
     // (both events order kernels of ONE device against each other: no system-scope fence when they complete)
@@ -440,7 +438,7 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
   // something touched the grid, the sensor or the context's ray-cast outputs since.
   const LaunchTarget tg = ctx_target(ctx);
   const RaycastArgs ra = sensor_raycast_launch_args(s);
-  if (!(s->fused.rc_pending && s->fused.rc_epoch == ctx->epoch)) {
+  if (!(s->fused.rc_pending && s->fused.rc_epoch == ctx->ledger.epoch())) {
     if (int rcd_ = drain_async_push(ctx)) return rcd_;     // (asynchronous mapping: a push still on the push stream comes first)
     rc = launch_raycast(ctx, tg, ra, &s->d_state->rc, s->d_rays);
     if (rc != TSD_OK) return rc;
@@ -505,7 +503,6 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     // (the push's halo pass is left to the ray cast that follows it at once: k_raycast's prologue, raycast_kernels.hip)
     rc = launch_push(ctx, ctx->stream, job, halo_in_raycast ? &halo : nullptr);
     if (rc != TSD_OK) return rc;
-    ctx->epoch++;                                          // the grid changes
     lap.lap(4);
     // the next scan's ray cast, right behind the push (see above): the host's work on the next scan no longer sits
     // between this push and that ray cast
@@ -514,7 +511,7 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
       if (halo_in_raycast) (void)launch_push_halo(ctx, ctx->stream, halo);      // (the grid's halos must not stay behind the push whatever happened to the ray cast)
       return rc;
     }
-    s->fused.rc_pending = true; s->fused.rc_epoch = ctx->epoch;
+    s->fused.rc_pending = true; s->fused.rc_epoch = ctx->ledger.epoch();      // (as the push left it)
     lap.lap(5);
   } else {
     // Asynchronous mapping (the reference's ThreadMapping: queuePush returns at once and the push lands when the mapping thread gets
@@ -539,8 +536,8 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_async_push, ctx->stream_push));
     (void)hipStreamQuery(ctx->stream_push);
     ctx->async_pending = true;
-    ctx->epoch++;                                          // the grid changes ...
-    s->fused.rc_pending = true; s->fused.rc_epoch = ctx->epoch;        // ... and the ray cast enqueued above is, by design, the one that does not see it
+    // (the push moved the epoch: the ray cast enqueued above is, by design, the one that does not see it)
+    s->fused.rc_pending = true; s->fused.rc_epoch = ctx->ledger.epoch();
     lap.lap(5);
   }
   s->fused.submitted = true;
@@ -631,8 +628,7 @@ int tsd_scan_begin(tsd_sensor* s, const double* ranges, const uint8_t* mask, con
   tsd_ctx* ctx = s->ctx;
   if (!s->posed) return set_error(ctx, TSD_E_ARG, "tsd_scan_begin before tsd_sensor_set_pose", hipSuccess);
   if (s->split.inflight) return set_error(ctx, TSD_E_ARG, "tsd_scan_begin: the previous scan of this sensor was not finished", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   int rc = sensor_conc_init(s, true);
   if (rc != TSD_OK) return rc;
   Lap lap(g_conc_timing);
@@ -690,8 +686,7 @@ int tsd_scan_finish(tsd_sensor* s, tsd_scan_result* result)
 {
   if (!s || !s->ctx || !result || !s->split.inflight) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   Lap lap(g_conc_timing);
   int rc = tsd_scan_wait(s);
   if (rc != TSD_OK) return set_error(ctx, TSD_E_HIP, "tsd_scan_finish: result record never arrived", hipSuccess);
@@ -703,13 +698,11 @@ int tsd_scan_finish(tsd_sensor* s, tsd_scan_result* result)
     // order by ENQUEUE time: a push enqueued early would pull every later ray cast of every robot behind its own
     // registration and serialise the robots; measured: 3.7 k scans/s for any N).  Behind the ray casts ticketed since
     // the last grid write.
-    std::lock_guard<std::mutex> lk_order(ctx->order_mutex);
+    WriterScope w(ctx); if (w.rc) return w.rc;
     lap.lap(5);
     TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, s->split.ev_icp_done, 0));
-    if (int rcw = wait_for_readers(ctx)) return rcw;
     rc = launch_push(ctx, ctx->stream, sensor_push_job(s, s->split.scan, s->d_rmq2[s->split.rmq_slot], s->split.gates));
     if (rc != TSD_OK) return rc;
-    ctx->epoch++;
     lap.lap(6);
   }
   deliver_result(s, result, 0);
@@ -853,8 +846,7 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
     if (s->split.inflight) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin: a sensor has a scan in flight already", hipSuccess);
     for (int j = 0; j < i; j++) if (sensors[j] == s) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin: a sensor appears twice", hipSuccess);
   }
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   for (int i = 0; i < n; i++) if (int rc = sensor_conc_init(sensors[i], false)) return rc;
 
   // staging: [registration entries | ray-cast entries | tables entries | scan 0 | scan 1 ...], one copy for all of it, into the
@@ -976,12 +968,10 @@ int tsd_batch_push(tsd_batch* b)
   if (!b || !b->ctx) return TSD_E_ARG;
   if (!b->n || b->push_enqueued) return TSD_OK;
   tsd_ctx* ctx = b->ctx;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
-  std::lock_guard<std::mutex> lk_order(ctx->order_mutex);
+  if (int rc = enter(ctx)) return rc;
+  WriterScope w(ctx); if (w.rc) return w.rc;
   const bool gate = b->dev_wait;                          // (else: the stream event for the whole batch's kernel)
   if (!gate) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_icp_done, 0));
-  if (int rcw = wait_for_readers(ctx)) return rcw;
   const int n = b->n;
   PushJob jobs[TSD_BATCH_MAX_SCANS];
   for (int i = 0; i < n; i++) {
@@ -1008,7 +998,6 @@ int tsd_batch_push(tsd_batch* b)
       if (int rc = launch_push(ctx, ctx->stream, jobs[i])) return rc;
     }
   }
-  ctx->epoch++;
   b->push_enqueued = true;
   return TSD_OK;
 }

@@ -245,15 +245,13 @@ int tsd_fuse_begin(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell
   held.reserve(all.size());
   for (tsd_ctx* c : all) held.emplace_back(c->order_mutex);
 
-  dst->epoch++;                             // (invalidates ray casts enqueued ahead of their scan)
-  TSD_HIP_CHECK(dst, hipSetDevice(dst->device));
+  if (int rc = enter(dst)) return rc;
   if (!dst->d_fuse_stats) {
     TSD_HIP_CHECK(dst, hipMalloc(&dst->d_fuse_stats, kFuseStatBytes));
     TSD_HIP_CHECK(dst, hipHostMalloc(&dst->h_fuse_stats, kFuseStatBytes, hipHostMallocDefault));
   }
   a.stats = dst->d_fuse_stats;
-  if (int rc = drain_async_push(dst)) return rc;
-  if (int rc = wait_for_readers(dst)) return rc;
+  WriterScope w(dst, /*held=*/true); if (w.rc) return w.rc;
   for (int i = 0; i < n; i++) {
     tsd_ctx* m = src[i];
     if (int rc = fuse_event(dst, &m->ev_fuse_src)) return rc;
@@ -267,14 +265,7 @@ int tsd_fuse_begin(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell
     }
   }
   // the push bookkeeping as tsd_reset leaves it: the fused halos agree with their neighbours, nothing is dirty
-  const size_t T = (size_t)g.tiles;
-  TSD_HIP_CHECK(dst, hipMemsetAsync(dst->d_dirty, 0, T, dst->stream));
-  TSD_HIP_CHECK(dst, hipMemsetAsync(dst->d_tile_rec, 0, T * sizeof(uint32_t), dst->stream));
-  TSD_HIP_CHECK(dst, hipMemsetAsync(dst->d_tile_totals, 0, T * 8 * sizeof(uint32_t), dst->stream));
-  TSD_HIP_CHECK(dst, hipMemsetAsync(dst->d_pushes, 0, 2 * sizeof(unsigned long long), dst->stream));
-  TSD_HIP_CHECK(dst, hipMemsetAsync(dst->d_list_cnt, 0, push_list_cnt_bytes(), dst->stream));
-  dst->box_prev = TileBox{}; dst->box_dirty = TileBox{};
-  dst->frame_prev_valid = false;          // (the next tsd_map_update_begin takes a full frame)
+  if (int rc = reset_push_bookkeeping(dst)) return rc;
   TSD_HIP_CHECK(dst, hipMemsetAsync(dst->d_fuse_stats, 0, kFuseStatBytes, dst->stream));
   if (int rc = launch_fuse(dst, a)) return rc;
   for (int i = 0; i < n; i++) {

@@ -148,7 +148,7 @@ static int ensure_frame_staging(tsd_ctx* ctx, bool image)
   // (a frame's staging is only replaced between frames: the last one's copies are done, tsd_map_frame_wait has seen them)
   if (ctx->d_frame) hipFree(ctx->d_frame);
   ctx->d_frame = nullptr; ctx->frame_bytes = 0;
-  ctx->frame_prev_valid = false;          // (a windowed frame has nothing to build on)
+  ctx->ledger.frame_lost();               // (a windowed frame has nothing to build on)
   TSD_HIP_CHECK(ctx, hipMalloc(&ctx->d_frame, need));
   // px / py exactly as the reference accumulates them (TsdGrid.cpp:433-486), then the tile ranges of the monotone tables
   std::vector<char> h(tab_bytes - 256);
@@ -176,29 +176,26 @@ static int ensure_frame_staging(tsd_ctx* ctx, bool image)
 }
 
 // tsd_map_frame_begin (win == nullptr) and tsd_map_update_begin: the whole map, or -- where the staging holds the previous frame of the
-// same parameters and the grid was not rewritten wholesale since -- the window around ctx->box_frame
+// same parameters and the grid was not rewritten wholesale since -- the window around the ledger's frame box
 static int frame_begin(tsd_ctx* ctx, const tsd_map_params* prm, int8_t* occ_host, uint8_t* rgb_host, tsd_map_window* win, const char* who)
 {
   if (!ctx || !prm || !occ_host) return TSD_E_ARG;
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (ctx->frame_inflight) return set_error(ctx, TSD_E_ARG, (std::string(who) + ": a frame is in flight (tsd_map_frame_wait first)").c_str(), hipSuccess);
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
   std::lock_guard<std::mutex> lk_order(ctx->order_mutex);
   const bool image = rgb_host != nullptr;
   if (int rc = ensure_frame_staging(ctx, image)) return rc;
   const GridDev& g = ctx->grid;
   const size_t N = (size_t)g.N, PX = (size_t)g.PX, cells = N * N;
   const int inflate = prm->inflate ? 1 : 0, factor = prm->inflate_factor;
-  // (with factor > 31 a mark at u + factor > N spills into the next row, far from any window: DESIGN 3.4)
-  const bool windowed = win && ctx->frame_prev_valid && (!image || ctx->frame_prev_image) && ctx->frame_prev_inflate == inflate &&
-                        (!inflate || (ctx->frame_prev_factor == factor && factor >= 0 && factor <= 31));
-  if (windowed && ctx->box_frame.empty()) {
+  const bool windowed = win && ctx->ledger.frame_may_be_windowed(image, inflate, factor);
+  if (windowed && ctx->ledger.frame_box().empty()) {
     win->x = win->y = win->width = win->height = 0;
     *ctx->h_frame_count = 0;
     ctx->frame_empty = true; ctx->frame_inflight = true;
     return TSD_OK;
   }
-  ctx->frame_prev_valid = false;            // (until this one is enqueued completely)
+  ctx->ledger.frame_started();
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t tab_bytes = up(256 + 2 * N * sizeof(double) + 2 * (PX + 1) * sizeof(int));
   int* d_count = reinterpret_cast<int*>(ctx->d_frame);
@@ -216,7 +213,7 @@ static int frame_begin(tsd_ctx* ctx, const tsd_map_params* prm, int8_t* occ_host
   TileBox u; u.x0 = 0; u.y0 = 0; u.x1 = (int)PX - 1; u.y1 = (int)PX - 1;
   if (windowed) {
     const int grow = window_growth(inflate, factor);
-    u = grow_box(ctx->box_frame, grow, (int)PX);
+    u = grow_box(ctx->ledger.frame_box(), grow, (int)PX);
     const TileBox m = grow_box(u, grow, (int)PX);
     const FrameWindow fw{u.x0, u.y0, u.x1, u.y1, m.x0, m.y0, m.x1 - m.x0 + 1};
     const int n_m = fw.mnx * (m.y1 - m.y0 + 1);
@@ -260,9 +257,7 @@ static int frame_begin(tsd_ctx* ctx, const tsd_map_params* prm, int8_t* occ_host
     win->x = u.x0 * TILE_DIM; win->y = u.y0 * TILE_DIM;
     win->width = (u.x1 - u.x0 + 1) * TILE_DIM; win->height = (u.y1 - u.y0 + 1) * TILE_DIM;
   }
-  ctx->box_frame = TileBox{};
-  ctx->frame_prev_valid = true; ctx->frame_prev_image = image;
-  ctx->frame_prev_inflate = inflate; ctx->frame_prev_factor = factor;
+  ctx->ledger.frame_enqueued(image, inflate, factor);
   ctx->frame_empty = false; ctx->frame_inflight = true;
   return TSD_OK;
 }
@@ -274,7 +269,7 @@ static int frame_wait(tsd_ctx* ctx, int* n_surface, const char* who)
   ctx->frame_inflight = false;
   if (!ctx->frame_empty) {
     const hipError_t e = hipEventSynchronize(ctx->ev_frame_done);
-    if (e != hipSuccess) { ctx->frame_prev_valid = false; return set_error(ctx, TSD_E_HIP, who, e); }
+    if (e != hipSuccess) { ctx->ledger.frame_lost(); return set_error(ctx, TSD_E_HIP, who, e); }
   }
   ctx->frame_empty = false;
   if (n_surface) *n_surface = *ctx->h_frame_count;

@@ -806,7 +806,7 @@ int launch_neg_scan(tsd_ctx* ctx)
 
 int launch_free_footprint(tsd_ctx* ctx, unsigned minX, unsigned maxX, unsigned minY, unsigned maxY)
 {
-  if (maxX <= minX || maxY <= minY) return TSD_OK;
+  if (maxX <= minX || maxY <= minY) { ctx->ledger.footprint(TileBox{}); return TSD_OK; }    // (nothing to write; the call still counts)
   const unsigned tx0 = minX / TILE_DIM, tx1 = (maxX - 1) / TILE_DIM;
   const unsigned ty0 = minY / TILE_DIM, ty1 = (maxY - 1) / TILE_DIM;
   const unsigned ntx = tx1 - tx0 + 1, nty = ty1 - ty0 + 1;
@@ -814,8 +814,7 @@ int launch_free_footprint(tsd_ctx* ctx, unsigned minX, unsigned maxX, unsigned m
                      maxX, minY, maxY, tx0, ty0, ntx, ctx->d_dirty);
   TSD_HIP_CHECK(ctx, hipGetLastError());
   TileBox b; b.x0 = (int)tx0; b.y0 = (int)ty0; b.x1 = (int)tx1; b.y1 = (int)ty1;
-  ctx->box_dirty.add(b);             // the next push refreshes the halos there
-  ctx->box_frame.add(b);             // ... and the next windowed frame covers them (tsd_map_update_begin)
+  ctx->ledger.footprint(b);
   return TSD_OK;
 }
 
@@ -852,14 +851,8 @@ int launch_push(tsd_ctx* ctx, hipStream_t stream, const PushJob& job, HaloArgs* 
   if (!a_dev) return set_error(ctx, TSD_E_ARG, "launch_push: the arguments must be on the device", hipSuccess);
   char* const rmq = job.rmq;
   const double cx = job.cx, cy = job.cy, slack = job.slack;
-  // Tile window (push_tile_window).  The window also covers the previous push (its records are rewritten) and whatever freeFootprint
-  // touched since.
-  TileBox box = push_tile_window(g, cx, cy, job.max_range, slack);
-  const TileBox cur = box;
-  box.add(ctx->box_prev);
-  box.add(ctx->box_dirty);
-  ctx->box_prev = cur; ctx->box_dirty = TileBox{};
-  ctx->box_frame.add(box);           // (counted whether or not the device-side gate lets the push run)
+  // Tile window: the push's own (push_tile_window), widened by the ledger to the previous push and what freeFootprint touched since.
+  const TileBox box = ctx->ledger.push_window(push_tile_window(g, cx, cy, job.max_range, slack));
   const int ntx = box.x1 - box.x0 + 1, nty = box.y1 - box.y0 + 1;
   const int parity = (int)(ctx->push_parity & 1u);
   ctx->push_parity++;

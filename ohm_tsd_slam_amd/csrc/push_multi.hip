@@ -424,19 +424,15 @@ int launch_push_multi(tsd_ctx* ctx, hipStream_t stream, int n, const PushJob* jo
   MultiPushArgs mp;
   std::memset(&mp, 0, sizeof(mp));
   mp.n = n;
-  TileBox box;
+  TileBox cur;
   int max_beams = 1;
   for (int i = 0; i < n; i++) {
     const PushJob& j = jobs[i];
     mp.r[i] = MultiPushRobot{j.a_dev, j.ranges, j.mask, j.rmq, j.cx, j.cy, j.slack + g.cs};
     if (j.beams > max_beams) max_beams = j.beams;
-    box.add(push_tile_window(g, j.cx, j.cy, j.max_range, j.slack));          // the robot's own window
+    cur.add(push_tile_window(g, j.cx, j.cy, j.max_range, j.slack));          // the robot's own window
   }
-  const TileBox cur = box;
-  box.add(ctx->box_prev);
-  box.add(ctx->box_dirty);
-  ctx->box_prev = cur; ctx->box_dirty = TileBox{};
-  ctx->box_frame.add(box);           // (counted whether or not the device-side gates let the pushes run)
+  const TileBox box = ctx->ledger.push_window(cur);
   mp.tx0 = box.x0; mp.ty0 = box.y0; mp.ntx = box.x1 - box.x0 + 1; mp.nty = box.y1 - box.y0 + 1;
   const size_t n_window = (size_t)mp.ntx * (size_t)mp.nty;
   // per-window-tile state of this path: the masks (zero between batches: every listed tile's workgroup gives its word back), the

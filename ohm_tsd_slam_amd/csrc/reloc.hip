@@ -296,9 +296,8 @@ int tsd_relocalize(tsd_ctx* ctx, const tsd_reloc_params* prm, const double* poin
   }
   if (scan_in_flight(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: a scan of this context is in flight (collect it first)", hipSuccess);
   // ---- the arguments stand: from here on the context changes ----
-  ctx->epoch++;                           // (the refinement rewrites the context's ray-cast outputs, like tsd_localize)
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;
+  if (int rc = enter(ctx)) return rc;
+  ctx->ledger.outputs_overwritten();      // (the refinement rewrites the context's ray-cast outputs, like tsd_localize)
   const size_t n = (size_t)nx * (size_t)ny * (size_t)nt;
   if (int rc = reloc_ensure(ctx, (size_t)nt, n)) return rc;
   tsd_ctx::Reloc& r = ctx->reloc;

@@ -10,6 +10,7 @@
 #include <mutex>
 
 #include "tsd_device.hpp"
+#include "grid_ledger.hpp"
 #include "../../include/tsd_hip.h"
 
 namespace tsd {
@@ -95,18 +96,6 @@ struct ScanPostArgs {
   int publish_done;          // also publish st->done_seq (agent-scope release): a gate kernel on another stream waits for it (batched scans)
   PushArgs* push_copy;       // asynchronous mapping: where this scan's push arguments are left for a push that runs beside the NEXT
                              // registration (whose epilogue rewrites st->push); nullptr = strict order, the push reads st->push
-};
-
-// inclusive tile rectangle (empty when x1 < x0)
-struct TileBox {
-  int x0 = 0, y0 = 0, x1 = -1, y1 = -1;
-  bool empty() const { return x1 < x0 || y1 < y0; }
-  void add(const TileBox& o)
-  {
-    if (o.empty()) return;
-    if (empty()) { *this = o; return; }
-    if (o.x0 < x0) x0 = o.x0; if (o.y0 < y0) y0 = o.y0; if (o.x1 > x1) x1 = o.x1; if (o.y1 > y1) y1 = o.y1;
-  }
 };
 
 // Where a ray cast and a registration run and what they write: the context's own stream and buffers (ctx_target: the unfused entry
@@ -215,8 +204,6 @@ struct tsd_ctx {
   uint8_t* d_dirty = nullptr;                // [tiles] written by freeFootprint since the last push
   uint32_t* d_tile_totals = nullptr;         // [tiles][8] records summed over the pushes since the last reset
   unsigned long long* d_pushes = nullptr;    // [2] pushes since the last reset, pushes whose launch window missed the sensor
-  // tile window of the push launches: what the last push covered and what freeFootprint dirtied since
-  tsd::TileBox box_prev{}, box_dirty{};
   uint32_t* d_list = nullptr;               // [tiles] work list of the current push (tile | kind << 28)
   uint32_t* d_list_h = nullptr;             // [tiles] the UPDATE tiles of that list k_push_halo has work for (materialised by the push, or dirty)
   char* d_list_aux = nullptr;               // [tiles] PushListAux of every list entry (push_kernels.hip): beam window, partition weight,
@@ -224,7 +211,12 @@ struct tsd_ctx {
   tsd::PushArgs* d_push_args = nullptr;     // arguments of an unfused tsd_push (the fused scan keeps them in the sensor state)
   unsigned int* d_list_cnt = nullptr;       // by push parity: UPDATE tiles listed, other tiles listed, the ticket heads of k_push_update's tile queue
   unsigned int push_parity = 0;
-  unsigned long long epoch = 0;             // bumped by everything that changes the grid, a sensor pose or the ctx's ray-cast outputs
+  // The grid's write ledger (grid_ledger.hpp): the epoch, the push launches' tile window, what the next windowed frame covers.  Its
+  // methods are the only writers.  The grid-writing entry points of the split and batched paths and the frame's begin call them under
+  // order_mutex (WriterScope, frame_begin); the fused scan, which takes no lock, and the unfused entry points that only outdate a ray
+  // cast call them under the caller's own grid mutex (host/: obvious::TsdGrid::mutex(), which also covers frame_begin there).  One
+  // grid is driven either way, never both at once.  (frame_wait reports a failed copy with neither lock held.)
+  tsd::GridLedger ledger;
   hipStream_t stream2 = nullptr;             // side stream: the tables are built while ray cast / ICP run
   // asynchronous mapping (tsd_sensor_set_async_mapping): the fused scan's push on a stream of its own, beside the next registration
   hipStream_t stream_push = nullptr;
@@ -286,13 +278,7 @@ struct tsd_ctx {
   hipEvent_t ev_frame = nullptr;                    // on `stream`: the frame's kernels are done
   hipEvent_t ev_frame_done = nullptr;               // on stream_io: the frame's copies to the host are done
   bool frame_inflight = false;
-  // The windowed frame (tsd_map_update_begin).  box_frame: the tiles anything may have written since the last frame or update was
-  // enqueued (every push's launch window, freeFootprint's box).  frame_prev_valid: the staging holds a complete frame taken with
-  // frame_prev_inflate / _factor (and its image, frame_prev_image) of the grid as box_frame describes it; cleared by whatever rewrites
-  // the grid wholesale, by a new staging and by a frame that ended in an error.
-  tsd::TileBox box_frame{};
-  bool frame_prev_valid = false, frame_prev_image = false, frame_empty = false;
-  int frame_prev_inflate = 0, frame_prev_factor = 0;
+  bool frame_empty = false;                         // the frame in flight is a windowed one that nothing was written for: no copy to wait for
   // TSD-level fusion (fuse.hip).  As the destination: the kernel's sharded counters and their pinned copy.  As a member: events of its
   // own -- "every grid write enqueued so far" on its stream / its push stream, "the fusion that read this grid last is done" (recorded
   // on the destination's stream; the member's streams wait for it at once) -- all created on first use
@@ -369,7 +355,7 @@ struct tsd_sensor {
                                      // k-1 and push k beside registration k+1 on the push stream: the host has no proof that it is
                                      // done, so the staging waits for the buffer's own push event (async.ev_slot_push).
     bool rc_pending = false;         // the next scan's ray cast was enqueued behind this scan's push ...
-    unsigned long long rc_epoch = 0; // ... when the context was in this state
+    unsigned long long rc_epoch = 0; // ... when the context's ledger was at this epoch
   } fused;
 
   // asynchronous mapping of the fused path (tsd_sensor_set_async_mapping)

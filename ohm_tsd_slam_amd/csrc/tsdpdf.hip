@@ -22,7 +22,7 @@
 // streams of raw rand() values as inputs; the C++ facade (csrc/host/obvision) draws them with rand() where the
 // reference does.  With given draws the result is a function of the inputs and is parity-tested against the oracle's
 // restatement (PARITY UNPINNED: the reference's translation unit needs GSL and cannot be compiled in this image).
-#include "tsd_ctx.hpp"
+#include "capi_internal.hpp"
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
@@ -913,8 +913,7 @@ extern "C" int tsd_tsdpdf_match(tsd_ctx* ctx, const double pose33[9], const doub
   if (int rc = pdf_check_match(ctx, {pose33, model_xy_2B, mask_m, scene_xy_2B, mask_s, draws_subsample, draws_control, draws_trials, result},
                                beams, prm, "tsd_tsdpdf_match: beams / control set out of range"))
     return rc;
-  if (int rcd_ = drain_async_push(ctx)) return rcd_;     // (the scoring reads the grid: behind a push still on the push stream)
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (int rc = enter(ctx)) return rc;                    // (the scoring reads the grid: behind a push still on the push stream)
   static PdfPhaseTimer tm("TSD_MODE3_TIMING");           // the host phases of this call
   PdfFrontEnd fe;
   if (int rc = pdf_front_end(ctx, model_xy_2B, mask_m, scene_xy_2B, mask_s, beams, prm->trials, prm->size_control_set, prm->phi_max,
