@@ -533,6 +533,34 @@ int tsd_map_update_wait(tsd_ctx* ctx, int* n_surface);
 void* tsd_host_alloc(uint64_t bytes);
 void tsd_host_free(void* p);
 
+/* ---- the map's surface as an ordered point list --------------------------------------------------------------- */
+/* The `coords` array of RayCastAxisAligned2D::calcCoords (RayCastAxisAligned2D.cpp:13-105), point for point and in its serial order:
+ * the linear zero crossings of the TSD along every row and column of every initialised tile of the processed ring (tiles 1 .. PX-2 in
+ * x and y, y outer; inside a tile the row scans py = 0..32, px = 1..32, then the column scans px = 0..32, py = 1..32, over the 33 x 33
+ * form with the halo), in fp64 and in the reference's operation order -- the points tsd_occupancy rounds into its 100 marks, so n
+ * equals its n_surface.  A seam point that two tiles find appears twice, as in the reference.  Coordinates are the grid's own (the ray
+ * cast's model points).
+ * Normals: TsdGrid::interpolateNormal (TsdGrid.cpp:517-546) AT EACH POINT.  (The reference passes the array's base pointer, so every
+ * normal it writes is the first point's: not reproduced.)  normal_ok[i] = 0 and normal (0, 0) where one of the four bilinear look-ups
+ * fails; a length <= 10e-6 leaves the normal unnormalised with normal_ok = 1.
+ * params == NULL: the whole grid, with normals.  Otherwise the tiles [tx0, tx1) x [ty0, ty1), clipped to the processed ring: the
+ * sublist those tiles contribute, in the same order; an empty window gives n = 0 and enqueues nothing.
+ * tsd_surface_extract runs on the context's stream, behind every push enqueued before it, and returns when the list is complete on
+ * the device; it reads the grid and writes nothing but the context's surface buffers (kept and grown geometrically: no allocation
+ * where the capacity suffices).  The grid must not be written while the call runs, as for every reading entry point.
+ * tsd_surface_fetch copies points [first, first + count) of the last list: xy[2 * count] interleaved, normals[2 * count] and
+ * normal_ok[count] where given.  TSD_E_ARG for a range outside [0, n) and for normals / normal_ok after an extraction without them.
+ * tsd_surface_dev gives the device arrays themselves (normals / ok NULL after an extraction without normals), valid until the next
+ * extraction on the context or tsd_destroy. */
+typedef struct {
+  int32_t tx0, ty0, tx1, ty1;   /* tiles, half open */
+  int32_t want_normals;
+  int32_t reserved;
+} tsd_surface_params;
+int tsd_surface_extract(tsd_ctx* ctx, const tsd_surface_params* params, int* n);
+int tsd_surface_fetch(tsd_ctx* ctx, int first, int count, double* xy, double* normals, uint8_t* normal_ok);
+int tsd_surface_dev(tsd_ctx* ctx, const double** xy_dev, const double** normals_dev, const uint8_t** ok_dev, int* n);
+
 /* ---- same-device merge group: N grids of one process on ONE GPU, one merged occupancy map ------------------ */
 /* The one-GPU counterpart of include/tsd_comm.h (whose RCCL all-reduce needs one GPU per rank): n contexts of this process on one
  * device, member i shifted by (cell_off_xy[2i], cell_off_xy[2i+1]) whole cells, merged by a local kernel into a width x height window.

@@ -186,6 +186,12 @@ class RelocResult(C.Structure):
                 ("search_ms", C.c_double), ("refine_ms", C.c_double)]
 
 
+class SurfaceParams(C.Structure):
+    """tsd_surface_params"""
+    _fields_ = [("tx0", C.c_int32), ("ty0", C.c_int32), ("tx1", C.c_int32), ("ty1", C.c_int32), ("want_normals", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # every symbol include/tsd_hip.h declares: name -> (restype, argtypes)
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
@@ -255,6 +261,9 @@ ABI = {
     "tsd_debug_reloc_scores": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),
     "tsd_debug_reloc_peaks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _ip]),
+    "tsd_surface_extract": (C.c_int, [C.c_void_p, C.POINTER(SurfaceParams), _ip]),
+    "tsd_surface_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _u8p]),
+    "tsd_surface_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _ip]),
     "tsd_scan_preregister": (C.c_int, [C.c_void_p, C.POINTER(TsdPdfParams), _dp, _u8p, _ip, _ip, _ip]),
     "tsd_scan_preregistration_result": (C.c_int, [C.c_void_p, C.POINTER(TsdPdfResult)]),
     "tsd_sensor_set_async_mapping": (C.c_int, [C.c_void_p, C.c_int]),
@@ -336,7 +345,7 @@ def load_library(path: str | None = None):
                           ("tsd_pdfmatch_params", PdfMatchParams), ("tsd_rnmatch_params", RnMatchParams),
                           ("tsd_rnmatch_result", RnMatchResult), ("tsd_map_params", MapParams),
                           ("tsd_fuse_stats", FuseStats), ("tsd_map_window", MapWindow), ("tsd_reloc_params", RelocParams),
-                          ("tsd_reloc_result", RelocResult)):
+                          ("tsd_reloc_result", RelocResult), ("tsd_surface_params", SurfaceParams)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -654,6 +663,41 @@ class TsdGridDevice:
         rc = self.lib.tsd_occupancy(self.h, occ.ctypes.data_as(_i8p), int(inflate), inflate_factor, C.byref(n))
         self._check(rc, "tsd_occupancy")
         return occ.reshape(self.cells, self.cells), n.value
+
+    def surface_extract(self, window=None, normals=True) -> int:
+        """tsd_surface_extract: builds the surface list on the device and returns its length.  window: (tx0, ty0, tx1, ty1) in tiles,
+        half open, clipped to the processed ring; None: the whole grid (with the C call's NULL parameters when normals are wanted)."""
+        n = C.c_int(0)
+        prm = None
+        if window is not None or not normals:
+            tx0, ty0, tx1, ty1 = window if window is not None else (0, 0, self.cells // 32, self.cells // 32)
+            prm = C.byref(SurfaceParams(int(tx0), int(ty0), int(tx1), int(ty1), 1 if normals else 0, 0))
+        self._check(self.lib.tsd_surface_extract(self.h, prm, C.byref(n)), "tsd_surface_extract")
+        return n.value
+
+    def surface_fetch(self, first: int, count: int, normals=True):
+        """tsd_surface_fetch: points [first, first + count) of the last list as (xy[count, 2], normals[count, 2] or None,
+        ok[count] or None)"""
+        xy = np.zeros((max(count, 0), 2))
+        nr = np.zeros((max(count, 0), 2)) if normals else None
+        ok = np.zeros(max(count, 0), dtype=np.uint8) if normals else None
+        rc = self.lib.tsd_surface_fetch(self.h, int(first), int(count), _d(xy), _d(nr) if normals else None, _u8(ok) if normals else None)
+        self._check(rc, "tsd_surface_fetch")
+        return xy, nr, ok
+
+    def surface_points(self, window=None, normals=True):
+        """The map's surface as an ordered point list (RayCastAxisAligned2D::calcCoords' coords, tsd_surface_extract + _fetch):
+        (xy[n, 2], normals[n, 2] or None, ok[n] or None), the normals being TsdGrid::interpolateNormal at each point and ok[i] = 0
+        where it fails (normal (0, 0))."""
+        # (through the class: a GridView takes the node's lock once, around this whole method)
+        n = TsdGridDevice.surface_extract(self, window, normals)
+        return TsdGridDevice.surface_fetch(self, 0, n, normals)
+
+    def surface_dev(self):
+        """tsd_surface_dev: (xy, normals, ok) device addresses (0 where there is none) and the length of the last list"""
+        a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+        self._check(self.lib.tsd_surface_dev(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)), "tsd_surface_dev")
+        return a.value or 0, b.value or 0, c.value or 0, n.value
 
     def occupancy_into(self, dev_ptr: int, inflate=False, inflate_factor=2):
         self._check(self.lib.tsd_occupancy_dev(self.h, C.c_void_p(dev_ptr), int(inflate), inflate_factor),

@@ -513,6 +513,7 @@ void tsd_destroy(tsd_ctx* ctx)
   if (ctx->d_pdf) hipFree(ctx->d_pdf);
   if (ctx->h_pdf) hipHostFree(ctx->h_pdf);
   reloc_free(ctx);
+  surface_free(ctx);
   if (ctx->stream) hipStreamDestroy(ctx->stream);
   delete ctx;
 }

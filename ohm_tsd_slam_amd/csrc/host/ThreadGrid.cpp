@@ -2,6 +2,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 namespace ohm_tsd_slam
 {
@@ -16,7 +17,8 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
     _hOcc(nullptr),
     _hRgb(nullptr),
     _frames(0),
-    _updates(0)
+    _updates(0),
+    _surfaces(0)
 {
   // (ThreadGrid.cpp:16-40)
   _occGrid->info.resolution           = static_cast<double>(_grid.getCellSize());
@@ -46,6 +48,13 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
   node->declare_parameter("publish_map_updates", false);
 #endif
   _publishUpdates = node->get_parameter("publish_map_updates").as_bool();
+#if OHM_TSD_SLAM_HAVE_ROS
+  if(!node->has_parameter("publish_surface_cloud"))
+    node->declare_parameter<bool>("publish_surface_cloud", false);
+#else
+  node->declare_parameter("publish_surface_cloud", false);
+#endif
+  _publishSurface = node->get_parameter("publish_surface_cloud").as_bool();
 
   const std::string node_name = _node->get_name();
   _gridPub = node->create_publisher<nav_msgs::msg::OccupancyGrid>(node_name + "/map", rclcpp::QoS(1).reliable().transient_local());
@@ -53,6 +62,8 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
   if(_publishUpdates)
     _updatePub = node->create_publisher<map_msgs::msg::OccupancyGridUpdate>(node_name + "/map_updates",
                                                                             rclcpp::QoS(10).reliable().durability_volatile());
+  if(_publishSurface)
+    _surfacePub = node->create_publisher<sensor_msgs::msg::PointCloud2>(node_name + "/surface", rclcpp::QoS(1).reliable().durability_volatile());
   _getMapServ = node->create_service<nav_msgs::srv::GetMap>(
     node_name + "/get_map",
     std::bind(&ThreadGrid::getMapServCallBack, this, std::placeholders::_1, std::placeholders::_2));
@@ -89,6 +100,18 @@ map_msgs::msg::OccupancyGridUpdate ThreadGrid::lastUpdate(void)
 {
   std::lock_guard<std::mutex> lk(_msgMutex);
   return _lastUpdate;
+}
+
+sensor_msgs::msg::PointCloud2 ThreadGrid::lastSurface(void)
+{
+  std::lock_guard<std::mutex> lk(_msgMutex);
+  return _lastSurface;
+}
+
+uint64_t ThreadGrid::surfaces(void)
+{
+  std::lock_guard<std::mutex> lk(_msgMutex);
+  return _surfaces;
 }
 
 void ThreadGrid::eventLoop(void)
@@ -133,7 +156,12 @@ int ThreadGrid::publish(void)
   if(_publishUpdates && win.width == 0)      // nothing was pushed since the last publication
     return TSD_OK;
   if(_publishUpdates && !((size_t)win.width == _width && (size_t)win.height == _height))
-    return publishUpdate(win);
+  {
+    rc = publishUpdate(win);
+    if(rc == TSD_OK && _publishSurface)
+      rc = publishSurface(_lastUpdate.header);
+    return rc;
+  }
   if(mapSize2 == 0)
   {
 #if OHM_TSD_SLAM_HAVE_ROS
@@ -159,6 +187,67 @@ int ThreadGrid::publish(void)
   _image.encoding = sensor_msgs::image_encodings::RGB8;
   std::memcpy(_image.data.data(), _hRgb, 3 * cells);
   _pubColorImage->publish(_image);
+  if(_publishSurface)
+    return publishSurface(msg.header);
+  return TSD_OK;
+}
+
+// The map's surface beside the map: calcCoords' sub-cell points (tsd_surface_extract) as float32 x y z normal_x normal_y normal_z, z =
+// normal_z = 0, moved into the map's frame by the origin <node>/map carries; a point whose normal failed keeps a zero normal.  The
+// header is the map's (or the update's).
+int ThreadGrid::publishSurface(const std_msgs::msg::Header& header)
+{
+  tsd_ctx* ctx = _grid.context();
+  int n = 0;
+  std::vector<double> xy, nr;
+  std::vector<uint8_t> ok;
+  {
+    // the grid's mutex for the whole extraction: the call waits for its count, and the grid must not be written meanwhile
+    std::lock_guard<std::mutex> g(_grid.mutex());
+    int rc = tsd_surface_extract(ctx, nullptr, &n);
+    if(rc != TSD_OK)
+      return rc;
+    xy.resize(2 * (size_t)n + 2); nr.resize(2 * (size_t)n + 2); ok.resize((size_t)n + 1);
+    rc = tsd_surface_fetch(ctx, 0, n, xy.data(), nr.data(), ok.data());
+    if(rc != TSD_OK)
+      return rc;
+  }
+  sensor_msgs::msg::PointCloud2 cloud;
+  cloud.header = header;
+  cloud.height = 1;
+  cloud.width = static_cast<uint32_t>(n);
+  static const char* const names[6] = {"x", "y", "z", "normal_x", "normal_y", "normal_z"};
+  cloud.fields.resize(6);
+  for(unsigned i = 0; i < 6; i++)
+  {
+    cloud.fields[i].name = names[i];
+    cloud.fields[i].offset = 4 * i;
+    cloud.fields[i].datatype = sensor_msgs::msg::PointField::FLOAT32;
+    cloud.fields[i].count = 1;
+  }
+  cloud.is_bigendian = false;
+  cloud.point_step = 24;
+  cloud.row_step = cloud.point_step * cloud.width;
+  cloud.is_dense = true;
+  cloud.data.resize((size_t)cloud.row_step);
+  double ox, oy;
+  {
+    std::lock_guard<std::mutex> m(_msgMutex);
+    ox = _occGrid->info.origin.position.x;
+    oy = _occGrid->info.origin.position.y;
+  }
+  for(int i = 0; i < n; i++)
+  {
+    const float p[6] = {static_cast<float>(xy[2 * (size_t)i] + ox), static_cast<float>(xy[2 * (size_t)i + 1] + oy), 0.f,
+                        ok[(size_t)i] ? static_cast<float>(nr[2 * (size_t)i]) : 0.f, ok[(size_t)i] ? static_cast<float>(nr[2 * (size_t)i + 1]) : 0.f, 0.f};
+    std::memcpy(cloud.data.data() + (size_t)i * cloud.point_step, p, sizeof(p));
+  }
+  {
+    std::lock_guard<std::mutex> m(_msgMutex);
+    _lastSurface = cloud;
+    _surfaces++;
+  }
+  _surfacePub->publish(cloud);
   return TSD_OK;
 }
 

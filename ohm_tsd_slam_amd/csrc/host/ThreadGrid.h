@@ -4,6 +4,8 @@
 // With the parameter publish_map_updates (not in the reference; default false) only the first publication, and every one the device
 // cannot take as a window, is a full map: the others are windowed frames (tsd_map_update_begin / _wait) published as
 // map_msgs/OccupancyGridUpdate on <node>/map_updates, the form rviz and nav2's static layer listen for.
+// With the parameter publish_surface_cloud (not in the reference; default false) every publication is followed by the map's surface
+// (tsd_surface_extract: calcCoords' sub-cell points with their normals) as sensor_msgs/PointCloud2 on <node>/surface, in the map's frame.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -35,6 +37,11 @@ public:
   std::shared_ptr<rclcpp::Publisher<map_msgs::msg::OccupancyGridUpdate>> updatePublisher() { return _updatePub; }
   /** the last update message (width 0 before the first one) */
   map_msgs::msg::OccupancyGridUpdate lastUpdate(void);
+  /** <node>/surface; nullptr unless publish_surface_cloud is set */
+  std::shared_ptr<rclcpp::Publisher<sensor_msgs::msg::PointCloud2>> surfacePublisher() { return _surfacePub; }
+  /** the last surface message (no fields before the first one) and the number published */
+  sensor_msgs::msg::PointCloud2 lastSurface(void);
+  uint64_t surfaces(void);
   std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> mapService() { return _getMapServ; }
 
   /** the get_map service (ThreadGrid.cpp:135-142): the last map with a fresh stamp */
@@ -46,6 +53,7 @@ protected:
 
 private:
   int publishUpdate(const tsd_map_window& win);
+  int publishSurface(const std_msgs::msg::Header& header);
 
 private:
   std::shared_ptr<rclcpp::Node> _node;
@@ -57,6 +65,9 @@ private:
   std::shared_ptr<rclcpp::Publisher<map_msgs::msg::OccupancyGridUpdate>> _updatePub;
   map_msgs::msg::OccupancyGridUpdate _lastUpdate;     // (kept here: a real publisher does not keep its messages)
   bool _publishUpdates;
+  std::shared_ptr<rclcpp::Publisher<sensor_msgs::msg::PointCloud2>> _surfacePub;
+  sensor_msgs::msg::PointCloud2 _lastSurface;         // (likewise)
+  bool _publishSurface;
   unsigned int _width;
   unsigned int _height;
   double _cellSize;
@@ -69,6 +80,7 @@ private:
   std::mutex _msgMutex;          // _occGrid between a publication and the get_map service
   uint64_t _frames;
   uint64_t _updates;
+  uint64_t _surfaces;
 };
 
 } /* namespace ohm_tsd_slam */

@@ -399,6 +399,27 @@ unsigned long long tsd_node_map_update_msg(tsd_node* n, int8_t* data_out, double
   return n->gridThread->updates();
 }
 
+// last message on <node>/surface (parameter publish_surface_cloud): width (points), point_step, stamp [ns], fields (4 doubles);
+// data (width * point_step bytes) when data_out is given; "frame_id|field,field,.." into text.  Returns the number published.
+unsigned long long tsd_node_surface(tsd_node* n, uint8_t* data_out, double* out4, char* text, int cap)
+{
+  if(!n || !n->gridThread || !out4)
+    return 0;
+  const sensor_msgs::msg::PointCloud2 m = n->gridThread->lastSurface();
+  out4[0] = m.width; out4[1] = m.point_step; out4[2] = (double)m.header.stamp.sec * 1e9 + (double)m.header.stamp.nanosec;
+  out4[3] = (double)m.fields.size();
+  if(data_out && !m.data.empty())
+    std::memcpy(data_out, m.data.data(), m.data.size());
+  if(text && cap > 0)
+  {
+    std::string t = m.header.frame_id + "|";
+    for(size_t i = 0; i < m.fields.size(); i++)
+      t += (i ? "," : "") + m.fields[i].name;
+    std::snprintf(text, (size_t)cap, "%s", t.c_str());
+  }
+  return n->gridThread->surfaces();
+}
+
 // an OccupancyGrid as flat values: resolution, width, height, origin x, y, z, qx, qy, qz, qw, stamp [ns], map_load_time [ns]
 // (12 doubles); data (width * height) when data_out is given; header.frame_id into frame_id
 static void map_out(const nav_msgs::msg::OccupancyGrid& m, int8_t* data_out, double* out12, char* frame_id, int cap)

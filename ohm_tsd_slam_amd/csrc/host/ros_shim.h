@@ -22,6 +22,7 @@
 #include <sensor_msgs/msg/image.hpp>
 #include <sensor_msgs/image_encodings.hpp>
 #include <map_msgs/msg/occupancy_grid_update.hpp>
+#include <sensor_msgs/msg/point_cloud2.hpp>
 #else
 #define OHM_TSD_SLAM_HAVE_ROS 0
 #include <chrono>
@@ -89,6 +90,20 @@ struct Image {
   uint8_t is_bigendian = 0;
   uint32_t step = 0;
   std::vector<uint8_t> data;
+};
+// the surface list on <node>/surface (sensor_msgs/PointCloud2): unordered cloud, height 1, point_step bytes per point
+struct PointField {
+  static constexpr uint8_t FLOAT32 = 7;
+  std::string name; uint32_t offset = 0; uint8_t datatype = 0; uint32_t count = 0;
+};
+struct PointCloud2 {
+  std_msgs::msg::Header header;
+  uint32_t height = 0, width = 0;
+  std::vector<PointField> fields;
+  bool is_bigendian = false;
+  uint32_t point_step = 0, row_step = 0;
+  std::vector<uint8_t> data;
+  bool is_dense = false;
 };
 } namespace image_encodings {
 static const std::string RGB8 = "rgb8";

@@ -1,5 +1,6 @@
 // occupancy_device.hpp -- the per-tile rules of ThreadGrid's two outputs, shared by the extraction kernels of occupancy_kernels.hip
-// (k_occ_cells, k_color_image) and the one-pass publication of map_publish.hip (k_map_frame, k_map_frame_window).
+// (k_occ_cells, k_color_image) and the one-pass publication of map_publish.hip (k_map_frame, k_map_frame_window); calcCoords' scan
+// positions, sign changes and surface points, shared by k_occ_mark and the surface list of surface.hip.
 #pragma once
 #include "tsd_ctx.hpp"
 
@@ -26,6 +27,40 @@ __device__ __forceinline__ int8_t occ_from_tsd(const GridDev& g, int p, int ly, 
 __device__ __forceinline__ uint32_t occ_bits4(double t0, double t1, double t2, double t3)
 {
   return (t0 > 0.0 ? 0u : 0xFFu) | (t1 > 0.0 ? 0u : 0xFF00u) | (t2 > 0.0 ? 0u : 0xFF0000u) | (t3 > 0.0 ? 0u : 0xFF000000u);
+}
+
+// calcCoords' scan positions of one tile, numbered in its serial order: c in [0, 1056) are the row scans (py = c / 32 in 0..32,
+// px = c % 32 + 1, :38-60), c in [1056, 2112) the column scans (px = (c - 1056) / 32 in 0..32, py = (c - 1056) % 32 + 1, :62-80)
+constexpr int SCAN_POSITIONS = 2 * TILE_PITCH * TILE_DIM;
+struct ScanPos { int px, py; bool col; };
+__device__ __forceinline__ ScanPos scan_pos(int c)
+{
+  ScanPos s;
+  s.col = c >= TILE_PITCH * TILE_DIM;
+  const int cc = s.col ? c - TILE_PITCH * TILE_DIM : c;
+  const int a = cc / TILE_DIM;          // fixed index 0..32
+  const int b = cc % TILE_DIM + 1;      // running index 1..32
+  s.py = s.col ? b : a; s.px = s.col ? a : b;
+  return s;
+}
+// the two cells of scan position s in T, the tile in the 33 x 33 form; true where they change sign (:51, :73): NaN and 0 make no event
+__device__ __forceinline__ bool scan_event(const double* T, const ScanPos& s, double& prev, double& cur)
+{
+  prev = s.col ? T[(s.py - 1) * TILE_PITCH + s.px] : T[s.py * TILE_PITCH + s.px - 1];
+  cur = T[s.py * TILE_PITCH + s.px];
+  return (prev > 0 && cur < 0) || (prev < 0 && cur > 0);
+}
+// the sub-cell surface point of a sign change at scan position s of tile (X, Y) (:53-55, :76-77), in the reference's operation order
+__device__ __forceinline__ void surface_point(const ScanPos& s, double prev, double cur, int X, int Y, double cs, double& x, double& y)
+{
+  const double interp = prev / (prev - cur);
+  if (!s.col) {
+    x = s.px * cs + cs * (interp - 1.0) + (X * TILE_DIM) * cs;
+    y = s.py * cs + (Y * TILE_DIM) * cs;
+  } else {
+    x = s.px * cs + (X * TILE_DIM) * cs;
+    y = s.py * cs + cs * (interp - 1.0) + (Y * TILE_DIM) * cs;
+  }
 }
 
 // This extraction's mark counter and the NEXT extraction's list heads are cleared by the launch's first workgroup -- the heads come in

@@ -80,35 +80,17 @@ k_occ_mark(GridDev g, int8_t* __restrict__ out, int* __restrict__ count, int inf
     int p_next = p;
     if (has_next) { p_next = (int)list[sh * cap + k + k_step]; request(p_next, cur); }
     // row scans: py in 0..32, px in 1..32 (:38-60); column scans: px in 0..32, py in 1..32 (:62-80)
-    for (int c = threadIdx.x; c < 2 * TILE_PITCH * TILE_DIM; c += 256) {
-      const bool col = c >= TILE_PITCH * TILE_DIM;
-      const int cc = col ? c - TILE_PITCH * TILE_DIM : c;
-      const int a = cc / TILE_DIM;          // fixed index 0..32
-      const int b = cc % TILE_DIM + 1;      // running index 1..32
-      const int py = col ? b : a, px = col ? a : b;
-      const double prev = col ? T[(py - 1) * TILE_PITCH + px] : T[py * TILE_PITCH + px - 1];
-      const double cur = T[py * TILE_PITCH + px];
-      if ((prev > 0 && cur < 0) || (prev < 0 && cur > 0)) s_ev[atomicAdd(&s_nev, 1)] = (unsigned short)c;
+    for (int c = threadIdx.x; c < SCAN_POSITIONS; c += 256) {
+      double prev, cur;
+      if (scan_event(T, scan_pos(c), prev, cur)) s_ev[atomicAdd(&s_nev, 1)] = (unsigned short)c;
     }
     __syncthreads();
     const int nev = s_nev;
     for (int e = threadIdx.x; e < nev; e += 256) {
-      const int c = (int)s_ev[e];
-      const bool col = c >= TILE_PITCH * TILE_DIM;
-      const int cc = col ? c - TILE_PITCH * TILE_DIM : c;
-      const int a = cc / TILE_DIM, b = cc % TILE_DIM + 1;
-      const int py = col ? b : a, px = col ? a : b;
-      const double prev = col ? T[(py - 1) * TILE_PITCH + px] : T[py * TILE_PITCH + px - 1];
-      const double cur = T[py * TILE_PITCH + px];
-      const double interp = prev / (prev - cur);
-      double x, y;
-      if (!col) {
-        x = px * cs + cs * (interp - 1.0) + (X * TILE_DIM) * cs;
-        y = py * cs + (Y * TILE_DIM) * cs;
-      } else {
-        x = px * cs + (X * TILE_DIM) * cs;
-        y = py * cs + cs * (interp - 1.0) + (Y * TILE_DIM) * cs;
-      }
+      const ScanPos s = scan_pos((int)s_ev[e]);
+      double prev, cur, x, y;
+      scan_event(T, s, prev, cur);
+      surface_point(s, prev, cur, X, Y, cs, x, y);      // (the same point tsd_surface_extract hands out: surface.hip)
       occ_mark(g, out, x, y, inflate, factor);
       n++;
     }

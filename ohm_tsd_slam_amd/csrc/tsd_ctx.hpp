@@ -297,6 +297,16 @@ struct tsd_ctx {
     int nx = 0, ny = 0, ntheta = 0;          // shape of the volume in d_scores (0: no search yet)
   } reloc;
 
+  // the surface list (surface.hip: tsd_surface_extract / _fetch / _dev): per-window-tile counts and offsets and the per-1024-tile bases
+  // of the scan (allocated on first use for the grid's processed ring), the last list (grown geometrically, kept), its pinned total
+  struct Surface {
+    uint32_t* d_counts = nullptr; uint32_t* d_offsets = nullptr; uint32_t* d_bsum = nullptr;
+    unsigned int* h_total = nullptr;         // pinned
+    double* d_xy = nullptr; size_t cap = 0;                                  // [2 * cap]
+    double* d_normals = nullptr; uint8_t* d_ok = nullptr; size_t ncap = 0;   // [2 * ncap], [ncap]
+    int n = 0; bool has_normals = false;     // the last extraction's
+  } surface;
+
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;
   unsigned profile_every = 1;   // time every n-th launch of a selected kernel ("name/n" in tsd_profile_select)
@@ -539,6 +549,7 @@ size_t icp_seed_bytes(int points);
 IcpSeedArgs icp_batch_seed_args(const tsd_ctx* ctx, void* buf, int beams, int batch_beams);
 
 void reloc_free(tsd_ctx* ctx);               // reloc.hip: releases tsd_ctx::reloc (tsd_destroy)
+void surface_free(tsd_ctx* ctx);             // surface.hip: releases tsd_ctx::surface (tsd_destroy)
 int launch_calibrate(tsd_ctx* ctx, double* t, double* w, size_t n);
 int launch_occupancy(tsd_ctx* ctx, int8_t* d_out, int inflate, int inflate_factor);
 size_t occ_heads_bytes();

@@ -193,6 +193,37 @@ __device__ __forceinline__ Quad load_quad(const tsd_cell_t* __restrict__ tile, i
   return q;
 }
 
+// TsdGrid::interpolateNormal (TsdGrid.cpp:517-546) + norm2 (mathbase.h:211-218) on ONE lane: the four bilinear look-ups at
+// (x+cs,y) (x-cs,y) (x,y+cs) (x,y-cs) with their 4 flag reads and 16 cell reads requested together (the tile storage exists for every
+// tile; only `flags` says whether it holds data), each look-up in the expressions of interpolate_bilinear and of the ray cast's four
+// lanes (raycast_kernels.hip).  False where a look-up fails (outside the grid, tile not initialised, NaN): (nx, ny) is then (0, 0).
+__device__ __forceinline__ bool interpolate_normal(const GridDev& g, double x, double y, double& nx, double& ny)
+{
+  const double sx[4] = {x + g.cs, x - g.cs, x, x}, sy[4] = {y, y, y + g.cs, y - g.cs};
+  bool in[4]; int lx[4], ly[4]; double dx[4], dy[4]; uint8_t f[4]; Quad q[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    int p = 0;
+    in[k] = coord2cell(g, sx[k], sy[k], p, lx[k], ly[k], dx[k], dy[k]);
+    if (!in[k]) { p = 0; lx[k] = 0; ly[k] = 0; }
+    f[k] = ld_pinned(&g.flags[p]);
+    q[k] = load_quad(g.tsd + (size_t)p * TILE_STRIDE, lx[k], ly[k]);
+  }
+  double v[4]; bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const double wx = fabs((sx[k] - dx[k]) * g.inv_cs), wy = fabs((sy[k] - dy[k]) * g.inv_cs);
+    v[k] = q[k].t00 * (1. - wy) * (1. - wx) + q[k].t10 * wy * (1. - wx) + q[k].t01 * (1. - wy) * wx + q[k].t11 * wy * wx;
+    ok = ok && in[k] && f[k] != 0 && !isnan(v[k]);
+  }
+  nx = 0.0; ny = 0.0;
+  if (!ok) return false;
+  nx = v[0] - v[1]; ny = v[2] - v[3];
+  const double len = sqrt(nx * nx + ny * ny);
+  if (!(fabs(len) <= 10e-6)) { nx /= len; ny /= len; }
+  return true;
+}
+
 // 64-lane sum (all lanes receive lane 0's total is NOT guaranteed: result valid in lane 0)
 __device__ __forceinline__ double wave_sum(double v)
 {

@@ -46,6 +46,7 @@ HOST_ABI = {
     "tsd_node_map_frames": (C.c_ulonglong, [C.c_void_p]),
     "tsd_node_map_updates": (C.c_ulonglong, [C.c_void_p]),
     "tsd_node_map_update_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
+    "tsd_node_surface": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
@@ -352,6 +353,21 @@ class SlamNode:
         return {"x": int(info[0]), "y": int(info[1]), "width": w, "height": h, "stamp_ns": int(info[4]),
                 "frame_id": frame.value.decode(), "data": data.reshape(h, w), "count": int(n)}
 
+    def surface_msg(self) -> dict:
+        """the last sensor_msgs/PointCloud2 on <node>/surface (parameter publish_surface_cloud): ``points`` as (width, 6) float32 in
+        the order of ``fields`` (x y z normal_x normal_y normal_z) and the number published (0: no message, the parameter is off)"""
+        info = np.zeros(4)
+        text = C.create_string_buffer(512)
+        self.lib.tsd_node_surface(self.h, None, info.ctypes.data_as(_dp), text, 512)
+        w, step = int(info[0]), int(info[1])
+        data = np.zeros(max(w * step, 1), dtype=np.uint8)
+        n = self.lib.tsd_node_surface(self.h, data.ctypes.data, info.ctypes.data_as(_dp), text, 512)
+        frame, fields = text.value.decode().split("|")
+        fields = [f for f in fields.split(",") if f]
+        pts = data[:w * step].view(np.float32).reshape(w, step // 4) if w and step else np.zeros((0, len(fields)), dtype=np.float32)
+        return {"width": w, "height": 1 if n else 0, "point_step": step, "stamp_ns": int(info[2]), "frame_id": frame, "fields": fields,
+                "points": pts, "count": int(n)}
+
     def map_image_msg(self) -> dict:
         """the last sensor_msgs/Image on <node>/map/image (data as (height, width, 3) uint8) and its publish count"""
         info = np.zeros(5)
@@ -465,7 +481,8 @@ class GridView(capi.TsdGridDevice):
     _LOCKED = ("reset", "sync", "free_footprint", "push", "raycast", "icp", "localize", "icp_trace", "download_tile_state",
                "download_tiles", "upload_tiles", "digest", "occupancy", "occupancy_into", "calibrate_rmw", "profile", "store_text",
                "load_text", "color_image", "push_stats_total", "profile_reset", "profile_get", "profile_spread", "profile_samples", "tsdpdf_match",
-               "relocalize", "debug_reloc_scores", "debug_reloc_peaks")
+               "relocalize", "debug_reloc_scores", "debug_reloc_peaks", "surface_extract", "surface_fetch", "surface_points",
+               "surface_dev")
 
     def __init__(self, ctx, node=None):  # noqa: D401 - does not call the base constructor on purpose
         self.lib = capi.load_library()
