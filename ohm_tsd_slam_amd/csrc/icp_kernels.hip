@@ -34,6 +34,7 @@
 // No dense contraction anywhere => no MFMA; fp64 VALU + LDS.  Latency-bound: reported as ms/iterate.
 #include "scan_device.hpp"
 #include "tsdpdf_device.hpp"
+#include "icp_shape.hpp"
 #include <atomic>
 #include <climits>
 #include <cstring>
@@ -45,10 +46,8 @@
 #define UNLIKELY(x) __builtin_expect(!!(x), 0)
 namespace tsd {
 
-constexpr int ICP_MAXW = 16;                    // waves per workgroup at most
 constexpr double SLACK = 1.0 - 1e-9;            // conservative factor on every pruning bound
 constexpr int HW = 6;                           // tier-1 window: k-HW .. k+HW (3 / 4 / 8 measured slower)
-constexpr int ICP_PAD = 96;                     // wrapped copies of the model at both ends of its LDS array
 constexpr unsigned REFRESH_A = 6, REFRESH_B = 15;      // steps with a scheduled bound renewal
 constexpr double WEAK_MULT = 36.0;                     // a scheduled renewal takes the bounds with less than sqrt(this) x slack in distance
 constexpr int IR_CNT = 32, IR_RMAX = 33, IR_CNT2 = 34, IR_TIE = 35, IR_SEEDED = 36;   // words of IcpLds::ired (SEEDED: points whose step-0 neighbour a helper delivered)
@@ -65,13 +64,12 @@ constexpr int IR_CNT = 32, IR_RMAX = 33, IR_CNT2 = 34, IR_TIE = 35, IR_SEEDED = 
 // rebuilt from the same fp32 root: the state after step 0 is bit for bit what the workgroup's own search would have left).  The wait
 // is bounded and per wave: points whose granules did not arrive in time (helpers that got no compute unit: a push on another stream
 // filling the device) simply search in step 0 as they always did; the results are the same either way, only the time differs.
-constexpr int ICP_HELPER_POINTS = 256;              // scene points per helper workgroup: one per lane of its waves 0-3 (one wave per SIMD)
-constexpr int ICP_MAX_HELPERS = 16;
 constexpr long long ICP_SEED_WAIT_TICKS = 2500;     // of the 100 MHz wall clock: 25 us
 
 // what the kernel needs again only after the last step (and the trace pointer, once per step by one
 // thread): parked in LDS so that it does not sit in scalar registers through the loop
 struct IcpTail { IcpResultDev* out; double* trace; ScanPostArgs post; ScanPostPre pre; };
+static_assert(sizeof(IcpTail) == ICP_TAIL_BYTES, "icp_shape.hpp sizes the LDS with this");
 
 struct IcpLds {
   IcpTail* tail;
@@ -96,46 +94,6 @@ struct IcpLds {
   double2* stage_s;                // compacted scene
   int* start;                      // first search position of every compacted scene point
 };
-
-// (up to the node's shape -- 1081 beams, capacity 1088 -- the list holds every point: one pass, always)
-__host__ __device__ inline int icp_list_cap(int cap) { return cap <= 1088 ? cap : 1024; }
-// bytes of the region shared by the work list (48 B per entry), the setup staging and the transpose buffer
-__host__ __device__ inline size_t icp_region_bytes(int cap, int threads)
-{
-  size_t b = 48u * (size_t)icp_list_cap(cap);
-  const size_t tr = (size_t)threads * 11u * sizeof(double);      // nsum_pitch(NSUM_PTL): the wider of the two
-  if (tr > b) b = tr;
-  return (b + 15u) & ~(size_t)15u;
-}
-// a half of the reciprocal filter's slot array: a whole number of entries per thread, so that giving a half back is the same stores in every
-// thread (no bound to test: a test is a branch)
-__host__ __device__ inline int icp_slot_cap(int cap, int threads) { return (cap + threads - 1) / threads * threads; }
-__host__ __device__ inline size_t icp_lds_base_bytes(int cap, int threads, bool normals)      // with ONE half of the slot array
-{
-  // the staging (cap double2 + cap int) aliases the list + result arrays: 40 * lc >= 20 * cap
-  return sizeof(double2) * 2 * (size_t)cap + sizeof(double2) * 2 * ICP_PAD + sizeof(unsigned long long) * (size_t)icp_slot_cap(cap, threads) + sizeof(int) * 2 * (size_t)cap +
-         icp_region_bytes(cap, threads) + sizeof(double) * (2 * ICP_MAXW * 16 + 16) + ((sizeof(IcpTail) + 15) & ~(size_t)15) +
-         sizeof(int) * 64 + 64 + (normals ? sizeof(double2) * (size_t)cap : 0);
-}
-#ifdef TSD_ICP_TIMELINE
-#ifndef TSD_ICP_TL_FIRST
-#define TSD_ICP_TL_FIRST 19
-#define TSD_ICP_TL_STEPS 4
-#endif
-constexpr size_t ICP_TL_BYTES = (size_t)TSD_ICP_TL_STEPS * 8 * 16 * sizeof(long long);     // the timeline build's stamp buffer behind the kernel's LDS (<= 8 waves)
-#else
-constexpr size_t ICP_TL_BYTES = 0;
-#endif
-// The reciprocal filter's slot array has two halves used by alternate steps wherever the CU's 160 KB hold them (every shape the node
-// runs; not the largest point counts of tsd_icp with the point-to-line estimator's normals): see the loop.  Same rule on both sides.
-__host__ __device__ inline int icp_slot_halves(int cap, int threads, bool normals)
-{
-  return icp_lds_base_bytes(cap, threads, normals) + sizeof(unsigned long long) * (size_t)icp_slot_cap(cap, threads) + ICP_TL_BYTES <= 160u * 1024u ? 2 : 1;
-}
-__host__ __device__ inline size_t icp_lds_bytes_for(int cap, int threads, bool normals = false)
-{
-  return icp_lds_base_bytes(cap, threads, normals) + sizeof(unsigned long long) * (size_t)icp_slot_cap(cap, threads) * (size_t)(icp_slot_halves(cap, threads, normals) - 1);
-}
 
 // a wave-uniform value the compiler must keep in a vector register
 __device__ __forceinline__ double vreg(double x) { asm volatile("" : "+v"(x)); return x; }
@@ -1595,120 +1553,38 @@ k_icp_batch(const IcpBatchEntry* __restrict__ entries, int cap, int n_entries)
                               e.trace, e.post, nullptr, e.normals, e.seed, role);
 }
 
-static int icp_cap_for(int n)
-{
-  int cap = (n + 63) & ~63;
-  if (cap < 64) cap = 64;
-  return cap;
-}
+// Every instantiation the code object carries: what icp_with_shape() can reach, and the fold's.  Naming them here, ahead of the launchers,
+// fixes the order in which they are instantiated and so laid out -- it is the order they have always had, so that a change to the
+// launch layer below leaves the device assembly identical under a plain diff.
+[[maybe_unused]] static const void* const ICP_KERNELS[] = {
+  (const void*)k_icp<8, 256, true>, (const void*)k_icp_pre<3, 512, 1088, 512>, (const void*)k_icp<3, 512, false, 1088, 512>,
+  (const void*)k_icp<8, 256, false>, (const void*)k_icp<3, 512, true>, (const void*)k_icp<3, 512, false>,
+  (const void*)k_icp_pairs<3, 512>, (const void*)k_icp_pairs<8, 256>,
+  (const void*)k_icp_batch<3, 512, true>, (const void*)k_icp_batch<3, 512, false, 1088, 512>, (const void*)k_icp_batch<3, 512, false>,
+  (const void*)k_icp_batch<8, 256, true>, (const void*)k_icp_batch<8, 256, false>};
 
-// helper workgroups of a registration with n scene points in workgroups of T threads (see ICP_HELPER_POINTS)
+// ---- host: every launch takes its IcpShape from icp_shape_for() and reaches its kernel through icp_with_shape() (icp_shape.hpp)
+static int shape_error(tsd_ctx* ctx, const IcpShape& s) { return set_error(ctx, s.rc, s.why, hipSuccess); }
+
+// the helpers' hand-off buffer: two granules per point, the second ones `stride` behind the first
+static int icp_seed_stride(int points) { return (points + 63) & ~63; }
+size_t icp_seed_bytes(int points) { return 2 * sizeof(unsigned long long) * (size_t)icp_seed_stride(points); }
 static std::atomic<unsigned int> g_seed_seq{1u};
-int icp_helpers_for(const tsd_ctx* ctx, int n, int T)
-{
-  if (!ctx->icp_helpers) return 0;
-  const int per = T < ICP_HELPER_POINTS ? T : ICP_HELPER_POINTS;
-  const int h = (n + per - 1) / per;
-  return h > ICP_MAX_HELPERS ? 0 : h;                // (more points than the helpers reach: the registration searches itself)
-}
-size_t icp_seed_bytes(int points) { return 2 * sizeof(unsigned long long) * (size_t)((points + 63) & ~63); }
-IcpSeedArgs icp_seed_args(void* buf, int points, int helpers)
+static IcpSeedArgs icp_seed_args(void* buf, int points, int helpers)
 {
   IcpSeedArgs sa;
   sa.g = reinterpret_cast<unsigned long long*>(buf);
-  sa.stride = (points + 63) & ~63;                   // the second granules follow the first (as laid out by icp_seed_bytes(points))
+  sa.stride = icp_seed_stride(points);
   unsigned int q = g_seed_seq.fetch_add(1u);
   if (q == 0u) q = g_seed_seq.fetch_add(1u);         // (0 is what a fresh buffer holds)
   sa.seq = q; sa.helpers = buf ? helpers : 0;
   return sa;
 }
 
-// threads of a registration of n points with R register slots per lane (four "old" waves take R blocks of 64 points each,
-// younger waves one block each where the blocks left allow it)
-static int icp_threads_for(int n, int R, int maxt)
-{
-  int T = ((n + R - 1) / R + 63) & ~63;
-  if (T < 64) T = 64;
-  const int B = (n + 63) / 64;
-  if (B > 4 * R) {
-    int W = 4 + (B - 4 * R);
-    if (W > maxt / 64) W = maxt / 64;
-    if (64 * W > T) T = 64 * W;
-  }
-  return T;
-}
-
-// workgroup shape: R scene points per thread, T threads.  One CU runs the whole registration and is
-// issue bound, so few waves (per-wave reduction / control cost paid once per SIMD) win.
-template <int R, int MAXT, bool PTL>
-static int launch_icp_shape_est(tsd_ctx* ctx, const LaunchTarget& tg, const IcpArgs& a, int n, int cap, const double* P_dev,
-                            const double* d_rays_local, const double* d_ranges, const uint8_t* d_mask,
-                            const ScanPostArgs& post, int force_T = 0, const IcpPreLaunch* pre = nullptr)
-{
-  int T = icp_threads_for(n, R, MAXT);
-  if (force_T > T) T = force_T;
-  if (T > MAXT) return set_error(ctx, TSD_E_CAPACITY, "icp workgroup shape", hipSuccess);
-  const bool ptl = a.estimator == TSD_ESTIMATOR_POINT_TO_LINE;
-  const size_t lds = icp_lds_bytes_for(cap, T, ptl) + ICP_TL_BYTES;
-  if (lds > 160u * 1024u) return set_error(ctx, TSD_E_CAPACITY, "registration does not fit the LDS of one CU (point-to-line: model normals too)", hipSuccess);
-  // The default scanner's shape (1081 beams: capacity 1088, 512 threads, closed form) has an instantiation of its own in which the
-  // capacity and the thread count are compile-time constants: the twenty offsets of the LDS layout then cost no scalar registers
-  // (spilled scalars of the loop 166 -> 56; -0.7 us per registration, profiles/r5_icp_helpers_ab.txt)
-  const bool node_shape = R == 3 && MAXT == 512 && !PTL && cap == 1088 && T == 512;
-  // fused registration_mode 3, the node's shape (icp_pre_supported): the arg-max rides as the launch's first workgroup
-  if (pre && (!node_shape || !post.st)) return set_error(ctx, TSD_E_ARG, "launch_icp: the arg-max can only ride with the node's registration shape", hipSuccess);
-  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp<R, MAXT, PTL>), lds)) return rc;
-  ScopedKernelTimer t(ctx, "icp");
-  // the per-iteration record (tsd_icp_trace) is kept by tsd_icp / tsd_localize; the fused scan has no reader for it and skips
-  // the 64-byte store per step
-  double* trace_buf = post.st ? nullptr : tg.trace;
-#ifdef TSD_ICP_TIMELINE
-  if (post.st) trace_buf = ctx->d_icp_trace;     // (diagnostic build: the stamps of a fused scan's registration; no per-step record)
-#endif
-  const IcpSeedArgs sa = icp_seed_args(tg.icp_seed, tg.icp_seed_points, icp_helpers_for(ctx, n, T));
-  if (pre) {
-    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp_pre<3, 512, 1088, 512>), lds)) return rc;
-    // (the launch's own completion is the event a pre-registration armed AHEAD waits for before it overwrites the inputs; a timed
-    // dispatch needs its stop event for the timer: a marker behind it then)
-    hipEvent_t stop = t.b ? t.b : pre->done;
-    hipExtLaunchKernelGGL((k_icp_pre<3, 512, 1088, 512>), dim3(2 + sa.helpers), dim3(T), lds, tg.stream, t.a, stop, 0, a, P_dev, cap,
-                     tg.coords, tg.mask_m, d_rays_local, d_ranges, d_mask, tg.icp_res, trace_buf, post, sa, pre->dev);
-    TSD_HIP_CHECK(ctx, hipGetLastError());
-    if (t.b && pre->done) TSD_HIP_CHECK(ctx, hipEventRecord(pre->done, tg.stream));
-    return TSD_OK;
-  }
-  // (k_icp's argument list, once for the generic instantiation and the node's)
-  auto launch = [&](auto kernel) {
-    hipExtLaunchKernelGGL(kernel, dim3(1 + sa.helpers), dim3(T), lds, tg.stream, t.a, t.b, 0, a, P_dev, cap, ctx->d_model, ctx->d_scene,
-                     ctx->d_morig, ctx->d_start, tg.coords, tg.mask_m, d_rays_local, d_ranges, d_mask, tg.icp_res,
-                     trace_buf, post, ctx->d_mnormals, tg.normals, sa);
-  };
-  if (node_shape) {
-    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp<3, 512, false, 1088, 512>), lds)) return rc;
-    launch(k_icp<3, 512, false, 1088, 512>);
-  } else {
-    launch(k_icp<R, MAXT, PTL>);
-  }
-  TSD_HIP_CHECK(ctx, hipGetLastError());
-  return TSD_OK;
-}
-
-template <int R, int MAXT>
-static int launch_icp_shape(tsd_ctx* ctx, const LaunchTarget& tg, const IcpArgs& a, int n, int cap, const double* P_dev,
-                            const double* d_rays_local, const double* d_ranges, const uint8_t* d_mask,
-                            const ScanPostArgs& post, int force_T = 0, const IcpPreLaunch* pre = nullptr)
-{
-  // the estimator is a compile-time choice: the node's closed form does not pay for the other one's tenth sum
-  if (a.estimator == TSD_ESTIMATOR_POINT_TO_LINE)
-    return launch_icp_shape_est<R, MAXT, true>(ctx, tg, a, n, cap, P_dev, d_rays_local, d_ranges, d_mask, post, force_T, pre);
-  return launch_icp_shape_est<R, MAXT, false>(ctx, tg, a, n, cap, P_dev, d_rays_local, d_ranges, d_mask, post, force_T, pre);
-}
-
 // can the pre-registration's arg-max ride with this registration's launch (k_icp_pre: the node's shape, closed form, fused scan)?
 bool icp_pre_supported(const tsd_ctx* ctx, const IcpArgs& a)
 {
-  if (a.beams < 1 || a.estimator != TSD_ESTIMATOR_CLOSED_FORM || ctx->icp_shape != 0) return false;
-  return icp_cap_for(a.beams) == 1088 && icp_threads_for(a.beams, 3, 512) == 512;
+  return ctx->icp_shape == 0 && a.estimator == TSD_ESTIMATOR_CLOSED_FORM && icp_shape_for(a.beams, a.beams, false, 0, ICP_TL_BYTES).node;
 }
 
 int launch_icp(tsd_ctx* ctx, const LaunchTarget& tg, const IcpArgs& a, const double* P_dev, const double* d_rays_local,
@@ -1720,60 +1596,60 @@ int launch_icp(tsd_ctx* ctx, const LaunchTarget& tg, const IcpArgs& a, const dou
   if (a.estimator != TSD_ESTIMATOR_CLOSED_FORM && a.estimator != TSD_ESTIMATOR_POINT_TO_LINE)
     return set_error(ctx, TSD_E_ARG, "tsd_icp_params.estimator", hipSuccess);
   const int n = a.beams > 0 ? a.beams : (a.n_model > a.n_scene ? a.n_model : a.n_scene);
-  if (n > TSD_MAX_ICP_POINTS) return set_error(ctx, TSD_E_CAPACITY, "icp points > TSD_MAX_ICP_POINTS", hipSuccess);
-  const int cap = icp_cap_for(n);
   const int nthr = a.beams > 0 ? a.beams : a.n_scene;     // scene points decide the thread count
-  // (round 3: the experimental shapes <2,576>, <5,512> and <5,256> are gone -- measured no faster in round 2, and the first spilled
-  // 21-27 registers per lane; TSD_ICP_SHAPE=8 forces the 8-points-per-thread shape, TSD_ICP_SHAPE >= 64 a thread count of <3,512>)
-  if (ctx->icp_shape == 8) return launch_icp_shape<8, 256>(ctx, tg, a, nthr, cap, P_dev, d_rays_local, d_ranges, d_mask, post);
-  if (pre && !icp_pre_supported(ctx, a)) return set_error(ctx, TSD_E_ARG, "launch_icp: the arg-max can only ride with the node's registration shape", hipSuccess);
-  if (nthr <= 3 * 512) return launch_icp_shape<3, 512>(ctx, tg, a, nthr, cap, P_dev, d_rays_local, d_ranges, d_mask, post, ctx->icp_shape >= 64 ? ctx->icp_shape : 0, pre);
-  return launch_icp_shape<8, 256>(ctx, tg, a, nthr, cap, P_dev, d_rays_local, d_ranges, d_mask, post);
-}
-
-template <int R, int MAXT>
-static int launch_icp_pairs_shape(tsd_ctx* ctx, const IcpArgs& a, int n, int cap, int* d_pairs)
-{
-  int T = icp_threads_for(n, R, MAXT);
-  if (T > MAXT) return set_error(ctx, TSD_E_CAPACITY, "icp workgroup shape", hipSuccess);
-  const size_t lds = icp_lds_bytes_for(cap, T, false);
-  if (lds > 160u * 1024u) return set_error(ctx, TSD_E_CAPACITY, "registration does not fit the LDS of one CU", hipSuccess);
-  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp_pairs<R, MAXT>), lds)) return rc;
-  hipLaunchKernelGGL((k_icp_pairs<R, MAXT>), dim3(1), dim3(T), lds, ctx->stream, a, cap, ctx->d_model, ctx->d_scene, ctx->d_morig, ctx->d_start,
-                     ctx->d_icp_res, ctx->d_icp_trace, d_pairs);
-  TSD_HIP_CHECK(ctx, hipGetLastError());
-  return TSD_OK;
+  const IcpShape s = icp_shape_for(n, nthr, a.estimator == TSD_ESTIMATOR_POINT_TO_LINE, ctx->icp_shape, ICP_TL_BYTES);
+  if (s.rc) return shape_error(ctx, s);
+  // fused registration_mode 3, the node's shape (icp_pre_supported): the arg-max rides as the launch's first workgroup
+  if (pre && !(s.node && post.st && ctx->icp_shape == 0))
+    return set_error(ctx, TSD_E_ARG, "launch_icp: the arg-max can only ride with the node's registration shape", hipSuccess);
+  // the per-iteration record (tsd_icp_trace) is kept by tsd_icp / tsd_localize; the fused scan has no reader for it and skips
+  // the 64-byte store per step
+  double* trace_buf = post.st ? nullptr : tg.trace;
+#ifdef TSD_ICP_TIMELINE
+  if (post.st) trace_buf = ctx->d_icp_trace;     // (diagnostic build: the stamps of a fused scan's registration; no per-step record)
+#endif
+  const IcpSeedArgs sa = icp_seed_args(tg.icp_seed, tg.icp_seed_points, icp_helpers(ctx->icp_helpers, nthr, s.T));
+  if (pre) {
+    const auto kernel = k_icp_pre<3, 512, 1088, 512>;
+    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kernel), s.lds)) return rc;
+    ScopedKernelTimer t(ctx, "icp");
+    // (the launch's own completion is the event a pre-registration armed AHEAD waits for before it overwrites the inputs; a timed
+    // dispatch needs its stop event for the timer: a marker behind it then)
+    hipEvent_t stop = t.b ? t.b : pre->done;
+    hipExtLaunchKernelGGL(kernel, dim3(2 + sa.helpers), dim3(s.T), s.lds, tg.stream, t.a, stop, 0, a, P_dev, s.cap,
+                     tg.coords, tg.mask_m, d_rays_local, d_ranges, d_mask, tg.icp_res, trace_buf, post, sa, pre->dev);
+    TSD_HIP_CHECK(ctx, hipGetLastError());
+    if (t.b && pre->done) TSD_HIP_CHECK(ctx, hipEventRecord(pre->done, tg.stream));
+    return TSD_OK;
+  }
+  return icp_with_shape(s, [&](auto tag) -> int {
+    using S = decltype(tag);
+    const auto kernel = k_icp<S::R, S::MAXT, S::PTL, S::FCAP, S::FT>;
+    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kernel), s.lds)) return rc;
+    ScopedKernelTimer t(ctx, "icp");
+    hipExtLaunchKernelGGL(kernel, dim3(1 + sa.helpers), dim3(s.T), s.lds, tg.stream, t.a, t.b, 0, a, P_dev, s.cap, ctx->d_model, ctx->d_scene,
+                     ctx->d_morig, ctx->d_start, tg.coords, tg.mask_m, d_rays_local, d_ranges, d_mask, tg.icp_res,
+                     trace_buf, post, ctx->d_mnormals, tg.normals, sa);
+    TSD_HIP_CHECK(ctx, hipGetLastError());
+    return TSD_OK;
+  });
 }
 
 // direct mode, closed form, the default workgroup shapes of launch_icp; d_pairs = [a.iterations][icp_pairs_cap(n)] ints preset to -1
 int icp_pairs_cap(int n_model, int n_scene) { return icp_cap_for(n_model > n_scene ? n_model : n_scene); }
 int launch_icp_pairs(tsd_ctx* ctx, const IcpArgs& a, int* d_pairs)
 {
-  const int n = a.n_model > a.n_scene ? a.n_model : a.n_scene;
-  if (n > TSD_MAX_ICP_POINTS) return set_error(ctx, TSD_E_CAPACITY, "icp points > TSD_MAX_ICP_POINTS", hipSuccess);
-  const int cap = icp_cap_for(n);
-  if (a.n_scene <= 3 * 512) return launch_icp_pairs_shape<3, 512>(ctx, a, a.n_scene, cap, d_pairs);
-  return launch_icp_pairs_shape<8, 256>(ctx, a, a.n_scene, cap, d_pairs);
-}
-
-template <int R, int MAXT, bool PTL>
-static int launch_icp_batch_shape(tsd_ctx* ctx, hipStream_t stream, const IcpBatchEntry* d_entries, int n, int nthr, int cap, int helpers)
-{
-  int T = icp_threads_for(nthr, R, MAXT);
-  if (T > MAXT) return set_error(ctx, TSD_E_CAPACITY, "icp workgroup shape", hipSuccess);
-  const size_t lds = icp_lds_bytes_for(cap, T, PTL);
-  if (lds > 160u * 1024u) return set_error(ctx, TSD_E_CAPACITY, "registration does not fit the LDS of one CU", hipSuccess);
-  if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp_batch<R, MAXT, PTL>), lds)) return rc;
-  ScopedKernelTimer t(ctx, "icp");
-  if (R == 3 && MAXT == 512 && !PTL && cap == 1088 && T == 512) {        // (the default scanner's shape: compile-time LDS layout, see launch_icp_shape_est)
-    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_icp_batch<3, 512, false, 1088, 512>), lds)) return rc;
-    hipExtLaunchKernelGGL((k_icp_batch<3, 512, false, 1088, 512>), dim3(n * (1 + helpers)), dim3(T), lds, stream, t.a, t.b, 0, d_entries, cap, n);
+  const IcpShape s = icp_shape_for(a.n_model > a.n_scene ? a.n_model : a.n_scene, a.n_scene, false, 0, 0);
+  if (s.rc) return shape_error(ctx, s);
+  return icp_with_shape(s, [&](auto tag) -> int {
+    using S = decltype(tag);
+    const auto kernel = k_icp_pairs<S::R, S::MAXT>;          // (no layout of its own for the node's shape)
+    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kernel), s.lds)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(s.T), s.lds, ctx->stream, a, s.cap, ctx->d_model, ctx->d_scene, ctx->d_morig, ctx->d_start,
+                       ctx->d_icp_res, ctx->d_icp_trace, d_pairs);
     TSD_HIP_CHECK(ctx, hipGetLastError());
     return TSD_OK;
-  }
-  hipExtLaunchKernelGGL((k_icp_batch<R, MAXT, PTL>), dim3(n * (1 + helpers)), dim3(T), lds, stream, t.a, t.b, 0, d_entries, cap, n);
-  TSD_HIP_CHECK(ctx, hipGetLastError());
-  return TSD_OK;
+  });
 }
 
 // every registration of a batch runs in the same workgroup shape (the widest sensor decides) and with the same estimator
@@ -1786,28 +1662,30 @@ int launch_icp_batch(tsd_ctx* ctx, hipStream_t stream, const IcpBatchEntry* host
     if (host[i].a.beams < 1) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin: fused registrations only", hipSuccess);
     if (host[i].a.beams > beams) beams = host[i].a.beams;
   }
-  if (beams > TSD_MAX_ICP_POINTS) return set_error(ctx, TSD_E_CAPACITY, "icp points > TSD_MAX_ICP_POINTS", hipSuccess);
-  const int cap = icp_cap_for(beams);
   const bool ptl = host[0].a.estimator == TSD_ESTIMATOR_POINT_TO_LINE;
+  const IcpShape s = icp_batch_shape(beams, ptl);
+  if (s.rc) return shape_error(ctx, s);
   if (host[0].a.estimator != TSD_ESTIMATOR_CLOSED_FORM && !ptl) return set_error(ctx, TSD_E_ARG, "tsd_icp_params.estimator", hipSuccess);
-  // (the entries' seed arguments were filled by the caller with icp_batch_helpers(): the largest helper count of the batch sizes the grid)
+  // (the entries' seed arguments were filled by the caller with icp_batch_seed_args(): the largest helper count of the batch sizes the grid)
   int helpers = 0;
   for (int i = 0; i < n; i++) if (host[i].seed.helpers > helpers) helpers = host[i].seed.helpers;
-  if (beams <= 3 * 512)
-    return ptl ? launch_icp_batch_shape<3, 512, true>(ctx, stream, d_entries, n, beams, cap, helpers)
-               : launch_icp_batch_shape<3, 512, false>(ctx, stream, d_entries, n, beams, cap, helpers);
-  return ptl ? launch_icp_batch_shape<8, 256, true>(ctx, stream, d_entries, n, beams, cap, helpers)
-             : launch_icp_batch_shape<8, 256, false>(ctx, stream, d_entries, n, beams, cap, helpers);
+  return icp_with_shape(s, [&](auto tag) -> int {
+    using S = decltype(tag);
+    const auto kernel = k_icp_batch<S::R, S::MAXT, S::PTL, S::FCAP, S::FT>;
+    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(kernel), s.lds)) return rc;
+    ScopedKernelTimer t(ctx, "icp");
+    hipExtLaunchKernelGGL(kernel, dim3(n * (1 + helpers)), dim3(s.T), s.lds, stream, t.a, t.b, 0, d_entries, s.cap, n);
+    TSD_HIP_CHECK(ctx, hipGetLastError());
+    return TSD_OK;
+  });
 }
 
-size_t icp_lds_bytes() { return icp_lds_bytes_for(TSD_MAX_ICP_POINTS, 256); }
-
-// seed arguments of one entry of a batch (tsd_batch_begin): the workgroup shape launch_icp_batch will choose for `batch_beams`;
-// `buf` was sized icp_seed_bytes(beams)
+// seed arguments of one entry of a batch (tsd_batch_begin) whose widest sensor has `batch_beams`: the helpers of `beams` points in the
+// batch's workgroups; `buf` was sized icp_seed_bytes(beams)
 IcpSeedArgs icp_batch_seed_args(const tsd_ctx* ctx, void* buf, int beams, int batch_beams)
 {
-  const int T = batch_beams <= 3 * 512 ? icp_threads_for(batch_beams, 3, 512) : icp_threads_for(batch_beams, 8, 256);
-  return icp_seed_args(buf, beams, icp_helpers_for(ctx, beams, T));
+  const IcpShape s = icp_batch_shape(batch_beams, false);        // (the estimator does not move the thread count)
+  return icp_seed_args(buf, beams, s.rc ? 0 : icp_helpers(ctx->icp_helpers, beams, s.T));   // (no shape: launch_icp_batch will say so)
 }
 
 }  // namespace tsd

@@ -518,6 +518,7 @@ int launch_grid_digest(tsd_ctx* ctx, unsigned long long* d_out, double* d_sums);
 // launch's own stop event: no marker behind it; a timed dispatch needs its stop event for the timer and records `done` behind it)
 int launch_raycast(tsd_ctx* ctx, const LaunchTarget& tg, const RaycastArgs& a, const RaycastArgs* a_dev, const double* d_rays,
                    const HaloArgs* halo = nullptr, hipEvent_t done = nullptr);
+// ---- the registration (icp_kernels.hip; the workgroup shape of every launch: icp_shape.hpp)
 // pre: fused registration_mode 3 -- the pre-registration's arg-max rides as the first workgroup of the registration's launch (k_icp_pre;
 // only where icp_pre_supported() says so); pre->done is recorded when the launch has completed
 bool icp_pre_supported(const tsd_ctx* ctx, const IcpArgs& a);
@@ -525,6 +526,12 @@ int launch_icp(tsd_ctx* ctx, const LaunchTarget& tg, const IcpArgs& a, const dou
                const double* d_ranges, const uint8_t* d_mask, const ScanPostArgs* post = nullptr, const IcpPreLaunch* pre = nullptr);
 int launch_icp_pairs(tsd_ctx* ctx, const IcpArgs& a, int* d_pairs);
 int icp_pairs_cap(int n_model, int n_scene);
+// the registrations of a batch in one launch on `stream`; the entry array lives in device memory, `host` is the host copy it was staged
+// from, its seed arguments filled with icp_batch_seed_args() (`batch_beams`: the widest sensor's)
+int launch_icp_batch(tsd_ctx* ctx, hipStream_t stream, const IcpBatchEntry* host, const IcpBatchEntry* d_entries, int n);
+IcpSeedArgs icp_batch_seed_args(const tsd_ctx* ctx, void* buf, int beams, int batch_beams);
+size_t icp_seed_bytes(int points);
+
 int launch_scan_prepare(tsd_ctx* ctx, SensorDev* st);
 // one wave on the context's stream that waits (on the device, bounded) until *seq == value; when the bound runs out it switches
 // the push behind it off (push->enabled = 0) and raises *err_host (coherent host memory) instead of letting stale arguments through
@@ -540,13 +547,10 @@ int probe_cross_stream_wait(tsd_ctx* ctx, hipStream_t a, hipStream_t b, unsigned
 int launch_raycast_batch(tsd_ctx* ctx, hipStream_t stream, const RaycastBatchEntry* d_entries, int n, int max_beams);
 int launch_raycast_batch_byval(tsd_ctx* ctx, hipStream_t stream, const RaycastBatchEntry* h_entries, int n, int max_beams);   // n <= RC_BATCH_BYVAL
 int launch_push_tables_batch(tsd_ctx* ctx, hipStream_t stream, const TablesBatchEntry* d_entries, int n, int max_beams);
-int launch_icp_batch(tsd_ctx* ctx, hipStream_t stream, const IcpBatchEntry* host, const IcpBatchEntry* d_entries, int n);
 int push_multi_max_robots();
 int launch_push_multi(tsd_ctx* ctx, hipStream_t stream, int n, const PushJob* jobs);
 int launch_wait_seq_multi(tsd_ctx* ctx, int n, const unsigned long long* const* seq, const unsigned long long* value, PushArgs* const* push,
                           unsigned int* err_host, unsigned int poll_bound);
-size_t icp_seed_bytes(int points);
-IcpSeedArgs icp_batch_seed_args(const tsd_ctx* ctx, void* buf, int beams, int batch_beams);
 
 void reloc_free(tsd_ctx* ctx);               // reloc.hip: releases tsd_ctx::reloc (tsd_destroy)
 void surface_free(tsd_ctx* ctx);             // surface.hip: releases tsd_ctx::surface (tsd_destroy)
@@ -558,7 +562,6 @@ struct OccHeads { unsigned int* cur; unsigned int* next; };
 OccHeads next_occ_heads(tsd_ctx* ctx);
 int launch_occ_mark(tsd_ctx* ctx, int8_t* d_out, int* d_count, int inflate, int inflate_factor, const unsigned int* heads, int max_tiles = -1);
 int launch_color_image(tsd_ctx* ctx, const double* d_px, const double* d_py, unsigned width, unsigned height, uint8_t* d_image);
-size_t icp_lds_bytes();
 
 // pose helpers (host): textbook LU inverse with partial pivoting in the order of
 // gsl_linalg_LU_decomp / LU_invert as used by obvious::Matrix::invert (gsl/Matrix.cpp:168-179)
