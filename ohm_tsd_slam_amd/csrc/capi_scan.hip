@@ -273,13 +273,13 @@ static int scan_stage_host(tsd_sensor* s, const double* ranges, const uint8_t* m
   tsd_ctx* ctx = s->ctx;
   if (int rc = sensor_conc_init(s, false)) return rc;       // (the sensor's own table buffers)
   Lap lap(g_stage_timing);
-  // three buffers in turn (see tsd_sensor::Fused::stage_slot): the push that read this one three scans ago is done -- and so is the device
-  // copy out of the pinned buffer, which that push was ordered behind; its event is looked at all the same (one query)
-  const int sslot = s->fused.stage_slot;
-  s->fused.stage_slot = (s->fused.stage_slot + 1) % 3;
-  if (s->fused.scan_copy_valid[sslot]) { TSD_HIP_CHECK(ctx, hipEventSynchronize(s->fused.ev_scan_copy[sslot])); s->fused.scan_copy_valid[sslot] = false; }
+  // three buffers in turn (tsd::ScanLedger): the push that read this one three scans ago is done -- and so is the device copy out of
+  // the pinned buffer, which that push was ordered behind; its event is looked at all the same (one query)
+  const ScanLedger::HostWrite w = s->ledger.host_write(s->scan_bar);
+  const int sslot = w.slot;
+  if (w.wait_copy) TSD_HIP_CHECK(ctx, hipEventSynchronize(s->fused.ev_scan_copy[sslot]));
   // (the host writes the device buffer itself: with asynchronous mapping the push that last read it has to be SEEN done first)
-  if (s->scan_bar && s->async.slot_push_valid[sslot]) { TSD_HIP_CHECK(ctx, hipEventSynchronize(s->async.ev_slot_push[sslot])); s->async.slot_push_valid[sslot] = false; }
+  if (w.wait_push) TSD_HIP_CHECK(ctx, hipEventSynchronize(s->async.ev_slot_push[sslot]));
   lap.lap(0);
   scan_pack(s->scan_bar ? s->d_scan2[sslot] : s->fused.h_scan3[sslot], s->beams, ranges, mask, mask_push);
 #if defined(__x86_64__)
@@ -292,29 +292,27 @@ static int scan_stage_host(tsd_sensor* s, const double* ranges, const uint8_t* m
   lap.lap(1);
   s->fused.scan = scan_view(s->d_scan2[sslot], s->beams);
   s->fused.h_scan = s->scan_bar ? s->fused.scan : scan_view(s->fused.hd_scan3[sslot], s->beams);
-  s->fused.rmq = s->d_rmq2[sslot]; s->fused.slot = sslot;
-  s->fused.device_done = false;
-  s->fused.staged = true;
+  s->fused.rmq = s->d_rmq2[sslot];
   return TSD_OK;
 }
 
 static int scan_stage_device(tsd_sensor* s)
 {
   tsd_ctx* ctx = s->ctx;
-  const int sslot = s->fused.slot;
+  const int sslot = s->ledger.slot();
   Lap lap(g_stage_timing);
   // Asynchronous mapping: the push that last read this buffer (three scans back) ran on the push stream beside a registration, and
   // nothing the host has seen since is ordered behind it -- the copy and the tables below wait for that push's own event (done long
-  // ago in practice: one query; the stream-side wait is the fall-back).  Strict order: see tsd_sensor::Fused::stage_slot.
-  if (s->async.slot_push_valid[sslot]) {
+  // ago in practice: one query; the stream-side wait is the fall-back).  Strict order: see tsd::ScanLedger.
+  if (s->ledger.side_write(sslot)) {
     if (!host_saw_event(s->async.ev_slot_push[sslot], 0)) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, s->async.ev_slot_push[sslot], 0));
-    else s->async.slot_push_valid[sslot] = false;
+    else s->ledger.push_seen_done(sslot);
   }
   if (!s->scan_bar) {
     TSD_HIP_CHECK(ctx, hipMemcpyAsync(s->d_scan2[sslot], s->fused.h_scan3[sslot], scan_bytes(s->beams), hipMemcpyHostToDevice, ctx->stream2));
     lap.lap(2);
     TSD_HIP_CHECK(ctx, hipEventRecord(s->fused.ev_scan_copy[sslot], ctx->stream2));
-    s->fused.scan_copy_valid[sslot] = true;
+    s->ledger.copy_recorded(sslot);
     TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_h2d, ctx->stream2));
     lap.lap(3);
   }
@@ -327,7 +325,7 @@ static int scan_stage_device(tsd_sensor* s)
   (void)hipStreamQuery(ctx->stream2);
   lap.lap(4);
   if (g_stage_timing.on) g_stage_timing.n++;
-  s->fused.device_done = true;
+  s->ledger.device_staged();
   return TSD_OK;
 }
 
@@ -335,7 +333,7 @@ int tsd_sensor_set_async_mapping(tsd_sensor* s, int on)
 {
   if (!s || !s->ctx) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
-  if (s->fused.submitted) return set_error(ctx, TSD_E_ARG, "tsd_sensor_set_async_mapping: a scan is in flight", hipSuccess);
+  if (s->ledger.collect_due()) return set_error(ctx, TSD_E_ARG, "tsd_sensor_set_async_mapping: a scan is in flight", hipSuccess);
   if (int rc = enter(ctx)) return rc;
   if (on) {
     if (!ctx->stream_push) TSD_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->stream_push, hipStreamNonBlocking));
@@ -350,7 +348,7 @@ int tsd_sensor_set_async_mapping(tsd_sensor* s, int on)
   s->async.mapping = on != 0;
   // a ray cast enqueued ahead by the previous scan saw (strict) or did not see (asynchronous) that scan's push: the next scan of the
   // other kind casts again
-  s->fused.rc_pending = false;
+  s->ledger.raycast_void();
   return TSD_OK;
 }
 
@@ -386,7 +384,7 @@ int tsd_scan_stage(tsd_sensor* s, const double* ranges, const uint8_t* mask, con
   if (!s || !s->ctx || !ranges || !mask) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
   if (!s->posed) return set_error(ctx, TSD_E_ARG, "tsd_scan_stage before tsd_sensor_set_pose", hipSuccess);
-  if (s->fused.staged) return set_error(ctx, TSD_E_ARG, "tsd_scan_stage: a staged scan is waiting for tsd_scan_submit already", hipSuccess);
+  if (!s->ledger.may_stage()) return set_error(ctx, TSD_E_ARG, "tsd_scan_stage: a staged scan is waiting for tsd_scan_submit already", hipSuccess);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (int rc = scan_stage_host(s, ranges, mask, mask_push)) return rc;
   return scan_stage_device(s);
@@ -398,8 +396,12 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
   if (!s || !s->ctx || !params || !gates || (ranges && !mask)) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
   if (!s->posed) return set_error(ctx, TSD_E_ARG, "tsd_scan before tsd_sensor_set_pose", hipSuccess);
-  if (s->fused.submitted) return set_error(ctx, TSD_E_ARG, "tsd_scan_submit: the previous scan was not collected", hipSuccess);
-  if (!ranges && !s->fused.staged) return set_error(ctx, TSD_E_ARG, "tsd_scan_submit without a scan (none given, none staged)", hipSuccess);
+  ScanLedger& led = s->ledger;
+  switch (led.may_submit(ranges != nullptr)) {
+    case ScanLedger::Submit::not_collected: return set_error(ctx, TSD_E_ARG, "tsd_scan_submit: the previous scan was not collected", hipSuccess);
+    case ScanLedger::Submit::no_scan: return set_error(ctx, TSD_E_ARG, "tsd_scan_submit without a scan (none given, none staged)", hipSuccess);
+    case ScanLedger::Submit::ok: break;
+  }
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   Lap lap(g_scan_timing);
   if (g_scan_timing.on && g_scan_timing.last_return) {
@@ -408,52 +410,45 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     if (gap > g_scan_timing.max[0] && g_scan_timing.n > 8) { g_scan_timing.max[0] = gap; g_scan_timing.max_at[0] = g_scan_timing.n.load(); }
   }
   const bool staged_ahead = ranges == nullptr;
+  // ---- the scan.  One that came with this call goes into the next buffer; a scan staged ahead that is not the one that came is
+  // dropped first and its buffers are REUSED (ScanLedger::drop_staged): the new copy and tables follow the dropped ones on the side
+  // stream (pinned mode), and nothing else ever read the dropped data.
   if (ranges) {
-    // A scan staged ahead that is not the one that came is dropped -- and its buffers are REUSED for the scan that did come: the
-    // three-buffer rotation is only safe when it advances once per scan (the buffer two rotations back may still be read by the
-    // push of the previous scan, which is ordered behind nothing the host has seen).  The new copy and tables follow the dropped
-    // ones on the side stream (pinned mode), and nothing else ever read the dropped data.
-    if (s->fused.staged) {
-      s->fused.stage_slot = s->fused.slot;
-      // (BAR mode: the host is about to store into that buffer itself -- the dropped scan's tables kernel on the side stream, which
-      // reads it, has to be SEEN done first; pinned mode orders the new copy behind it on the side stream)
-      if (s->scan_bar && s->fused.device_done) TSD_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev_tables));
-    }
-    s->fused.staged = false;
+    // (BAR mode: the host is about to store into that buffer itself -- the dropped scan's tables kernel on the side stream, which
+    // reads it, has to be SEEN done first; pinned mode orders the new copy behind it on the side stream)
+    if (!led.may_stage() && led.drop_staged(s->scan_bar).need_tables_seen) TSD_HIP_CHECK(ctx, hipEventSynchronize(ctx->ev_tables));
     int rcs = scan_stage_host(s, ranges, mask, mask_push);
     if (rcs != TSD_OK) return rcs;
   }
-  s->fused.staged = false;
   // A scan that came with this call is in the scan buffer (device memory the host stored into, or the pinned buffer) and its tables are
   // not built yet: its registration reads it from there, and the tables (pinned mode: the device copy first) are enqueued BEHIND the
   // registration's launch -- the host's work on them no longer sits between the result of the
   // previous scan and this launch (the main stream ran dry for ~10 us per scan there; the push needs them 100+ us from now).
-  const bool icp_from_host = !s->fused.device_done;
+  const bool scan_from_host = led.scan_from_host();
+  const bool raycast_stands = led.raycast_stands(ctx->ledger.epoch());
+  led.submit();
   const ScanView scan = s->fused.scan;
   int rc = TSD_OK;
   lap.lap(1);
 
-  // The ray cast needs nothing from the scan (its pose arguments were left on the device by the previous
+  // ---- the ray cast needs nothing from the scan (its pose arguments were left on the device by the previous
   // registration), so the previous tsd_scan enqueued it right behind its push; it is launched here only if
   // something touched the grid, the sensor or the context's ray-cast outputs since.
   const LaunchTarget tg = ctx_target(ctx);
   const RaycastArgs ra = sensor_raycast_launch_args(s);
-  if (!(s->fused.rc_pending && s->fused.rc_epoch == ctx->ledger.epoch())) {
+  if (!raycast_stands) {
     if (int rcd_ = drain_async_push(ctx)) return rcd_;     // (asynchronous mapping: a push still on the push stream comes first)
     rc = launch_raycast(ctx, tg, ra, &s->d_state->rc, s->d_rays);
     if (rc != TSD_OK) return rc;
   }
-  s->fused.rc_pending = false;
   lap.lap(2);
   IcpArgs ia = sensor_icp_args(s, params);
-  // registration_mode 3: the pre-registration armed by tsd_scan_preregister runs here, between the ray cast and the registration,
-  // whose Tinit it leaves on the device
-  s->pre.ran = false;
+  // ---- registration_mode 3: the pre-registration armed by tsd_scan_preregister runs here, between the ray cast and the
+  // registration, whose Tinit it leaves on the device
   IcpPreLaunch prel;
   std::memset(&prel, 0, sizeof(prel));
   bool fold_argmax = false;
-  if (s->pre.armed) {
-    s->pre.armed = false;
+  if (s->pre_ledger.take()) {
     // (asynchronous mapping: the SCORING reads the grid -- the previous scan's push, still on the push stream, has to land first; the
     // normals and the list building ahead of it do not, and run beside that push.  The order is then ray cast, previous push,
     // pre-registration, registration: still one of the reference's interleavings)
@@ -464,9 +459,8 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     fold_argmax = !argmax_kernel && icp_pre_supported(ctx, ia);
     rc = launch_preregistration(ctx, s, tg.stream, tg.coords, tg.mask_m, s->d_state->icpP, &ia.Tinit_dev, before_score, fold_argmax ? &prel : nullptr);
     if (rc != TSD_OK) return rc;
-    s->pre.ran = true;
   }
-  // the gates, Sensor::transform and the push decision run as the epilogue of the registration kernel
+  // ---- the registration: the gates, Sensor::transform and the push decision run as the epilogue of the registration kernel
   const unsigned long long seq = ++s->seq;
   ScanPostArgs sp = sensor_post_args(s, seq, *gates);
   const bool async_map = s->async.mapping && s->async.d_push_slot != nullptr;
@@ -477,11 +471,11 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
   // cross-stream barrier between the two kernels; the barrier is the fall-back.  (A scan staged ahead was copied
   // during the previous registration: nothing to wait for.)
   if (s->fused.d_bar_mismatch) {
-    hipLaunchKernelGGL(k_bar_verify, dim3(4), dim3(256), 0, ctx->stream, reinterpret_cast<const unsigned char*>(s->d_scan2[s->fused.slot]),
-                       reinterpret_cast<const unsigned char*>(s->fused.hd_scan3[s->fused.slot]), (int)scan_bytes(s->beams), s->fused.d_bar_mismatch);
+    hipLaunchKernelGGL(k_bar_verify, dim3(4), dim3(256), 0, ctx->stream, reinterpret_cast<const unsigned char*>(s->d_scan2[led.slot()]),
+                       reinterpret_cast<const unsigned char*>(s->fused.hd_scan3[led.slot()]), (int)scan_bytes(s->beams), s->fused.d_bar_mismatch);
     TSD_HIP_CHECK(ctx, hipGetLastError());
   }
-  if (icp_from_host) {
+  if (scan_from_host) {
     rc = launch_icp(ctx, tg, ia, s->d_state->icpP, s->d_rays_local, s->fused.h_scan.ranges, s->fused.h_scan.mask, &sp, fold_argmax ? &prel : nullptr);
     if (rc != TSD_OK) return rc;
     rc = scan_stage_device(s);
@@ -492,6 +486,7 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     if (rc != TSD_OK) return rc;
   }
   lap.lap(3);
+  // ---- the push and the next scan's ray cast
   PushJob job = sensor_push_job(s, scan, s->fused.rmq, *gates);      // this scan's tables (the sensor's own buffers)
   // TSD_HALO_KERNEL=1: the push's halo pass as a kernel of its own even here (the form every other path uses; A/B)
   static const bool halo_in_raycast = [] { const char* e = std::getenv("TSD_HALO_KERNEL"); return !(e && *e == '1'); }();
@@ -511,7 +506,7 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
       if (halo_in_raycast) (void)launch_push_halo(ctx, ctx->stream, halo);      // (the grid's halos must not stay behind the push whatever happened to the ray cast)
       return rc;
     }
-    s->fused.rc_pending = true; s->fused.rc_epoch = ctx->ledger.epoch();      // (as the push left it)
+    led.raycast_ahead(ctx->ledger.epoch());      // (as the push left it)
     lap.lap(5);
   } else {
     // Asynchronous mapping (the reference's ThreadMapping: queuePush returns at once and the push lands when the mapping thread gets
@@ -531,16 +526,16 @@ int tsd_scan_submit(tsd_sensor* s, const double* ranges, const uint8_t* mask, co
     job.a_dev = push_slot;                                 // (its own copy of the arguments, see above)
     rc = launch_push(ctx, ctx->stream_push, job);
     if (rc != TSD_OK) return rc;
-    ctx->ev_async_push = s->async.ev_slot_push[s->fused.slot];      // (fused.slot: the buffers of the scan being submitted)
-    s->async.slot_push_valid[s->fused.slot] = true;
+    ctx->ev_async_push = s->async.ev_slot_push[led.slot()];      // (the buffers of the scan being submitted)
+    led.push_recorded(led.slot());
     TSD_HIP_CHECK(ctx, hipEventRecord(ctx->ev_async_push, ctx->stream_push));
     (void)hipStreamQuery(ctx->stream_push);
     ctx->async_pending = true;
     // (the push moved the epoch: the ray cast enqueued above is, by design, the one that does not see it)
-    s->fused.rc_pending = true; s->fused.rc_epoch = ctx->ledger.epoch();
+    led.raycast_ahead(ctx->ledger.epoch());
     lap.lap(5);
   }
-  s->fused.submitted = true;
+  led.enqueued();
   return TSD_OK;
 }
 
@@ -548,8 +543,8 @@ int tsd_scan_collect(tsd_sensor* s, tsd_scan_result* result)
 {
   if (!s || !s->ctx || !result) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
-  if (!s->fused.submitted) return set_error(ctx, TSD_E_ARG, "tsd_scan_collect without tsd_scan_submit", hipSuccess);
-  s->fused.submitted = false;
+  if (!s->ledger.collect_due()) return set_error(ctx, TSD_E_ARG, "tsd_scan_collect without tsd_scan_submit", hipSuccess);
+  s->ledger.collect();
   Lap lap(g_scan_timing);
   const unsigned long long seq = s->seq;
   // The result is known once k_scan_post has run; the push kernels behind it only touch the grid, and
@@ -627,7 +622,7 @@ int tsd_scan_begin(tsd_sensor* s, const double* ranges, const uint8_t* mask, con
   if (!s || !s->ctx || !ranges || !mask || !params || !gates) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
   if (!s->posed) return set_error(ctx, TSD_E_ARG, "tsd_scan_begin before tsd_sensor_set_pose", hipSuccess);
-  if (s->split.inflight) return set_error(ctx, TSD_E_ARG, "tsd_scan_begin: the previous scan of this sensor was not finished", hipSuccess);
+  if (s->ledger.split_in_flight()) return set_error(ctx, TSD_E_ARG, "tsd_scan_begin: the previous scan of this sensor was not finished", hipSuccess);
   if (int rc = enter(ctx)) return rc;
   int rc = sensor_conc_init(s, true);
   if (rc != TSD_OK) return rc;
@@ -665,32 +660,31 @@ int tsd_scan_begin(tsd_sensor* s, const double* ranges, const uint8_t* mask, con
   __atomic_store_n(&s->split.rc_recorded, 1, __ATOMIC_RELEASE);      // (always: a writer may be spinning on it)
   if (rc != TSD_OK) return rc;
   if (e_rc != hipSuccess) return set_error(ctx, TSD_E_HIP, "hipEventRecord(ev_rc_done)", e_rc);
-  s->fused.rc_pending = false;
   const ScanPostArgs sp = sensor_post_args(s, ++s->seq, *gates);
   rc = launch_icp(ctx, tg, sensor_icp_args(s, params), s->d_state->icpP, s->d_rays_local, scan.ranges, scan.mask, &sp);
   if (rc != TSD_OK) return rc;
   TSD_HIP_CHECK(ctx, hipEventRecord(s->split.ev_icp_done, s->split.stream));
   s->split.gates = *gates; s->split.scan = scan;
-  s->split.inflight = true;
+  s->ledger.split_begin();
   lap.lap(3);
   return TSD_OK;
 }
 
 int tsd_scan_wait(tsd_sensor* s)
 {
-  if (!s || !s->split.inflight) return TSD_E_ARG;
+  if (!s || !s->ledger.split_in_flight()) return TSD_E_ARG;
   return wait_arrival([&] { return scan_result_arrived(s, s->seq); }, s->split.stream, no_nudge) ? TSD_OK : TSD_E_HIP;
 }
 
 int tsd_scan_finish(tsd_sensor* s, tsd_scan_result* result)
 {
-  if (!s || !s->ctx || !result || !s->split.inflight) return TSD_E_ARG;
+  if (!s || !s->ctx || !result || !s->ledger.split_in_flight()) return TSD_E_ARG;
   tsd_ctx* ctx = s->ctx;
   if (int rc = enter(ctx)) return rc;
   Lap lap(g_conc_timing);
   int rc = tsd_scan_wait(s);
   if (rc != TSD_OK) return set_error(ctx, TSD_E_HIP, "tsd_scan_finish: result record never arrived", hipSuccess);
-  s->split.inflight = false;
+  s->ledger.split_end();
   lap.lap(4);
   {
     // ORDERED SECTION: the push on the grid stream -- enqueued only now, when the registration has finished, so it
@@ -770,7 +764,7 @@ static void batch_abandon(tsd_batch* b, bool registration_launched)
   }
   if (b->stream) hipStreamSynchronize(b->stream);
   hipStreamSynchronize(ctx->stream);
-  for (tsd_sensor* s : b->sensors) if (s) s->split.inflight = false;
+  for (tsd_sensor* s : b->sensors) if (s) s->ledger.split_end();
   b->n = 0; b->push_enqueued = false;
 }
 
@@ -813,7 +807,7 @@ void tsd_batch_destroy(tsd_batch* b)
     auto& v = b->ctx->batches;
     v.erase(std::remove(v.begin(), v.end(), b), v.end());
   }
-  for (tsd_sensor* s : b->sensors) if (s) s->split.inflight = false;
+  for (tsd_sensor* s : b->sensors) if (s) s->ledger.split_end();
   for (hipEvent_t e : {b->ev_rc_done, b->ev_icp_done, b->ev_copy_done}) if (e) hipEventDestroy(e);
   if (b->stream) hipStreamDestroy(b->stream);
   if (b->h_stage) hipHostFree(b->h_stage);
@@ -843,7 +837,7 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
     tsd_sensor* s = sensors[i];
     if (!s || s->ctx != ctx || !ranges[i] || !mask[i]) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin: sensor / scan", hipSuccess);
     if (!s->posed) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin before tsd_sensor_set_pose", hipSuccess);
-    if (s->split.inflight) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin: a sensor has a scan in flight already", hipSuccess);
+    if (s->ledger.split_in_flight()) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin: a sensor has a scan in flight already", hipSuccess);
     for (int j = 0; j < i; j++) if (sensors[j] == s) return set_error(ctx, TSD_E_ARG, "tsd_batch_begin: a sensor appears twice", hipSuccess);
   }
   if (int rc = enter(ctx)) return rc;
@@ -863,6 +857,7 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
   b->seqs.resize((size_t)n); b->gates.assign(gates, gates + n); b->scan_off.resize((size_t)n);
   size_t off = b->head_bytes;
   int max_beams = 0;
+  std::vector<tsd_sensor*> armed;      // the robots whose scan comes with a pre-registration (registration_mode 3)
   for (int i = 0; i < n; i++) {
     tsd_sensor* s = sensors[i];
     if (s->beams > max_beams) max_beams = s->beams;
@@ -877,13 +872,13 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
     std::memset(&e, 0, sizeof(e));
     e.a = sensor_icp_args(s, &params[i]);
     // registration_mode 3 (tsd_scan_preregister armed this sensor): the registration starts from the pre-registration's result, which
-    // k_pdf_argmax leaves in the sensor's own buffer (the kernels go out below, behind the batch's ray casts)
-    if (s->pre.armed) e.a.Tinit_dev = reinterpret_cast<const double*>(s->pre.d + s->pre.layout.off_res);
+    // k_pdf_argmax leaves in the sensor's own buffer (the kernels go out below, behind the batch's ray casts); any other scan has no
+    // pre-registration result (tsd_scan_preregistration_result)
+    if (s->pre_ledger.take()) { e.a.Tinit_dev = reinterpret_cast<const double*>(s->pre.d + s->pre.layout.off_res); armed.push_back(s); }
     e.P_dev = s->d_state->icpP; e.coords = s->split.d_coords; e.mask_m = s->split.d_mask_m; e.rays_local = s->d_rays_local;
     e.ranges = scan.ranges; e.mask = scan.mask; e.out = s->split.d_icp_res; e.trace = nullptr /* no reader in the fused path */; e.normals = s->split.d_normals;
     const unsigned long long seq = ++s->seq;
     b->seqs[(size_t)i] = seq;
-    if (!s->pre.armed) s->pre.ran = false;                 // (tsd_scan_preregistration_result: this scan has none)
     e.post = sensor_post_args(s, seq, gates[i]);
     e.post.publish_done = 1;               // (tsd_batch_push gates this robot's push on it)
   }
@@ -897,8 +892,7 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
   // A batch that carries a pre-registration (registration_mode 3) orders its registrations behind the grid stream's work by an
   // event instead: the pre-registration kernels sit between the ray casts and the registrations, on the grid's stream -- the scoring
   // reads the grid, like the ray casts, and takes its place between the pushes the same way.
-  bool any_pre = false;
-  for (int i = 0; i < n; i++) any_pre |= sensors[i]->pre.armed;
+  const bool any_pre = !armed.empty();
   const bool dev_wait = b->dev_wait && !any_pre;
   if (dev_wait) {
     b->rc_batches++;
@@ -938,11 +932,8 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
       // TSD_PDFMatching::match of every armed robot (ThreadLocalize.cpp:557-567, each robot's own thread in the reference) on the
       // model its ray cast just produced; all of them score against the grid as it is before any push of this batch
       // (four launches for all of them: launch_preregistration_batch)
-      std::vector<tsd_sensor*> armed;
-      for (int i = 0; i < n; i++) if (sensors[i]->pre.armed) armed.push_back(sensors[i]);
       rc = launch_preregistration_batch(ctx, ctx->stream, armed.data(), (int)armed.size());
       if (rc != TSD_OK) return FAIL(rc);
-      for (tsd_sensor* s : armed) { s->pre.armed = false; s->pre.ran = true; }
     }
     if (dev_wait) {
       rc = launch_set_flag(ctx, ctx->stream, b->d_rc_flag, b->rc_batches);
@@ -958,7 +949,7 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
     icp_launched = true;
   }
   if (hipEventRecord(b->ev_icp_done, b->stream) != hipSuccess) return FAIL(set_error(ctx, TSD_E_HIP, "tsd_batch_begin: event", hipGetLastError()));
-  for (int i = 0; i < n; i++) { sensors[i]->split.inflight = true; sensors[i]->fused.rc_pending = false; }
+  for (int i = 0; i < n; i++) sensors[i]->ledger.split_begin();
   b->n = n; b->push_enqueued = false;
   return TSD_OK;
 }
@@ -1027,7 +1018,7 @@ int tsd_batch_results(tsd_batch* b, tsd_scan_result* results)
     // reserved != 0: this robot's registration never ran (k_icp_batch): flagged to the caller, the sensor's position untouched
     deliver_result(s, &results[i], s->h_result->reserved);
     if (results[i].reserved != 0) failed = results[i].reserved;
-    s->split.inflight = false;
+    s->ledger.split_end();
   }
   b->n = 0;
   if (failed) {

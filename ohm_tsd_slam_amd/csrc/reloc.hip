@@ -253,7 +253,7 @@ static bool lattice_near(const GridDev& g, double a0, int n, double step)
 
 static bool scan_in_flight(const tsd_ctx* ctx)
 {
-  for (const tsd_sensor* s : ctx->sensors) if (s->fused.submitted || s->split.inflight) return true;
+  for (const tsd_sensor* s : ctx->sensors) if (s->ledger.in_flight()) return true;
   for (const tsd_batch* b : ctx->batches) if (b->n > 0) return true;
   return false;
 }

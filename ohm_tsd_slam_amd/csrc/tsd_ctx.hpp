@@ -11,6 +11,7 @@
 
 #include "tsd_device.hpp"
 #include "grid_ledger.hpp"
+#include "scan_ledger.hpp"
 #include "../../include/tsd_hip.h"
 
 namespace tsd {
@@ -331,15 +332,22 @@ struct tsd_sensor {
   tsd::ScanResultDev* d_result = nullptr;   // device address of h_rwords (ScanPostArgs::out)
   unsigned long long seq = 0;
   double pos[2] = {0, 0};          // host mirror of the sensor position (window of the push launches)
-  // Shared by the fused and the split path: scan buffers (tsd::ScanView's layout), used in turn -- all three by the fused path
-  // (fused.stage_slot), 0 / 1 by the split path (split.scan_slot) -- and the range-query tables of a scan's push, in turn likewise
-  // (fused.stage_slot; split and batched path: 0 / 1 by split.rmq_slot).  The tables are allocated on first use (split.ready).
+  // Shared by the fused and the split path: scan buffers (tsd::ScanView's layout) and the range-query tables of a scan's push, used in
+  // turn -- all three by the fused path, as `ledger` hands them out; 0 / 1 by the split path (split.scan_slot; tables, batched path
+  // too: split.rmq_slot).  The tables are allocated on first use (split.ready).
   char* d_scan2[3] = {nullptr, nullptr, nullptr};
   char* d_rmq2[3] = {nullptr, nullptr, nullptr};
   // Where the device's memory is mapped into the host's address space (large PCIe BAR: every MI300-class server), d_scan2[] is
   // fine-grained device memory and the HOST writes a scan straight into it: no pinned copy, no device copy, and the registration reads
   // its 10 KB from local memory (1 us) instead of over the host link (3.5-4 us at the top of every registration: tools/exp/bar.hip).
   bool scan_bar = false;
+  // The bookkeeping of the scan paths (scan_ledger.hpp): buffer rotation, which events stand between a buffer and its next writer,
+  // staged / submitted / in flight, the ray cast ahead; how the next pre-registration is armed.  Their methods are the only writers.
+  // The fused path (tsd_scan_stage / _submit / _collect, tsd_scan_preregister, tsd_sensor_set_async_mapping) calls them under the
+  // caller's own grid mutex, like tsd_ctx::ledger; the split and batched paths call split_begin / split_end / split_in_flight and
+  // pre_ledger.take / launched_batch from the sensor's own thread (a sensor is driven by one path at a time).
+  tsd::ScanLedger ledger;
+  tsd::PreLedger pre_ledger;
 
   // tsd_scan_stage / _submit / _collect
   struct Fused {
@@ -349,35 +357,24 @@ struct tsd_sensor {
     char* h_scan3[3] = {nullptr, nullptr, nullptr};
     char* hd_scan3[3] = {nullptr, nullptr, nullptr};  // device addresses of h_scan3
     hipEvent_t ev_scan_copy[3] = {nullptr, nullptr, nullptr};   // "the device copy out of h_scan3[i] is done" (before the host rewrites it)
-    bool scan_copy_valid[3] = {false, false, false};
     unsigned int* h_bar_mismatch = nullptr;   // TSD_SCAN_BAR_VERIFY=1: bytes in which a scan's two copies differed on the device (pinned, coherent)
     unsigned int* d_bar_mismatch = nullptr;   // ... its device address
-    // the scan that is staged (copied, tables built) and not yet submitted
-    bool staged = false, submitted = false;
+    // the scan that was staged last (ledger.slot()): where it lies and where its push's tables go
     tsd::ScanView scan{};            // in d_scan2[slot]
     tsd::ScanView h_scan{};          // its ranges / mask in h_scan3[slot] (device addresses; scan_bar: the same as `scan`)
-    char* rmq = nullptr; int slot = 0;
-    bool device_done = false;        // the staged scan's device copy and tables are enqueued
-    int stage_slot = 0;              // the scan / table buffers are used in turn, THREE of them: the scan staged ahead of scan k+2 goes
-                                     // where scan k was, and by then the host has seen the result of scan k+1, whose ray cast ran behind
-                                     // the push of scan k on the stream -- so that push is done without any event on the stream.
-                                     // That argument needs the STRICT order.  With asynchronous mapping ray cast k+1 runs behind push
-                                     // k-1 and push k beside registration k+1 on the push stream: the host has no proof that it is
-                                     // done, so the staging waits for the buffer's own push event (async.ev_slot_push).
-    bool rc_pending = false;         // the next scan's ray cast was enqueued behind this scan's push ...
-    unsigned long long rc_epoch = 0; // ... when the context's ledger was at this epoch
+    char* rmq = nullptr;
   } fused;
 
   // asynchronous mapping of the fused path (tsd_sensor_set_async_mapping)
   struct Async {
     bool mapping = false;
     tsd::PushArgs* d_push_slot = nullptr;     // [2] push arguments by scan parity
-    hipEvent_t ev_slot_push[3] = {nullptr, nullptr, nullptr};   // "the push that read buffer i is done"
-    bool slot_push_valid[3] = {false, false, false};            // ... recorded and not yet seen complete
+    hipEvent_t ev_slot_push[3] = {nullptr, nullptr, nullptr};   // "the push that read buffer i is done" (ledger.push_recorded)
   } async;
 
   // fused registration_mode 3 (tsd_scan_preregister, tsdpdf.hip): inputs of the pre-registration that the next tsd_scan_submit runs
-  // on the device between its ray cast and its registration; one device + one pinned buffer, grown on demand
+  // on the device between its ray cast and its registration; one device + one pinned buffer, grown on demand (armed or not, copied
+  // how, where the collected scan's header / result are: pre_ledger)
   struct PreLayout {
     size_t off_S, off_ms, off_msp, off_dc, off_dt, in_bytes;             // inputs (host -> device each scan)
     size_t off_mo_m, off_mo_s, off_phi_m, off_phi_s, off_C, off_K, off_prob, off_hdr, off_res;
@@ -388,20 +385,15 @@ struct tsd_sensor {
     char* d = nullptr; char* h = nullptr; size_t bytes = 0;
     char* h_dev = nullptr;                    // `h` as the device sees it (looked up once per allocation)
     hipEvent_t ev_done = nullptr;             // the in-flight scan's pre-registration kernels have read their inputs (the arg-max's own stop event)
-    bool done_valid = false;
-    size_t res_off_hdr = 0, res_off_res = 0;  // where the collected scan's header / result are in `h` (the layout may be re-armed meanwhile)
     hipEvent_t ev = nullptr;                  // the pre-registration's inputs are on the device (copied on the side stream by tsd_scan_preregister)
-    bool copied = false;
-    bool bar = false;         // `d` is fine-grained device memory (tsd_sensor::scan_bar) ...
-    bool direct = false;      // ... and the armed inputs were stored into it by the host: nothing to copy, nothing to wait for
-    bool armed = false, ran = false;
+    bool bar = false;         // `d` is fine-grained device memory (tsd_sensor::scan_bar): the host may store the armed inputs into it
     unsigned int* d_flag = nullptr;           // k_icp_pre: the launch number of the last arg-max whose TBest stands (its own small allocation)
     unsigned int seq = 0;
     PreLayout layout{};
   } pre;
 
   // concurrent multi-robot path (tsd_scan_begin / tsd_scan_wait / tsd_scan_finish): ray cast + registration on the sensor's own stream
-  // into its own buffers, created on first use.  The batched path (tsd_batch_*) uses the buffers, `rmq_slot` and `inflight` as well.
+  // into its own buffers, created on first use.  The batched path (tsd_batch_*) uses the buffers and `rmq_slot` as well.
   struct Split {
     bool ready = false;
     hipStream_t stream = nullptr;      // ONE stream per sensor: streams are multiplexed onto a few in-order hardware queues
@@ -413,8 +405,7 @@ struct tsd_sensor {
     tsd::IcpResultDev* d_icp_res = nullptr; double* d_icp_trace = nullptr; void* d_icp_seed = nullptr;
     int scan_slot = 0, rmq_slot = 0;
     char* h_stage2[2] = {nullptr, nullptr};   // pinned staging of the scan, alternating
-    bool inflight = false;           // begin() without finish()
-    tsd_gate_params gates{};         // of the scan in flight, and where its push finds ranges / mask_push
+    tsd_gate_params gates{};         // of the scan in flight (ledger.split_in_flight), and where its push finds ranges / mask_push
     tsd::ScanView scan{};
   } split;
 };

@@ -956,13 +956,9 @@ extern "C" int tsd_scan_preregister(tsd_sensor* s, const tsd_tsdpdf_params* prm,
   if (!(prm->ang_res > 1e-6)) return set_error(ctx, TSD_E_ARG, "tsd_scan_preregister: resolution not properly set", hipSuccess);
   // A scan of this sensor may be IN FLIGHT (submitted, not collected): the pre-registration of the scan after it is then armed ahead --
   // its inputs are copied behind that scan's own pre-registration kernels (which read the same device buffer), beside its registration.
-  const bool inflight = s->fused.submitted;
-  if (s->split.inflight) return set_error(ctx, TSD_E_ARG, "tsd_scan_preregister: the sensor has a batched / split scan in flight (arm it between two scans)", hipSuccess);
+  const bool inflight = s->ledger.collect_due();
+  if (s->ledger.split_in_flight()) return set_error(ctx, TSD_E_ARG, "tsd_scan_preregister: the sensor has a batched / split scan in flight (arm it between two scans)", hipSuccess);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // The last side-stream copy out of the pinned buffer has to have left it before the host rewrites it (and, BAR mode, before the host
-  // stores into d_pre itself).  That copy belongs to the in-flight scan -- or to a pre-registration that was armed ahead while a scan
-  // was in flight and is now being RE-armed without having been submitted: nothing the host has seen is ordered behind that one.
-  if (s->pre.ev && s->pre.copied && !s->pre.direct) TSD_HIP_CHECK(ctx, hipEventSynchronize(s->pre.ev));
   tsd_sensor::PreLayout L{};
   L.n = n; L.trials = prm->trials; L.size_control_set = prm->size_control_set; L.zrand = prm->zrand;
   L.max_cand = (int)std::min<size_t>(pdf_candidate_bound(prm->phi_max, prm->ang_res, n, prm->trials, L.phi_max, L.span), (size_t)1 << 22);
@@ -975,10 +971,13 @@ extern "C" int tsd_scan_preregister(tsd_sensor* s, const tsd_tsdpdf_params* prm,
   L.off_C = carve(nCtrl * 16); L.off_K = carve((size_t)L.max_cand * sizeof(PdfCandidate));
   L.off_prob = carve((size_t)L.max_cand * 8); L.off_hdr = carve(sizeof(PdfHeader)); L.off_res = carve(sizeof(PdfResult));
   const size_t total = carve.off;
-  // The in-flight scan's arg-max writes its header and result into the PINNED buffer at the offsets of ITS layout (pre_res_off_*),
-  // and tsd_scan_preregistration_result reads them there after the collect: a layout that needs new buffers, or whose inputs would
-  // reach into those records, cannot be armed ahead -- the caller arms it after tsd_scan_collect.
-  if (inflight && s->pre.ran && (total > s->pre.bytes || L.in_bytes > s->pre.res_off_hdr))
+  PreLedger& led = s->pre_ledger;
+  const PreLedger::MayArm may = led.may_arm(inflight, total, L.in_bytes, s->pre.bytes);
+  // The last side-stream copy out of the pinned buffer has to have left it before the host rewrites it (and, BAR mode, before the host
+  // stores into d_pre itself): nothing the host has seen is ordered behind it.
+  if (s->pre.ev && may.sync_prev_copy) TSD_HIP_CHECK(ctx, hipEventSynchronize(s->pre.ev));
+  // (a layout that needs new buffers, or whose inputs would reach into the in-flight scan's result records: PreLedger::may_arm)
+  if (may.refused)
     return set_error(ctx, TSD_E_ARG, "tsd_scan_preregister: a larger layout than the in-flight scan's cannot be armed ahead of its collect", hipSuccess);
   if (total > s->pre.bytes) {
     TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1009,27 +1008,27 @@ extern "C" int tsd_scan_preregister(tsd_sensor* s, const tsd_tsdpdf_params* prm,
   // starts) is off the scan's chain.  The previous scan's kernels that read d_pre ran ahead of its registration, which has ended (the
   // scan was collected).  TSD_PRE_COPY_MAIN=1: the copy at tsd_scan_submit, on the main stream (round 3's first form; A/B).
   static const bool copy_main = [] { const char* e = std::getenv("TSD_PRE_COPY_MAIN"); return e && *e == '1'; }();
-  s->pre.copied = false; s->pre.direct = false;
-  if (s->pre.bar && !inflight && !copy_main) {
-    // the host stores the inputs into the device buffer itself (the previous scan was collected: nothing on the device reads it)
-    std::memcpy(s->pre.d, s->pre.h, L.in_bytes);
+  switch (led.arm(inflight, s->pre.bar, copy_main)) {
+    case PreLedger::Arm::refuse_copy_main:
+      return set_error(ctx, TSD_E_ARG, "tsd_scan_preregister ahead of the collect needs the side-stream copy (TSD_PRE_COPY_MAIN is set)", hipSuccess);
+    case PreLedger::Arm::direct:
+      // the host stores the inputs into the device buffer itself (the previous scan was collected: nothing on the device reads it)
+      std::memcpy(s->pre.d, s->pre.h, L.in_bytes);
 #if defined(__x86_64__)
-    _mm_sfence();
+      _mm_sfence();
 #endif
-    s->pre.copied = true; s->pre.direct = true;
-    s->pre.armed = true;
-    return TSD_OK;
+      break;
+    case PreLedger::Arm::side_copy_behind_done:
+      TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, s->pre.ev_done, 0));
+      [[fallthrough]];
+    case PreLedger::Arm::side_copy:
+      if (!s->pre.ev) TSD_HIP_CHECK(ctx, hipEventCreateWithFlags(&s->pre.ev, hipEventDisableTiming));
+      TSD_HIP_CHECK(ctx, hipMemcpyAsync(s->pre.d, s->pre.h, L.in_bytes, hipMemcpyHostToDevice, ctx->stream2));
+      TSD_HIP_CHECK(ctx, hipEventRecord(s->pre.ev, ctx->stream2));
+      (void)hipStreamQuery(ctx->stream2);
+      break;
+    case PreLedger::Arm::at_submit: break;
   }
-  if (copy_main && inflight) return set_error(ctx, TSD_E_ARG, "tsd_scan_preregister ahead of the collect needs the side-stream copy (TSD_PRE_COPY_MAIN is set)", hipSuccess);
-  if (!copy_main) {
-    if (inflight && s->pre.done_valid) TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream2, s->pre.ev_done, 0));
-    if (!s->pre.ev) TSD_HIP_CHECK(ctx, hipEventCreateWithFlags(&s->pre.ev, hipEventDisableTiming));
-    TSD_HIP_CHECK(ctx, hipMemcpyAsync(s->pre.d, s->pre.h, L.in_bytes, hipMemcpyHostToDevice, ctx->stream2));
-    TSD_HIP_CHECK(ctx, hipEventRecord(s->pre.ev, ctx->stream2));
-    (void)hipStreamQuery(ctx->stream2);
-    s->pre.copied = true;
-  }
-  s->pre.armed = true;
   return TSD_OK;
 }
 
@@ -1075,11 +1074,17 @@ static PreLaunch pre_launch_args(const tsd_sensor* s, const double* d_coords, co
 // by event) or, where that was switched off, here
 static int pre_inputs_ready(tsd_ctx* ctx, tsd_sensor* s, hipStream_t stream)
 {
-  if (s->pre.direct) return TSD_OK;
-  if (!s->pre.copied) TSD_HIP_CHECK(ctx, hipMemcpyAsync(s->pre.d, s->pre.h, s->pre.layout.in_bytes, hipMemcpyHostToDevice, stream));
-  else if (hipEventQuery(s->pre.ev) != hipSuccess) {
-    (void)hipGetLastError();                 // (hipErrorNotReady is sticky as "last error")
-    TSD_HIP_CHECK(ctx, hipStreamWaitEvent(stream, s->pre.ev, 0));
+  switch (s->pre_ledger.inputs_ready()) {
+    case PreLedger::Inputs::ready: break;
+    case PreLedger::Inputs::copy_now:
+      TSD_HIP_CHECK(ctx, hipMemcpyAsync(s->pre.d, s->pre.h, s->pre.layout.in_bytes, hipMemcpyHostToDevice, stream));
+      break;
+    case PreLedger::Inputs::wait_copy_event:
+      if (hipEventQuery(s->pre.ev) != hipSuccess) {
+        (void)hipGetLastError();                 // (hipErrorNotReady is sticky as "last error")
+        TSD_HIP_CHECK(ctx, hipStreamWaitEvent(stream, s->pre.ev, 0));
+      }
+      break;
   }
   return TSD_OK;
 }
@@ -1113,8 +1118,7 @@ int launch_preregistration(tsd_ctx* ctx, tsd_sensor* s, hipStream_t stream, cons
     } else
     hipExtLaunchKernelGGL(k_pdf_argmax, dim3(1), dim3(1024), 0, stream, nullptr, s->pre.ev_done, 0, pl.argmax.prob, pl.argmax.cand, pl.argmax.max_cand, pl.argmax.M,
                        pl.argmax.S, pl.argmax.out, pl.argmax.hdr, pl.argmax.host_hdr, pl.argmax.host_res);
-    s->pre.done_valid = true;
-    s->pre.res_off_hdr = L.off_hdr; s->pre.res_off_res = L.off_res;
+    s->pre_ledger.launched_single(L.off_hdr, L.off_res);
   }
   TSD_HIP_CHECK(ctx, hipGetLastError());
   *tinit_dev = reinterpret_cast<const double*>(s->pre.d + L.off_res);
@@ -1136,8 +1140,7 @@ int launch_preregistration_batch(tsd_ctx* ctx, hipStream_t stream, tsd_sensor* c
       const PreLaunch pl = pre_launch_args(s, s->split.d_coords, s->split.d_mask_m, s->d_state->icpP);
       bn.e[i] = pl.normals; bp.e[i] = pl.prepare; bs.e[i] = pl.score; ba.e[i] = pl.argmax;
       max_points = std::max(max_points, pl.normals.points); max_blocks = std::max(max_blocks, pl.score_blocks); max_lds = std::max(max_lds, pl.prep_lds);
-      s->pre.done_valid = false;              // (no event of this sensor's own behind the batched arg-max; batches are armed between scans)
-      s->pre.res_off_hdr = s->pre.layout.off_hdr; s->pre.res_off_res = s->pre.layout.off_res;
+      s->pre_ledger.launched_batch(s->pre.layout.off_hdr, s->pre.layout.off_res);      // (batches are armed between scans)
     }
     if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(k_pdf_prepare_batch), max_lds)) return rc;
     // (the scoring strides a fixed grid over each robot's candidates: a share of the single launch's grid per robot keeps the
@@ -1157,9 +1160,9 @@ int launch_preregistration_batch(tsd_ctx* ctx, hipStream_t stream, tsd_sensor* c
 extern "C" int tsd_scan_preregistration_result(tsd_sensor* s, tsd_tsdpdf_result* result)
 {
   if (!s || !s->ctx || !result) return TSD_E_ARG;
-  if (!s->pre.ran || s->fused.submitted) return set_error(s->ctx, TSD_E_ARG, "tsd_scan_preregistration_result: no collected scan with a pre-registration", hipSuccess);
-  const PdfHeader* hd = reinterpret_cast<const PdfHeader*>(s->pre.h + s->pre.res_off_hdr);
-  const PdfResult* r = reinterpret_cast<const PdfResult*>(s->pre.h + s->pre.res_off_res);
+  if (!s->pre_ledger.result_readable(s->ledger.collect_due())) return set_error(s->ctx, TSD_E_ARG, "tsd_scan_preregistration_result: no collected scan with a pre-registration", hipSuccess);
+  const PdfHeader* hd = reinterpret_cast<const PdfHeader*>(s->pre.h + s->pre_ledger.res_off_hdr());
+  const PdfResult* r = reinterpret_cast<const PdfResult*>(s->pre.h + s->pre_ledger.res_off_res());
   pdf_fill_result(result, r);
   result->candidates = hd->identity ? 0 : hd->n_cand;
   result->valid_model = hd->n_model_valid; result->valid_scene = hd->n_scene_valid; result->control_points = hd->n_control;
