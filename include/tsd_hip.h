@@ -561,6 +561,107 @@ int tsd_surface_extract(tsd_ctx* ctx, const tsd_surface_params* params, int* n);
 int tsd_surface_fetch(tsd_ctx* ctx, int first, int count, double* xy, double* normals, uint8_t* normal_ok);
 int tsd_surface_dev(tsd_ctx* ctx, const double** xy_dev, const double** normals_dev, const uint8_t** ok_dev, int* n);
 
+/* ---- map-to-map alignment: surface points against the TSD ------------------------------------------------------ */
+/* Which rigid transform carries one map into another?  tsd_align_points places a list of points (the surface of another map) in this
+ * context's grid; tsd_map_align takes the list from a second context.  Two stages, both on the device: a search over a pose lattice
+ * scored on the TSD (as tsd_relocalize, over map points and without its free-space gate), then a point-to-TSD Gauss-Newton refinement
+ * of the K best peaks, all peaks in one launch.
+ *
+ * Lattice: candidate (ix, iy, k), idx = (k * ny + iy) * nx + ix, carries a point p to R_k * (p - pivot) + (x0 + ix * step_xy,
+ * y0 + iy * step_xy): a lattice node is where the PIVOT lands, the rotation turns about the pivot (about the origin, one degree would
+ * move a point 13 m away by 0.2 m and smear the peaks).  The lattice fields have tsd_reloc_params' meaning and limits.
+ * Coarse score (k_align_score): over the coarse points -- every stride-th point of the list, stride = ceil(n / TSD_MAX_ICP_POINTS), minus
+ * the pivot (fp64 subtraction) -- the sum of 1048576 - (uint32)rint(fabs(v) * 1048576.0), v = TsdGrid::interpolateBilinear at
+ * ((c*px - s*py) + t.x, (s*px + c*py) + t.y), over the look-ups that succeed: tsd_relocalize's sum (one copy of the loop), no gate.  Peaks
+ * as there.
+ * Refinement (k_align_refine), per peak, state m = where the pivot lands (the node), (c, s) = the peak's rotation, gain = 1, prev = 0.
+ * One accumulation at the state, over ALL n points, p relative to the pivot: q = ((c*px - s*py) + m.x, (s*px + c*py) + m.y);
+ * v = interpolateBilinear(q), (nx, ny) = TsdGrid::interpolateNormal(q) (TsdGrid.cpp:517-546, normalised); the point counts (n_ok) when
+ * all five look-ups succeed and the unnormalised normal's length is > 10e-6; u = v / v_cut, w = (1 - u*u)^2 for |u| < 1, else 0 (Tukey);
+ * r = v * max_truncation; J = (nx, ny, nx * (-(q.y - m.y)) + ny * (q.x - m.x)); sums[11] = the six entries of A = sum w J J^T
+ * (00 01 02 11 12 22), b = -sum w J r, sum w, sum w r^2.  Every thread sums its points in index order, the workgroup's sums are
+ * reduced in a fixed order, no floating-point atomics: the same call twice gives the same bits.
+ * The iteration: accumulate; n_ok < 3: "degenerate", stop.  Converged, or `iterations` steps done: stop.  Solve A d = b by LDL^T without
+ * pivoting (fp64); a pivot <= 0 (or NaN): "degenerate", stop.  If d.prev < 0 in the metric dx*dx' + dy*dy' + lever^2 * dth*dth', gain =
+ * max(gain / 2, 1/16) (without this the iteration falls into a two-cycle on the kinks of the bilinear field); d *= gain; prev = d.
+ * (c, s) <- (c - s*dth, s + c*dth) / hypot(1, dth), renormalised by its own hypot (no sine on the device); m += (dx, dy).  Converged
+ * when hypot(dx, dy) < eps and lever * |dth| < eps; the sums of the record are then taken once more at the final state.
+ * Winner: the peak with the largest sum w whose status is not degenerate, the earlier peak keeps a tie (decided on the host).
+ * What the lattice has to be: the refinement sees a point only inside the cut, |tsd| < v_cut, i.e. within v_cut * max_truncation of
+ * a surface, so some node must bring most points that close: step_xy of the order of v_cut * max_truncation, and a rotation step of
+ * that length divided by the distance of the farthest surfaces from the pivot, unless near surfaces can pull the far ones in.
+ *
+ * The list sits half a cell below the field: calcCoords places a crossing between cells px-1 and px at (px - 1 + interp) * cs, while
+ * interpolateBilinear takes a cell's value to lie at its centre (px + 0.5) * cs.  A surface list is displaced by (-cs/2, -cs/2) against
+ * the zero set the look-ups read; tsd_map_align therefore stages p + (cs_src/2, cs_src/2).  tsd_align_points takes its points as
+ * they are: in field coordinates.  tsd_surface_* is unchanged. */
+#define TSD_ALIGN_MAX_POINTS (1 << 20)
+#define TSD_ALIGN_MAXITER    0   /* status of a peak: `iterations` steps without meeting eps */
+#define TSD_ALIGN_CONVERGED  1
+#define TSD_ALIGN_DEGENERATE 2
+typedef struct {
+  double  x0, y0, step_xy;      /* as tsd_reloc_params */
+  int32_t nx, ny, ntheta;
+  int32_t theta_wraps;
+  const double* cos_sin;
+  double  theta0, dtheta;
+  int32_t K;                    /* peaks to refine, 1 .. TSD_RELOC_MAX_PEAKS */
+  int32_t iterations;           /* Gauss-Newton steps at most, 0 .. 64 (0: the coarse pose with its sums) */
+  double  pivot_x, pivot_y;     /* in the points' (src's) coordinates, finite; tsd_map_align with both NaN: the centre of src's grid */
+  double  v_cut;                /* Tukey cut on the normalised tsd, in (0, 1]; 0 = the default 0.75 */
+  double  eps;                  /* metres, > 0; 0 = the default 1e-6 */
+  double  lever;                /* metres per radian in the step metric; <= 0: half of dst's grid width */
+  double  min_overlap, max_rms; /* found = converged, sum w / n >= min_overlap, rms <= max_rms (max_rms <= 0: no limit) */
+} tsd_align_params;
+typedef struct {                /* one refined peak (tsd_debug_align_peaks) */
+  int32_t  idx;                 /* lattice candidate */
+  uint32_t score;
+  int32_t  status;              /* TSD_ALIGN_* */
+  int32_t  iterations;          /* steps taken */
+  int32_t  n_ok;
+  int32_t  reserved;
+  double   m[2], c, s;          /* the final state */
+  double   gain;
+  double   sums[11];            /* at the final state */
+} tsd_align_peak;
+typedef struct {
+  int32_t  found;
+  int32_t  winner_idx;          /* candidate index of the winning peak, -1 without one */
+  double   T33[9];              /* src -> dst, 3x3 row-major: rotation (c, s), translation m - R * pivot; NaN without a winner */
+  double   coarse_x, coarse_y, coarse_cos, coarse_sin;   /* the winner's lattice pose (where the pivot lands) */
+  uint32_t winner_score;
+  int32_t  n_peaks, n_refined, iterations, converged;
+  int32_t  n, stride, n_ok;
+  double   weight_sum, rms, overlap;   /* sum w, sqrt(sum w r^2 / sum w), sum w / n */
+  double   info[6];             /* A at the end (00 01 02 11 12 22): the information matrix a pose graph would take */
+  int32_t  cell_off[2];         /* the whole-cell shift nearest to T in tsd_fuse's cell_off_xy convention for the pair (dst at 0, src at
+                                 * cell_off): src's cell (x, y) is dst's cell (x + cell_off[0], y + cell_off[1]) */
+  double   cell_error;          /* largest distance, in dst cells, between T p and p + cell_off * cs over the four corners p of src's grid
+                                 * (tsd_align_points: of a square of dst's size): < 0.5 says a whole-cell shift describes T */
+  double   search_ms, refine_ms;/* tsd_profile_enable: stream time of scores + peaks and of the refinement launch; 0 otherwise */
+} tsd_align_result;
+/* points_xy: n points x0 y0 x1 y1 .. in field coordinates, on the host or (on_device != 0) on ctx's device, complete before the call;
+ * 1 <= n (TSD_E_ARG) <= TSD_ALIGN_MAX_POINTS (TSD_E_CAPACITY); every coordinate finite and within TSD_RELOC_MAX_REACH grid widths
+ * (TSD_E_ARG; a device list is checked by the staging kernel and refused when the call's one wait returns).  Contract of tsd_relocalize:
+ * every argument is checked before the context is touched, refused with TSD_E_ARG while a scan of the context is in flight, only the
+ * grid is read (no cell, flag, ledger state or sensor changes), the call waits for its result, tsd_destroy frees the buffers kept
+ * (the score volume up to 2^23 candidates, the staged list, the records).  No peak or only degenerate ones: TSD_OK with found = 0. */
+int tsd_align_points(tsd_ctx* ctx, const tsd_align_params* params, const double* points_xy, int n, int on_device,
+                     tsd_align_result* result);
+/* The transform that carries src's map coordinates into dst's.  dst and src distinct contexts on one device (TSD_E_ARG otherwise), no
+ * scan of either in flight.  Runs tsd_surface_extract(src, NULL, &n) -- it REPLACES src's last surface list --, stages p + cs_src/2 into
+ * a buffer dst owns (a small kernel on dst's stream) and calls tsd_align_points.  n == 0 is no error: found = 0.  A caller that
+ * serialises each context with a lock of its own holds both for the call. */
+int tsd_map_align(tsd_ctx* dst, tsd_ctx* src, const tsd_align_params* params, tsd_align_result* result);
+/* TEST HOOK: the score volume of the last alignment of this context, as tsd_debug_reloc_scores */
+int tsd_debug_align_scores(tsd_ctx* ctx, uint32_t* scores, int cap);
+/* TEST HOOK: the per-peak records of the last alignment, in the peaks' order: copies min(n, cap), returns n */
+int tsd_debug_align_peaks(tsd_ctx* ctx, tsd_align_peak* records, int cap);
+/* TEST HOOK: one accumulation of the refinement kernel (its own code, iterations = 0) over n host points at the state (m, c, s) with
+ * pivot[2] and v_cut: sums[11] and n_ok */
+int tsd_debug_align_sums(tsd_ctx* ctx, const double* points_xy, int n, const double pivot[2], const double m[2], double c, double s,
+                         double v_cut, double sums[11], int* n_ok);
+
 /* ---- same-device merge group: N grids of one process on ONE GPU, one merged occupancy map ------------------ */
 /* The one-GPU counterpart of include/tsd_comm.h (whose RCCL all-reduce needs one GPU per rank): n contexts of this process on one
  * device, member i shifted by (cell_off_xy[2i], cell_off_xy[2i+1]) whole cells, merged by a local kernel into a width x height window.

@@ -186,6 +186,35 @@ class RelocResult(C.Structure):
                 ("search_ms", C.c_double), ("refine_ms", C.c_double)]
 
 
+ALIGN_MAX_POINTS = 1 << 20
+ALIGN_MAXITER, ALIGN_CONVERGED, ALIGN_DEGENERATE = 0, 1, 2
+
+
+class AlignParams(C.Structure):
+    """tsd_align_params"""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("step_xy", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("ntheta", C.c_int32), ("theta_wraps", C.c_int32), ("cos_sin", C.POINTER(C.c_double)), ("theta0", C.c_double),
+                ("dtheta", C.c_double), ("K", C.c_int32), ("iterations", C.c_int32), ("pivot_x", C.c_double), ("pivot_y", C.c_double),
+                ("v_cut", C.c_double), ("eps", C.c_double), ("lever", C.c_double), ("min_overlap", C.c_double), ("max_rms", C.c_double)]
+
+
+class AlignPeak(C.Structure):
+    """tsd_align_peak"""
+    _fields_ = [("idx", C.c_int32), ("score", C.c_uint32), ("status", C.c_int32), ("iterations", C.c_int32), ("n_ok", C.c_int32),
+                ("reserved", C.c_int32), ("m", C.c_double * 2), ("c", C.c_double), ("s", C.c_double), ("gain", C.c_double),
+                ("sums", C.c_double * 11)]
+
+
+class AlignResult(C.Structure):
+    """tsd_align_result"""
+    _fields_ = [("found", C.c_int32), ("winner_idx", C.c_int32), ("T33", C.c_double * 9), ("coarse_x", C.c_double),
+                ("coarse_y", C.c_double), ("coarse_cos", C.c_double), ("coarse_sin", C.c_double), ("winner_score", C.c_uint32),
+                ("n_peaks", C.c_int32), ("n_refined", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32),
+                ("n", C.c_int32), ("stride", C.c_int32), ("n_ok", C.c_int32), ("weight_sum", C.c_double), ("rms", C.c_double),
+                ("overlap", C.c_double), ("info", C.c_double * 6), ("cell_off", C.c_int32 * 2), ("cell_error", C.c_double),
+                ("search_ms", C.c_double), ("refine_ms", C.c_double)]
+
+
 class SurfaceParams(C.Structure):
     """tsd_surface_params"""
     _fields_ = [("tx0", C.c_int32), ("ty0", C.c_int32), ("tx1", C.c_int32), ("ty1", C.c_int32), ("want_normals", C.c_int32),
@@ -261,6 +290,11 @@ ABI = {
     "tsd_debug_reloc_scores": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),
     "tsd_debug_reloc_peaks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_uint32), _ip]),
+    "tsd_align_points": (C.c_int, [C.c_void_p, C.POINTER(AlignParams), C.c_void_p, C.c_int, C.c_int, C.POINTER(AlignResult)]),
+    "tsd_map_align": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AlignParams), C.POINTER(AlignResult)]),
+    "tsd_debug_align_scores": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),
+    "tsd_debug_align_peaks": (C.c_int, [C.c_void_p, C.POINTER(AlignPeak), C.c_int]),
+    "tsd_debug_align_sums": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_double, C.c_double, C.c_double, _dp, _ip]),
     "tsd_surface_extract": (C.c_int, [C.c_void_p, C.POINTER(SurfaceParams), _ip]),
     "tsd_surface_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _u8p]),
     "tsd_surface_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _ip]),
@@ -345,7 +379,8 @@ def load_library(path: str | None = None):
                           ("tsd_pdfmatch_params", PdfMatchParams), ("tsd_rnmatch_params", RnMatchParams),
                           ("tsd_rnmatch_result", RnMatchResult), ("tsd_map_params", MapParams),
                           ("tsd_fuse_stats", FuseStats), ("tsd_map_window", MapWindow), ("tsd_reloc_params", RelocParams),
-                          ("tsd_reloc_result", RelocResult), ("tsd_surface_params", SurfaceParams)):
+                          ("tsd_reloc_result", RelocResult), ("tsd_surface_params", SurfaceParams),
+                          ("tsd_align_params", AlignParams), ("tsd_align_peak", AlignPeak), ("tsd_align_result", AlignResult)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -607,6 +642,84 @@ class TsdGridDevice:
                                             idx.ctypes.data_as(C.POINTER(C.c_int32)), sc.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n))
         self._check(rc, "tsd_debug_reloc_peaks")
         return idx[:n.value].copy(), sc[:n.value].copy()
+
+    @staticmethod
+    def _align_params(x0, y0, step_xy, nx, ny, ntheta, theta0, dtheta, cos_sin, theta_wraps, K, iterations, pivot, v_cut, eps, lever,
+                      min_overlap, max_rms):
+        tab = None if cos_sin is None else _f64(cos_sin).reshape(-1)
+        assert tab is None or tab.size == 2 * ntheta
+        pv = (float("nan"), float("nan")) if pivot is None else (float(pivot[0]), float(pivot[1]))
+        prm = AlignParams(float(x0), float(y0), float(step_xy), int(nx), int(ny), int(ntheta), int(bool(theta_wraps)),
+                          None if tab is None else _d(tab), float(theta0), float(dtheta), int(K), int(iterations), pv[0], pv[1],
+                          float(v_cut), float(eps), float(lever), float(min_overlap), float(max_rms))
+        return prm, tab                # (the table must outlive the call)
+
+    @staticmethod
+    def _align_dict(r: AlignResult) -> dict:
+        return dict(found=bool(r.found), T=np.array(r.T33[:]).reshape(3, 3), idx=int(r.winner_idx), score=int(r.winner_score),
+                    coarse=(r.coarse_x, r.coarse_y, r.coarse_cos, r.coarse_sin), n_peaks=int(r.n_peaks), n_refined=int(r.n_refined),
+                    iterations=int(r.iterations), converged=bool(r.converged), n=int(r.n), stride=int(r.stride), n_ok=int(r.n_ok),
+                    weight_sum=r.weight_sum, rms=r.rms, overlap=r.overlap, info=np.array(r.info[:]),
+                    cell_off=(int(r.cell_off[0]), int(r.cell_off[1])), cell_error=r.cell_error, search_ms=r.search_ms,
+                    refine_ms=r.refine_ms, raw=bytes(r))
+
+    def align_points(self, points_xy, x0, y0, step_xy, nx, ny, ntheta, pivot, theta0=0.0, dtheta=0.0, cos_sin=None,
+                     theta_wraps=False, K=16, iterations=40, v_cut=0.75, eps=1e-6, lever=0.0, min_overlap=0.0, max_rms=0.0,
+                     device_ptr=None, n=None) -> dict:
+        """tsd_align_points: the rigid transform that carries ``points_xy`` (n, 2; field coordinates) into this grid: lattice search
+        (a node is where ``pivot`` lands, the rotations turn about it), then the Gauss-Newton refinement of the K best peaks on the
+        device.  ``device_ptr`` / ``n``: a list that lies on this grid's device instead.  Returns the result's fields as a dict (T:
+        3 x 3, points -> grid)."""
+        prm, tab = self._align_params(x0, y0, step_xy, nx, ny, ntheta, theta0, dtheta, cos_sin, theta_wraps, K, iterations, pivot,
+                                      v_cut, eps, lever, min_overlap, max_rms)
+        r = AlignResult()
+        if device_ptr is None:
+            pts = _f64(points_xy).reshape(-1)
+            rc = self.lib.tsd_align_points(self.h, C.byref(prm), pts.ctypes.data, pts.size // 2, 0, C.byref(r))
+        else:
+            rc = self.lib.tsd_align_points(self.h, C.byref(prm), C.c_void_p(device_ptr), int(n), 1, C.byref(r))
+        self.last_rc = rc
+        self._check(rc, "tsd_align_points")
+        return self._align_dict(r)
+
+    def align_to(self, src, x0, y0, step_xy, nx, ny, ntheta, pivot=None, theta0=0.0, dtheta=0.0, cos_sin=None, theta_wraps=False,
+                 K=16, iterations=40, v_cut=0.75, eps=1e-6, lever=0.0, min_overlap=0.0, max_rms=0.0) -> dict:
+        """tsd_map_align(self, src): the transform T that carries ``src``'s map coordinates into this grid's (src's surface list,
+        replaced by the call, against this grid's TSD).  pivot None: the centre of src's grid.  ``cell_off`` / ``cell_error`` say
+        whether a whole-cell shift describes T: ``fuse_begin([.., src], offsets=[.., cell_off])``."""
+        prm, tab = self._align_params(x0, y0, step_xy, nx, ny, ntheta, theta0, dtheta, cos_sin, theta_wraps, K, iterations, pivot,
+                                      v_cut, eps, lever, min_overlap, max_rms)
+        r = AlignResult()
+        rc = self.lib.tsd_map_align(self.h, src.h if src is not None else None, C.byref(prm), C.byref(r))
+        self.last_rc = rc
+        self._check(rc, "tsd_map_align")
+        return self._align_dict(r)
+
+    def debug_align_scores(self) -> np.ndarray:
+        """TEST HOOK: the score volume of the last alignment, uint32 [nx * ny * ntheta] in candidate order"""
+        n = self.lib.tsd_debug_align_scores(self.h, None, 0)
+        self._check(min(n, 0), "tsd_debug_align_scores")
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        self._check(min(self.lib.tsd_debug_align_scores(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n), 0), "tsd_debug_align_scores")
+        return out[:n]
+
+    def debug_align_peaks(self) -> list:
+        """TEST HOOK: the per-peak records of the last alignment, in the peaks' order, as dicts (``raw``: the record's bytes)"""
+        recs = (AlignPeak * RELOC_MAX_PEAKS)()
+        n = self.lib.tsd_debug_align_peaks(self.h, recs, RELOC_MAX_PEAKS)
+        self._check(min(n, 0), "tsd_debug_align_peaks")
+        return [dict(idx=int(p.idx), score=int(p.score), status=int(p.status), iterations=int(p.iterations), n_ok=int(p.n_ok),
+                     m=(p.m[0], p.m[1]), c=p.c, s=p.s, gain=p.gain, sums=np.array(p.sums[:]), raw=bytes(p)) for p in recs[:n]]
+
+    def debug_align_sums(self, points_xy, pivot, m, c, s, v_cut=0.75):
+        """TEST HOOK: one accumulation of the refinement kernel at the state (m, c, s): (sums[11], n_ok)"""
+        pts = _f64(points_xy).reshape(-1)
+        pv, mm, sums, nok = _f64(pivot).reshape(2), _f64(m).reshape(2), np.zeros(11), C.c_int(0)
+        rc = self.lib.tsd_debug_align_sums(self.h, _d(pts), pts.size // 2, _d(pv), _d(mm), float(c), float(s), float(v_cut), _d(sums),
+                                           C.byref(nok))
+        self.last_rc = rc
+        self._check(rc, "tsd_debug_align_sums")
+        return sums, nok.value
 
     def set_icp_helpers(self, on: bool):
         """test hook: off = every registration does its first step's searches itself (same results, tsd_debug_set_icp_helpers)"""

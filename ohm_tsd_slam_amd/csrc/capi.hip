@@ -514,6 +514,7 @@ void tsd_destroy(tsd_ctx* ctx)
   if (ctx->h_pdf) hipHostFree(ctx->h_pdf);
   reloc_free(ctx);
   surface_free(ctx);
+  align_free(ctx);
   if (ctx->stream) hipStreamDestroy(ctx->stream);
   delete ctx;
 }

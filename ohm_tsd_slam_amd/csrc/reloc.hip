@@ -14,18 +14,11 @@
 // rotations, the points staged in LDS once, a wave per rotation, lanes over points, RELOC_BATCH look-ups per lane in flight with the tile
 // flag and the four cells of each issued together (ld_pinned / load_quad: not behind the flag test).  The rotations of one position sweep
 // the same discs of cells, so neighbouring waves hit the same lines.  The gate is one look-up per workgroup, issued ahead of the staging.
-// The device computes no sine: the rotation table comes from the host.
-#include "capi_internal.hpp"
+// The device computes no sine: the rotation table comes from the host.  The look-up loop of a candidate (reloc_lane_score), the
+// constants of the shape and the launcher of the peak kernels are shared with the map alignment (align.hip) through reloc_shared.hpp.
+#include "reloc_shared.hpp"
 
 namespace tsd {
-
-constexpr int RELOC_WAVES = 4;             // rotations a workgroup has in flight
-constexpr int RELOC_BATCH = 4;             // look-ups per lane in flight together
-constexpr int RELOC_MIN_BLOCKS = 2048;     // a lattice of few positions is cut along its rotations until the launch has about this many workgroups
-constexpr unsigned int RELOC_ONE = 1048576u;    // 2^20: the weight of a point that lies exactly on a surface
-constexpr size_t RELOC_KEEP_CANDIDATES = (size_t)1 << 23;   // a score volume up to this (32 MiB) stays with the context for the next search
-
-struct RelocLattice { double x0, y0, step; int nx, ny, ntheta; };
 
 __global__ void __launch_bounds__(64 * RELOC_WAVES)
 k_reloc_score(GridDev g, RelocLattice L, const double* __restrict__ pts, int P, const double* __restrict__ cos_sin,
@@ -55,31 +48,7 @@ k_reloc_score(GridDev g, RelocLattice L, const double* __restrict__ pts, int P, 
   __syncthreads();
   for (int k = k0 + wave; k < k1; k += RELOC_WAVES) {                 // (whole waves: no barrier below)
     const double c = cos_sin[2 * k], s = cos_sin[2 * k + 1];
-    unsigned int acc = 0u;
-    for (int i0 = 0; i0 < P; i0 += 64 * RELOC_BATCH) {
-      uint8_t fl[RELOC_BATCH]; Quad qv[RELOC_BATCH]; double wx[RELOC_BATCH], wy[RELOC_BATCH]; bool inside[RELOC_BATCH];
-#pragma unroll
-      for (int b = 0; b < RELOC_BATCH; b++) {
-        const int i = i0 + 64 * b + lane, ic = i < P ? i : 0;
-        const double px = s_pts[ic], py = s_pts[P + ic];
-        const double x = (c * px - s * py) + tx;
-        const double y = (s * px + c * py) + ty;
-        int p = 0, lx = 0, ly = 0; double dx = 0.0, dy = 0.0;
-        inside[b] = coord2cell(g, x, y, p, lx, ly, dx, dy) && i < P;
-        if (!inside[b]) { p = 0; lx = 0; ly = 0; }
-        fl[b] = ld_pinned(&g.flags[p]);
-        qv[b] = load_quad(g.tsd + (size_t)p * TILE_STRIDE, lx, ly);
-        wx[b] = fabs((x - dx) * g.inv_cs); wy[b] = fabs((y - dy) * g.inv_cs);
-      }
-#pragma unroll
-      for (int b = 0; b < RELOC_BATCH; b++) {
-        // TsdGrid::interpolateBilinear (TsdGrid.h:284-304), interpolate_bilinear's expression
-        const double v = qv[b].t00 * (1. - wy[b]) * (1. - wx[b]) + qv[b].t10 * wy[b] * (1. - wx[b])
-                       + qv[b].t01 * (1. - wy[b]) * wx[b] + qv[b].t11 * wy[b] * wx[b];
-        const bool ok = inside[b] && fl[b] != 0 && !isnan(v);
-        acc += ok ? RELOC_ONE - (unsigned int)rint(fabs(v) * 1048576.0) : 0u;
-      }
-    }
+    unsigned int acc = reloc_lane_score(g, s_pts, P, lane, c, s, tx, ty);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += (unsigned int)__shfl_down((int)acc, off, 64);
     if (lane == 0) scores[(size_t)k * plane + at] = acc;
@@ -89,7 +58,6 @@ k_reloc_score(GridDev g, RelocLattice L, const double* __restrict__ pts, int P, 
 // ---- peaks: a stream of 64-bit keys (score << 32 | ~idx: larger = better score, then lower index), the best PK_KEEP kept in LDS ----------
 constexpr int PK_THREADS = 256;
 constexpr int PK_CAP = 1024;               // keys the LDS buffer holds (a power of two: bitonic sort); a round adds at most PK_THREADS
-constexpr int PK_KEEP = TSD_RELOC_MAX_PEAKS;
 constexpr int RELOC_PEAK_GRID = 512;       // workgroups of k_reloc_peaks at most; they stride over the volume
 
 __device__ __forceinline__ unsigned long long peak_key(unsigned int score, unsigned int idx)
@@ -206,7 +174,7 @@ static void reloc_drop_volume(tsd_ctx::Reloc& r)
   hipFree(r.d_scores); r.d_scores = nullptr; r.score_cap = 0; r.nx = r.ny = r.ntheta = 0;
 }
 
-static int reloc_ensure(tsd_ctx* ctx, size_t rotations, size_t candidates)
+int reloc_ensure(tsd_ctx* ctx, size_t rotations, size_t candidates)
 {
   tsd_ctx::Reloc& r = ctx->reloc;
   if (!r.d_points) TSD_HIP_CHECK(ctx, hipMalloc(&r.d_points, sizeof(double) * 2 * TSD_MAX_ICP_POINTS));
@@ -226,7 +194,7 @@ static int reloc_ensure(tsd_ctx* ctx, size_t rotations, size_t candidates)
 }
 
 // the two peak kernels on the context's stream over a volume on the device; the merged keys and their count arrive in r.h_keys
-static int launch_reloc_peaks(tsd_ctx* ctx, const uint32_t* d_scores, int nx, int ny, int nt, int wraps, int K)
+int launch_reloc_peaks(tsd_ctx* ctx, const uint32_t* d_scores, int nx, int ny, int nt, int wraps, int K)
 {
   tsd_ctx::Reloc& r = ctx->reloc;
   const long long n = (long long)nx * ny * nt;
@@ -239,19 +207,21 @@ static int launch_reloc_peaks(tsd_ctx* ctx, const uint32_t* d_scores, int nx, in
   return TSD_OK;
 }
 
-static bool lattice_ok(int nx, int ny, int nt) { return nx >= 1 && ny >= 1 && nt >= 1; }
-static bool lattice_fits(int nx, int ny, int nt) { return (long long)nx * ny <= TSD_RELOC_MAX_CANDIDATES && (long long)nx * ny * nt <= TSD_RELOC_MAX_CANDIDATES; }
+const unsigned long long* reloc_merged_keys(const tsd_ctx* ctx) { return ctx->reloc.d_keys + (size_t)RELOC_PEAK_GRID * PK_KEEP; }
+
+bool reloc_lattice_ok(int nx, int ny, int nt) { return nx >= 1 && ny >= 1 && nt >= 1; }
+bool reloc_lattice_fits(int nx, int ny, int nt) { return (long long)nx * ny <= TSD_RELOC_MAX_CANDIDATES && (long long)nx * ny * nt <= TSD_RELOC_MAX_CANDIDATES; }
 
 // Every lattice position within TSD_RELOC_MAX_REACH grid widths of the grid, every scan point within as many of the sensor: a carried
 // point then lies within a dozen grid widths, (int)floor(x / cellSize) of coord2cell is defined and equals the restatement's int64.
-static double reloc_reach(const GridDev& g) { return (double)TSD_RELOC_MAX_REACH * ((double)g.N * g.cs); }
-static bool lattice_near(const GridDev& g, double a0, int n, double step)
+double reloc_reach(const GridDev& g) { return (double)TSD_RELOC_MAX_REACH * ((double)g.N * g.cs); }
+bool reloc_lattice_near(const GridDev& g, double a0, int n, double step)
 {
   const double a1 = a0 + (double)(n - 1) * step;
   return a0 >= -reloc_reach(g) && a1 <= (double)g.N * g.cs + reloc_reach(g);
 }
 
-static bool scan_in_flight(const tsd_ctx* ctx)
+bool reloc_scan_in_flight(const tsd_ctx* ctx)
 {
   for (const tsd_sensor* s : ctx->sensors) if (s->ledger.in_flight()) return true;
   for (const tsd_batch* b : ctx->batches) if (b->n > 0) return true;
@@ -275,12 +245,12 @@ int tsd_relocalize(tsd_ctx* ctx, const tsd_reloc_params* prm, const double* poin
     return set_error(ctx, TSD_E_CAPACITY, "tsd_relocalize: beams out of range for the registration", hipSuccess);
   if (prm->K < 1 || prm->K > TSD_RELOC_MAX_PEAKS) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: K outside 1 .. TSD_RELOC_MAX_PEAKS", hipSuccess);
   if (prm->min_pairs < 0) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: min_pairs < 0", hipSuccess);
-  if (!lattice_ok(prm->nx, prm->ny, prm->ntheta)) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: nx, ny, ntheta must be >= 1", hipSuccess);
+  if (!reloc_lattice_ok(prm->nx, prm->ny, prm->ntheta)) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: nx, ny, ntheta must be >= 1", hipSuccess);
   if (!std::isfinite(prm->x0) || !std::isfinite(prm->y0) || !std::isfinite(prm->step_xy) || !(prm->step_xy > 0.0))
     return set_error(ctx, TSD_E_ARG, "tsd_relocalize: x0, y0 finite and step_xy > 0", hipSuccess);
-  if (!lattice_fits(prm->nx, prm->ny, prm->ntheta))
+  if (!reloc_lattice_fits(prm->nx, prm->ny, prm->ntheta))
     return set_error(ctx, TSD_E_CAPACITY, "tsd_relocalize: nx * ny * ntheta > TSD_RELOC_MAX_CANDIDATES", hipSuccess);
-  if (!lattice_near(ctx->grid, prm->x0, prm->nx, prm->step_xy) || !lattice_near(ctx->grid, prm->y0, prm->ny, prm->step_xy))
+  if (!reloc_lattice_near(ctx->grid, prm->x0, prm->nx, prm->step_xy) || !reloc_lattice_near(ctx->grid, prm->y0, prm->ny, prm->step_xy))
     return set_error(ctx, TSD_E_ARG, "tsd_relocalize: the lattice reaches further than TSD_RELOC_MAX_REACH grid widths from the grid", hipSuccess);
   if (!prm->cos_sin && (!std::isfinite(prm->theta0) || !std::isfinite(prm->dtheta) || prm->dtheta == 0.0))
     return set_error(ctx, TSD_E_ARG, "tsd_relocalize: without a cos_sin table, theta0 and a non-zero dtheta are needed", hipSuccess);
@@ -294,7 +264,7 @@ int tsd_relocalize(tsd_ctx* ctx, const tsd_reloc_params* prm, const double* poin
     else { const double th = prm->theta0 + (double)k * prm->dtheta; table[2 * k] = std::cos(th); table[2 * k + 1] = std::sin(th); }
     if (!std::isfinite(table[2 * k]) || !std::isfinite(table[2 * k + 1])) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: cos_sin is not finite", hipSuccess);
   }
-  if (scan_in_flight(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: a scan of this context is in flight (collect it first)", hipSuccess);
+  if (reloc_scan_in_flight(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: a scan of this context is in flight (collect it first)", hipSuccess);
   // ---- the arguments stand: from here on the context changes ----
   if (int rc = enter(ctx)) return rc;
   ctx->ledger.outputs_overwritten();      // (the refinement rewrites the context's ray-cast outputs, like tsd_localize)
@@ -320,11 +290,8 @@ int tsd_relocalize(tsd_ctx* ctx, const tsd_reloc_params* prm, const double* poin
   if (e != hipSuccess) { drop_events(); return set_error(ctx, TSD_E_HIP, "tsd_relocalize: copy of the points", e); }
   if (timed) hipEventRecord(ev[0], ctx->stream);
   const long long positions = (long long)nx * ny;
-  long long cuts = (RELOC_MIN_BLOCKS + positions - 1) / positions;                 // along the rotations, whole rounds of RELOC_WAVES at least
-  cuts = std::max<long long>(1, std::min<long long>(cuts, (nt + RELOC_WAVES - 1) / RELOC_WAVES));
-  cuts = std::min<long long>(cuts, 65535);
-  const int rot_per_block = (int)((nt + cuts - 1) / cuts);
-  const int blocks_y = (nt + rot_per_block - 1) / rot_per_block;
+  int rot_per_block = 0, blocks_y = 0;
+  reloc_cut(nx, ny, nt, rot_per_block, blocks_y);
   const RelocLattice L{prm->x0, prm->y0, prm->step_xy, nx, ny, nt};
   hipLaunchKernelGGL(k_reloc_score, dim3((unsigned)positions, (unsigned)blocks_y), dim3(64 * RELOC_WAVES), sizeof(double) * 2 * (size_t)P, ctx->stream,
                      ctx->grid, L, (const double*)r.d_points, P, (const double*)r.d_cos_sin, r.d_scores, rot_per_block);
@@ -410,9 +377,9 @@ int tsd_debug_reloc_peaks(tsd_ctx* ctx, const uint32_t* scores, int nx, int ny, 
                           int32_t* idx_out, uint32_t* score_out, int* n_out)
 {
   if (!ctx || !scores || !idx_out || !score_out || !n_out) return TSD_E_ARG;
-  if (!lattice_ok(nx, ny, ntheta) || K < 1 || K > TSD_RELOC_MAX_PEAKS) return set_error(ctx, TSD_E_ARG, "tsd_debug_reloc_peaks: shape or K", hipSuccess);
-  if (!lattice_fits(nx, ny, ntheta)) return set_error(ctx, TSD_E_CAPACITY, "tsd_debug_reloc_peaks: volume > TSD_RELOC_MAX_CANDIDATES", hipSuccess);
-  if (scan_in_flight(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_debug_reloc_peaks: a scan of this context is in flight (collect it first)", hipSuccess);
+  if (!reloc_lattice_ok(nx, ny, ntheta) || K < 1 || K > TSD_RELOC_MAX_PEAKS) return set_error(ctx, TSD_E_ARG, "tsd_debug_reloc_peaks: shape or K", hipSuccess);
+  if (!reloc_lattice_fits(nx, ny, ntheta)) return set_error(ctx, TSD_E_CAPACITY, "tsd_debug_reloc_peaks: volume > TSD_RELOC_MAX_CANDIDATES", hipSuccess);
+  if (reloc_scan_in_flight(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_debug_reloc_peaks: a scan of this context is in flight (collect it first)", hipSuccess);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (int rc = reloc_ensure(ctx, 0, 0)) return rc;
   const size_t n = (size_t)nx * (size_t)ny * (size_t)ntheta;

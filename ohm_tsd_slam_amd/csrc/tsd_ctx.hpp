@@ -308,6 +308,19 @@ struct tsd_ctx {
     int n = 0; bool has_normals = false;     // the last extraction's
   } surface;
 
+  // map alignment (align.hip: tsd_align_points / tsd_map_align): the staged point list, the score volume of the last search (kept like
+  // the relocalisation's), the per-peak records and the staging kernel's count of bad coordinates with their pinned copies; the
+  // rotation table and the peak keys are tsd_ctx::reloc's
+  struct Align {
+    double* d_pts = nullptr; size_t pts_cap = 0;     // [2 * pts_cap]
+    uint32_t* d_scores = nullptr; size_t score_cap = 0;
+    int nx = 0, ny = 0, ntheta = 0;                  // shape of the volume in d_scores (0: none)
+    tsd_align_peak* d_rec = nullptr;                 // [TSD_RELOC_MAX_PEAKS]
+    tsd_align_peak* h_rec = nullptr;                 // pinned [TSD_RELOC_MAX_PEAKS]
+    unsigned int* d_bad = nullptr; unsigned int* h_bad = nullptr;   // coordinates refused by the staging kernel (h_bad pinned)
+    int n_rec = 0;                                   // records of the last alignment in h_rec
+  } align;
+
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;
   unsigned profile_every = 1;   // time every n-th launch of a selected kernel ("name/n" in tsd_profile_select)
@@ -545,6 +558,7 @@ int launch_wait_seq_multi(tsd_ctx* ctx, int n, const unsigned long long* const* 
 
 void reloc_free(tsd_ctx* ctx);               // reloc.hip: releases tsd_ctx::reloc (tsd_destroy)
 void surface_free(tsd_ctx* ctx);             // surface.hip: releases tsd_ctx::surface (tsd_destroy)
+void align_free(tsd_ctx* ctx);               // align.hip: releases tsd_ctx::align (tsd_destroy)
 int launch_calibrate(tsd_ctx* ctx, double* t, double* w, size_t n);
 int launch_occupancy(tsd_ctx* ctx, int8_t* d_out, int inflate, int inflate_factor);
 size_t occ_heads_bytes();

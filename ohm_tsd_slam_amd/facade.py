@@ -442,6 +442,26 @@ class SlamFleet:
             raise capi.TsdError(f"tsd_fleet_fuse_tsd failed ({rc.value})")
         return GridView(ctx, _FusedLock(self))
 
+    def align(self, i, j, **lattice) -> dict:
+        """The pose of node j's map in node i's (``TsdGridDevice.align_to``: tsd_map_align(grid i, grid j)): ``T`` carries node j's
+        map coordinates into node i's, ``cell_off`` is the whole-cell shift ``fuse`` and the merge group would take for the pair.
+        Holds both nodes' grid locks, taken in ascending node index, for the whole call.  ``lattice``: align_to's arguments."""
+        if i == j:
+            raise capi.TsdError("SlamFleet.align: a node's map against itself")
+        held = []
+        try:
+            for k in sorted((i, j)):
+                node = self.nodes[k]
+                node.lib.tsd_node_grid_lock(node.h)
+                held.append(node)
+            # (through the class, on views without a lock of their own: both locks are held here)
+            dst = GridView(self.nodes[i].lib.tsd_node_grid_ctx(self.nodes[i].h), None)
+            src = GridView(self.nodes[j].lib.tsd_node_grid_ctx(self.nodes[j].h), None)
+            return capi.TsdGridDevice.align_to(dst, src, **lattice)
+        finally:
+            for node in reversed(held):
+                node.lib.tsd_node_grid_unlock(node.h)
+
     def fused_image_msg(self) -> dict:
         """the colour image of the fused grid (after ``fuse_tsd``) as a sensor_msgs/Image: ``map_image_msg``'s fields"""
         info = np.zeros(5)
@@ -482,7 +502,7 @@ class GridView(capi.TsdGridDevice):
                "download_tiles", "upload_tiles", "digest", "occupancy", "occupancy_into", "calibrate_rmw", "profile", "store_text",
                "load_text", "color_image", "push_stats_total", "profile_reset", "profile_get", "profile_spread", "profile_samples", "tsdpdf_match",
                "relocalize", "debug_reloc_scores", "debug_reloc_peaks", "surface_extract", "surface_fetch", "surface_points",
-               "surface_dev")
+               "surface_dev", "align_points", "debug_align_scores", "debug_align_peaks", "debug_align_sums")
 
     def __init__(self, ctx, node=None):  # noqa: D401 - does not call the base constructor on purpose
         self.lib = capi.load_library()
