@@ -705,6 +705,39 @@ void* tsd_group_member_map_dev(tsd_group* g, int i);
 int   tsd_group_profile(tsd_group* g, int on);
 int   tsd_group_merge_times(tsd_group* g, double* extract_ms_total, double* merge_ms_total, int* merges);
 
+/* ---- the same group under rigid transforms: members rotated and shifted by fractions of a cell ------------------ */
+/* Member i is placed by a rigid transform T_i (3x3 row-major) that carries its grid coordinates (metres from the grid's corner, the
+ * coordinates tsd_map_align speaks) into the group's frame: c = T[0][0], s = T[1][0], t = (T[0][2], T[1][2]).  The merged window is
+ * W x H cells of the members' common cell size cs with its corner at (x0, y0) in frame cells.  For window cell (X, Y) and member i,
+ * all in fp64, in this order, every operation rounded on its own (no contraction):
+ *   px = ((double)(x0 + X) + 0.5) * cs;   py = ((double)(y0 + Y) + 0.5) * cs        the cell's centre in the frame
+ *   dx = px - t.x;   dy = py - t.y
+ *   qx = c*dx + s*dy;   qy = c*dy - s*dx                                            T_i^-1 of the centre
+ *   u = qx / cs;   v = qy / cs
+ *   kx in [ceil(u - 1.25), floor(u + 0.25)],   ky in [ceil(v - 1.25), floor(v + 0.25)]
+ * The footprint: the source cells whose centre (k + 0.5) lies within 0.75 cells (Chebyshev) of the back-projected centre, 1 or 2 cells
+ * per axis.  Member i's value at (X, Y) is the SIGNED int8 maximum over the footprint cells that lie inside the member (0 <= kx, ky <
+ * cells_i); if none does, the member does not cover the cell.  The merged cell is the signed maximum over the covering members, -1
+ * without one: the group's rule above.  No occupied cell is dropped: the centre of an occupied source cell lands in some window cell D,
+ * and D's centre back-projects to within 0.5 * sqrt(2) < 0.75 cells of that source centre on both axes, so the source cell is in D's
+ * footprint (a nearest-neighbour warp loses cells of walls one cell thick; here a wall may thicken to two cells, the "occupied wins"
+ * bias the maximum has anyway).  At c = 1, s = 0 and a whole-cell translation the fractions of u and v are .5, a quarter cell from
+ * both thresholds: the footprint is the one source cell and the result is tsd_group_create's, byte for byte.
+ *
+ * width = height = 0: the window is the bounding box of the members.  Over the corners (x, y) in {0, L_i}^2, L_i = (double)cells_i * cs,
+ * of every member, carried to ((c*x - s*y) + t.x, (s*x + c*y) + t.y):  x0 = floor(min_x / cs + 1e-9), x1 = ceil(max_x / cs - 1e-9),
+ * W = x1 - x0, and y likewise (the 1e-9 keeps 17 * cs / cs from falling to 16; with whole-cell identity transforms the box is
+ * tsd_group_create's).  An explicit window has its corner at frame cell (0, 0).  tsd_group_corner gives (x0, y0).
+ *
+ * T33: 9n doubles, NULL = identities.  tsd_group_create's conditions hold (one device, bit-equal cell sizes, distinct contexts, 1 .. 64
+ * members, sides 0 or 1 .. 65536); refused as well, before the first HIP call, with NULL and a message on stderr: an entry that is not
+ * finite, a last row other than (0, 0, 1), |T00 - T11| or |T01 + T10| above 1e-12 (shear, reflection), |c*c + s*s - 1| above 1e-9 (scale),
+ * a translation beyond 2^24 cells, a bounding box over 65536 cells.  Every other tsd_group_* call works on such a group as on a
+ * translation group, with the same ordering; tsd_group_merge_maps_begin launches k_group_merge_rigid. */
+tsd_group* tsd_group_create_rigid(int n, tsd_ctx* const* ctxs, const double* T33 /* 9n, NULL = identities */, int width, int height);
+/* member i's transform into the group's frame; on a translation group the shift (ox_i * cs, oy_i * cs) as a transform */
+int   tsd_group_member_transform(const tsd_group* g, int i, double T33[9]);
+
 /* ---- TSD-level fusion: the grids of several robots on ONE GPU fused into one grid ------------------------------- */
 /* dst becomes the grid that would have seen every member's scans: member i's cell (x, y) is dst's cell (x + ox_i, y + oy_i), offsets
  * in whole cells, any integer in +-2^24 (no multiple of 32 is asked for); members are clipped to dst, what no member reaches becomes

@@ -1,7 +1,8 @@
 // group.hip -- the same-device merge group of include/tsd_hip.h (tsd_group_*): N grid contexts of ONE process on ONE GPU, each shifted by
 // whole cells, merged into one int8 occupancy map by a local kernel -- the signed maximum ncclAllReduce(int8, max) gives across GPUs
 // (comm.hip), without RCCL.  Part of libtsd_hip.so; uses the contexts only through the public C ABI (tsd_stream,
-// tsd_occupancy_dev_async), like comm.hip does.
+// tsd_occupancy_dev_async), like comm.hip does.  A group made by tsd_group_create_rigid is the same group with its members placed by
+// rigid transforms: same buffers, events and ordering, k_group_merge_rigid in k_group_merge's place.
 //
 // Ordering (events only; nothing waits on the host before tsd_group_merge_wait, nothing spins on the device):
 //   member i's stream :  [wait ev_merged]  extraction into d_member[i]  record ev_extracted[i]
@@ -10,6 +11,7 @@
 // would take one of the few hardware queues the scans' streams are mapped onto, see comm.hip).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -174,11 +176,165 @@ __global__ void __launch_bounds__(256) k_group_merge(const GroupArgs a)
     atomicAdd(a.count + (((blockIdx.x << 2) | (threadIdx.x >> 6)) & (GROUP_COUNT_SHARDS - 1)) * GROUP_COUNT_STRIDE, n100);
 }
 
+// ---- members under rigid transforms (tsd_group_create_rigid; the rule is stated in include/tsd_hip.h) ------------------------------
+struct RigidMember {
+  const int8_t* map;      // side * side bytes, row = y, 16-byte aligned, side a multiple of 16
+  int side;
+  int whole;              // T is a whole-cell shift: the member's cell (x, y) is the window's cell (x + ox, y + oy), as in GroupMember
+  int ox, oy;
+  double c, s, tx, ty;    // T = [c -s tx; s c ty]: the member's grid coordinates (metres) into the frame
+};
+struct RigidArgs {        // by value, as GroupArgs
+  int8_t* out;
+  int* count;
+  int W, H, n, x0, y0, reserved;   // (x0, y0): the window's corner in frame cells
+  double cs;
+  RigidMember m[TSD_GROUP_MAX];
+};
+static_assert(sizeof(RigidArgs) <= 4096, "the kernel-argument segment holds 4 KiB");
+
+// A workgroup owns 64 x 64 window cells.  Their back-projected centres span at most 63 (|c| + |s|) <= 89.1 member cells per axis, the
+// footprints 1.5 more: at most 91 rows of at most 7 aligned 16-byte pieces.  One spare piece per row keeps rows 4 banks apart.
+constexpr int RIGID_BLOCK = 64, RIGID_ROWS = 96, RIGID_PIECES = 8, RIGID_STRIDE = RIGID_PIECES * 16 + 16;
+
+// u, v of the header for window cell (X, Y).  Every operation is monotone in its operands after rounding as before it, so u and v are
+// monotone in X and in Y: over a block of cells their extremes are taken at the block's corners, exactly.
+__device__ __forceinline__ double rigid_centre(int k0, int K, double cs) { return ((double)(k0 + K) + 0.5) * cs; }
+
+// k_group_merge's step for one member and one 16-byte piece of window row y that starts at column x0 (a multiple of 16): the member's
+// bytes go into the accumulator, the bytes it covers into cov
+__device__ __forceinline__ void take_shifted(Acc4& acc, u32x4& cov, const int8_t* map, int w, int h, int ox, int oy, int y, int x0)
+{
+  const int my = y - oy, mx0 = x0 - ox;
+  if ((unsigned)my >= (unsigned)h || mx0 <= -16 || mx0 >= w) return;
+  const int8_t* row = map + (size_t)my * (size_t)w;
+  const int s = (-ox) & 15;                     // = mx0 & 15, from scalars only: uniform
+  const int b0 = mx0 - s;
+  if (s == 0) {
+    acc.take(*reinterpret_cast<const u32x4*>(row + b0));
+    cov = (u32x4)(~0u);
+    return;
+  }
+  const bool in0 = b0 >= 0, in1 = b0 + 16 < w;
+  u32x4 lo = (u32x4)(0u), hi = (u32x4)(0u);
+  if (in0) lo = *reinterpret_cast<const u32x4*>(row + b0);
+  if (in1) hi = *reinterpret_cast<const u32x4*>(row + b0 + 16);
+  u32x4 v = funnel16(lo, hi, s);
+  if (in0 && in1) { acc.take(v); cov = (u32x4)(~0u); return; }
+  const u32x4 c = funnel16(in0 ? (u32x4)(~0u) : (u32x4)(0u), in1 ? (u32x4)(~0u) : (u32x4)(0u), s);
+  acc.take((v & c) | ((u32x4)(0x80808080u) & ~c));
+  cov |= c;
+}
+
+// One lane per 16 cells of a window row, four lanes per row, 64 rows per workgroup.  Per member: the box of member cells the block's
+// footprints can touch, from the block's four corners (wave-uniform); a member it misses costs that and nothing else.  Otherwise the
+// box is staged in LDS with aligned 16-byte loads (k_group_merge's loads) and every lane takes its cells' footprint maxima from there:
+// a wave walking a window row walks a slanted line through the member, up to 64 |s| rows of it, a few bytes from each.
+// A member whose transform is a whole-cell shift (the frame's owner, as a rule) takes k_group_merge's path instead: with c = 1, s = 0
+// and a translation within 1e-6 cells of whole cells, u and v lie within 2e-6 of (cell + 0.5), a quarter cell from both thresholds,
+// so the footprint is that one cell -- no fp64, no LDS (measured: profiles/group_merge_rigid.txt).
+template <bool ROWS16>
+__global__ void __launch_bounds__(256) k_group_merge_rigid(const RigidArgs a)
+{
+  __shared__ __attribute__((aligned(16))) int8_t tile[RIGID_ROWS * RIGID_STRIDE];
+  const int bX = (int)blockIdx.x * RIGID_BLOCK, bY = (int)blockIdx.y * RIGID_BLOCK;
+  const int Y = bY + (int)(threadIdx.x >> 2), X0 = bX + (int)(threadIdx.x & 3u) * 16;
+  const bool live = Y < a.H && X0 < a.W;
+  const double cs = a.cs;
+  const double py = rigid_centre(a.y0, Y, cs);
+  Acc4 acc;
+  acc.init();
+  u32x4 cov = (u32x4)(0u);
+  for (int i = 0; i < a.n; i++) {
+    const int side = a.m[i].side;
+    if (a.m[i].whole) {
+      if (live) take_shifted(acc, cov, a.m[i].map, side, side, a.m[i].ox, a.m[i].oy, Y, X0);
+      continue;
+    }
+    const double c = a.m[i].c, s = a.m[i].s, tx = a.m[i].tx, ty = a.m[i].ty;
+    int lox = INT32_MAX, loy = INT32_MAX, hix = INT32_MIN, hiy = INT32_MIN;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const double dx = rigid_centre(a.x0, bX + ((k & 1) ? RIGID_BLOCK - 1 : 0), cs) - tx;
+      const double dy = rigid_centre(a.y0, bY + ((k & 2) ? RIGID_BLOCK - 1 : 0), cs) - ty;
+      const double u = (c * dx + s * dy) / cs, v = (c * dy - s * dx) / cs;
+      lox = min(lox, (int)ceil(u - 1.25)); hix = max(hix, (int)floor(u + 0.25));
+      loy = min(loy, (int)ceil(v - 1.25)); hiy = max(hiy, (int)floor(v + 0.25));
+    }
+    lox = __builtin_amdgcn_readfirstlane(max(lox, 0)); hix = __builtin_amdgcn_readfirstlane(min(hix, side - 1));
+    loy = __builtin_amdgcn_readfirstlane(max(loy, 0)); hiy = __builtin_amdgcn_readfirstlane(min(hiy, side - 1));
+    if (lox > hix || loy > hiy) continue;        // the block misses the member (uniform: every lane computed the same box)
+    const int ax = lox & ~15;
+    const int pieces = min(((hix - ax) >> 4) + 1, RIGID_PIECES), rows = min(hiy - loy + 1, RIGID_ROWS);
+    __syncthreads();                             // the previous member's reads of the tile
+    const int8_t* src = a.m[i].map + (size_t)loy * (size_t)side + (size_t)ax;
+    for (int k = (int)threadIdx.x; k < rows * pieces; k += 256) {
+      const int r = k / pieces, p = k - r * pieces;
+      *reinterpret_cast<u32x4*>(tile + r * RIGID_STRIDE + p * 16) = *reinterpret_cast<const u32x4*>(src + (size_t)r * (size_t)side + p * 16);
+    }
+    __syncthreads();
+    if (!live) continue;
+    const double dy = py - ty, sdy = s * dy, cdy = c * dy;
+    const int xmax = ax + pieces * 16 - 1, ymax = loy + rows - 1;
+    u32x4 val = (u32x4)(0u), msk = (u32x4)(0u);  // the member's 16 values (-128, the maximum's identity, where it does not cover) and the bytes it covers
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const double dx = rigid_centre(a.x0, X0 + j, cs) - tx;
+      const double u = (c * dx + sdy) / cs, v = (cdy - s * dx) / cs;
+      int kx0 = max((int)ceil(u - 1.25), 0), kx1 = min((int)floor(u + 0.25), side - 1);
+      int ky0 = max((int)ceil(v - 1.25), 0), ky1 = min((int)floor(v + 0.25), side - 1);
+      int m = -128;
+      if (kx0 <= kx1 && ky0 <= ky1) {            // (otherwise the footprint lies outside the member)
+        // inside the staged box by the corners' argument; clamped all the same, so that no index can leave the tile
+        kx0 = min(max(kx0, ax), xmax) - ax; kx1 = min(max(kx1, ax), xmax) - ax;
+        const int8_t* r0 = tile + (min(max(ky0, loy), ymax) - loy) * RIGID_STRIDE;
+        const int8_t* r1 = tile + (min(max(ky1, loy), ymax) - loy) * RIGID_STRIDE;
+        m = max(max((int)r0[kx0], (int)r0[kx1]), max((int)r1[kx0], (int)r1[kx1]));
+        msk[j >> 2] |= 0xFFu << (8 * (j & 3));
+      }
+      val[j >> 2] |= (uint32_t)(uint8_t)m << (8 * (j & 3));
+    }
+    acc.take(val);
+    cov |= msk;
+  }
+  int n100 = 0;
+  if (live) {
+    u32x4 r;
+#pragma unroll
+    for (int k = 0; k < 4; k++) r[k] = acc.dword(k) | ~cov[k];          // uncovered: 0x80 | 0xFF = -1
+    int8_t* o = a.out + (size_t)Y * (size_t)a.W + (size_t)X0;
+    if (ROWS16) {
+      *reinterpret_cast<u32x4*>(o) = r;
+#pragma unroll
+      for (int k = 0; k < 4; k++) n100 += count100(r[k]);
+    } else if (X0 + 16 <= a.W) {
+      *reinterpret_cast<u32x4_u*>(o) = r;
+#pragma unroll
+      for (int k = 0; k < 4; k++) n100 += count100(r[k]);
+    } else {                                     // the row's last, partial piece
+      for (int j = 0; X0 + j < a.W; j++) {
+        const int8_t b = (int8_t)(r[j >> 2] >> (8 * (j & 3)));
+        o[j] = b;
+        n100 += b == 100;
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) n100 += __shfl_down(n100, off, 64);
+  if ((threadIdx.x & 63) == 0 && n100) {
+    const unsigned wave = ((blockIdx.y * gridDim.x + blockIdx.x) << 2) | (threadIdx.x >> 6);
+    atomicAdd(a.count + (wave & (GROUP_COUNT_SHARDS - 1)) * GROUP_COUNT_STRIDE, n100);
+  }
+}
+
 }  // namespace
 
 struct tsd_group {
   int n = 0, W = 0, H = 0, device = 0;
   int x0 = 0, y0 = 0;                          // the window's corner in the offsets' frame (bounding box: the smallest offsets)
+  bool rigid = false;                          // tsd_group_create_rigid: the members are placed by T
+  std::vector<double> T;                       // 9 per member
+  std::vector<int> whole;                      // T[i] is a whole-cell shift: ox / oy hold it, relative to the window's corner
   std::vector<tsd_ctx*> ctx;
   std::vector<int> ox, oy, side;               // offsets relative to the window's corner; cells per side of each member
   std::vector<int8_t*> d_member;
@@ -295,6 +451,68 @@ tsd_group* tsd_group_create(int n, tsd_ctx* const* ctxs, const int32_t* cell_off
   return g;
 }
 
+tsd_group* tsd_group_create_rigid(int n, tsd_ctx* const* ctxs, const double* T33, int width, int height)
+{
+  auto refuse = [](const char* what) -> tsd_group* { std::fprintf(stderr, "tsd_group_create_rigid: %s\n", what); return nullptr; };
+  // ---- the transforms and the window; the members themselves are checked by tsd_group_create below.  Nothing here touches HIP.
+  if (n < 1 || n > TSD_GROUP_MAX) return refuse("the number of members must be 1 .. 64");
+  if (!ctxs) return refuse("no contexts");
+  for (int i = 0; i < n; i++) if (!ctxs[i]) return refuse("a member context is NULL");
+  const double cs = tsd_cell_size(ctxs[0]);
+  std::vector<double> T((size_t)9 * (size_t)n);
+  double lo_x = INFINITY, lo_y = INFINITY, hi_x = -INFINITY, hi_y = -INFINITY;
+  for (int i = 0; i < n; i++) {
+    double* t = &T[(size_t)9 * (size_t)i];
+    for (int k = 0; k < 9; k++) t[k] = T33 ? T33[9 * i + k] : (k % 4 == 0 ? 1.0 : 0.0);
+    for (int k = 0; k < 9; k++) if (!std::isfinite(t[k])) return refuse("a transform has an entry that is not finite");
+    if (t[6] != 0.0 || t[7] != 0.0 || t[8] != 1.0) return refuse("a transform's last row is not (0, 0, 1)");
+    if (std::fabs(t[0] - t[4]) > 1e-12 || std::fabs(t[1] + t[3]) > 1e-12) return refuse("a transform is no rotation (shear or reflection)");
+    const double c = t[0], s = t[3];
+    if (std::fabs(c * c + s * s - 1.0) > 1e-9) return refuse("a transform is no rotation (scale)");
+    if (!(std::fabs(t[2] / cs) <= 16777216.0) || !(std::fabs(t[5] / cs) <= 16777216.0)) return refuse("a translation exceeds 2^24 cells");
+    const double L = (double)tsd_cells(ctxs[i]) * cs;
+    for (int k = 0; k < 4; k++) {
+      const double x = (k & 1) ? L : 0.0, y = (k & 2) ? L : 0.0;
+      const double X = (c * x - s * y) + t[2], Y = (s * x + c * y) + t[5];
+      lo_x = X < lo_x ? X : lo_x; hi_x = X > hi_x ? X : hi_x;
+      lo_y = Y < lo_y ? Y : lo_y; hi_y = Y > hi_y ? Y : hi_y;
+    }
+  }
+  int x0 = 0, y0 = 0;
+  if (width == 0 && height == 0) {
+    const double fx0 = std::floor(lo_x / cs + 1e-9), fx1 = std::ceil(hi_x / cs - 1e-9);
+    const double fy0 = std::floor(lo_y / cs + 1e-9), fy1 = std::ceil(hi_y / cs - 1e-9);
+    if (!(fx1 - fx0 >= 1.0 && fx1 - fx0 <= (double)TSD_GROUP_MAX_SIDE && fy1 - fy0 >= 1.0 && fy1 - fy0 <= (double)TSD_GROUP_MAX_SIDE))
+      return refuse("the bounding box exceeds 65536 cells");
+    x0 = (int)fx0; y0 = (int)fy0; width = (int)(fx1 - fx0); height = (int)(fy1 - fy0);
+  }
+  // ---- the members' checks and every device object: a translation group with this window and no shifts
+  tsd_group* g = tsd_group_create(n, ctxs, nullptr, width, height);
+  if (!g) return nullptr;
+  g->rigid = true; g->x0 = x0; g->y0 = y0;
+  g->T.swap(T);
+  // a member shifted by whole cells (within 1e-6 of a cell, the facade's rule) is merged as tsd_group_create's members are
+  g->whole.assign(n, 0);
+  for (int i = 0; i < n; i++) {
+    const double* t = &g->T[(size_t)9 * (size_t)i];
+    const double dx = t[2] / cs, dy = t[5] / cs, rx = std::rint(dx), ry = std::rint(dy);
+    if (t[0] == 1.0 && t[4] == 1.0 && t[1] == 0.0 && t[3] == 0.0 && std::fabs(dx - rx) <= 1e-6 && std::fabs(dy - ry) <= 1e-6) {
+      g->whole[i] = 1; g->ox[i] = (int)rx - x0; g->oy[i] = (int)ry - y0;
+    }
+  }
+  return g;
+}
+
+int tsd_group_member_transform(const tsd_group* g, int i, double T33[9])
+{
+  if (!g || i < 0 || i >= g->n || !T33) return TSD_E_ARG;
+  if (g->rigid) { std::memcpy(T33, &g->T[(size_t)9 * (size_t)i], 9 * sizeof(double)); return TSD_OK; }
+  const double cs = tsd_cell_size(g->ctx[i]);
+  const double T[9] = {1.0, 0.0, (double)(g->ox[i] + g->x0) * cs, 0.0, 1.0, (double)(g->oy[i] + g->y0) * cs, 0.0, 0.0, 1.0};
+  std::memcpy(T33, T, sizeof(T));
+  return TSD_OK;
+}
+
 void tsd_group_destroy(tsd_group* g)
 {
   if (!g) return;
@@ -356,11 +574,17 @@ int tsd_group_merge_maps_begin(tsd_group* g, const void* const* member_maps_dev,
 {
   if (!g) return TSD_E_ARG;
   GroupArgs a;
+  RigidArgs ra;                                // (filled for a rigid group only)
   std::memset(&a, 0, sizeof(a));
+  if (g->rigid) std::memset(&ra, 0, sizeof(ra));
   for (int i = 0; i < g->n; i++) {
     const void* p = member_maps_dev ? member_maps_dev[i] : g->d_member[i];
     if (!p || (reinterpret_cast<uintptr_t>(p) & 15u)) { g->err = "a member map is NULL or not 16-byte aligned"; return TSD_E_ARG; }
     a.m[i] = GroupMember{static_cast<const int8_t*>(p), g->ox[i], g->oy[i], g->side[i], g->side[i]};
+    if (g->rigid) {
+      const double* t = &g->T[(size_t)9 * (size_t)i];
+      ra.m[i] = RigidMember{static_cast<const int8_t*>(p), g->side[i], g->whole[i], g->ox[i], g->oy[i], t[0], t[3], t[2], t[5]};
+    }
   }
   if (hipSetDevice(g->device) != hipSuccess) return group_fail(g, "hipSetDevice", hipGetLastError());
   for (int i = 0; i < g->n; i++)
@@ -375,7 +599,14 @@ int tsd_group_merge_maps_begin(tsd_group* g, const void* const* member_maps_dev,
   if (g->profile) { t0 = group_event(g); t1 = group_event(g); if (t0) hipEventRecord(t0, g->gstream); }
   const unsigned long long pieces = (unsigned long long)a.chunks * (unsigned long long)g->H;      // <= 2^28
   const unsigned blocks = (unsigned)((pieces + 255) / 256);
-  if (g->W % 16 == 0) hipLaunchKernelGGL(k_group_merge<true>, dim3(blocks), dim3(256), 0, g->gstream, a);
+  if (g->rigid) {
+    ra.out = g->d_merged; ra.count = g->d_count; ra.W = g->W; ra.H = g->H; ra.n = g->n; ra.x0 = g->x0; ra.y0 = g->y0;
+    ra.cs = tsd_cell_size(g->ctx[0]);
+    const dim3 grid((unsigned)((g->W + RIGID_BLOCK - 1) / RIGID_BLOCK), (unsigned)((g->H + RIGID_BLOCK - 1) / RIGID_BLOCK));   // <= 1024 x 1024
+    if (g->W % 16 == 0) hipLaunchKernelGGL(k_group_merge_rigid<true>, grid, dim3(256), 0, g->gstream, ra);
+    else hipLaunchKernelGGL(k_group_merge_rigid<false>, grid, dim3(256), 0, g->gstream, ra);
+  }
+  else if (g->W % 16 == 0) hipLaunchKernelGGL(k_group_merge<true>, dim3(blocks), dim3(256), 0, g->gstream, a);
   else hipLaunchKernelGGL(k_group_merge<false>, dim3(blocks), dim3(256), 0, g->gstream, a);
   e = hipGetLastError();
   if (e != hipSuccess) { if (t0) g->pool.push_back(t0); if (t1) g->pool.push_back(t1); return group_fail(g, "k_group_merge", e); }

@@ -30,6 +30,7 @@ ThreadGridGroup::ThreadGridGroup(const std::shared_ptr<rclcpp::Node>& node, cons
     _node(node),
     _members(members),
     _group(nullptr),
+    _fusable(true),
     _occGrid(std::make_shared<nav_msgs::msg::OccupancyGrid>()),
     _width(0),
     _height(0),
@@ -156,6 +157,14 @@ int ThreadGridGroup::fuse(obvious::TsdGrid* dst)
 {
   if(!dst || !dst->valid())
     return TSD_E_ARG;
+  std::vector<int32_t> cellOff;
+  {
+    // (setTransforms may replace the placement between two calls)
+    std::lock_guard<std::mutex> lk(_publishMutex);
+    if(!_fusable)
+      return TSD_E_ARG;           // a member is rotated or lies a fraction of a cell off: the TSD-level fusion shifts by whole cells
+    cellOff = _cellOff;
+  }
   std::vector<tsd_ctx*> ctxs(_members.size());
   for(size_t i = 0; i < _members.size(); i++)
   {
@@ -171,12 +180,55 @@ int ThreadGridGroup::fuse(obvious::TsdGrid* dst)
     for(size_t i = 0; i < _members.size(); i++)
       held.emplace_back(_members[i].grid->mutex());
     held.emplace_back(dst->mutex());
-    rc = tsd_fuse_begin(dst->context(), static_cast<int>(ctxs.size()), ctxs.data(), _cellOff.data());
+    rc = tsd_fuse_begin(dst->context(), static_cast<int>(ctxs.size()), ctxs.data(), cellOff.data());
   }
   if(rc != TSD_OK)
     return rc;
   std::lock_guard<std::mutex> g(dst->mutex());
   return tsd_fuse_wait(dst->context(), nullptr);
+}
+
+void ThreadGridGroup::setTransforms(const std::vector<std::array<double, 9>>& T)
+{
+  if(T.size() != _members.size())
+    throw std::invalid_argument("ThreadGridGroup::setTransforms: one transform per grid");
+  static const std::array<double, 9> identity = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+  if(T[0] != identity)
+    throw std::invalid_argument("ThreadGridGroup::setTransforms: T[0] must be the identity (the frame is grid 0's)");
+  const double cs = static_cast<double>(_grid.getCellSize());
+  std::vector<tsd_ctx*> ctxs(_members.size());
+  std::vector<double> flat;
+  std::vector<int32_t> off(2 * _members.size(), 0);
+  bool fusable = true;
+  for(size_t i = 0; i < _members.size(); i++)
+  {
+    ctxs[i] = _members[i].grid->context();
+    flat.insert(flat.end(), T[i].begin(), T[i].end());
+    const bool turned = !(T[i][0] == 1.0 && T[i][4] == 1.0 && T[i][1] == 0.0 && T[i][3] == 0.0);
+    if(turned || !cellOffset(T[i][2], 0.0, cs, &off[2 * i]) || !cellOffset(T[i][5], 0.0, cs, &off[2 * i + 1]))
+      fusable = false;
+  }
+  std::lock_guard<std::mutex> lk(_publishMutex);
+  tsd_group* group = tsd_group_create_rigid(static_cast<int>(ctxs.size()), ctxs.data(), flat.data(), 0, 0);
+  if(!group)
+    throw std::invalid_argument("ThreadGridGroup::setTransforms: the device refused the transforms (rigid, finite, within 65536 cells)");
+  tsd_group_destroy(_group);
+  _group = group;
+  _cellOff = off;
+  _fusable = fusable;
+  if(_hOcc)
+    tsd_host_free(_hOcc);
+  _hOcc = nullptr;               // (publish() allocates the landing buffer for the new window)
+  _width = static_cast<unsigned int>(tsd_group_width(_group));
+  _height = static_cast<unsigned int>(tsd_group_height(_group));
+  int32_t x0 = 0, y0 = 0;
+  tsd_group_corner(_group, &x0, &y0);
+  std::lock_guard<std::mutex> m(_msgMutex);
+  _occGrid->info.width             = _width;
+  _occGrid->info.height            = _height;
+  _occGrid->info.origin.position.x = mapOrigin(_members[0].grid, _members[0].grid->getCellsX(), _members[0].xOffset) + static_cast<double>(x0) * cs;
+  _occGrid->info.origin.position.y = mapOrigin(_members[0].grid, _members[0].grid->getCellsY(), _members[0].yOffset) + static_cast<double>(y0) * cs;
+  _occGrid->data.assign((size_t)_width * _height, -1);
 }
 
 bool ThreadGridGroup::getMapServCallBack(const std::shared_ptr<nav_msgs::srv::GetMap::Request>,

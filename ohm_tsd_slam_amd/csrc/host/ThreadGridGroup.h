@@ -1,8 +1,10 @@
 // ThreadGridGroup.h -- the merged-map worker of several grids on ONE GPU (not in the reference, whose robots share one TsdGrid): every
 // wake-up extracts each grid's occupancy map on that grid's own stream, merges them on the device (tsd_group_*: the signed maximum,
 // each grid shifted by the whole-cell difference of the map origins) and publishes one nav_msgs/OccupancyGrid on <node>/merged_map;
-// <node>/get_merged_map answers with the last one.  Across GPUs the merge is include/tsd_comm.h's; this one never maps RCCL.
+// <node>/get_merged_map answers with the last one.  setTransforms() places the grids by rigid transforms instead (tsd_group_create_rigid):
+// grids turned against each other or a fraction of a cell apart.  Across GPUs the merge is include/tsd_comm.h's; this one never maps RCCL.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <memory>
 #include <mutex>
@@ -45,6 +47,15 @@ public:
    *  member order, then dst's; nothing else holds two grids -- and none of the members' while it runs.  TSD_OK or the error code. */
   int fuse(obvious::TsdGrid* dst);
 
+  /** Places the members by rigid transforms instead of the whole-cell distances of their map origins: T[i] (3x3 row-major) carries
+   *  member i's grid coordinates into member 0's, what tsd_map_align(grid 0, grid i) returns; T[0] must be the identity.  The group
+   *  is replaced by a rigid one (tsd_group_create_rigid, bounding box) between two publications; the merged map's origin becomes
+   *  member 0's map origin plus the window's corner, its orientation stays the identity.  fuse() returns TSD_E_ARG from then on
+   *  unless every T[i] is a whole-cell shift (no rotation, cellOffset's 1e-6-cell rule), and fuses with those shifts if they all are.
+   *  Throws std::invalid_argument (the group stays as it was) on a wrong count, a T[0] other than the identity or a transform the
+   *  device library refuses. */
+  void setTransforms(const std::vector<std::array<double, 9>>& T);
+
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }
   std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> mapService() { return _getMapServ; }
   bool getMapServCallBack(const std::shared_ptr<nav_msgs::srv::GetMap::Request> req,
@@ -58,6 +69,7 @@ private:
   std::vector<Member> _members;
   tsd_group* _group;
   std::vector<int32_t> _cellOff;   // (x, y) per member: whole cells from grid 0's map origin
+  bool _fusable;                   // _cellOff describes the members' placement (always, until setTransforms says otherwise)
   std::shared_ptr<nav_msgs::msg::OccupancyGrid> _occGrid;
   std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> _getMapServ;
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> _gridPub;

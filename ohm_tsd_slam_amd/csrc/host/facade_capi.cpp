@@ -1,6 +1,7 @@
 // facade_capi.cpp -- a flat C surface over the C++ facade so that the Python test / bench drivers can
 // exercise ThreadLocalize / ThreadMapping / ThreadGrid exactly as SlamNode wires them (SlamNode.cpp:27-129): one
 // TsdGrid, one ThreadMapping, one ThreadGrid woken every occ_grid_time_interval, N ThreadLocalize sharing them, laser callbacks per robot.
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -545,6 +546,30 @@ tsd_ctx* tsd_fleet_fuse_tsd(tsd_fleet* f, int* rc)
   f->fused->setMaxTruncation(g0->getMaxTruncation());
   *rc = f->group->fuse(f->fused);
   return *rc == TSD_OK ? f->fused->context() : nullptr;
+}
+
+// ThreadGridGroup::setTransforms: T33s holds one 3x3 row-major transform per node (9n doubles), T[i] = node i's grid coordinates into
+// node 0's.  TSD_OK, or TSD_E_ARG with the reason in err (the group stays as it was).
+int tsd_fleet_set_transforms(tsd_fleet* f, const double* T33s, char* err, int cap)
+{
+  auto refuse = [&](const char* what) {
+    if(err && cap > 0) std::snprintf(err, (size_t)cap, "%s", what);
+    return TSD_E_ARG;
+  };
+  if(!f || !f->group || !T33s)
+    return refuse("tsd_fleet_set_transforms: no fleet or no transforms");
+  std::vector<std::array<double, 9>> T(f->nodes.size());
+  for(size_t i = 0; i < T.size(); i++)
+    std::memcpy(T[i].data(), T33s + 9 * i, 9 * sizeof(double));
+  try
+  {
+    f->group->setTransforms(T);
+  }
+  catch(const std::exception& e)
+  {
+    return refuse(e.what());
+  }
+  return TSD_OK;
 }
 
 void tsd_fleet_fused_lock(tsd_fleet* f) { if(f && f->fused) f->fused->mutex().lock(); }

@@ -60,6 +60,7 @@ HOST_ABI = {
     "tsd_fleet_merged_map_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_fleet_get_merged_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_fleet_fuse_tsd": (C.c_void_p, [C.c_void_p, _ip]),
+    "tsd_fleet_set_transforms": (C.c_int, [C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_fleet_fused_lock": (None, [C.c_void_p]),
     "tsd_fleet_fused_unlock": (None, [C.c_void_p]),
     "tsd_fleet_fused_image_msg": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
@@ -387,7 +388,8 @@ class SlamNode:
 class SlamFleet:
     """Several :class:`SlamNode` s on ONE GPU, each with its own grid, and their merged map (``ThreadGridGroup``): every node's
     ``x_offset`` / ``y_offset`` places its grid, offsets that do not differ by whole cells are refused.  The first node publishes
-    ``<node>/merged_map`` and answers ``<node>/get_merged_map``.  Close the fleet before its nodes."""
+    ``<node>/merged_map`` and answers ``<node>/get_merged_map``.  Maps turned against each other, or a fraction of a cell apart, are
+    merged after ``set_transforms`` (with what ``align`` found).  Close the fleet before its nodes."""
 
     def __init__(self, nodes):
         self.lib = load_library()
@@ -461,6 +463,21 @@ class SlamFleet:
         finally:
             for node in reversed(held):
                 node.lib.tsd_node_grid_unlock(node.h)
+
+    def set_transforms(self, Ts):
+        """Places the nodes' maps by rigid transforms (``ThreadGridGroup::setTransforms``): ``Ts[i]`` (3x3) carries node i's grid
+        coordinates into node 0's, ``Ts[0]`` is the identity --
+        ``[np.eye(3)] + [fleet.align(0, j, ...)["T"] for j in range(1, n)]``.  The merged map published from then on is the
+        occupancy-level merge under those transforms (rotations and fractions of a cell included); ``fuse_tsd`` raises unless every
+        transform is a whole-cell shift."""
+        Ts = list(Ts)
+        if len(Ts) != len(self.nodes):
+            raise capi.TsdError(f"SlamFleet.set_transforms: {len(Ts)} transforms for {len(self.nodes)} nodes")
+        flat = np.ascontiguousarray([np.asarray(T, dtype=np.float64).reshape(9) for T in Ts], dtype=np.float64).reshape(-1)
+        err = C.create_string_buffer(512)
+        rc = self.lib.tsd_fleet_set_transforms(self.h, flat.ctypes.data_as(_dp), err, 512)
+        if rc != 0:
+            raise capi.TsdError(f"tsd_fleet_set_transforms refused ({rc}): {err.value.decode()}")
 
     def fused_image_msg(self) -> dict:
         """the colour image of the fused grid (after ``fuse_tsd``) as a sensor_msgs/Image: ``map_image_msg``'s fields"""

@@ -143,22 +143,42 @@ class LocalOccupancyGroup:
     shifted by ``cell_offsets[i] = (ox, oy)`` whole cells, merged by a local kernel into one int8 map -- the signed maximum
     :class:`NativeOccupancyMerger` gets from ``ncclAllReduce`` across GPUs.  ``width = height = 0``: the window is the members'
     bounding box (``corner`` is its corner in the offsets' frame).  ``merge_async`` / ``merge_maps_async`` only enqueue; ``wait``
-    synchronises.  This is co-residency on one chip, never a scaling curve."""
+    synchronises.  This is co-residency on one chip, never a scaling curve.
 
-    def __init__(self, grids, cell_offsets=None, width: int = 0, height: int = 0):
+    ``transforms`` (exclusive with ``cell_offsets``): one 3x3 rigid transform per grid that carries the grid's coordinates (metres,
+    what ``align_to`` speaks) into the group's frame -- rotations and fractions of a cell included (``tsd_group_create_rigid``: every
+    merged cell is the maximum over a footprint of one or two source cells per axis, so no occupied cell is lost).  ``corner`` is then
+    the window's corner in frame cells, ``transforms`` what the group holds (for a translation group: the shifts as transforms)."""
+
+    def __init__(self, grids, cell_offsets=None, width: int = 0, height: int = 0, transforms=None):
         self.lib = capi.load_library()
         self.grids = list(grids)
         n = len(self.grids)
+        if cell_offsets is not None and transforms is not None:
+            raise capi.TsdError("cell_offsets and transforms are exclusive")
         hs = (C.c_void_p * max(n, 1))(*[g.h for g in self.grids])
-        offs = None
-        if cell_offsets is not None:
-            flat = [int(v) for xy in cell_offsets for v in xy]
-            if len(flat) != 2 * n:
-                raise capi.TsdError("cell_offsets: one (ox, oy) per grid")
-            offs = (C.c_int32 * max(2 * n, 1))(*flat)
-        self.h = self.lib.tsd_group_create(n, hs, offs, int(width), int(height))
-        if not self.h:
-            raise capi.TsdError("tsd_group_create refused the group (see stderr)")
+        if transforms is not None:
+            flat = np.ascontiguousarray([np.asarray(T, dtype=np.float64).reshape(9) for T in transforms], dtype=np.float64).reshape(-1)
+            if flat.size != 9 * n:
+                raise capi.TsdError("transforms: one 3x3 matrix per grid")
+            self.h = self.lib.tsd_group_create_rigid(n, hs, flat.ctypes.data_as(C.POINTER(C.c_double)), int(width), int(height))
+            if not self.h:
+                raise capi.TsdError("tsd_group_create_rigid refused the group (see stderr)")
+        else:
+            offs = None
+            if cell_offsets is not None:
+                flat = [int(v) for xy in cell_offsets for v in xy]
+                if len(flat) != 2 * n:
+                    raise capi.TsdError("cell_offsets: one (ox, oy) per grid")
+                offs = (C.c_int32 * max(2 * n, 1))(*flat)
+            self.h = self.lib.tsd_group_create(n, hs, offs, int(width), int(height))
+            if not self.h:
+                raise capi.TsdError("tsd_group_create refused the group (see stderr)")
+        self.transforms = []
+        for i in range(n):
+            T = np.zeros(9)
+            self.lib.tsd_group_member_transform(self.h, i, T.ctypes.data_as(C.POINTER(C.c_double)))
+            self.transforms.append(T.reshape(3, 3))
         self.width, self.height = self.lib.tsd_group_width(self.h), self.lib.tsd_group_height(self.h)
         x0, y0 = C.c_int32(0), C.c_int32(0)
         self.lib.tsd_group_corner(self.h, C.byref(x0), C.byref(y0))
