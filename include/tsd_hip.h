@@ -737,6 +737,9 @@ int   tsd_group_merge_times(tsd_group* g, double* extract_ms_total, double* merg
 tsd_group* tsd_group_create_rigid(int n, tsd_ctx* const* ctxs, const double* T33 /* 9n, NULL = identities */, int width, int height);
 /* member i's transform into the group's frame; on a translation group the shift (ox_i * cs, oy_i * cs) as a transform */
 int   tsd_group_member_transform(const tsd_group* g, int i, double T33[9]);
+/* the members' whole-cell offsets (what tsd_group_create and tsd_fuse_begin take) when every member is a whole-cell shift, by the
+ * group's own decision (tsd_group_create: always; tsd_group_create_rigid: no rotation, within 1e-6 cells); TSD_E_ARG otherwise */
+int   tsd_group_cell_offsets(const tsd_group* g, int32_t* cell_off_xy /* 2n */);
 
 /* ---- TSD-level fusion: the grids of several robots on ONE GPU fused into one grid ------------------------------- */
 /* dst becomes the grid that would have seen every member's scans: member i's cell (x, y) is dst's cell (x + ox_i, y + oy_i), offsets

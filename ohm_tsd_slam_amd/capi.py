@@ -326,6 +326,7 @@ ABI = {
     "tsd_group_create": (C.c_void_p, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int]),
     "tsd_group_create_rigid": (C.c_void_p, [C.c_int, C.POINTER(C.c_void_p), _dp, C.c_int, C.c_int]),
     "tsd_group_member_transform": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "tsd_group_cell_offsets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "tsd_group_destroy": (None, [C.c_void_p]),
     "tsd_group_size": (C.c_int, [C.c_void_p]),
     "tsd_group_width": (C.c_int, [C.c_void_p]),

@@ -4,6 +4,9 @@
 // tsd_occupancy_dev_async), like comm.hip does.  A group made by tsd_group_create_rigid is the same group with its members placed by
 // rigid transforms: same buffers, events and ordering, k_group_merge_rigid in k_group_merge's place.
 //
+// Both kernels share the step per member and 16-byte piece (take_shifted), the end (store_piece, count_flush) and the arguments
+// (group_args); both constructors share group_new and one form of placement: the window and, per member, T, `whole`, ox / oy.
+//
 // Ordering (events only; nothing waits on the host before tsd_group_merge_wait, nothing spins on the device):
 //   member i's stream :  [wait ev_merged]  extraction into d_member[i]  record ev_extracted[i]
 //   group stream      :  wait ev_extracted[*]  clear count  k_group_merge  record ev_merged  copy count (+ map) to the host
@@ -35,15 +38,35 @@ typedef short s16x2 __attribute__((ext_vector_type(2)));
 // counters on lines of their own, in turn; tsd_group_merge_wait sums them.
 constexpr int GROUP_COUNT_SHARDS = 32, GROUP_COUNT_STRIDE = 32;
 
+// One member record and one argument struct, filled by group_args() for either kernel
 struct GroupMember {
-  const int8_t* map;      // w * h bytes, row = y, 16-byte aligned, w a multiple of 16
-  int ox, oy, w, h;       // the member's cell (x, y) is the window's cell (x + ox, y + oy)
+  const int8_t* map;      // side * side bytes, row = y, 16-byte aligned, side a multiple of 16
+  int side;
+  int whole;              // T is a whole-cell shift: the member's cell (x, y) is the window's cell (x + ox, y + oy)
+  int ox, oy;
+  double c, s, tx, ty;    // T = [c -s tx; s c ty]: the member's grid coordinates (metres) into the frame
 };
 struct GroupArgs {        // by value: the member table is read with scalar loads from the kernel-argument segment
   int8_t* out;            // W * H bytes, row = y
   int* count;             // GROUP_COUNT_SHARDS counters, one per 128-byte line: their sum += cells equal to 100
-  int W, H, n, chunks;    // chunks: 16-byte pieces per output row, (W + 15) / 16
+  int W, H, n;
+  int x0, y0, chunks;     // (x0, y0): the window's corner in frame cells; chunks: 16-byte pieces per output row, (W + 15) / 16
+  double cs;
   GroupMember m[TSD_GROUP_MAX];
+};
+static_assert(sizeof(GroupArgs) <= 4096, "the kernel-argument segment holds 4 KiB");
+// k_group_merge takes the part of GroupArgs it reads, 24 bytes per member.  Its lanes walk the table with one dependent pair of scalar
+// loads per member, and with the 56-byte records -- the same instructions, the stride apart -- it measured 0.2 / 0.9 us slower at
+// N = 2 / 8 (15.7 -> 15.9, 31.0 -> 32.0 us; profiles/group_refactor_ab.txt).
+struct ShiftArgs {
+  int8_t* out;
+  int* count;
+  int W, H, n, chunks;
+  struct Member { const int8_t* map; int side, ox, oy, reserved; } m[TSD_GROUP_MAX];
+  explicit ShiftArgs(const GroupArgs& a) : out(a.out), count(a.count), W(a.W), H(a.H), n(a.n), chunks(a.chunks)
+  {
+    for (int i = 0; i < TSD_GROUP_MAX; i++) m[i] = Member{a.m[i].map, a.m[i].side, a.m[i].ox, a.m[i].oy, 0};
+  }
 };
 
 // bytes s .. s + 15 of the 32 bytes lo | hi (s = 1 .. 15, the same in every lane): four v_alignbit-class instructions
@@ -109,13 +132,71 @@ __device__ __forceinline__ int count100(uint32_t w)
   return __popc(~t & 0x80808080u);
 }
 
-// One lane per 16 bytes of an output row.  Per lane: for every member whose rows cover y and whose columns touch the piece, one aligned
-// 16-byte load (x offset a multiple of 16) or two aligned 16-byte loads funnelled by the offset's low four bits (the same shift in
-// every lane: member rows and output pieces both start on multiples of 16); a member that does not cover the row costs a scalar
-// compare.  -128 is the maximum's identity, and since -128 is also a legal map value the covered bytes are tracked beside it: what no
-// member covers becomes -1.  ROWS16: W is a multiple of 16 -- every piece is whole and its store is one aligned 16-byte store.
+// The step for one member and one 16-byte piece of window row y that starts at column x0 (a multiple of 16): the member's bytes go
+// into the accumulator, the bytes it covers into cov.  One aligned 16-byte load (x offset a multiple of 16) or two aligned 16-byte
+// loads funnelled by the offset's low four bits (the same shift in every lane: member rows and output pieces both start on multiples
+// of 16); a member that does not cover the row costs a scalar compare.
+__device__ __forceinline__ void take_shifted(Acc4& acc, u32x4& cov, const int8_t* map, int side, int ox, int oy, int y, int x0)
+{
+  const int my = y - oy, mx0 = x0 - ox;
+  if ((unsigned)my >= (unsigned)side || mx0 <= -16 || mx0 >= side) return;
+  const int8_t* row = map + (size_t)my * (size_t)side;
+  const int s = (-ox) & 15;                     // = mx0 & 15, from scalars only: uniform
+  const int b0 = mx0 - s;                       // the aligned 16 bytes that hold the piece's first byte: -16 <= b0 < side
+  if (s == 0) {                                 // (then mx0 = b0 >= 0: the piece is one whole aligned block of the member)
+    acc.take(*reinterpret_cast<const u32x4*>(row + b0));
+    cov = (u32x4)(~0u);
+    return;
+  }
+  const bool in0 = b0 >= 0, in1 = b0 + 16 < side;
+  u32x4 lo = (u32x4)(0u), hi = (u32x4)(0u);
+  if (in0) lo = *reinterpret_cast<const u32x4*>(row + b0);
+  if (in1) hi = *reinterpret_cast<const u32x4*>(row + b0 + 16);
+  u32x4 v = funnel16(lo, hi, s);
+  if (in0 && in1) { acc.take(v); cov = (u32x4)(~0u); return; }
+  // the member ends inside this piece: the bytes beyond it take the identity and stay uncovered
+  const u32x4 c = funnel16(in0 ? (u32x4)(~0u) : (u32x4)(0u), in1 ? (u32x4)(~0u) : (u32x4)(0u), s);
+  acc.take((v & c) | ((u32x4)(0x80808080u) & ~c));
+  cov |= c;
+}
+
+// Both kernels' end, part one: the piece of window row y at column x0 is stored, what no member covers as -1; returns how many of
+// the stored bytes equal 100.  ROWS16: W is a multiple of 16 -- every piece is whole and its store is one aligned 16-byte store.
 template <bool ROWS16>
-__global__ void __launch_bounds__(256) k_group_merge(const GroupArgs a)
+__device__ __forceinline__ int store_piece(int8_t* out, int W, int y, int x0, const Acc4& acc, u32x4 cov)
+{
+  u32x4 r;
+#pragma unroll
+  for (int k = 0; k < 4; k++) r[k] = acc.dword(k) | ~cov[k];            // uncovered: 0x80 | 0xFF = -1
+  int8_t* o = out + (size_t)y * (size_t)W + (size_t)x0;
+  int n100 = 0;
+  if (ROWS16 || x0 + 16 <= W) {
+    if (ROWS16) *reinterpret_cast<u32x4*>(o) = r;
+    else *reinterpret_cast<u32x4_u*>(o) = r;
+#pragma unroll
+    for (int k = 0; k < 4; k++) n100 += count100(r[k]);
+  } else {                                       // the row's last, partial piece
+    for (int j = 0; x0 + j < W; j++) {
+      const int8_t b = (int8_t)(r[j >> 2] >> (8 * (j & 3)));
+      o[j] = b;
+      n100 += b == 100;
+    }
+  }
+  return n100;
+}
+
+// Part two: the wave's sum of n100 goes to the counter that the wave's index selects, one atomic per wave at most
+__device__ __forceinline__ void count_flush(int* count, unsigned wave, int n100)
+{
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) n100 += __shfl_down(n100, off, 64);
+  if ((threadIdx.x & 63) == 0 && n100) atomicAdd(count + (wave & (GROUP_COUNT_SHARDS - 1)) * GROUP_COUNT_STRIDE, n100);
+}
+
+// One lane per 16 bytes of an output row; per lane take_shifted() for every member.  -128 is the maximum's identity, and since -128 is
+// also a legal map value the covered bytes are tracked beside it: what no member covers becomes -1.
+template <bool ROWS16>
+__global__ void __launch_bounds__(256) k_group_merge(const ShiftArgs a)
 {
   const unsigned t = blockIdx.x * 256u + threadIdx.x;
   const unsigned chunks = (unsigned)a.chunks;
@@ -126,73 +207,13 @@ __global__ void __launch_bounds__(256) k_group_merge(const GroupArgs a)
     Acc4 acc;
     acc.init();
     u32x4 cov = (u32x4)(0u);
-    for (int i = 0; i < a.n; i++) {
-      const int ox = a.m[i].ox, oy = a.m[i].oy, w = a.m[i].w, h = a.m[i].h;
-      const int my = y - oy, mx0 = x0 - ox;
-      if ((unsigned)my >= (unsigned)h || mx0 <= -16 || mx0 >= w) continue;
-      const int8_t* row = a.m[i].map + (size_t)my * (size_t)w;
-      const int s = (-ox) & 15;                 // = mx0 & 15, from scalars only: uniform
-      const int b0 = mx0 - s;                   // the aligned 16 bytes that hold the piece's first byte: -16 <= b0 < w
-      if (s == 0) {                             // (then mx0 = b0 >= 0: the piece is one whole aligned block of the member)
-        acc.take(*reinterpret_cast<const u32x4*>(row + b0));
-        cov = (u32x4)(~0u);
-        continue;
-      }
-      const bool in0 = b0 >= 0, in1 = b0 + 16 < w;
-      u32x4 lo = (u32x4)(0u), hi = (u32x4)(0u);
-      if (in0) lo = *reinterpret_cast<const u32x4*>(row + b0);
-      if (in1) hi = *reinterpret_cast<const u32x4*>(row + b0 + 16);
-      u32x4 v = funnel16(lo, hi, s);
-      if (in0 && in1) { acc.take(v); cov = (u32x4)(~0u); continue; }
-      // the member ends inside this piece: the bytes beyond it take the identity and stay uncovered
-      const u32x4 c = funnel16(in0 ? (u32x4)(~0u) : (u32x4)(0u), in1 ? (u32x4)(~0u) : (u32x4)(0u), s);
-      v = (v & c) | ((u32x4)(0x80808080u) & ~c);
-      acc.take(v);
-      cov |= c;
-    }
-    u32x4 r;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { r[k] = acc.dword(k) | ~cov[k]; }      // uncovered: 0x80 | 0xFF = -1
-    int8_t* o = a.out + (size_t)y * (size_t)a.W + (size_t)x0;
-    if (ROWS16) {
-      *reinterpret_cast<u32x4*>(o) = r;
-#pragma unroll
-      for (int k = 0; k < 4; k++) n100 += count100(r[k]);
-    } else if (x0 + 16 <= a.W) {
-      *reinterpret_cast<u32x4_u*>(o) = r;
-#pragma unroll
-      for (int k = 0; k < 4; k++) n100 += count100(r[k]);
-    } else {                                     // the row's last, partial piece
-      for (int j = 0; x0 + j < a.W; j++) {
-        const int8_t b = (int8_t)(r[j >> 2] >> (8 * (j & 3)));
-        o[j] = b;
-        n100 += b == 100;
-      }
-    }
+    for (int i = 0; i < a.n; i++) take_shifted(acc, cov, a.m[i].map, a.m[i].side, a.m[i].ox, a.m[i].oy, y, x0);
+    n100 = store_piece<ROWS16>(a.out, a.W, y, x0, acc, cov);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n100 += __shfl_down(n100, off, 64);
-  if ((threadIdx.x & 63) == 0 && n100)                                // one atomic per wave at most
-    atomicAdd(a.count + (((blockIdx.x << 2) | (threadIdx.x >> 6)) & (GROUP_COUNT_SHARDS - 1)) * GROUP_COUNT_STRIDE, n100);
+  count_flush(a.count, (blockIdx.x << 2) | (threadIdx.x >> 6), n100);
 }
 
 // ---- members under rigid transforms (tsd_group_create_rigid; the rule is stated in include/tsd_hip.h) ------------------------------
-struct RigidMember {
-  const int8_t* map;      // side * side bytes, row = y, 16-byte aligned, side a multiple of 16
-  int side;
-  int whole;              // T is a whole-cell shift: the member's cell (x, y) is the window's cell (x + ox, y + oy), as in GroupMember
-  int ox, oy;
-  double c, s, tx, ty;    // T = [c -s tx; s c ty]: the member's grid coordinates (metres) into the frame
-};
-struct RigidArgs {        // by value, as GroupArgs
-  int8_t* out;
-  int* count;
-  int W, H, n, x0, y0, reserved;   // (x0, y0): the window's corner in frame cells
-  double cs;
-  RigidMember m[TSD_GROUP_MAX];
-};
-static_assert(sizeof(RigidArgs) <= 4096, "the kernel-argument segment holds 4 KiB");
-
 // A workgroup owns 64 x 64 window cells.  Their back-projected centres span at most 63 (|c| + |s|) <= 89.1 member cells per axis, the
 // footprints 1.5 more: at most 91 rows of at most 7 aligned 16-byte pieces.  One spare piece per row keeps rows 4 banks apart.
 constexpr int RIGID_BLOCK = 64, RIGID_ROWS = 96, RIGID_PIECES = 8, RIGID_STRIDE = RIGID_PIECES * 16 + 16;
@@ -201,40 +222,15 @@ constexpr int RIGID_BLOCK = 64, RIGID_ROWS = 96, RIGID_PIECES = 8, RIGID_STRIDE 
 // monotone in X and in Y: over a block of cells their extremes are taken at the block's corners, exactly.
 __device__ __forceinline__ double rigid_centre(int k0, int K, double cs) { return ((double)(k0 + K) + 0.5) * cs; }
 
-// k_group_merge's step for one member and one 16-byte piece of window row y that starts at column x0 (a multiple of 16): the member's
-// bytes go into the accumulator, the bytes it covers into cov
-__device__ __forceinline__ void take_shifted(Acc4& acc, u32x4& cov, const int8_t* map, int w, int h, int ox, int oy, int y, int x0)
-{
-  const int my = y - oy, mx0 = x0 - ox;
-  if ((unsigned)my >= (unsigned)h || mx0 <= -16 || mx0 >= w) return;
-  const int8_t* row = map + (size_t)my * (size_t)w;
-  const int s = (-ox) & 15;                     // = mx0 & 15, from scalars only: uniform
-  const int b0 = mx0 - s;
-  if (s == 0) {
-    acc.take(*reinterpret_cast<const u32x4*>(row + b0));
-    cov = (u32x4)(~0u);
-    return;
-  }
-  const bool in0 = b0 >= 0, in1 = b0 + 16 < w;
-  u32x4 lo = (u32x4)(0u), hi = (u32x4)(0u);
-  if (in0) lo = *reinterpret_cast<const u32x4*>(row + b0);
-  if (in1) hi = *reinterpret_cast<const u32x4*>(row + b0 + 16);
-  u32x4 v = funnel16(lo, hi, s);
-  if (in0 && in1) { acc.take(v); cov = (u32x4)(~0u); return; }
-  const u32x4 c = funnel16(in0 ? (u32x4)(~0u) : (u32x4)(0u), in1 ? (u32x4)(~0u) : (u32x4)(0u), s);
-  acc.take((v & c) | ((u32x4)(0x80808080u) & ~c));
-  cov |= c;
-}
-
 // One lane per 16 cells of a window row, four lanes per row, 64 rows per workgroup.  Per member: the box of member cells the block's
 // footprints can touch, from the block's four corners (wave-uniform); a member it misses costs that and nothing else.  Otherwise the
-// box is staged in LDS with aligned 16-byte loads (k_group_merge's loads) and every lane takes its cells' footprint maxima from there:
+// box is staged in LDS with aligned 16-byte loads (take_shifted's loads) and every lane takes its cells' footprint maxima from there:
 // a wave walking a window row walks a slanted line through the member, up to 64 |s| rows of it, a few bytes from each.
-// A member whose transform is a whole-cell shift (the frame's owner, as a rule) takes k_group_merge's path instead: with c = 1, s = 0
+// A member whose transform is a whole-cell shift (the frame's owner, as a rule) takes k_group_merge's step instead: with c = 1, s = 0
 // and a translation within 1e-6 cells of whole cells, u and v lie within 2e-6 of (cell + 0.5), a quarter cell from both thresholds,
 // so the footprint is that one cell -- no fp64, no LDS (measured: profiles/group_merge_rigid.txt).
 template <bool ROWS16>
-__global__ void __launch_bounds__(256) k_group_merge_rigid(const RigidArgs a)
+__global__ void __launch_bounds__(256) k_group_merge_rigid(const GroupArgs a)
 {
   __shared__ __attribute__((aligned(16))) int8_t tile[RIGID_ROWS * RIGID_STRIDE];
   const int bX = (int)blockIdx.x * RIGID_BLOCK, bY = (int)blockIdx.y * RIGID_BLOCK;
@@ -248,7 +244,7 @@ __global__ void __launch_bounds__(256) k_group_merge_rigid(const RigidArgs a)
   for (int i = 0; i < a.n; i++) {
     const int side = a.m[i].side;
     if (a.m[i].whole) {
-      if (live) take_shifted(acc, cov, a.m[i].map, side, side, a.m[i].ox, a.m[i].oy, Y, X0);
+      if (live) take_shifted(acc, cov, a.m[i].map, side, a.m[i].ox, a.m[i].oy, Y, X0);
       continue;
     }
     const double c = a.m[i].c, s = a.m[i].s, tx = a.m[i].tx, ty = a.m[i].ty;
@@ -297,46 +293,22 @@ __global__ void __launch_bounds__(256) k_group_merge_rigid(const RigidArgs a)
     acc.take(val);
     cov |= msk;
   }
-  int n100 = 0;
-  if (live) {
-    u32x4 r;
-#pragma unroll
-    for (int k = 0; k < 4; k++) r[k] = acc.dword(k) | ~cov[k];          // uncovered: 0x80 | 0xFF = -1
-    int8_t* o = a.out + (size_t)Y * (size_t)a.W + (size_t)X0;
-    if (ROWS16) {
-      *reinterpret_cast<u32x4*>(o) = r;
-#pragma unroll
-      for (int k = 0; k < 4; k++) n100 += count100(r[k]);
-    } else if (X0 + 16 <= a.W) {
-      *reinterpret_cast<u32x4_u*>(o) = r;
-#pragma unroll
-      for (int k = 0; k < 4; k++) n100 += count100(r[k]);
-    } else {                                     // the row's last, partial piece
-      for (int j = 0; X0 + j < a.W; j++) {
-        const int8_t b = (int8_t)(r[j >> 2] >> (8 * (j & 3)));
-        o[j] = b;
-        n100 += b == 100;
-      }
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n100 += __shfl_down(n100, off, 64);
-  if ((threadIdx.x & 63) == 0 && n100) {
-    const unsigned wave = ((blockIdx.y * gridDim.x + blockIdx.x) << 2) | (threadIdx.x >> 6);
-    atomicAdd(a.count + (wave & (GROUP_COUNT_SHARDS - 1)) * GROUP_COUNT_STRIDE, n100);
-  }
+  const int n100 = live ? store_piece<ROWS16>(a.out, a.W, Y, X0, acc, cov) : 0;
+  count_flush(a.count, ((blockIdx.y * gridDim.x + blockIdx.x) << 2) | (threadIdx.x >> 6), n100);
 }
 
 }  // namespace
 
 struct tsd_group {
-  int n = 0, W = 0, H = 0, device = 0;
-  int x0 = 0, y0 = 0;                          // the window's corner in the offsets' frame (bounding box: the smallest offsets)
-  bool rigid = false;                          // tsd_group_create_rigid: the members are placed by T
+  int n = 0, device = 0;
+  // the placement, one form for every group: the window, W x H cells with its corner at (x0, y0) in frame cells (the offsets' frame of
+  // tsd_group_create), and per member its transform into the frame, whether that is a whole-cell shift and, where it is, the shift
+  int W = 0, H = 0, x0 = 0, y0 = 0;
+  bool rigid = false;                          // k_group_merge_rigid is launched (tsd_group_create_rigid), k_group_merge otherwise
   std::vector<double> T;                       // 9 per member
-  std::vector<int> whole;                      // T[i] is a whole-cell shift: ox / oy hold it, relative to the window's corner
+  std::vector<int> whole, ox, oy;              // T[i] is a whole-cell shift: ox / oy hold it, relative to the window's corner
   std::vector<tsd_ctx*> ctx;
-  std::vector<int> ox, oy, side;               // offsets relative to the window's corner; cells per side of each member
+  std::vector<int> side;                       // cells per side of each member
   std::vector<int8_t*> d_member;
   std::vector<hipEvent_t> ev_extracted;        // member i's map written (its context's stream)
   std::vector<char> extracted_pending;
@@ -386,15 +358,25 @@ static void group_release(tsd_group* g)
   delete g;
 }
 
-extern "C" {
+static const char kOutOfRange[] = "a member's size or offset is out of range";
 
-tsd_group* tsd_group_create(int n, tsd_ctx* const* ctxs, const int32_t* cell_off_xy, int width, int height)
+// what either constructor asks before it looks at a context; the refusal's text or nullptr
+static const char* members_listed(int n, tsd_ctx* const* ctxs)
+{
+  if (n < 1 || n > TSD_GROUP_MAX) return "the number of members must be 1 .. 64";
+  if (!ctxs) return "no contexts";
+  for (int i = 0; i < n; i++) if (!ctxs[i]) return "a member context is NULL";
+  return nullptr;
+}
+
+// The one constructor: the checks of the members and of an explicit window (worded as tsd_group_create's for either caller), then
+// place(g) -- the caller's placement of the checked members: T, whole, ox / oy and, for a bounding box, the window; it returns a
+// refusal's text or nullptr --, then every device object.  Nothing before the device objects touches the HIP runtime.
+template <class Place>
+static tsd_group* group_new(int n, tsd_ctx* const* ctxs, int width, int height, Place place)
 {
   auto refuse = [](const char* what) -> tsd_group* { std::fprintf(stderr, "tsd_group_create: %s\n", what); return nullptr; };
-  // ---- argument checks: nothing here touches the HIP runtime
-  if (n < 1 || n > TSD_GROUP_MAX) return refuse("the number of members must be 1 .. 64");
-  if (!ctxs) return refuse("no contexts");
-  for (int i = 0; i < n; i++) if (!ctxs[i]) return refuse("a member context is NULL");
+  if (const char* what = members_listed(n, ctxs)) return refuse(what);
   if ((width == 0) != (height == 0) || width < 0 || height < 0 || width > TSD_GROUP_MAX_SIDE || height > TSD_GROUP_MAX_SIDE)
     return refuse("width and height are both 0 (bounding box) or both 1 .. 65536");
   const int device = tsd_device(ctxs[0]);
@@ -407,30 +389,18 @@ tsd_group* tsd_group_create(int n, tsd_ctx* const* ctxs, const int32_t* cell_off
   }
   tsd_group* g = new (std::nothrow) tsd_group();
   if (!g) return nullptr;
-  g->n = n; g->device = device;
+  g->n = n; g->device = device; g->W = width; g->H = height;
   g->ctx.assign(ctxs, ctxs + n);
-  g->ox.resize(n); g->oy.resize(n); g->side.resize(n);
-  int64_t lo_x = INT64_MAX, lo_y = INT64_MAX, hi_x = INT64_MIN, hi_y = INT64_MIN;
-  for (int i = 0; i < n; i++) {
+  g->T.assign((size_t)9 * (size_t)n, 0.0); g->whole.assign(n, 0); g->ox.assign(n, 0); g->oy.assign(n, 0); g->side.resize(n);
+  const char* what = nullptr;
+  for (int i = 0; i < n && !what; i++) {
     g->side[i] = tsd_cells(ctxs[i]);
-    const int64_t x = cell_off_xy ? cell_off_xy[2 * i] : 0, y = cell_off_xy ? cell_off_xy[2 * i + 1] : 0;
-    if (g->side[i] <= 0 || g->side[i] % 16 != 0 || x < -(1 << 24) || x > (1 << 24) || y < -(1 << 24) || y > (1 << 24)) {
-      delete g;
-      return refuse("a member's size or offset is out of range");
-    }
-    g->ox[i] = (int)x; g->oy[i] = (int)y;
-    lo_x = x < lo_x ? x : lo_x; lo_y = y < lo_y ? y : lo_y;
-    hi_x = x + g->side[i] > hi_x ? x + g->side[i] : hi_x; hi_y = y + g->side[i] > hi_y ? y + g->side[i] : hi_y;
+    if (g->side[i] <= 0 || g->side[i] % 16 != 0) what = kOutOfRange;
   }
-  if (width == 0) {
-    if (hi_x - lo_x > TSD_GROUP_MAX_SIDE || hi_y - lo_y > TSD_GROUP_MAX_SIDE) { delete g; return refuse("the bounding box exceeds 65536 cells"); }
-    g->x0 = (int)lo_x; g->y0 = (int)lo_y; g->W = (int)(hi_x - lo_x); g->H = (int)(hi_y - lo_y);
-    for (int i = 0; i < n; i++) { g->ox[i] -= g->x0; g->oy[i] -= g->y0; }
-  } else {
-    g->W = width; g->H = height;
-  }
+  if (!what) what = place(*g);
+  if (what) { delete g; return refuse(what); }
   // ---- device objects; the group's stream first
-  auto fail = [&](const char* what) -> tsd_group* { std::fprintf(stderr, "tsd_group_create: %s\n", what); group_release(g); return nullptr; };
+  auto fail = [&](const char* step) -> tsd_group* { group_release(g); return refuse(step); };
   g->d_member.assign(n, nullptr); g->ev_extracted.assign(n, nullptr); g->extracted_pending.assign(n, 0);
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&g->gstream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&g->ev_merged, hipEventDisableTiming) != hipSuccess)
@@ -451,13 +421,52 @@ tsd_group* tsd_group_create(int n, tsd_ctx* const* ctxs, const int32_t* cell_off
   return g;
 }
 
+// the kernels' arguments from the placement and the members' maps (NULL: the group's own buffers)
+static int group_args(tsd_group* g, const void* const* member_maps_dev, GroupArgs& a)
+{
+  std::memset(&a, 0, sizeof(a));
+  a.out = g->d_merged; a.count = g->d_count; a.W = g->W; a.H = g->H; a.n = g->n; a.chunks = (g->W + 15) / 16;
+  a.x0 = g->x0; a.y0 = g->y0; a.cs = tsd_cell_size(g->ctx[0]);
+  for (int i = 0; i < g->n; i++) {
+    const void* p = member_maps_dev ? member_maps_dev[i] : g->d_member[i];
+    if (!p || (reinterpret_cast<uintptr_t>(p) & 15u)) { g->err = "a member map is NULL or not 16-byte aligned"; return TSD_E_ARG; }
+    const double* t = &g->T[(size_t)9 * (size_t)i];
+    a.m[i] = GroupMember{static_cast<const int8_t*>(p), g->side[i], g->whole[i], g->ox[i], g->oy[i], t[0], t[3], t[2], t[5]};
+  }
+  return TSD_OK;
+}
+
+extern "C" {
+
+tsd_group* tsd_group_create(int n, tsd_ctx* const* ctxs, const int32_t* cell_off_xy, int width, int height)
+{
+  // every member a whole-cell shift; the bounding box's corner is the smallest offsets
+  return group_new(n, ctxs, width, height, [&](tsd_group& g) -> const char* {
+    const double cs = tsd_cell_size(ctxs[0]);
+    int64_t lo_x = INT64_MAX, lo_y = INT64_MAX, hi_x = INT64_MIN, hi_y = INT64_MIN;
+    for (int i = 0; i < n; i++) {
+      const int64_t x = cell_off_xy ? cell_off_xy[2 * i] : 0, y = cell_off_xy ? cell_off_xy[2 * i + 1] : 0;
+      if (x < -(1 << 24) || x > (1 << 24) || y < -(1 << 24) || y > (1 << 24)) return kOutOfRange;
+      g.whole[i] = 1; g.ox[i] = (int)x; g.oy[i] = (int)y;
+      const double T[9] = {1.0, 0.0, (double)x * cs, 0.0, 1.0, (double)y * cs, 0.0, 0.0, 1.0};
+      std::memcpy(&g.T[(size_t)9 * (size_t)i], T, sizeof(T));
+      lo_x = x < lo_x ? x : lo_x; lo_y = y < lo_y ? y : lo_y;
+      hi_x = x + g.side[i] > hi_x ? x + g.side[i] : hi_x; hi_y = y + g.side[i] > hi_y ? y + g.side[i] : hi_y;
+    }
+    if (width == 0) {
+      if (hi_x - lo_x > TSD_GROUP_MAX_SIDE || hi_y - lo_y > TSD_GROUP_MAX_SIDE) return "the bounding box exceeds 65536 cells";
+      g.x0 = (int)lo_x; g.y0 = (int)lo_y; g.W = (int)(hi_x - lo_x); g.H = (int)(hi_y - lo_y);
+      for (int i = 0; i < n; i++) { g.ox[i] -= g.x0; g.oy[i] -= g.y0; }
+    }
+    return nullptr;
+  });
+}
+
 tsd_group* tsd_group_create_rigid(int n, tsd_ctx* const* ctxs, const double* T33, int width, int height)
 {
   auto refuse = [](const char* what) -> tsd_group* { std::fprintf(stderr, "tsd_group_create_rigid: %s\n", what); return nullptr; };
-  // ---- the transforms and the window; the members themselves are checked by tsd_group_create below.  Nothing here touches HIP.
-  if (n < 1 || n > TSD_GROUP_MAX) return refuse("the number of members must be 1 .. 64");
-  if (!ctxs) return refuse("no contexts");
-  for (int i = 0; i < n; i++) if (!ctxs[i]) return refuse("a member context is NULL");
+  // ---- the transforms and the window, ahead of the members' own checks.  Nothing here touches HIP.
+  if (const char* what = members_listed(n, ctxs)) return refuse(what);
   const double cs = tsd_cell_size(ctxs[0]);
   std::vector<double> T((size_t)9 * (size_t)n);
   double lo_x = INFINITY, lo_y = INFINITY, hi_x = -INFINITY, hi_y = -INFINITY;
@@ -486,30 +495,33 @@ tsd_group* tsd_group_create_rigid(int n, tsd_ctx* const* ctxs, const double* T33
       return refuse("the bounding box exceeds 65536 cells");
     x0 = (int)fx0; y0 = (int)fy0; width = (int)(fx1 - fx0); height = (int)(fy1 - fy0);
   }
-  // ---- the members' checks and every device object: a translation group with this window and no shifts
-  tsd_group* g = tsd_group_create(n, ctxs, nullptr, width, height);
-  if (!g) return nullptr;
-  g->rigid = true; g->x0 = x0; g->y0 = y0;
-  g->T.swap(T);
-  // a member shifted by whole cells (within 1e-6 of a cell, the facade's rule) is merged as tsd_group_create's members are
-  g->whole.assign(n, 0);
-  for (int i = 0; i < n; i++) {
-    const double* t = &g->T[(size_t)9 * (size_t)i];
-    const double dx = t[2] / cs, dy = t[5] / cs, rx = std::rint(dx), ry = std::rint(dy);
-    if (t[0] == 1.0 && t[4] == 1.0 && t[1] == 0.0 && t[3] == 0.0 && std::fabs(dx - rx) <= 1e-6 && std::fabs(dy - ry) <= 1e-6) {
-      g->whole[i] = 1; g->ox[i] = (int)rx - x0; g->oy[i] = (int)ry - y0;
+  return group_new(n, ctxs, width, height, [&](tsd_group& g) -> const char* {
+    g.rigid = true; g.x0 = x0; g.y0 = y0;
+    g.T.swap(T);
+    // a member shifted by whole cells (within 1e-6 of a cell) is merged as tsd_group_create's members are
+    for (int i = 0; i < n; i++) {
+      const double* t = &g.T[(size_t)9 * (size_t)i];
+      const double dx = t[2] / cs, dy = t[5] / cs, rx = std::rint(dx), ry = std::rint(dy);
+      if (t[0] == 1.0 && t[4] == 1.0 && t[1] == 0.0 && t[3] == 0.0 && std::fabs(dx - rx) <= 1e-6 && std::fabs(dy - ry) <= 1e-6) {
+        g.whole[i] = 1; g.ox[i] = (int)rx - x0; g.oy[i] = (int)ry - y0;
+      }
     }
-  }
-  return g;
+    return nullptr;
+  });
 }
 
 int tsd_group_member_transform(const tsd_group* g, int i, double T33[9])
 {
   if (!g || i < 0 || i >= g->n || !T33) return TSD_E_ARG;
-  if (g->rigid) { std::memcpy(T33, &g->T[(size_t)9 * (size_t)i], 9 * sizeof(double)); return TSD_OK; }
-  const double cs = tsd_cell_size(g->ctx[i]);
-  const double T[9] = {1.0, 0.0, (double)(g->ox[i] + g->x0) * cs, 0.0, 1.0, (double)(g->oy[i] + g->y0) * cs, 0.0, 0.0, 1.0};
-  std::memcpy(T33, T, sizeof(T));
+  std::memcpy(T33, &g->T[(size_t)9 * (size_t)i], 9 * sizeof(double));
+  return TSD_OK;
+}
+
+int tsd_group_cell_offsets(const tsd_group* g, int32_t* cell_off_xy)
+{
+  if (!g || !cell_off_xy) return TSD_E_ARG;
+  for (int i = 0; i < g->n; i++) if (!g->whole[i]) return TSD_E_ARG;
+  for (int i = 0; i < g->n; i++) { cell_off_xy[2 * i] = g->ox[i] + g->x0; cell_off_xy[2 * i + 1] = g->oy[i] + g->y0; }
   return TSD_OK;
 }
 
@@ -574,25 +586,14 @@ int tsd_group_merge_maps_begin(tsd_group* g, const void* const* member_maps_dev,
 {
   if (!g) return TSD_E_ARG;
   GroupArgs a;
-  RigidArgs ra;                                // (filled for a rigid group only)
-  std::memset(&a, 0, sizeof(a));
-  if (g->rigid) std::memset(&ra, 0, sizeof(ra));
-  for (int i = 0; i < g->n; i++) {
-    const void* p = member_maps_dev ? member_maps_dev[i] : g->d_member[i];
-    if (!p || (reinterpret_cast<uintptr_t>(p) & 15u)) { g->err = "a member map is NULL or not 16-byte aligned"; return TSD_E_ARG; }
-    a.m[i] = GroupMember{static_cast<const int8_t*>(p), g->ox[i], g->oy[i], g->side[i], g->side[i]};
-    if (g->rigid) {
-      const double* t = &g->T[(size_t)9 * (size_t)i];
-      ra.m[i] = RigidMember{static_cast<const int8_t*>(p), g->side[i], g->whole[i], g->ox[i], g->oy[i], t[0], t[3], t[2], t[5]};
-    }
-  }
+  const int rc = group_args(g, member_maps_dev, a);
+  if (rc != TSD_OK) return rc;
   if (hipSetDevice(g->device) != hipSuccess) return group_fail(g, "hipSetDevice", hipGetLastError());
   for (int i = 0; i < g->n; i++)
     if (g->extracted_pending[i]) {
       if (hipStreamWaitEvent(g->gstream, g->ev_extracted[i], 0) != hipSuccess) return group_fail(g, "hipStreamWaitEvent", hipGetLastError());
       g->extracted_pending[i] = 0;
     }
-  a.out = g->d_merged; a.count = g->d_count; a.W = g->W; a.H = g->H; a.n = g->n; a.chunks = (g->W + 15) / 16;
   hipError_t e = hipMemsetAsync(g->d_count, 0, kCountBytes, g->gstream);
   if (e != hipSuccess) return group_fail(g, "hipMemsetAsync", e);
   hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -600,14 +601,12 @@ int tsd_group_merge_maps_begin(tsd_group* g, const void* const* member_maps_dev,
   const unsigned long long pieces = (unsigned long long)a.chunks * (unsigned long long)g->H;      // <= 2^28
   const unsigned blocks = (unsigned)((pieces + 255) / 256);
   if (g->rigid) {
-    ra.out = g->d_merged; ra.count = g->d_count; ra.W = g->W; ra.H = g->H; ra.n = g->n; ra.x0 = g->x0; ra.y0 = g->y0;
-    ra.cs = tsd_cell_size(g->ctx[0]);
     const dim3 grid((unsigned)((g->W + RIGID_BLOCK - 1) / RIGID_BLOCK), (unsigned)((g->H + RIGID_BLOCK - 1) / RIGID_BLOCK));   // <= 1024 x 1024
-    if (g->W % 16 == 0) hipLaunchKernelGGL(k_group_merge_rigid<true>, grid, dim3(256), 0, g->gstream, ra);
-    else hipLaunchKernelGGL(k_group_merge_rigid<false>, grid, dim3(256), 0, g->gstream, ra);
+    if (g->W % 16 == 0) hipLaunchKernelGGL(k_group_merge_rigid<true>, grid, dim3(256), 0, g->gstream, a);
+    else hipLaunchKernelGGL(k_group_merge_rigid<false>, grid, dim3(256), 0, g->gstream, a);
   }
-  else if (g->W % 16 == 0) hipLaunchKernelGGL(k_group_merge<true>, dim3(blocks), dim3(256), 0, g->gstream, a);
-  else hipLaunchKernelGGL(k_group_merge<false>, dim3(blocks), dim3(256), 0, g->gstream, a);
+  else if (g->W % 16 == 0) hipLaunchKernelGGL(k_group_merge<true>, dim3(blocks), dim3(256), 0, g->gstream, ShiftArgs(a));
+  else hipLaunchKernelGGL(k_group_merge<false>, dim3(blocks), dim3(256), 0, g->gstream, ShiftArgs(a));
   e = hipGetLastError();
   if (e != hipSuccess) { if (t0) g->pool.push_back(t0); if (t1) g->pool.push_back(t1); return group_fail(g, "k_group_merge", e); }
   if (t0 && t1) { hipEventRecord(t1, g->gstream); g->pending.push_back({t0, t1, true}); }

@@ -30,7 +30,6 @@ ThreadGridGroup::ThreadGridGroup(const std::shared_ptr<rclcpp::Node>& node, cons
     _node(node),
     _members(members),
     _group(nullptr),
-    _fusable(true),
     _occGrid(std::make_shared<nav_msgs::msg::OccupancyGrid>()),
     _width(0),
     _height(0),
@@ -59,7 +58,6 @@ ThreadGridGroup::ThreadGridGroup(const std::shared_ptr<rclcpp::Node>& node, cons
     if(ox < originX) originX = ox;
     if(oy < originY) originY = oy;
   }
-  _cellOff = off;
   _group = tsd_group_create(static_cast<int>(_members.size()), ctxs.data(), off.data(), 0, 0);
   if(!_group)
     throw std::invalid_argument("ThreadGridGroup: the device refused the group (one device, one cell size, at most 64 grids)");
@@ -157,13 +155,12 @@ int ThreadGridGroup::fuse(obvious::TsdGrid* dst)
 {
   if(!dst || !dst->valid())
     return TSD_E_ARG;
-  std::vector<int32_t> cellOff;
+  std::vector<int32_t> cellOff(2 * _members.size());
   {
-    // (setTransforms may replace the placement between two calls)
+    // (setTransforms may replace the group between two calls)
     std::lock_guard<std::mutex> lk(_publishMutex);
-    if(!_fusable)
+    if(tsd_group_cell_offsets(_group, cellOff.data()) != TSD_OK)
       return TSD_E_ARG;           // a member is rotated or lies a fraction of a cell off: the TSD-level fusion shifts by whole cells
-    cellOff = _cellOff;
   }
   std::vector<tsd_ctx*> ctxs(_members.size());
   for(size_t i = 0; i < _members.size(); i++)
@@ -198,15 +195,10 @@ void ThreadGridGroup::setTransforms(const std::vector<std::array<double, 9>>& T)
   const double cs = static_cast<double>(_grid.getCellSize());
   std::vector<tsd_ctx*> ctxs(_members.size());
   std::vector<double> flat;
-  std::vector<int32_t> off(2 * _members.size(), 0);
-  bool fusable = true;
   for(size_t i = 0; i < _members.size(); i++)
   {
     ctxs[i] = _members[i].grid->context();
     flat.insert(flat.end(), T[i].begin(), T[i].end());
-    const bool turned = !(T[i][0] == 1.0 && T[i][4] == 1.0 && T[i][1] == 0.0 && T[i][3] == 0.0);
-    if(turned || !cellOffset(T[i][2], 0.0, cs, &off[2 * i]) || !cellOffset(T[i][5], 0.0, cs, &off[2 * i + 1]))
-      fusable = false;
   }
   std::lock_guard<std::mutex> lk(_publishMutex);
   tsd_group* group = tsd_group_create_rigid(static_cast<int>(ctxs.size()), ctxs.data(), flat.data(), 0, 0);
@@ -214,8 +206,6 @@ void ThreadGridGroup::setTransforms(const std::vector<std::array<double, 9>>& T)
     throw std::invalid_argument("ThreadGridGroup::setTransforms: the device refused the transforms (rigid, finite, within 65536 cells)");
   tsd_group_destroy(_group);
   _group = group;
-  _cellOff = off;
-  _fusable = fusable;
   if(_hOcc)
     tsd_host_free(_hOcc);
   _hOcc = nullptr;               // (publish() allocates the landing buffer for the new window)

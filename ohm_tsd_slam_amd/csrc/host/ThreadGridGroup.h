@@ -41,7 +41,7 @@ public:
   uint64_t frames(void);
 
   /** TSD-level fusion of the members' grids into `dst` (tsd_fuse_*), on the caller's thread: `dst` lies where grid 0 lies and
-   *  member i is shifted by the whole-cell distance of its map origin from grid 0's, the offsets of the occupancy merge.  `dst`
+   *  member i is shifted by the whole-cell offset the group holds for it (the occupancy merge's own placement).  `dst`
    *  (same cell size and truncation as the members, not one of them) is an ordinary grid afterwards.  The fusion must not run
    *  beside a grid write of a member enqueued in between, so the mutexes of ALL grids involved are held while it is enqueued -- in
    *  member order, then dst's; nothing else holds two grids -- and none of the members' while it runs.  TSD_OK or the error code. */
@@ -50,8 +50,8 @@ public:
   /** Places the members by rigid transforms instead of the whole-cell distances of their map origins: T[i] (3x3 row-major) carries
    *  member i's grid coordinates into member 0's, what tsd_map_align(grid 0, grid i) returns; T[0] must be the identity.  The group
    *  is replaced by a rigid one (tsd_group_create_rigid, bounding box) between two publications; the merged map's origin becomes
-   *  member 0's map origin plus the window's corner, its orientation stays the identity.  fuse() returns TSD_E_ARG from then on
-   *  unless every T[i] is a whole-cell shift (no rotation, cellOffset's 1e-6-cell rule), and fuses with those shifts if they all are.
+   *  member 0's map origin plus the window's corner, its orientation stays the identity.  fuse() asks the group for the members'
+   *  whole-cell offsets (tsd_group_cell_offsets) and returns TSD_E_ARG where it has none: a member turned or a fraction of a cell off.
    *  Throws std::invalid_argument (the group stays as it was) on a wrong count, a T[0] other than the identity or a transform the
    *  device library refuses. */
   void setTransforms(const std::vector<std::array<double, 9>>& T);
@@ -68,8 +68,6 @@ private:
   std::shared_ptr<rclcpp::Node> _node;
   std::vector<Member> _members;
   tsd_group* _group;
-  std::vector<int32_t> _cellOff;   // (x, y) per member: whole cells from grid 0's map origin
-  bool _fusable;                   // _cellOff describes the members' placement (always, until setTransforms says otherwise)
   std::shared_ptr<nav_msgs::msg::OccupancyGrid> _occGrid;
   std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> _getMapServ;
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> _gridPub;

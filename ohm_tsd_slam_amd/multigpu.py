@@ -208,6 +208,15 @@ class LocalOccupancyGroup:
         if rc != 0:
             raise capi.TsdError(f"{what} failed ({rc}): {self.lib.tsd_group_last_error(self.h).decode()}")
 
+    def cell_offsets(self):
+        """the members' whole-cell offsets ``[(ox, oy), ...]`` as the group holds them, or ``None`` unless every member is a
+        whole-cell shift (``tsd_group_cell_offsets``)"""
+        n = len(self.grids)
+        off = (C.c_int32 * (2 * n))()
+        if self.lib.tsd_group_cell_offsets(self.h, off) != 0:
+            return None
+        return [(off[2 * i], off[2 * i + 1]) for i in range(n)]
+
     def merge_async(self, inflate: bool = False, inflate_factor: int = 2):
         """every member's extraction on its own stream, the merge and the copy to the host behind them; nothing waits"""
         prm = capi.MapParams(int(bool(inflate)), int(inflate_factor))

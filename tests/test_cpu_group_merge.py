@@ -79,6 +79,12 @@ def test_group_create_refuses_bad_arguments_without_a_device(hip_lib, capfd):
         multigpu.LocalOccupancyGroup([])
 
 
+def test_cell_offsets_refuses_null_arguments_without_a_device(hip_lib):
+    buf = (C.c_int32 * 4)()
+    assert hip_lib.tsd_group_cell_offsets(None, buf) == -1            # TSD_E_ARG
+    assert hip_lib.tsd_group_cell_offsets(None, None) == -1
+
+
 def test_libtsd_hip_needs_no_rccl():
     """the group lives in libtsd_hip.so, and a single-GPU host still never maps RCCL: checked in a fresh interpreter that loads and
     binds the library (this process may have loaded libtsd_comm.so for other tests)"""

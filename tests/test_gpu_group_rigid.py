@@ -269,3 +269,73 @@ def test_slam_fleet_merges_maps_turned_against_each_other():
         fleet.close()
         for n in nodes:
             n.close()
+
+
+OFFS = [(1, 7), (-5, 0), (17, -40)]
+
+
+def _cell_offsets(n, **kw):
+    """(cell_offsets(), corner) of a group of n 256^2 grids"""
+    grids = [capi.TsdGridDevice(8, CS, 3 * CS) for _ in range(n)]
+    grp = multigpu.LocalOccupancyGroup(grids, **kw)
+    try:
+        return grp.cell_offsets(), grp.corner
+    finally:
+        grp.close()
+
+
+@pytest.mark.parametrize("how", ["offsets", "shifts"])
+def test_cell_offsets_of_whole_cell_groups(how):
+    """the group answers with the offsets it was given, in the offsets' frame (the bounding box's corner is not (0, 0)), whichever
+    constructor made it"""
+    kw = dict(cell_offsets=OFFS) if how == "offsets" else dict(transforms=[R.shift(ox, oy, CS) for ox, oy in OFFS])
+    offs, corner = _cell_offsets(3, **kw)
+    assert corner == (-5, -40)
+    assert offs == OFFS
+
+
+@pytest.mark.parametrize("T,want", [(R.shift(17 + 5e-7, -40, CS), [(0, 0), (17, -40)]),      # the 1e-6-cell rule, inside
+                                    (R.shift(17 + 2e-6, -40, CS), None),                      # and outside
+                                    (R.rigid(1e-6), None),
+                                    (R.shift(17.25, -40.5, CS), None)],
+                         ids=["5e-7_off", "2e-6_off", "turned_1e-6_rad", "quarter_and_half_cell"])
+def test_cell_offsets_follow_the_groups_whole_cell_decision(T, want):
+    offs, _ = _cell_offsets(2, transforms=[np.eye(3), T])
+    assert offs == want
+
+
+def test_slam_fleet_fuses_by_the_groups_placement():
+    """Two nodes whose grids lie 12 cells apart (x_offset 0 and 0.6 m).  A fleet that places them by those offsets from the start and a
+    fleet over the same nodes that is told the same placement by set_transforms fuse to the same grid, bit for bit; between the two
+    a turn makes fuse_tsd raise, and the whole-cell shift after it fuses again: fuse() asks the group it has, not a copy."""
+    gc = synth.GridConfig(8, CS)
+    geo = synth.ScanGeometry.full_circle_360()
+    world = synth.World("room", gc)
+    scans = synth.scans_for(world, geo, synth.trajectory(world, 4))
+    nodes = [facade.SlamNode(facade.node_params(gc, geo, x_offset=xo, occ_grid_time_interval=1000.0), synchronous=True,
+                             name=f"tsd_slam_{i}") for i, xo in enumerate((0.0, 0.6))]
+    try:
+        for k in range(len(scans)):
+            for i, n in enumerate(nodes):
+                n.laser(scans[(k + i) % len(scans)], geo.angle_min, geo.angle_increment)
+        placed = facade.SlamFleet(nodes)
+        try:
+            want = placed.fuse_tsd().digest()
+        finally:
+            placed.close()
+        assert want["cells_valid"] > 1000
+        fleet = facade.SlamFleet(nodes)
+        try:
+            h = 0.5 * gc.cells * CS
+            fleet.set_transforms([np.eye(3), R.about(7.3 * DEG, (h, h))])
+            with pytest.raises(capi.TsdError):
+                fleet.fuse_tsd()
+            off = GR.cell_offset(GR.map_origin(gc.cells, CS, 0.6), GR.map_origin(gc.cells, CS, 0.0), CS)
+            assert off == -12
+            fleet.set_transforms([np.eye(3), R.shift(off, 0, CS)])
+            assert fleet.fuse_tsd().digest() == want
+        finally:
+            fleet.close()
+    finally:
+        for n in nodes:
+            n.close()
