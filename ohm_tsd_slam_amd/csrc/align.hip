@@ -4,8 +4,8 @@
 //   k_align_stage    the list's way into the context: p + add (the half-cell offset between calcCoords' list and the field the look-ups
 //                    read, for tsd_map_align), and the count of coordinates that are not finite or out of reach
 //   k_align_score    k_reloc_score's sum over the coarse points (every stride-th, minus the pivot, read from the device list), without the
-//                    free-space gate; the look-up loop is reloc_shared.hpp's reloc_lane_score: one copy
-//   (peaks)          reloc.hip's k_reloc_peaks / k_reloc_peaks_merge, unchanged
+//                    free-space gate: reloc_shared.hpp's lattice_score<false>, the body both score kernels run
+//   (peaks)          reloc.hip's k_reloc_peaks / k_reloc_peaks_merge, launched with the score kernel by launch_lattice_search
 //   k_align_refine   point-to-TSD Gauss-Newton: ONE persistent workgroup per peak, all K peaks in one launch; its threads stride over all
 //                    n points every iteration, the 11 sums are reduced inside the workgroup in a fixed order (per thread in index order,
 //                    shuffle tree per wave, waves in order: no floating-point atomics), one lane solves the 3 x 3 system and steps the
@@ -13,7 +13,10 @@
 //                    start pose from the merged peak keys on the device: the host waits once per call.
 //
 // Shape of k_align_refine: a divergent gather of 25 reads per point (five look-ups: the value and interpolate_normal's four, a tile flag
-// and four cells each).  All 25 are requested before the first is used (ld_pinned / load_quad: not behind the flag tests).
+// and four cells each).  All 25 are requested before the first is used (tsd_device.hpp's lookup_issue: not behind the flag tests).
+//
+// The lattice's refusals, the rotation table, the score volume, the launch of the search and the decoding of a peak key are the
+// relocalisation's, through reloc_shared.hpp; this file keeps what is the alignment's own.
 #include "reloc_shared.hpp"
 
 namespace tsd {
@@ -33,30 +36,11 @@ k_align_stage(const double* __restrict__ in, double* __restrict__ out, int n, do
   if (out) { out[2 * (size_t)i] = x + add; out[2 * (size_t)i + 1] = y + add; }
 }
 
-// a workgroup = one lattice position and a run of its rotations, a wave per rotation (k_reloc_score's shape without the gate)
 __global__ void __launch_bounds__(64 * RELOC_WAVES)
 k_align_score(GridDev g, RelocLattice L, const double* __restrict__ pts, int P, int stride, double pvx, double pvy,
               const double* __restrict__ cos_sin, uint32_t* __restrict__ scores, int rot_per_block)
 {
-  extern __shared__ __attribute__((aligned(16))) double s_pts[];      // [P] x | [P] y, relative to the pivot
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int ix = (int)blockIdx.x % L.nx, iy = (int)blockIdx.x / L.nx;
-  const double tx = L.x0 + (double)ix * L.step, ty = L.y0 + (double)iy * L.step;
-  for (int i = threadIdx.x; i < P; i += 64 * RELOC_WAVES) {
-    const size_t at = (size_t)i * (size_t)stride;
-    s_pts[i] = pts[2 * at] - pvx; s_pts[P + i] = pts[2 * at + 1] - pvy;
-  }
-  const int k0 = (int)blockIdx.y * rot_per_block;
-  const int k1 = k0 + rot_per_block < L.ntheta ? k0 + rot_per_block : L.ntheta;
-  const size_t plane = (size_t)L.nx * (size_t)L.ny, at = (size_t)iy * (size_t)L.nx + (size_t)ix;
-  __syncthreads();
-  for (int k = k0 + wave; k < k1; k += RELOC_WAVES) {                 // (whole waves: no barrier below)
-    const double c = cos_sin[2 * k], s = cos_sin[2 * k + 1];
-    unsigned int acc = reloc_lane_score(g, s_pts, P, lane, c, s, tx, ty);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += (unsigned int)__shfl_down((int)acc, off, 64);
-    if (lane == 0) scores[(size_t)k * plane + at] = acc;
-  }
+  lattice_score<false>(g, L, pts, P, stride, pvx, pvy, cos_sin, scores, rot_per_block);
 }
 
 struct AlignRefineArgs {
@@ -80,17 +64,12 @@ __device__ __forceinline__ void align_accumulate(const GridDev& g, const AlignRe
     const double qx = (c * px - s * py) + mx;
     const double qy = (s * px + c * py) + my;
     // the value's look-up and the normal's four: 5 flag reads and 20 cell reads requested together
-    int p = 0, lx = 0, ly = 0; double dx = 0.0, dy = 0.0;
-    const bool in = coord2cell(g, qx, qy, p, lx, ly, dx, dy);
-    if (!in) { p = 0; lx = 0; ly = 0; }
-    const uint8_t fl = ld_pinned(&g.flags[p]);
-    const Quad qd = load_quad(g.tsd + (size_t)p * TILE_STRIDE, lx, ly);
-    double nx, ny;
+    const Lookup at = lookup_issue(g, qx, qy);
+    double nx, ny, v;
     const bool okn = interpolate_normal(g, qx, qy, nx, ny);
-    const double wx = fabs((qx - dx) * g.inv_cs), wy = fabs((qy - dy) * g.inv_cs);
-    const double v = qd.t00 * (1. - wy) * (1. - wx) + qd.t10 * wy * (1. - wx) + qd.t01 * (1. - wy) * wx + qd.t11 * wy * wx;
+    const bool okv = lookup_value(at, v);
     // (interpolate_normal normalises exactly when the length is > 10e-6: a normalised normal has length 1, any other at most 10e-6)
-    const bool ok = in && fl != 0 && !isnan(v) && okn && (nx * nx + ny * ny > 0.25);
+    const bool ok = okv && okn && (nx * nx + ny * ny > 0.25);
     if (ok) {
       n_ok++;
       const double u = v / a.v_cut;
@@ -122,10 +101,10 @@ k_align_refine(GridDev g, const AlignRefineArgs a)
   if (a.keys) {                            // (uniform)
     const unsigned long long key = a.keys[blockIdx.x];
     if (key == 0ull) return;               // fewer peaks than workgroups
-    score = (unsigned int)(key >> 32); idx = (int)(0xFFFFFFFFu - (unsigned int)(key & 0xFFFFFFFFull));
-    const int per = a.L.nx * a.L.ny, k = idx / per, rem = idx % per, iy = rem / a.L.nx, ix = rem % a.L.nx;
-    mx = a.L.x0 + (double)ix * a.L.step; my = a.L.y0 + (double)iy * a.L.step;
-    c = a.cos_sin[2 * k]; s = a.cos_sin[2 * k + 1];
+    const Peak pk = peak_of(key);
+    const LatticePose at = lattice_pose(a.L, a.cos_sin, pk.idx);
+    score = pk.score; idx = (int)pk.idx;
+    mx = at.x; my = at.y; c = at.c; s = at.s;
   }
   // thread 0's: the step control
   double gain = 1.0, pdx = 0.0, pdy = 0.0, pdt = 0.0;
@@ -198,18 +177,13 @@ k_align_refine(GridDev g, const AlignRefineArgs a)
 void align_free(tsd_ctx* ctx)
 {
   tsd_ctx::Align& al = ctx->align;
-  hipFree(al.d_pts); hipFree(al.d_scores); hipFree(al.d_rec); hipFree(al.d_bad);
+  hipFree(al.d_pts); hipFree(al.volume.d); hipFree(al.d_rec); hipFree(al.d_bad);
   if (al.h_rec) hipHostFree(al.h_rec);
   if (al.h_bad) hipHostFree(al.h_bad);
   al = tsd_ctx::Align{};
 }
 
-static void align_drop_volume(tsd_ctx::Align& al)
-{
-  hipFree(al.d_scores); al.d_scores = nullptr; al.score_cap = 0; al.nx = al.ny = al.ntheta = 0;
-}
-
-static int align_ensure(tsd_ctx* ctx, size_t points, size_t candidates)
+static int align_ensure(tsd_ctx* ctx, size_t points)
 {
   tsd_ctx::Align& al = ctx->align;
   if (!al.d_rec) TSD_HIP_CHECK(ctx, hipMalloc(&al.d_rec, sizeof(tsd_align_peak) * (TSD_RELOC_MAX_PEAKS + 1)));
@@ -222,34 +196,22 @@ static int align_ensure(tsd_ctx* ctx, size_t points, size_t candidates)
     TSD_HIP_CHECK(ctx, hipMalloc(&al.d_pts, sizeof(double) * 2 * cap));
     al.pts_cap = cap;
   }
-  if (candidates > al.score_cap) {
-    align_drop_volume(al);
-    TSD_HIP_CHECK(ctx, hipMalloc(&al.d_scores, sizeof(uint32_t) * candidates));
-    al.score_cap = candidates;
-  }
   return TSD_OK;
 }
 
 static double align_v_cut(const tsd_align_params* p) { return p->v_cut == 0.0 ? 0.75 : p->v_cut; }
 static double align_eps(const tsd_align_params* p) { return p->eps == 0.0 ? 1e-6 : p->eps; }
 
-// everything of the parameters that can be checked without the points; `who` names the entry point in the message
-static int align_check_params(tsd_ctx* ctx, const tsd_align_params* prm, bool pivot_may_be_nan, const char* who)
+// everything of the parameters that can be checked without the points, and the call's rotation table; `who` names the entry point in
+// the message
+static int align_check_params(tsd_ctx* ctx, const tsd_align_params* prm, bool pivot_may_be_nan, const char* who, std::vector<double>& table)
 {
-  auto refuse = [&](int code, const char* what) { return set_error(ctx, code, (std::string(who) + ": " + what).c_str(), hipSuccess); };
+  auto refuse = [&](int code, const char* what) { return tsd::refuse(ctx, who, code, what); };
   if (prm->K < 1 || prm->K > TSD_RELOC_MAX_PEAKS) return refuse(TSD_E_ARG, "K outside 1 .. TSD_RELOC_MAX_PEAKS");
   if (prm->iterations < 0 || prm->iterations > 64) return refuse(TSD_E_ARG, "iterations outside 0 .. 64");
-  if (!reloc_lattice_ok(prm->nx, prm->ny, prm->ntheta)) return refuse(TSD_E_ARG, "nx, ny, ntheta must be >= 1");
-  if (!std::isfinite(prm->x0) || !std::isfinite(prm->y0) || !std::isfinite(prm->step_xy) || !(prm->step_xy > 0.0))
-    return refuse(TSD_E_ARG, "x0, y0 finite and step_xy > 0");
-  if (!reloc_lattice_fits(prm->nx, prm->ny, prm->ntheta)) return refuse(TSD_E_CAPACITY, "nx * ny * ntheta > TSD_RELOC_MAX_CANDIDATES");
-  if (!reloc_lattice_near(ctx->grid, prm->x0, prm->nx, prm->step_xy) || !reloc_lattice_near(ctx->grid, prm->y0, prm->ny, prm->step_xy))
-    return refuse(TSD_E_ARG, "the lattice reaches further than TSD_RELOC_MAX_REACH grid widths from the grid");
-  if (!prm->cos_sin && (!std::isfinite(prm->theta0) || !std::isfinite(prm->dtheta) || prm->dtheta == 0.0))
-    return refuse(TSD_E_ARG, "without a cos_sin table, theta0 and a non-zero dtheta are needed");
-  if (prm->cos_sin)
-    for (int k = 0; k < 2 * prm->ntheta; k++)
-      if (!std::isfinite(prm->cos_sin[k])) return refuse(TSD_E_ARG, "cos_sin is not finite");
+  const LatticeSpec lat = lattice_spec(*prm);
+  if (int rc = lattice_check(ctx, lat, who)) return rc;
+  if (!lattice_table(lat, table)) return refuse(TSD_E_ARG, "cos_sin is not finite");
   const bool pivot_nan = std::isnan(prm->pivot_x) && std::isnan(prm->pivot_y);
   if (!(pivot_may_be_nan && pivot_nan) && (!(std::fabs(prm->pivot_x) <= reloc_reach(ctx->grid)) || !(std::fabs(prm->pivot_y) <= reloc_reach(ctx->grid))))
     return refuse(TSD_E_ARG, "the pivot is not finite or further than TSD_RELOC_MAX_REACH grid widths away");
@@ -270,33 +232,24 @@ static void align_clear_result(tsd_align_result* out)
   out->cell_error = nan;
 }
 
-// the whole alignment; the arguments have been checked.  src_cells: the side of the grid the points come from, for cell_error
-static int align_run(tsd_ctx* ctx, const tsd_align_params* prm, const double* points_xy, int n, bool on_device, int src_cells,
-                     tsd_align_result* out)
+// the whole alignment; the arguments have been checked and `table` is theirs.  src_cells: the side of the grid the points come from,
+// for cell_error
+static int align_run(tsd_ctx* ctx, const tsd_align_params* prm, const std::vector<double>& table, const double* points_xy, int n,
+                     bool on_device, int src_cells, tsd_align_result* out)
 {
-  const int nx = prm->nx, ny = prm->ny, nt = prm->ntheta;
-  std::vector<double> table((size_t)2 * nt);
-  for (int k = 0; k < nt; k++) {
-    if (prm->cos_sin) { table[2 * k] = prm->cos_sin[2 * k]; table[2 * k + 1] = prm->cos_sin[2 * k + 1]; }
-    else { const double th = prm->theta0 + (double)k * prm->dtheta; table[2 * k] = std::cos(th); table[2 * k + 1] = std::sin(th); }
-  }
+  const LatticeSpec lat = lattice_spec(*prm);
+  const RelocLattice& L = lat.L;
   if (int rc = enter(ctx)) return rc;
   tsd_ctx::Align& al = ctx->align;
-  const size_t cand = (size_t)nx * (size_t)ny * (size_t)nt;
   al.n_rec = 0;
-  if (int rc = reloc_ensure(ctx, (size_t)nt, 0)) return rc;
-  if (int rc = align_ensure(ctx, on_device ? 0 : (size_t)n, cand)) return rc;
+  ScoreVolume::GiveBack give_back{al.volume};
+  if (int rc = reloc_ensure(ctx, (size_t)L.ntheta)) return rc;
+  if (int rc = align_ensure(ctx, on_device ? 0 : (size_t)n)) return rc;
+  if (int rc = al.volume.ensure(ctx, (size_t)L.nx * (size_t)L.ny * (size_t)L.ntheta)) return rc;
   tsd_ctx::Reloc& r = ctx->reloc;
-  struct VolumeGuard { tsd_ctx::Align& al; ~VolumeGuard() { if (al.score_cap > RELOC_KEEP_CANDIDATES) align_drop_volume(al); } } volume_guard{al};
   align_clear_result(out);
-  const bool timed = ctx->profile;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  auto drop_events = [&]() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); };
-  if (timed)
-    for (hipEvent_t& e : ev) {
-      const hipError_t ee = hipEventCreate(&e);
-      if (ee != hipSuccess) { e = nullptr; drop_events(); return set_error(ctx, TSD_E_HIP, "tsd_align_points: hipEventCreate", ee); }
-    }
+  StageEvents stages;                      // 0 .. 1 the search, 1 .. 2 the refinement
+  if (int rc = stages.open(ctx, 3, "tsd_align_points")) return rc;
   const double* d_pts = points_xy;
   hipError_t e = hipMemsetAsync(al.d_bad, 0, sizeof(unsigned int), ctx->stream);
   if (!on_device) {                        // (checked on the host already; the source stays valid until the wait)
@@ -306,19 +259,13 @@ static int align_run(tsd_ctx* ctx, const tsd_align_params* prm, const double* po
     hipLaunchKernelGGL(k_align_stage, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, points_xy, (double*)nullptr, n, 0.0,
                        reloc_reach(ctx->grid), al.d_bad);
   if (e == hipSuccess) e = hipMemcpyAsync(r.d_cos_sin, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) { drop_events(); return set_error(ctx, TSD_E_HIP, "tsd_align_points: copy of the points", e); }
+  if (e != hipSuccess) return set_error(ctx, TSD_E_HIP, "tsd_align_points: copy of the points", e);
   // ---- search ----
   const int stride = (n + TSD_MAX_ICP_POINTS - 1) / TSD_MAX_ICP_POINTS;
   const int P = (n + stride - 1) / stride;
-  if (timed) hipEventRecord(ev[0], ctx->stream);
-  int rot_per_block = 0, blocks_y = 0;
-  reloc_cut(nx, ny, nt, rot_per_block, blocks_y);
-  const RelocLattice L{prm->x0, prm->y0, prm->step_xy, nx, ny, nt};
-  hipLaunchKernelGGL(k_align_score, dim3((unsigned)((long long)nx * ny), (unsigned)blocks_y), dim3(64 * RELOC_WAVES), sizeof(double) * 2 * (size_t)P,
-                     ctx->stream, ctx->grid, L, d_pts, P, stride, prm->pivot_x, prm->pivot_y, (const double*)r.d_cos_sin, al.d_scores, rot_per_block);
-  al.nx = nx; al.ny = ny; al.ntheta = nt;
-  int rc = launch_reloc_peaks(ctx, al.d_scores, nx, ny, nt, prm->theta_wraps ? 1 : 0, prm->K);
-  if (timed) hipEventRecord(ev[1], ctx->stream);
+  stages.record(0);
+  int rc = launch_lattice_search(ctx, al.volume, lat, false, d_pts, P, stride, prm->pivot_x, prm->pivot_y);
+  stages.record(1);
   // ---- refinement: every peak in one launch, the start poses decoded from the merged keys on the device ----
   const double lever = prm->lever > 0.0 ? prm->lever : 0.5 * ((double)ctx->grid.N * ctx->grid.cs);
   if (rc == TSD_OK) {
@@ -328,19 +275,15 @@ static int align_run(tsd_ctx* ctx, const tsd_align_params* prm, const double* po
     a.keys = reloc_merged_keys(ctx); a.L = L; a.cos_sin = r.d_cos_sin; a.rec = al.d_rec;
     hipLaunchKernelGGL(k_align_refine, dim3((unsigned)prm->K), dim3(ALIGN_THREADS), 0, ctx->stream, ctx->grid, a);
     e = hipGetLastError();
-    if (timed) hipEventRecord(ev[2], ctx->stream);
+    stages.record(2);
     if (e == hipSuccess) e = hipMemcpyAsync(al.h_rec, al.d_rec, sizeof(tsd_align_peak) * (size_t)prm->K, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(al.h_bad, al.d_bad, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);       // the one wait of the call
     if (e != hipSuccess) rc = set_error(ctx, TSD_E_HIP, "tsd_align_points: search and refinement", e);
   }
-  if (rc == TSD_OK && timed) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) out->search_ms = (double)ms;
-    if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) out->refine_ms = (double)ms;
-  }
-  drop_events();
   if (rc != TSD_OK) return rc;
+  stages.measure(0, 1, out->search_ms);
+  stages.measure(1, 2, out->refine_ms);
   if (*al.h_bad != 0u)
     return set_error(ctx, TSD_E_ARG, "tsd_align_points: a point is not finite or further than TSD_RELOC_MAX_REACH grid widths away", hipSuccess);
   const int n_peaks = (int)r.h_keys[PK_KEEP];
@@ -355,10 +298,9 @@ static int align_run(tsd_ctx* ctx, const tsd_align_params* prm, const double* po
   }
   if (best < 0) return TSD_OK;
   const tsd_align_peak& w = al.h_rec[best];
-  const int per = nx * ny, k = w.idx / per, rem = w.idx % per;
+  const LatticePose coarse = lattice_pose(L, table.data(), (unsigned int)w.idx);
   out->winner_idx = w.idx; out->winner_score = w.score;
-  out->coarse_x = prm->x0 + (double)(rem % nx) * prm->step_xy; out->coarse_y = prm->y0 + (double)(rem / nx) * prm->step_xy;
-  out->coarse_cos = table[2 * k]; out->coarse_sin = table[2 * k + 1];
+  out->coarse_x = coarse.x; out->coarse_y = coarse.y; out->coarse_cos = coarse.c; out->coarse_sin = coarse.s;
   out->iterations = w.iterations; out->converged = w.status == TSD_ALIGN_CONVERGED ? 1 : 0;
   out->n_ok = w.n_ok; out->weight_sum = w.sums[9];
   out->rms = w.sums[9] > 0.0 ? std::sqrt(w.sums[10] / w.sums[9]) : std::nan("");
@@ -402,13 +344,12 @@ int tsd_align_points(tsd_ctx* ctx, const tsd_align_params* prm, const double* po
 {
   if (!ctx || !prm || !points_xy || !out) return TSD_E_ARG;
   if (int rc = align_check_count(ctx, n, "tsd_align_points")) return rc;
-  if (int rc = align_check_params(ctx, prm, false, "tsd_align_points")) return rc;
-  if (!on_device)
-    for (int i = 0; i < 2 * n; i++)
-      if (!(std::fabs(points_xy[i]) <= reloc_reach(ctx->grid)))   // (NaN fails too)
-        return set_error(ctx, TSD_E_ARG, "tsd_align_points: a point is not finite or further than TSD_RELOC_MAX_REACH grid widths away", hipSuccess);
+  std::vector<double> table;
+  if (int rc = align_check_params(ctx, prm, false, "tsd_align_points", table)) return rc;
+  if (!on_device && !points_in_reach(ctx->grid, points_xy, n))
+    return set_error(ctx, TSD_E_ARG, "tsd_align_points: a point is not finite or further than TSD_RELOC_MAX_REACH grid widths away", hipSuccess);
   if (reloc_scan_in_flight(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_align_points: a scan of this context is in flight (collect it first)", hipSuccess);
-  return align_run(ctx, prm, points_xy, n, on_device != 0, ctx->grid.N, out);
+  return align_run(ctx, prm, table, points_xy, n, on_device != 0, ctx->grid.N, out);
 }
 
 int tsd_map_align(tsd_ctx* dst, tsd_ctx* src, const tsd_align_params* prm, tsd_align_result* out)
@@ -416,7 +357,8 @@ int tsd_map_align(tsd_ctx* dst, tsd_ctx* src, const tsd_align_params* prm, tsd_a
   if (!dst || !src || !prm || !out) return TSD_E_ARG;
   if (dst == src) return set_error(dst, TSD_E_ARG, "tsd_map_align: dst and src are the same context", hipSuccess);
   if (dst->device != src->device) return set_error(dst, TSD_E_ARG, "tsd_map_align: dst and src are on different devices", hipSuccess);
-  if (int rc = align_check_params(dst, prm, true, "tsd_map_align")) return rc;
+  std::vector<double> table;
+  if (int rc = align_check_params(dst, prm, true, "tsd_map_align", table)) return rc;
   if (reloc_scan_in_flight(dst) || reloc_scan_in_flight(src))
     return set_error(dst, TSD_E_ARG, "tsd_map_align: a scan of dst or src is in flight (collect it first)", hipSuccess);
   // ---- the arguments stand ----
@@ -427,26 +369,17 @@ int tsd_map_align(tsd_ctx* dst, tsd_ctx* src, const tsd_align_params* prm, tsd_a
   tsd_align_params p = *prm;
   if (std::isnan(p.pivot_x) && std::isnan(p.pivot_y)) p.pivot_x = p.pivot_y = 0.5 * ((double)src->grid.N * src->grid.cs);
   if (int rc = enter(dst)) return rc;
-  if (int rc = align_ensure(dst, (size_t)n, 0)) return rc;
+  if (int rc = align_ensure(dst, (size_t)n)) return rc;
   // (the list is complete: tsd_surface_extract waited for it.  The half-cell offset: see the header.)
   hipLaunchKernelGGL(k_align_stage, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, dst->stream, (const double*)src->surface.d_xy,
                      dst->align.d_pts, n, 0.5 * src->grid.cs, reloc_reach(dst->grid) + (double)src->grid.N * src->grid.cs, dst->align.d_bad);
   TSD_HIP_CHECK(dst, hipGetLastError());
-  return align_run(dst, &p, dst->align.d_pts, n, true, src->grid.N, out);
+  return align_run(dst, &p, table, dst->align.d_pts, n, true, src->grid.N, out);
 }
 
 int tsd_debug_align_scores(tsd_ctx* ctx, uint32_t* scores, int cap)
 {
-  if (!ctx) return TSD_E_ARG;
-  const tsd_ctx::Align& al = ctx->align;
-  const long long n = (long long)al.nx * al.ny * al.ntheta;
-  const long long m = std::min<long long>(n, cap > 0 ? cap : 0);
-  if (m > 0 && scores) {
-    TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    TSD_HIP_CHECK(ctx, hipMemcpyAsync(scores, al.d_scores, sizeof(uint32_t) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return (int)n;
+  return ctx ? ctx->align.volume.copy_out(ctx, scores, cap) : TSD_E_ARG;
 }
 
 int tsd_debug_align_peaks(tsd_ctx* ctx, tsd_align_peak* records, int cap)
@@ -466,7 +399,7 @@ int tsd_debug_align_sums(tsd_ctx* ctx, const double* points_xy, int n, const dou
   if (!(v_cut > 0.0 && v_cut <= 1.0)) return set_error(ctx, TSD_E_ARG, "tsd_debug_align_sums: v_cut outside (0, 1]", hipSuccess);
   if (reloc_scan_in_flight(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_debug_align_sums: a scan of this context is in flight", hipSuccess);
   if (int rc = enter(ctx)) return rc;
-  if (int rc = align_ensure(ctx, (size_t)n, 0)) return rc;
+  if (int rc = align_ensure(ctx, (size_t)n)) return rc;
   tsd_ctx::Align& al = ctx->align;
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(al.d_pts, points_xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   AlignRefineArgs a{};

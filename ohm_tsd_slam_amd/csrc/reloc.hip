@@ -10,60 +10,33 @@
 //   k_reloc_peaks        strict local maxima over the 26 lattice neighbours (ties to the lower index), the 64 best of every workgroup
 //   k_reloc_peaks_merge  the K best of those, score descending, index ascending
 //
-// Shape of k_reloc_score (measured there).  A divergent gather like k_pdf_score: a workgroup = one position and a run of its
-// rotations, the points staged in LDS once, a wave per rotation, lanes over points, RELOC_BATCH look-ups per lane in flight with the tile
-// flag and the four cells of each issued together (ld_pinned / load_quad: not behind the flag test).  The rotations of one position sweep
-// the same discs of cells, so neighbouring waves hit the same lines.  The gate is one look-up per workgroup, issued ahead of the staging.
-// The device computes no sine: the rotation table comes from the host.  The look-up loop of a candidate (reloc_lane_score), the
-// constants of the shape and the launcher of the peak kernels are shared with the map alignment (align.hip) through reloc_shared.hpp.
+// Shape of the score kernels (reloc_shared.hpp's lattice_score; DESIGN.md 3.8, measured there).  A divergent gather like k_pdf_score: a
+// workgroup = one position and a run of its rotations, the points staged in LDS once, a wave per rotation, lanes over points,
+// RELOC_BATCH look-ups per lane in flight, the tile flag and the four cells of each issued together (tsd_device.hpp's lookup_issue).  The
+// rotations of one position sweep the same discs of cells, so neighbouring waves hit the same lines.  The device computes no sine: the
+// rotation table comes from the host.
+//
+// This file also holds the search's host side for both of its users (the map alignment, align.hip, is the other): the lattice's
+// refusals and rotation table, the score volume's operations, the one launch of score and peak kernels.
 #include "reloc_shared.hpp"
 
 namespace tsd {
 
+constexpr int RELOC_MIN_BLOCKS = 2048;     // a lattice of few positions is cut along its rotations until the launch has about this many workgroups
+constexpr size_t RELOC_KEEP_CANDIDATES = (size_t)1 << 23;   // a score volume up to this (32 MiB) stays with the context for the next search
+
+// the points as they are: every one, no pivot (x - 0.0 is x for every x)
 __global__ void __launch_bounds__(64 * RELOC_WAVES)
 k_reloc_score(GridDev g, RelocLattice L, const double* __restrict__ pts, int P, const double* __restrict__ cos_sin,
               uint32_t* __restrict__ scores, int rot_per_block)
 {
-  extern __shared__ __attribute__((aligned(16))) double s_pts[];      // [P] x | [P] y
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int ix = (int)blockIdx.x % L.nx, iy = (int)blockIdx.x / L.nx;
-  const double tx = L.x0 + (double)ix * L.step, ty = L.y0 + (double)iy * L.step;
-  // the gate's look-up first: its round trip runs beside the staging of the points
-  int gp = 0, glx = 0, gly = 0; double gdx = 0.0, gdy = 0.0;
-  const bool g_in = coord2cell(g, tx, ty, gp, glx, gly, gdx, gdy);
-  if (!g_in) { gp = 0; glx = 0; gly = 0; }
-  const uint8_t g_fl = ld_pinned(&g.flags[gp]);
-  const Quad gq = load_quad(g.tsd + (size_t)gp * TILE_STRIDE, glx, gly);
-  for (int i = threadIdx.x; i < P; i += 64 * RELOC_WAVES) { s_pts[i] = pts[2 * i]; s_pts[P + i] = pts[2 * i + 1]; }
-  const double gwx = fabs((tx - gdx) * g.inv_cs), gwy = fabs((ty - gdy) * g.inv_cs);
-  const double gv = gq.t00 * (1. - gwy) * (1. - gwx) + gq.t10 * gwy * (1. - gwx) + gq.t01 * (1. - gwy) * gwx + gq.t11 * gwy * gwx;
-  const bool gate = g_in && g_fl != 0 && !isnan(gv) && gv > 0.0;      // INTERP_SUCCESS with a value > 0 (the same for every thread)
-  const int k0 = (int)blockIdx.y * rot_per_block;
-  const int k1 = k0 + rot_per_block < L.ntheta ? k0 + rot_per_block : L.ntheta;
-  const size_t plane = (size_t)L.nx * (size_t)L.ny, at = (size_t)iy * (size_t)L.nx + (size_t)ix;
-  if (!gate) {
-    for (int k = k0 + (int)threadIdx.x; k < k1; k += 64 * RELOC_WAVES) scores[(size_t)k * plane + at] = 0u;
-    return;
-  }
-  __syncthreads();
-  for (int k = k0 + wave; k < k1; k += RELOC_WAVES) {                 // (whole waves: no barrier below)
-    const double c = cos_sin[2 * k], s = cos_sin[2 * k + 1];
-    unsigned int acc = reloc_lane_score(g, s_pts, P, lane, c, s, tx, ty);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += (unsigned int)__shfl_down((int)acc, off, 64);
-    if (lane == 0) scores[(size_t)k * plane + at] = acc;
-  }
+  lattice_score<true>(g, L, pts, P, 1, 0.0, 0.0, cos_sin, scores, rot_per_block);
 }
 
-// ---- peaks: a stream of 64-bit keys (score << 32 | ~idx: larger = better score, then lower index), the best PK_KEEP kept in LDS ----------
+// ---- peaks: a stream of 64-bit keys (reloc_shared.hpp's peak_key), the best PK_KEEP kept in LDS -------------------------------------------
 constexpr int PK_THREADS = 256;
 constexpr int PK_CAP = 1024;               // keys the LDS buffer holds (a power of two: bitonic sort); a round adds at most PK_THREADS
 constexpr int RELOC_PEAK_GRID = 512;       // workgroups of k_reloc_peaks at most; they stride over the volume
-
-__device__ __forceinline__ unsigned long long peak_key(unsigned int score, unsigned int idx)
-{
-  return ((unsigned long long)score << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
-}
 
 // all PK_THREADS threads; descending
 __device__ void pk_sort(unsigned long long* s_keys)
@@ -164,17 +137,37 @@ k_reloc_peaks_merge(const unsigned long long* __restrict__ wg_keys, int n_keys, 
 void reloc_free(tsd_ctx* ctx)
 {
   tsd_ctx::Reloc& r = ctx->reloc;
-  hipFree(r.d_points); hipFree(r.d_cos_sin); hipFree(r.d_scores); hipFree(r.d_keys);
+  hipFree(r.d_points); hipFree(r.d_cos_sin); hipFree(r.volume.d); hipFree(r.d_keys);
   if (r.h_keys) hipHostFree(r.h_keys);
   r = tsd_ctx::Reloc{};
 }
 
-static void reloc_drop_volume(tsd_ctx::Reloc& r)
+void ScoreVolume::drop() { hipFree(d); *this = ScoreVolume{}; }
+ScoreVolume::GiveBack::~GiveBack() { if (v.cap > RELOC_KEEP_CANDIDATES) v.drop(); }
+
+int ScoreVolume::ensure(tsd_ctx* ctx, size_t candidates)
 {
-  hipFree(r.d_scores); r.d_scores = nullptr; r.score_cap = 0; r.nx = r.ny = r.ntheta = 0;
+  if (candidates > cap) {
+    drop();
+    TSD_HIP_CHECK(ctx, hipMalloc(&d, sizeof(uint32_t) * candidates));
+    cap = candidates;
+  }
+  return TSD_OK;
 }
 
-int reloc_ensure(tsd_ctx* ctx, size_t rotations, size_t candidates)
+int ScoreVolume::copy_out(tsd_ctx* ctx, uint32_t* scores, int room) const
+{
+  const long long n = (long long)nx * ny * ntheta;
+  const long long m = std::min<long long>(n, room > 0 ? room : 0);
+  if (m > 0 && scores) {
+    TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    TSD_HIP_CHECK(ctx, hipMemcpyAsync(scores, d, sizeof(uint32_t) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return (int)n;
+}
+
+int reloc_ensure(tsd_ctx* ctx, size_t rotations)
 {
   tsd_ctx::Reloc& r = ctx->reloc;
   if (!r.d_points) TSD_HIP_CHECK(ctx, hipMalloc(&r.d_points, sizeof(double) * 2 * TSD_MAX_ICP_POINTS));
@@ -185,16 +178,11 @@ int reloc_ensure(tsd_ctx* ctx, size_t rotations, size_t candidates)
     TSD_HIP_CHECK(ctx, hipMalloc(&r.d_cos_sin, sizeof(double) * 2 * rotations));
     r.rot_cap = rotations;
   }
-  if (candidates > r.score_cap) {
-    reloc_drop_volume(r);
-    TSD_HIP_CHECK(ctx, hipMalloc(&r.d_scores, sizeof(uint32_t) * candidates));
-    r.score_cap = candidates;
-  }
   return TSD_OK;
 }
 
 // the two peak kernels on the context's stream over a volume on the device; the merged keys and their count arrive in r.h_keys
-int launch_reloc_peaks(tsd_ctx* ctx, const uint32_t* d_scores, int nx, int ny, int nt, int wraps, int K)
+static int launch_reloc_peaks(tsd_ctx* ctx, const uint32_t* d_scores, int nx, int ny, int nt, int wraps, int K)
 {
   tsd_ctx::Reloc& r = ctx->reloc;
   const long long n = (long long)nx * ny * nt;
@@ -209,16 +197,72 @@ int launch_reloc_peaks(tsd_ctx* ctx, const uint32_t* d_scores, int nx, int ny, i
 
 const unsigned long long* reloc_merged_keys(const tsd_ctx* ctx) { return ctx->reloc.d_keys + (size_t)RELOC_PEAK_GRID * PK_KEEP; }
 
-bool reloc_lattice_ok(int nx, int ny, int nt) { return nx >= 1 && ny >= 1 && nt >= 1; }
-bool reloc_lattice_fits(int nx, int ny, int nt) { return (long long)nx * ny <= TSD_RELOC_MAX_CANDIDATES && (long long)nx * ny * nt <= TSD_RELOC_MAX_CANDIDATES; }
+// how a lattice of nx * ny positions and nt rotations is cut into workgroups of RELOC_WAVES waves: (rotations per workgroup, grid.y)
+static void reloc_cut(int nx, int ny, int nt, int& rot_per_block, int& blocks_y)
+{
+  const long long positions = (long long)nx * ny;
+  long long cuts = (RELOC_MIN_BLOCKS + positions - 1) / positions;                 // along the rotations, whole rounds of RELOC_WAVES at least
+  cuts = std::max<long long>(1, std::min<long long>(cuts, (nt + RELOC_WAVES - 1) / RELOC_WAVES));
+  cuts = std::min<long long>(cuts, 65535);
+  rot_per_block = (int)((nt + cuts - 1) / cuts);
+  blocks_y = (nt + rot_per_block - 1) / rot_per_block;
+}
 
-// Every lattice position within TSD_RELOC_MAX_REACH grid widths of the grid, every scan point within as many of the sensor: a carried
-// point then lies within a dozen grid widths, (int)floor(x / cellSize) of coord2cell is defined and equals the restatement's int64.
+int launch_lattice_search(tsd_ctx* ctx, ScoreVolume& vol, const LatticeSpec& lat, bool gate, const double* d_pts, int P, int stride,
+                          double pvx, double pvy)
+{
+  const RelocLattice& L = lat.L;
+  int rot_per_block = 0, blocks_y = 0;
+  reloc_cut(L.nx, L.ny, L.ntheta, rot_per_block, blocks_y);
+  const dim3 grid((unsigned)((long long)L.nx * L.ny), (unsigned)blocks_y), block(64 * RELOC_WAVES);
+  const size_t lds = sizeof(double) * 2 * (size_t)P;                    // the staged points
+  const double* table = ctx->reloc.d_cos_sin;
+  if (gate) hipLaunchKernelGGL(k_reloc_score, grid, block, lds, ctx->stream, ctx->grid, L, d_pts, P, table, vol.d, rot_per_block);
+  else hipLaunchKernelGGL(k_align_score, grid, block, lds, ctx->stream, ctx->grid, L, d_pts, P, stride, pvx, pvy, table, vol.d, rot_per_block);
+  vol.nx = L.nx; vol.ny = L.ny; vol.ntheta = L.ntheta;
+  return launch_reloc_peaks(ctx, vol.d, L.nx, L.ny, L.ntheta, lat.theta_wraps, lat.K);
+}
+
+static bool reloc_lattice_ok(int nx, int ny, int nt) { return nx >= 1 && ny >= 1 && nt >= 1; }
+static bool reloc_lattice_fits(int nx, int ny, int nt) { return (long long)nx * ny <= TSD_RELOC_MAX_CANDIDATES && (long long)nx * ny * nt <= TSD_RELOC_MAX_CANDIDATES; }
+
 double reloc_reach(const GridDev& g) { return (double)TSD_RELOC_MAX_REACH * ((double)g.N * g.cs); }
-bool reloc_lattice_near(const GridDev& g, double a0, int n, double step)
+static bool reloc_lattice_near(const GridDev& g, double a0, int n, double step)
 {
   const double a1 = a0 + (double)(n - 1) * step;
   return a0 >= -reloc_reach(g) && a1 <= (double)g.N * g.cs + reloc_reach(g);
+}
+
+int lattice_check(tsd_ctx* ctx, const LatticeSpec& lat, const char* who)
+{
+  const RelocLattice& L = lat.L;
+  if (!reloc_lattice_ok(L.nx, L.ny, L.ntheta)) return refuse(ctx, who, TSD_E_ARG, "nx, ny, ntheta must be >= 1");
+  if (!std::isfinite(L.x0) || !std::isfinite(L.y0) || !std::isfinite(L.step) || !(L.step > 0.0))
+    return refuse(ctx, who, TSD_E_ARG, "x0, y0 finite and step_xy > 0");
+  if (!reloc_lattice_fits(L.nx, L.ny, L.ntheta)) return refuse(ctx, who, TSD_E_CAPACITY, "nx * ny * ntheta > TSD_RELOC_MAX_CANDIDATES");
+  if (!reloc_lattice_near(ctx->grid, L.x0, L.nx, L.step) || !reloc_lattice_near(ctx->grid, L.y0, L.ny, L.step))
+    return refuse(ctx, who, TSD_E_ARG, "the lattice reaches further than TSD_RELOC_MAX_REACH grid widths from the grid");
+  if (!lat.cos_sin && (!std::isfinite(lat.theta0) || !std::isfinite(lat.dtheta) || lat.dtheta == 0.0))
+    return refuse(ctx, who, TSD_E_ARG, "without a cos_sin table, theta0 and a non-zero dtheta are needed");
+  return TSD_OK;
+}
+
+bool lattice_table(const LatticeSpec& lat, std::vector<double>& table)
+{
+  table.resize((size_t)2 * lat.L.ntheta);
+  for (int k = 0; k < lat.L.ntheta; k++) {
+    if (lat.cos_sin) { table[2 * k] = lat.cos_sin[2 * k]; table[2 * k + 1] = lat.cos_sin[2 * k + 1]; }
+    else { const double th = lat.theta0 + (double)k * lat.dtheta; table[2 * k] = std::cos(th); table[2 * k + 1] = std::sin(th); }
+    if (!std::isfinite(table[2 * k]) || !std::isfinite(table[2 * k + 1])) return false;
+  }
+  return true;
+}
+
+bool points_in_reach(const GridDev& g, const double* points_xy, int n)
+{
+  for (int i = 0; i < 2 * n; i++)
+    if (!(std::fabs(points_xy[i]) <= reloc_reach(g))) return false;      // (NaN fails too)
+  return true;
 }
 
 bool reloc_scan_in_flight(const tsd_ctx* ctx)
@@ -245,64 +289,37 @@ int tsd_relocalize(tsd_ctx* ctx, const tsd_reloc_params* prm, const double* poin
     return set_error(ctx, TSD_E_CAPACITY, "tsd_relocalize: beams out of range for the registration", hipSuccess);
   if (prm->K < 1 || prm->K > TSD_RELOC_MAX_PEAKS) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: K outside 1 .. TSD_RELOC_MAX_PEAKS", hipSuccess);
   if (prm->min_pairs < 0) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: min_pairs < 0", hipSuccess);
-  if (!reloc_lattice_ok(prm->nx, prm->ny, prm->ntheta)) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: nx, ny, ntheta must be >= 1", hipSuccess);
-  if (!std::isfinite(prm->x0) || !std::isfinite(prm->y0) || !std::isfinite(prm->step_xy) || !(prm->step_xy > 0.0))
-    return set_error(ctx, TSD_E_ARG, "tsd_relocalize: x0, y0 finite and step_xy > 0", hipSuccess);
-  if (!reloc_lattice_fits(prm->nx, prm->ny, prm->ntheta))
-    return set_error(ctx, TSD_E_CAPACITY, "tsd_relocalize: nx * ny * ntheta > TSD_RELOC_MAX_CANDIDATES", hipSuccess);
-  if (!reloc_lattice_near(ctx->grid, prm->x0, prm->nx, prm->step_xy) || !reloc_lattice_near(ctx->grid, prm->y0, prm->ny, prm->step_xy))
-    return set_error(ctx, TSD_E_ARG, "tsd_relocalize: the lattice reaches further than TSD_RELOC_MAX_REACH grid widths from the grid", hipSuccess);
-  if (!prm->cos_sin && (!std::isfinite(prm->theta0) || !std::isfinite(prm->dtheta) || prm->dtheta == 0.0))
-    return set_error(ctx, TSD_E_ARG, "tsd_relocalize: without a cos_sin table, theta0 and a non-zero dtheta are needed", hipSuccess);
-  for (int i = 0; i < 2 * P; i++)
-    if (!(std::fabs(points_xy[i]) <= reloc_reach(ctx->grid)))   // (NaN fails too)
-      return set_error(ctx, TSD_E_ARG, "tsd_relocalize: a scan point is not finite or further than TSD_RELOC_MAX_REACH grid widths from the sensor", hipSuccess);
-  const int nx = prm->nx, ny = prm->ny, nt = prm->ntheta;
-  std::vector<double> table((size_t)2 * nt);
-  for (int k = 0; k < nt; k++) {
-    if (prm->cos_sin) { table[2 * k] = prm->cos_sin[2 * k]; table[2 * k + 1] = prm->cos_sin[2 * k + 1]; }
-    else { const double th = prm->theta0 + (double)k * prm->dtheta; table[2 * k] = std::cos(th); table[2 * k + 1] = std::sin(th); }
-    if (!std::isfinite(table[2 * k]) || !std::isfinite(table[2 * k + 1])) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: cos_sin is not finite", hipSuccess);
-  }
+  const LatticeSpec lat = lattice_spec(*prm);
+  if (int rc = lattice_check(ctx, lat, "tsd_relocalize")) return rc;
+  if (!points_in_reach(ctx->grid, points_xy, P))
+    return set_error(ctx, TSD_E_ARG, "tsd_relocalize: a scan point is not finite or further than TSD_RELOC_MAX_REACH grid widths from the sensor", hipSuccess);
+  std::vector<double> table;
+  if (!lattice_table(lat, table)) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: cos_sin is not finite", hipSuccess);
   if (reloc_scan_in_flight(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_relocalize: a scan of this context is in flight (collect it first)", hipSuccess);
   // ---- the arguments stand: from here on the context changes ----
   if (int rc = enter(ctx)) return rc;
   ctx->ledger.outputs_overwritten();      // (the refinement rewrites the context's ray-cast outputs, like tsd_localize)
-  const size_t n = (size_t)nx * (size_t)ny * (size_t)nt;
-  if (int rc = reloc_ensure(ctx, (size_t)nt, n)) return rc;
   tsd_ctx::Reloc& r = ctx->reloc;
-  // a volume beyond RELOC_KEEP_CANDIDATES is given back when the call ends, whichever way it ends
-  struct VolumeGuard { tsd_ctx::Reloc& r; ~VolumeGuard() { if (r.score_cap > RELOC_KEEP_CANDIDATES) reloc_drop_volume(r); } } volume_guard{r};
+  ScoreVolume::GiveBack give_back{r.volume};
+  if (int rc = reloc_ensure(ctx, (size_t)lat.L.ntheta)) return rc;
+  if (int rc = r.volume.ensure(ctx, (size_t)lat.L.nx * (size_t)lat.L.ny * (size_t)lat.L.ntheta)) return rc;
   std::memset(result, 0, sizeof(*result));
-  const bool timed = ctx->profile;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  auto drop_events = [&]() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); };
-  if (timed)
-    for (hipEvent_t& e : ev) {
-      const hipError_t ee = hipEventCreate(&e);
-      if (ee != hipSuccess) { e = nullptr; drop_events(); return set_error(ctx, TSD_E_HIP, "tsd_relocalize: hipEventCreate", ee); }
-    }
+  StageEvents stages;                     // 0 .. 1 the search, 2 .. 3 the refinement
+  if (int rc = stages.open(ctx, 4, "tsd_relocalize")) return rc;
 
   // ---- search ----
   // (the sources stay valid until the wait behind the search)
   hipError_t e = hipMemcpyAsync(r.d_points, points_xy, sizeof(double) * 2 * (size_t)P, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(r.d_cos_sin, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) { drop_events(); return set_error(ctx, TSD_E_HIP, "tsd_relocalize: copy of the points", e); }
-  if (timed) hipEventRecord(ev[0], ctx->stream);
-  const long long positions = (long long)nx * ny;
-  int rot_per_block = 0, blocks_y = 0;
-  reloc_cut(nx, ny, nt, rot_per_block, blocks_y);
-  const RelocLattice L{prm->x0, prm->y0, prm->step_xy, nx, ny, nt};
-  hipLaunchKernelGGL(k_reloc_score, dim3((unsigned)positions, (unsigned)blocks_y), dim3(64 * RELOC_WAVES), sizeof(double) * 2 * (size_t)P, ctx->stream,
-                     ctx->grid, L, (const double*)r.d_points, P, (const double*)r.d_cos_sin, r.d_scores, rot_per_block);
-  r.nx = nx; r.ny = ny; r.ntheta = nt;
-  int rc = launch_reloc_peaks(ctx, r.d_scores, nx, ny, nt, prm->theta_wraps ? 1 : 0, prm->K);
-  if (timed) hipEventRecord(ev[1], ctx->stream);
+  if (e != hipSuccess) return set_error(ctx, TSD_E_HIP, "tsd_relocalize: copy of the points", e);
+  stages.record(0);
+  int rc = launch_lattice_search(ctx, r.volume, lat, true, r.d_points, P, 1, 0.0, 0.0);
+  stages.record(1);
   if (rc == TSD_OK && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = set_error(ctx, TSD_E_HIP, "tsd_relocalize: search", e);
-  if (rc != TSD_OK) { drop_events(); return rc; }
+  if (rc != TSD_OK) return rc;
   const int n_peaks = (int)r.h_keys[PK_KEEP];
-  unsigned int pk_idx[TSD_RELOC_MAX_PEAKS], pk_score[TSD_RELOC_MAX_PEAKS];
-  for (int j = 0; j < n_peaks; j++) { pk_score[j] = (unsigned int)(r.h_keys[j] >> 32); pk_idx[j] = 0xFFFFFFFFu - (unsigned int)(r.h_keys[j] & 0xFFFFFFFFull); }
+  Peak pk[TSD_RELOC_MAX_PEAKS];
+  for (int j = 0; j < n_peaks; j++) pk[j] = peak_of(r.h_keys[j]);
 
   // ---- refinement: the unfused localisation from every peak, in the peaks' order; strictly more pairs win (IcpMultiInitIterator.cpp:26-38) ----
   const double nan = std::nan("");
@@ -313,12 +330,11 @@ int tsd_relocalize(tsd_ctx* ctx, const tsd_reloc_params* prm, const double* poin
   const double cs = ctx->grid.cs;
   std::vector<double> rays_world(2 * nb);
   int best = -1; tsd_icp_result best_icp{}; double best_pose[9] = {0};
-  if (timed) hipEventRecord(ev[2], ctx->stream);
+  stages.record(2);
   for (int j = 0; j < n_peaks; j++) {
-    const int k = (int)(pk_idx[j] / (unsigned int)(nx * ny)), rem = (int)(pk_idx[j] % (unsigned int)(nx * ny));
-    const int iy = rem / nx, ix = rem % nx;
-    const double c = table[2 * k], s = table[2 * k + 1], ms = -s;
-    const double pose[9] = {c, ms, prm->x0 + (double)ix * prm->step_xy, s, c, prm->y0 + (double)iy * prm->step_xy, 0.0, 0.0, 1.0};
+    const LatticePose at = lattice_pose(lat.L, table.data(), pk[j].idx);
+    const double c = at.c, s = at.s, ms = -s;
+    const double pose[9] = {c, ms, at.x, s, c, at.y, 0.0, 0.0, 1.0};
     for (size_t i = 0; i < nb; i++) {
       const double x = rays_local_2xB[i], y = rays_local_2xB[nb + i];
       double wx = 0.0, wy = 0.0;                               // Sensor::transform (Sensor.cpp:50-55)
@@ -333,18 +349,12 @@ int tsd_relocalize(tsd_ctx* ctx, const tsd_reloc_params* prm, const double* poin
     result->n_refined++;
     if (best < 0 || ir.pairs > best_icp.pairs) { best = j; best_icp = ir; std::memcpy(best_pose, pose, sizeof(pose)); }
   }
-  if (timed) {
-    hipEventRecord(ev[3], ctx->stream);
-    float ms = 0.f;
-    if (hipEventSynchronize(ev[3]) == hipSuccess) {
-      if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) result->search_ms = (double)ms;
-      if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) result->refine_ms = (double)ms;
-    }
-  }
-  drop_events();
+  stages.record(3);
+  stages.measure(0, 1, result->search_ms);
+  stages.measure(2, 3, result->refine_ms);
   if (rc != TSD_OK) return rc;
   if (best >= 0) {
-    result->winner_idx = (int32_t)pk_idx[best]; result->winner_score = pk_score[best];
+    result->winner_idx = (int32_t)pk[best].idx; result->winner_score = pk[best].score;
     result->coarse_x = best_pose[2]; result->coarse_y = best_pose[5]; result->coarse_cos = best_pose[0]; result->coarse_sin = best_pose[3];
     result->icp = best_icp;
     result->found = best_icp.pairs >= prm->min_pairs ? 1 : 0;
@@ -361,16 +371,7 @@ int tsd_relocalize(tsd_ctx* ctx, const tsd_reloc_params* prm, const double* poin
 
 int tsd_debug_reloc_scores(tsd_ctx* ctx, uint32_t* scores, int cap)
 {
-  if (!ctx) return TSD_E_ARG;
-  const tsd_ctx::Reloc& r = ctx->reloc;
-  const long long n = (long long)r.nx * r.ny * r.ntheta;
-  const long long m = std::min<long long>(n, cap > 0 ? cap : 0);
-  if (m > 0 && scores) {
-    TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    TSD_HIP_CHECK(ctx, hipMemcpyAsync(scores, r.d_scores, sizeof(uint32_t) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    TSD_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return (int)n;
+  return ctx ? ctx->reloc.volume.copy_out(ctx, scores, cap) : TSD_E_ARG;
 }
 
 int tsd_debug_reloc_peaks(tsd_ctx* ctx, const uint32_t* scores, int nx, int ny, int ntheta, int theta_wraps, int K,
@@ -381,7 +382,7 @@ int tsd_debug_reloc_peaks(tsd_ctx* ctx, const uint32_t* scores, int nx, int ny, 
   if (!reloc_lattice_fits(nx, ny, ntheta)) return set_error(ctx, TSD_E_CAPACITY, "tsd_debug_reloc_peaks: volume > TSD_RELOC_MAX_CANDIDATES", hipSuccess);
   if (reloc_scan_in_flight(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_debug_reloc_peaks: a scan of this context is in flight (collect it first)", hipSuccess);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (int rc = reloc_ensure(ctx, 0, 0)) return rc;
+  if (int rc = reloc_ensure(ctx, 0)) return rc;
   const size_t n = (size_t)nx * (size_t)ny * (size_t)ntheta;
   uint32_t* d_vol = nullptr;
   TSD_HIP_CHECK(ctx, hipMalloc(&d_vol, sizeof(uint32_t) * n));
@@ -395,8 +396,8 @@ int tsd_debug_reloc_peaks(tsd_ctx* ctx, const uint32_t* scores, int nx, int ny, 
   const tsd_ctx::Reloc& r = ctx->reloc;
   *n_out = (int)r.h_keys[PK_KEEP];
   for (int j = 0; j < *n_out; j++) {
-    score_out[j] = (uint32_t)(r.h_keys[j] >> 32);
-    idx_out[j] = (int32_t)(0xFFFFFFFFu - (unsigned int)(r.h_keys[j] & 0xFFFFFFFFull));
+    const Peak pk = peak_of(r.h_keys[j]);
+    score_out[j] = pk.score; idx_out[j] = (int32_t)pk.idx;
   }
   return TSD_OK;
 }

@@ -178,6 +178,19 @@ struct KernelTimer {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// The score volume of a pose-lattice search (reloc.hip): one uint32 per candidate of the last search.  Relocalisation and alignment
+// keep one each.  Up to RELOC_KEEP_CANDIDATES it stays with the context for the next search and for the debug entry points.
+struct ScoreVolume {
+  uint32_t* d = nullptr; size_t cap = 0;   // [cap]
+  int nx = 0, ny = 0, ntheta = 0;          // shape of the last search (0: none)
+  int ensure(tsd_ctx* ctx, size_t candidates);
+  void drop();
+  // tsd_debug_*_scores: copies min(n, room) scores to the host, returns n = nx * ny * ntheta
+  int copy_out(tsd_ctx* ctx, uint32_t* scores, int room) const;
+  // a volume beyond RELOC_KEEP_CANDIDATES is given back when the call that holds this ends, whichever way it ends
+  struct GiveBack { ScoreVolume& v; ~GiveBack(); };
+};
+
 }  // namespace tsd
 
 struct tsd_sensor;
@@ -292,10 +305,9 @@ struct tsd_ctx {
   struct Reloc {
     double* d_points = nullptr;              // [2 * TSD_MAX_ICP_POINTS] x0 y0 x1 y1 ..
     double* d_cos_sin = nullptr; size_t rot_cap = 0;
-    uint32_t* d_scores = nullptr; size_t score_cap = 0;
+    tsd::ScoreVolume volume;
     unsigned long long* d_keys = nullptr;    // [(RELOC_PEAK_GRID + 1) * 64 + 1]: per-workgroup keys, merged keys, count
     unsigned long long* h_keys = nullptr;    // pinned [64 + 1]
-    int nx = 0, ny = 0, ntheta = 0;          // shape of the volume in d_scores (0: no search yet)
   } reloc;
 
   // the surface list (surface.hip: tsd_surface_extract / _fetch / _dev): per-window-tile counts and offsets and the per-1024-tile bases
@@ -313,8 +325,7 @@ struct tsd_ctx {
   // rotation table and the peak keys are tsd_ctx::reloc's
   struct Align {
     double* d_pts = nullptr; size_t pts_cap = 0;     // [2 * pts_cap]
-    uint32_t* d_scores = nullptr; size_t score_cap = 0;
-    int nx = 0, ny = 0, ntheta = 0;                  // shape of the volume in d_scores (0: none)
+    tsd::ScoreVolume volume;
     tsd_align_peak* d_rec = nullptr;                 // [TSD_RELOC_MAX_PEAKS]
     tsd_align_peak* h_rec = nullptr;                 // pinned [TSD_RELOC_MAX_PEAKS]
     unsigned int* d_bad = nullptr; unsigned int* h_bad = nullptr;   // coordinates refused by the staging kernel (h_bad pinned)

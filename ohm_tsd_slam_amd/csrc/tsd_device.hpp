@@ -193,29 +193,43 @@ __device__ __forceinline__ Quad load_quad(const tsd_cell_t* __restrict__ tile, i
   return q;
 }
 
+// interpolate_bilinear in two steps, for the kernels that have several look-ups in flight: lookup_issue requests the tile flag and the
+// four cells together (not behind the flag test; outside the grid it reads tile 0, whose storage exists like every tile's -- only
+// `flags` says whether a tile holds data; so does a lane that is not `live`, one without a point of its own, and its look-up fails),
+// lookup_value, later, gives the value in interpolate_bilinear's expression and whether the look-up is an INTERP_SUCCESS (v is NaN
+// otherwise).  The expression stays behind the test of inside / flag: waves whose look-ups all fail skip it.
+struct Lookup { bool inside; uint8_t flag; Quad q; double wx, wy; };
+__device__ __forceinline__ Lookup lookup_issue(const GridDev& g, double x, double y, bool live = true)
+{
+  Lookup l;
+  int p = 0, lx = 0, ly = 0; double dx = 0.0, dy = 0.0;
+  l.inside = coord2cell(g, x, y, p, lx, ly, dx, dy) && live;
+  if (!l.inside) { p = 0; lx = 0; ly = 0; }
+  l.flag = ld_pinned(&g.flags[p]);
+  l.q = load_quad(g.tsd + (size_t)p * TILE_STRIDE, lx, ly);
+  l.wx = fabs((x - dx) * g.inv_cs); l.wy = fabs((y - dy) * g.inv_cs);
+  return l;
+}
+__device__ __forceinline__ bool lookup_value(const Lookup& l, double& v)
+{
+  v = __builtin_nan("");
+  if (!l.inside || l.flag == 0) return false;
+  v = l.q.t00 * (1. - l.wy) * (1. - l.wx) + l.q.t10 * l.wy * (1. - l.wx) + l.q.t01 * (1. - l.wy) * l.wx + l.q.t11 * l.wy * l.wx;
+  return !isnan(v);
+}
+
 // TsdGrid::interpolateNormal (TsdGrid.cpp:517-546) + norm2 (mathbase.h:211-218) on ONE lane: the four bilinear look-ups at
-// (x+cs,y) (x-cs,y) (x,y+cs) (x,y-cs) with their 4 flag reads and 16 cell reads requested together (the tile storage exists for every
-// tile; only `flags` says whether it holds data), each look-up in the expressions of interpolate_bilinear and of the ray cast's four
-// lanes (raycast_kernels.hip).  False where a look-up fails (outside the grid, tile not initialised, NaN): (nx, ny) is then (0, 0).
+// (x+cs,y) (x-cs,y) (x,y+cs) (x,y-cs) with their 4 flag reads and 16 cell reads requested together.  False where a look-up fails
+// (outside the grid, tile not initialised, NaN): (nx, ny) is then (0, 0).
 __device__ __forceinline__ bool interpolate_normal(const GridDev& g, double x, double y, double& nx, double& ny)
 {
   const double sx[4] = {x + g.cs, x - g.cs, x, x}, sy[4] = {y, y, y + g.cs, y - g.cs};
-  bool in[4]; int lx[4], ly[4]; double dx[4], dy[4]; uint8_t f[4]; Quad q[4];
+  Lookup l[4];
 #pragma unroll
-  for (int k = 0; k < 4; k++) {
-    int p = 0;
-    in[k] = coord2cell(g, sx[k], sy[k], p, lx[k], ly[k], dx[k], dy[k]);
-    if (!in[k]) { p = 0; lx[k] = 0; ly[k] = 0; }
-    f[k] = ld_pinned(&g.flags[p]);
-    q[k] = load_quad(g.tsd + (size_t)p * TILE_STRIDE, lx[k], ly[k]);
-  }
+  for (int k = 0; k < 4; k++) l[k] = lookup_issue(g, sx[k], sy[k]);
   double v[4]; bool ok = true;
 #pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const double wx = fabs((sx[k] - dx[k]) * g.inv_cs), wy = fabs((sy[k] - dy[k]) * g.inv_cs);
-    v[k] = q[k].t00 * (1. - wy) * (1. - wx) + q[k].t10 * wy * (1. - wx) + q[k].t01 * (1. - wy) * wx + q[k].t11 * wy * wx;
-    ok = ok && in[k] && f[k] != 0 && !isnan(v[k]);
-  }
+  for (int k = 0; k < 4; k++) ok = lookup_value(l[k], v[k]) && ok;
   nx = 0.0; ny = 0.0;
   if (!ok) return false;
   nx = v[0] - v[1]; ny = v[2] - v[3];

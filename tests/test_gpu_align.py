@@ -59,7 +59,7 @@ def test_scores_equal_the_restatement():
     assert np.array_equal(g.debug_align_scores().reshape(A.NTHETA, A.NXY, A.NXY), want)
 
 
-SCORE_EDGES = ["nx1", "ntheta1", "n1", "n63", "n64", "n65", "n2048", "n2049", "n4097", "border"]
+SCORE_EDGES = ["nx1", "ntheta1", "n1", "n63", "n64", "n65", "n2048", "n2049", "n4097", "border", "share_rotations", "share_single_position"]
 
 
 @pytest.mark.parametrize("case", SCORE_EDGES)
@@ -78,6 +78,10 @@ def test_scores_on_edge_shapes(case):
         # the pivot: points are carried over the border, into tiles no scan initialised, onto NaN cells and into the halo strip
         lat = dict(x0=-2.0, y0=-2.0, step_xy=1.0, nx=30, ny=30); table = sc.table[::9]
         pts = np.concatenate([sc.points, (sc.points - np.array(pivot)) * 1.7 + np.array(pivot)])[:2048]
+    elif case == "share_rotations":
+        lat.update(nx=5, ny=3); table = sc.table[:7]           # 15 positions, 7 rotations: workgroups of 4 and of 3 rotations
+    elif case == "share_single_position":
+        lat.update(nx=1, ny=1, x0=sc.x0 + 11 * A.STEP, y0=sc.y0 + 12 * A.STEP); table = sc.table[:13]     # 13 rotations over 4 workgroups
     else:
         n = int(case[1:])
         # (beyond the list's length: a synthetic list made by repeating points)
@@ -105,6 +109,65 @@ def test_scores_on_edge_shapes(case):
     idx, sco = R.peaks(want, want.shape, False, 4)
     recs = g.debug_align_peaks()
     assert [r["idx"] for r in recs] == idx.tolist() and [r["score"] for r in recs] == sco.tolist()
+
+
+# --------------------------------------------------------------------------------------- the two searches' score volumes
+def _both_searches():
+    """one context that holds map A (the "self" scene: the alignment's dst and, the same 12 scans, the relocalisation's map) with a
+    relocalisation and an alignment over small lattices on it: (grid, reloc(lattice, table) -> restated volume,
+    align(lattice, table) -> restated volume)"""
+    sa, sr = A.scene("self"), R.scene(360)
+    g = upload(sa, sa.dump_b)
+    icp = g.icp_params(R.ICP["iterations"], R.ICP["dist_max"], R.ICP["dist_min"])
+
+    def reloc(lat, table, points=sr.points, restate=True):
+        g.relocalize(points, sr.rays_local, sr.data, sr.mask, R.MIN_RANGE, R.MAX_RANGE, icp, cos_sin=table, ntheta=len(table), K=1, **lat)
+        if restate:
+            want, gate = R.scores(sa.view_b, points, lat["x0"], lat["y0"], lat["step_xy"], lat["nx"], lat["ny"], table)
+            assert gate.any() and want.any()
+            return want.reshape(-1)
+
+    def align(lat, table, points=sa.points, restate=True):
+        g.align_points(points, pivot=sa.pivot, cos_sin=table, ntheta=len(table), K=1, iterations=0, **lat)
+        if restate:
+            want = A.scores(sa.view_b, points, sa.pivot, lat["x0"], lat["y0"], lat["step_xy"], lat["nx"], lat["ny"], table)
+            assert want.any()
+            return want.reshape(-1)
+    return g, sa, sr, reloc, align
+
+
+def test_the_two_score_volumes_are_independent():
+    """a relocalisation leaves the alignment's volume as it was and the other way round; each search's own is the restatement's"""
+    g, sa, sr, reloc, align = _both_searches()
+    want_r = reloc(dict(x0=sr.x0 + 10 * R.STEP, y0=sr.y0 + 10 * R.STEP, step_xy=R.STEP, nx=3, ny=3), sr.table[10:14])
+    assert np.array_equal(g.debug_reloc_scores(), want_r) and g.debug_align_scores().size == 0
+    want_a = align(dict(x0=sa.x0 + 9 * A.STEP, y0=sa.y0 + 10 * A.STEP, step_xy=A.STEP, nx=4, ny=2), sa.table[11:14])
+    assert np.array_equal(g.debug_align_scores(), want_a) and np.array_equal(g.debug_reloc_scores(), want_r)
+    want_r = reloc(dict(x0=sr.x0 + 9 * R.STEP, y0=sr.y0 + 11 * R.STEP, step_xy=R.STEP, nx=2, ny=3), sr.table[9:14])
+    assert np.array_equal(g.debug_reloc_scores(), want_r) and np.array_equal(g.debug_align_scores(), want_a)
+    assert want_r.size == 30 and want_a.size == 24
+    g.close()
+
+
+@pytest.mark.parametrize("search", ["reloc", "align"])
+def test_a_volume_beyond_2_23_candidates_is_given_back_and_a_small_one_kept(search):
+    """512 x 512 x 33 candidates (just over 2^23) over the whole grid: nothing of it stays with the context; the small search that
+    follows is kept, and the other search's volume is not touched by either"""
+    g, sa, sr, reloc, align = _both_searches()
+    small_r = dict(x0=sr.x0 + 10 * R.STEP, y0=sr.y0 + 10 * R.STEP, step_xy=R.STEP, nx=3, ny=3)
+    small_a = dict(x0=sa.x0 + 9 * A.STEP, y0=sa.y0 + 10 * A.STEP, step_xy=A.STEP, nx=4, ny=2)
+    want_r, want_a = reloc(small_r, sr.table[10:14]), align(small_a, sa.table[11:14])
+    big = dict(x0=0.5 * sa.cs, y0=0.5 * sa.cs, step_xy=sa.cs, nx=512, ny=512)
+    assert 512 * 512 * 33 > 1 << 23
+    if search == "reloc":
+        reloc(big, sr.table[:33], restate=False)
+        assert g.debug_reloc_scores().size == 0 and np.array_equal(g.debug_align_scores(), want_a)
+        assert np.array_equal(reloc(small_r, sr.table[10:14]), g.debug_reloc_scores())
+    else:
+        align(big, sa.table[:33], points=sa.points[::len(sa.points) // 64][:64], restate=False)
+        assert g.debug_align_scores().size == 0 and np.array_equal(g.debug_reloc_scores(), want_r)
+        assert np.array_equal(align(small_a, sa.table[11:14]), g.debug_align_scores())
+    g.close()
 
 
 # -------------------------------------------------------------------------------------------------------------------- sums
@@ -270,24 +333,37 @@ def test_refusals_allocate_nothing_and_a_good_call_follows():
     ref, other = grids("diff")
     d0 = g.digest()
 
-    def refused(code, **kw):
+    def refused(code, text, **kw):
         with pytest.raises(capi.TsdError):
             align(g, sc, **kw)
         assert g.last_rc == code, (kw, g.last_rc)
+        assert g.lib.tsd_last_error(g.h).decode() == "tsd_align_points: " + text, kw
 
-    refused(E_ARG, K=0); refused(E_ARG, K=65); refused(E_ARG, iterations=-1); refused(E_ARG, iterations=65)
-    refused(E_ARG, nx=0); refused(E_ARG, step_xy=0.0); refused(E_ARG, x0=float("nan"))
-    refused(E_CAPACITY, nx=1 << 14, ny=1 << 14, step_xy=1e-4)
-    refused(E_ARG, v_cut=1.5); refused(E_ARG, v_cut=-0.1); refused(E_ARG, eps=-1.0); refused(E_ARG, lever=float("inf"))
-    refused(E_ARG, pivot=(float("inf"), 0.0)); refused(E_ARG, min_overlap=float("nan"))
-    refused(E_ARG, cos_sin=None, dtheta=0.0)
+    K_RANGE, STEPS, SHAPE = "K outside 1 .. TSD_RELOC_MAX_PEAKS", "iterations outside 0 .. 64", "nx, ny, ntheta must be >= 1"
+    ORIGIN, TABLE = "x0, y0 finite and step_xy > 0", "cos_sin is not finite"
+    POINT = "a point is not finite or further than TSD_RELOC_MAX_REACH grid widths away"
+    refused(E_ARG, K_RANGE, K=0); refused(E_ARG, K_RANGE, K=65)
+    refused(E_ARG, STEPS, iterations=-1); refused(E_ARG, STEPS, iterations=65)
+    refused(E_ARG, SHAPE, nx=0); refused(E_ARG, ORIGIN, step_xy=0.0); refused(E_ARG, ORIGIN, x0=float("nan"))
+    refused(E_CAPACITY, "nx * ny * ntheta > TSD_RELOC_MAX_CANDIDATES", nx=1 << 14, ny=1 << 14, step_xy=1e-4)
+    refused(E_ARG, "the lattice reaches further than TSD_RELOC_MAX_REACH grid widths from the grid", x0=-4.0 * sc.side - 1.0)
+    refused(E_ARG, "v_cut outside (0, 1]", v_cut=1.5); refused(E_ARG, "v_cut outside (0, 1]", v_cut=-0.1)
+    refused(E_ARG, "eps must be > 0", eps=-1.0); refused(E_ARG, "lever is not finite", lever=float("inf"))
+    refused(E_ARG, "the pivot is not finite or further than TSD_RELOC_MAX_REACH grid widths away", pivot=(float("inf"), 0.0))
+    refused(E_ARG, "min_overlap / max_rms is NaN", min_overlap=float("nan"))
+    refused(E_ARG, "without a cos_sin table, theta0 and a non-zero dtheta are needed", cos_sin=None, dtheta=0.0)
     bad = sc.table.copy(); bad[7, 0] = np.nan
-    refused(E_ARG, cos_sin=bad)
+    refused(E_ARG, TABLE, cos_sin=bad)
     far = sc.points.copy(); far[3, 1] = 5.0 * sc.side
-    refused(E_ARG, points=far)
+    refused(E_ARG, POINT, points=far)
     nan = sc.points.copy(); nan[0, 0] = np.nan
-    refused(E_ARG, points=nan)
-    refused(E_ARG, points=np.zeros((0, 2)))
+    refused(E_ARG, POINT, points=nan)
+    refused(E_ARG, "no point", points=np.zeros((0, 2)))
+    # several bad arguments: the one that is checked first is named -- K, iterations, the lattice (shape, then x0 / y0 / step_xy), the
+    # table, the pivot
+    refused(E_ARG, K_RANGE, K=0, nx=0)
+    refused(E_ARG, SHAPE, nx=0, x0=float("nan"))
+    refused(E_ARG, TABLE, cos_sin=bad, pivot=(float("inf"), 0.0))
     assert g.lib.tsd_align_points(g.h, None, None, 0, 0, None) == E_ARG
     assert g.debug_align_scores().size == 0 and g.debug_align_peaks() == []       # nothing was searched, nothing is kept
     # dst == src, src missing
@@ -307,7 +383,7 @@ def test_refusals_allocate_nothing_and_a_good_call_follows():
     prm = g.icp_params(R.ICP["iterations"], R.ICP["dist_max"], R.ICP["dist_min"])
     rg, mk = np.ascontiguousarray(data), np.ascontiguousarray(mask, dtype=np.uint8)
     g._check(g.lib.tsd_scan_submit(s.h, capi._d(rg), capi._u8(mk), None, C.byref(prm), C.byref(gates)), "tsd_scan_submit")
-    refused(E_ARG)
+    refused(E_ARG, "a scan of this context is in flight (collect it first)")
     with pytest.raises(capi.TsdError):
         g.align_to(other, **sc.lattice)
     assert g.last_rc == E_ARG

@@ -194,29 +194,41 @@ def test_refused_calls_leave_the_grid_alone():
     g = make_grid(sc)
     d0 = g.digest()
 
-    def refused(code, **kw):
+    def refused(code, text, **kw):
         with pytest.raises(capi.TsdError):
             reloc(g, sc, **kw)
         assert g.last_rc == code
+        assert g.lib.tsd_last_error(g.h).decode() == "tsd_relocalize: " + text, kw
         assert g.digest() == d0
 
-    refused(E_ARG, points=np.zeros((0, 2)))
-    refused(E_CAPACITY, points=np.zeros((capi.MAX_ICP_POINTS + 1, 2)))
-    refused(E_ARG, K=65)
-    refused(E_ARG, K=0)
-    refused(E_CAPACITY, nx=4096, ny=4096, ntheta=5, cos_sin=sc.table[:5])
-    refused(E_ARG, cos_sin=None, theta0=0.3, dtheta=0.0)
-    refused(E_ARG, nx=0)
+    K_RANGE, SHAPE = "K outside 1 .. TSD_RELOC_MAX_PEAKS", "nx, ny, ntheta must be >= 1"
+    REACH = "the lattice reaches further than TSD_RELOC_MAX_REACH grid widths from the grid"
+    FAR_POINT = "a scan point is not finite or further than TSD_RELOC_MAX_REACH grid widths from the sensor"
+    refused(E_ARG, "no scan point", points=np.zeros((0, 2)))
+    refused(E_CAPACITY, "points > TSD_MAX_ICP_POINTS", points=np.zeros((capi.MAX_ICP_POINTS + 1, 2)))
+    refused(E_ARG, K_RANGE, K=65)
+    refused(E_ARG, K_RANGE, K=0)
+    refused(E_ARG, "min_pairs < 0", min_pairs=-1)
+    refused(E_CAPACITY, "nx * ny * ntheta > TSD_RELOC_MAX_CANDIDATES", nx=4096, ny=4096, ntheta=5, cos_sin=sc.table[:5])
+    refused(E_ARG, "without a cos_sin table, theta0 and a non-zero dtheta are needed", cos_sin=None, theta0=0.3, dtheta=0.0)
+    refused(E_ARG, SHAPE, nx=0)
+    refused(E_ARG, "x0, y0 finite and step_xy > 0", step_xy=0.0)
     # a lattice, or a scan point, further from the grid than TSD_RELOC_MAX_REACH grid widths (its cell index would not fit an int);
     # a table entry that is not finite
     width = sc.gc.cells * sc.gc.cell_size
-    refused(E_ARG, x0=1e300)
-    refused(E_ARG, y0=-4.0 * width - 1.0)
-    refused(E_ARG, x0=5.0 * width - (R.NXY - 1) * R.STEP + 1.0)
+    refused(E_ARG, REACH, x0=1e300)
+    refused(E_ARG, REACH, y0=-4.0 * width - 1.0)
+    refused(E_ARG, REACH, x0=5.0 * width - (R.NXY - 1) * R.STEP + 1.0)
     far = sc.points.copy(); far[3, 1] = 4.0 * width + 1.0
-    refused(E_ARG, points=far)
+    refused(E_ARG, FAR_POINT, points=far)
     bad = sc.table.copy(); bad[7, 0] = np.nan
-    refused(E_ARG, cos_sin=bad)
+    refused(E_ARG, "cos_sin is not finite", cos_sin=bad)
+    # several bad arguments: the one that is checked first is named -- K, min_pairs, the lattice (shape, then x0 / y0 / step_xy), the
+    # points, the table
+    refused(E_ARG, K_RANGE, K=0, nx=0)
+    refused(E_ARG, "min_pairs < 0", min_pairs=-1, nx=0)
+    refused(E_ARG, SHAPE, nx=0, x0=float("nan"))
+    refused(E_ARG, FAR_POINT, points=far, cos_sin=bad)
     # while a scan of the context is in flight
     s = capi.TsdSensorDevice(g, sc.geo.beams, sc.geo.angle_increment, sc.geo.angle_min, R.MAX_RANGE, R.MIN_RANGE, R.LOW_REFL)
     pose = synth.pose_matrix(*sc.poses[-1])
@@ -231,6 +243,7 @@ def test_refused_calls_leave_the_grid_alone():
     with pytest.raises(capi.TsdError):
         reloc(g, sc)
     assert g.last_rc == E_ARG
+    assert g.lib.tsd_last_error(g.h).decode() == "tsd_relocalize: a scan of this context is in flight (collect it first)"
     res = capi.ScanResult()
     g._check(g.lib.tsd_scan_collect(s.h, C.byref(res)), "tsd_scan_collect")
     assert not res.pushed and g.digest() == d0
