@@ -241,6 +241,40 @@ void ThreadLocalize::deviceError(int rc, const ScanReport& rep)
   publish(rep);
 }
 
+// what every scan path does with the outcome of its ray cast: the pose and the point counts go into the report; false = the scan
+// ends here and is reported -- a device error, or "Raycasting found no coordinates" -> skip the scan (ThreadLocalize.cpp:354-358)
+bool ThreadLocalize::scanHasModel(int rc, ScanReport& rep, int validModel, int validScene, bool noModel)
+{
+  _sensor->getTransformation().getData(rep.pose);
+  rep.validModel = validModel; rep.validScene = validScene;
+  if(rc != TSD_OK)
+  {
+    deviceError(rc, rep);
+    return false;
+  }
+  if(noModel)
+  {
+    rep.noModel = true;
+    publish(rep);
+    return false;
+  }
+  return true;
+}
+
+// The pre-registration as the reference calls it, its host part between the ray cast and the registration (processScanPreRegistered):
+//   registration_mode 1 and 2    always
+//   registration_mode 3          unfused localiser or no device sensor; TSD_MODE3_UNFUSED set (A/B); after the device refused the
+//                                arming's sizes (AheadLedger::capacity_refused); several robots on one grid without the batched
+//                                dispatcher (the batch runs the pre-registration behind its ray casts, the split scan does not)
+// Otherwise registration_mode 3 pre-registers inside the fused scan, on the device between the ray cast and the registration --
+// single robot or batched --, and registration_mode 0 takes the fused scan or, without it, tsd_localize with the host's gates.
+bool ThreadLocalize::hostPreRegisters() const
+{
+  static const bool mode3Unfused = std::getenv("TSD_MODE3_UNFUSED") != nullptr;
+  return _matcher && (!_tsdPdf || mode3Unfused || !_lookAhead.pre_fused_ok() || !_fused || !_sensor->deviceHandle() ||
+                      (_concurrent && !_grid.batcher()));
+}
+
 void ThreadLocalize::laserCallBack(const std::shared_ptr<sensor_msgs::msg::LaserScan> scan)
 {
   // the reference clamps in place through an aliased shared_ptr (Appendix B #15); copy instead
@@ -318,12 +352,7 @@ void ThreadLocalize::processScan(const std::vector<float>& ranges, const builtin
   _stampLaser = stamp;
 
   // (a scan that was announced, ingested and staged on the device during the previous registration is in _sensor already)
-  // Accepted only if it IS this scan: same stamp AND the same readings (drivers that leave the stamp at 0 or repeat it must not
-  // get the previously staged ranges registered in place of the scan they delivered); anything else is a drop.
-  const bool staged = _stagedValid && _stagedStampNs == rep.stampNs && _stagedRanges.size() == ranges.size() &&
-                      (ranges.empty() || std::memcmp(_stagedRanges.data(), ranges.data(), ranges.size() * sizeof(float)) == 0);
-  if(_stagedValid && !staged) _stagedValid = false;     // something else came: tsd_scan_submit drops the staged scan
-  if(!staged)
+  if(!_lookAhead.arrived(rep.stampNs, ranges.data(), ranges.size()))
   {
     _sensor->setRealMeasurementData(ranges);
     _sensor->setStandardMask();
@@ -335,12 +364,7 @@ void ThreadLocalize::processScan(const std::vector<float>& ranges, const builtin
     _haveLastPose = true;
   }
 
-  // registration_mode 3: inside the fused scan (the pre-registration on the device between the ray cast and the registration) when
-  // this robot has the fused path to itself; the reference's own call structure otherwise (and with TSD_MODE3_UNFUSED set: A/B)
-  static const bool mode3Unfused = std::getenv("TSD_MODE3_UNFUSED") != nullptr;
-  // (several robots on one grid: the batched dispatcher runs the pre-registration behind its batch's ray casts; the split scan does not)
-  // (registration_mode 2: always the reference's call structure, the matcher's host part between the ray cast and the registration)
-  if(_matcher && (!_tsdPdf || mode3Unfused || !_preFusedOk || !_fused || !_sensor->deviceHandle() || (_concurrent && !_grid.batcher())))
+  if(hostPreRegisters())
   {
     processScanPreRegistered(rep);
     return;
@@ -355,21 +379,8 @@ void ThreadLocalize::processScan(const std::vector<float>& ranges, const builtin
   tsd_icp_result res;
   std::memset(&res, 0, sizeof(res));
   const int rc = _grid.localize(_sensor, _icpParams, &res);
-  _sensor->getTransformation().getData(rep.pose);
-  if(rc != TSD_OK)
-  {
-    deviceError(rc, rep);
-    return;
-  }
-  rep.validModel = res.n_model; rep.validScene = res.n_scene;
-  if(res.n_model == 0)
-  {
-    // "Raycasting found no coordinates" -> skip the scan (ThreadLocalize.cpp:354-358)
-    rep.noModel = true;
-    publish(rep);
-    return;
-  }
-  finishScan(rep, res);
+  if(scanHasModel(rc, rep, res.n_model, res.n_scene, res.n_model == 0))
+    finishScan(rep, res);
 }
 
 // registration_mode 3 (ThreadLocalize.cpp:353-406 with doRegistration's case TSD, :557-567): ray cast, the TSD_PDF
@@ -407,19 +418,8 @@ void ThreadLocalize::processScanPreRegistered(ScanReport& rep)
   unsigned int validModelPoints = 0;
   const int rcR = _grid.raycast(_sensor, _modelCoords.data(), _modelNormals.data(), maskM, &validModelPoints);
   g_m3.lap(0);
-  _sensor->getTransformation().getData(rep.pose);
-  rep.validModel = (int)validModelPoints;
-  if(rcR != TSD_OK)
-  {
-    deviceError(rcR, rep);
+  if(!scanHasModel(rcR, rep, (int)validModelPoints, 0, validModelPoints == 0))
     return;
-  }
-  if(validModelPoints == 0)
-  {
-    rep.noModel = true;
-    publish(rep);
-    return;
-  }
   const unsigned int validScenePoints = _sensor->dataToCartesianVectorMask(_scene.data(), maskS);
   rep.validScene = (int)validScenePoints;
   g_m3.lap(1);
@@ -467,33 +467,38 @@ bool ThreadLocalize::lastPreregistration(tsd_tsdpdf_result* out)
   return true;
 }
 
-// what follows the registration (ThreadLocalize.cpp:381-406): gate, Sensor::transform, pose / tf, push decision
-void ThreadLocalize::finishScan(ScanReport& rep, const tsd_icp_result& res)
+// what follows the registration (ThreadLocalize.cpp:381-406): gate, Sensor::transform, pose / tf, push decision.  Without `device`
+// the host's gates decide and the push goes through the mapper; with the fused scan's result the device has decided both in stream
+// order and pushed already: its verdicts are taken, the host sensor is kept as a mirror.
+void ThreadLocalize::finishScan(ScanReport& rep, const tsd_icp_result& res, const tsd_scan_result* device)
 {
   obvious::Matrix T(3, 3, res.T);
   std::memcpy(rep.T, res.T, sizeof(rep.T));
   rep.rms = res.rms; rep.pairs = res.pairs; rep.iterations = res.iterations; rep.icpState = res.state;
-  if(isRegistrationError(&T, _trnsMax, _rotMax))
+  if(device ? device->reg_error != 0 : isRegistrationError(&T, _trnsMax, _rotMax))
   {
     rep.regError = true;
     sendNanTransform();
   }
   else
   {
-    _sensor->transform(&T);
+    _sensor->transform(&T);                          // (fused: the host mirror, same arithmetic as the device)
+    if(device)
+      _sensor->setTransformation(obvious::Matrix(3, 3, device->pose));     // the device pose is the authoritative one
     obvious::Matrix curPose = _sensor->getTransformation();
     curPose.getData(rep.pose);
     sendTransform(&curPose);
-    if(this->isPoseChangeSignificant(_lastPose, &curPose))
+    if(device ? device->pushed != 0 : this->isPoseChangeSignificant(_lastPose, &curPose))
     {
       *_lastPose = curPose;
-      if(_synchronous)
+      // (fused: the device has pushed already, behind the registration)
+      if(!device && _synchronous)
       {
         // what queuePush + the mapping thread do, in stream order on this thread
         std::unique_ptr<obvious::SensorPolar2D> local(_sensor->copyForMapping());
         _grid.push(local.get());
       }
-      else
+      else if(!device)
         _mapper.queuePush(_sensor);
       rep.pushed = true;
     }
@@ -513,25 +518,16 @@ void ThreadLocalize::processScanFused(ScanReport& rep)
   tsd_scan_result sr;
   std::memset(&sr, 0, sizeof(sr));
   // single robot: the scan may have been staged, and its pre-registration armed, while the previous scan registered
-  const bool useStaged = !_concurrent && _stagedValid;
-  const bool preStaged = _preStagedValid && useStaged;      // (a dropped staged scan takes its armed pre-registration along)
-  // ... but not its draws: they do not depend on the scan, and the scan that came instead uses the very same ones, so that a seeded
-  // sequence (tsdpdf_seed) stays one drawStreams() call per REGISTERED scan, as in the unfused path
-  if(!_concurrent)
-  {
-    if(_preStagedValid && !useStaged) _drawsReady = true;
-    _stagedValid = false;
-    _preStagedValid = false;
-  }
+  const AheadLedger::Entry ahead = _lookAhead.enter_fused(_concurrent);
   int rc = TSD_OK;
   // arm: registration_mode 3's pre-registration for this scan.  Several robots on one grid: armed for this robot's scan of the batch,
   // which runs it behind the batch's ray casts (tsd_batch_begin) -- fresh draws every time; single robot: the draws taken ahead.
-  if(_tsdPdf && !preStaged && (rc = armPreregistration(!_concurrent)) == TSD_E_CAPACITY)
+  if(_tsdPdf && !ahead.preStaged && (rc = armPreregistration(!_concurrent)) == TSD_E_CAPACITY)
   {
     // more trials / control points than the device-side list building holds in LDS: the reference's call structure instead,
     // from this scan on (nothing was enqueued; the draws are consumed, like a match() that ran)
     std::fprintf(stderr, "Localizer(%s): registration_mode 3 runs unfused (%s)\n", _nameSpace.c_str(), tsd_last_error(_grid.context()));
-    _preFusedOk = false;
+    _lookAhead.capacity_refused();
     processScanPreRegistered(rep);
     return;
   }
@@ -543,51 +539,14 @@ void ThreadLocalize::processScanFused(ScanReport& rep)
   else
   {
     // submit, stage the next scan while the device registers this one, collect
-    if(rc == TSD_OK) rc = _grid.scanSubmit(_sensor, useStaged, maskPush.data(), _icpParams, gates);
+    if(rc == TSD_OK) rc = _grid.scanSubmit(_sensor, ahead.useStaged, maskPush.data(), _icpParams, gates);
     stageNextScan(rc == TSD_OK);
-    if(rc == TSD_OK && _tsdPdf && _preFusedOk && !_drawsReady && !_preStagedValid)
-    {
+    if(rc == TSD_OK && _lookAhead.submitted_needs_draws(_tsdPdf != nullptr))
       _matcher->drawStreams(_sensor->getRealMeasurementSize(), _dSub, _dCtrl, _dTrials);      // the next scan's, while the device is busy
-      _drawsReady = true;
-    }
     if(rc == TSD_OK) rc = _grid.scanCollect(_sensor, &sr);
   }
-  _sensor->getTransformation().getData(rep.pose);
-  if(rc != TSD_OK)
-  {
-    deviceError(rc, rep);
-    return;
-  }
-  rep.validModel = sr.icp.n_model; rep.validScene = sr.icp.n_scene;
-  if(sr.no_model)
-  {
-    rep.noModel = true;
-    publish(rep);
-    return;
-  }
-  obvious::Matrix T(3, 3, sr.icp.T);
-  std::memcpy(rep.T, sr.icp.T, sizeof(rep.T));
-  rep.rms = sr.icp.rms; rep.pairs = sr.icp.pairs; rep.iterations = sr.icp.iterations; rep.icpState = sr.icp.state;
-  if(sr.reg_error)
-  {
-    rep.regError = true;
-    sendNanTransform();
-  }
-  else
-  {
-    _sensor->transform(&T);                          // host mirror: same arithmetic as the device
-    obvious::Matrix devPose(3, 3, sr.pose);
-    _sensor->setTransformation(devPose);             // the device pose is the authoritative one
-    obvious::Matrix curPose = _sensor->getTransformation();
-    curPose.getData(rep.pose);
-    sendTransform(&curPose);
-    if(sr.pushed)
-    {
-      *_lastPose = curPose;
-      rep.pushed = true;
-    }
-  }
-  publish(rep);
+  if(scanHasModel(rc, rep, sr.icp.n_model, sr.icp.n_scene, sr.no_model != 0))
+    finishScan(rep, sr.icp, &sr);
 }
 
 // doRegistration, case TSD (ThreadLocalize.cpp:557-567) inside the fused scan: the scene points and the match's three rand() streams
@@ -600,8 +559,7 @@ int ThreadLocalize::armPreregistration(bool reuseDraws)
   if(_scene.size() != 2 * (size_t)n) { _scene.assign(2 * (size_t)n, 0.0); _maskS.assign(n, 0); }
   bool* maskS = reinterpret_cast<bool*>(_maskS.data());
   _sensor->dataToCartesianVectorMask(_scene.data(), maskS);
-  if(!reuseDraws || !_drawsReady || _dSub.size() != n) _matcher->drawStreams(n, _dSub, _dCtrl, _dTrials);
-  _drawsReady = false;
+  if(_lookAhead.arm(reuseDraws, n, _dSub.size())) _matcher->drawStreams(n, _dSub, _dCtrl, _dTrials);
   return _grid.scanPreregister(_sensor, _tsdPdf->params(_ranPhiMax * M_PI / 180.0, _sensor->getAngularResolution()), _scene.data(), maskS,
                                _dSub.data(), _dCtrl.data(), _dTrials.data());
 }
@@ -630,13 +588,11 @@ void ThreadLocalize::stageNextScan(bool submitted)
   _sensor->maskForMapping(maskNext);
   if(_grid.scanStage(_sensor, maskNext.data()) != TSD_OK)
     return;
-  _stagedValid = true;
-  _stagedStampNs = stampNs(next->header.stamp);
-  _stagedRanges = next->ranges;
+  _lookAhead.staged(stampNs(next->header.stamp), next->ranges.data(), next->ranges.size());
   // ... and its pre-registration: scene points, draws and the inputs' copy NOW, while the device registers this scan -- between
   // two scans the host then only submits (the device was waiting for the host there: 40 us of host work per scan in mode 3)
-  if(_tsdPdf && _preFusedOk && armPreregistration(true) == TSD_OK)
-    _preStagedValid = true;
+  if(_tsdPdf && _lookAhead.pre_fused_ok() && armPreregistration(true) == TSD_OK)
+    _lookAhead.staged_and_armed();
 }
 
 bool ThreadLocalize::startAt(const double pose33[9], const sensor_msgs::msg::LaserScan& scan)
@@ -656,7 +612,7 @@ bool ThreadLocalize::startAt(const double pose33[9], const sensor_msgs::msg::Las
   _sensor->resetPose();
   _sensor->transform(&T);
   _haveLastPose = false;
-  _stagedValid = false; _preStagedValid = false;
+  _lookAhead.reseated();
   {
     std::lock_guard<std::mutex> lk(_dataMutex);
     _ahead.reset();

@@ -11,6 +11,7 @@
 #include <string>
 
 #include "ThreadSLAM.h"
+#include "ahead_ledger.hpp"
 #include "ros_shim.h"
 
 namespace ohm_tsd_slam
@@ -92,7 +93,9 @@ private:
   void processScan(const std::vector<float>& rangesIn, const builtin_interfaces::msg::Time& stamp);
   void processScanFused(ScanReport& rep);
   void processScanPreRegistered(ScanReport& rep);
-  void finishScan(ScanReport& rep, const tsd_icp_result& res);
+  bool hostPreRegisters() const;
+  bool scanHasModel(int rc, ScanReport& rep, int validModel, int validScene, bool noModel);
+  void finishScan(ScanReport& rep, const tsd_icp_result& res, const tsd_scan_result* device = nullptr);
   int armPreregistration(bool reuseDraws);
   void stageNextScan(bool submitted);
   void publish(const ScanReport& rep);
@@ -128,17 +131,10 @@ private:
   bool _haveLastPose;
   builtin_interfaces::msg::Time _stampLaser, _stampLaserOld;
 
-  std::shared_ptr<sensor_msgs::msg::LaserScan> _ahead;      // announced next scan (clamped like laserCallBack does)
-  bool _stagedValid = false;                                // _sensor holds, and the device has staged, the scan with ...
+  std::shared_ptr<sensor_msgs::msg::LaserScan> _ahead;      // announced next scan (clamped like laserCallBack does; guarded by _dataMutex)
+  AheadLedger _lookAhead;           // what was staged, armed and drawn ahead of the next scan (ahead_ledger.hpp)
+  std::vector<int> _dSub, _dCtrl, _dTrials;     // registration_mode 3, fused: the three rand() streams the ledger speaks of
   bool _asyncMapping = false;       // "async_mapping" (addition): the fused scan's push beside the next registration (tsd_sensor_set_async_mapping)
-  bool _preFusedOk = true;          // registration_mode 3: the device-side pre-registration takes these parameters (else: the unfused calls)
-  // registration_mode 3, fused: the NEXT scan's three rand() streams, drawn while the device registers this one (1 311 rand() calls
-  // are 23 us of host time -- more than the host has between two scans before the device runs dry)
-  std::vector<int> _dSub, _dCtrl, _dTrials;
-  bool _drawsReady = false;
-  bool _preStagedValid = false;     // the staged scan's pre-registration is armed on the device already (tsd_scan_preregister ahead of the collect)
-  long long _stagedStampNs = 0;                             // ... this stamp ...
-  std::vector<float> _stagedRanges;                         // ... and these readings (in the sensor's beam order)
   std::deque<std::shared_ptr<sensor_msgs::msg::LaserScan>> _laserData;
   std::mutex _dataMutex;
   bool _busy;

@@ -209,8 +209,8 @@ int tsd_scan(tsd_sensor* s, const double* ranges, const uint8_t* mask, const uin
 int tsd_scan_preregister(tsd_sensor* s, const tsd_tsdpdf_params* prm, const double* scene, const uint8_t* ms, const int* d0, const int* d1,
                          const int* d2)
 {
-  (void)s; (void)prm; (void)scene; (void)ms; (void)d0; (void)d1; (void)d2;
-  rec(STUB_PREREGISTER, 0, 0);
+  (void)s; (void)prm; (void)scene; (void)ms; (void)d1; (void)d2;
+  rec(STUB_PREREGISTER, d0 ? (double)d0[0] : 0.0, 0);    /* tag: the first value of the sub-sampling stream = which draws it got */
   return TSD_OK;
 }
 int tsd_scan_begin(tsd_sensor* s, const double* ranges, const uint8_t* mask, const uint8_t* mask_push, const tsd_icp_params* p,

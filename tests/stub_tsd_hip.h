@@ -15,7 +15,7 @@ enum {
 typedef struct {
   int op;                      /* STUB_* */
   int flag;                    /* STUB_SCAN_SUBMIT: 1 = from the staged scan, 2 = a staged scan was dropped, 0 = plain */
-  double tag;                  /* the scan's beam-0 range: the tests number their scans there */
+  double tag;                  /* the scan's beam-0 range: the tests number their scans there (STUB_PREREGISTER: d0[0] of its draws) */
   unsigned long long thread;   /* calling thread */
 } stub_entry;
 

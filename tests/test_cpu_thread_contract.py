@@ -19,7 +19,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "ohm_tsd_slam_amd", "csrc", "host")
 CASES = ["first_scan_is_synchronous", "newest_scan_wins", "mapper_is_lifo", "threaded_unfused_scan_goes_through_the_mapper",
-         "announce_next_accept_and_drop", "threaded_fused_stages_the_queued_scan", "shutdown_with_work_queued", "tf_map_to_odom"]
+         "announce_next_accept_and_drop", "seeded_mode3_draws_follow_the_registered_scans",
+         "threaded_fused_stages_the_queued_scan", "shutdown_with_work_queued", "tf_map_to_odom"]
 
 
 def _build(tmp, tag, flags):

@@ -15,7 +15,9 @@
 #include <cstring>
 #include <functional>
 #include <memory>
+#include <cstdlib>
 #include <set>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -70,11 +72,13 @@ struct Rig
   obvious::TsdGrid* grid;
   ThreadMapping* mapping;
   ThreadLocalize* loc;
-  Rig(bool fused, bool synchronous)
+  Rig(bool fused, bool synchronous, int registrationMode = 0, int tsdpdfSeed = -1)
   {
     stub_reset();
     node = std::make_shared<rclcpp::Node>("tsd_slam");
     node->set_parameter("laser_min_range", 0.26);
+    if(registrationMode != 0) node->set_parameter("registration_mode", registrationMode);
+    if(tsdpdfSeed >= 0) node->set_parameter("tsdpdf_seed", tsdpdfSeed);
     grid = new obvious::TsdGrid(0.05, obvious::LAYOUT_32x32, static_cast<obvious::EnumTsdGridLayout>(9), 0);
     grid->setMaxTruncation(0.15);
     mapping = new ThreadMapping(grid);
@@ -217,6 +221,51 @@ static void case_announce_next_accept_and_drop()
   std::printf("ok announce_next_accept_and_drop\n");
 }
 
+// registration_mode 3, fused, seeded: which drawStreams() call's draws each tsd_scan_preregister carries.  The stub logs the first
+// value of the sub-sampling stream as the entry's tag; call number k of a matcher seeded with s starts with srand(s + k), and the
+// sub-sampling stream is the first thing drawn (RandomMatching::drawStreams), so that value is the first rand() after srand(s + k).
+// One call per REGISTERED scan, without a gap: a staged scan that is dropped hands its draws to the scan that came instead, and a
+// scan accepted from the staged state keeps the arming it got ahead.
+static void case_seeded_mode3_draws_follow_the_registered_scans()
+{
+  const int seed = 11;
+  Rig r(/*fused*/ true, /*synchronous*/ true, /*registration_mode*/ 3, seed);
+  r.loc->laserCallBack(make_scan(0));
+  r.loc->announceNext(make_scan(2));
+  r.loc->laserCallBack(make_scan(1));                          // armed with call 0; stages scan 2 and arms it ahead with call 1
+  r.loc->announceNext(make_scan(3));
+  r.loc->laserCallBack(make_scan(2));                          // accepted: not armed again; stages scan 3, armed ahead with call 2
+  r.loc->laserCallBack(make_scan(7));                          // scan 3 is dropped: scan 7 is armed with the same call 2
+  auto fake = make_scan(9);
+  r.loc->announceNext(fake);
+  r.loc->laserCallBack(make_scan(8));                          // call 3 (taken ahead during scan 7); stages scan 9, call 4
+  auto impostor = make_scan(9);
+  impostor->ranges[5] = 2.5f;
+  r.loc->laserCallBack(impostor);                              // scan 9 is dropped: the impostor is armed with the same call 4
+  // P = tsd_scan_preregister, S = tsd_scan_submit, in the order the device library saw them
+  std::string order;
+  std::vector<stub_entry> pre;
+  for(int i = 0, n = stub_log_count(); i < n; i++)
+  {
+    const stub_entry e = stub_log_get(i);
+    if(e.op == STUB_PREREGISTER) { order += 'P'; pre.push_back(e); }
+    else if(e.op == STUB_SCAN_SUBMIT) order += 'S';
+  }
+  // scan 1: P S P(ahead) | scan 2: S P(ahead) | scan 7: P S | scan 8: P S P(ahead) | impostor: P S
+  CHECK(order == "PSPSPPSPSPPS", "preregister / submit order %s", order.c_str());
+  double first[5];
+  for(int k = 0; k < 5; k++) { std::srand((unsigned)(seed + k)); first[k] = (double)std::rand(); }
+  for(int k = 1; k < 5; k++) CHECK(first[k] != first[k - 1], "calls %d and %d start alike: the check cannot tell them apart", k - 1, k);
+  const int call[7] = {0, 1, 2, 2, 3, 4, 4};                  // scans 1, 2 (ahead), 3 (ahead, dropped), 7, 8, 9 (ahead, dropped), impostor
+  CHECK(pre.size() == 7, "%zu pre-registrations", pre.size());
+  for(size_t i = 0; i < pre.size() && i < 7; i++)
+    CHECK(pre[i].tag == first[call[i]], "pre-registration %zu carries draws starting with %.0f, expected call %d (%.0f)", i, pre[i].tag, call[i], first[call[i]]);
+  const auto sub = log_of(STUB_SCAN_SUBMIT);
+  CHECK(sub.size() == 5 && sub[1].flag == 1 && sub[2].flag == 2 && sub[4].flag == 2, "%zu submits", sub.size());
+  CHECK(log_of(STUB_TSDPDF).empty(), "a pre-registration ran unfused");
+  std::printf("ok seeded_mode3_draws_follow_the_registered_scans\n");
+}
+
 static void case_threaded_fused_stages_the_queued_scan()
 {
   // threaded + fused: a scan that queued up during a registration is staged ahead and, if a NEWER one arrives, dropped for it
@@ -350,6 +399,7 @@ int main()
   case_mapper_is_lifo();
   case_threaded_unfused_scan_goes_through_the_mapper();
   case_announce_next_accept_and_drop();
+  case_seeded_mode3_draws_follow_the_registered_scans();
   case_threaded_fused_stages_the_queued_scan();
   case_shutdown_with_work_queued();
   case_tf_map_to_odom();
