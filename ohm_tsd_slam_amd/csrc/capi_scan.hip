@@ -904,6 +904,12 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
   if (hipMemcpyAsync(d_base, h_base, off, hipMemcpyHostToDevice, b->stream) != hipSuccess)
     return FAIL(set_error(ctx, TSD_E_HIP, "tsd_batch_begin: copy", hipGetLastError()));
   b->d_stage_cur = d_base;
+  // More scans than travel as kernel arguments: the ray casts read their entries from this copy and wait for it by event.  The event
+  // is recorded HERE, right behind the copy -- behind the registrations (launched ahead on this stream where they wait on the device)
+  // it would complete only when they have finished, and they wait for the ray casts: each side waiting for the other until the
+  // registrations' bounded wait runs out (the first batch of 17 robots came back as "timed out; NOT registered").
+  if (n > RC_BATCH_BYVAL && hipEventRecord(b->ev_copy_done, b->stream) != hipSuccess)
+    return FAIL(set_error(ctx, TSD_E_HIP, "tsd_batch_begin: copy event", hipGetLastError()));
   int rc = launch_push_tables_batch(ctx, b->stream, reinterpret_cast<const TablesBatchEntry*>(d_base + off_tb), n, max_beams);
   if (rc != TSD_OK) return FAIL(rc);
   {
@@ -923,7 +929,7 @@ int tsd_batch_begin(tsd_batch* b, int n, tsd_sensor* const* sensors, const doubl
       // (the entries as kernel arguments: nothing of the batch's copy is needed, one wait less on the grid's stream)
       rc = launch_raycast_batch_byval(ctx, ctx->stream, h_rc, n, max_beams);
     } else {
-      if (hipEventRecord(b->ev_copy_done, b->stream) != hipSuccess || hipStreamWaitEvent(ctx->stream, b->ev_copy_done, 0) != hipSuccess)
+      if (hipStreamWaitEvent(ctx->stream, b->ev_copy_done, 0) != hipSuccess)
         return FAIL(set_error(ctx, TSD_E_HIP, "tsd_batch_begin: copy event", hipGetLastError()));
       rc = launch_raycast_batch(ctx, ctx->stream, reinterpret_cast<const RaycastBatchEntry*>(d_base + off_rc), n, max_beams);
     }

@@ -47,6 +47,8 @@ class Robot:
         kw = self.kw
         data, mask, _ = self.ingest(r32)
         for g in (og, dg):
+            if g is None:       # (the oracle alone: tests/test_cpu_batch_shapes.py)
+                continue
             g.free_footprint([self.sx + kw["footprint_x_offset"], self.sy], kw["footprint_width"], kw["footprint_height"])
             g.push(self.pose, data, mask, kw["angle_increment"], kw["angle_min"], kw["max_range"], kw["min_range"], kw["low_refl_range"])
         self.rays = self.o.rays_rescale(self.rays, self.cs, 1.0)
@@ -99,23 +101,41 @@ class Robot:
             og.push(pose, d2, m2, kw["angle_increment"], kw["angle_min"], kw["max_range"], kw["min_range"], kw["low_refl_range"])
 
 
-def _setup(oracle, cfg, n_robots, n_scans):
+def _setup(oracle, cfg, n_robots, n_scans, geos=None, offsets=None, poses=None, device=True):
+    """geos: one ScanGeometry per robot (None: the configuration's for all of them, one parameter set shared by the robots);
+    offsets: the robots' starts relative to the grid's centre (None: OFFSETS); poses: per robot the ground-truth poses its scans
+    are taken from (None: synth.trajectory from its start).  device=False: the oracle's side alone -- no device grid, no sensors."""
     gc, geo, scene = synth.CONFIGS[cfg]
-    geo_msg = synth.ScanGeometry(geo.beams, float(np.float32(geo.angle_min)), float(np.float32(geo.angle_increment)))
-    kw = slam_kwargs(gc, geo_msg)
+    if offsets is None:
+        offsets = OFFSETS[:n_robots]
+        n_robots = len(offsets)         # (OFFSETS holds four starts: a caller that asks for more without its own list drives four robots)
+    else:
+        offsets = offsets[:n_robots]
+    geo_of = [geo] * n_robots if geos is None else list(geos)
+    assert len(geo_of) == n_robots and len(offsets) == n_robots
+
+    def kwargs_for(g):
+        return slam_kwargs(gc, synth.ScanGeometry(g.beams, float(np.float32(g.angle_min)), float(np.float32(g.angle_increment))))
+
+    kw = kwargs_for(geo)
+    kw_of = [kw] * n_robots if geos is None else [kwargs_for(g) for g in geo_of]
     og = oracle.Grid(gc.map_size_log2, gc.cell_size, gc.truncation_radius * gc.cell_size)
-    dg = capi.TsdGridDevice(gc.map_size_log2, gc.cell_size, gc.truncation_radius * gc.cell_size)
+    dg = capi.TsdGridDevice(gc.map_size_log2, gc.cell_size, gc.truncation_radius * gc.cell_size) if device else None
     robots, scans, sensors = [], [], []
-    for off in OFFSETS[:n_robots]:
+    for i, (off, g, k) in enumerate(zip(offsets, geo_of, kw_of)):
         w = synth.World(scene, gc, start_xy=[0.5 * gc.width + off[0], 0.5 * gc.width + off[1]])
-        scans.append(synth.scans_for(w, geo, synth.trajectory(w, n_scans, yaw0=off[2])))
-        robots.append(Robot(oracle, gc, geo, off, kw))
+        scans.append(synth.scans_for(w, g, synth.trajectory(w, n_scans, yaw0=off[2]) if poses is None else poses[i]))
+        robots.append(Robot(oracle, gc, g, off, k))
     for rb, sc in zip(robots, scans):
         rb.init_both(og, dg, sc[0])
-    for rb in robots:
-        s = capi.TsdSensorDevice(dg, geo.beams, kw["angle_increment"], kw["angle_min"], kw["max_range"], kw["min_range"], kw["low_refl_range"])
+    if not device:
+        return gc, geo, robots[0].kw, og, None, robots, scans, [], None, None
+    for rb, g in zip(robots, geo_of):
+        k = rb.kw
+        s = capi.TsdSensorDevice(dg, g.beams, k["angle_increment"], k["angle_min"], k["max_range"], k["min_range"], k["low_refl_range"])
         s.set_pose(rb.pose, rb.rays, rb.rays_local)
         sensors.append(s)
+    kw = robots[0].kw
     params = dg.icp_params(kw["icp_iterations"], kw["dist_filter_max"], kw["dist_filter_min"])
     gates = capi.GateParams(kw["reg_trs_max"], kw["reg_sin_rot_max"], 0.05, 0.03)
     return gc, geo, kw, og, dg, robots, scans, sensors, params, gates

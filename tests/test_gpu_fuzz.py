@@ -110,6 +110,15 @@ def test_randomised_batched_robots_short():
 
 
 @pytest.mark.gpu
+def test_randomised_batched_robots_mixed_scanners_short():
+    """tools/fuzz_batch.py mixed: every robot draws its own scanner (360 / 1081 / 270 beams), 2-17 robots per fleet, 3-6 rounds
+    (these six seeds draw fleets of 16, 2, 3, 17, 12 and 5 robots)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_batch.py"), "6", "3095", "mode3", "mixed"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    assert "all 6 cases ok" in p.stdout
+
+
+@pytest.mark.gpu
 def test_randomised_icp_point_sets_short():
     """tools/fuzz_icp.py: tsd_icp on synthetic point sets -- lattices (exact multi-way ties), circles, polylines, clouds, duplicates,
     outliers, non-finite points, 3..2048 model points in random order."""

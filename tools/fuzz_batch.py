@@ -6,8 +6,11 @@ at random into one or two batch slots that are BEGUN together (both slots' ray c
 pushes follow slot by slot in robot order, the results are collected afterwards -- the two-slot pattern of the facade's dispatcher, with
 the device-side waits and gates it uses.  Per robot and round: ray-cast hits, gates, pairs / iterations / state exact, pose 1e-9; final
 grid 1e-9.  "mode3": in half of the cases a random subset of the robots has its TSD_PDF pre-registration armed every round
-(tsd_scan_preregister with random draws; armed and unarmed scans share batches), winner and candidate count compared too.
-usage (GPU box): python3 tools/fuzz_batch.py [cases] [first_seed] [mode3]"""
+(tsd_scan_preregister with random draws; armed and unarmed scans share batches), winner and candidate count compared too.  "mixed":
+every robot draws its own scanner from three (360 beams of 1 degree, 1081 of 0.25 degree, 270 of 1 degree over 270 degrees) and the
+fleet has 2-17 robots -- a batch runs in its widest scanner's shapes, takes the one-pass push up to 16 scans and the by-value ray-cast
+entries up to 16 -- over 3-6 rounds.
+usage (GPU box): python3 tools/fuzz_batch.py [cases] [first_seed] [mode3] [mixed]"""
 import math, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,7 +23,13 @@ import tests.test_gpu_batch as T
 O.build()
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-with_mode3 = len(sys.argv) > 3 and sys.argv[3] == "mode3"
+with_mode3 = "mode3" in sys.argv[3:]
+with_mixed = "mixed" in sys.argv[3:]
+SCANNERS = [synth.ScanGeometry.full_circle_360(), synth.ScanGeometry.utm30lx(), synth.ScanGeometry(270, math.radians(-135.0), 2.0 * math.pi / 360.0)]
+
+
+def msg_geometry(g):
+    return synth.ScanGeometry(g.beams, float(np.float32(g.angle_min)), float(np.float32(g.angle_increment)))
 t_start = time.time()
 tot = dict(rounds=0, scans=0, pushes=0, two_slot_rounds=0, armed_scans=0)
 
@@ -41,17 +50,20 @@ for case in range(n_cases):
     scene = str(rng.choice(["room", "pillars"]))
     geo = synth.ScanGeometry.full_circle_360() if rng.random() < 0.4 else synth.ScanGeometry.utm30lx()
     gc = synth.GridConfig(map_log2, cs)
-    R = int(rng.integers(2, 7))
-    n = int(rng.integers(5, 14))
-    geo_msg = synth.ScanGeometry(geo.beams, float(np.float32(geo.angle_min)), float(np.float32(geo.angle_increment)))
-    kw = slam_kwargs(gc, geo_msg)
+    R = int(rng.integers(2, 18)) if with_mixed else int(rng.integers(2, 7))
+    n = int(rng.integers(4, 8)) if with_mixed else int(rng.integers(5, 14))
+    geos = [SCANNERS[int(rng.integers(0, 3))] for _ in range(R)] if with_mixed else [geo] * R
+    kw = slam_kwargs(gc, msg_geometry(geo))
+    kws = [slam_kwargs(gc, msg_geometry(g)) for g in geos] if with_mixed else [kw] * R
     mode3 = with_mode3 and rng.random() < 0.5
     if mode3:
-        kw.update(trials=int(rng.choice([20, 40, 100])), size_control_set=int(rng.choice([60, 120, 140])))
+        pre = dict(trials=int(rng.choice([20, 40, 100])), size_control_set=int(rng.choice([60, 120, 140])))
+        for k_ in kws + [kw]:
+            k_.update(pre)
         phi_max3 = np.radians(kw["ransac_phi_max"])
     og = O.Grid(gc.map_size_log2, gc.cell_size, gc.truncation_radius * gc.cell_size)
     dg = capi.TsdGridDevice(gc.map_size_log2, gc.cell_size, gc.truncation_radius * gc.cell_size)
-    tag = f"seed {seed}: 2^{map_log2} cells, {scene}, {geo.beams} beams, {R} robots, {n} rounds" + (", mode 3" if mode3 else "")
+    tag = f"seed {seed}: 2^{map_log2} cells, {scene}, {'/'.join(str(g.beams) for g in geos) if with_mixed else geo.beams} beams, {R} robots, {n} rounds" + (", mode 3" if mode3 else "")
     robots, scans, sensors, slots = [], [], [], []
     try:
         world0 = synth.World(scene, gc)
@@ -61,17 +73,17 @@ for case in range(n_cases):
             x, y, yaw = w.start[0], w.start[1], off[2]
             sc = []
             for k in range(n):
-                r32 = world0.scan(x, y, yaw, geo)        # (ONE world for all robots: they map the same room)
+                r32 = world0.scan(x, y, yaw, geos[r])    # (ONE world for all robots: they map the same room)
                 sc.append(spoil(rng, r32) if rng.random() < 0.3 else r32)
                 u = rng.random()
                 step = rng.uniform(0.0, 0.04) if u < 0.2 else rng.uniform(0.05, 0.1)
                 x += step * math.cos(yaw); y += step * math.sin(yaw); yaw += rng.uniform(-0.03, 0.03)
             scans.append(sc)
-            robots.append(T.Robot(O, gc, geo, off, kw))
+            robots.append(T.Robot(O, gc, geos[r], off, kws[r]))
         for rb, sc in zip(robots, scans):
             rb.init_both(og, dg, sc[0])
-        for rb in robots:
-            s = capi.TsdSensorDevice(dg, geo.beams, kw["angle_increment"], kw["angle_min"], kw["max_range"], kw["min_range"], kw["low_refl_range"])
+        for rb, g_ in zip(robots, geos):
+            s = capi.TsdSensorDevice(dg, g_.beams, rb.kw["angle_increment"], rb.kw["angle_min"], rb.kw["max_range"], rb.kw["min_range"], rb.kw["low_refl_range"])
             s.set_pose(rb.pose, rb.rays, rb.rays_local)
             sensors.append(s)
         params = dg.icp_params(kw["icp_iterations"], kw["dist_filter_max"], kw["dist_filter_min"])
@@ -85,13 +97,13 @@ for case in range(n_cases):
             groups = [g for g in (perm[:cut], perm[cut:]) if g]
             order = [i for g in groups for i in g]
             ing = {i: robots[i].ingest(scans[i][k]) for i in order}
-            draws = {i: (tuple(rng.integers(0, 2 ** 31 - 1, m) for m in (geo.beams, kw["size_control_set"], kw["trials"])) if (mode3 and rng.random() < 0.7) else None)
+            draws = {i: (tuple(rng.integers(0, 2 ** 31 - 1, m) for m in (geos[i].beams, kw["size_control_set"], kw["trials"])) if (mode3 and rng.random() < 0.7) else None)
                      for i in order}
             ros = {i: robots[i].localise(og, ing[i][0], ing[i][1], bounds, draws[i]) for i in order}      # all against the grid before the round's pushes
             for i in order:
                 if draws[i] is not None:
                     sc_, ms_, _n = O.scene_from_scan(robots[i].rays_local, ing[i][0], ing[i][1])
-                    sensors[i].preregister(sc_, ms_, kw["trials"], kw["size_control_set"], kw["zrand"], phi_max3, kw["angle_increment"], *draws[i])
+                    sensors[i].preregister(sc_, ms_, kw["trials"], kw["size_control_set"], kw["zrand"], phi_max3, robots[i].kw["angle_increment"], *draws[i])
                     tot["armed_scans"] += 1
             for i in order:
                 robots[i].apply_push(og)                                                            # ... the pushes in the round's order
