@@ -533,6 +533,66 @@ int tsd_map_update_wait(tsd_ctx* ctx, int* n_surface);
 void* tsd_host_alloc(uint64_t bytes);
 void tsd_host_free(void* p);
 
+/* ---- clearance: the Euclidean distance to the nearest occupied cell, and the cost map of nav2's inflation layer ------------------- */
+/* How far is this cell from the nearest obstacle?  Input: an int8 map, width x height, row = y, `stride` bytes from row to row -- a
+ * frame's staged map, a group's merged map, any device map.  In integers throughout (the kernels do no floating point), so a
+ * restatement agrees to the byte (tests/clearance_ref.py).
+ *   O              the cells of the WHOLE map whose value equals 100; there is no obstacle outside the map
+ *   R              the radius in cells, 1 .. TSD_CLEARANCE_MAX_RADIUS
+ *   g(x, y)        min over (ox, y) in O of |x - ox|, capped: min(that, R + 1); R + 1 on a row without an obstacle          (row pass)
+ *   m(x, y)        min over dy in [-R, R] with 0 <= y + dy < height of g(x, y + dy)^2 + dy^2                                (column pass)
+ *   d2(x, y)       m if m <= R*R, else 0xFFFF                                                              (uint16, the distance field)
+ * which is min over (ox, oy) in O of (x - ox)^2 + (y - oy)^2 where that minimum is <= R*R, 0xFFFF otherwise: the cut-off is Euclidean
+ * (at R = 5 an obstacle at offset (3, 4) counts, one at (5, 1) does not).
+ * Cost map (int8) from a table T[0 .. R*R] of int8, s = the source cell:
+ *   d2 <= R*R      c = T[d2];  out = -1 if s == -1 and c < 99, else max(s, c)            (signed; nav2: unknown stays unknown unless
+ *   d2 == 0xFFFF   out = s                                                                 it lies inside the inscribed band)
+ * A window w is the unit of work: only the cells of w are written; the map is read in w grown by R, clipped to the map. */
+#define TSD_CLEARANCE_MAX_RADIUS 255
+/* The table of nav2's inflation layer (host code, no GPU): T[0] = 100; with d = sqrt((double)d2) * cell_size, T[d2] = 99 where
+ * d <= inscribed_radius_m, else clamp((int)(98.0 * exp(-cost_scaling * (d - inscribed_radius_m))), 1, 98) -- nav2's 252 * exp(..) taken
+ * through the 1..252 -> 1..98 scale of its OccupancyGrid publisher.  table: radius_cells^2 + 1 entries.  TSD_E_ARG for a NULL
+ * table, a radius outside 1 .. TSD_CLEARANCE_MAX_RADIUS, a cell size that is not > 0. */
+int tsd_costmap_table(double cell_size, int radius_cells, double inscribed_radius_m, double cost_scaling, int8_t* table);
+/* The generic form, for any map on the context's device (e.g. tsd_group_map_dev): enqueues on the context's stream and waits.
+ * win NULL: the whole map.  table: radius_cells^2 + 1 host entries, NULL: no cost map (cost_dev must be NULL then).  dist2_dev (uint16)
+ * / cost_dev (int8): width x height each, rows of `width` elements, either may be NULL (not both); only the window is written.
+ * Scratch (one bit per cell, one byte per 32 x 32 tile) stays with the context and grows on demand: a repeated call allocates
+ * nothing.  TSD_E_ARG: a NULL map, a side outside 1 .. 65536, stride < width, a radius out of range, an empty window or one not
+ * inside the map, no output, a cost map of this context in flight. */
+int tsd_clearance_dev(tsd_ctx* ctx, const void* map_dev, int width, int height, int stride, const tsd_map_window* win /* NULL: whole */,
+                      int radius_cells, const int8_t* table /* host, NULL: no cost map */, void* dist2_dev /* or NULL */,
+                      void* cost_dev /* or NULL */);
+/* The cost map of the frame just taken: reads the device copy of the map that the context's last tsd_map_frame_* / tsd_map_update_*
+ * left in its frame staging -- the bytes <node>/map carried, so map and cost map never disagree.  map_win: the window that update
+ * returned (NULL: the whole map; width 0: nothing changed, nothing is enqueued, *out_win is empty and wait returns at once).  The cost
+ * map is recomputed in map_win grown by radius_cells and clipped, returned in *out_win; only those rows and columns are copied into
+ * the caller's FULL buffers cost_host (cells*cells int8) and dist2_host (cells*cells uint16; with want_dist2), as tsd_map_update_begin
+ * does -- the staged map differs from the previous one only inside map_win, so d2 can differ only within R of it, and those cells
+ * read obstacles within 2R of it from a map that is complete on the device.  Kernels and copies run on the context's copy stream
+ * behind the frame's event; the grid's stream never waits for them.  The table is tsd_costmap_table(cell size, params).  The
+ * buffers must stay valid until tsd_costmap_wait returns.  TSD_E_ARG: no completed previous frame, a frame in flight, a radius out of
+ * range, a window not inside the map, a cost map already in flight, want_dist2 without dist2_host.  A frame begun while a cost map is
+ * in flight is refused like a second frame.  The grid and its write ledger are not touched. */
+typedef struct {
+  int32_t radius_cells;         /* R */
+  int32_t want_dist2;           /* != 0: the distance field is copied to dist2_host as well */
+  double  inscribed_radius_m;
+  double  cost_scaling;
+} tsd_costmap_params;
+int tsd_costmap_begin(tsd_ctx* ctx, const tsd_costmap_params* params, int8_t* cost_host, uint16_t* dist2_host /* or NULL */,
+                      const tsd_map_window* map_win /* NULL: whole */, tsd_map_window* out_win);
+int tsd_costmap_wait(tsd_ctx* ctx);
+/* Plain device memory on the context's device for a caller without a HIP runtime of its own (a ctypes driver), e.g. a map handed to
+ * tsd_clearance_dev and its outputs: allocation (NULL on failure), release (waits for the context's stream first), and a copy of
+ * `bytes` between host and device (to_device != 0: host to device) on the context's stream, which waits for it. */
+void* tsd_dev_alloc(tsd_ctx* ctx, uint64_t bytes);
+void  tsd_dev_free(tsd_ctx* ctx, void* p);
+int   tsd_dev_copy(tsd_ctx* ctx, void* dst, const void* src, uint64_t bytes, int to_device);
+/* TEST HOOK: on = 0 makes every workgroup of the column pass walk its rows instead of skipping where no tile within R holds an
+ * obstacle.  The outputs are the same byte for byte (tests/test_gpu_clearance.py); only the time differs. */
+int tsd_debug_set_clearance_skip(tsd_ctx* ctx, int on);
+
 /* ---- the map's surface as an ordered point list --------------------------------------------------------------- */
 /* The `coords` array of RayCastAxisAligned2D::calcCoords (RayCastAxisAligned2D.cpp:13-105), point for point and in its serial order:
  * the linear zero crossings of the TSD along every row and column of every initialised tile of the processed ring (tiles 1 .. PX-2 in
@@ -779,7 +839,7 @@ int tsd_fuse(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell_off_x
 
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the ctx stream.  Kernel names: "push_classify", "push_update",
- * "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse". */
+ * "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse", "clearance" (both kernels of tsd_clearance_dev). */
 int tsd_profile_enable(tsd_ctx* ctx, int on);
 /* restrict timing to a comma separated list of kernel names, or "all"; a "/n" suffix times every n-th
  * launch only (two event records cost ~13 us of stream time per timed launch); a name may carry its own

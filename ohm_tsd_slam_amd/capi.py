@@ -114,6 +114,16 @@ class MapWindow(C.Structure):
         return (int(self.x), int(self.y), int(self.width), int(self.height))
 
 
+CLEARANCE_MAX_RADIUS = 255
+DIST2_NONE = 0xFFFF      # the distance field's value where no obstacle lies within the radius
+
+
+class CostmapParams(C.Structure):
+    """tsd_costmap_params"""
+    _fields_ = [("radius_cells", C.c_int32), ("want_dist2", C.c_int32), ("inscribed_radius_m", C.c_double),
+                ("cost_scaling", C.c_double)]
+
+
 class FuseStats(C.Structure):
     """tsd_fuse_stats"""
     _fields_ = [("tiles_materialised", C.c_int64), ("tiles_empty", C.c_int64), ("cells_valid", C.c_int64),
@@ -310,6 +320,16 @@ ABI = {
     "tsd_map_frame_wait": (C.c_int, [C.c_void_p, _ip]),
     "tsd_map_update_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsd_map_update_wait": (C.c_int, [C.c_void_p, _ip]),
+    "tsd_costmap_table": (C.c_int, [C.c_double, C.c_int, C.c_double, C.c_double, _i8p]),
+    "tsd_clearance_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MapWindow), C.c_int, _i8p,
+                                    C.c_void_p, C.c_void_p]),
+    "tsd_costmap_begin": (C.c_int, [C.c_void_p, C.POINTER(CostmapParams), C.c_void_p, C.c_void_p, C.POINTER(MapWindow),
+                                    C.POINTER(MapWindow)]),
+    "tsd_costmap_wait": (C.c_int, [C.c_void_p]),
+    "tsd_debug_set_clearance_skip": (C.c_int, [C.c_void_p, C.c_int]),
+    "tsd_dev_alloc": (C.c_void_p, [C.c_void_p, C.c_uint64]),
+    "tsd_dev_free": (None, [C.c_void_p, C.c_void_p]),
+    "tsd_dev_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
     "tsd_host_alloc": (C.c_void_p, [C.c_uint64]),
     "tsd_host_free": (None, [C.c_void_p]),
     "tsd_store_grid_text": (C.c_int, [C.c_void_p, C.c_char_p]),
@@ -383,7 +403,8 @@ def load_library(path: str | None = None):
                           ("tsd_rnmatch_result", RnMatchResult), ("tsd_map_params", MapParams),
                           ("tsd_fuse_stats", FuseStats), ("tsd_map_window", MapWindow), ("tsd_reloc_params", RelocParams),
                           ("tsd_reloc_result", RelocResult), ("tsd_surface_params", SurfaceParams),
-                          ("tsd_align_params", AlignParams), ("tsd_align_peak", AlignPeak), ("tsd_align_result", AlignResult)):
+                          ("tsd_align_params", AlignParams), ("tsd_align_peak", AlignPeak), ("tsd_align_result", AlignResult),
+                          ("tsd_costmap_params", CostmapParams)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -399,6 +420,49 @@ def device_memory(device: int = 0):
     if rc != 0:
         raise TsdError(f"tsd_device_memory({device}) failed ({rc})")
     return f.value, t.value
+
+
+def costmap_table(cell_size, radius, inscribed_radius_m=0.25, cost_scaling=10.0) -> np.ndarray:
+    """tsd_costmap_table: the int8 table [radius^2 + 1] of nav2's inflation layer on the OccupancyGrid scale (host code: no GPU)"""
+    lib = load_library()
+    tab = np.zeros(max(int(radius), 0) ** 2 + 1, dtype=np.int8)
+    rc = lib.tsd_costmap_table(float(cell_size), int(radius), float(inscribed_radius_m), float(cost_scaling), tab.ctypes.data_as(_i8p))
+    if rc != 0:
+        raise TsdError(f"tsd_costmap_table refused (rc {rc}): radius {radius}, cell size {cell_size}")
+    return tab
+
+
+class DeviceBuffer:
+    """``nbytes`` of plain device memory on a grid's device (tsd_dev_alloc / _free / _copy, through the library's own HIP runtime),
+    for maps handed to ``clearance_of`` and for its outputs.  Free it before the grid is closed."""
+
+    def __init__(self, grid, nbytes: int):
+        self.grid, self.nbytes = grid, int(nbytes)
+        self.ptr = grid.lib.tsd_dev_alloc(grid.h, max(self.nbytes, 1))
+        if not self.ptr:
+            raise TsdError(f"tsd_dev_alloc({nbytes}) failed")
+
+    def upload(self, a: np.ndarray, offset: int = 0):
+        a = np.ascontiguousarray(a)
+        assert offset + a.nbytes <= self.nbytes
+        self.grid._check(self.grid.lib.tsd_dev_copy(self.grid.h, self.ptr + offset, a.ctypes.data, a.nbytes, 1), "tsd_dev_copy")
+
+    def download(self, dtype, count: int, offset: int = 0) -> np.ndarray:
+        out = np.zeros(count, dtype=dtype)
+        assert offset + out.nbytes <= self.nbytes
+        self.grid._check(self.grid.lib.tsd_dev_copy(self.grid.h, out.ctypes.data, self.ptr + offset, out.nbytes, 0), "tsd_dev_copy")
+        return out
+
+    def free(self):
+        if getattr(self, "ptr", None) and getattr(self.grid, "h", None):
+            self.grid.lib.tsd_dev_free(self.grid.h, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def _d(a):
@@ -446,6 +510,9 @@ class TsdGridDevice:
         self.min_y, self.max_y = self.lib.tsd_min_y(self.h), self.lib.tsd_max_y(self.h)
 
     def close(self):
+        for buf in getattr(self, "_dev_bufs", {}).values():
+            buf.free()
+        self._dev_bufs = {}
         if getattr(self, "h", None):
             self.lib.tsd_destroy(self.h)
             self.h = None
@@ -941,6 +1008,93 @@ class TsdGridDevice:
         win = self.map_update_begin(inflate, factor, image, occ, rgb)
         o, r, ns = self.map_update_wait()
         return win, o, r, ns
+
+    # ---- clearance field and cost map (tsd_costmap_table, tsd_clearance_dev, tsd_costmap_begin / _wait)
+    def costmap_table(self, radius, inscribed_radius_m=0.25, cost_scaling=10.0) -> np.ndarray:
+        """tsd_costmap_table at this grid's cell size: int8 [radius^2 + 1]"""
+        return costmap_table(self.cell_size, radius, inscribed_radius_m, cost_scaling)
+
+    def set_clearance_skip(self, on: bool):
+        """test hook: off = every workgroup of the column pass walks its rows (same bytes, tsd_debug_set_clearance_skip)"""
+        self._check(self.lib.tsd_debug_set_clearance_skip(self.h, 1 if on else 0), "tsd_debug_set_clearance_skip")
+
+    def _dev_out(self, name, nbytes):
+        """a device buffer kept by the wrapper for clearance_of's outputs (replaced when a larger one is asked for)"""
+        bufs = self.__dict__.setdefault("_dev_bufs", {})
+        if name not in bufs or bufs[name].nbytes < nbytes:
+            if name in bufs:
+                bufs[name].free()
+            bufs[name] = DeviceBuffer(self, nbytes)
+        return bufs[name]
+
+    def clearance_of(self, dev_ptr: int, width: int, height: int, stride: int, radius: int, window=None, table=None, prefill=None):
+        """tsd_clearance_dev on a device map (``dev_ptr``: int8, ``height`` rows of ``stride`` bytes): (dist2 (height, width)
+        uint16, cost (height, width) int8 or None without a ``table``), copied to the host.  window: (x, y, width, height), None: the
+        whole map; only its cells are written.  prefill: (uint16, int8) values the outputs hold before the call (default 0)."""
+        n = int(width) * int(height)
+        d_d2 = self._dev_out("dist2", 2 * n)
+        d_cost = self._dev_out("cost", n) if table is not None else None
+        p2, pc = prefill if prefill is not None else (0, 0)
+        d_d2.upload(np.full(n, p2, dtype=np.uint16))
+        if d_cost is not None:
+            d_cost.upload(np.full(n, pc, dtype=np.int8))
+        tab = None if table is None else np.ascontiguousarray(table, dtype=np.int8)
+        assert tab is None or tab.size == int(radius) * int(radius) + 1
+        win = None if window is None else C.byref(MapWindow(*[int(v) for v in window]))
+        rc = self.lib.tsd_clearance_dev(self.h, C.c_void_p(dev_ptr), int(width), int(height), int(stride), win, int(radius),
+                                        None if tab is None else tab.ctypes.data_as(_i8p), C.c_void_p(d_d2.ptr),
+                                        None if d_cost is None else C.c_void_p(d_cost.ptr))
+        self.last_rc = rc
+        self._check(rc, "tsd_clearance_dev")
+        d2 = d_d2.download(np.uint16, n).reshape(height, width)
+        cost = None if d_cost is None else d_cost.download(np.int8, n).reshape(height, width)
+        return d2, cost
+
+    def costmap_begin(self, radius, inscribed_radius_m=0.25, cost_scaling=10.0, map_win=None, want_dist2=False, cost=None, dist2=None):
+        """tsd_costmap_begin: the cost map of the frame or update taken last, recomputed in ``map_win`` (x, y, width, height; None:
+        the whole map) grown by ``radius`` and clipped -- the window returned.  Written into the wrapper's pinned buffers, which always
+        hold the full current cost map, or into ``cost`` (cells, cells) int8 / ``dist2`` (cells, cells) uint16 where the caller hands
+        in full C-contiguous buffers of its own (which must live until the wait)."""
+        n = self.cells * self.cells
+        if cost is None:
+            cost = self._pinned("cost", n)
+            dist2 = self._pinned("dist2", 2 * n) if want_dist2 else None
+        else:
+            assert cost.dtype == np.int8 and cost.size == n and cost.flags.c_contiguous
+            assert not want_dist2 or (dist2 is not None and dist2.dtype == np.uint16 and dist2.size == n and dist2.flags.c_contiguous)
+            dist2 = dist2 if want_dist2 else None
+        prm = CostmapParams(int(radius), int(bool(want_dist2)), float(inscribed_radius_m), float(cost_scaling))
+        mw = None if map_win is None else C.byref(MapWindow(*[int(v) for v in map_win]))
+        out = MapWindow()
+        rc = self.lib.tsd_costmap_begin(self.h, C.byref(prm), cost.ctypes.data, None if dist2 is None else dist2.ctypes.data, mw,
+                                        C.byref(out))
+        self.last_rc = rc
+        self._check(rc, "tsd_costmap_begin")
+        self._costmap_bufs = (cost, dist2)       # (kept alive until the wait)
+        return out.as_tuple()
+
+    def costmap_wait(self):
+        """tsd_costmap_wait: (cost (cells, cells) int8, dist2 (cells, cells) uint16 or None) -- copies of the full buffers"""
+        self._check(self.lib.tsd_costmap_wait(self.h), "tsd_costmap_wait")
+        cost, dist2 = self._costmap_bufs
+        self._costmap_bufs = None
+        cost = cost.view(np.int8).reshape(self.cells, self.cells).copy()
+        dist2 = None if dist2 is None else dist2.view(np.uint16).reshape(self.cells, self.cells).copy()
+        return cost, dist2
+
+    def costmap(self, radius, inscribed_radius_m=0.25, cost_scaling=10.0, map_win=None, want_dist2=False, cost=None, dist2=None):
+        """tsd_costmap_begin + _wait: (window, cost, dist2 or None)"""
+        win = self.costmap_begin(radius, inscribed_radius_m, cost_scaling, map_win, want_dist2, cost, dist2)
+        c, d = self.costmap_wait()
+        return win, c, d
+
+    def clearance(self, radius) -> np.ndarray:
+        """Distance of every cell of the frame taken last to the nearest occupied cell, metres as float32 (cells, cells):
+        sqrt(d2) * cell_size, inf beyond ``radius`` cells"""
+        _, _, d2 = self.costmap(radius, want_dist2=True)
+        out = (np.sqrt(d2.astype(np.float64)) * self.cell_size).astype(np.float32)
+        out[d2 == DIST2_NONE] = np.inf
+        return out
 
     def push_stats_total(self, reset=False):
         st = PushStats()

@@ -27,7 +27,7 @@ int set_error(tsd_ctx* ctx, int code, const char* what, hipError_t e)
   return code;
 }
 
-const char* const kKernelNames[] = {"push_classify", "push_update", "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse"};
+const char* const kKernelNames[] = {"push_classify", "push_update", "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse", "clearance"};
 
 bool kernel_is_timed(const tsd_ctx* ctx, const char* name)
 {
@@ -515,6 +515,7 @@ void tsd_destroy(tsd_ctx* ctx)
   reloc_free(ctx);
   surface_free(ctx);
   align_free(ctx);
+  clearance_free(ctx);
   if (ctx->stream) hipStreamDestroy(ctx->stream);
   delete ctx;
 }

@@ -1,5 +1,6 @@
 #include "ThreadGrid.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -11,6 +12,9 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
     ThreadSLAM(*grid),
     _node(node),
     _occGrid(std::make_shared<nav_msgs::msg::OccupancyGrid>()),
+    _publishCostmap(false),
+    _hCost(nullptr),
+    _costmaps(0),
     _width(grid->getCellsX()),
     _height(grid->getCellsY()),
     _cellSize(grid->getCellSize()),
@@ -55,6 +59,36 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
   node->declare_parameter("publish_surface_cloud", false);
 #endif
   _publishSurface = node->get_parameter("publish_surface_cloud").as_bool();
+#if OHM_TSD_SLAM_HAVE_ROS
+  if(!node->has_parameter("publish_costmap"))
+    node->declare_parameter<bool>("publish_costmap", false);
+  if(!node->has_parameter("costmap_inflation_radius"))
+    node->declare_parameter<double>("costmap_inflation_radius", 0.55);
+  if(!node->has_parameter("costmap_inscribed_radius"))
+    node->declare_parameter<double>("costmap_inscribed_radius", 0.25);
+  if(!node->has_parameter("costmap_cost_scaling_factor"))
+    node->declare_parameter<double>("costmap_cost_scaling_factor", 10.0);
+#else
+  node->declare_parameter("publish_costmap", false);
+  node->declare_parameter("costmap_inflation_radius", 0.55);
+  node->declare_parameter("costmap_inscribed_radius", 0.25);
+  node->declare_parameter("costmap_cost_scaling_factor", 10.0);
+#endif
+  _publishCostmap = node->get_parameter("publish_costmap").as_bool();
+  // R = ceil(radius / cell size), where a quotient that is whole up to rounding stays whole (0.55 / 0.025 is 22, not 23)
+  double cellsR = std::ceil(node->get_parameter("costmap_inflation_radius").as_double() / _cellSize - 1e-9);
+  if(!(cellsR >= 1.0))
+    cellsR = 1.0;
+  if(cellsR > (double)TSD_CLEARANCE_MAX_RADIUS)
+  {
+    if(_publishCostmap)
+      std::fprintf(stderr, "ThreadGrid: costmap_inflation_radius is %.0f cells, clamped to %d\n", cellsR, TSD_CLEARANCE_MAX_RADIUS);
+    cellsR = (double)TSD_CLEARANCE_MAX_RADIUS;
+  }
+  _costPrm.radius_cells = static_cast<int32_t>(cellsR);
+  _costPrm.want_dist2 = 0;
+  _costPrm.inscribed_radius_m = node->get_parameter("costmap_inscribed_radius").as_double();
+  _costPrm.cost_scaling = node->get_parameter("costmap_cost_scaling_factor").as_double();
 
   const std::string node_name = _node->get_name();
   _gridPub = node->create_publisher<nav_msgs::msg::OccupancyGrid>(node_name + "/map", rclcpp::QoS(1).reliable().transient_local());
@@ -64,6 +98,13 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
                                                                             rclcpp::QoS(10).reliable().durability_volatile());
   if(_publishSurface)
     _surfacePub = node->create_publisher<sensor_msgs::msg::PointCloud2>(node_name + "/surface", rclcpp::QoS(1).reliable().durability_volatile());
+  if(_publishCostmap)        // (the map's QoS on both topics)
+  {
+    _costmapPub = node->create_publisher<nav_msgs::msg::OccupancyGrid>(node_name + "/costmap", rclcpp::QoS(1).reliable().transient_local());
+    if(_publishUpdates)
+      _costmapUpdatePub = node->create_publisher<map_msgs::msg::OccupancyGridUpdate>(node_name + "/costmap_updates",
+                                                                                     rclcpp::QoS(10).reliable().durability_volatile());
+  }
   _getMapServ = node->create_service<nav_msgs::srv::GetMap>(
     node_name + "/get_map",
     std::bind(&ThreadGrid::getMapServCallBack, this, std::placeholders::_1, std::placeholders::_2));
@@ -82,6 +123,19 @@ ThreadGrid::~ThreadGrid()
   joinThread();
   tsd_host_free(_hOcc);
   tsd_host_free(_hRgb);
+  tsd_host_free(_hCost);
+}
+
+map_msgs::msg::OccupancyGridUpdate ThreadGrid::lastCostmapUpdate(void)
+{
+  std::lock_guard<std::mutex> lk(_msgMutex);
+  return _lastCostmapUpdate;
+}
+
+uint64_t ThreadGrid::costmaps(void)
+{
+  std::lock_guard<std::mutex> lk(_msgMutex);
+  return _costmaps;
 }
 
 uint64_t ThreadGrid::frames(void)
@@ -158,6 +212,8 @@ int ThreadGrid::publish(void)
   if(_publishUpdates && !((size_t)win.width == _width && (size_t)win.height == _height))
   {
     rc = publishUpdate(win);
+    if(rc == TSD_OK && _publishCostmap)
+      rc = publishCostmap(&win);
     if(rc == TSD_OK && _publishSurface)
       rc = publishSurface(_lastUpdate.header);
     return rc;
@@ -187,8 +243,72 @@ int ThreadGrid::publish(void)
   _image.encoding = sensor_msgs::image_encodings::RGB8;
   std::memcpy(_image.data.data(), _hRgb, 3 * cells);
   _pubColorImage->publish(_image);
+  if(_publishCostmap)
+  {
+    rc = publishCostmap(nullptr);
+    if(rc != TSD_OK)
+      return rc;
+  }
   if(_publishSurface)
     return publishSurface(msg.header);
+  return TSD_OK;
+}
+
+// The cost map of the map just published, from the device copy of that very frame.  mapWin == nullptr: behind a full map, a full
+// nav_msgs/OccupancyGrid with the map's info and header.  Otherwise behind the update of window *mapWin: the update's window grown by
+// the inflation radius (what tsd_costmap_begin recomputed and copied into _hCost, which holds the full current cost map) as a
+// map_msgs/OccupancyGridUpdate.
+int ThreadGrid::publishCostmap(const tsd_map_window* mapWin)
+{
+  const size_t cells = (size_t)_width * _height;
+  if(!_hCost)
+    _hCost = static_cast<int8_t*>(tsd_host_alloc(cells));
+  if(!_hCost)
+    return TSD_E_ARG;
+  tsd_ctx* ctx = _grid.context();
+  tsd_map_window out = {0, 0, 0, 0};
+  int rc;
+  {
+    // the grid's mutex only while the call is enqueued, as for the frame
+    std::lock_guard<std::mutex> g(_grid.mutex());
+    rc = tsd_costmap_begin(ctx, &_costPrm, _hCost, nullptr, mapWin, &out);
+  }
+  if(rc != TSD_OK)
+    return rc;
+  rc = tsd_costmap_wait(ctx);
+  if(rc != TSD_OK)
+    return rc;
+  if(!mapWin)
+  {
+    nav_msgs::msg::OccupancyGrid msg;
+    {
+      std::lock_guard<std::mutex> m(_msgMutex);
+      msg.header = _occGrid->header;
+      msg.info = _occGrid->info;
+      _costmaps++;
+    }
+    msg.data.resize(cells);
+    std::memcpy(msg.data.data(), _hCost, cells);
+    _costmapPub->publish(msg);
+    return TSD_OK;
+  }
+  if(out.width == 0 || out.height == 0 || !_costmapUpdatePub)
+    return TSD_OK;
+  map_msgs::msg::OccupancyGridUpdate upd;
+  upd.x = out.x;
+  upd.y = out.y;
+  upd.width = static_cast<uint32_t>(out.width);
+  upd.height = static_cast<uint32_t>(out.height);
+  upd.data.resize((size_t)out.width * out.height);
+  for(int32_t r = 0; r < out.height; r++)
+    std::memcpy(upd.data.data() + (size_t)r * out.width, _hCost + (size_t)(out.y + r) * _width + (size_t)out.x, (size_t)out.width);
+  {
+    std::lock_guard<std::mutex> m(_msgMutex);
+    upd.header = _occGrid->header;
+    _lastCostmapUpdate = upd;
+    _costmaps++;
+  }
+  _costmapUpdatePub->publish(upd);
   return TSD_OK;
 }
 

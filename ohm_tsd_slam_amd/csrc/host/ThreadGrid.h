@@ -6,6 +6,11 @@
 // map_msgs/OccupancyGridUpdate on <node>/map_updates, the form rviz and nav2's static layer listen for.
 // With the parameter publish_surface_cloud (not in the reference; default false) every publication is followed by the map's surface
 // (tsd_surface_extract: calcCoords' sub-cell points with their normals) as sensor_msgs/PointCloud2 on <node>/surface, in the map's frame.
+// With the parameter publish_costmap (not in the reference; default false) every publication is followed by the cost map nav2's
+// inflation layer would compute from the map just published (tsd_costmap_begin / _wait: the exact Euclidean clearance on the device):
+// a full map is followed by a nav_msgs/OccupancyGrid on <node>/costmap, an update by a map_msgs/OccupancyGridUpdate on
+// <node>/costmap_updates for the update's window grown by the inflation radius.  costmap_inflation_radius [m], costmap_inscribed_radius
+// [m] and costmap_cost_scaling_factor are nav2's inflation_radius, the robot's inscribed radius and cost_scaling_factor.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -43,6 +48,14 @@ public:
   sensor_msgs::msg::PointCloud2 lastSurface(void);
   uint64_t surfaces(void);
   std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> mapService() { return _getMapServ; }
+  /** <node>/costmap and <node>/costmap_updates; nullptr unless publish_costmap is set (the latter also needs publish_map_updates) */
+  std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> costmapPublisher() { return _costmapPub; }
+  std::shared_ptr<rclcpp::Publisher<map_msgs::msg::OccupancyGridUpdate>> costmapUpdatePublisher() { return _costmapUpdatePub; }
+  /** the last cost map update message (width 0 before the first one), the messages published on the two topics together, and the
+   *  inflation radius in cells (0 with the parameter off) */
+  map_msgs::msg::OccupancyGridUpdate lastCostmapUpdate(void);
+  uint64_t costmaps(void);
+  int costmapRadiusCells(void) const { return _publishCostmap ? _costPrm.radius_cells : 0; }
 
   /** the get_map service (ThreadGrid.cpp:135-142): the last map with a fresh stamp */
   bool getMapServCallBack(const std::shared_ptr<nav_msgs::srv::GetMap::Request> req,
@@ -54,6 +67,7 @@ protected:
 private:
   int publishUpdate(const tsd_map_window& win);
   int publishSurface(const std_msgs::msg::Header& header);
+  int publishCostmap(const tsd_map_window* mapWin);
 
 private:
   std::shared_ptr<rclcpp::Node> _node;
@@ -68,6 +82,13 @@ private:
   std::shared_ptr<rclcpp::Publisher<sensor_msgs::msg::PointCloud2>> _surfacePub;
   sensor_msgs::msg::PointCloud2 _lastSurface;         // (likewise)
   bool _publishSurface;
+  std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> _costmapPub;
+  std::shared_ptr<rclcpp::Publisher<map_msgs::msg::OccupancyGridUpdate>> _costmapUpdatePub;
+  map_msgs::msg::OccupancyGridUpdate _lastCostmapUpdate;   // (likewise)
+  bool _publishCostmap;
+  tsd_costmap_params _costPrm;
+  int8_t* _hCost;                // page-locked: the full current cost map
+  uint64_t _costmaps;
   unsigned int _width;
   unsigned int _height;
   double _cellSize;

@@ -444,6 +444,49 @@ unsigned long long tsd_node_map_msg(tsd_node* n, int8_t* data_out, double* out12
   return pub->count();
 }
 
+// <node>/costmap and <node>/costmap_updates (parameter publish_costmap): messages published on the two topics together
+unsigned long long tsd_node_costmaps(tsd_node* n) { return (n && n->gridThread) ? n->gridThread->costmaps() : 0; }
+
+// the inflation radius in cells the node computes its cost map with (0 with the parameter off)
+int tsd_node_costmap_radius(tsd_node* n) { return (n && n->gridThread) ? n->gridThread->costmapRadiusCells() : 0; }
+
+// last message on <node>/costmap (map_out layout) and the topic's name into `topic`; returns the topic's publish count.  Without the
+// topic (the parameter is off): 0, an empty name, out12 zeroed.
+unsigned long long tsd_node_costmap(tsd_node* n, int8_t* data_out, double* out12, char* frame_id, int cap, char* topic, int topic_cap)
+{
+  if(topic && topic_cap > 0)
+    topic[0] = 0;
+  if(!n || !n->gridThread || !out12)
+    return 0;
+  auto pub = n->gridThread->costmapPublisher();
+  if(!pub)
+  {
+    for(int i = 0; i < 12; i++) out12[i] = 0.0;
+    if(frame_id && cap > 0) frame_id[0] = 0;
+    return 0;
+  }
+  map_out(pub->last(), data_out, out12, frame_id, cap);
+  if(topic && topic_cap > 0)
+    std::snprintf(topic, (size_t)topic_cap, "%s", pub->topic().c_str());
+  return pub->count();
+}
+
+// last message on <node>/costmap_updates, as tsd_node_map_update_msg; returns the topic's publish count (0 without the topic)
+unsigned long long tsd_node_costmap_update(tsd_node* n, int8_t* data_out, double* out5, char* frame_id, int cap)
+{
+  if(!n || !n->gridThread || !out5)
+    return 0;
+  const map_msgs::msg::OccupancyGridUpdate m = n->gridThread->lastCostmapUpdate();
+  out5[0] = m.x; out5[1] = m.y; out5[2] = m.width; out5[3] = m.height;
+  out5[4] = (double)m.header.stamp.sec * 1e9 + (double)m.header.stamp.nanosec;
+  if(data_out && !m.data.empty())
+    std::memcpy(data_out, m.data.data(), m.data.size());
+  if(frame_id && cap > 0)
+    std::snprintf(frame_id, (size_t)cap, "%s", m.header.frame_id.c_str());
+  auto pub = n->gridThread->costmapUpdatePublisher();
+  return pub ? pub->count() : 0;
+}
+
 // <node>/get_map (ThreadGrid::getMapServCallBack): the last map with a fresh stamp (map_out layout); 1 if the service answered
 int tsd_node_get_map(tsd_node* n, int8_t* data_out, double* out12, char* frame_id, int cap)
 {

@@ -147,7 +147,7 @@ static int ensure_frame_staging(tsd_ctx* ctx, bool image)
   if (!ctx->h_frame_count) TSD_HIP_CHECK(ctx, hipHostMalloc(&ctx->h_frame_count, sizeof(int), hipHostMallocDefault));
   // (a frame's staging is only replaced between frames: the last one's copies are done, tsd_map_frame_wait has seen them)
   if (ctx->d_frame) hipFree(ctx->d_frame);
-  ctx->d_frame = nullptr; ctx->frame_bytes = 0;
+  ctx->d_frame = nullptr; ctx->frame_bytes = 0; ctx->frame_map_valid = false;
   ctx->ledger.frame_lost();               // (a windowed frame has nothing to build on)
   TSD_HIP_CHECK(ctx, hipMalloc(&ctx->d_frame, need));
   // px / py exactly as the reference accumulates them (TsdGrid.cpp:433-486), then the tile ranges of the monotone tables
@@ -181,6 +181,8 @@ static int frame_begin(tsd_ctx* ctx, const tsd_map_params* prm, int8_t* occ_host
 {
   if (!ctx || !prm || !occ_host) return TSD_E_ARG;
   if (ctx->frame_inflight) return set_error(ctx, TSD_E_ARG, (std::string(who) + ": a frame is in flight (tsd_map_frame_wait first)").c_str(), hipSuccess);
+  // (a cost map in flight still reads the staged map on the copy stream)
+  if (ctx->clearance.inflight) return set_error(ctx, TSD_E_ARG, (std::string(who) + ": a cost map is in flight (tsd_costmap_wait first)").c_str(), hipSuccess);
   if (int rc = enter(ctx)) return rc;
   std::lock_guard<std::mutex> lk_order(ctx->order_mutex);
   const bool image = rgb_host != nullptr;
@@ -196,6 +198,7 @@ static int frame_begin(tsd_ctx* ctx, const tsd_map_params* prm, int8_t* occ_host
     return TSD_OK;
   }
   ctx->ledger.frame_started();
+  ctx->frame_map_valid = false;
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t tab_bytes = up(256 + 2 * N * sizeof(double) + 2 * (PX + 1) * sizeof(int));
   int* d_count = reinterpret_cast<int*>(ctx->d_frame);
@@ -258,7 +261,7 @@ static int frame_begin(tsd_ctx* ctx, const tsd_map_params* prm, int8_t* occ_host
     win->width = (u.x1 - u.x0 + 1) * TILE_DIM; win->height = (u.y1 - u.y0 + 1) * TILE_DIM;
   }
   ctx->ledger.frame_enqueued(image, inflate, factor);
-  ctx->frame_empty = false; ctx->frame_inflight = true;
+  ctx->frame_empty = false; ctx->frame_inflight = true; ctx->frame_map_valid = true;
   return TSD_OK;
 }
 
@@ -269,11 +272,19 @@ static int frame_wait(tsd_ctx* ctx, int* n_surface, const char* who)
   ctx->frame_inflight = false;
   if (!ctx->frame_empty) {
     const hipError_t e = hipEventSynchronize(ctx->ev_frame_done);
-    if (e != hipSuccess) { ctx->ledger.frame_lost(); return set_error(ctx, TSD_E_HIP, who, e); }
+    if (e != hipSuccess) { ctx->ledger.frame_lost(); ctx->frame_map_valid = false; return set_error(ctx, TSD_E_HIP, who, e); }
   }
   ctx->frame_empty = false;
   if (n_surface) *n_surface = *ctx->h_frame_count;
   return TSD_OK;
+}
+
+int8_t* frame_staged_map(const tsd_ctx* ctx)
+{
+  if (!ctx->d_frame) return nullptr;
+  const size_t N = (size_t)ctx->grid.N, PX = (size_t)ctx->grid.PX;
+  const size_t tab_bytes = (256 + 2 * N * sizeof(double) + 2 * (PX + 1) * sizeof(int) + 255) & ~(size_t)255;
+  return reinterpret_cast<int8_t*>(ctx->d_frame + tab_bytes);
 }
 
 }  // namespace tsd

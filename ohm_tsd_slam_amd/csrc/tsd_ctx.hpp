@@ -293,6 +293,20 @@ struct tsd_ctx {
   hipEvent_t ev_frame_done = nullptr;               // on stream_io: the frame's copies to the host are done
   bool frame_inflight = false;
   bool frame_empty = false;                         // the frame in flight is a windowed one that nothing was written for: no copy to wait for
+  bool frame_map_valid = false;                     // the staging holds the complete map of the frame or update enqueued last (what
+                                                    // tsd_costmap_begin reads once that frame has been waited for)
+  // clearance field and cost map (clearance.hip: tsd_clearance_dev, tsd_costmap_begin / _wait).  Scratch of the kernels -- the obstacle
+  // bit mask, the per-tile summary, the cost table and its pinned copy -- and the frame's device outputs, all allocated on first use,
+  // grown on demand and kept; at most one cost map in flight
+  struct Clearance {
+    uint8_t* d_mask = nullptr; size_t mask_bytes = 0;
+    uint8_t* d_tiles = nullptr; size_t tiles_bytes = 0;
+    int8_t* d_table = nullptr; int8_t* h_table = nullptr;   // [TSD_CLEARANCE_MAX_RADIUS^2 + 4]; h_table pinned
+    int8_t* d_cost = nullptr; uint16_t* d_dist2 = nullptr; size_t out_cells = 0, dist2_cells = 0;
+    hipEvent_t ev_done = nullptr;            // on stream_io: the cost map's copies to the host are done
+    bool inflight = false, empty = false;
+    int skip = 1;                            // the tile skip of the column pass (tsd_debug_set_clearance_skip: 0 = every block walks)
+  } clearance;
   // TSD-level fusion (fuse.hip).  As the destination: the kernel's sharded counters and their pinned copy.  As a member: events of its
   // own -- "every grid write enqueued so far" on its stream / its push stream, "the fusion that read this grid last is done" (recorded
   // on the destination's stream; the member's streams wait for it at once) -- all created on first use
@@ -570,6 +584,8 @@ int launch_wait_seq_multi(tsd_ctx* ctx, int n, const unsigned long long* const* 
 void reloc_free(tsd_ctx* ctx);               // reloc.hip: releases tsd_ctx::reloc (tsd_destroy)
 void surface_free(tsd_ctx* ctx);             // surface.hip: releases tsd_ctx::surface (tsd_destroy)
 void align_free(tsd_ctx* ctx);               // align.hip: releases tsd_ctx::align (tsd_destroy)
+void clearance_free(tsd_ctx* ctx);           // clearance.hip: releases tsd_ctx::clearance (tsd_destroy)
+int8_t* frame_staged_map(const tsd_ctx* ctx);   // map_publish.hip: the frame staging's map (cells * cells int8), nullptr without a staging
 int launch_calibrate(tsd_ctx* ctx, double* t, double* w, size_t n);
 int launch_occupancy(tsd_ctx* ctx, int8_t* d_out, int inflate, int inflate_factor);
 size_t occ_heads_bytes();

@@ -48,6 +48,10 @@ HOST_ABI = {
     "tsd_node_map_update_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_surface": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
+    "tsd_node_costmaps": (C.c_ulonglong, [C.c_void_p]),
+    "tsd_node_costmap_radius": (C.c_int, [C.c_void_p]),
+    "tsd_node_costmap": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int, C.c_char_p, C.c_int]),
+    "tsd_node_costmap_update": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_grid_lock": (None, [C.c_void_p]),
@@ -354,6 +358,34 @@ class SlamNode:
         return {"x": int(info[0]), "y": int(info[1]), "width": w, "height": h, "stamp_ns": int(info[4]),
                 "frame_id": frame.value.decode(), "data": data.reshape(h, w), "count": int(n)}
 
+    def costmaps(self) -> int:
+        """messages on <node>/costmap and <node>/costmap_updates so far (parameter publish_costmap; 0 with it off)"""
+        return int(self.lib.tsd_node_costmaps(self.h))
+
+    def costmap_radius_cells(self) -> int:
+        """the inflation radius in cells: ceil(costmap_inflation_radius / cellsize), at most 255 (0 with publish_costmap off)"""
+        return int(self.lib.tsd_node_costmap_radius(self.h))
+
+    def costmap_msg(self) -> dict:
+        """the last nav_msgs/OccupancyGrid on <node>/costmap (``map_msg``'s fields), its publish count and the topic's name
+        (``topic`` None: the parameter is off, there is no such topic)"""
+        topic = C.create_string_buffer(256)
+        n, m = self._map_dict(lambda d, i, f, c: self.lib.tsd_node_costmap(self.h, d, i, f, c, topic, 256))
+        m["count"] = int(n)
+        m["topic"] = topic.value.decode() or None
+        return m
+
+    def costmap_update_msg(self) -> dict:
+        """the last map_msgs/OccupancyGridUpdate on <node>/costmap_updates (``map_update_msg``'s fields) and the number published"""
+        info = np.zeros(5)
+        frame = C.create_string_buffer(256)
+        self.lib.tsd_node_costmap_update(self.h, None, info.ctypes.data_as(_dp), frame, 256)
+        w, h = int(info[2]), int(info[3])
+        data = np.zeros(w * h, dtype=np.int8)
+        n = self.lib.tsd_node_costmap_update(self.h, data.ctypes.data, info.ctypes.data_as(_dp), frame, 256)
+        return {"x": int(info[0]), "y": int(info[1]), "width": w, "height": h, "stamp_ns": int(info[4]),
+                "frame_id": frame.value.decode(), "data": data.reshape(h, w), "count": int(n)}
+
     def surface_msg(self) -> dict:
         """the last sensor_msgs/PointCloud2 on <node>/surface (parameter publish_surface_cloud): ``points`` as (width, 6) float32 in
         the order of ``fields`` (x y z normal_x normal_y normal_z) and the number published (0: no message, the parameter is off)"""
@@ -519,7 +551,8 @@ class GridView(capi.TsdGridDevice):
                "download_tiles", "upload_tiles", "digest", "occupancy", "occupancy_into", "calibrate_rmw", "profile", "store_text",
                "load_text", "color_image", "push_stats_total", "profile_reset", "profile_get", "profile_spread", "profile_samples", "tsdpdf_match",
                "relocalize", "debug_reloc_scores", "debug_reloc_peaks", "surface_extract", "surface_fetch", "surface_points",
-               "surface_dev", "align_points", "debug_align_scores", "debug_align_peaks", "debug_align_sums")
+               "surface_dev", "align_points", "debug_align_scores", "debug_align_peaks", "debug_align_sums",
+               "clearance_of", "costmap_begin")
 
     def __init__(self, ctx, node=None):  # noqa: D401 - does not call the base constructor on purpose
         self.lib = capi.load_library()
