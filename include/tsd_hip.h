@@ -28,6 +28,7 @@ extern "C" {
 #define TSD_E_NODEVICE   -3   /* no usable gfx950 device */
 #define TSD_E_BOUNDS     -4   /* freeFootprint rectangle outside the grid (TsdGrid.cpp:617-622) */
 #define TSD_E_CAPACITY   -5   /* more beams / points than the kernels are built for */
+#define TSD_E_NOMEM      -6   /* the device cannot hold a call's scratch (tsd_frontiers_*); see tsd_last_error */
 
 #define TSD_TILE_DIM     32   /* SlamNode.cpp:77 hard-codes LAYOUT_32x32 */
 #define TSD_TILE_PITCH   33   /* 32 cells + 1 halo (TsdGridPartition.cpp:97) */
@@ -593,6 +594,66 @@ int   tsd_dev_copy(tsd_ctx* ctx, void* dst, const void* src, uint64_t bytes, int
  * obstacle.  The outputs are the same byte for byte (tests/test_gpu_clearance.py); only the time differs. */
 int tsd_debug_set_clearance_skip(tsd_ctx* ctx, int on);
 
+/* ---- frontiers: where to drive to make the map bigger --------------------------------------------------------- */
+/* The free cells that border unknown space, grouped into connected frontiers, each with its size, the sums its centroid follows from,
+ * its bounding box, and whether a robot standing on a seed cell can reach it.  Input: an int8 map on the context's device, width x
+ * height, `stride` bytes from row to row (as tsd_clearance_dev); bytes beyond `width` in a row are never read.  Sides 1 .. 32768, so a
+ * linear index y * width + x fits a uint32 and 0xFFFFFFFF means "none".  In integers throughout (the kernels do no floating point): a
+ * restatement agrees to the byte and the list's order is fixed (tests/frontier_ref.py).
+ *   unknown        v < 0
+ *   traversable    0 <= v <= free_max           (free_max = 0: the free cells of an occupancy map; larger: the low costs of a cost map)
+ *   frontier cell  a traversable cell with at least one of its four edge neighbours INSIDE THE MAP unknown (the border is not unknown)
+ *   frontier       an 8-connected component of frontier cells; its root is the smallest linear index among its cells
+ *   region         a 4-connected component of traversable cells, root likewise (a diagonal gap in a wall is no passage)
+ *   used seed      a seed inside the map on a traversable cell; other seeds are ignored, *seeds_used counts the used ones
+ *   reachable      1 where a cell of the frontier lies in the region of a used seed, else 0; -1 in every record with n_seeds == 0
+ *                  (no regions are computed then)
+ * Outputs: a label image, uint32 width x height, rows of `width` elements, every cell written -- the root's linear index on frontier
+ * cells, 0xFFFFFFFF elsewhere, for ALL frontiers whatever min_size is -- and the list of tsd_frontier records of the frontiers with
+ * size >= min_size in ascending root index.  The centroid is host arithmetic: (sum_x / size, sum_y / size) in cells. */
+#define TSD_FRONTIER_MAX_SEEDS 16
+#define TSD_FRONTIER_MAX_SIDE  32768
+#define TSD_FRONTIER_NONE      0xFFFFFFFFu
+typedef struct {
+  int32_t  root_x, root_y;      /* the frontier's cell with the smallest linear index */
+  uint32_t size;                /* cells */
+  int32_t  reachable;           /* 1 / 0; -1: no seeds were given */
+  uint64_t sum_x, sum_y;        /* sums of the cells' x and y */
+  int32_t  min_x, min_y, max_x, max_y;   /* bounding box, inclusive */
+} tsd_frontier;                 /* 48 bytes */
+typedef struct {
+  int32_t  free_max;            /* 0 .. 99 */
+  uint32_t min_size;            /* >= 1: smaller frontiers keep their labels but get no record */
+  int32_t  n_seeds;             /* 0 .. TSD_FRONTIER_MAX_SEEDS */
+  int32_t  reserved;
+  const int32_t* seeds_xy;      /* n_seeds pairs (x, y) of cells, host memory; may be NULL with n_seeds == 0 */
+} tsd_frontier_params;
+/* The generic form, for any map on the context's device (a group's merged map, a cost map): enqueues on the context's stream and
+ * waits.  *n: the list's length, *seeds_used (may be NULL): the seeds that counted.  Scratch stays with the context and grows on
+ * demand -- 4 bytes per cell for the labels, 4 for the roots' ranks, 4 more for the regions' labels once a call brings seeds, one
+ * count per 32 cells of a row, 2 bytes per tile, the records -- so a repeated call at the same size allocates nothing.  Both forms
+ * share that scratch and the result: one frontier call at a time per context, from the call to the last fetch of its result -- the
+ * caller's duty (the facade: obvious::TsdGrid::frontierMutex, taken by ThreadGrid and ThreadGridGroup alike).  TSD_E_NOMEM
+ * (tsd_last_error says which buffer) where the device cannot hold it; the previous result is gone then.  TSD_E_ARG, with the previous
+ * result left fetchable: a NULL map or params, a side outside 1 .. TSD_FRONTIER_MAX_SIDE, stride < width, free_max outside 0 .. 99,
+ * min_size < 1, n_seeds outside 0 .. TSD_FRONTIER_MAX_SEEDS, seeds_xy NULL with n_seeds > 0, a NULL n. */
+int tsd_frontiers_dev(tsd_ctx* ctx, const void* map_dev, int width, int height, int stride, const tsd_frontier_params* params,
+                      int* n, int* seeds_used /* or NULL */);
+/* The same for the map that the context's last tsd_map_frame_* / tsd_map_update_* left in its frame staging (cells x cells, the bytes
+ * <node>/map carried).  Runs where the cost map runs: on the context's copy stream behind the frame's event, never on the grid's
+ * stream, and waits for it.  TSD_E_ARG also without a completed frame and with a frame or a cost map in flight.  The grid and its write
+ * ledger are not touched. */
+int tsd_frontiers_frame(tsd_ctx* ctx, const tsd_frontier_params* params, int* n, int* seeds_used /* or NULL */);
+/* Records first .. first + count - 1 of the last result.  TSD_E_ARG for a range outside [0, n) (count == 0 is served anywhere in
+ * [0, n]) and for a NULL out with count > 0. */
+int tsd_frontiers_fetch(tsd_ctx* ctx, int first, int count, tsd_frontier* out);
+/* The last result on the device: the records (n of them), the label image (uint32, width x height of that call).  Valid until the
+ * next frontier call on the context or tsd_destroy.  TSD_E_ARG without a result. */
+int tsd_frontiers_dev_ptrs(tsd_ctx* ctx, const void** records_dev, const void** labels_dev, int* n);
+/* What the last call counted (each pointer may be NULL): the frontiers before min_size, and the unions the seam pass made between
+ * tiles for the frontiers' and for the regions' labels. */
+int tsd_frontiers_counts(tsd_ctx* ctx, int* n_all, int* seam_unions, int* region_seam_unions);
+
 /* ---- the map's surface as an ordered point list --------------------------------------------------------------- */
 /* The `coords` array of RayCastAxisAligned2D::calcCoords (RayCastAxisAligned2D.cpp:13-105), point for point and in its serial order:
  * the linear zero crossings of the TSD along every row and column of every initialised tile of the processed ring (tiles 1 .. PX-2 in
@@ -839,7 +900,9 @@ int tsd_fuse(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell_off_x
 
 /* ---- measurement ----------------------------------------------------------------------------- */
 /* Per-kernel HIP-event timing on the ctx stream.  Kernel names: "push_classify", "push_update",
- * "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse", "clearance" (both kernels of tsd_clearance_dev). */
+ * "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse", "clearance" (both kernels of tsd_clearance_dev), and the passes of
+ * tsd_frontiers_dev: "frontier_tile", "frontier_seam", "frontier_flatten" (each once for the frontiers and once more for the regions
+ * where seeds are given), "frontier_rank" (count, scan, emit), "frontier_stats" (with the min_size compaction). */
 int tsd_profile_enable(tsd_ctx* ctx, int on);
 /* restrict timing to a comma separated list of kernel names, or "all"; a "/n" suffix times every n-th
  * launch only (two event records cost ~13 us of stream time per timed launch); a name may carry its own

@@ -124,6 +124,28 @@ class CostmapParams(C.Structure):
                 ("cost_scaling", C.c_double)]
 
 
+FRONTIER_MAX_SEEDS = 16
+FRONTIER_NONE = 0xFFFFFFFF   # the label image's value off the frontier cells
+
+
+class Frontier(C.Structure):
+    """tsd_frontier"""
+    _fields_ = [("root_x", C.c_int32), ("root_y", C.c_int32), ("size", C.c_uint32), ("reachable", C.c_int32),
+                ("sum_x", C.c_uint64), ("sum_y", C.c_uint64), ("min_x", C.c_int32), ("min_y", C.c_int32),
+                ("max_x", C.c_int32), ("max_y", C.c_int32)]
+
+
+FRONTIER_DTYPE = np.dtype([("root_x", "<i4"), ("root_y", "<i4"), ("size", "<u4"), ("reachable", "<i4"), ("sum_x", "<u8"),
+                           ("sum_y", "<u8"), ("min_x", "<i4"), ("min_y", "<i4"), ("max_x", "<i4"), ("max_y", "<i4")])
+assert FRONTIER_DTYPE.itemsize == C.sizeof(Frontier) == 48
+
+
+class FrontierParams(C.Structure):
+    """tsd_frontier_params"""
+    _fields_ = [("free_max", C.c_int32), ("min_size", C.c_uint32), ("n_seeds", C.c_int32), ("reserved", C.c_int32),
+                ("seeds_xy", C.POINTER(C.c_int32))]
+
+
 class FuseStats(C.Structure):
     """tsd_fuse_stats"""
     _fields_ = [("tiles_materialised", C.c_int64), ("tiles_empty", C.c_int64), ("cells_valid", C.c_int64),
@@ -327,6 +349,11 @@ ABI = {
                                     C.POINTER(MapWindow)]),
     "tsd_costmap_wait": (C.c_int, [C.c_void_p]),
     "tsd_debug_set_clearance_skip": (C.c_int, [C.c_void_p, C.c_int]),
+    "tsd_frontiers_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FrontierParams), _ip, _ip]),
+    "tsd_frontiers_frame": (C.c_int, [C.c_void_p, C.POINTER(FrontierParams), _ip, _ip]),
+    "tsd_frontiers_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "tsd_frontiers_dev_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _ip]),
+    "tsd_frontiers_counts": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),
     "tsd_dev_alloc": (C.c_void_p, [C.c_void_p, C.c_uint64]),
     "tsd_dev_free": (None, [C.c_void_p, C.c_void_p]),
     "tsd_dev_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
@@ -404,7 +431,8 @@ def load_library(path: str | None = None):
                           ("tsd_fuse_stats", FuseStats), ("tsd_map_window", MapWindow), ("tsd_reloc_params", RelocParams),
                           ("tsd_reloc_result", RelocResult), ("tsd_surface_params", SurfaceParams),
                           ("tsd_align_params", AlignParams), ("tsd_align_peak", AlignPeak), ("tsd_align_result", AlignResult),
-                          ("tsd_costmap_params", CostmapParams)):
+                          ("tsd_costmap_params", CostmapParams), ("tsd_frontier", Frontier),
+                          ("tsd_frontier_params", FrontierParams)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -1095,6 +1123,58 @@ class TsdGridDevice:
         out = (np.sqrt(d2.astype(np.float64)) * self.cell_size).astype(np.float32)
         out[d2 == DIST2_NONE] = np.inf
         return out
+
+    # ---- frontiers (tsd_frontiers_dev / _frame / _fetch / _dev_ptrs)
+    @staticmethod
+    def _frontier_params(free_max, min_size, seeds):
+        """(tsd_frontier_params, the seed array it points into -- to be kept alive over the call)"""
+        xy = np.ascontiguousarray(np.asarray(list(seeds), dtype=np.int32).reshape(-1, 2))
+        prm = FrontierParams(int(free_max), int(min_size), int(xy.shape[0]), 0,
+                             xy.ctypes.data_as(C.POINTER(C.c_int32)) if xy.shape[0] else None)
+        return prm, xy
+
+    def _frontier_result(self, n, width, height):
+        rec = np.zeros(n, dtype=FRONTIER_DTYPE)
+        self._check(self.lib.tsd_frontiers_fetch(self.h, 0, n, rec.ctypes.data), "tsd_frontiers_fetch")
+        _, labels_dev, n2 = self.frontiers_dev_ptrs()
+        assert n2 == n
+        labels = np.zeros((int(height), int(width)), dtype=np.uint32)
+        self._check(self.lib.tsd_dev_copy(self.h, labels.ctypes.data, labels_dev, labels.nbytes, 0), "tsd_dev_copy")
+        return rec, labels
+
+    def frontiers_dev_ptrs(self):
+        """tsd_frontiers_dev_ptrs: (records_dev, labels_dev, n) of the last frontier call, valid until the next one"""
+        r, l, n = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        self._check(self.lib.tsd_frontiers_dev_ptrs(self.h, C.byref(r), C.byref(l), C.byref(n)), "tsd_frontiers_dev_ptrs")
+        return r.value, l.value, n.value
+
+    def frontiers_counts(self):
+        """tsd_frontiers_counts: (frontiers before min_size, seam unions of the frontiers' labels, of the regions' labels)"""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self.lib.tsd_frontiers_counts(self.h, C.byref(a), C.byref(b), C.byref(c)), "tsd_frontiers_counts")
+        return a.value, b.value, c.value
+
+    def frontiers_of(self, dev_ptr: int, width: int, height: int, stride: int, free_max=0, min_size=1, seeds=()):
+        """tsd_frontiers_dev on a device map (``dev_ptr``: int8, ``height`` rows of ``stride`` bytes): (records as a structured
+        array of FRONTIER_DTYPE in ascending root index, labels (height, width) uint32, seeds_used).  seeds: (x, y) cells."""
+        prm, xy = self._frontier_params(free_max, min_size, seeds)
+        n, used = C.c_int(0), C.c_int(0)
+        rc = self.lib.tsd_frontiers_dev(self.h, C.c_void_p(dev_ptr), int(width), int(height), int(stride), C.byref(prm),
+                                        C.byref(n), C.byref(used))
+        self.last_rc = rc
+        self._check(rc, "tsd_frontiers_dev")
+        rec, labels = self._frontier_result(n.value, width, height)
+        return rec, labels, used.value
+
+    def frontiers(self, free_max=0, min_size=1, seeds=()):
+        """tsd_frontiers_frame: the same for the map of the frame or update taken last (cells x cells)"""
+        prm, xy = self._frontier_params(free_max, min_size, seeds)
+        n, used = C.c_int(0), C.c_int(0)
+        rc = self.lib.tsd_frontiers_frame(self.h, C.byref(prm), C.byref(n), C.byref(used))
+        self.last_rc = rc
+        self._check(rc, "tsd_frontiers_frame")
+        rec, labels = self._frontier_result(n.value, self.cells, self.cells)
+        return rec, labels, used.value
 
     def push_stats_total(self, reset=False):
         st = PushStats()

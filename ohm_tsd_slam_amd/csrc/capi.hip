@@ -27,7 +27,8 @@ int set_error(tsd_ctx* ctx, int code, const char* what, hipError_t e)
   return code;
 }
 
-const char* const kKernelNames[] = {"push_classify", "push_update", "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse", "clearance"};
+const char* const kKernelNames[] = {"push_classify", "push_update", "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse", "clearance",
+                                   "frontier_tile", "frontier_seam", "frontier_flatten", "frontier_rank", "frontier_stats"};
 
 bool kernel_is_timed(const tsd_ctx* ctx, const char* name)
 {
@@ -516,6 +517,7 @@ void tsd_destroy(tsd_ctx* ctx)
   surface_free(ctx);
   align_free(ctx);
   clearance_free(ctx);
+  frontier_free(ctx);
   if (ctx->stream) hipStreamDestroy(ctx->stream);
   delete ctx;
 }

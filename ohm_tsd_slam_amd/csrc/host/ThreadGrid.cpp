@@ -15,6 +15,9 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
     _publishCostmap(false),
     _hCost(nullptr),
     _costmaps(0),
+    _publishFrontiers(false),
+    _frontierMinSize(8),
+    _frontierClouds(0),
     _width(grid->getCellsX()),
     _height(grid->getCellsY()),
     _cellSize(grid->getCellSize()),
@@ -89,6 +92,18 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
   _costPrm.want_dist2 = 0;
   _costPrm.inscribed_radius_m = node->get_parameter("costmap_inscribed_radius").as_double();
   _costPrm.cost_scaling = node->get_parameter("costmap_cost_scaling_factor").as_double();
+#if OHM_TSD_SLAM_HAVE_ROS
+  if(!node->has_parameter("publish_frontiers"))
+    node->declare_parameter<bool>("publish_frontiers", false);
+  if(!node->has_parameter("frontier_min_size"))
+    node->declare_parameter<int>("frontier_min_size", 8);
+#else
+  node->declare_parameter("publish_frontiers", false);
+  node->declare_parameter("frontier_min_size", 8);
+#endif
+  _publishFrontiers = node->get_parameter("publish_frontiers").as_bool();
+  const int64_t minSize = node->get_parameter("frontier_min_size").as_int();
+  _frontierMinSize = minSize < 1 ? 1u : (minSize > 0x7FFFFFFF ? 0x7FFFFFFFu : static_cast<uint32_t>(minSize));
 
   const std::string node_name = _node->get_name();
   _gridPub = node->create_publisher<nav_msgs::msg::OccupancyGrid>(node_name + "/map", rclcpp::QoS(1).reliable().transient_local());
@@ -105,6 +120,8 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
       _costmapUpdatePub = node->create_publisher<map_msgs::msg::OccupancyGridUpdate>(node_name + "/costmap_updates",
                                                                                      rclcpp::QoS(10).reliable().durability_volatile());
   }
+  if(_publishFrontiers)
+    _frontierPub = node->create_publisher<sensor_msgs::msg::PointCloud2>(node_name + "/frontiers", rclcpp::QoS(1).reliable().durability_volatile());
   _getMapServ = node->create_service<nav_msgs::srv::GetMap>(
     node_name + "/get_map",
     std::bind(&ThreadGrid::getMapServCallBack, this, std::placeholders::_1, std::placeholders::_2));
@@ -136,6 +153,18 @@ uint64_t ThreadGrid::costmaps(void)
 {
   std::lock_guard<std::mutex> lk(_msgMutex);
   return _costmaps;
+}
+
+sensor_msgs::msg::PointCloud2 ThreadGrid::lastFrontiers(void)
+{
+  std::lock_guard<std::mutex> lk(_msgMutex);
+  return _lastFrontiers;
+}
+
+uint64_t ThreadGrid::frontierClouds(void)
+{
+  std::lock_guard<std::mutex> lk(_msgMutex);
+  return _frontierClouds;
 }
 
 uint64_t ThreadGrid::frames(void)
@@ -214,6 +243,8 @@ int ThreadGrid::publish(void)
     rc = publishUpdate(win);
     if(rc == TSD_OK && _publishCostmap)
       rc = publishCostmap(&win);
+    if(rc == TSD_OK && _publishFrontiers)
+      rc = publishFrontiers(_lastUpdate.header);
     if(rc == TSD_OK && _publishSurface)
       rc = publishSurface(_lastUpdate.header);
     return rc;
@@ -249,8 +280,114 @@ int ThreadGrid::publish(void)
     if(rc != TSD_OK)
       return rc;
   }
+  if(_publishFrontiers)
+  {
+    rc = publishFrontiers(msg.header);
+    if(rc != TSD_OK)
+      return rc;
+  }
   if(_publishSurface)
     return publishSurface(msg.header);
+  return TSD_OK;
+}
+
+// The frontiers of the frame staged last.  The call runs on the context's copy stream and waits for it; the grid's mutex is not
+// needed (the grid is not read).  The caller holds _publishMutex, so the staging is not replaced meanwhile; the grid's frontierMutex
+// keeps the context's frontier scratch and result to one call at a time, this worker's or a ThreadGridGroup's on the same context,
+// from the call to the fetch.
+static int frameFrontiers(obvious::TsdGrid& grid, const int32_t* seedsXy, int n, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed)
+{
+  std::lock_guard<std::mutex> fl(grid.frontierMutex());
+  tsd_ctx* ctx = grid.context();
+  tsd_frontier_params prm;
+  prm.free_max = 0;
+  prm.min_size = minSize;
+  prm.n_seeds = n;
+  prm.reserved = 0;
+  prm.seeds_xy = n > 0 ? seedsXy : nullptr;
+  int count = 0, used = 0;
+  int rc = tsd_frontiers_frame(ctx, &prm, &count, &used);
+  if(rc != TSD_OK)
+    return rc;
+  out->resize((size_t)count);
+  if(count > 0)
+    rc = tsd_frontiers_fetch(ctx, 0, count, out->data());
+  if(seedsUsed)
+    *seedsUsed = used;
+  return rc;
+}
+
+void ThreadGrid::mapPlacement(double* originRes)
+{
+  std::lock_guard<std::mutex> m(_msgMutex);
+  originRes[0] = _occGrid->info.origin.position.x;
+  originRes[1] = _occGrid->info.origin.position.y;
+  originRes[2] = static_cast<double>(_occGrid->info.resolution);
+}
+
+int ThreadGrid::frontiers(const int32_t* seedsXy, int n, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed, double* originRes)
+{
+  if(!out || (n > 0 && !seedsXy))
+    return TSD_E_ARG;
+  std::lock_guard<std::mutex> lk(_publishMutex);
+  if(originRes)
+    mapPlacement(originRes);
+  return frameFrontiers(_grid, seedsXy, n, minSize, out, seedsUsed);
+}
+
+// The frontiers of the map just published as a cloud, one point per frontier of at least frontier_min_size cells in ascending root
+// index: float32 x y z -- the centroid of the frontier's cell centres in the map's frame,
+//   x = (float)(((double)sum_x / (double)size + 0.5) * (double)info.resolution + origin.x), y likewise, z = 0
+// with the resolution (a float32, as a subscriber reads it) and the origin <node>/map carries -- then uint32 size and int32 min_x min_y max_x max_y (cells).  No seeds: ThreadGrid knows no poses.
+int ThreadGrid::publishFrontiers(const std_msgs::msg::Header& header)
+{
+  std::vector<tsd_frontier> recs;
+  const int rc = frameFrontiers(_grid, nullptr, 0, _frontierMinSize, &recs, nullptr);
+  if(rc != TSD_OK)
+    return rc;
+  sensor_msgs::msg::PointCloud2 cloud;
+  cloud.header = header;
+  cloud.height = 1;
+  cloud.width = static_cast<uint32_t>(recs.size());
+  static const char* const names[8] = {"x", "y", "z", "size", "min_x", "min_y", "max_x", "max_y"};
+  cloud.fields.resize(8);
+  for(unsigned i = 0; i < 8; i++)
+  {
+    cloud.fields[i].name = names[i];
+    cloud.fields[i].offset = 4 * i;
+    cloud.fields[i].datatype = i < 3 ? sensor_msgs::msg::PointField::FLOAT32
+                                     : (i == 3 ? sensor_msgs::msg::PointField::UINT32 : sensor_msgs::msg::PointField::INT32);
+    cloud.fields[i].count = 1;
+  }
+  cloud.is_bigendian = false;
+  cloud.point_step = 32;
+  cloud.row_step = cloud.point_step * cloud.width;
+  cloud.is_dense = true;
+  cloud.data.resize((size_t)cloud.row_step);
+  double ox, oy, res;
+  {
+    std::lock_guard<std::mutex> m(_msgMutex);
+    ox = _occGrid->info.origin.position.x;
+    oy = _occGrid->info.origin.position.y;
+    res = static_cast<double>(_occGrid->info.resolution);
+  }
+  for(size_t i = 0; i < recs.size(); i++)
+  {
+    const tsd_frontier& f = recs[i];
+    const float c[3] = {static_cast<float>(((double)f.sum_x / (double)f.size + 0.5) * res + ox),
+                        static_cast<float>(((double)f.sum_y / (double)f.size + 0.5) * res + oy), 0.f};
+    const int32_t box[4] = {f.min_x, f.min_y, f.max_x, f.max_y};
+    uint8_t* p = cloud.data.data() + i * cloud.point_step;
+    std::memcpy(p, c, 12);
+    std::memcpy(p + 12, &f.size, 4);
+    std::memcpy(p + 16, box, 16);
+  }
+  {
+    std::lock_guard<std::mutex> m(_msgMutex);
+    _lastFrontiers = cloud;
+    _frontierClouds++;
+  }
+  _frontierPub->publish(cloud);
   return TSD_OK;
 }
 

@@ -11,9 +11,13 @@
 // a full map is followed by a nav_msgs/OccupancyGrid on <node>/costmap, an update by a map_msgs/OccupancyGridUpdate on
 // <node>/costmap_updates for the update's window grown by the inflation radius.  costmap_inflation_radius [m], costmap_inscribed_radius
 // [m] and costmap_cost_scaling_factor are nav2's inflation_radius, the robot's inscribed radius and cost_scaling_factor.
+// With the parameter publish_frontiers (not in the reference; default false) every publication, full or update, is followed by the
+// frontiers of the map just published (tsd_frontiers_frame: the free cells that border unknown space as 8-connected components, on
+// the device) as sensor_msgs/PointCloud2 on <node>/frontiers, one point per frontier of at least frontier_min_size cells (default 8).
 #pragma once
 #include <cstdint>
 #include <memory>
+#include <vector>
 #include <mutex>
 
 #include "ThreadSLAM.h"
@@ -56,6 +60,19 @@ public:
   map_msgs::msg::OccupancyGridUpdate lastCostmapUpdate(void);
   uint64_t costmaps(void);
   int costmapRadiusCells(void) const { return _publishCostmap ? _costPrm.radius_cells : 0; }
+  /** <node>/frontiers; nullptr unless publish_frontiers is set */
+  std::shared_ptr<rclcpp::Publisher<sensor_msgs::msg::PointCloud2>> frontierPublisher() { return _frontierPub; }
+  /** the last frontier message (no fields before the first one), the number published, and frontier_min_size */
+  sensor_msgs::msg::PointCloud2 lastFrontiers(void);
+  uint64_t frontierClouds(void);
+  uint32_t frontierMinSize(void) const { return _frontierMinSize; }
+  /** The frontiers of the map published last (tsd_frontiers_frame), between two publications: records of at least minSize cells in
+   *  ascending root index, reachability from the n seed cells seedsXy (x, y pairs; n == 0: -1 everywhere), the number of seeds that
+   *  counted, and in originRes the origin x, y and the resolution (a float32) <node>/map carries.  Holds the publish mutex, so the map
+   *  is the one the records belong to, and the grid's frontierMutex for the call.  TSD_E_ARG before the first publication. */
+  int frontiers(const int32_t* seedsXy, int n, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed, double* originRes);
+  /** origin x, y and resolution of <node>/map: fixed by the parameters at construction, the same before and after a publication */
+  void mapPlacement(double* originRes);
 
   /** the get_map service (ThreadGrid.cpp:135-142): the last map with a fresh stamp */
   bool getMapServCallBack(const std::shared_ptr<nav_msgs::srv::GetMap::Request> req,
@@ -68,6 +85,7 @@ private:
   int publishUpdate(const tsd_map_window& win);
   int publishSurface(const std_msgs::msg::Header& header);
   int publishCostmap(const tsd_map_window* mapWin);
+  int publishFrontiers(const std_msgs::msg::Header& header);
 
 private:
   std::shared_ptr<rclcpp::Node> _node;
@@ -89,6 +107,11 @@ private:
   tsd_costmap_params _costPrm;
   int8_t* _hCost;                // page-locked: the full current cost map
   uint64_t _costmaps;
+  std::shared_ptr<rclcpp::Publisher<sensor_msgs::msg::PointCloud2>> _frontierPub;
+  sensor_msgs::msg::PointCloud2 _lastFrontiers;       // (likewise)
+  bool _publishFrontiers;
+  uint32_t _frontierMinSize;
+  uint64_t _frontierClouds;
   unsigned int _width;
   unsigned int _height;
   double _cellSize;

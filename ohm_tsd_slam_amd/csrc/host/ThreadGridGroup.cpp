@@ -151,6 +151,70 @@ int ThreadGridGroup::publish(void)
   return TSD_OK;
 }
 
+int ThreadGridGroup::frontiers(const double* gridXy, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed, int32_t* seedsXy,
+                               double* originCs)
+{
+  if(!gridXy || !out || _members.size() > (size_t)TSD_FRONTIER_MAX_SEEDS)
+    return TSD_E_ARG;
+  std::lock_guard<std::mutex> lk(_publishMutex);      // (the merged map on the device stays as the last publication left it)
+  const double cs = static_cast<double>(_grid.getCellSize());
+  {
+    std::lock_guard<std::mutex> m(_msgMutex);
+    if(_frames == 0)
+      return TSD_E_ARG;
+    if(originCs)
+    {
+      originCs[0] = _occGrid->info.origin.position.x;
+      originCs[1] = _occGrid->info.origin.position.y;
+      originCs[2] = static_cast<double>(_occGrid->info.resolution);
+    }
+  }
+  int32_t x0 = 0, y0 = 0;
+  if(tsd_group_corner(_group, &x0, &y0) != TSD_OK)
+    return TSD_E_ARG;
+  std::vector<int32_t> seeds(2 * _members.size(), -1);
+  for(size_t i = 0; i < _members.size(); i++)
+  {
+    double T[9];
+    if(tsd_group_member_transform(_group, static_cast<int>(i), T) != TSD_OK)
+      return TSD_E_ARG;
+    const double x = gridXy[2 * i], y = gridXy[2 * i + 1];
+    const double fx = std::floor((T[0] * x + T[1] * y + T[2]) / cs) - (double)x0, fy = std::floor((T[3] * x + T[4] * y + T[5]) / cs) - (double)y0;
+    if(fx >= 0.0 && fx < (double)_width && fy >= 0.0 && fy < (double)_height)       // (false for a NaN)
+    {
+      seeds[2 * i] = static_cast<int32_t>(fx);
+      seeds[2 * i + 1] = static_cast<int32_t>(fy);
+    }
+  }
+  if(seedsXy)
+    std::memcpy(seedsXy, seeds.data(), seeds.size() * sizeof(int32_t));
+  tsd_frontier_params prm;
+  prm.free_max = 0;
+  prm.min_size = minSize < 1u ? 1u : minSize;
+  prm.n_seeds = static_cast<int32_t>(_members.size());
+  prm.reserved = 0;
+  prm.seeds_xy = seeds.data();
+  int count = 0, used = 0, rc;
+  {
+    // member 0's context and stream carry the call: its frontierMutex, because that context's frontier scratch also serves member
+    // 0's own ThreadGrid (whose frame-form calls do not take the grid's mutex), then its grid's mutex, as for every call on that stream
+    std::lock_guard<std::mutex> fl(_members[0].grid->frontierMutex());
+    std::lock_guard<std::mutex> g(_members[0].grid->mutex());
+    tsd_ctx* ctx = _members[0].grid->context();
+    rc = tsd_frontiers_dev(ctx, tsd_group_map_dev(_group), static_cast<int>(_width), static_cast<int>(_height), static_cast<int>(_width),
+                           &prm, &count, &used);
+    if(rc == TSD_OK)
+    {
+      out->resize((size_t)count);
+      if(count > 0)
+        rc = tsd_frontiers_fetch(ctx, 0, count, out->data());
+    }
+  }
+  if(seedsUsed)
+    *seedsUsed = used;
+  return rc;
+}
+
 int ThreadGridGroup::fuse(obvious::TsdGrid* dst)
 {
   if(!dst || !dst->valid())

@@ -56,6 +56,16 @@ public:
    *  device library refuses. */
   void setTransforms(const std::vector<std::array<double, 9>>& T);
 
+  /** The frontiers of the merged map published last (tsd_frontiers_dev on the group's device map, on member 0's context), with one
+   *  seed per member: gridXy[2i], gridXy[2i + 1] is member i's current position in ITS grid's coordinates [m] (NaN: no pose yet, the
+   *  seed lies outside the map), carried into the merged map by the group's placement -- tsd_group_member_transform, then
+   *  floor(. / cell size) minus the window's corner (tsd_group_corner).  out: the records of at least minSize cells in ascending root
+   *  index (member 0's frontierMutex and grid mutex are held from the call to the fetch: its ThreadGrid uses the same scratch); seedsXy
+   *  (2 per member): the seed cells; originCs: the merged map's origin x, y and its resolution (the message's float32).  TSD_E_ARG before the
+   *  first publication. */
+  int frontiers(const double* gridXy, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed, int32_t* seedsXy, double* originCs);
+  size_t members(void) const { return _members.size(); }
+
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }
   std::shared_ptr<rclcpp::Service<nav_msgs::srv::GetMap>> mapService() { return _getMapServ; }
   bool getMapServCallBack(const std::shared_ptr<nav_msgs::srv::GetMap::Request> req,

@@ -1,9 +1,11 @@
 // facade_capi.cpp -- a flat C surface over the C++ facade so that the Python test / bench drivers can
 // exercise ThreadLocalize / ThreadMapping / ThreadGrid exactly as SlamNode wires them (SlamNode.cpp:27-129): one
 // TsdGrid, one ThreadMapping, one ThreadGrid woken every occ_grid_time_interval, N ThreadLocalize sharing them, laser callbacks per robot.
+#include <algorithm>
 #include <array>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +28,7 @@ struct tsd_node;
 struct tsd_fleet
 {
   std::vector<tsd_node*> nodes;
+  std::vector<tsd_frontier> frontiers;    // the last tsd_fleet_frontiers
   ThreadGridGroup* group = nullptr;
   obvious::TsdGrid* fused = nullptr;      // the fleet's own grid: the TSD-level fusion of the nodes' grids (created by the first fusion)
 };
@@ -45,6 +48,7 @@ struct tsd_node
   std::vector<uint64_t> submitted;
   bool synchronous = false;
   bool fused = true;
+  std::vector<tsd_frontier> frontiers;    // the last tsd_node_frontiers
 };
 
 extern "C" {
@@ -487,6 +491,84 @@ unsigned long long tsd_node_costmap_update(tsd_node* n, int8_t* data_out, double
   return pub ? pub->count() : 0;
 }
 
+// <node>/frontiers (parameter publish_frontiers): the last sensor_msgs/PointCloud2, as tsd_node_surface; returns the number published
+unsigned long long tsd_node_frontier_cloud(tsd_node* n, uint8_t* data_out, double* out4, char* text, int cap)
+{
+  if(!n || !n->gridThread || !out4)
+    return 0;
+  const sensor_msgs::msg::PointCloud2 m = n->gridThread->lastFrontiers();
+  out4[0] = m.width; out4[1] = m.point_step; out4[2] = (double)m.header.stamp.sec * 1e9 + (double)m.header.stamp.nanosec;
+  out4[3] = (double)m.fields.size();
+  if(data_out && !m.data.empty())
+    std::memcpy(data_out, m.data.data(), m.data.size());
+  if(text && cap > 0)
+  {
+    std::string t = m.header.frame_id + "|";
+    for(size_t i = 0; i < m.fields.size(); i++)
+      t += (i ? "," : "") + m.fields[i].name;
+    std::snprintf(text, (size_t)cap, "%s", t.c_str());
+  }
+  return n->gridThread->frontierClouds();
+}
+
+// frontier_min_size as the node read it
+unsigned tsd_node_frontier_min_size(tsd_node* n) { return (n && n->gridThread) ? n->gridThread->frontierMinSize() : 0u; }
+
+// a pose's cell in a map with origin (ox, oy): floor((p - o) / cs); (-1, -1) for a pose that is not finite or far outside
+static void pose_cell(double px, double py, double ox, double oy, double cs, int32_t* xy)
+{
+  const double fx = std::floor((px - ox) / cs), fy = std::floor((py - oy) / cs);
+  const bool ok = fx >= 0.0 && fx < 2147483647.0 && fy >= 0.0 && fy < 2147483647.0;
+  xy[0] = ok ? static_cast<int32_t>(fx) : -1;
+  xy[1] = ok ? static_cast<int32_t>(fy) : -1;
+}
+
+// The frontiers of the map the node published last (ThreadGrid::frontiers), kept for tsd_node_frontiers_fetch.  n_seeds < 0: one seed
+// per robot of the node, the cell of its last estimated pose.  min_size 0: frontier_min_size.  seeds_out (2 * TSD_FRONTIER_MAX_SEEDS
+// int32) / n_seeds_out: the seeds taken; origin_cs: the map's origin x, y and its resolution.  Returns TSD_OK or the error code.
+int tsd_node_frontiers(tsd_node* n, const int32_t* seeds_xy, int n_seeds, unsigned min_size, int* count, int* seeds_used,
+                       int32_t* seeds_out, int* n_seeds_out, double* origin_cs)
+{
+  if(!n || !n->gridThread || !count || n_seeds > TSD_FRONTIER_MAX_SEEDS || (n_seeds > 0 && !seeds_xy))
+    return TSD_E_ARG;
+  // (a map's origin and resolution are fixed when the node is built: the seeds' cells use the values the call returns below)
+  double place[3];
+  n->gridThread->mapPlacement(place);
+  const double ox = place[0], oy = place[1], cs = place[2];
+  int32_t seeds[2 * TSD_FRONTIER_MAX_SEEDS];
+  int ns = n_seeds;
+  if(n_seeds < 0)
+  {
+    ns = static_cast<int>(std::min<size_t>(n->localizers.size(), TSD_FRONTIER_MAX_SEEDS));
+    for(int r = 0; r < ns; r++)
+    {
+      const auto pose = n->localizers[(size_t)r]->posePublisher()->last();
+      pose_cell(pose.pose.position.x, pose.pose.position.y, ox, oy, cs, &seeds[2 * r]);
+    }
+  }
+  else
+    std::memcpy(seeds, seeds_xy, (size_t)(2 * ns) * sizeof(int32_t));
+  const int rc = n->gridThread->frontiers(seeds, ns, min_size ? min_size : n->gridThread->frontierMinSize(), &n->frontiers, seeds_used, place);
+  if(rc != TSD_OK)
+    return rc;
+  *count = static_cast<int>(n->frontiers.size());
+  if(seeds_out)
+    std::memcpy(seeds_out, seeds, (size_t)(2 * ns) * sizeof(int32_t));
+  if(n_seeds_out)
+    *n_seeds_out = ns;
+  if(origin_cs)
+  {
+    origin_cs[0] = place[0]; origin_cs[1] = place[1]; origin_cs[2] = place[2];
+  }
+  return TSD_OK;
+}
+
+void tsd_node_frontiers_fetch(tsd_node* n, tsd_frontier* out)
+{
+  if(n && out && !n->frontiers.empty())
+    std::memcpy(out, n->frontiers.data(), n->frontiers.size() * sizeof(tsd_frontier));
+}
+
 // <node>/get_map (ThreadGrid::getMapServCallBack): the last map with a fresh stamp (map_out layout); 1 if the service answered
 int tsd_node_get_map(tsd_node* n, int8_t* data_out, double* out12, char* frame_id, int cap)
 {
@@ -638,6 +720,46 @@ int tsd_fleet_fused_image_msg(tsd_fleet* f, uint8_t* data_out, double* out5, cha
 
 // one merge and publication now, on the caller's thread (what a wake-up of the worker does); TSD_OK or the error
 int tsd_fleet_publish_merged(tsd_fleet* f) { return (f && f->group) ? f->group->publish() : TSD_E_ARG; }
+
+// The frontiers of the merged map published last with one seed per node: robot 0's last estimated pose, taken from the map frame into
+// the node's grid coordinates by the node's own map origin and carried on by the group (ThreadGridGroup::frontiers).  Kept for
+// tsd_fleet_frontiers_fetch.  seeds_out: 2 int32 per node, *n_seeds_out: the nodes; origin_cs: the merged map's origin x, y and its
+// resolution.  At most TSD_FRONTIER_MAX_SEEDS nodes (TSD_E_ARG beyond).
+int tsd_fleet_frontiers(tsd_fleet* f, unsigned min_size, int* count, int* seeds_used, int32_t* seeds_out, int* n_seeds_out, double* origin_cs)
+{
+  if(!f || !f->group || !count)
+    return TSD_E_ARG;
+  std::vector<double> xy(2 * f->nodes.size());
+  for(size_t i = 0; i < f->nodes.size(); i++)
+  {
+    tsd_node* n = f->nodes[i];
+    const double nan = std::nan("");
+    xy[2 * i] = xy[2 * i + 1] = nan;
+    if(n->localizers.empty() || !n->gridThread)
+      continue;
+    const auto pose = n->localizers[0]->posePublisher()->last();
+    if(n->localizers[0]->posePublisher()->count() == 0)
+      continue;
+    // (the origin a node's map carries is fixed by its parameters: -(W / 2 + offset), whether or not a map was published yet)
+    const double W = (double)n->grid->getCellsX() * (double)n->grid->getCellSize();
+    const double ox = -(W * 0.5 + n->node->get_parameter("x_offset").as_double()), oy = -(W * 0.5 + n->node->get_parameter("y_offset").as_double());
+    xy[2 * i] = pose.pose.position.x - ox;
+    xy[2 * i + 1] = pose.pose.position.y - oy;
+  }
+  const int rc = f->group->frontiers(xy.data(), min_size ? min_size : 1u, &f->frontiers, seeds_used, seeds_out, origin_cs);
+  if(rc != TSD_OK)
+    return rc;
+  *count = static_cast<int>(f->frontiers.size());
+  if(n_seeds_out)
+    *n_seeds_out = static_cast<int>(f->nodes.size());
+  return TSD_OK;
+}
+
+void tsd_fleet_frontiers_fetch(tsd_fleet* f, tsd_frontier* out)
+{
+  if(f && out && !f->frontiers.empty())
+    std::memcpy(out, f->frontiers.data(), f->frontiers.size() * sizeof(tsd_frontier));
+}
 unsigned long long tsd_fleet_merged_frames(tsd_fleet* f) { return (f && f->group) ? f->group->frames() : 0; }
 
 // last message on <node>/merged_map (map_out layout); returns the publish count
@@ -664,6 +786,10 @@ tsd_ctx* tsd_node_grid_ctx(tsd_node* n) { return n->grid ? n->grid->context() : 
 // node's worker threads may be running takes it around each call, like the facade's own classes do
 void tsd_node_grid_lock(tsd_node* n) { if(n && n->grid) n->grid->mutex().lock(); }
 void tsd_node_grid_unlock(tsd_node* n) { if(n && n->grid) n->grid->mutex().unlock(); }
+// obvious::TsdGrid::frontierMutex for a caller that runs tsd_frontiers_* on the node's context itself: taken BEFORE tsd_node_grid_lock,
+// held until the result is fetched
+void tsd_node_frontier_lock(tsd_node* n) { if(n && n->grid) n->grid->frontierMutex().lock(); }
+void tsd_node_frontier_unlock(tsd_node* n) { if(n && n->grid) n->grid->frontierMutex().unlock(); }
 
 // SlamNode::~SlamNode shutdown order (SlamNode.cpp:131-152): localisers, then ThreadGrid (its timer first), then the mapper
 void tsd_node_destroy(tsd_node* n)

@@ -214,10 +214,16 @@ public:
 
   tsd_ctx* context() { return _ctx; }
   std::mutex& mutex() { return _mutex; }
+  // The context's frontier scratch and result (tsd_frontiers_*) belong to one call at a time, and a frame-form call does not take
+  // mutex(): whoever runs a frontier call on this grid's context -- its own ThreadGrid, a ThreadGridGroup that borrows the context
+  // for its merged map -- holds this from before the call until the records are fetched.  Order: a worker's publish mutex, then
+  // this, then mutex().
+  std::mutex& frontierMutex() { return _frontierMutex; }
 protected:
   tsd_ctx* _ctx;
   std::unique_ptr<ScanBatcher> _batcher;
   std::mutex _mutex;
+  std::mutex _frontierMutex;
   bool _initialPushAccomplished;
 };
 

@@ -93,7 +93,7 @@ struct Image {
 };
 // the surface list on <node>/surface (sensor_msgs/PointCloud2): unordered cloud, height 1, point_step bytes per point
 struct PointField {
-  static constexpr uint8_t FLOAT32 = 7;
+  static constexpr uint8_t INT32 = 5, UINT32 = 6, FLOAT32 = 7;
   std::string name; uint32_t offset = 0; uint8_t datatype = 0; uint32_t count = 0;
 };
 struct PointCloud2 {

@@ -307,6 +307,18 @@ struct tsd_ctx {
     bool inflight = false, empty = false;
     int skip = 1;                            // the tile skip of the column pass (tsd_debug_set_clearance_skip: 0 = every block walks)
   } clearance;
+  // frontiers (frontier.hip: tsd_frontiers_dev / _frame / _fetch / _dev_ptrs).  Scratch of the kernels and the last result, allocated on
+  // first use, grown on demand and kept.  Every call waits for its own work, so nothing of this is ever in flight between calls
+  struct Frontier {
+    uint32_t* d_lab = nullptr; uint32_t* d_rank = nullptr; size_t cells = 0;      // the frontiers' labels, the roots' ranks
+    uint32_t* d_lab_t = nullptr; size_t cells_t = 0;                              // the regions' labels (calls with seeds only)
+    uint8_t* d_any = nullptr; size_t tiles = 0;                                   // [2][tiles]: a tile holds a frontier / a traversable cell
+    uint32_t* d_seg = nullptr; size_t segs = 0;                                   // roots per 32 cells of a row, then the scan's block sums
+    tsd_frontier* d_rec = nullptr; size_t recs = 0;
+    uint32_t* d_res = nullptr; uint32_t* h_res = nullptr;                         // the call's counters and the seeds' roots; h_res pinned
+    int n = -1, n_all = 0, W = 0, H = 0;                                          // the last result (n < 0: none)
+    int seam_unions = 0, region_seam_unions = 0;
+  } frontier;
   // TSD-level fusion (fuse.hip).  As the destination: the kernel's sharded counters and their pinned copy.  As a member: events of its
   // own -- "every grid write enqueued so far" on its stream / its push stream, "the fusion that read this grid last is done" (recorded
   // on the destination's stream; the member's streams wait for it at once) -- all created on first use
@@ -585,6 +597,7 @@ void reloc_free(tsd_ctx* ctx);               // reloc.hip: releases tsd_ctx::rel
 void surface_free(tsd_ctx* ctx);             // surface.hip: releases tsd_ctx::surface (tsd_destroy)
 void align_free(tsd_ctx* ctx);               // align.hip: releases tsd_ctx::align (tsd_destroy)
 void clearance_free(tsd_ctx* ctx);           // clearance.hip: releases tsd_ctx::clearance (tsd_destroy)
+void frontier_free(tsd_ctx* ctx);            // frontier.hip: releases tsd_ctx::frontier (tsd_destroy)
 int8_t* frame_staged_map(const tsd_ctx* ctx);   // map_publish.hip: the frame staging's map (cells * cells int8), nullptr without a staging
 int launch_calibrate(tsd_ctx* ctx, double* t, double* w, size_t n);
 int launch_occupancy(tsd_ctx* ctx, int8_t* d_out, int inflate, int inflate_factor);

@@ -52,6 +52,14 @@ HOST_ABI = {
     "tsd_node_costmap_radius": (C.c_int, [C.c_void_p]),
     "tsd_node_costmap": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int, C.c_char_p, C.c_int]),
     "tsd_node_costmap_update": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
+    "tsd_node_frontier_cloud": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
+    "tsd_node_frontier_min_size": (C.c_uint, [C.c_void_p]),
+    "tsd_node_frontiers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, _ip, _ip, C.c_void_p, _ip, _dp]),
+    "tsd_node_frontiers_fetch": (None, [C.c_void_p, C.c_void_p]),
+    "tsd_fleet_frontiers": (C.c_int, [C.c_void_p, C.c_uint, _ip, _ip, C.c_void_p, _ip, _dp]),
+    "tsd_node_frontier_lock": (None, [C.c_void_p]),
+    "tsd_node_frontier_unlock": (None, [C.c_void_p]),
+    "tsd_fleet_frontiers_fetch": (None, [C.c_void_p, C.c_void_p]),
     "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_grid_lock": (None, [C.c_void_p]),
@@ -386,6 +394,38 @@ class SlamNode:
         return {"x": int(info[0]), "y": int(info[1]), "width": w, "height": h, "stamp_ns": int(info[4]),
                 "frame_id": frame.value.decode(), "data": data.reshape(h, w), "count": int(n)}
 
+    def frontier_msg(self) -> dict:
+        """the last sensor_msgs/PointCloud2 on <node>/frontiers (parameter publish_frontiers), one point per frontier of at least
+        frontier_min_size cells in ascending root index: ``points`` as a structured array of FRONTIER_POINT -- float32 x y z, the
+        centroid in the map's frame, (float32)((sum / size + 0.5) * resolution + origin) -- and the number published (0: no message)"""
+        info = np.zeros(4)
+        text = C.create_string_buffer(512)
+        self.lib.tsd_node_frontier_cloud(self.h, None, info.ctypes.data_as(_dp), text, 512)
+        w, step = int(info[0]), int(info[1])
+        data = np.zeros(max(w * step, 1), dtype=np.uint8)
+        n = self.lib.tsd_node_frontier_cloud(self.h, data.ctypes.data, info.ctypes.data_as(_dp), text, 512)
+        frame, fields = text.value.decode().split("|")
+        pts = data[:w * step].view(FRONTIER_POINT) if w and step == FRONTIER_POINT.itemsize else np.zeros(0, dtype=FRONTIER_POINT)
+        return {"width": w, "height": 1 if n else 0, "point_step": step, "stamp_ns": int(info[2]), "frame_id": frame,
+                "fields": [f for f in fields.split(",") if f], "points": pts, "count": int(n)}
+
+    def frontier_min_size(self) -> int:
+        return int(self.lib.tsd_node_frontier_min_size(self.h))
+
+    def frontiers(self, seeds=None, min_size=None) -> dict:
+        """The frontiers of the map published last (tsd_frontiers_frame), reachability included: ``records`` (capi.FRONTIER_DTYPE, at
+        least ``min_size`` cells -- default frontier_min_size -- in ascending root index), ``centroids`` (n, 2) float64 in the map's
+        frame [m], (sum / size + 0.5) * resolution + origin, ``seeds`` the (x, y) cells taken, ``seeds_used``.  seeds None: one per
+        robot, the cell of its current pose; else (x, y) cells of the map."""
+        if seeds is None:
+            xy, ns = None, -1
+        else:
+            xy = np.ascontiguousarray(np.asarray(list(seeds), dtype=np.int32).reshape(-1, 2))
+            ns = xy.shape[0]
+        return _frontier_dict(lambda c, u, so, no, oc: self.lib.tsd_node_frontiers(
+            self.h, None if xy is None or ns == 0 else xy.ctypes.data, ns, int(min_size or 0), c, u, so, no, oc),
+            lambda out: self.lib.tsd_node_frontiers_fetch(self.h, out), "tsd_node_frontiers")
+
     def surface_msg(self) -> dict:
         """the last sensor_msgs/PointCloud2 on <node>/surface (parameter publish_surface_cloud): ``points`` as (width, 6) float32 in
         the order of ``fields`` (x y z normal_x normal_y normal_z) and the number published (0: no message, the parameter is off)"""
@@ -415,6 +455,27 @@ class SlamNode:
 
     def grid(self) -> "GridView":
         return GridView(self.lib.tsd_node_grid_ctx(self.h), self)
+
+
+FRONTIER_POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("size", "<u4"), ("min_x", "<i4"), ("min_y", "<i4"),
+                           ("max_x", "<i4"), ("max_y", "<i4")])
+
+
+def _frontier_dict(call, fetch, what):
+    count, used, n_seeds = C.c_int(0), C.c_int(0), C.c_int(0)
+    seeds = np.zeros(2 * capi.FRONTIER_MAX_SEEDS, dtype=np.int32)
+    origin_cs = np.zeros(3)
+    rc = call(C.byref(count), C.byref(used), seeds.ctypes.data, C.byref(n_seeds), origin_cs.ctypes.data_as(_dp))
+    if rc != 0:
+        raise capi.TsdError(f"{what} failed ({rc}): no map published yet?")
+    rec = np.zeros(count.value, dtype=capi.FRONTIER_DTYPE)
+    if count.value:
+        fetch(rec.ctypes.data)
+    size = rec["size"].astype(np.float64)
+    cen = np.stack([(rec["sum_x"].astype(np.float64) / size + 0.5) * origin_cs[2] + origin_cs[0],
+                    (rec["sum_y"].astype(np.float64) / size + 0.5) * origin_cs[2] + origin_cs[1]], axis=1)
+    return {"records": rec, "centroids": cen, "seeds": [tuple(int(v) for v in seeds[2 * k:2 * k + 2]) for k in range(n_seeds.value)],
+            "seeds_used": used.value, "origin": origin_cs[:2].copy(), "resolution": float(origin_cs[2])}
 
 
 class SlamFleet:
@@ -449,6 +510,13 @@ class SlamFleet:
         if rc != 0:
             raise capi.TsdError(f"tsd_fleet_publish_merged failed ({rc})")
         return self.merged_map_msg()
+
+    def frontiers(self, min_size=1) -> dict:
+        """The frontiers of the merged map published last with one seed per node -- the cell of that node's current pose in the
+        merged map, carried there by the group's placement -- as ``SlamNode.frontiers`` returns them: what an exploration allocator
+        for the fleet consumes."""
+        return _frontier_dict(lambda c, u, so, no, oc: self.lib.tsd_fleet_frontiers(self.h, int(min_size), c, u, so, no, oc),
+                              lambda out: self.lib.tsd_fleet_frontiers_fetch(self.h, out), "tsd_fleet_frontiers")
 
     def merged_frames(self) -> int:
         return int(self.lib.tsd_fleet_merged_frames(self.h))
@@ -552,7 +620,7 @@ class GridView(capi.TsdGridDevice):
                "load_text", "color_image", "push_stats_total", "profile_reset", "profile_get", "profile_spread", "profile_samples", "tsdpdf_match",
                "relocalize", "debug_reloc_scores", "debug_reloc_peaks", "surface_extract", "surface_fetch", "surface_points",
                "surface_dev", "align_points", "debug_align_scores", "debug_align_peaks", "debug_align_sums",
-               "clearance_of", "costmap_begin")
+               "clearance_of", "costmap_begin", "frontiers_of", "frontiers")
 
     def __init__(self, ctx, node=None):  # noqa: D401 - does not call the base constructor on purpose
         self.lib = capi.load_library()
@@ -565,17 +633,27 @@ class GridView(capi.TsdGridDevice):
         self.min_x, self.max_x = self.lib.tsd_min_x(ctx), self.lib.tsd_max_x(ctx)
         self.min_y, self.max_y = self.lib.tsd_min_y(ctx), self.lib.tsd_max_y(ctx)
 
+    # these also use the context's frontier scratch, which the node's ThreadGrid (and a fleet's group) use: the grid's frontierMutex
+    # is taken first and held until the records and labels are fetched
+    _FRONTIER = ("frontiers_of", "frontiers")
+
     def __getattribute__(self, name):
         attr = object.__getattribute__(self, name)
         if name in GridView._LOCKED and callable(attr):
             node = object.__getattribute__(self, "_node")
             if node is not None and getattr(node, "h", None):
+                scratch = name in GridView._FRONTIER and hasattr(node.lib, "tsd_node_frontier_lock")
+
                 def locked(*a, **k):
+                    if scratch:
+                        node.lib.tsd_node_frontier_lock(node.h)
                     node.lib.tsd_node_grid_lock(node.h)
                     try:
                         return attr(*a, **k)
                     finally:
                         node.lib.tsd_node_grid_unlock(node.h)
+                        if scratch:
+                            node.lib.tsd_node_frontier_unlock(node.h)
                 return locked
         return attr
 
