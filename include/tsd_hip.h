@@ -654,6 +654,101 @@ int tsd_frontiers_dev_ptrs(tsd_ctx* ctx, const void** records_dev, const void** 
  * tiles for the frontiers' and for the regions' labels. */
 int tsd_frontiers_counts(tsd_ctx* ctx, int* n_all, int* seam_unions, int* region_seam_unions);
 
+/* ---- routes: what it costs to drive to a cell, which robot is nearest, and the way there ------------------------ */
+/* The cost-to-go field of an int8 map from up to 16 seed cells (the robots), the cheapest cell of every frontier with the seed it is
+ * cheapest from, and the paths.  Input: an int8 map on the context's device as for the frontiers -- width x height, `stride` bytes
+ * from row to row, bytes beyond `width` in a row never read, sides 1 .. TSD_FRONTIER_MAX_SIDE.  In integers throughout (the kernels
+ * do no floating point), so a restatement agrees to the byte (tests/route_ref.py).
+ *   traversable    0 <= v <= free_max, free_max in 0 .. 99                                                  (the frontiers' rule)
+ *   W[v]           the weight of a traversable cell of value v: a host table of uint8 W[0 .. free_max], each 1 .. 255; NULL: all 1
+ *   neighbour k    k = 0 .. 7 in this order: (-1,0) (1,0) (0,-1) (0,1) (-1,-1) (1,-1) (-1,1) (1,1)
+ *   move a -> b    both cells inside the map and traversable; a diagonal move also needs both cells it cuts, (a.x, b.y) and (b.x, a.y),
+ *                  traversable -- a diagonal gap in a wall is no passage, so the cells a seed reaches are its 4-connected region
+ *   cost of a move c_k * W[v_b], the weight of the cell entered; c_k = 5 for k < 4, 7 for the diagonals
+ *   used seed      a seed inside the map on a traversable cell (*seeds_used counts them); seed i keeps its index i of the caller's
+ *                  list whether or not earlier seeds were used
+ *   key(cell)      uint32 (d << 4) | i: the minimum over all used seeds i and all paths from seed i to the cell of
+ *                  (path cost << 4) | i -- d is the least cost, i the lowest seed index that attains it; a seed's cell has d = 0
+ *   limit          only d <= limit counts, 1 <= limit <= TSD_ROUTE_MAX_DIST; 0 means TSD_ROUTE_MAX_DIST.  The largest step is
+ *                  7 * 255 = 1785, so no candidate d + step leaves 28 bits
+ *   every other cell -- not traversable, not reached, beyond the limit -- holds TSD_ROUTE_NONE
+ * The weights are positive, so the key image is the unique fixed point of key[b] = min(key[b], key[a] + (c_k * W[v_b] << 4)) over
+ * all moves, started from the seeds; candidates beyond the limit are dropped, which is exact because every prefix of a path within the
+ * limit is within the limit.  The result does not depend on the order of the work.
+ * Output: the key image, uint32 width x height, rows of `width` elements, every cell written.
+ *   goal of a frontier   over the frontier's cells with a key, the minimum of (key << 32) | linear index: the cheapest cell to reach,
+ *                        the smallest index among ties, and in the key the nearest robot
+ *   path to a cell b     from b with d > 0 step to a = b - offset_k for the first k in the order above where a -> b is a move and
+ *                        key[a] + (c_k * W[v_b] << 4) == key[b]; b is written, then a, ... the seed's cell (d = 0) last */
+#define TSD_ROUTE_NONE     0xFFFFFFFFu
+#define TSD_ROUTE_MAX_DIST 0x0FFFF000u
+#define TSD_ROUTE_MAX_ROUNDS (1 << 20)
+#define TSD_ROUTE_MAX_GOALS  4096
+#define TSD_ROUTE_MAP      0            /* tsd_route_frame's sources: the staged map of the last frame or update ... */
+#define TSD_ROUTE_COSTMAP  1            /* ... the cost map of the last completed tsd_costmap_begin / _wait */
+typedef struct {
+  int32_t  free_max;            /* 0 .. 99 */
+  int32_t  n_seeds;             /* 1 .. TSD_FRONTIER_MAX_SEEDS */
+  const int32_t* seeds_xy;      /* n_seeds pairs (x, y) of cells, host memory */
+  const uint8_t* weights;       /* W[0 .. free_max], host memory; NULL: all 1 */
+  uint32_t limit;               /* 0: TSD_ROUTE_MAX_DIST */
+  int32_t  max_rounds;          /* 0: 16 * (tiles_x + tiles_y) + 64; at most TSD_ROUTE_MAX_ROUNDS */
+} tsd_route_params;
+typedef struct {
+  int32_t  seeds_used;
+  int32_t  rounds;              /* launches of the relaxation */
+  int32_t  converged;           /* 0: max_rounds ran out; every key is then an upper bound of the rule's key */
+  uint32_t reached;             /* cells with a key */
+} tsd_route_info;
+typedef struct {
+  uint32_t cell;                /* linear index y * width + x; TSD_ROUTE_NONE where no cell of the frontier has a key */
+  uint32_t dist;                /* d; TSD_ROUTE_NONE likewise */
+  int32_t  seed;                /* i; -1 likewise */
+  uint32_t reserved;
+} tsd_route_goal;               /* 16 bytes */
+/* W[v] = min(255, 1 + v * (max_weight - 1) / 98) by integer division for v = 0 .. free_max: 1 on a free cell, max_weight at 98, the
+ * highest cost outside the inscribed band of a cost map (the minimum only binds at v = 99).  Host code, no GPU.  TSD_E_ARG for a NULL table, free_max outside 0 .. 99, max_weight
+ * outside 1 .. 255. */
+int tsd_route_weights(int free_max, int max_weight, uint8_t* table /* free_max + 1 entries */);
+/* The generic form, for any map on the context's device: enqueues on the context's stream and waits.  The relaxation runs in
+ * rounds, one launch each, one workgroup per 32 x 32 tile; a tile works in a round only where a neighbour's keys fell in the round
+ * before, and the host reads one word per batch of rounds.  Only kernel boundaries order the tiles: no workgroup waits for another.
+ * Scratch stays with the context and grows on demand -- 4 bytes per cell for the keys, 1 for the cells' weights (what the paths are
+ * traced on, so the map may be released after the call), 2 bytes per tile, the goals, the paths and their pinned copy -- so a repeated
+ * call at the same size allocates nothing.  One route call at a time per context, from the call to the last fetch, and since the
+ * goals read the frontier result, under the same lock as the frontier calls.  TSD_E_NOMEM (tsd_last_error says which buffer) where
+ * the device cannot hold it; the previous result is gone then.  TSD_E_ARG, with the previous result left in place: a NULL map, params
+ * or info, a side outside 1 .. TSD_FRONTIER_MAX_SIDE, stride < width, free_max outside 0 .. 99, a weight of 0, limit >
+ * TSD_ROUTE_MAX_DIST, n_seeds outside 1 .. TSD_FRONTIER_MAX_SEEDS, seeds_xy NULL, max_rounds outside 0 .. TSD_ROUTE_MAX_ROUNDS. */
+int tsd_route_dev(tsd_ctx* ctx, const void* map_dev, int width, int height, int stride, const tsd_route_params* params,
+                  tsd_route_info* info);
+/* The same for what the context's last frame left on the device (cells x cells), on the context's copy stream behind the frame's
+ * event like tsd_frontiers_frame, never on the grid's stream.  source TSD_ROUTE_MAP: the staged map; TSD_ROUTE_COSTMAP: the cost
+ * map of the last completed tsd_costmap_begin / _wait.  TSD_E_ARG also without a completed frame, for TSD_ROUTE_COSTMAP without a
+ * completed cost map or with one of another size, with a frame or a cost map in flight, and for another source.  The grid and its
+ * write ledger are not touched. */
+int tsd_route_frame(tsd_ctx* ctx, int source, const tsd_route_params* params, tsd_route_info* info);
+/* The goals of the frontier result the context holds (tsd_frontiers_*), one per record and in the records' order, from the key image
+ * it holds: *n is their number.  Labels whose root has no record (min_size) are skipped.  TSD_E_ARG without a route result, without
+ * a frontier result, or where their widths or heights differ. */
+int tsd_route_goals(tsd_ctx* ctx, int* n);
+/* Goals first .. first + count - 1 of the last tsd_route_goals, as tsd_frontiers_fetch. */
+int tsd_route_goals_fetch(tsd_ctx* ctx, int first, int count, tsd_route_goal* out);
+/* The paths to n_goals cells (any cells, linear indices; 1 .. TSD_ROUTE_MAX_GOALS of them, n_goals * max_len <= 1 << 24, max_len >=
+ * 1) on the key image the context holds: paths_host[g * max_len + j], j < min(len, max_len), goal first and seed last; len_host[g] is
+ * the full length even where the path is cut at max_len, 0 for a goal without a key or outside the map, -1 where no neighbour
+ * matches (only on an image that did not converge).  TSD_E_ARG without a route result. */
+int tsd_route_trace(tsd_ctx* ctx, const uint32_t* goal_cells, int n_goals, int max_len, uint32_t* paths_host, int32_t* len_host);
+/* The last result on the device: the key image (uint32, width x height of that call), valid until the next route call on the
+ * context or tsd_destroy.  Each pointer may be NULL.  TSD_E_ARG without a result. */
+int tsd_route_dev_ptrs(tsd_ctx* ctx, const void** keys_dev, int* width, int* height);
+/* What the last call counted (each pointer may be NULL): the workgroups that found their tile active, over all rounds, and the
+ * times the host waited for the device. */
+int tsd_route_counts(tsd_ctx* ctx, long long* tile_visits, int* host_waits);
+/* TEST HOOK: the sweeps a tile makes inside one launch before it hands itself on to the next round (default 2048; 0 restores it).
+ * 1 is the other extreme of the schedule: the keys are the same byte for byte (tests/test_gpu_route.py), only the rounds differ. */
+int tsd_debug_set_route_sweeps(tsd_ctx* ctx, int n);
+
 /* ---- the map's surface as an ordered point list --------------------------------------------------------------- */
 /* The `coords` array of RayCastAxisAligned2D::calcCoords (RayCastAxisAligned2D.cpp:13-105), point for point and in its serial order:
  * the linear zero crossings of the TSD along every row and column of every initialised tile of the processed ring (tiles 1 .. PX-2 in
@@ -902,7 +997,8 @@ int tsd_fuse(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell_off_x
 /* Per-kernel HIP-event timing on the ctx stream.  Kernel names: "push_classify", "push_update",
  * "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse", "clearance" (both kernels of tsd_clearance_dev), and the passes of
  * tsd_frontiers_dev: "frontier_tile", "frontier_seam", "frontier_flatten" (each once for the frontiers and once more for the regions
- * where seeds are given), "frontier_rank" (count, scan, emit), "frontier_stats" (with the min_size compaction). */
+ * where seeds are given), "frontier_rank" (count, scan, emit), "frontier_stats" (with the min_size compaction), and those of
+ * tsd_route_dev, tsd_route_goals and tsd_route_trace: "route_init", "route_relax" (a batch of rounds), "route_goals", "route_trace". */
 int tsd_profile_enable(tsd_ctx* ctx, int on);
 /* restrict timing to a comma separated list of kernel names, or "all"; a "/n" suffix times every n-th
  * launch only (two event records cost ~13 us of stream time per timed launch); a name may carry its own

@@ -146,6 +146,34 @@ class FrontierParams(C.Structure):
                 ("seeds_xy", C.POINTER(C.c_int32))]
 
 
+ROUTE_NONE = 0xFFFFFFFF      # the key image's value where no path within the limit ends
+ROUTE_MAX_DIST = 0x0FFFF000
+ROUTE_SOURCES = {"map": 0, "costmap": 1}
+
+
+class RouteParams(C.Structure):
+    """tsd_route_params"""
+    _fields_ = [("free_max", C.c_int32), ("n_seeds", C.c_int32), ("seeds_xy", C.POINTER(C.c_int32)),
+                ("weights", C.POINTER(C.c_uint8)), ("limit", C.c_uint32), ("max_rounds", C.c_int32)]
+
+
+class RouteInfo(C.Structure):
+    """tsd_route_info"""
+    _fields_ = [("seeds_used", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32), ("reached", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class RouteGoal(C.Structure):
+    """tsd_route_goal"""
+    _fields_ = [("cell", C.c_uint32), ("dist", C.c_uint32), ("seed", C.c_int32), ("reserved", C.c_uint32)]
+
+
+ROUTE_GOAL_DTYPE = np.dtype([("cell", "<u4"), ("dist", "<u4"), ("seed", "<i4"), ("reserved", "<u4")])
+assert ROUTE_GOAL_DTYPE.itemsize == C.sizeof(RouteGoal) == 16
+
+
 class FuseStats(C.Structure):
     """tsd_fuse_stats"""
     _fields_ = [("tiles_materialised", C.c_int64), ("tiles_empty", C.c_int64), ("cells_valid", C.c_int64),
@@ -354,6 +382,15 @@ ABI = {
     "tsd_frontiers_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "tsd_frontiers_dev_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _ip]),
     "tsd_frontiers_counts": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),
+    "tsd_route_weights": (C.c_int, [C.c_int, C.c_int, _u8p]),
+    "tsd_route_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RouteParams), C.POINTER(RouteInfo)]),
+    "tsd_route_frame": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RouteParams), C.POINTER(RouteInfo)]),
+    "tsd_route_goals": (C.c_int, [C.c_void_p, _ip]),
+    "tsd_route_goals_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "tsd_route_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tsd_route_dev_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), _ip, _ip]),
+    "tsd_route_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _ip]),
+    "tsd_debug_set_route_sweeps": (C.c_int, [C.c_void_p, C.c_int]),
     "tsd_dev_alloc": (C.c_void_p, [C.c_void_p, C.c_uint64]),
     "tsd_dev_free": (None, [C.c_void_p, C.c_void_p]),
     "tsd_dev_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
@@ -432,7 +469,8 @@ def load_library(path: str | None = None):
                           ("tsd_reloc_result", RelocResult), ("tsd_surface_params", SurfaceParams),
                           ("tsd_align_params", AlignParams), ("tsd_align_peak", AlignPeak), ("tsd_align_result", AlignResult),
                           ("tsd_costmap_params", CostmapParams), ("tsd_frontier", Frontier),
-                          ("tsd_frontier_params", FrontierParams)):
+                          ("tsd_frontier_params", FrontierParams), ("tsd_route_params", RouteParams),
+                          ("tsd_route_info", RouteInfo), ("tsd_route_goal", RouteGoal)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -448,6 +486,16 @@ def device_memory(device: int = 0):
     if rc != 0:
         raise TsdError(f"tsd_device_memory({device}) failed ({rc})")
     return f.value, t.value
+
+
+def route_weights(free_max=0, max_weight=1) -> np.ndarray:
+    """tsd_route_weights: the uint8 table W[0 .. free_max] = 1 + v * (max_weight - 1) / 98 of the routes (host code: no GPU)"""
+    lib = load_library()
+    tab = np.zeros(max(int(free_max), 0) + 1, dtype=np.uint8)
+    rc = lib.tsd_route_weights(int(free_max), int(max_weight), tab.ctypes.data_as(_u8p))
+    if rc != 0:
+        raise TsdError(f"tsd_route_weights refused (rc {rc}): free_max {free_max}, max_weight {max_weight}")
+    return tab
 
 
 def costmap_table(cell_size, radius, inscribed_radius_m=0.25, cost_scaling=10.0) -> np.ndarray:
@@ -1175,6 +1223,87 @@ class TsdGridDevice:
         self._check(rc, "tsd_frontiers_frame")
         rec, labels = self._frontier_result(n.value, self.cells, self.cells)
         return rec, labels, used.value
+
+    # ---- routes (tsd_route_dev / _frame / _goals / _trace / _dev_ptrs)
+    @staticmethod
+    def route_weights(free_max=0, max_weight=1) -> np.ndarray:
+        """tsd_route_weights: uint8 W[0 .. free_max]"""
+        return route_weights(free_max, max_weight)
+
+    @staticmethod
+    def _route_params(seeds, free_max, weights, limit, max_rounds):
+        """(tsd_route_params, the arrays it points into -- to be kept alive over the call)"""
+        xy = np.ascontiguousarray(np.asarray(list(seeds), dtype=np.int32).reshape(-1, 2))
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint8)
+        assert w is None or w.size == int(free_max) + 1
+        prm = RouteParams(int(free_max), int(xy.shape[0]), xy.ctypes.data_as(C.POINTER(C.c_int32)) if xy.shape[0] else None,
+                          None if w is None else w.ctypes.data_as(_u8p), int(limit), int(max_rounds))
+        return prm, (xy, w)
+
+    def set_route_sweeps(self, n: int):
+        """test hook: the sweeps a tile makes per launch (tsd_debug_set_route_sweeps; 0: the default; same bytes at any value)"""
+        self._check(self.lib.tsd_debug_set_route_sweeps(self.h, int(n)), "tsd_debug_set_route_sweeps")
+
+    def route_dev_ptrs(self):
+        """tsd_route_dev_ptrs: (keys_dev, width, height) of the last route call, valid until the next one"""
+        k, w, h = C.c_void_p(), C.c_int(0), C.c_int(0)
+        self._check(self.lib.tsd_route_dev_ptrs(self.h, C.byref(k), C.byref(w), C.byref(h)), "tsd_route_dev_ptrs")
+        return k.value, w.value, h.value
+
+    def route_counts(self):
+        """tsd_route_counts: (workgroups that found their tile active over all rounds, host waits) of the last route call"""
+        v, w = C.c_longlong(0), C.c_int(0)
+        self._check(self.lib.tsd_route_counts(self.h, C.byref(v), C.byref(w)), "tsd_route_counts")
+        return v.value, w.value
+
+    def route_keys(self) -> np.ndarray:
+        """the key image of the last route call, (height, width) uint32, copied to the host"""
+        keys_dev, w, h = self.route_dev_ptrs()
+        keys = np.zeros((h, w), dtype=np.uint32)
+        self._check(self.lib.tsd_dev_copy(self.h, keys.ctypes.data, keys_dev, keys.nbytes, 0), "tsd_dev_copy")
+        return keys
+
+    def route_of(self, dev_ptr: int, width: int, height: int, stride: int, seeds, free_max=0, weights=None, limit=0, max_rounds=0):
+        """tsd_route_dev on a device map (``dev_ptr``: int8, ``height`` rows of ``stride`` bytes): (keys (height, width) uint32 --
+        (d << 4) | seed index, ROUTE_NONE without a path within the limit --, info as a dict).  seeds: (x, y) cells."""
+        prm, keep = self._route_params(seeds, free_max, weights, limit, max_rounds)
+        info = RouteInfo()
+        rc = self.lib.tsd_route_dev(self.h, C.c_void_p(dev_ptr), int(width), int(height), int(stride), C.byref(prm), C.byref(info))
+        self.last_rc = rc
+        self._check(rc, "tsd_route_dev")
+        return self.route_keys(), info.as_dict()
+
+    def route(self, source="map", seeds=(), free_max=0, weights=None, limit=0, max_rounds=0):
+        """tsd_route_frame: the same for the map ("map") of the frame or update taken last or for the cost map ("costmap") made of
+        it last (cells x cells)"""
+        prm, keep = self._route_params(seeds, free_max, weights, limit, max_rounds)
+        info = RouteInfo()
+        rc = self.lib.tsd_route_frame(self.h, ROUTE_SOURCES[source], C.byref(prm), C.byref(info))
+        self.last_rc = rc
+        self._check(rc, "tsd_route_frame")
+        return self.route_keys(), info.as_dict()
+
+    def route_goals(self) -> np.ndarray:
+        """tsd_route_goals + _fetch: for every record of the frontier call made last the cheapest cell to reach on the key image of
+        the route call made last, as a structured array of ROUTE_GOAL_DTYPE (cell, dist, seed)"""
+        n = C.c_int(0)
+        rc = self.lib.tsd_route_goals(self.h, C.byref(n))
+        self.last_rc = rc
+        self._check(rc, "tsd_route_goals")
+        out = np.zeros(n.value, dtype=ROUTE_GOAL_DTYPE)
+        self._check(self.lib.tsd_route_goals_fetch(self.h, 0, n.value, out.ctypes.data), "tsd_route_goals_fetch")
+        return out
+
+    def route_paths(self, cells, max_len=4096):
+        """tsd_route_trace: (paths -- one uint32 array of linear cell indices per goal cell, goal first and seed last, cut at
+        ``max_len`` --, lengths int32: the full length, 0 without a key, -1 where the image did not converge)"""
+        cells = np.ascontiguousarray(cells, dtype=np.uint32).ravel()
+        paths = np.zeros((cells.size, int(max_len)), dtype=np.uint32)
+        lens = np.zeros(cells.size, dtype=np.int32)
+        rc = self.lib.tsd_route_trace(self.h, cells.ctypes.data, int(cells.size), int(max_len), paths.ctypes.data, lens.ctypes.data)
+        self.last_rc = rc
+        self._check(rc, "tsd_route_trace")
+        return [paths[g, :min(max(int(n), 0), int(max_len))].copy() for g, n in enumerate(lens)], lens
 
     def push_stats_total(self, reset=False):
         st = PushStats()

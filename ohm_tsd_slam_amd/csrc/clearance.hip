@@ -332,7 +332,7 @@ int tsd_costmap_begin(tsd_ctx* ctx, const tsd_costmap_params* prm, int8_t* cost_
   if (!c.ev_done) TSD_HIP_CHECK(ctx, hipEventCreateWithFlags(&c.ev_done, hipEventDisableTiming));
   if (c.out_cells < cells) {
     if (c.d_cost) hipFree(c.d_cost);
-    c.d_cost = nullptr; c.out_cells = 0;
+    c.d_cost = nullptr; c.out_cells = 0; c.cost_cells = 0;
     TSD_HIP_CHECK(ctx, hipMalloc(&c.d_cost, cells));
     c.out_cells = cells;
   }
@@ -367,6 +367,7 @@ int tsd_costmap_begin(tsd_ctx* ctx, const tsd_costmap_params* prm, int8_t* cost_
   TSD_HIP_CHECK(ctx, hipEventRecord(c.ev_done, ctx->stream_io));
   *out_win = ow;
   c.inflight = true; c.empty = false;
+  c.cost_cells = cells;
   return TSD_OK;
 }
 

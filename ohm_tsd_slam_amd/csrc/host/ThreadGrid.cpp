@@ -1,5 +1,6 @@
 #include "ThreadGrid.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -295,9 +296,8 @@ int ThreadGrid::publish(void)
 // needed (the grid is not read).  The caller holds _publishMutex, so the staging is not replaced meanwhile; the grid's frontierMutex
 // keeps the context's frontier scratch and result to one call at a time, this worker's or a ThreadGridGroup's on the same context,
 // from the call to the fetch.
-static int frameFrontiers(obvious::TsdGrid& grid, const int32_t* seedsXy, int n, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed)
+static int frameFrontiersLocked(obvious::TsdGrid& grid, const int32_t* seedsXy, int n, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed)
 {
-  std::lock_guard<std::mutex> fl(grid.frontierMutex());
   tsd_ctx* ctx = grid.context();
   tsd_frontier_params prm;
   prm.free_max = 0;
@@ -315,6 +315,100 @@ static int frameFrontiers(obvious::TsdGrid& grid, const int32_t* seedsXy, int n,
   if(seedsUsed)
     *seedsUsed = used;
   return rc;
+}
+
+static int frameFrontiers(obvious::TsdGrid& grid, const int32_t* seedsXy, int n, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed)
+{
+  std::lock_guard<std::mutex> fl(grid.frontierMutex());
+  return frameFrontiersLocked(grid, seedsXy, n, minSize, out, seedsUsed);
+}
+
+// The route entry points are weak references in the facade's workers: they also link against stand-ins of the device ABI that have
+// no routes (tests/frontier_lock.cpp), where routePlan answers TSD_E_ARG.
+#pragma weak tsd_route_weights
+#pragma weak tsd_route_dev
+#pragma weak tsd_route_frame
+#pragma weak tsd_route_goals
+#pragma weak tsd_route_goals_fetch
+#pragma weak tsd_route_trace
+
+int routePlan(tsd_ctx* ctx, const void* mapDev, int width, int height, int source, const tsd_route_params& prm, int maxLen, ExplorePlan* out)
+{
+  if(!tsd_route_dev || !tsd_route_frame || !tsd_route_goals || !tsd_route_goals_fetch || !tsd_route_trace)
+    return TSD_E_ARG;
+  if(!out || maxLen < 1 || maxLen > (1 << 24))
+    return TSD_E_ARG;
+  int rc = mapDev ? tsd_route_dev(ctx, mapDev, width, height, width, &prm, &out->route) : tsd_route_frame(ctx, source, &prm, &out->route);
+  if(rc != TSD_OK)
+    return rc;
+  int count = 0;
+  rc = tsd_route_goals(ctx, &count);
+  if(rc != TSD_OK)
+    return rc;
+  out->goals.resize((size_t)count);
+  out->lens.assign((size_t)count, 0);
+  out->paths.clear();
+  if(count == 0)
+    return TSD_OK;
+  rc = tsd_route_goals_fetch(ctx, 0, count, out->goals.data());
+  if(rc != TSD_OK)
+    return rc;
+  // the goals with a cell, traced in chunks the trace call takes (at most TSD_ROUTE_MAX_GOALS goals and 1 << 24 path cells)
+  std::vector<uint32_t> cells, buf;
+  std::vector<int32_t> lens;
+  std::vector<size_t> which;
+  const size_t chunk = std::min<size_t>(TSD_ROUTE_MAX_GOALS, ((size_t)1 << 24) / (size_t)maxLen);
+  for(size_t i = 0; i <= (size_t)count; i++)
+  {
+    if(i < (size_t)count && out->goals[i].cell != TSD_ROUTE_NONE)
+    {
+      cells.push_back(out->goals[i].cell);
+      which.push_back(i);
+    }
+    if(cells.empty() || (cells.size() < chunk && i < (size_t)count))
+      continue;
+    buf.resize(cells.size() * (size_t)maxLen);
+    lens.resize(cells.size());
+    rc = tsd_route_trace(ctx, cells.data(), static_cast<int>(cells.size()), maxLen, buf.data(), lens.data());
+    if(rc != TSD_OK)
+      return rc;
+    for(size_t g = 0; g < cells.size(); g++)
+    {
+      out->lens[which[g]] = lens[g];
+      const size_t kept = (size_t)std::min(std::max(lens[g], 0), maxLen);
+      out->paths.insert(out->paths.end(), buf.begin() + (ptrdiff_t)(g * (size_t)maxLen), buf.begin() + (ptrdiff_t)(g * (size_t)maxLen + kept));
+    }
+    cells.clear();
+    which.clear();
+  }
+  return TSD_OK;
+}
+
+int ThreadGrid::explorePlan(const int32_t* seedsXy, int n, uint32_t minSize, int source, int maxWeight, int maxLen, ExplorePlan* out,
+                            double* originRes)
+{
+  if(!out || !seedsXy || n < 1 || n > TSD_FRONTIER_MAX_SEEDS || (source != TSD_ROUTE_MAP && source != TSD_ROUTE_COSTMAP))
+    return TSD_E_ARG;
+  uint8_t weights[100];
+  const int freeMax = source == TSD_ROUTE_COSTMAP ? 98 : 0;
+  if(!tsd_route_weights || tsd_route_weights(freeMax, source == TSD_ROUTE_COSTMAP ? maxWeight : 1, weights) != TSD_OK)
+    return TSD_E_ARG;
+  std::lock_guard<std::mutex> lk(_publishMutex);
+  if(originRes)
+    mapPlacement(originRes);
+  // the goals read the frontier result: one lock from the frontier call to the last fetch
+  std::lock_guard<std::mutex> fl(_grid.frontierMutex());
+  int rc = frameFrontiersLocked(_grid, seedsXy, n, minSize, &out->frontiers, &out->seedsUsed);
+  if(rc != TSD_OK)
+    return rc;
+  tsd_route_params prm;
+  prm.free_max = freeMax;
+  prm.n_seeds = n;
+  prm.seeds_xy = seedsXy;
+  prm.weights = weights;
+  prm.limit = 0;
+  prm.max_rounds = 0;
+  return routePlan(_grid.context(), nullptr, 0, 0, source, prm, maxLen, out);
 }
 
 void ThreadGrid::mapPlacement(double* originRes)

@@ -26,6 +26,23 @@
 namespace ohm_tsd_slam
 {
 
+/** What an explorer asks of a map in one call (ThreadGrid::explorePlan, ThreadGridGroup::explorePlan): the frontiers, for each the
+ *  cheapest cell to drive to with its cost and the seed (robot) it is cheapest from, and the path to it. */
+struct ExplorePlan
+{
+  std::vector<tsd_frontier> frontiers;
+  std::vector<tsd_route_goal> goals;     // one per frontier, in the frontiers' order
+  std::vector<int32_t> lens;             // one per frontier: the path's full length in cells (0: no goal; -1: the field did not converge)
+  std::vector<uint32_t> paths;           // the paths one after the other, min(len, maxLen) linear cell indices each, goal first, seed last
+  tsd_route_info route;
+  int seedsUsed;
+};
+
+/** Route, goals and paths (tsd_route_*) on a context whose frontier result is in place, into out->goals, lens, paths and route.
+ *  mapDev nullptr: the frame form from `source`, else the generic form on mapDev (width x height, rows of width bytes).  The caller
+ *  holds the context's frontierMutex, and for the generic form the grid's mutex.  TSD_E_ARG where the device library has no routes. */
+int routePlan(tsd_ctx* ctx, const void* mapDev, int width, int height, int source, const tsd_route_params& prm, int maxLen, ExplorePlan* out);
+
 class ThreadGrid : public ThreadSLAM
 {
 public:
@@ -71,6 +88,12 @@ public:
    *  counted, and in originRes the origin x, y and the resolution (a float32) <node>/map carries.  Holds the publish mutex, so the map
    *  is the one the records belong to, and the grid's frontierMutex for the call.  TSD_E_ARG before the first publication. */
   int frontiers(const int32_t* seedsXy, int n, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed, double* originRes);
+  /** frontiers(), then the cost-to-go field from the same seeds (tsd_route_frame on `source`: TSD_ROUTE_MAP with unit weights, or
+   *  TSD_ROUTE_COSTMAP -- the cost map of the last publication, parameter publish_costmap -- with free_max 98 and
+   *  tsd_route_weights(98, maxWeight)), the goal of every frontier and the paths to them, cut at maxLen cells.  n is 1 ..
+   *  TSD_FRONTIER_MAX_SEEDS.  Holds the publish mutex and, from the frontier call to the last fetch, the grid's frontierMutex (the
+   *  goals read the frontier result).  TSD_E_ARG before the first publication. */
+  int explorePlan(const int32_t* seedsXy, int n, uint32_t minSize, int source, int maxWeight, int maxLen, ExplorePlan* out, double* originRes);
   /** origin x, y and resolution of <node>/map: fixed by the parameters at construction, the same before and after a publication */
   void mapPlacement(double* originRes);
 

@@ -1,4 +1,5 @@
 #include "ThreadGridGroup.h"
+#include "ThreadGrid.h"
 
 #include <cmath>
 #include <cstdio>
@@ -154,6 +155,21 @@ int ThreadGridGroup::publish(void)
 int ThreadGridGroup::frontiers(const double* gridXy, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed, int32_t* seedsXy,
                                double* originCs)
 {
+  return frontiersAndPlan(gridXy, minSize, out, seedsUsed, seedsXy, originCs, nullptr, 0);
+}
+
+int ThreadGridGroup::explorePlan(const double* gridXy, uint32_t minSize, int maxLen, ExplorePlan* out, int32_t* seedsXy, double* originCs)
+{
+  if(!out || maxLen < 1)
+    return TSD_E_ARG;
+  return frontiersAndPlan(gridXy, minSize, &out->frontiers, &out->seedsUsed, seedsXy, originCs, out, maxLen);
+}
+
+// frontiers(); with `plan` also the routes from the same seeds on the same map (unit weights, free_max 0), under the same two locks:
+// the goals read the frontier result
+int ThreadGridGroup::frontiersAndPlan(const double* gridXy, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed, int32_t* seedsXy,
+                                      double* originCs, ExplorePlan* plan, int maxLen)
+{
   if(!gridXy || !out || _members.size() > (size_t)TSD_FRONTIER_MAX_SEEDS)
     return TSD_E_ARG;
   std::lock_guard<std::mutex> lk(_publishMutex);      // (the merged map on the device stays as the last publication left it)
@@ -208,6 +224,17 @@ int ThreadGridGroup::frontiers(const double* gridXy, uint32_t minSize, std::vect
       out->resize((size_t)count);
       if(count > 0)
         rc = tsd_frontiers_fetch(ctx, 0, count, out->data());
+    }
+    if(rc == TSD_OK && plan)
+    {
+      tsd_route_params rp;
+      rp.free_max = 0;
+      rp.n_seeds = prm.n_seeds;
+      rp.seeds_xy = seeds.data();
+      rp.weights = nullptr;
+      rp.limit = 0;
+      rp.max_rounds = 0;
+      rc = routePlan(ctx, tsd_group_map_dev(_group), static_cast<int>(_width), static_cast<int>(_height), TSD_ROUTE_MAP, rp, maxLen, plan);
     }
   }
   if(seedsUsed)

@@ -17,6 +17,8 @@
 namespace ohm_tsd_slam
 {
 
+struct ExplorePlan;      // ThreadGrid.h
+
 class ThreadGridGroup : public ThreadSLAM
 {
 public:
@@ -64,6 +66,10 @@ public:
    *  (2 per member): the seed cells; originCs: the merged map's origin x, y and its resolution (the message's float32).  TSD_E_ARG before the
    *  first publication. */
   int frontiers(const double* gridXy, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed, int32_t* seedsXy, double* originCs);
+  /** frontiers(), then on the same merged map and from the same seeds the cost-to-go field (tsd_route_dev: unit weights, free_max 0),
+   *  the goal of every frontier -- its `seed` is the member nearest to that frontier, what an allocator starts from -- and the paths,
+   *  cut at maxLen cells.  The two locks of frontiers() are held to the last fetch. */
+  int explorePlan(const double* gridXy, uint32_t minSize, int maxLen, ExplorePlan* out, int32_t* seedsXy, double* originCs);
   size_t members(void) const { return _members.size(); }
 
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }
@@ -75,6 +81,9 @@ protected:
   virtual void eventLoop(void);
 
 private:
+  int frontiersAndPlan(const double* gridXy, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed, int32_t* seedsXy, double* originCs,
+                       ExplorePlan* plan, int maxLen);
+
   std::shared_ptr<rclcpp::Node> _node;
   std::vector<Member> _members;
   tsd_group* _group;

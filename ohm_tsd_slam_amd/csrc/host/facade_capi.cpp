@@ -29,6 +29,7 @@ struct tsd_fleet
 {
   std::vector<tsd_node*> nodes;
   std::vector<tsd_frontier> frontiers;    // the last tsd_fleet_frontiers
+  ExplorePlan plan;                       // the last tsd_fleet_explore_plan
   ThreadGridGroup* group = nullptr;
   obvious::TsdGrid* fused = nullptr;      // the fleet's own grid: the TSD-level fusion of the nodes' grids (created by the first fusion)
 };
@@ -49,6 +50,7 @@ struct tsd_node
   bool synchronous = false;
   bool fused = true;
   std::vector<tsd_frontier> frontiers;    // the last tsd_node_frontiers
+  ExplorePlan plan;                       // the last tsd_node_explore_plan
 };
 
 extern "C" {
@@ -523,19 +525,13 @@ static void pose_cell(double px, double py, double ox, double oy, double cs, int
   xy[1] = ok ? static_cast<int32_t>(fy) : -1;
 }
 
-// The frontiers of the map the node published last (ThreadGrid::frontiers), kept for tsd_node_frontiers_fetch.  n_seeds < 0: one seed
-// per robot of the node, the cell of its last estimated pose.  min_size 0: frontier_min_size.  seeds_out (2 * TSD_FRONTIER_MAX_SEEDS
-// int32) / n_seeds_out: the seeds taken; origin_cs: the map's origin x, y and its resolution.  Returns TSD_OK or the error code.
-int tsd_node_frontiers(tsd_node* n, const int32_t* seeds_xy, int n_seeds, unsigned min_size, int* count, int* seeds_used,
-                       int32_t* seeds_out, int* n_seeds_out, double* origin_cs)
+// The seeds of a frontier or route call on the node's map and the map's placement: n_seeds < 0: one seed per robot of the node, the
+// cell of its last estimated pose, else the caller's.  Returns their number.
+static int node_seeds(tsd_node* n, const int32_t* seeds_xy, int n_seeds, double* place, int32_t* seeds)
 {
-  if(!n || !n->gridThread || !count || n_seeds > TSD_FRONTIER_MAX_SEEDS || (n_seeds > 0 && !seeds_xy))
-    return TSD_E_ARG;
   // (a map's origin and resolution are fixed when the node is built: the seeds' cells use the values the call returns below)
-  double place[3];
   n->gridThread->mapPlacement(place);
   const double ox = place[0], oy = place[1], cs = place[2];
-  int32_t seeds[2 * TSD_FRONTIER_MAX_SEEDS];
   int ns = n_seeds;
   if(n_seeds < 0)
   {
@@ -548,6 +544,20 @@ int tsd_node_frontiers(tsd_node* n, const int32_t* seeds_xy, int n_seeds, unsign
   }
   else
     std::memcpy(seeds, seeds_xy, (size_t)(2 * ns) * sizeof(int32_t));
+  return ns;
+}
+
+// The frontiers of the map the node published last (ThreadGrid::frontiers), kept for tsd_node_frontiers_fetch.  n_seeds < 0: one seed
+// per robot of the node, the cell of its last estimated pose.  min_size 0: frontier_min_size.  seeds_out (2 * TSD_FRONTIER_MAX_SEEDS
+// int32) / n_seeds_out: the seeds taken; origin_cs: the map's origin x, y and its resolution.  Returns TSD_OK or the error code.
+int tsd_node_frontiers(tsd_node* n, const int32_t* seeds_xy, int n_seeds, unsigned min_size, int* count, int* seeds_used,
+                       int32_t* seeds_out, int* n_seeds_out, double* origin_cs)
+{
+  if(!n || !n->gridThread || !count || n_seeds > TSD_FRONTIER_MAX_SEEDS || (n_seeds > 0 && !seeds_xy))
+    return TSD_E_ARG;
+  double place[3];
+  int32_t seeds[2 * TSD_FRONTIER_MAX_SEEDS];
+  const int ns = node_seeds(n, seeds_xy, n_seeds, place, seeds);
   const int rc = n->gridThread->frontiers(seeds, ns, min_size ? min_size : n->gridThread->frontierMinSize(), &n->frontiers, seeds_used, place);
   if(rc != TSD_OK)
     return rc;
@@ -567,6 +577,60 @@ void tsd_node_frontiers_fetch(tsd_node* n, tsd_frontier* out)
 {
   if(n && out && !n->frontiers.empty())
     std::memcpy(out, n->frontiers.data(), n->frontiers.size() * sizeof(tsd_frontier));
+}
+
+// what a plan's fetch copies: counts[0] frontiers (as many goals and lengths), counts[1] path cells, counts[2] seeds used
+static void plan_counts(const ExplorePlan& p, int* counts)
+{
+  counts[0] = static_cast<int>(p.frontiers.size());
+  counts[1] = static_cast<int>(p.paths.size());
+  counts[2] = p.seedsUsed;
+}
+
+static void plan_fetch(const ExplorePlan& p, tsd_frontier* rec, tsd_route_goal* goals, int32_t* lens, uint32_t* paths)
+{
+  if(rec && !p.frontiers.empty())
+    std::memcpy(rec, p.frontiers.data(), p.frontiers.size() * sizeof(tsd_frontier));
+  if(goals && !p.goals.empty())
+    std::memcpy(goals, p.goals.data(), p.goals.size() * sizeof(tsd_route_goal));
+  if(lens && !p.lens.empty())
+    std::memcpy(lens, p.lens.data(), p.lens.size() * sizeof(int32_t));
+  if(paths && !p.paths.empty())
+    std::memcpy(paths, p.paths.data(), p.paths.size() * sizeof(uint32_t));
+}
+
+// Frontiers, cost-to-go field, goals and paths of the map the node published last (ThreadGrid::explorePlan), kept for
+// tsd_node_explore_plan_fetch.  Seeds, min_size, seeds_out, n_seeds_out and origin_cs as tsd_node_frontiers (at least one seed);
+// source TSD_ROUTE_MAP / TSD_ROUTE_COSTMAP; counts: see plan_counts; *info: the route's.
+int tsd_node_explore_plan(tsd_node* n, const int32_t* seeds_xy, int n_seeds, unsigned min_size, int source, int max_weight, int max_len,
+                          int* counts, tsd_route_info* info, int32_t* seeds_out, int* n_seeds_out, double* origin_cs)
+{
+  if(!n || !n->gridThread || !counts || !info || n_seeds == 0 || n_seeds > TSD_FRONTIER_MAX_SEEDS || (n_seeds > 0 && !seeds_xy))
+    return TSD_E_ARG;
+  double place[3];
+  int32_t seeds[2 * TSD_FRONTIER_MAX_SEEDS];
+  const int ns = node_seeds(n, seeds_xy, n_seeds, place, seeds);
+  const int rc = n->gridThread->explorePlan(seeds, ns, min_size ? min_size : n->gridThread->frontierMinSize(), source, max_weight, max_len,
+                                            &n->plan, place);
+  if(rc != TSD_OK)
+    return rc;
+  plan_counts(n->plan, counts);
+  *info = n->plan.route;
+  if(seeds_out)
+    std::memcpy(seeds_out, seeds, (size_t)(2 * ns) * sizeof(int32_t));
+  if(n_seeds_out)
+    *n_seeds_out = ns;
+  if(origin_cs)
+  {
+    origin_cs[0] = place[0]; origin_cs[1] = place[1]; origin_cs[2] = place[2];
+  }
+  return TSD_OK;
+}
+
+void tsd_node_explore_plan_fetch(tsd_node* n, tsd_frontier* rec, tsd_route_goal* goals, int32_t* lens, uint32_t* paths)
+{
+  if(n)
+    plan_fetch(n->plan, rec, goals, lens, paths);
 }
 
 // <node>/get_map (ThreadGrid::getMapServCallBack): the last map with a fresh stamp (map_out layout); 1 if the service answered
@@ -725,10 +789,48 @@ int tsd_fleet_publish_merged(tsd_fleet* f) { return (f && f->group) ? f->group->
 // the node's grid coordinates by the node's own map origin and carried on by the group (ThreadGridGroup::frontiers).  Kept for
 // tsd_fleet_frontiers_fetch.  seeds_out: 2 int32 per node, *n_seeds_out: the nodes; origin_cs: the merged map's origin x, y and its
 // resolution.  At most TSD_FRONTIER_MAX_SEEDS nodes (TSD_E_ARG beyond).
+static std::vector<double> fleet_grid_xy(tsd_fleet* f);
 int tsd_fleet_frontiers(tsd_fleet* f, unsigned min_size, int* count, int* seeds_used, int32_t* seeds_out, int* n_seeds_out, double* origin_cs)
 {
   if(!f || !f->group || !count)
     return TSD_E_ARG;
+  const std::vector<double> xy = fleet_grid_xy(f);
+  const int rc = f->group->frontiers(xy.data(), min_size ? min_size : 1u, &f->frontiers, seeds_used, seeds_out, origin_cs);
+  if(rc != TSD_OK)
+    return rc;
+  *count = static_cast<int>(f->frontiers.size());
+  if(n_seeds_out)
+    *n_seeds_out = static_cast<int>(f->nodes.size());
+  return TSD_OK;
+}
+
+// The same with the routes (ThreadGridGroup::explorePlan), kept for tsd_fleet_explore_plan_fetch: counts and info as
+// tsd_node_explore_plan; a goal's seed is the index of the node nearest to that frontier.
+int tsd_fleet_explore_plan(tsd_fleet* f, unsigned min_size, int max_len, int* counts, tsd_route_info* info, int32_t* seeds_out, int* n_seeds_out,
+                           double* origin_cs)
+{
+  if(!f || !f->group || !counts || !info)
+    return TSD_E_ARG;
+  const std::vector<double> xy = fleet_grid_xy(f);
+  const int rc = f->group->explorePlan(xy.data(), min_size ? min_size : 1u, max_len, &f->plan, seeds_out, origin_cs);
+  if(rc != TSD_OK)
+    return rc;
+  plan_counts(f->plan, counts);
+  *info = f->plan.route;
+  if(n_seeds_out)
+    *n_seeds_out = static_cast<int>(f->nodes.size());
+  return TSD_OK;
+}
+
+void tsd_fleet_explore_plan_fetch(tsd_fleet* f, tsd_frontier* rec, tsd_route_goal* goals, int32_t* lens, uint32_t* paths)
+{
+  if(f)
+    plan_fetch(f->plan, rec, goals, lens, paths);
+}
+
+// every node's position (robot 0's last estimated pose) in ITS grid's coordinates, NaN without a pose: what the group's calls take
+static std::vector<double> fleet_grid_xy(tsd_fleet* f)
+{
   std::vector<double> xy(2 * f->nodes.size());
   for(size_t i = 0; i < f->nodes.size(); i++)
   {
@@ -746,13 +848,7 @@ int tsd_fleet_frontiers(tsd_fleet* f, unsigned min_size, int* count, int* seeds_
     xy[2 * i] = pose.pose.position.x - ox;
     xy[2 * i + 1] = pose.pose.position.y - oy;
   }
-  const int rc = f->group->frontiers(xy.data(), min_size ? min_size : 1u, &f->frontiers, seeds_used, seeds_out, origin_cs);
-  if(rc != TSD_OK)
-    return rc;
-  *count = static_cast<int>(f->frontiers.size());
-  if(n_seeds_out)
-    *n_seeds_out = static_cast<int>(f->nodes.size());
-  return TSD_OK;
+  return xy;
 }
 
 void tsd_fleet_frontiers_fetch(tsd_fleet* f, tsd_frontier* out)

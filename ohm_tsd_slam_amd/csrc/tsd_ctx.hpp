@@ -303,6 +303,7 @@ struct tsd_ctx {
     uint8_t* d_tiles = nullptr; size_t tiles_bytes = 0;
     int8_t* d_table = nullptr; int8_t* h_table = nullptr;   // [TSD_CLEARANCE_MAX_RADIUS^2 + 4]; h_table pinned
     int8_t* d_cost = nullptr; uint16_t* d_dist2 = nullptr; size_t out_cells = 0, dist2_cells = 0;
+    size_t cost_cells = 0;                   // the cells of the cost map d_cost holds (0: none yet; what tsd_route_frame asks before it reads d_cost)
     hipEvent_t ev_done = nullptr;            // on stream_io: the cost map's copies to the host are done
     bool inflight = false, empty = false;
     int skip = 1;                            // the tile skip of the column pass (tsd_debug_set_clearance_skip: 0 = every block walks)
@@ -319,6 +320,20 @@ struct tsd_ctx {
     int n = -1, n_all = 0, W = 0, H = 0;                                          // the last result (n < 0: none)
     int seam_unions = 0, region_seam_unions = 0;
   } frontier;
+  // routes (route.hip: tsd_route_dev / _frame / _goals / _trace / _dev_ptrs).  Scratch of the kernels and the last result, allocated on
+  // first use, grown on demand and kept.  Every call waits for its own work, so nothing of this is ever in flight between calls
+  struct Route {
+    uint32_t* d_key = nullptr; uint8_t* d_w = nullptr; size_t cells = 0;          // the key image; the cells' weights (0: not traversable)
+    uint8_t* d_act = nullptr; size_t tiles = 0;                                   // [2][tiles]: a tile works in the even / odd rounds
+    tsd_route_goal* d_goal = nullptr; size_t goals = 0;
+    uint32_t* d_path = nullptr; uint32_t* h_path = nullptr; size_t path_words = 0, h_path_words = 0;   // goal cells, lengths, paths; h_path pinned
+    uint32_t* d_res = nullptr; uint32_t* h_res = nullptr;                         // the call's counters; h_res pinned
+    hipStream_t stream = nullptr;                                                 // the stream the result was made on: goals and paths follow it
+    bool valid = false;                                                           // the last result (false: none)
+    int W = 0, H = 0, n_goals = -1;
+    int sweeps = 0;                                                               // tsd_debug_set_route_sweeps (0: the default)
+    long long tile_visits = 0; int host_waits = 0;
+  } route;
   // TSD-level fusion (fuse.hip).  As the destination: the kernel's sharded counters and their pinned copy.  As a member: events of its
   // own -- "every grid write enqueued so far" on its stream / its push stream, "the fusion that read this grid last is done" (recorded
   // on the destination's stream; the member's streams wait for it at once) -- all created on first use
@@ -361,7 +376,7 @@ struct tsd_ctx {
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;
   unsigned profile_every = 1;   // time every n-th launch of a selected kernel ("name/n" in tsd_profile_select)
-  unsigned profile_every_k[16] = {};   // a kernel's own period ("name:m"), 0 = the list's
+  unsigned profile_every_k[18] = {};   // a kernel's own period ("name:m"), 0 = the list's
   bool profile = false;
   std::map<std::string, tsd::KernelTimer> timers;
   std::vector<hipEvent_t> event_pool;
@@ -598,6 +613,7 @@ void surface_free(tsd_ctx* ctx);             // surface.hip: releases tsd_ctx::s
 void align_free(tsd_ctx* ctx);               // align.hip: releases tsd_ctx::align (tsd_destroy)
 void clearance_free(tsd_ctx* ctx);           // clearance.hip: releases tsd_ctx::clearance (tsd_destroy)
 void frontier_free(tsd_ctx* ctx);            // frontier.hip: releases tsd_ctx::frontier (tsd_destroy)
+void route_free(tsd_ctx* ctx);               // route.hip: releases tsd_ctx::route (tsd_destroy)
 int8_t* frame_staged_map(const tsd_ctx* ctx);   // map_publish.hip: the frame staging's map (cells * cells int8), nullptr without a staging
 int launch_calibrate(tsd_ctx* ctx, double* t, double* w, size_t n);
 int launch_occupancy(tsd_ctx* ctx, int8_t* d_out, int inflate, int inflate_factor);

@@ -60,6 +60,11 @@ HOST_ABI = {
     "tsd_node_frontier_lock": (None, [C.c_void_p]),
     "tsd_node_frontier_unlock": (None, [C.c_void_p]),
     "tsd_fleet_frontiers_fetch": (None, [C.c_void_p, C.c_void_p]),
+    "tsd_node_explore_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, _ip,
+                                        C.POINTER(capi.RouteInfo), C.c_void_p, _ip, _dp]),
+    "tsd_node_explore_plan_fetch": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsd_fleet_explore_plan": (C.c_int, [C.c_void_p, C.c_uint, C.c_int, _ip, C.POINTER(capi.RouteInfo), C.c_void_p, _ip, _dp]),
+    "tsd_fleet_explore_plan_fetch": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_grid_lock": (None, [C.c_void_p]),
@@ -426,6 +431,19 @@ class SlamNode:
             self.h, None if xy is None or ns == 0 else xy.ctypes.data, ns, int(min_size or 0), c, u, so, no, oc),
             lambda out: self.lib.tsd_node_frontiers_fetch(self.h, out), "tsd_node_frontiers")
 
+    def explore_plan(self, min_size=None, source="map", max_weight=1, max_len=4096) -> dict:
+        """Where to drive next, in one call on the map published last: what ``frontiers()`` returns with the robot's cell as the
+        seed, plus ``goals`` (capi.ROUTE_GOAL_DTYPE, one per frontier: the cheapest cell to reach, its cost d -- 5 per straight and 7
+        per diagonal step, times the weight of the cell entered -- and the seed it is cheapest from; capi.ROUTE_NONE / -1 for a
+        frontier the robot cannot reach), ``goal_xy`` (n, 2) float64 in the map's frame [m], (cell + 0.5) * resolution + origin (NaN
+        without a goal), ``paths`` (a list of (len, 2) float64 arrays in metres, ordered seed to goal, the ``max_len`` cells nearest to
+        the goal where the path is longer), ``path_lens`` (the full lengths in cells) and ``route`` (tsd_route_info as a dict).
+        source "map": unit weights on the free cells; "costmap": the cost map of the last publication (parameter publish_costmap),
+        traversable below the inscribed band, weights tsd_route_weights(98, max_weight)."""
+        return _plan_dict(lambda c, i, so, no, oc: self.lib.tsd_node_explore_plan(
+            self.h, None, -1, int(min_size or 0), capi.ROUTE_SOURCES[source], int(max_weight), int(max_len), c, i, so, no, oc),
+            lambda *out: self.lib.tsd_node_explore_plan_fetch(self.h, *out), self.map_msg()["width"], max_len, "tsd_node_explore_plan")
+
     def surface_msg(self) -> dict:
         """the last sensor_msgs/PointCloud2 on <node>/surface (parameter publish_surface_cloud): ``points`` as (width, 6) float32 in
         the order of ``fields`` (x y z normal_x normal_y normal_z) and the number published (0: no message, the parameter is off)"""
@@ -478,6 +496,44 @@ def _frontier_dict(call, fetch, what):
             "seeds_used": used.value, "origin": origin_cs[:2].copy(), "resolution": float(origin_cs[2])}
 
 
+def _plan_dict(call, fetch, width, max_len, what):
+    counts = (C.c_int * 3)()
+    info, n_seeds = capi.RouteInfo(), C.c_int(0)
+    seeds = np.zeros(2 * capi.FRONTIER_MAX_SEEDS, dtype=np.int32)
+    origin_cs = np.zeros(3)
+    rc = call(counts, C.byref(info), seeds.ctypes.data, C.byref(n_seeds), origin_cs.ctypes.data_as(_dp))
+    if rc != 0:
+        raise capi.TsdError(f"{what} failed ({rc}): no map (or, for the cost map, no cost map) published yet?")
+    n, n_cells = counts[0], counts[1]
+    rec = np.zeros(n, dtype=capi.FRONTIER_DTYPE)
+    goals = np.zeros(n, dtype=capi.ROUTE_GOAL_DTYPE)
+    lens = np.zeros(n, dtype=np.int32)
+    cells = np.zeros(max(n_cells, 1), dtype=np.uint32)
+    if n:
+        fetch(rec.ctypes.data, goals.ctypes.data, lens.ctypes.data, cells.ctypes.data)
+    res, origin = float(origin_cs[2]), origin_cs[:2].copy()
+
+    def metres(c):
+        c = np.asarray(c, dtype=np.int64)
+        return np.stack([((c % width) + 0.5) * res + origin[0], ((c // width) + 0.5) * res + origin[1]], axis=-1)
+
+    size = rec["size"].astype(np.float64)
+    cen = np.stack([(rec["sum_x"].astype(np.float64) / size + 0.5) * res + origin[0],
+                    (rec["sum_y"].astype(np.float64) / size + 0.5) * res + origin[1]], axis=1)
+    goal_xy = metres(goals["cell"]).reshape(n, 2)
+    goal_xy[goals["cell"] == capi.ROUTE_NONE] = np.nan
+    # the paths lie one after the other, min(len, max_len) cells each, goal first
+    paths, at = [], 0
+    stored = np.minimum(np.maximum(lens, 0), int(max_len))
+    assert int(stored.sum()) == n_cells
+    for k in range(n):
+        paths.append(metres(cells[at:at + stored[k]][::-1]).reshape(-1, 2))
+        at += int(stored[k])
+    return {"records": rec, "centroids": cen, "goals": goals, "goal_xy": goal_xy, "paths": paths, "path_lens": lens,
+            "route": info.as_dict(), "seeds": [tuple(int(v) for v in seeds[2 * k:2 * k + 2]) for k in range(n_seeds.value)],
+            "seeds_used": counts[2], "origin": origin, "resolution": res}
+
+
 class SlamFleet:
     """Several :class:`SlamNode` s on ONE GPU, each with its own grid, and their merged map (``ThreadGridGroup``): every node's
     ``x_offset`` / ``y_offset`` places its grid, offsets that do not differ by whole cells are refused.  The first node publishes
@@ -517,6 +573,14 @@ class SlamFleet:
         for the fleet consumes."""
         return _frontier_dict(lambda c, u, so, no, oc: self.lib.tsd_fleet_frontiers(self.h, int(min_size), c, u, so, no, oc),
                               lambda out: self.lib.tsd_fleet_frontiers_fetch(self.h, out), "tsd_fleet_frontiers")
+
+    def explore_plan(self, min_size=1, max_len=4096) -> dict:
+        """``SlamNode.explore_plan`` on the merged map published last with one seed per node (``frontiers()``'s seeds), unit weights
+        on the free cells: ``goals["seed"]`` is the node nearest to each frontier -- the assignment an exploration allocator starts
+        from -- and each path starts at that node's cell."""
+        return _plan_dict(lambda c, i, so, no, oc: self.lib.tsd_fleet_explore_plan(self.h, int(min_size), int(max_len), c, i, so, no, oc),
+                          lambda *out: self.lib.tsd_fleet_explore_plan_fetch(self.h, *out), self.merged_map_msg()["width"], max_len,
+                          "tsd_fleet_explore_plan")
 
     def merged_frames(self) -> int:
         return int(self.lib.tsd_fleet_merged_frames(self.h))
@@ -620,7 +684,7 @@ class GridView(capi.TsdGridDevice):
                "load_text", "color_image", "push_stats_total", "profile_reset", "profile_get", "profile_spread", "profile_samples", "tsdpdf_match",
                "relocalize", "debug_reloc_scores", "debug_reloc_peaks", "surface_extract", "surface_fetch", "surface_points",
                "surface_dev", "align_points", "debug_align_scores", "debug_align_peaks", "debug_align_sums",
-               "clearance_of", "costmap_begin", "frontiers_of", "frontiers")
+               "clearance_of", "costmap_begin", "frontiers_of", "frontiers", "route_of", "route", "route_goals", "route_paths")
 
     def __init__(self, ctx, node=None):  # noqa: D401 - does not call the base constructor on purpose
         self.lib = capi.load_library()
@@ -635,7 +699,7 @@ class GridView(capi.TsdGridDevice):
 
     # these also use the context's frontier scratch, which the node's ThreadGrid (and a fleet's group) use: the grid's frontierMutex
     # is taken first and held until the records and labels are fetched
-    _FRONTIER = ("frontiers_of", "frontiers")
+    _FRONTIER = ("frontiers_of", "frontiers", "route_of", "route", "route_goals", "route_paths")      # (the goals read the frontier result)
 
     def __getattribute__(self, name):
         attr = object.__getattribute__(self, name)
