@@ -749,6 +749,83 @@ int tsd_route_counts(tsd_ctx* ctx, long long* tile_visits, int* host_waits);
  * 1 is the other extreme of the schedule: the keys are the same byte for byte (tests/test_gpu_route.py), only the rounds differ. */
 int tsd_debug_set_route_sweeps(tsd_ctx* ctx, int n);
 
+/* ---- views: what a scan from a cell would uncover, and who is about to see it ------------------------------------ */
+/* The expected information gain of candidate cells (exploration goals) and the coordination rule on top of it: what one robot is
+ * about to see is no longer worth a visit by another.  Input: an int8 map on the context's device as for the frontiers and routes --
+ * width x height, `stride` bytes from row to row, bytes beyond `width` in a row never read, sides 1 .. TSD_FRONTIER_MAX_SIDE.  In
+ * integers throughout (the kernels do no floating point), so a restatement agrees to the byte (tests/view_ref.py).
+ *   cell classes   unknown: v < 0; clear: 0 <= v <= free_max; blocking: v > free_max; free_max in 0 .. 99.  A cell outside the map
+ *                  is neither seen nor passed
+ *   targets        for a candidate c = (cx, cy) and a radius R in 1 .. TSD_VIEW_MAX_RADIUS the 8R cells of the Chebyshev ring of
+ *                  radius R around c, in this order: the top row, x from -R to R at y = -R; the right column, y from -R + 1 to R;
+ *                  the bottom row, x from R - 1 to -R; the left column, y from R - 1 to -R + 1
+ *   ray to (tx, ty) step j = 1 .. R lies at the offset o(j) = (sgn(tx) * ((2 j |tx| + R) / 2R), sgn(ty) * ((2 j |ty| + R) / 2R)) by
+ *                  integer division: a closed form in j, no accumulated error term; consecutive steps differ by at most one cell
+ *                  per axis and |ox|, |oy| never decrease
+ *   a ray ends     before step j -- step j and everything behind it stay unseen -- at the first j where, tested in this order,
+ *                  1. ox^2 + oy^2 > R^2 (the range is a disc), 2. the cell lies outside the map, 3. the step is diagonal against
+ *                  step j - 1 and both cells it cuts, (x_j, y_j-1) and (x_j-1, y_j), are blocking or outside the map (an
+ *                  8-connected wall drawn on the diagonal is a wall), 4. the cell is blocking.  Otherwise the cell is seen; if it
+ *                  is unknown and unknown_depth > 0, the ray ends behind the unknown_depth-th unknown cell it has seen (the
+ *                  candidate's own cell is no step and does not count).  unknown_depth 0: no such end
+ *   V(c)           the cells seen by any of the 8R rays, plus c itself.  A candidate outside the map (cell >= width * height) or on
+ *                  a blocking cell has an empty V: its record holds its cell and zeros
+ *   record         visible = |V|, unknown = the unknown cells of V, gain = the unknown cells of V that are not claimed (= unknown
+ *                  where claims are not in use); every cell counts once however many rays cross it
+ *   claims         a uint8 image (0 / 1) of width x height that belongs to the context; claim(c) stores 1 on every unknown cell of
+ *                  V(c) -- byte stores of one value, no atomics on global memory --, so claiming is idempotent and independent of order
+ * The scanner is taken to see all around (the robot can turn): its field of view and beam count are not modelled. */
+#define TSD_VIEW_MAX_RADIUS 511
+#define TSD_VIEW_MAX_CELLS  4096
+typedef struct {
+  int32_t free_max;             /* 0 .. 99 */
+  int32_t radius;               /* R, in cells: 1 .. TSD_VIEW_MAX_RADIUS */
+  int32_t unknown_depth;        /* >= 0; 0: a ray does not end in unknown space */
+  int32_t use_claims;           /* tsd_view_gains: 0 / 1, gain leaves out the claimed cells */
+} tsd_view_params;              /* 16 bytes */
+typedef struct {
+  uint32_t cell;                /* the candidate, as given */
+  uint32_t gain, unknown, visible;
+} tsd_view_gain;                /* 16 bytes */
+/* The records of n candidates (linear indices y * width + x, host memory; 1 .. TSD_VIEW_MAX_CELLS of them), one workgroup each, whose
+ * seen set is a bit mask of the candidate's window in LDS sized by the radius.  map_dev != NULL: any map on the context's device; the
+ * call runs on the context's stream.  map_dev == NULL: the staged map of the context's last frame or update (width, height and
+ * stride are ignored), on the context's copy stream behind the frame's event, under tsd_route_frame's conditions and refusals.
+ * Either way the call waits; the grid and its write ledger are not touched.  Candidates, records, claims and their pinned copies stay
+ * with the context and grow on demand, so a repeated call at the same size allocates nothing.  One view call at a time per context,
+ * under the same lock as the frontier and route calls.  TSD_E_NOMEM (tsd_last_error says which buffer) where the device cannot
+ * hold it.  TSD_E_ARG, with the claims image left as it was: a NULL params, cells or out, n outside 1 .. TSD_VIEW_MAX_CELLS, a
+ * radius outside 1 .. TSD_VIEW_MAX_RADIUS, free_max outside 0 .. 99, unknown_depth < 0, a side outside 1 .. TSD_FRONTIER_MAX_SIDE,
+ * stride < width, use_claims without a claims image of the map's width and height. */
+int tsd_view_gains(tsd_ctx* ctx, const void* map_dev, int width, int height, int stride, const tsd_view_params* params,
+                   const uint32_t* cells_host, int n, tsd_view_gain* out_host);
+/* claim(c) for n candidates: the same rays, a store pass in place of the count.  use_claims is ignored.  TSD_E_ARG as above, and
+ * without a claims image of the map's width and height. */
+int tsd_view_claim(tsd_ctx* ctx, const void* map_dev, int width, int height, int stride, const tsd_view_params* params,
+                   const uint32_t* cells_host, int n);
+/* Allocates the claims image at width x height, or clears it; on the context's stream, waited for.  TSD_E_ARG for a side outside
+ * 1 .. TSD_FRONTIER_MAX_SIDE. */
+int tsd_view_claims_reset(tsd_ctx* ctx, int width, int height);
+/* The claims image on the device (uint8, rows of `width` bytes), valid until the next reset at a larger size or tsd_destroy.  Each
+ * pointer may be NULL.  TSD_E_ARG without an image. */
+int tsd_view_claims_dev_ptr(tsd_ctx* ctx, const void** claims_dev, int* width, int* height);
+/* The coordination rule, on the goals of a route plan (tsd_route_goals_fetch; host memory, 0 .. TSD_VIEW_MAX_CELLS of them) for
+ * robots 0 .. n_robots - 1 (the route's seeds; 1 .. TSD_FRONTIER_MAX_SEEDS):
+ *   1. the claims are reset at the map's size;  2. the goals with cell != TSD_ROUTE_NONE and 0 <= seed < n_robots are remaining;
+ *   3. a round takes the gains of all remaining goals with claims in use;  4. it scores (int64) gain * gain_weight - dist;
+ *   5. it picks the highest score, on a tie the lower goal index;  6. it stops if that goal's gain is 0;
+ *   7. it gives the goal to robot `seed` and claims V of its cell;  8. it drops that goal and every goal with the same seed;
+ *   9. it goes on while goals remain.
+ * goal_of_robot[r]: the index of robot r's goal, -1 where it got none; picked[r] (may be NULL): that goal's record as its round saw it,
+ * {TSD_ROUTE_NONE, 0, 0, 0} without a goal; *rounds: the rounds begun (at most n_robots), each one launch for the gains, one wait and,
+ * where a goal was given, one launch for the claim.  The limit of the rule: a robot is only ever offered the goals it is nearest to,
+ * because the route's key image holds one field for all seeds.  The claims image holds the claims of the goals given when the call
+ * returns.  The map source, the stream and the refusals are tsd_view_gains'; TSD_E_ARG also for n_goals or n_robots out of range, a
+ * NULL goals with n_goals > 0, a NULL goal_of_robot or rounds -- the claims image is left as it was then. */
+int tsd_view_assign(tsd_ctx* ctx, const void* map_dev, int width, int height, int stride, const tsd_view_params* params,
+                    const tsd_route_goal* goals, int n_goals, int n_robots, uint32_t gain_weight,
+                    int32_t* goal_of_robot /* n_robots, -1: none */, tsd_view_gain* picked /* n_robots or NULL */, int* rounds);
+
 /* ---- the map's surface as an ordered point list --------------------------------------------------------------- */
 /* The `coords` array of RayCastAxisAligned2D::calcCoords (RayCastAxisAligned2D.cpp:13-105), point for point and in its serial order:
  * the linear zero crossings of the TSD along every row and column of every initialised tile of the processed ring (tiles 1 .. PX-2 in
@@ -998,7 +1075,8 @@ int tsd_fuse(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell_off_x
  * "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse", "clearance" (both kernels of tsd_clearance_dev), and the passes of
  * tsd_frontiers_dev: "frontier_tile", "frontier_seam", "frontier_flatten" (each once for the frontiers and once more for the regions
  * where seeds are given), "frontier_rank" (count, scan, emit), "frontier_stats" (with the min_size compaction), and those of
- * tsd_route_dev, tsd_route_goals and tsd_route_trace: "route_init", "route_relax" (a batch of rounds), "route_goals", "route_trace". */
+ * tsd_route_dev, tsd_route_goals and tsd_route_trace: "route_init", "route_relax" (a batch of rounds), "route_goals", "route_trace",
+ * and the launches of tsd_view_gains and tsd_view_claim on the context's stream: "view_gain", "view_claim". */
 int tsd_profile_enable(tsd_ctx* ctx, int on);
 /* restrict timing to a comma separated list of kernel names, or "all"; a "/n" suffix times every n-th
  * launch only (two event records cost ~13 us of stream time per timed launch); a name may carry its own

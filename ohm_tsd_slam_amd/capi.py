@@ -174,6 +174,24 @@ ROUTE_GOAL_DTYPE = np.dtype([("cell", "<u4"), ("dist", "<u4"), ("seed", "<i4"), 
 assert ROUTE_GOAL_DTYPE.itemsize == C.sizeof(RouteGoal) == 16
 
 
+VIEW_MAX_RADIUS = 511
+VIEW_MAX_CELLS = 4096
+
+
+class ViewParams(C.Structure):
+    """tsd_view_params"""
+    _fields_ = [("free_max", C.c_int32), ("radius", C.c_int32), ("unknown_depth", C.c_int32), ("use_claims", C.c_int32)]
+
+
+class ViewGain(C.Structure):
+    """tsd_view_gain"""
+    _fields_ = [("cell", C.c_uint32), ("gain", C.c_uint32), ("unknown", C.c_uint32), ("visible", C.c_uint32)]
+
+
+VIEW_GAIN_DTYPE = np.dtype([("cell", "<u4"), ("gain", "<u4"), ("unknown", "<u4"), ("visible", "<u4")])
+assert VIEW_GAIN_DTYPE.itemsize == C.sizeof(ViewGain) == C.sizeof(ViewParams) == 16
+
+
 class FuseStats(C.Structure):
     """tsd_fuse_stats"""
     _fields_ = [("tiles_materialised", C.c_int64), ("tiles_empty", C.c_int64), ("cells_valid", C.c_int64),
@@ -391,6 +409,12 @@ ABI = {
     "tsd_route_dev_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), _ip, _ip]),
     "tsd_route_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _ip]),
     "tsd_debug_set_route_sweeps": (C.c_int, [C.c_void_p, C.c_int]),
+    "tsd_view_gains": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_void_p]),
+    "tsd_view_claim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int]),
+    "tsd_view_claims_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "tsd_view_claims_dev_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), _ip, _ip]),
+    "tsd_view_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_int,
+                                  C.c_uint32, C.c_void_p, C.c_void_p, _ip]),
     "tsd_dev_alloc": (C.c_void_p, [C.c_void_p, C.c_uint64]),
     "tsd_dev_free": (None, [C.c_void_p, C.c_void_p]),
     "tsd_dev_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
@@ -470,7 +494,8 @@ def load_library(path: str | None = None):
                           ("tsd_align_params", AlignParams), ("tsd_align_peak", AlignPeak), ("tsd_align_result", AlignResult),
                           ("tsd_costmap_params", CostmapParams), ("tsd_frontier", Frontier),
                           ("tsd_frontier_params", FrontierParams), ("tsd_route_params", RouteParams),
-                          ("tsd_route_info", RouteInfo), ("tsd_route_goal", RouteGoal)):
+                          ("tsd_route_info", RouteInfo), ("tsd_route_goal", RouteGoal),
+                          ("tsd_view_params", ViewParams), ("tsd_view_gain", ViewGain)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -1304,6 +1329,77 @@ class TsdGridDevice:
         self.last_rc = rc
         self._check(rc, "tsd_route_trace")
         return [paths[g, :min(max(int(n), 0), int(max_len))].copy() for g, n in enumerate(lens)], lens
+
+    # ---- views (tsd_view_gains / _claim / _claims_reset / _claims_dev_ptr / _assign)
+    def view_gains_of(self, dev_ptr, width: int, height: int, stride: int, cells, radius: int, free_max=0, unknown_depth=0,
+                      use_claims=False) -> np.ndarray:
+        """tsd_view_gains on a device map (``dev_ptr``: int8, ``height`` rows of ``stride`` bytes; None: the staged map of the frame
+        or update taken last): for every candidate cell (linear index) what a scanner there would see within ``radius`` cells, as a
+        structured array of VIEW_GAIN_DTYPE (cell, gain, unknown, visible)"""
+        cells = np.ascontiguousarray(cells, dtype=np.uint32).ravel()
+        out = np.zeros(cells.size, dtype=VIEW_GAIN_DTYPE)
+        prm = ViewParams(int(free_max), int(radius), int(unknown_depth), int(bool(use_claims)))
+        rc = self.lib.tsd_view_gains(self.h, None if dev_ptr is None else C.c_void_p(dev_ptr), int(width), int(height), int(stride),
+                                     C.byref(prm), cells.ctypes.data, int(cells.size), out.ctypes.data)
+        self.last_rc = rc
+        self._check(rc, "tsd_view_gains")
+        return out
+
+    def view_gains(self, cells, radius: int, free_max=0, unknown_depth=0, use_claims=False) -> np.ndarray:
+        """the same for the map of the frame or update taken last (cells x cells)"""
+        return self.view_gains_of(None, 0, 0, 0, cells, radius, free_max, unknown_depth, use_claims)
+
+    def view_claim_of(self, dev_ptr, width: int, height: int, stride: int, cells, radius: int, free_max=0, unknown_depth=0):
+        """tsd_view_claim: marks the unknown cells every candidate would see in the context's claims image (view_claims_reset first)"""
+        cells = np.ascontiguousarray(cells, dtype=np.uint32).ravel()
+        prm = ViewParams(int(free_max), int(radius), int(unknown_depth), 0)
+        rc = self.lib.tsd_view_claim(self.h, None if dev_ptr is None else C.c_void_p(dev_ptr), int(width), int(height), int(stride),
+                                     C.byref(prm), cells.ctypes.data, int(cells.size))
+        self.last_rc = rc
+        self._check(rc, "tsd_view_claim")
+
+    def view_claim(self, cells, radius: int, free_max=0, unknown_depth=0):
+        """the same for the map of the frame or update taken last"""
+        self.view_claim_of(None, 0, 0, 0, cells, radius, free_max, unknown_depth)
+
+    def view_claims_reset(self, width: int, height: int):
+        """tsd_view_claims_reset: the claims image at width x height, all 0"""
+        rc = self.lib.tsd_view_claims_reset(self.h, int(width), int(height))
+        self.last_rc = rc
+        self._check(rc, "tsd_view_claims_reset")
+
+    def view_claims_dev_ptr(self):
+        """tsd_view_claims_dev_ptr: (claims_dev, width, height)"""
+        p, w, h = C.c_void_p(), C.c_int(0), C.c_int(0)
+        self._check(self.lib.tsd_view_claims_dev_ptr(self.h, C.byref(p), C.byref(w), C.byref(h)), "tsd_view_claims_dev_ptr")
+        return p.value, w.value, h.value
+
+    def view_claims(self) -> np.ndarray:
+        """the claims image, (height, width) uint8, copied to the host"""
+        p, w, h = self.view_claims_dev_ptr()
+        img = np.zeros((h, w), dtype=np.uint8)
+        self._check(self.lib.tsd_dev_copy(self.h, img.ctypes.data, p, img.nbytes, 0), "tsd_dev_copy")
+        return img
+
+    def view_assign_of(self, dev_ptr, width: int, height: int, stride: int, goals, n_robots: int, radius: int, gain_weight: int,
+                       free_max=0, unknown_depth=0):
+        """tsd_view_assign on the goals of a route plan (ROUTE_GOAL_DTYPE): (goal_of_robot int32[n_robots] -- the index of the goal
+        each robot is given, -1 for none --, the picked goals' records as their rounds saw them, the rounds)"""
+        goals = np.ascontiguousarray(goals, dtype=ROUTE_GOAL_DTYPE).ravel()
+        goal_of = np.full(int(n_robots), -7, dtype=np.int32)
+        picked = np.zeros(int(n_robots), dtype=VIEW_GAIN_DTYPE)
+        rounds = C.c_int(-1)
+        prm = ViewParams(int(free_max), int(radius), int(unknown_depth), 0)
+        rc = self.lib.tsd_view_assign(self.h, None if dev_ptr is None else C.c_void_p(dev_ptr), int(width), int(height), int(stride),
+                                      C.byref(prm), goals.ctypes.data if goals.size else None, int(goals.size), int(n_robots),
+                                      int(gain_weight), goal_of.ctypes.data, picked.ctypes.data, C.byref(rounds))
+        self.last_rc = rc
+        self._check(rc, "tsd_view_assign")
+        return goal_of, picked, rounds.value
+
+    def view_assign(self, goals, n_robots: int, radius: int, gain_weight: int, free_max=0, unknown_depth=0):
+        """the same for the map of the frame or update taken last"""
+        return self.view_assign_of(None, 0, 0, 0, goals, n_robots, radius, gain_weight, free_max, unknown_depth)
 
     def push_stats_total(self, reset=False):
         st = PushStats()

@@ -26,6 +26,7 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
     _hRgb(nullptr),
     _frames(0),
     _updates(0),
+    _planStamp(~(uint64_t)0),
     _surfaces(0)
 {
   // (ThreadGrid.cpp:16-40)
@@ -408,7 +409,51 @@ int ThreadGrid::explorePlan(const int32_t* seedsXy, int n, uint32_t minSize, int
   prm.weights = weights;
   prm.limit = 0;
   prm.max_rounds = 0;
-  return routePlan(_grid.context(), nullptr, 0, 0, source, prm, maxLen, out);
+  _planStamp = ~(uint64_t)0;
+  rc = routePlan(_grid.context(), nullptr, 0, 0, source, prm, maxLen, out);
+  if(rc == TSD_OK)
+    _planStamp = _frames + _updates;
+  return rc;
+}
+
+// The view entry points are weak references like the routes'.
+#pragma weak tsd_view_gains
+#pragma weak tsd_view_assign
+
+int viewRadiusCells(double viewRadius, double cellSize)
+{
+  if(!(viewRadius > 0.0) || !(cellSize > 0.0))
+    return 1;
+  const double cells = std::floor(viewRadius / cellSize + 0.5);
+  return cells < 1.0 ? 1 : cells > (double)TSD_VIEW_MAX_RADIUS ? TSD_VIEW_MAX_RADIUS : static_cast<int>(cells);
+}
+
+int ThreadGrid::exploreGains(const tsd_route_goal* goals, size_t n, double viewRadius, int unknownDepth, tsd_view_gain* out, int* radiusCells)
+{
+  if(!tsd_view_gains || (n > 0 && (!goals || !out)) || unknownDepth < 0)
+    return TSD_E_ARG;
+  std::lock_guard<std::mutex> lk(_publishMutex);
+  if(_planStamp != _frames + _updates)
+    return TSD_E_ARG;                  // no plan, or one of a map that has been published over
+  tsd_view_params prm;
+  prm.free_max = 0;
+  prm.radius = viewRadiusCells(viewRadius, static_cast<double>(_grid.getCellSize()));
+  prm.unknown_depth = unknownDepth;
+  prm.use_claims = 0;
+  if(radiusCells)
+    *radiusCells = prm.radius;
+  std::lock_guard<std::mutex> fl(_grid.frontierMutex());
+  std::vector<uint32_t> cells(n);
+  for(size_t i = 0; i < n; i++)
+    cells[i] = goals[i].cell;          // (TSD_ROUTE_NONE lies outside every map: a record of zeros)
+  for(size_t first = 0; first < n; first += TSD_VIEW_MAX_CELLS)
+  {
+    const int count = static_cast<int>(std::min<size_t>(TSD_VIEW_MAX_CELLS, n - first));
+    const int rc = tsd_view_gains(_grid.context(), nullptr, 0, 0, 0, &prm, cells.data() + first, count, out + first);
+    if(rc != TSD_OK)
+      return rc;
+  }
+  return TSD_OK;
 }
 
 void ThreadGrid::mapPlacement(double* originRes)

@@ -42,6 +42,8 @@ struct ExplorePlan
  *  mapDev nullptr: the frame form from `source`, else the generic form on mapDev (width x height, rows of width bytes).  The caller
  *  holds the context's frontierMutex, and for the generic form the grid's mutex.  TSD_E_ARG where the device library has no routes. */
 int routePlan(tsd_ctx* ctx, const void* mapDev, int width, int height, int source, const tsd_route_params& prm, int maxLen, ExplorePlan* out);
+/** A view radius [m] in cells: rounded to the nearest, at least 1 and at most TSD_VIEW_MAX_RADIUS. */
+int viewRadiusCells(double viewRadius, double cellSize);
 
 class ThreadGrid : public ThreadSLAM
 {
@@ -94,6 +96,11 @@ public:
    *  TSD_FRONTIER_MAX_SEEDS.  Holds the publish mutex and, from the frontier call to the last fetch, the grid's frontierMutex (the
    *  goals read the frontier result).  TSD_E_ARG before the first publication. */
   int explorePlan(const int32_t* seedsXy, int n, uint32_t minSize, int source, int maxWeight, int maxLen, ExplorePlan* out, double* originRes);
+  /** What a scanner standing on each of `n` goals of the plan made last would see within viewRadius [m] (tsd_view_gains on the staged
+   *  map, free_max 0; the radius rounded to cells, at least 1 and at most TSD_VIEW_MAX_RADIUS, returned in *radiusCells): one record
+   *  per goal, zeros for a goal without a cell.  Holds the publish mutex and the grid's frontierMutex.  TSD_E_ARG without a plan, where
+   *  the map has been published again since the plan was made, and where the device library has no views. */
+  int exploreGains(const tsd_route_goal* goals, size_t n, double viewRadius, int unknownDepth, tsd_view_gain* out, int* radiusCells);
   /** origin x, y and resolution of <node>/map: fixed by the parameters at construction, the same before and after a publication */
   void mapPlacement(double* originRes);
 
@@ -147,6 +154,7 @@ private:
   std::mutex _msgMutex;          // _occGrid between a publication and the get_map service
   uint64_t _frames;
   uint64_t _updates;
+  uint64_t _planStamp;           // _frames + _updates when explorePlan last succeeded (under _publishMutex; ~0: no plan)
   uint64_t _surfaces;
 };
 

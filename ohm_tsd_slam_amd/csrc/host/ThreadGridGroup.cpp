@@ -35,7 +35,8 @@ ThreadGridGroup::ThreadGridGroup(const std::shared_ptr<rclcpp::Node>& node, cons
     _width(0),
     _height(0),
     _hOcc(nullptr),
-    _frames(0)
+    _frames(0),
+    _planFrames(0)
 {
   const double cs = static_cast<double>(_grid.getCellSize());
   // the merged window's origin is the smallest origin along each axis; every grid lies a whole number of cells from grid 0
@@ -239,7 +240,35 @@ int ThreadGridGroup::frontiersAndPlan(const double* gridXy, uint32_t minSize, st
   }
   if(seedsUsed)
     *seedsUsed = used;
+  if(plan)
+    _planFrames = rc == TSD_OK ? _frames : 0;
   return rc;
+}
+
+#pragma weak tsd_view_assign
+
+int ThreadGridGroup::exploreAssign(const tsd_route_goal* goals, size_t n, double viewRadius, uint32_t gainWeight, int unknownDepth,
+                                   int32_t* goalOfRobot, tsd_view_gain* picked, int* rounds, int* radiusCells)
+{
+  if(!tsd_view_assign || (n > 0 && !goals) || n > (size_t)TSD_VIEW_MAX_CELLS || !goalOfRobot || !rounds || unknownDepth < 0 ||
+     _members.size() > (size_t)TSD_FRONTIER_MAX_SEEDS)
+    return TSD_E_ARG;
+  std::lock_guard<std::mutex> lk(_publishMutex);
+  if(_planFrames == 0 || _planFrames != _frames)
+    return TSD_E_ARG;                  // no plan, or one of a merged map that has been published over
+  tsd_view_params prm;
+  prm.free_max = 0;
+  prm.radius = viewRadiusCells(viewRadius, static_cast<double>(_grid.getCellSize()));
+  prm.unknown_depth = unknownDepth;
+  prm.use_claims = 0;
+  if(radiusCells)
+    *radiusCells = prm.radius;
+  // as for the plan: member 0's context and stream carry the call
+  std::lock_guard<std::mutex> fl(_members[0].grid->frontierMutex());
+  std::lock_guard<std::mutex> g(_members[0].grid->mutex());
+  return tsd_view_assign(_members[0].grid->context(), tsd_group_map_dev(_group), static_cast<int>(_width), static_cast<int>(_height),
+                         static_cast<int>(_width), &prm, goals, static_cast<int>(n), static_cast<int>(_members.size()), gainWeight, goalOfRobot,
+                         picked, rounds);
 }
 
 int ThreadGridGroup::fuse(obvious::TsdGrid* dst)
@@ -297,6 +326,7 @@ void ThreadGridGroup::setTransforms(const std::vector<std::array<double, 9>>& T)
     throw std::invalid_argument("ThreadGridGroup::setTransforms: the device refused the transforms (rigid, finite, within 65536 cells)");
   tsd_group_destroy(_group);
   _group = group;
+  _planFrames = 0;               // (a plan's cells are those of the window that goes)
   if(_hOcc)
     tsd_host_free(_hOcc);
   _hOcc = nullptr;               // (publish() allocates the landing buffer for the new window)

@@ -70,6 +70,14 @@ public:
    *  the goal of every frontier -- its `seed` is the member nearest to that frontier, what an allocator starts from -- and the paths,
    *  cut at maxLen cells.  The two locks of frontiers() are held to the last fetch. */
   int explorePlan(const double* gridXy, uint32_t minSize, int maxLen, ExplorePlan* out, int32_t* seedsXy, double* originCs);
+  /** Which member drives to which goal of the plan made last (tsd_view_assign on the merged map, free_max 0, one robot per member):
+   *  a goal's worth is the unknown cells a scanner there would see within viewRadius [m] (rounded to cells, at least 1 and at most
+   *  TSD_VIEW_MAX_RADIUS, returned in *radiusCells), and what one member is about to see is no longer worth a visit by another.
+   *  goalOfRobot and picked hold one entry per member.  A member is only ever offered the goals it is nearest to.  Holds the publish
+   *  mutex and member 0's frontierMutex and grid mutex.  TSD_E_ARG without a plan, where the merged map has been published again or
+   *  re-placed since the plan was made, and where the device library has no views. */
+  int exploreAssign(const tsd_route_goal* goals, size_t n, double viewRadius, uint32_t gainWeight, int unknownDepth, int32_t* goalOfRobot,
+                    tsd_view_gain* picked, int* rounds, int* radiusCells);
   size_t members(void) const { return _members.size(); }
 
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }
@@ -98,6 +106,7 @@ private:
   std::mutex _publishMutex;      // one merge at a time (event loop, publish())
   std::mutex _msgMutex;          // _occGrid between a publication and the get_merged_map service
   uint64_t _frames;
+  uint64_t _planFrames;          // _frames when explorePlan last succeeded (under _publishMutex; 0: no plan)
 };
 
 } /* namespace ohm_tsd_slam */

@@ -633,6 +633,15 @@ void tsd_node_explore_plan_fetch(tsd_node* n, tsd_frontier* rec, tsd_route_goal*
     plan_fetch(n->plan, rec, goals, lens, paths);
 }
 
+// What a scan from each goal of the plan made last would uncover (ThreadGrid::exploreGains): one tsd_view_gain per goal of
+// tsd_node_explore_plan's counts, on the same frame; *radius_cells: the radius the call used.
+int tsd_node_explore_gains(tsd_node* n, double view_radius_m, int unknown_depth, tsd_view_gain* out, int* radius_cells)
+{
+  if(!n || !n->gridThread || (!out && !n->plan.goals.empty()))
+    return TSD_E_ARG;
+  return n->gridThread->exploreGains(n->plan.goals.data(), n->plan.goals.size(), view_radius_m, unknown_depth, out, radius_cells);
+}
+
 // <node>/get_map (ThreadGrid::getMapServCallBack): the last map with a fresh stamp (map_out layout); 1 if the service answered
 int tsd_node_get_map(tsd_node* n, int8_t* data_out, double* out12, char* frame_id, int cap)
 {
@@ -826,6 +835,16 @@ void tsd_fleet_explore_plan_fetch(tsd_fleet* f, tsd_frontier* rec, tsd_route_goa
 {
   if(f)
     plan_fetch(f->plan, rec, goals, lens, paths);
+}
+
+// Which node takes which goal of the plan made last (ThreadGridGroup::exploreAssign): goal_of_robot and picked hold one entry per node.
+int tsd_fleet_explore_assign(tsd_fleet* f, double view_radius_m, unsigned gain_weight, int unknown_depth, int32_t* goal_of_robot,
+                             tsd_view_gain* picked, int* rounds, int* radius_cells)
+{
+  if(!f || !f->group)
+    return TSD_E_ARG;
+  return f->group->exploreAssign(f->plan.goals.data(), f->plan.goals.size(), view_radius_m, gain_weight, unknown_depth, goal_of_robot, picked,
+                                 rounds, radius_cells);
 }
 
 // every node's position (robot 0's last estimated pose) in ITS grid's coordinates, NaN without a pose: what the group's calls take

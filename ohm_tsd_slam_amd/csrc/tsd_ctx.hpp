@@ -334,6 +334,13 @@ struct tsd_ctx {
     int sweeps = 0;                                                               // tsd_debug_set_route_sweeps (0: the default)
     long long tile_visits = 0; int host_waits = 0;
   } route;
+  // views (view.hip: tsd_view_gains / _claim / _claims_reset / _assign).  The candidates, their records and the pinned copies of both
+  // (one capacity), and the claims image with the size it was reset at (cW == 0: none).  Allocated on first use, grown on demand and
+  // kept.  Every call waits for its own work, so nothing of this is ever in flight between calls
+  struct View {
+    uint32_t* d_cells = nullptr; tsd_view_gain* d_rec = nullptr; uint32_t* h_cells = nullptr; tsd_view_gain* h_rec = nullptr; size_t cap = 0;
+    uint8_t* d_claims = nullptr; size_t claims_cap = 0; int cW = 0, cH = 0;
+  } view;
   // TSD-level fusion (fuse.hip).  As the destination: the kernel's sharded counters and their pinned copy.  As a member: events of its
   // own -- "every grid write enqueued so far" on its stream / its push stream, "the fusion that read this grid last is done" (recorded
   // on the destination's stream; the member's streams wait for it at once) -- all created on first use
@@ -376,7 +383,7 @@ struct tsd_ctx {
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;
   unsigned profile_every = 1;   // time every n-th launch of a selected kernel ("name/n" in tsd_profile_select)
-  unsigned profile_every_k[18] = {};   // a kernel's own period ("name:m"), 0 = the list's
+  unsigned profile_every_k[20] = {};   // a kernel's own period ("name:m"), 0 = the list's
   bool profile = false;
   std::map<std::string, tsd::KernelTimer> timers;
   std::vector<hipEvent_t> event_pool;
@@ -614,6 +621,7 @@ void align_free(tsd_ctx* ctx);               // align.hip: releases tsd_ctx::ali
 void clearance_free(tsd_ctx* ctx);           // clearance.hip: releases tsd_ctx::clearance (tsd_destroy)
 void frontier_free(tsd_ctx* ctx);            // frontier.hip: releases tsd_ctx::frontier (tsd_destroy)
 void route_free(tsd_ctx* ctx);               // route.hip: releases tsd_ctx::route (tsd_destroy)
+void view_free(tsd_ctx* ctx);                // view.hip: releases tsd_ctx::view (tsd_destroy)
 int8_t* frame_staged_map(const tsd_ctx* ctx);   // map_publish.hip: the frame staging's map (cells * cells int8), nullptr without a staging
 int launch_calibrate(tsd_ctx* ctx, double* t, double* w, size_t n);
 int launch_occupancy(tsd_ctx* ctx, int8_t* d_out, int inflate, int inflate_factor);

@@ -65,6 +65,8 @@ HOST_ABI = {
     "tsd_node_explore_plan_fetch": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsd_fleet_explore_plan": (C.c_int, [C.c_void_p, C.c_uint, C.c_int, _ip, C.POINTER(capi.RouteInfo), C.c_void_p, _ip, _dp]),
     "tsd_fleet_explore_plan_fetch": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsd_node_explore_gains": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_void_p, _ip]),
+    "tsd_fleet_explore_assign": (C.c_int, [C.c_void_p, C.c_double, C.c_uint, C.c_int, C.c_void_p, C.c_void_p, _ip, _ip]),
     "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_grid_lock": (None, [C.c_void_p]),
@@ -440,9 +442,28 @@ class SlamNode:
         the goal where the path is longer), ``path_lens`` (the full lengths in cells) and ``route`` (tsd_route_info as a dict).
         source "map": unit weights on the free cells; "costmap": the cost map of the last publication (parameter publish_costmap),
         traversable below the inscribed band, weights tsd_route_weights(98, max_weight)."""
-        return _plan_dict(lambda c, i, so, no, oc: self.lib.tsd_node_explore_plan(
+        self._plan_goals = None
+        out = _plan_dict(lambda c, i, so, no, oc: self.lib.tsd_node_explore_plan(
             self.h, None, -1, int(min_size or 0), capi.ROUTE_SOURCES[source], int(max_weight), int(max_len), c, i, so, no, oc),
             lambda *out: self.lib.tsd_node_explore_plan_fetch(self.h, *out), self.map_msg()["width"], max_len, "tsd_node_explore_plan")
+        self._plan_goals = len(out["goals"])
+        return out
+
+    def explore_gains(self, view_radius_m: float, unknown_depth=0) -> np.ndarray:
+        """What each goal of the plan made last is worth: the capi.VIEW_GAIN_DTYPE records (cell, gain, unknown, visible), one per
+        goal and in the goals' order, of a scanner standing on the goal and seeing ``view_radius_m`` far all around on the map the
+        plan was made on -- the radius rounded to cells, at most capi.VIEW_MAX_RADIUS; ``unknown_depth`` > 0 ends a ray behind that
+        many unknown cells.  Zeros for a goal without a cell.  Refused without a plan and once the map has been published again."""
+        n = getattr(self, "_plan_goals", None)
+        if n is None:
+            raise capi.TsdError("explore_gains: no plan (explore_plan first)")
+        out = np.zeros(n, dtype=capi.VIEW_GAIN_DTYPE)
+        radius = C.c_int(0)
+        rc = self.lib.tsd_node_explore_gains(self.h, float(view_radius_m), int(unknown_depth), out.ctypes.data, C.byref(radius))
+        if rc != 0:
+            raise capi.TsdError(f"tsd_node_explore_gains failed ({rc})")
+        self.view_radius_cells = radius.value
+        return out
 
     def surface_msg(self) -> dict:
         """the last sensor_msgs/PointCloud2 on <node>/surface (parameter publish_surface_cloud): ``points`` as (width, 6) float32 in
@@ -581,6 +602,22 @@ class SlamFleet:
         return _plan_dict(lambda c, i, so, no, oc: self.lib.tsd_fleet_explore_plan(self.h, int(min_size), int(max_len), c, i, so, no, oc),
                           lambda *out: self.lib.tsd_fleet_explore_plan_fetch(self.h, *out), self.merged_map_msg()["width"], max_len,
                           "tsd_fleet_explore_plan")
+
+    def explore_assign(self, view_radius_m: float, gain_weight: int, unknown_depth=0) -> dict:
+        """Which node drives where, on the merged map's plan made last (tsd_view_assign): ``goal_of_robot`` int32 per node -- an index
+        into the plan's goals, -1 for a node that gets none --, ``picked`` (capi.VIEW_GAIN_DTYPE per node: the goal's record as its
+        round saw it), ``rounds`` and ``radius_cells``.  A goal scores gain * ``gain_weight`` - dist; the best goal goes to the node
+        it is nearest to, what that node will see is claimed, and the rest is scored again.  A node is only ever offered the goals it
+        is nearest to.  Refused without a plan and once the merged map has been published again."""
+        n = len(self.nodes)
+        goal_of = np.full(n, -1, dtype=np.int32)
+        picked = np.zeros(n, dtype=capi.VIEW_GAIN_DTYPE)
+        rounds, radius = C.c_int(0), C.c_int(0)
+        rc = self.lib.tsd_fleet_explore_assign(self.h, float(view_radius_m), int(gain_weight), int(unknown_depth), goal_of.ctypes.data,
+                                               picked.ctypes.data, C.byref(rounds), C.byref(radius))
+        if rc != 0:
+            raise capi.TsdError(f"tsd_fleet_explore_assign failed ({rc})")
+        return {"goal_of_robot": goal_of, "picked": picked, "rounds": rounds.value, "radius_cells": radius.value}
 
     def merged_frames(self) -> int:
         return int(self.lib.tsd_fleet_merged_frames(self.h))
