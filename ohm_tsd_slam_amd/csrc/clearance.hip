@@ -15,15 +15,15 @@
 //
 // The mask pass covers the column pass's workgroup-aligned area grown by R, so every word and tile flag the column pass reads was
 // written by the same call.
-#include "capi_internal.hpp"
+#include "map_product.hpp"
 
 namespace tsd {
 
 constexpr int CLR_BW = 64, CLR_BH = 32;      // cells of one workgroup of the column pass
 constexpr int CLR_CHUNK = 512;               // cells of a row that one wave of the mask pass turns into 64 mask bytes
 constexpr int CLR_TABLE_BYTES = TSD_CLEARANCE_MAX_RADIUS * TSD_CLEARANCE_MAX_RADIUS + 4;   // the table, padded to dwords
+constexpr int CLR_MAX_SIDE = 65536;          // the sides this file takes: above TSD_FRONTIER_MAX_SIDE, the other products' limit
 
-struct ClrMap { const int8_t* map; int W, H; size_t stride; };
 struct ClrScratch { uint8_t* mask; size_t row_bytes; uint8_t* tiles; int tiles_w; };
 struct ClrWindow { int x0, y0, x1, y1; };    // cells, half open
 
@@ -36,7 +36,7 @@ __device__ __forceinline__ unsigned bytes_equal_100(uint64_t v)
 }
 
 __global__ void __launch_bounds__(256)
-k_clear_mask(ClrMap m, ClrScratch s, int c0, int t0, int aligned)
+k_clear_mask(MapView m, ClrScratch s, int c0, int t0, int aligned)
 {
   __shared__ unsigned int s_any;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -80,7 +80,7 @@ __device__ __forceinline__ int8_t cost_of(int8_t src, int8_t c)
 // kx0 / ty0: the mask word and the tile row of workgroup (0, 0).  d2 / cost: W x H, may be nullptr (cost only with kCost).
 template <bool kCost>
 __global__ void __launch_bounds__(256)
-k_clear_field(ClrMap m, ClrScratch s, ClrWindow w, int kx0, int ty0, int R, const int8_t* __restrict__ table,
+k_clear_field(MapView m, ClrScratch s, ClrWindow w, int kx0, int ty0, int R, const int8_t* __restrict__ table,
               uint16_t* __restrict__ d2, int8_t* __restrict__ cost, int skip, int aligned)
 {
   extern __shared__ __attribute__((aligned(16))) uint16_t s_g[];      // [32 + 2R][64], then the table
@@ -181,7 +181,8 @@ k_clear_field(ClrMap m, ClrScratch s, ClrWindow w, int kx0, int ty0, int R, cons
 
 static size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
 
-// the scratch for a W x H map; replaced (behind everything that may still read it) where it is too small
+// the scratch for a W x H map; replaced (behind everything that may still read it) where it is too small.  Not map_product.hpp's scratch_grow,
+// here and in tsd_costmap_begin: this file waits for both streams before a buffer goes, and a failed allocation is TSD_E_HIP, out of memory too.
 static int clearance_scratch(tsd_ctx* ctx, int W, int H, ClrScratch* out)
 {
   tsd_ctx::Clearance& c = ctx->clearance;
@@ -214,7 +215,7 @@ static int clearance_scratch(tsd_ctx* ctx, int W, int H, ClrScratch* out)
 
 // Both kernels on `stream` for the window `win` of the map; table: R * R + 1 host bytes or nullptr (then cost is nullptr too).
 // The caller has checked the arguments and that nothing else of the context uses the scratch.
-static int launch_clearance(tsd_ctx* ctx, hipStream_t stream, const ClrMap& m, const tsd_map_window& win, int R, const int8_t* table,
+static int launch_clearance(tsd_ctx* ctx, hipStream_t stream, const MapView& m, const tsd_map_window& win, int R, const int8_t* table,
                             uint16_t* d2, int8_t* cost, bool timed)
 {
   ClrScratch s;
@@ -287,8 +288,7 @@ int tsd_clearance_dev(tsd_ctx* ctx, const void* map_dev, int width, int height, 
                       const int8_t* table, void* dist2_dev, void* cost_dev)
 {
   if (!ctx) return TSD_E_ARG;
-  if (!map_dev || width < 1 || height < 1 || width > 65536 || height > 65536 || stride < width || (!dist2_dev && !cost_dev) ||
-      (cost_dev && !table))
+  if (caller_map_wrong(map_dev, width, height, stride, CLR_MAX_SIDE) || (!dist2_dev && !cost_dev) || (cost_dev && !table))
     return set_error(ctx, TSD_E_ARG, "tsd_clearance_dev: a null map, a size outside 1 .. 65536, no output, or a cost map without a table", hipSuccess);
   if (radius_cells < 1 || radius_cells > TSD_CLEARANCE_MAX_RADIUS)
     return set_error(ctx, TSD_E_ARG, "tsd_clearance_dev: the radius is outside 1 .. TSD_CLEARANCE_MAX_RADIUS", hipSuccess);
@@ -298,7 +298,7 @@ int tsd_clearance_dev(tsd_ctx* ctx, const void* map_dev, int width, int height, 
     return set_error(ctx, TSD_E_ARG, "tsd_clearance_dev: the window is empty or not inside the map", hipSuccess);
   if (ctx->clearance.inflight) return set_error(ctx, TSD_E_ARG, "tsd_clearance_dev: a cost map is in flight (tsd_costmap_wait first)", hipSuccess);
   if (int rc = enter(ctx)) return rc;
-  const ClrMap m{static_cast<const int8_t*>(map_dev), width, height, (size_t)stride};
+  const MapView m{static_cast<const int8_t*>(map_dev), width, height, (size_t)stride};
   if (int rc = launch_clearance(ctx, ctx->stream, m, w, radius_cells, cost_dev ? table : nullptr, static_cast<uint16_t*>(dist2_dev),
                                 static_cast<int8_t*>(cost_dev), true))
     return rc;
@@ -315,9 +315,8 @@ int tsd_costmap_begin(tsd_ctx* ctx, const tsd_costmap_params* prm, int8_t* cost_
   tsd_ctx::Clearance& c = ctx->clearance;
   const int N = ctx->grid.N, R = prm->radius_cells;
   if (R < 1 || R > TSD_CLEARANCE_MAX_RADIUS) return set_error(ctx, TSD_E_ARG, "tsd_costmap_begin: the radius is outside 1 .. TSD_CLEARANCE_MAX_RADIUS", hipSuccess);
-  if (c.inflight) return set_error(ctx, TSD_E_ARG, "tsd_costmap_begin: a cost map is in flight (tsd_costmap_wait first)", hipSuccess);
-  if (ctx->frame_inflight) return set_error(ctx, TSD_E_ARG, "tsd_costmap_begin: a frame is in flight (tsd_map_frame_wait first)", hipSuccess);
-  if (!ctx->frame_map_valid || !frame_staged_map(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_costmap_begin: no completed frame to read", hipSuccess);
+  MapSource src{};                               // (every grid's side is below CLR_MAX_SIDE)
+  if (int rc = map_source_frame(ctx, "tsd_costmap_begin", false, &src, CLR_MAX_SIDE)) return rc;
   const tsd_map_window whole{0, 0, N, N};
   const tsd_map_window mw = map_win ? *map_win : whole;
   if (!window_inside(mw, N, N)) return set_error(ctx, TSD_E_ARG, "tsd_costmap_begin: the window is not inside the map", hipSuccess);
@@ -326,7 +325,7 @@ int tsd_costmap_begin(tsd_ctx* ctx, const tsd_costmap_params* prm, int8_t* cost_
     c.inflight = true; c.empty = true;
     return TSD_OK;
   }
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (int rc = map_source_enter(ctx, src)) return rc;
   const size_t cells = (size_t)N * N;
   const bool dist2 = prm->want_dist2 != 0;
   if (!c.ev_done) TSD_HIP_CHECK(ctx, hipEventCreateWithFlags(&c.ev_done, hipEventDisableTiming));
@@ -349,10 +348,7 @@ int tsd_costmap_begin(tsd_ctx* ctx, const tsd_costmap_params* prm, int8_t* cost_
   tsd_map_window ow;
   ow.x = std::max(0, mw.x - R); ow.y = std::max(0, mw.y - R);
   ow.width = std::min(N, mw.x + mw.width + R) - ow.x; ow.height = std::min(N, mw.y + mw.height + R) - ow.y;
-  // On the copy stream, behind the frame's kernels: the grid's stream never waits for the cost map.
-  TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream_io, ctx->ev_frame, 0));
-  const ClrMap m{frame_staged_map(ctx), N, N, (size_t)N};
-  if (int rc = launch_clearance(ctx, ctx->stream_io, m, ow, R, table.data(), dist2 ? c.d_dist2 : nullptr, c.d_cost, false)) return rc;
+  if (int rc = launch_clearance(ctx, src.stream, src.m, ow, R, table.data(), dist2 ? c.d_dist2 : nullptr, c.d_cost, src.timed)) return rc;
   const size_t o = (size_t)ow.y * N + ow.x;
   if (ow.width == N && ow.height == N) {
     TSD_HIP_CHECK(ctx, hipMemcpyAsync(cost_host, c.d_cost, cells, hipMemcpyDeviceToHost, ctx->stream_io));

@@ -20,7 +20,7 @@
 // No loop in these kernels waits for another wave: the only retry loop is the union's, and it strictly lowers a label or exits (see
 // fr_union).  The order between the passes is the stream's.  The host waits twice: for the number of roots (the records are sized by
 // it) and for the result.
-#include "capi_internal.hpp"
+#include "map_product.hpp"
 
 #include <climits>
 
@@ -34,8 +34,7 @@ constexpr int FR_SLOTS = 64;                         // the stats pass's table i
 constexpr int FR_RES_N_ALL = 0, FR_RES_N = 1, FR_RES_USED = 2, FR_RES_UNIONS = 3, FR_RES_UNIONS_T = 4, FR_RES_SEED_ROOTS = 8;
 constexpr int FR_RES_WORDS = FR_RES_SEED_ROOTS + TSD_FRONTIER_MAX_SEEDS;
 
-struct FrMap { const int8_t* map; int W, H; size_t stride; int free_max; };
-struct FrSeeds { int n; int xy[2 * TSD_FRONTIER_MAX_SEEDS]; };
+struct FrMap : MapView { int free_max; };             // (the same bytes as the map's four fields followed by free_max)
 
 #define FR_WG __HIP_MEMORY_SCOPE_WORKGROUP
 #define FR_AGENT __HIP_MEMORY_SCOPE_AGENT
@@ -264,7 +263,7 @@ k_fr_scan_top(uint32_t* __restrict__ bsum, uint32_t nb, uint32_t* __restrict__ t
 
 // ---- seeds: the root of each seed's region (FR_NONE for a seed outside the map or on a cell that is not traversable)
 __global__ void __launch_bounds__(64)
-k_fr_seeds(const uint32_t* __restrict__ Lt, int W, int H, FrSeeds sd, uint32_t* __restrict__ res)
+k_fr_seeds(const uint32_t* __restrict__ Lt, int W, int H, MapSeeds sd, uint32_t* __restrict__ res)
 {
   const int k = (int)threadIdx.x;
   uint32_t r = FR_NONE;
@@ -359,30 +358,6 @@ k_fr_compact(tsd_frontier* rec, uint32_t n_all, uint32_t min_size, uint32_t* __r
 }
 
 // ---- host
-static int fr_nomem(tsd_ctx* ctx, const char* what, size_t bytes)
-{
-  (void)hipGetLastError();
-  ctx->frontier.n = -1;
-  char buf[160];
-  snprintf(buf, sizeof(buf), "tsd_frontiers: the device cannot hold %s (%zu bytes)", what, bytes);
-  return set_error(ctx, TSD_E_NOMEM, buf, hipSuccess);
-}
-
-// p (capacity *cap elements of `elem` bytes) holds `need` elements, or TSD_E_NOMEM.  Nothing of the context reads the old buffer: every
-// frontier call has waited for its own work.
-template <typename T>
-static int fr_grow(tsd_ctx* ctx, T** p, size_t* cap, size_t need, const char* what)
-{
-  if (*cap >= need) return TSD_OK;
-  if (*p) hipFree(*p);
-  *p = nullptr; *cap = 0;
-  const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T));
-  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) { *p = nullptr; return fr_nomem(ctx, what, need * sizeof(T)); }
-  if (e != hipSuccess) { *p = nullptr; return set_error(ctx, TSD_E_HIP, "hipMalloc (tsd_frontiers)", e); }
-  *cap = need;
-  return TSD_OK;
-}
-
 template <int KIND>
 static void fr_label(tsd_ctx* ctx, hipStream_t stream, const FrMap& m, uint32_t* L, uint8_t* any, uint32_t* unions, dim3 tiles, bool timed)
 {
@@ -394,35 +369,28 @@ static void fr_label(tsd_ctx* ctx, hipStream_t stream, const FrMap& m, uint32_t*
     hipLaunchKernelGGL(k_fr_flatten, tiles, dim3(256), 0, stream, L, any, m.W, m.H); }
 }
 
-// The whole pipeline on `stream`, which it waits for.  The caller has checked the arguments.
-static int run_frontiers(tsd_ctx* ctx, hipStream_t stream, const FrMap& m, const tsd_frontier_params* prm, int* n_out, int* used_out, bool timed)
+// The whole pipeline on the source's stream, entered here, which it waits for.  The caller has checked the arguments.
+static int run_frontiers(tsd_ctx* ctx, const MapSource& src, const tsd_frontier_params* prm, int* n_out, int* used_out)
 {
+  constexpr const char* who = "tsd_frontiers";
+  if (int rc = map_source_enter(ctx, src)) return rc;
   tsd_ctx::Frontier& f = ctx->frontier;
-  f.n = -1;                                            // (no result until this call has one)
+  f.n = -1;                                            // (no result until this call has one: none where an allocation below fails)
+  const auto& [map, stream, timed] = src;
+  const FrMap m{map, prm->free_max};
   const int W = m.W, H = m.H, tw = (W + 31) / 32, th = (H + 31) / 32;
   const size_t cells = (size_t)W * H, tiles = (size_t)tw * th;
   const size_t n_seg = (size_t)tw * H, n_blk = (n_seg + FR_SCAN_BLOCK - 1) / FR_SCAN_BLOCK;
   const bool seeds = prm->n_seeds > 0;
-  if (f.cells < cells) {                               // (labels and ranks share one capacity)
-    size_t cap = f.cells;
-    if (int rc = fr_grow(ctx, &f.d_lab, &cap, cells, "the label image")) { f.cells = 0; return rc; }
-    cap = f.cells;
-    if (int rc = fr_grow(ctx, &f.d_rank, &cap, cells, "the roots' ranks")) { f.cells = 0; return rc; }
-    f.cells = cells;
-  }
-  if (seeds) if (int rc = fr_grow(ctx, &f.d_lab_t, &f.cells_t, cells, "the regions' label image")) return rc;
-  {
-    size_t cap = f.tiles * 2;
-    if (int rc = fr_grow(ctx, &f.d_any, &cap, tiles * 2, "the tile bytes")) { f.tiles = 0; return rc; }
-    f.tiles = cap / 2;
-  }
-  if (int rc = fr_grow(ctx, &f.d_seg, &f.segs, n_seg + n_blk, "the segment counts")) return rc;
+  if (int rc = scratch_grow_all(ctx, who, &f.cells, cells, scratch_part(&f.d_lab, "the label image"), scratch_part(&f.d_rank, "the roots' ranks")))
+    return rc;
+  if (seeds) if (int rc = scratch_grow(ctx, who, &f.d_lab_t, &f.cells_t, cells, "the regions' label image")) return rc;
+  if (int rc = scratch_grow_all(ctx, who, &f.tiles, tiles, scratch_part(&f.d_any, "the tile bytes", false, 2))) return rc;
+  if (int rc = scratch_grow(ctx, who, &f.d_seg, &f.segs, n_seg + n_blk, "the segment counts")) return rc;
   if (!f.d_res) TSD_HIP_CHECK(ctx, hipMalloc(&f.d_res, FR_RES_WORDS * sizeof(uint32_t)));
   if (!f.h_res) TSD_HIP_CHECK(ctx, hipHostMalloc(&f.h_res, FR_RES_WORDS * sizeof(uint32_t), hipHostMallocDefault));
 
-  FrSeeds sd{};
-  sd.n = prm->n_seeds;
-  for (int k = 0; k < 2 * prm->n_seeds; k++) sd.xy[k] = prm->seeds_xy[k];
+  const MapSeeds sd = map_seeds(prm->n_seeds, prm->seeds_xy);
   uint8_t* any_f = f.d_any;
   uint8_t* any_t = f.d_any + f.tiles;
   uint32_t* bsum = f.d_seg + n_seg;
@@ -446,7 +414,7 @@ static int run_frontiers(tsd_ctx* ctx, hipStream_t stream, const FrMap& m, const
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(f.h_res, f.d_res, FR_RES_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(stream));
   const uint32_t n_all = f.h_res[FR_RES_N_ALL];
-  if (int rc = fr_grow(ctx, &f.d_rec, &f.recs, std::max<size_t>(n_all, 1), "the records")) return rc;
+  if (int rc = scratch_grow(ctx, who, &f.d_rec, &f.recs, std::max<size_t>(n_all, 1), "the records")) return rc;
   uint32_t n = n_all;
   if (n_all > 0) {
     {
@@ -473,8 +441,9 @@ static int run_frontiers(tsd_ctx* ctx, hipStream_t stream, const FrMap& m, const
   return TSD_OK;
 }
 
-static const char* fr_params_wrong(const tsd_frontier_params* p)
+static const char* fr_params_wrong(const tsd_frontier_params* p, const int* n)
 {
+  if (!n) return "n is NULL";
   if (!p) return "params is NULL";
   if (p->free_max < 0 || p->free_max > 99) return "free_max is outside 0 .. 99";
   if (p->min_size < 1u) return "min_size is below 1";
@@ -501,29 +470,19 @@ int tsd_frontiers_dev(tsd_ctx* ctx, const void* map_dev, int width, int height, 
                       int* seeds_used)
 {
   if (!ctx) return TSD_E_ARG;
-  if (!map_dev || !n || width < 1 || height < 1 || width > TSD_FRONTIER_MAX_SIDE || height > TSD_FRONTIER_MAX_SIDE || stride < width)
-    return set_error(ctx, TSD_E_ARG, "tsd_frontiers_dev: a null map or n, a side outside 1 .. TSD_FRONTIER_MAX_SIDE, or stride < width", hipSuccess);
-  if (const char* why = fr_params_wrong(params)) return set_error(ctx, TSD_E_ARG, (std::string("tsd_frontiers_dev: ") + why).c_str(), hipSuccess);
-  if (int rc = enter(ctx)) return rc;
-  const FrMap m{static_cast<const int8_t*>(map_dev), width, height, (size_t)stride, params->free_max};
-  return run_frontiers(ctx, ctx->stream, m, params, n, seeds_used, true);
+  MapSource src{};
+  if (int rc = map_source_caller(ctx, "tsd_frontiers_dev", map_dev, width, height, stride, &src)) return rc;
+  if (const char* why = fr_params_wrong(params, n)) return map_refused(ctx, "tsd_frontiers_dev", why);
+  return run_frontiers(ctx, src, params, n, seeds_used);
 }
 
 int tsd_frontiers_frame(tsd_ctx* ctx, const tsd_frontier_params* params, int* n, int* seeds_used)
 {
   if (!ctx) return TSD_E_ARG;
-  if (!n) return set_error(ctx, TSD_E_ARG, "tsd_frontiers_frame: n is NULL", hipSuccess);
-  if (const char* why = fr_params_wrong(params)) return set_error(ctx, TSD_E_ARG, (std::string("tsd_frontiers_frame: ") + why).c_str(), hipSuccess);
-  if (ctx->clearance.inflight) return set_error(ctx, TSD_E_ARG, "tsd_frontiers_frame: a cost map is in flight (tsd_costmap_wait first)", hipSuccess);
-  if (ctx->frame_inflight) return set_error(ctx, TSD_E_ARG, "tsd_frontiers_frame: a frame is in flight (tsd_map_frame_wait first)", hipSuccess);
-  if (!ctx->frame_map_valid || !frame_staged_map(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_frontiers_frame: no completed frame to read", hipSuccess);
-  const int N = ctx->grid.N;
-  if (N > TSD_FRONTIER_MAX_SIDE) return set_error(ctx, TSD_E_ARG, "tsd_frontiers_frame: the grid's side is above TSD_FRONTIER_MAX_SIDE", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // On the copy stream, behind the frame's kernels: the grid's stream never waits for the frontiers.
-  TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream_io, ctx->ev_frame, 0));
-  const FrMap m{frame_staged_map(ctx), N, N, (size_t)N, params->free_max};
-  return run_frontiers(ctx, ctx->stream_io, m, params, n, seeds_used, false);
+  if (const char* why = fr_params_wrong(params, n)) return map_refused(ctx, "tsd_frontiers_frame", why);
+  MapSource src{};
+  if (int rc = map_source_frame(ctx, "tsd_frontiers_frame", false, &src)) return rc;
+  return run_frontiers(ctx, src, params, n, seeds_used);
 }
 
 int tsd_frontiers_fetch(tsd_ctx* ctx, int first, int count, tsd_frontier* out)
@@ -531,8 +490,7 @@ int tsd_frontiers_fetch(tsd_ctx* ctx, int first, int count, tsd_frontier* out)
   if (!ctx) return TSD_E_ARG;
   const tsd_ctx::Frontier& f = ctx->frontier;
   if (f.n < 0) return set_error(ctx, TSD_E_ARG, "tsd_frontiers_fetch: no result to fetch", hipSuccess);
-  if (first < 0 || count < 0 || first > f.n || count > f.n - first || (count > 0 && !out))
-    return set_error(ctx, TSD_E_ARG, "tsd_frontiers_fetch: the range is outside [0, n) or out is NULL", hipSuccess);
+  if (const char* why = fetch_range_wrong(first, count, f.n, out)) return map_refused(ctx, "tsd_frontiers_fetch", why);
   if (count == 0) return TSD_OK;
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   TSD_HIP_CHECK(ctx, hipMemcpy(out, f.d_rec + first, (size_t)count * sizeof(tsd_frontier), hipMemcpyDeviceToHost));

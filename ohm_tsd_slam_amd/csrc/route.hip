@@ -19,7 +19,7 @@
 // bounded below, every round with an active tile lowers a key or ends, so the rounds end; the host caps them all the same.  No
 // workgroup waits for another: no flag spin, no ticket, no persistent kernel.  The only atomics are the visit counter (one add per
 // active workgroup, a statistic), the cell count and the goals' 64-bit minimum, which commutes.
-#include "capi_internal.hpp"
+#include "map_product.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -30,12 +30,11 @@ constexpr uint32_t RT_NONE = TSD_ROUTE_NONE;
 constexpr int RT_P = 34;                             // the pitch of a tile with its apron in LDS
 constexpr int RT_SWEEPS = 2048;                      // sweeps per launch before a tile hands itself on to the next round
 constexpr int RT_BATCH = 32;                         // rounds between two reads of the "any" word (8 and 16 for the first two batches)
+constexpr const char* RT_WHO = "tsd_route";          // the scratch's owner in an out-of-memory message
 // d_res / h_res, in uint32 (the visits are one uint64)
 constexpr int RT_RES_USED = 0, RT_RES_REACHED = 1, RT_RES_ANY = 2, RT_RES_VISITS = 4, RT_RES_WORDS = 8;
 
-struct RtMap { const int8_t* map; int W, H; size_t stride; };
 struct RtWeights { uint8_t w[128]; };                // by map value; 0 above free_max
-struct RtSeeds { int n; int xy[2 * TSD_FRONTIER_MAX_SEEDS]; };
 
 #define RT_WG __HIP_MEMORY_SCOPE_WORKGROUP
 #define RT_AGENT __HIP_MEMORY_SCOPE_AGENT
@@ -46,7 +45,7 @@ __device__ __forceinline__ int rt_dy(int k) { return k < 4 ? (k == 2 ? -1 : k ==
 
 // ---- init
 __global__ void __launch_bounds__(256)
-k_route_init(RtMap m, RtWeights wt, RtSeeds sd, uint32_t* __restrict__ key, uint8_t* __restrict__ wimg, uint8_t* __restrict__ act0,
+k_route_init(MapView m, RtWeights wt, MapSeeds sd, uint32_t* __restrict__ key, uint8_t* __restrict__ wimg, uint8_t* __restrict__ act0,
              uint8_t* __restrict__ act1, uint32_t* __restrict__ res)
 {
   __shared__ uint8_t s_wt[128];
@@ -279,32 +278,6 @@ k_route_trace(const uint32_t* __restrict__ key, const uint8_t* __restrict__ wimg
 }
 
 // ---- host
-static int rt_nomem(tsd_ctx* ctx, const char* what, size_t bytes)
-{
-  (void)hipGetLastError();
-  ctx->route.valid = false;
-  ctx->route.n_goals = -1;
-  char buf[160];
-  snprintf(buf, sizeof(buf), "tsd_route: the device cannot hold %s (%zu bytes)", what, bytes);
-  return set_error(ctx, TSD_E_NOMEM, buf, hipSuccess);
-}
-
-// p (capacity *cap elements) holds `need` elements, or TSD_E_NOMEM.  Nothing of the context reads the old buffer: every route call has
-// waited for its own work.  pinned: page-locked host memory.
-template <typename T>
-static int rt_grow(tsd_ctx* ctx, T** p, size_t* cap, size_t need, const char* what, bool pinned = false)
-{
-  if (*cap >= need) return TSD_OK;
-  if (*p) { if (pinned) hipHostFree(*p); else hipFree(*p); }
-  *p = nullptr; *cap = 0;
-  const hipError_t e = pinned ? hipHostMalloc(reinterpret_cast<void**>(p), need * sizeof(T), hipHostMallocDefault)
-                              : hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T));
-  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) { *p = nullptr; return rt_nomem(ctx, what, need * sizeof(T)); }
-  if (e != hipSuccess) { *p = nullptr; return set_error(ctx, TSD_E_HIP, "allocation (tsd_route)", e); }
-  *cap = need;
-  return TSD_OK;
-}
-
 static const char* rt_params_wrong(const tsd_route_params* p, const tsd_route_info* info)
 {
   if (!p) return "params is NULL";
@@ -320,33 +293,24 @@ static const char* rt_params_wrong(const tsd_route_params* p, const tsd_route_in
   return nullptr;
 }
 
-// The field on `stream`, which it waits for.  The caller has checked the arguments.
-static int run_route(tsd_ctx* ctx, hipStream_t stream, const RtMap& m, const tsd_route_params* prm, tsd_route_info* info, bool timed)
+// The field on the source's stream, entered here, which it waits for.  The caller has checked the arguments.
+static int run_route(tsd_ctx* ctx, const MapSource& src, const tsd_route_params* prm, tsd_route_info* info)
 {
+  if (int rc = map_source_enter(ctx, src)) return rc;
   tsd_ctx::Route& r = ctx->route;
-  r.valid = false; r.n_goals = -1;                     // (no result until this call has one)
+  r.valid = false; r.n_goals = -1;                     // (no result until this call has one: none where an allocation below fails)
+  const auto& [m, stream, timed] = src;
   const int W = m.W, H = m.H, tw = (W + 31) / 32, th = (H + 31) / 32;
   const size_t cells = (size_t)W * H, tiles = (size_t)tw * th;
-  if (r.cells < cells) {                               // (keys and weights share one capacity)
-    size_t cap = r.cells;
-    if (int rc = rt_grow(ctx, &r.d_key, &cap, cells, "the key image")) { r.cells = 0; return rc; }
-    cap = r.cells;
-    if (int rc = rt_grow(ctx, &r.d_w, &cap, cells, "the cells' weights")) { r.cells = 0; return rc; }
-    r.cells = cells;
-  }
-  {
-    size_t cap = r.tiles * 2;
-    if (int rc = rt_grow(ctx, &r.d_act, &cap, tiles * 2, "the tile bytes")) { r.tiles = 0; return rc; }
-    r.tiles = cap / 2;
-  }
+  if (int rc = scratch_grow_all(ctx, RT_WHO, &r.cells, cells, scratch_part(&r.d_key, "the key image"), scratch_part(&r.d_w, "the cells' weights")))
+    return rc;
+  if (int rc = scratch_grow_all(ctx, RT_WHO, &r.tiles, tiles, scratch_part(&r.d_act, "the tile bytes", false, 2))) return rc;
   if (!r.d_res) TSD_HIP_CHECK(ctx, hipMalloc(&r.d_res, RT_RES_WORDS * sizeof(uint32_t)));
   if (!r.h_res) TSD_HIP_CHECK(ctx, hipHostMalloc(&r.h_res, RT_RES_WORDS * sizeof(uint32_t), hipHostMallocDefault));
 
   RtWeights wt{};
   for (int v = 0; v <= prm->free_max; v++) wt.w[v] = prm->weights ? prm->weights[v] : (uint8_t)1;
-  RtSeeds sd{};
-  sd.n = prm->n_seeds;
-  for (int k = 0; k < 2 * prm->n_seeds; k++) sd.xy[k] = prm->seeds_xy[k];
+  const MapSeeds sd = map_seeds(prm->n_seeds, prm->seeds_xy);
   const uint32_t limit = prm->limit ? prm->limit : TSD_ROUTE_MAX_DIST;
   const uint32_t lim_key = (limit << 4) | 15u;
   const int max_rounds = prm->max_rounds ? prm->max_rounds : 16 * (tw + th) + 64;
@@ -418,32 +382,20 @@ int tsd_route_weights(int free_max, int max_weight, uint8_t* table)
 int tsd_route_dev(tsd_ctx* ctx, const void* map_dev, int width, int height, int stride, const tsd_route_params* params, tsd_route_info* info)
 {
   if (!ctx) return TSD_E_ARG;
-  if (!map_dev || width < 1 || height < 1 || width > TSD_FRONTIER_MAX_SIDE || height > TSD_FRONTIER_MAX_SIDE || stride < width)
-    return set_error(ctx, TSD_E_ARG, "tsd_route_dev: a null map, a side outside 1 .. TSD_FRONTIER_MAX_SIDE, or stride < width", hipSuccess);
-  if (const char* why = rt_params_wrong(params, info)) return set_error(ctx, TSD_E_ARG, (std::string("tsd_route_dev: ") + why).c_str(), hipSuccess);
-  if (int rc = enter(ctx)) return rc;
-  const RtMap m{static_cast<const int8_t*>(map_dev), width, height, (size_t)stride};
-  return run_route(ctx, ctx->stream, m, params, info, true);
+  MapSource src{};
+  if (int rc = map_source_caller(ctx, "tsd_route_dev", map_dev, width, height, stride, &src)) return rc;
+  if (const char* why = rt_params_wrong(params, info)) return map_refused(ctx, "tsd_route_dev", why);
+  return run_route(ctx, src, params, info);
 }
 
 int tsd_route_frame(tsd_ctx* ctx, int source, const tsd_route_params* params, tsd_route_info* info)
 {
   if (!ctx) return TSD_E_ARG;
   if (source != TSD_ROUTE_MAP && source != TSD_ROUTE_COSTMAP) return set_error(ctx, TSD_E_ARG, "tsd_route_frame: no such source", hipSuccess);
-  if (const char* why = rt_params_wrong(params, info)) return set_error(ctx, TSD_E_ARG, (std::string("tsd_route_frame: ") + why).c_str(), hipSuccess);
-  if (ctx->clearance.inflight) return set_error(ctx, TSD_E_ARG, "tsd_route_frame: a cost map is in flight (tsd_costmap_wait first)", hipSuccess);
-  if (ctx->frame_inflight) return set_error(ctx, TSD_E_ARG, "tsd_route_frame: a frame is in flight (tsd_map_frame_wait first)", hipSuccess);
-  if (!ctx->frame_map_valid || !frame_staged_map(ctx)) return set_error(ctx, TSD_E_ARG, "tsd_route_frame: no completed frame to read", hipSuccess);
-  const int N = ctx->grid.N;
-  if (N > TSD_FRONTIER_MAX_SIDE) return set_error(ctx, TSD_E_ARG, "tsd_route_frame: the grid's side is above TSD_FRONTIER_MAX_SIDE", hipSuccess);
-  if (source == TSD_ROUTE_COSTMAP && (!ctx->clearance.d_cost || ctx->clearance.cost_cells != (size_t)N * N))
-    return set_error(ctx, TSD_E_ARG, "tsd_route_frame: no completed cost map of the grid's size to read", hipSuccess);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // On the copy stream, behind the frame's kernels (the cost map's ran there and have been waited for): the grid's stream never
-  // waits for the routes.
-  TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream_io, ctx->ev_frame, 0));
-  const RtMap m{source == TSD_ROUTE_COSTMAP ? ctx->clearance.d_cost : frame_staged_map(ctx), N, N, (size_t)N};
-  return run_route(ctx, ctx->stream_io, m, params, info, false);
+  if (const char* why = rt_params_wrong(params, info)) return map_refused(ctx, "tsd_route_frame", why);
+  MapSource src{};
+  if (int rc = map_source_frame(ctx, "tsd_route_frame", source == TSD_ROUTE_COSTMAP, &src)) return rc;
+  return run_route(ctx, src, params, info);
 }
 
 int tsd_route_goals(tsd_ctx* ctx, int* n)
@@ -457,7 +409,9 @@ int tsd_route_goals(tsd_ctx* ctx, int* n)
   if (f.W != r.W || f.H != r.H) return set_error(ctx, TSD_E_ARG, "tsd_route_goals: the frontier result and the route result differ in size", hipSuccess);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   r.n_goals = -1;
-  if (int rc = rt_grow(ctx, &r.d_goal, &r.goals, std::max<size_t>((size_t)f.n, 1), "the goals")) return rc;
+  const int rc = scratch_grow(ctx, RT_WHO, &r.d_goal, &r.goals, std::max<size_t>((size_t)f.n, 1), "the goals");
+  if (rc == TSD_E_NOMEM) r.valid = false;              // out of memory takes the route result along with the goals
+  if (rc) return rc;
   if (f.n > 0) {
     unsigned long long* slots = reinterpret_cast<unsigned long long*>(r.d_goal);
     const unsigned nb = (unsigned)((f.n + 255) / 256);
@@ -478,8 +432,7 @@ int tsd_route_goals_fetch(tsd_ctx* ctx, int first, int count, tsd_route_goal* ou
   if (!ctx) return TSD_E_ARG;
   const tsd_ctx::Route& r = ctx->route;
   if (!r.valid || r.n_goals < 0) return set_error(ctx, TSD_E_ARG, "tsd_route_goals_fetch: no goals to fetch", hipSuccess);
-  if (first < 0 || count < 0 || first > r.n_goals || count > r.n_goals - first || (count > 0 && !out))
-    return set_error(ctx, TSD_E_ARG, "tsd_route_goals_fetch: the range is outside [0, n) or out is NULL", hipSuccess);
+  if (const char* why = fetch_range_wrong(first, count, r.n_goals, out)) return map_refused(ctx, "tsd_route_goals_fetch", why);
   if (count == 0) return TSD_OK;
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   TSD_HIP_CHECK(ctx, hipMemcpy(out, r.d_goal + first, (size_t)count * sizeof(tsd_route_goal), hipMemcpyDeviceToHost));
@@ -498,8 +451,10 @@ int tsd_route_trace(tsd_ctx* ctx, const uint32_t* goal_cells, int n_goals, int m
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   // d_path: the goal cells, the lengths, the paths; h_path: the lengths, the paths
   const size_t ng = (size_t)n_goals, back = ng + ng * (size_t)max_len;
-  if (int rc = rt_grow(ctx, &r.d_path, &r.path_words, ng + back, "the paths")) return rc;
-  if (int rc = rt_grow(ctx, &r.h_path, &r.h_path_words, back, "the paths' pinned copy", true)) return rc;
+  int rc = scratch_grow(ctx, RT_WHO, &r.d_path, &r.path_words, ng + back, "the paths");
+  if (!rc) rc = scratch_grow(ctx, RT_WHO, &r.h_path, &r.h_path_words, back, "the paths' pinned copy", true);
+  if (rc == TSD_E_NOMEM) { r.valid = false; r.n_goals = -1; }        // out of memory takes the route result and its goals along
+  if (rc) return rc;
   uint32_t* d_goals = r.d_path;
   int32_t* d_len = reinterpret_cast<int32_t*>(r.d_path + ng);
   uint32_t* d_paths = r.d_path + 2 * ng;

@@ -17,7 +17,7 @@
 //                = true: a byte store of 1 on every unknown cell seen.  Stores of one value from many workgroups: no atomics, no order.
 //
 // No workgroup reads what another one writes in the same launch: gains read the claims and write records, claims write the claims.
-#include "capi_internal.hpp"
+#include "map_product.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -26,7 +26,6 @@ namespace tsd {
 
 constexpr int VIEW_THREADS = 1024;                   // 16 waves: a candidate's rays are independent, and a call often brings few candidates
 
-struct ViewMap { const int8_t* map; int W, H; size_t stride; };
 struct ViewArgs {
   int R, free_max, depth;
   uint32_t recip;                                    // floor(2^32 / 2R) + 1: umulhi(n, recip) == n / 2R for every n <= 2 R^2 + R (host: view_recip)
@@ -48,7 +47,7 @@ __device__ __forceinline__ void view_target(int r, int R, int& tx, int& ty)
 
 template <bool CLAIM>
 __global__ void __launch_bounds__(VIEW_THREADS)
-k_view(ViewMap m, ViewArgs a, const uint32_t* __restrict__ cells, const uint8_t* claims_in, uint8_t* claims_out,
+k_view(MapView m, ViewArgs a, const uint32_t* __restrict__ cells, const uint8_t* claims_in, uint8_t* claims_out,
        tsd_view_gain* __restrict__ out)
 {
   extern __shared__ uint32_t s_mask[];               // [(2R + 1) * wpr]
@@ -156,30 +155,6 @@ k_view(ViewMap m, ViewArgs a, const uint32_t* __restrict__ cells, const uint8_t*
 }
 
 // ---- host
-static int vw_nomem(tsd_ctx* ctx, const char* what, size_t bytes)
-{
-  (void)hipGetLastError();
-  char buf[160];
-  snprintf(buf, sizeof(buf), "tsd_view: the device cannot hold %s (%zu bytes)", what, bytes);
-  return set_error(ctx, TSD_E_NOMEM, buf, hipSuccess);
-}
-
-// p (capacity *cap elements) holds `need` elements, or TSD_E_NOMEM.  Nothing of the context reads the old buffer: every view call has
-// waited for its own work.  pinned: page-locked host memory.
-template <typename T>
-static int vw_grow(tsd_ctx* ctx, T** p, size_t* cap, size_t need, const char* what, bool pinned = false)
-{
-  if (*cap >= need) return TSD_OK;
-  if (*p) { if (pinned) hipHostFree(*p); else hipFree(*p); }
-  *p = nullptr; *cap = 0;
-  const hipError_t e = pinned ? hipHostMalloc(reinterpret_cast<void**>(p), need * sizeof(T), hipHostMallocDefault)
-                              : hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T));
-  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) { *p = nullptr; return vw_nomem(ctx, what, need * sizeof(T)); }
-  if (e != hipSuccess) { *p = nullptr; return set_error(ctx, TSD_E_HIP, "allocation (tsd_view)", e); }
-  *cap = need;
-  return TSD_OK;
-}
-
 static uint32_t view_recip(int R) { return (uint32_t)((1ull << 32) / (unsigned)(2 * R)) + 1u; }
 
 static ViewArgs view_args(const tsd_view_params* p)
@@ -194,9 +169,6 @@ static ViewArgs view_args(const tsd_view_params* p)
   return a;
 }
 
-// the map of a call and the stream it runs on, from the caller's arguments: the staged map of the last frame where map_dev is NULL
-struct ViewSource { ViewMap m; hipStream_t stream; bool timed; };
-
 static const char* vw_params_wrong(const tsd_view_params* p)
 {
   if (!p) return "params is NULL";
@@ -206,36 +178,13 @@ static const char* vw_params_wrong(const tsd_view_params* p)
   return nullptr;
 }
 
-// Checks the map arguments and, for the frame form, tsd_route_frame's conditions; enqueues nothing.
-static int vw_source(tsd_ctx* ctx, const char* who, const void* map_dev, int width, int height, int stride, ViewSource* src)
+// The views' entry points take both forms in one signature: map_dev NULL is the staged map of the last frame.
+static int vw_map_source(tsd_ctx* ctx, const char* who, const void* map_dev, int width, int height, int stride, MapSource* src)
 {
-  auto refuse = [&](const char* why) { return set_error(ctx, TSD_E_ARG, (std::string(who) + ": " + why).c_str(), hipSuccess); };
-  if (map_dev) {
-    if (width < 1 || height < 1 || width > TSD_FRONTIER_MAX_SIDE || height > TSD_FRONTIER_MAX_SIDE || stride < width)
-      return refuse("a side outside 1 .. TSD_FRONTIER_MAX_SIDE, or stride < width");
-    *src = ViewSource{ViewMap{static_cast<const int8_t*>(map_dev), width, height, (size_t)stride}, ctx->stream, true};
-    return TSD_OK;
-  }
-  if (ctx->clearance.inflight) return refuse("a cost map is in flight (tsd_costmap_wait first)");
-  if (ctx->frame_inflight) return refuse("a frame is in flight (tsd_map_frame_wait first)");
-  if (!ctx->frame_map_valid || !frame_staged_map(ctx)) return refuse("no completed frame to read");
-  const int N = ctx->grid.N;
-  if (N > TSD_FRONTIER_MAX_SIDE) return refuse("the grid's side is above TSD_FRONTIER_MAX_SIDE");
-  *src = ViewSource{ViewMap{frame_staged_map(ctx), N, N, (size_t)N}, ctx->stream_io, false};
-  return TSD_OK;
+  return map_dev ? map_source_caller(ctx, who, map_dev, width, height, stride, src) : map_source_frame(ctx, who, false, src);
 }
 
-// The top of a call once its arguments stand: the device, and the stream behind what it has to follow.
-static int vw_enter(tsd_ctx* ctx, const ViewSource& src)
-{
-  if (src.stream == ctx->stream) return enter(ctx);
-  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // On the copy stream, behind the frame's kernels: the grid's stream never waits for the views.
-  TSD_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream_io, ctx->ev_frame, 0));
-  return TSD_OK;
-}
-
-static bool vw_claims_fit(const tsd_ctx* ctx, const ViewMap& m) { return ctx->view.d_claims && ctx->view.cW == m.W && ctx->view.cH == m.H; }
+static bool vw_claims_fit(const tsd_ctx* ctx, const MapView& m) { return ctx->view.d_claims && ctx->view.cW == m.W && ctx->view.cH == m.H; }
 
 // The claims image at W x H, all 0, enqueued on `stream` (not waited for).
 static int vw_claims_reset(tsd_ctx* ctx, hipStream_t stream, int W, int H)
@@ -243,7 +192,7 @@ static int vw_claims_reset(tsd_ctx* ctx, hipStream_t stream, int W, int H)
   tsd_ctx::View& v = ctx->view;
   const size_t cells = (size_t)W * H;
   if (v.claims_cap < cells) { v.cW = v.cH = 0; }
-  if (int rc = vw_grow(ctx, &v.d_claims, &v.claims_cap, cells, "the claims image")) return rc;
+  if (int rc = scratch_grow(ctx, "tsd_view", &v.d_claims, &v.claims_cap, cells, "the claims image")) return rc;
   v.cW = W; v.cH = H;
   TSD_HIP_CHECK(ctx, hipMemsetAsync(v.d_claims, 0, cells, stream));
   return TSD_OK;
@@ -253,18 +202,9 @@ static int vw_claims_reset(tsd_ctx* ctx, hipStream_t stream, int W, int H)
 static int vw_stage(tsd_ctx* ctx, const uint32_t* cells, int n)
 {
   tsd_ctx::View& v = ctx->view;
-  if (v.cap < (size_t)n) {
-    const size_t need = std::max<size_t>((size_t)n, 64);
-    size_t cap = v.cap;
-    if (int rc = vw_grow(ctx, &v.d_cells, &cap, need, "the candidates")) { v.cap = 0; return rc; }
-    cap = v.cap;
-    if (int rc = vw_grow(ctx, &v.d_rec, &cap, need, "the records")) { v.cap = 0; return rc; }
-    cap = v.cap;
-    if (int rc = vw_grow(ctx, &v.h_cells, &cap, need, "the candidates' pinned copy", true)) { v.cap = 0; return rc; }
-    cap = v.cap;
-    if (int rc = vw_grow(ctx, &v.h_rec, &cap, need, "the records' pinned copy", true)) { v.cap = 0; return rc; }
-    v.cap = need;
-  }
+  if (int rc = scratch_grow_all(ctx, "tsd_view", &v.cap, std::max<size_t>((size_t)n, 64), scratch_part(&v.d_cells, "the candidates"),
+                                scratch_part(&v.d_rec, "the records"), scratch_part(&v.h_cells, "the candidates' pinned copy", true),
+                                scratch_part(&v.h_rec, "the records' pinned copy", true))) return rc;   // (invalidates nothing: no result is kept)
   std::memcpy(v.h_cells, cells, (size_t)n * sizeof(uint32_t));
   return TSD_OK;
 }
@@ -272,7 +212,7 @@ static int vw_stage(tsd_ctx* ctx, const uint32_t* cells, int n)
 // One launch over n candidates.  upload: they are the staged ones (h_cells), copied to d_cells first; otherwise `d_cells` points at
 // candidates a launch before this one left on the device.  claim: the store pass, not waited for (what follows on the stream sees it);
 // else the records arrive in h_rec and the call waits.
-static int vw_run(tsd_ctx* ctx, const ViewSource& src, const tsd_view_params* prm, const uint32_t* d_cells, int n, bool upload, bool claim)
+static int vw_run(tsd_ctx* ctx, const MapSource& src, const tsd_view_params* prm, const uint32_t* d_cells, int n, bool upload, bool claim)
 {
   tsd_ctx::View& v = ctx->view;
   const ViewArgs a = view_args(prm);
@@ -317,11 +257,11 @@ int tsd_view_gains(tsd_ctx* ctx, const void* map_dev, int width, int height, int
   if (const char* why = vw_params_wrong(params)) return set_error(ctx, TSD_E_ARG, (std::string("tsd_view_gains: ") + why).c_str(), hipSuccess);
   if (!cells_host || !out_host || n < 1 || n > TSD_VIEW_MAX_CELLS)
     return set_error(ctx, TSD_E_ARG, "tsd_view_gains: cells or out is NULL, or n is outside 1 .. TSD_VIEW_MAX_CELLS", hipSuccess);
-  ViewSource src{};
-  if (int rc = vw_source(ctx, "tsd_view_gains", map_dev, width, height, stride, &src)) return rc;
+  MapSource src{};
+  if (int rc = vw_map_source(ctx, "tsd_view_gains", map_dev, width, height, stride, &src)) return rc;
   if (params->use_claims && !vw_claims_fit(ctx, src.m))
     return set_error(ctx, TSD_E_ARG, "tsd_view_gains: use_claims without a claims image of the map's size (tsd_view_claims_reset)", hipSuccess);
-  if (int rc = vw_enter(ctx, src)) return rc;
+  if (int rc = map_source_enter(ctx, src)) return rc;
   if (int rc = vw_stage(ctx, cells_host, n)) return rc;
   if (int rc = vw_run(ctx, src, params, ctx->view.d_cells, n, true, false)) return rc;
   std::memcpy(out_host, ctx->view.h_rec, (size_t)n * sizeof(tsd_view_gain));
@@ -335,11 +275,11 @@ int tsd_view_claim(tsd_ctx* ctx, const void* map_dev, int width, int height, int
   if (const char* why = vw_params_wrong(params)) return set_error(ctx, TSD_E_ARG, (std::string("tsd_view_claim: ") + why).c_str(), hipSuccess);
   if (!cells_host || n < 1 || n > TSD_VIEW_MAX_CELLS)
     return set_error(ctx, TSD_E_ARG, "tsd_view_claim: cells is NULL, or n is outside 1 .. TSD_VIEW_MAX_CELLS", hipSuccess);
-  ViewSource src{};
-  if (int rc = vw_source(ctx, "tsd_view_claim", map_dev, width, height, stride, &src)) return rc;
+  MapSource src{};
+  if (int rc = vw_map_source(ctx, "tsd_view_claim", map_dev, width, height, stride, &src)) return rc;
   if (!vw_claims_fit(ctx, src.m))
     return set_error(ctx, TSD_E_ARG, "tsd_view_claim: no claims image of the map's size (tsd_view_claims_reset)", hipSuccess);
-  if (int rc = vw_enter(ctx, src)) return rc;
+  if (int rc = map_source_enter(ctx, src)) return rc;
   if (int rc = vw_stage(ctx, cells_host, n)) return rc;
   if (int rc = vw_run(ctx, src, params, ctx->view.d_cells, n, true, true)) return rc;
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(src.stream));
@@ -377,9 +317,9 @@ int tsd_view_assign(tsd_ctx* ctx, const void* map_dev, int width, int height, in
   if (n_goals < 0 || n_goals > TSD_VIEW_MAX_CELLS || (n_goals > 0 && !goals) || n_robots < 1 || n_robots > TSD_FRONTIER_MAX_SEEDS || !goal_of_robot || !rounds)
     return set_error(ctx, TSD_E_ARG, "tsd_view_assign: n_goals outside 0 .. TSD_VIEW_MAX_CELLS, goals NULL, n_robots outside 1 .. TSD_FRONTIER_MAX_SEEDS, or a NULL output",
                      hipSuccess);
-  ViewSource src{};
-  if (int rc = vw_source(ctx, "tsd_view_assign", map_dev, width, height, stride, &src)) return rc;
-  if (int rc = vw_enter(ctx, src)) return rc;
+  MapSource src{};
+  if (int rc = vw_map_source(ctx, "tsd_view_assign", map_dev, width, height, stride, &src)) return rc;
+  if (int rc = map_source_enter(ctx, src)) return rc;
   if (int rc = vw_claims_reset(ctx, src.stream, src.m.W, src.m.H)) return rc;        // (the round's first launch runs behind it)
   tsd_view_params prm = *params;
   prm.use_claims = 1;
