@@ -749,6 +749,58 @@ int tsd_route_counts(tsd_ctx* ctx, long long* tile_visits, int* host_waits);
  * 1 is the other extreme of the schedule: the keys are the same byte for byte (tests/test_gpu_route.py), only the rounds differ. */
 int tsd_debug_set_route_sweeps(tsd_ctx* ctx, int n);
 
+/* ---- waypoints: a traced path straightened into cells joined by straight drivable segments ----------------------- */
+/* For each goal cell a short list of cells of its path, in DRIVING order -- the seed's cell first, the goal last: the opposite of
+ * tsd_route_trace's order -- such that consecutive cells are joined by a straight segment a robot can drive.  It works on the route
+ * result the context holds: the key image and the weight image w the paths are traced on (0: not traversable), with the routes'
+ * constants: c = 5 for a straight step, 7 for a diagonal one, d = key >> 4.  In integers throughout (the kernel does no floating
+ * point), so a restatement agrees to the byte (tests/waypoint_ref.py).
+ *   path           tsd_route_trace's path of the goal cell, reversed: p_0 is the seed's cell (d = 0), p_{n-1} the goal, n the trace's
+ *                  full length `len`
+ *   line p -> q    dx = q.x - p.x, dy = q.y - p.y, N = max(|dx|, |dy|) >= 1; step j = 1 .. N lies at
+ *                  p + (sgn(dx) * ((2 j |dx| + N) / 2N), sgn(dy) * ((2 j |dy| + N) / 2N)) by integer division: the views' ray with
+ *                  R = N, and step N is q.  The major axis advances by exactly one per step, the minor axis by zero or one, so every
+ *                  step is a straight or a diagonal neighbour step and the line stays inside the bounding box of p and q
+ *   a segment p -> q passes   if every step is a move of the routes' rule: the cell entered has w != 0, and on a diagonal step
+ *                  both cells it cuts have w != 0 -- ONE blocked corner cell refuses the step (the routes' rule, not the views',
+ *                  where both must block).  Its cost is the sum over its steps of c * w[cell entered]
+ *   next waypoint  from an anchor p_a the LARGEST j in (a, min(a + lookahead, n - 1)] whose segment p_a -> p_j passes and costs at
+ *                  most d[p_j] - d[p_a] + slack.  j = a + 1 always qualifies (a traced step: its cost is exactly the difference).
+ *                  p_j is emitted and becomes the anchor, until the goal is emitted; p_0 is emitted first
+ * The result is defined by "largest j", not by a search order: it does not depend on how the work is scheduled.  On a converged key
+ * image a passing segment is a path of the routes' graph and never costs less than d[p_j] - d[p_a], so with slack = 0 every segment
+ * is an equally cheap way and the total cost equals d(goal); with unit weights the line's cost is the octile distance, a lower bound
+ * of every path, so the slack never binds, the rule is pure line of sight and the total is d(goal) again; in general the total is at
+ * most d(goal) + (n_way - 1) * slack.  With cost-map weights, slack is how much extra cost per segment a shortcut may pay to leave
+ * the cost valley.
+ *   record         len: as tsd_route_trace gives it (0: no key or outside the map, -1: no matching neighbour);  n_way: the full
+ *                  count even where it is larger than max_way, 0 where len <= 0 or len > max_len (a path the trace buffer cuts is
+ *                  not straightened), 1 for a goal on its seed;  cost: the sum of the segments' costs (modulo 2^32);  dist: the
+ *                  goal's d, TSD_ROUTE_NONE without a key */
+#define TSD_WAYPOINT_MAX_LOOKAHEAD 1024
+typedef struct {
+  int32_t  lookahead;           /* path cells a segment may span: 1 .. TSD_WAYPOINT_MAX_LOOKAHEAD */
+  uint32_t slack;               /* extra cost a segment may pay over the field's difference */
+  int32_t  max_len;             /* the trace buffer per goal, >= 1 */
+  int32_t  max_way;             /* waypoints returned per goal, >= 1 */
+} tsd_waypoint_params;          /* 16 bytes */
+typedef struct {
+  int32_t  len;
+  int32_t  n_way;
+  uint32_t cost;
+  uint32_t dist;
+} tsd_waypoint_info;            /* 16 bytes */
+/* The waypoints of n_goals cells (any cells, linear indices; 1 .. TSD_ROUTE_MAX_GOALS of them, n_goals * max_len <= 1 << 24 and
+ * n_goals * max_way <= 1 << 24): way_host[g * max_way + i], i < min(n_way, max_way), seed first and goal last; words beyond that are
+ * not written.  The trace runs into the route's scratch and k_route_waypoints right behind it, one workgroup per goal, on the stream
+ * of the route result like tsd_route_trace and under the same lock as the frontier, route and view calls; the call waits.  Scratch
+ * stays with the context and grows on demand: a repeated call at the same size allocates nothing.  TSD_E_ARG, with the outputs and
+ * the context's result left as they were: no route result, a NULL argument, lookahead outside 1 .. TSD_WAYPOINT_MAX_LOOKAHEAD,
+ * max_len < 1, max_way < 1, n_goals outside 1 .. TSD_ROUTE_MAX_GOALS, n_goals * max_len or n_goals * max_way above 1 << 24. */
+int tsd_route_waypoints(tsd_ctx* ctx, const uint32_t* goal_cells, int n_goals, const tsd_waypoint_params* params,
+                        uint32_t* way_host /* [g * max_way + i], i < min(n_way, max_way): linear cell indices, seed first, goal last */,
+                        tsd_waypoint_info* info_host /* n_goals */);
+
 /* ---- views: what a scan from a cell would uncover, and who is about to see it ------------------------------------ */
 /* The expected information gain of candidate cells (exploration goals) and the coordination rule on top of it: what one robot is
  * about to see is no longer worth a visit by another.  Input: an int8 map on the context's device as for the frontiers and routes --
@@ -1076,6 +1128,7 @@ int tsd_fuse(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell_off_x
  * tsd_frontiers_dev: "frontier_tile", "frontier_seam", "frontier_flatten" (each once for the frontiers and once more for the regions
  * where seeds are given), "frontier_rank" (count, scan, emit), "frontier_stats" (with the min_size compaction), and those of
  * tsd_route_dev, tsd_route_goals and tsd_route_trace: "route_init", "route_relax" (a batch of rounds), "route_goals", "route_trace",
+ * tsd_route_waypoints' launch behind its trace: "route_waypoints",
  * and the launches of tsd_view_gains and tsd_view_claim on the context's stream: "view_gain", "view_claim". */
 int tsd_profile_enable(tsd_ctx* ctx, int on);
 /* restrict timing to a comma separated list of kernel names, or "all"; a "/n" suffix times every n-th

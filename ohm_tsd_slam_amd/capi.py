@@ -174,6 +174,24 @@ ROUTE_GOAL_DTYPE = np.dtype([("cell", "<u4"), ("dist", "<u4"), ("seed", "<i4"), 
 assert ROUTE_GOAL_DTYPE.itemsize == C.sizeof(RouteGoal) == 16
 
 
+WAYPOINT_MAX_LOOKAHEAD = 1024
+ROUTE_MAX_GOALS = 4096
+
+
+class WaypointParams(C.Structure):
+    """tsd_waypoint_params"""
+    _fields_ = [("lookahead", C.c_int32), ("slack", C.c_uint32), ("max_len", C.c_int32), ("max_way", C.c_int32)]
+
+
+class WaypointInfo(C.Structure):
+    """tsd_waypoint_info"""
+    _fields_ = [("len", C.c_int32), ("n_way", C.c_int32), ("cost", C.c_uint32), ("dist", C.c_uint32)]
+
+
+WAYPOINT_INFO_DTYPE = np.dtype([("len", "<i4"), ("n_way", "<i4"), ("cost", "<u4"), ("dist", "<u4")])
+assert WAYPOINT_INFO_DTYPE.itemsize == C.sizeof(WaypointInfo) == C.sizeof(WaypointParams) == 16
+
+
 VIEW_MAX_RADIUS = 511
 VIEW_MAX_CELLS = 4096
 
@@ -409,6 +427,7 @@ ABI = {
     "tsd_route_dev_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), _ip, _ip]),
     "tsd_route_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _ip]),
     "tsd_debug_set_route_sweeps": (C.c_int, [C.c_void_p, C.c_int]),
+    "tsd_route_waypoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(WaypointParams), C.c_void_p, C.c_void_p]),
     "tsd_view_gains": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_void_p]),
     "tsd_view_claim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int]),
     "tsd_view_claims_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -495,7 +514,8 @@ def load_library(path: str | None = None):
                           ("tsd_costmap_params", CostmapParams), ("tsd_frontier", Frontier),
                           ("tsd_frontier_params", FrontierParams), ("tsd_route_params", RouteParams),
                           ("tsd_route_info", RouteInfo), ("tsd_route_goal", RouteGoal),
-                          ("tsd_view_params", ViewParams), ("tsd_view_gain", ViewGain)):
+                          ("tsd_view_params", ViewParams), ("tsd_view_gain", ViewGain),
+                          ("tsd_waypoint_params", WaypointParams), ("tsd_waypoint_info", WaypointInfo)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -1329,6 +1349,21 @@ class TsdGridDevice:
         self.last_rc = rc
         self._check(rc, "tsd_route_trace")
         return [paths[g, :min(max(int(n), 0), int(max_len))].copy() for g, n in enumerate(lens)], lens
+
+    def route_waypoints(self, cells, lookahead=128, slack=0, max_len=4096, max_way=256):
+        """tsd_route_waypoints: (waypoints -- one uint32 array of linear cell indices per goal cell, SEED FIRST and goal last (the
+        opposite of route_paths), consecutive cells joined by a straight drivable segment that spans at most ``lookahead`` path cells
+        and costs at most the field's difference plus ``slack``, cut at ``max_way`` --, info as a structured array of
+        WAYPOINT_INFO_DTYPE: len as route_paths gives it, n_way the full count (0 where the path is longer than ``max_len``), the
+        segments' cost, the goal's dist)"""
+        cells = np.ascontiguousarray(cells, dtype=np.uint32).ravel()
+        way = np.zeros((cells.size, max(int(max_way), 1)), dtype=np.uint32)
+        info = np.zeros(cells.size, dtype=WAYPOINT_INFO_DTYPE)
+        prm = WaypointParams(int(lookahead), int(slack), int(max_len), int(max_way))
+        rc = self.lib.tsd_route_waypoints(self.h, cells.ctypes.data, int(cells.size), C.byref(prm), way.ctypes.data, info.ctypes.data)
+        self.last_rc = rc
+        self._check(rc, "tsd_route_waypoints")
+        return [way[g, :min(max(int(n), 0), int(max_way))].copy() for g, n in enumerate(info["n_way"])], info
 
     # ---- views (tsd_view_gains / _claim / _claims_reset / _claims_dev_ptr / _assign)
     def view_gains_of(self, dev_ptr, width: int, height: int, stride: int, cells, radius: int, free_max=0, unknown_depth=0,

@@ -456,6 +456,53 @@ int ThreadGrid::exploreGains(const tsd_route_goal* goals, size_t n, double viewR
   return TSD_OK;
 }
 
+// The waypoint entry point is a weak reference like the routes'.
+#pragma weak tsd_route_waypoints
+
+int waypointLookaheadCells(double lookahead, double cellSize)
+{
+  if(!(lookahead > 0.0) || !(cellSize > 0.0))
+    return 1;
+  const double cells = std::floor(lookahead / cellSize + 0.5);
+  return cells < 1.0 ? 1 : cells > (double)TSD_WAYPOINT_MAX_LOOKAHEAD ? TSD_WAYPOINT_MAX_LOOKAHEAD : static_cast<int>(cells);
+}
+
+int routeWaypoints(tsd_ctx* ctx, const tsd_route_goal* goals, size_t n, const tsd_waypoint_params& prm, uint32_t* way, tsd_waypoint_info* info)
+{
+  if(!tsd_route_waypoints || (n > 0 && (!goals || !way || !info)) || prm.max_len < 1 || prm.max_len > (1 << 24) || prm.max_way < 1 ||
+     prm.max_way > (1 << 24))
+    return TSD_E_ARG;
+  std::vector<uint32_t> cells(n);
+  for(size_t i = 0; i < n; i++)
+    cells[i] = goals[i].cell;            // (TSD_ROUTE_NONE lies outside every map: a record of len 0, n_way 0)
+  const size_t chunk = std::min<size_t>(TSD_ROUTE_MAX_GOALS, ((size_t)1 << 24) / (size_t)std::max(prm.max_len, prm.max_way));
+  for(size_t first = 0; first < n; first += chunk)
+  {
+    const int count = static_cast<int>(std::min(chunk, n - first));
+    const int rc = tsd_route_waypoints(ctx, cells.data() + first, count, &prm, way + first * (size_t)prm.max_way, info + first);
+    if(rc != TSD_OK)
+      return rc;
+  }
+  return TSD_OK;
+}
+
+int ThreadGrid::exploreWaypoints(const tsd_route_goal* goals, size_t n, double lookahead, uint32_t slack, int maxLen, int maxWay, uint32_t* way,
+                                 tsd_waypoint_info* info, int* lookaheadCells)
+{
+  std::lock_guard<std::mutex> lk(_publishMutex);
+  if(_planStamp != _frames + _updates)
+    return TSD_E_ARG;                  // no plan, or one of a map that has been published over
+  tsd_waypoint_params prm;
+  prm.lookahead = waypointLookaheadCells(lookahead, static_cast<double>(_grid.getCellSize()));
+  prm.slack = slack;
+  prm.max_len = maxLen;
+  prm.max_way = maxWay;
+  if(lookaheadCells)
+    *lookaheadCells = prm.lookahead;
+  std::lock_guard<std::mutex> fl(_grid.frontierMutex());
+  return routeWaypoints(_grid.context(), goals, n, prm, way, info);
+}
+
 void ThreadGrid::mapPlacement(double* originRes)
 {
   std::lock_guard<std::mutex> m(_msgMutex);

@@ -44,6 +44,13 @@ struct ExplorePlan
 int routePlan(tsd_ctx* ctx, const void* mapDev, int width, int height, int source, const tsd_route_params& prm, int maxLen, ExplorePlan* out);
 /** A view radius [m] in cells: rounded to the nearest, at least 1 and at most TSD_VIEW_MAX_RADIUS. */
 int viewRadiusCells(double viewRadius, double cellSize);
+/** A waypoint look-ahead [m] in path cells: rounded to the nearest, at least 1 and at most TSD_WAYPOINT_MAX_LOOKAHEAD. */
+int waypointLookaheadCells(double lookahead, double cellSize);
+/** The waypoints (tsd_route_waypoints) of `n` goals of a plan on the context that holds the plan's route result, in chunks the entry
+ *  takes: way[i * prm.max_way + k], k < min(info[i].n_way, prm.max_way), seed first and goal last; a goal without a cell gets a record
+ *  of len 0 and n_way 0.  The caller holds the context's frontierMutex, and for a route made by the generic form the grid's mutex.
+ *  TSD_E_ARG where the device library has no waypoints. */
+int routeWaypoints(tsd_ctx* ctx, const tsd_route_goal* goals, size_t n, const tsd_waypoint_params& prm, uint32_t* way, tsd_waypoint_info* info);
 
 class ThreadGrid : public ThreadSLAM
 {
@@ -101,6 +108,14 @@ public:
    *  per goal, zeros for a goal without a cell.  Holds the publish mutex and the grid's frontierMutex.  TSD_E_ARG without a plan, where
    *  the map has been published again since the plan was made, and where the device library has no views. */
   int exploreGains(const tsd_route_goal* goals, size_t n, double viewRadius, int unknownDepth, tsd_view_gain* out, int* radiusCells);
+  /** The paths to `n` goals of the plan made last, straightened into waypoints joined by straight drivable segments
+   *  (tsd_route_waypoints on the plan's route result): segments span at most `lookahead` [m] of path -- rounded to cells, at least 1 and
+   *  at most TSD_WAYPOINT_MAX_LOOKAHEAD, returned in *lookaheadCells -- and may cost `slack` more than the field's difference; paths
+   *  longer than maxLen cells are not straightened; way[i * maxWay + k], seed first, goal last.  Holds the publish mutex and the grid's
+   *  frontierMutex.  TSD_E_ARG without a plan, where the map has been published again since the plan was made, and where the device
+   *  library has no waypoints. */
+  int exploreWaypoints(const tsd_route_goal* goals, size_t n, double lookahead, uint32_t slack, int maxLen, int maxWay, uint32_t* way,
+                       tsd_waypoint_info* info, int* lookaheadCells);
   /** origin x, y and resolution of <node>/map: fixed by the parameters at construction, the same before and after a publication */
   void mapPlacement(double* originRes);
 

@@ -271,6 +271,25 @@ int ThreadGridGroup::exploreAssign(const tsd_route_goal* goals, size_t n, double
                          picked, rounds);
 }
 
+int ThreadGridGroup::exploreWaypoints(const tsd_route_goal* goals, size_t n, double lookahead, uint32_t slack, int maxLen, int maxWay,
+                                      uint32_t* way, tsd_waypoint_info* info, int* lookaheadCells)
+{
+  std::lock_guard<std::mutex> lk(_publishMutex);
+  if(_planFrames == 0 || _planFrames != _frames)
+    return TSD_E_ARG;                  // no plan, or one of a merged map that has been published over
+  tsd_waypoint_params prm;
+  prm.lookahead = waypointLookaheadCells(lookahead, static_cast<double>(_grid.getCellSize()));
+  prm.slack = slack;
+  prm.max_len = maxLen;
+  prm.max_way = maxWay;
+  if(lookaheadCells)
+    *lookaheadCells = prm.lookahead;
+  // as for the plan: member 0's context and stream carry the call
+  std::lock_guard<std::mutex> fl(_members[0].grid->frontierMutex());
+  std::lock_guard<std::mutex> g(_members[0].grid->mutex());
+  return routeWaypoints(_members[0].grid->context(), goals, n, prm, way, info);
+}
+
 int ThreadGridGroup::fuse(obvious::TsdGrid* dst)
 {
   if(!dst || !dst->valid())

@@ -78,6 +78,12 @@ public:
    *  re-placed since the plan was made, and where the device library has no views. */
   int exploreAssign(const tsd_route_goal* goals, size_t n, double viewRadius, uint32_t gainWeight, int unknownDepth, int32_t* goalOfRobot,
                     tsd_view_gain* picked, int* rounds, int* radiusCells);
+  /** ThreadGrid::exploreWaypoints for the plan made last on the merged map: the paths to its goals straightened into waypoints
+   *  (tsd_route_waypoints on member 0's context, which holds the plan's route result).  Holds the publish mutex and member 0's
+   *  frontierMutex and grid mutex.  TSD_E_ARG without a plan, where the merged map has been published again or re-placed since the plan
+   *  was made, and where the device library has no waypoints. */
+  int exploreWaypoints(const tsd_route_goal* goals, size_t n, double lookahead, uint32_t slack, int maxLen, int maxWay, uint32_t* way,
+                       tsd_waypoint_info* info, int* lookaheadCells);
   size_t members(void) const { return _members.size(); }
 
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }

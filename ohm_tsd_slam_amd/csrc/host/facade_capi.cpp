@@ -642,6 +642,18 @@ int tsd_node_explore_gains(tsd_node* n, double view_radius_m, int unknown_depth,
   return n->gridThread->exploreGains(n->plan.goals.data(), n->plan.goals.size(), view_radius_m, unknown_depth, out, radius_cells);
 }
 
+// The paths of the plan made last straightened into waypoints (ThreadGrid::exploreWaypoints): for each goal of
+// tsd_node_explore_plan's counts one tsd_waypoint_info and way[i * max_way + k], k < min(n_way, max_way), linear cell indices, seed
+// first and goal last; *lookahead_cells: the look-ahead the call used.
+int tsd_node_explore_waypoints(tsd_node* n, double lookahead_m, unsigned slack, int max_len, int max_way, uint32_t* way, tsd_waypoint_info* info,
+                               int* lookahead_cells)
+{
+  if(!n || !n->gridThread || ((!way || !info) && !n->plan.goals.empty()))
+    return TSD_E_ARG;
+  return n->gridThread->exploreWaypoints(n->plan.goals.data(), n->plan.goals.size(), lookahead_m, slack, max_len, max_way, way, info,
+                                         lookahead_cells);
+}
+
 // <node>/get_map (ThreadGrid::getMapServCallBack): the last map with a fresh stamp (map_out layout); 1 if the service answered
 int tsd_node_get_map(tsd_node* n, int8_t* data_out, double* out12, char* frame_id, int cap)
 {
@@ -845,6 +857,15 @@ int tsd_fleet_explore_assign(tsd_fleet* f, double view_radius_m, unsigned gain_w
     return TSD_E_ARG;
   return f->group->exploreAssign(f->plan.goals.data(), f->plan.goals.size(), view_radius_m, gain_weight, unknown_depth, goal_of_robot, picked,
                                  rounds, radius_cells);
+}
+
+// The merged plan's paths straightened into waypoints (ThreadGridGroup::exploreWaypoints), as tsd_node_explore_waypoints.
+int tsd_fleet_explore_waypoints(tsd_fleet* f, double lookahead_m, unsigned slack, int max_len, int max_way, uint32_t* way, tsd_waypoint_info* info,
+                                int* lookahead_cells)
+{
+  if(!f || !f->group || ((!way || !info) && !f->plan.goals.empty()))
+    return TSD_E_ARG;
+  return f->group->exploreWaypoints(f->plan.goals.data(), f->plan.goals.size(), lookahead_m, slack, max_len, max_way, way, info, lookahead_cells);
 }
 
 // every node's position (robot 0's last estimated pose) in ITS grid's coordinates, NaN without a pose: what the group's calls take

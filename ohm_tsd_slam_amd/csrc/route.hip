@@ -13,6 +13,7 @@
 // k_route_goals  every frontier cell with a key finds its record by binary search over the records' roots and lowers the record's
 //                slot to (key << 32) | cell; k_route_goals_emit turns the slots into tsd_route_goal in place.
 // k_route_trace  one wave per goal cell: lanes 0 .. 7 test the eight neighbours, the lowest lane that matches is the step.
+//                (route_trace_enqueue: the launch both tsd_route_trace and waypoint.hip's tsd_route_waypoints use)
 //
 // ORDER.  Only kernel boundaries order anything between tiles.  Within a round an apron read may return a neighbour's key of the
 // round before: that neighbour's keys fell in this round, so it has set this tile's byte for the next one.  Keys only fall and are
@@ -357,11 +358,35 @@ static int run_route(tsd_ctx* ctx, const MapSource& src, const tsd_route_params*
   return TSD_OK;
 }
 
+// The trace of n_goals cells on the route result's stream, into the route's scratch and not waited for: what tsd_route_trace copies
+// back and what tsd_route_waypoints (waypoint.hip) works on in place.  d_path holds the goal cells, the lengths, the paths, in this
+// order.  The caller has checked the arguments and set the device.  Out of memory takes the route result and its goals along.
+int route_trace_enqueue(tsd_ctx* ctx, const uint32_t* goal_cells, int n_goals, int max_len, RouteTrace* out)
+{
+  tsd_ctx::Route& r = ctx->route;
+  const size_t ng = (size_t)n_goals;
+  const int rc = scratch_grow(ctx, RT_WHO, &r.d_path, &r.path_words, 2 * ng + ng * (size_t)max_len, "the paths");
+  if (rc == TSD_E_NOMEM) { r.valid = false; r.n_goals = -1; }
+  if (rc) return rc;
+  uint32_t* d_goals = r.d_path;
+  int32_t* d_len = reinterpret_cast<int32_t*>(r.d_path + ng);
+  uint32_t* d_paths = r.d_path + 2 * ng;
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d_goals, goal_cells, ng * sizeof(uint32_t), hipMemcpyHostToDevice, r.stream));
+  {
+    ScopedKernelTimer t(ctx, r.stream == ctx->stream ? "route_trace" : "", true);
+    hipLaunchKernelGGL(k_route_trace, dim3((unsigned)n_goals), dim3(64), 0, r.stream, r.d_key, r.d_w, r.W, r.H, d_goals, max_len, d_paths, d_len);
+  }
+  TSD_HIP_CHECK(ctx, hipGetLastError());
+  *out = RouteTrace{d_goals, d_len, d_paths};
+  return TSD_OK;
+}
+
 void route_free(tsd_ctx* ctx)
 {
   tsd_ctx::Route& r = ctx->route;
-  hipFree(r.d_key); hipFree(r.d_w); hipFree(r.d_act); hipFree(r.d_goal); hipFree(r.d_path); hipFree(r.d_res);
+  hipFree(r.d_key); hipFree(r.d_w); hipFree(r.d_act); hipFree(r.d_goal); hipFree(r.d_path); hipFree(r.d_res); hipFree(r.d_way);
   if (r.h_path) hipHostFree(r.h_path);
+  if (r.h_way) hipHostFree(r.h_way);
   if (r.h_res) hipHostFree(r.h_res);
   r = tsd_ctx::Route{};
 }
@@ -449,22 +474,15 @@ int tsd_route_trace(tsd_ctx* ctx, const uint32_t* goal_cells, int n_goals, int m
                      hipSuccess);
   if (!r.valid) return set_error(ctx, TSD_E_ARG, "tsd_route_trace: no route result", hipSuccess);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  // d_path: the goal cells, the lengths, the paths; h_path: the lengths, the paths
+  // h_path: the lengths, the paths
   const size_t ng = (size_t)n_goals, back = ng + ng * (size_t)max_len;
-  int rc = scratch_grow(ctx, RT_WHO, &r.d_path, &r.path_words, ng + back, "the paths");
-  if (!rc) rc = scratch_grow(ctx, RT_WHO, &r.h_path, &r.h_path_words, back, "the paths' pinned copy", true);
-  if (rc == TSD_E_NOMEM) { r.valid = false; r.n_goals = -1; }        // out of memory takes the route result and its goals along
-  if (rc) return rc;
-  uint32_t* d_goals = r.d_path;
-  int32_t* d_len = reinterpret_cast<int32_t*>(r.d_path + ng);
-  uint32_t* d_paths = r.d_path + 2 * ng;
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d_goals, goal_cells, ng * sizeof(uint32_t), hipMemcpyHostToDevice, r.stream));
-  {
-    ScopedKernelTimer t(ctx, r.stream == ctx->stream ? "route_trace" : "", true);
-    hipLaunchKernelGGL(k_route_trace, dim3((unsigned)n_goals), dim3(64), 0, r.stream, r.d_key, r.d_w, r.W, r.H, d_goals, max_len, d_paths, d_len);
+  if (int rc = scratch_grow(ctx, RT_WHO, &r.h_path, &r.h_path_words, back, "the paths' pinned copy", true)) {
+    if (rc == TSD_E_NOMEM) { r.valid = false; r.n_goals = -1; }        // out of memory takes the route result and its goals along
+    return rc;
   }
-  TSD_HIP_CHECK(ctx, hipGetLastError());
-  TSD_HIP_CHECK(ctx, hipMemcpyAsync(r.h_path, d_len, back * sizeof(uint32_t), hipMemcpyDeviceToHost, r.stream));
+  RouteTrace tr{};
+  if (int rc = route_trace_enqueue(ctx, goal_cells, n_goals, max_len, &tr)) return rc;
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(r.h_path, tr.d_len, back * sizeof(uint32_t), hipMemcpyDeviceToHost, r.stream));   // (the lengths, then the paths)
   TSD_HIP_CHECK(ctx, hipStreamSynchronize(r.stream));
   const int32_t* h_len = reinterpret_cast<const int32_t*>(r.h_path);
   for (size_t g = 0; g < ng; g++) {

@@ -328,6 +328,7 @@ struct tsd_ctx {
     tsd_route_goal* d_goal = nullptr; size_t goals = 0;
     uint32_t* d_path = nullptr; uint32_t* h_path = nullptr; size_t path_words = 0, h_path_words = 0;   // goal cells, lengths, paths; h_path pinned
     uint32_t* d_res = nullptr; uint32_t* h_res = nullptr;                         // the call's counters; h_res pinned
+    uint32_t* d_way = nullptr; uint32_t* h_way = nullptr; size_t way_words = 0, h_way_words = 0;       // waypoint.hip: the records, the waypoints; h_way pinned
     hipStream_t stream = nullptr;                                                 // the stream the result was made on: goals and paths follow it
     bool valid = false;                                                           // the last result (false: none)
     int W = 0, H = 0, n_goals = -1;
@@ -383,7 +384,7 @@ struct tsd_ctx {
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;
   unsigned profile_every = 1;   // time every n-th launch of a selected kernel ("name/n" in tsd_profile_select)
-  unsigned profile_every_k[20] = {};   // a kernel's own period ("name:m"), 0 = the list's
+  unsigned profile_every_k[21] = {};   // a kernel's own period ("name:m"), 0 = the list's
   bool profile = false;
   std::map<std::string, tsd::KernelTimer> timers;
   std::vector<hipEvent_t> event_pool;
@@ -621,6 +622,10 @@ void align_free(tsd_ctx* ctx);               // align.hip: releases tsd_ctx::ali
 void clearance_free(tsd_ctx* ctx);           // clearance.hip: releases tsd_ctx::clearance (tsd_destroy)
 void frontier_free(tsd_ctx* ctx);            // frontier.hip: releases tsd_ctx::frontier (tsd_destroy)
 void route_free(tsd_ctx* ctx);               // route.hip: releases tsd_ctx::route (tsd_destroy)
+// route.hip: k_route_trace enqueued on the route result's stream, not waited for; where it leaves the goal cells, the lengths and the
+// paths ([g * max_len + j], goal first) in tsd_ctx::route's scratch
+struct RouteTrace { const uint32_t* d_goals; const int32_t* d_len; const uint32_t* d_paths; };
+int route_trace_enqueue(tsd_ctx* ctx, const uint32_t* goal_cells, int n_goals, int max_len, RouteTrace* out);
 void view_free(tsd_ctx* ctx);                // view.hip: releases tsd_ctx::view (tsd_destroy)
 int8_t* frame_staged_map(const tsd_ctx* ctx);   // map_publish.hip: the frame staging's map (cells * cells int8), nullptr without a staging
 int launch_calibrate(tsd_ctx* ctx, double* t, double* w, size_t n);

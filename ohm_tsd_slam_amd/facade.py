@@ -67,6 +67,8 @@ HOST_ABI = {
     "tsd_fleet_explore_plan_fetch": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsd_node_explore_gains": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_void_p, _ip]),
     "tsd_fleet_explore_assign": (C.c_int, [C.c_void_p, C.c_double, C.c_uint, C.c_int, C.c_void_p, C.c_void_p, _ip, _ip]),
+    "tsd_node_explore_waypoints": (C.c_int, [C.c_void_p, C.c_double, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _ip]),
+    "tsd_fleet_explore_waypoints": (C.c_int, [C.c_void_p, C.c_double, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _ip]),
     "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_grid_lock": (None, [C.c_void_p]),
@@ -447,7 +449,21 @@ class SlamNode:
             self.h, None, -1, int(min_size or 0), capi.ROUTE_SOURCES[source], int(max_weight), int(max_len), c, i, so, no, oc),
             lambda *out: self.lib.tsd_node_explore_plan_fetch(self.h, *out), self.map_msg()["width"], max_len, "tsd_node_explore_plan")
         self._plan_goals = len(out["goals"])
+        self._plan_frame = (self.map_msg()["width"], int(max_len), out["origin"], out["resolution"])
         return out
+
+    def explore_waypoints(self, lookahead_m: float, slack=0, max_way=256) -> dict:
+        """The paths of the plan made last straightened for a controller (tsd_route_waypoints): ``waypoints`` -- per goal an (n, 2)
+        float64 array in the map's frame [m], (cell + 0.5) * resolution + origin, ordered seed to goal like ``explore_plan``'s paths,
+        consecutive points joined by a straight segment that is drivable cell by cell under the routes' rule, spans at most
+        ``lookahead_m`` of path (rounded to cells, at most capi.WAYPOINT_MAX_LOOKAHEAD: ``lookahead_cells``) and costs at most
+        ``slack`` more than the stretch of path it replaces; cut at ``max_way`` points --, ``info`` (capi.WAYPOINT_INFO_DTYPE per
+        goal: the path's len, the full count n_way -- 0 without a path and where the path is longer than the plan's ``max_len`` --,
+        the segments' cost, the goal's dist).  Refused without a plan and once the map has been published again."""
+        if getattr(self, "_plan_goals", None) is None:
+            raise capi.TsdError("explore_waypoints: no plan (explore_plan first)")
+        return _waypoint_dict(lambda *a: self.lib.tsd_node_explore_waypoints(self.h, *a), self._plan_goals, self._plan_frame, lookahead_m,
+                              slack, max_way, "tsd_node_explore_waypoints")
 
     def explore_gains(self, view_radius_m: float, unknown_depth=0) -> np.ndarray:
         """What each goal of the plan made last is worth: the capi.VIEW_GAIN_DTYPE records (cell, gain, unknown, visible), one per
@@ -555,6 +571,22 @@ def _plan_dict(call, fetch, width, max_len, what):
             "seeds_used": counts[2], "origin": origin, "resolution": res}
 
 
+def _waypoint_dict(call, n, frame, lookahead_m, slack, max_way, what):
+    width, max_len, origin, res = frame
+    max_way = int(max_way)
+    way = np.zeros((n, max(max_way, 1)), dtype=np.uint32)
+    info = np.zeros(n, dtype=capi.WAYPOINT_INFO_DTYPE)
+    cells = C.c_int(0)
+    rc = call(float(lookahead_m), int(slack), max_len, max_way, way.ctypes.data, info.ctypes.data, C.byref(cells))
+    if rc != 0:
+        raise capi.TsdError(f"{what} failed ({rc}): no plan of the map published last, or max_way < 1?")
+    out = []
+    for k in range(n):
+        c = way[k, :min(max(int(info["n_way"][k]), 0), max_way)].astype(np.int64)
+        out.append(np.stack([((c % width) + 0.5) * res + origin[0], ((c // width) + 0.5) * res + origin[1]], axis=-1).reshape(-1, 2))
+    return {"waypoints": out, "info": info, "lookahead_cells": cells.value}
+
+
 class SlamFleet:
     """Several :class:`SlamNode` s on ONE GPU, each with its own grid, and their merged map (``ThreadGridGroup``): every node's
     ``x_offset`` / ``y_offset`` places its grid, offsets that do not differ by whole cells are refused.  The first node publishes
@@ -599,9 +631,21 @@ class SlamFleet:
         """``SlamNode.explore_plan`` on the merged map published last with one seed per node (``frontiers()``'s seeds), unit weights
         on the free cells: ``goals["seed"]`` is the node nearest to each frontier -- the assignment an exploration allocator starts
         from -- and each path starts at that node's cell."""
-        return _plan_dict(lambda c, i, so, no, oc: self.lib.tsd_fleet_explore_plan(self.h, int(min_size), int(max_len), c, i, so, no, oc),
-                          lambda *out: self.lib.tsd_fleet_explore_plan_fetch(self.h, *out), self.merged_map_msg()["width"], max_len,
-                          "tsd_fleet_explore_plan")
+        self._plan_goals = None
+        width = self.merged_map_msg()["width"]
+        out = _plan_dict(lambda c, i, so, no, oc: self.lib.tsd_fleet_explore_plan(self.h, int(min_size), int(max_len), c, i, so, no, oc),
+                         lambda *out: self.lib.tsd_fleet_explore_plan_fetch(self.h, *out), width, max_len, "tsd_fleet_explore_plan")
+        self._plan_goals = len(out["goals"])
+        self._plan_frame = (width, int(max_len), out["origin"], out["resolution"])
+        return out
+
+    def explore_waypoints(self, lookahead_m: float, slack=0, max_way=256) -> dict:
+        """``SlamNode.explore_waypoints`` for the merged map's plan made last: every goal's path, from the node nearest to it,
+        straightened into waypoints.  Refused without a plan and once the merged map has been published again."""
+        if getattr(self, "_plan_goals", None) is None:
+            raise capi.TsdError("explore_waypoints: no plan (explore_plan first)")
+        return _waypoint_dict(lambda *a: self.lib.tsd_fleet_explore_waypoints(self.h, *a), self._plan_goals, self._plan_frame, lookahead_m,
+                              slack, max_way, "tsd_fleet_explore_waypoints")
 
     def explore_assign(self, view_radius_m: float, gain_weight: int, unknown_depth=0) -> dict:
         """Which node drives where, on the merged map's plan made last (tsd_view_assign): ``goal_of_robot`` int32 per node -- an index
