@@ -801,6 +801,62 @@ int tsd_route_waypoints(tsd_ctx* ctx, const uint32_t* goal_cells, int n_goals, c
                         uint32_t* way_host /* [g * max_way + i], i < min(n_way, max_way): linear cell indices, seed first, goal last */,
                         tsd_waypoint_info* info_host /* n_goals */);
 
+/* ---- fields: a cost-to-go field per robot, for a fleet whose robots compete for the same goals ------------------- */
+/* A fields call takes tsd_route_params like a route call and relaxes L = n_seeds key images ("layers") side by side in the same
+ * rounds, uint32 each, layer r at keys + r * width * height:
+ *   layer r        the key image of the routes' rule with seed r ALONE; its index r stays in the key's low four bits.  It is byte
+ *                  for byte what tsd_route_dev leaves when every other seed of the list lies outside the map
+ *   unused seed    a seed outside the map or not on a traversable cell gives a layer of TSD_ROUTE_NONE only (used[r] = 0)
+ *   shared cell    two seeds on one cell get a full field each
+ *   identity       the element-wise minimum of the layers is tsd_route_dev's image for the whole list
+ *   goal matrix    tsd_route_goal[L][n] over the n records of the frontier result: row r holds the routes' goal of every frontier
+ *                  on layer r -- robot r's cheapest cell of that frontier, seed == r -- or {NONE, NONE, -1} where the frontier
+ *                  has no cell with a key on that layer
+ *   paths          a goal is a pair (cell, layer): the routes' path and waypoint rules on that layer's keys
+ * The fields result is a second instance of the route result in the context: a tsd_route_dev / _frame result and a fields result
+ * live side by side, and neither kind of call touches the other's keys, goals or paths.  The same kernels run both, a route call
+ * with one layer: one workgroup per tile AND layer in a round, the "any" word shared by all layers (one host wait per batch of
+ * rounds serves them all), so `rounds` is the rounds of the slowest layer.  Scratch stays with the context and grows on demand -- 4
+ * bytes per cell and layer for the keys, 1 per cell for the weights, 2 per tile and layer, the matrix, the paths and their pinned
+ * copies -- so a repeated call at the same size and seed count allocates nothing.  The fields calls take the same lock as the
+ * frontier, route and view calls.  TSD_E_NOMEM (tsd_last_error names the buffer) where the device cannot hold it; the fields
+ * result is gone then.  tsd_debug_set_route_sweeps applies to fields calls as well. */
+typedef struct {
+  int32_t  layers;              /* L = n_seeds */
+  int32_t  rounds;              /* launches of the relaxation: the slowest layer's */
+  int32_t  converged;           /* 0: max_rounds ran out; every key of every layer is then an upper bound of the rule's key */
+  int32_t  seeds_used;
+  uint8_t  used[TSD_FRONTIER_MAX_SEEDS];       /* 1: seed r is used */
+  uint32_t reached[TSD_FRONTIER_MAX_SEEDS];    /* cells with a key on layer r; 0 for r >= layers */
+} tsd_route_fields_info;        /* 96 bytes */
+/* The layers of any map on the context's device: as tsd_route_dev -- the context's stream, waited for, the same refusals with the
+ * previous fields result left in place.  Timed launches: "route_fields_init", "route_fields_relax". */
+int tsd_route_fields_dev(tsd_ctx* ctx, const void* map_dev, int width, int height, int stride, const tsd_route_params* params,
+                         tsd_route_fields_info* info);
+/* The same for what the context's last frame left on the device, as tsd_route_frame: sources, stream and refusals are its. */
+int tsd_route_fields_frame(tsd_ctx* ctx, int source, const tsd_route_params* params, tsd_route_fields_info* info);
+/* The goal matrix of the frontier result the context holds on the fields result it holds: *n is the number of records, the row
+ * length.  A frontier cell finds its record by one search and lowers its slot on every layer whose key it has.  TSD_E_ARG as
+ * tsd_route_goals: without a fields result, without a frontier result, or where their sizes differ.  Timed: "route_fields_goals". */
+int tsd_route_fields_goals(tsd_ctx* ctx, int* n);
+/* Goals first .. first + count - 1 of row `layer` of the last matrix, as tsd_route_goals_fetch; TSD_E_ARG also for a layer outside
+ * 0 .. layers - 1. */
+int tsd_route_fields_goals_fetch(tsd_ctx* ctx, int layer, int first, int count, tsd_route_goal* out);
+/* tsd_route_trace with a layer per goal: goal g is traced on layer goal_layers[g], all goals in one launch ("route_fields_trace").
+ * A goal without a key on its layer has len 0 whatever the other layers hold.  TSD_E_ARG, with the outputs untouched, as
+ * tsd_route_trace, and for a NULL goal_layers or a goal_layers[g] >= layers. */
+int tsd_route_fields_trace(tsd_ctx* ctx, const uint32_t* goal_cells, const uint8_t* goal_layers, int n_goals, int max_len,
+                           uint32_t* paths_host, int32_t* len_host);
+/* tsd_route_waypoints with a layer per goal, likewise: the same trace launch, then the same waypoint launch ("route_waypoints") on
+ * each goal's layer.  Refusals as tsd_route_waypoints and as tsd_route_fields_trace for the layers. */
+int tsd_route_fields_waypoints(tsd_ctx* ctx, const uint32_t* goal_cells, const uint8_t* goal_layers, int n_goals,
+                               const tsd_waypoint_params* params, uint32_t* way_host, tsd_waypoint_info* info_host);
+/* The fields result on the device: layer r at keys + r * width * height (uint32), valid until the next fields call on the context or
+ * tsd_destroy.  Each pointer may be NULL.  TSD_E_ARG without a result. */
+int tsd_route_fields_dev_ptrs(tsd_ctx* ctx, const void** keys_dev, int* width, int* height, int* layers);
+/* As tsd_route_counts, over all layers: the workgroups that found their tile active, and the host's waits. */
+int tsd_route_fields_counts(tsd_ctx* ctx, long long* tile_visits, int* host_waits);
+
 /* ---- views: what a scan from a cell would uncover, and who is about to see it ------------------------------------ */
 /* The expected information gain of candidate cells (exploration goals) and the coordination rule on top of it: what one robot is
  * about to see is no longer worth a visit by another.  Input: an int8 map on the context's device as for the frontiers and routes --
@@ -871,12 +927,35 @@ int tsd_view_claims_dev_ptr(tsd_ctx* ctx, const void** claims_dev, int* width, i
  * goal_of_robot[r]: the index of robot r's goal, -1 where it got none; picked[r] (may be NULL): that goal's record as its round saw it,
  * {TSD_ROUTE_NONE, 0, 0, 0} without a goal; *rounds: the rounds begun (at most n_robots), each one launch for the gains, one wait and,
  * where a goal was given, one launch for the claim.  The limit of the rule: a robot is only ever offered the goals it is nearest to,
- * because the route's key image holds one field for all seeds.  The claims image holds the claims of the goals given when the call
+ * because the route's key image holds one field for all seeds (tsd_view_assign_fields lifts it).  The claims image holds the claims of the goals given when the call
  * returns.  The map source, the stream and the refusals are tsd_view_gains'; TSD_E_ARG also for n_goals or n_robots out of range, a
  * NULL goals with n_goals > 0, a NULL goal_of_robot or rounds -- the claims image is left as it was then. */
 int tsd_view_assign(tsd_ctx* ctx, const void* map_dev, int width, int height, int stride, const tsd_view_params* params,
                     const tsd_route_goal* goals, int n_goals, int n_robots, uint32_t gain_weight,
                     int32_t* goal_of_robot /* n_robots, -1: none */, tsd_view_gain* picked /* n_robots or NULL */, int* rounds);
+/* The coordination rule across robots, on the goal matrix of a fields plan (tsd_route_fields_goals_fetch, row by row into host
+ * memory: goals[r * n_frontiers + f]).  Pair (r, f) stands for robot r and frontier f; cell_rf and dist_rf are goals[r][f]'s.
+ *   1. The claims are reset at the map's size.
+ *   2. Every pair with goals[r][f].cell != TSD_ROUTE_NONE is remaining.  Each robot drives to ITS cheapest cell of the frontier.
+ *   3. A round takes the gains, with claims in use, of the cells of all remaining pairs.  Each distinct cell is rated once.  A launch
+ *      takes at most TSD_VIEW_MAX_CELLS candidates, so a round makes as many launches as that needs.
+ *   4. score(r, f) = gain(cell_rf) * gain_weight - dist_rf in int64.
+ *   5. Only pairs with gain > 0 compete.  The highest score wins.  On a tie the lower f wins, then the lower r.
+ *   6. The call stops when no pair competes.
+ *   7. goal_of_robot[r] = f, picked[r] is that record, and V(cell_rf) is claimed.
+ *   8. Every pair of robot r and every pair of frontier f is dropped.
+ *   9. The call goes on while pairs remain.  There are at most min(n_robots, n_frontiers) rounds.
+ * Step 5 differs from tsd_view_assign on purpose: there a best-scored goal with gain 0 ends the call; here such a pair does not
+ * compete, and a pair with a gain behind it may still win.  Limits: n_frontiers in 0 .. TSD_VIEW_MAX_CELLS, n_robots in 1 ..
+ * TSD_FRONTIER_MAX_SEEDS.  goal_of_robot[r]: the FRONTIER index f of robot r's goal (its goal is goals[r][f]), -1 where it got none;
+ * picked[r] (may be NULL): the record of cell_rf as its round saw it, {TSD_ROUTE_NONE, 0, 0, 0} without a goal; *rounds: the rounds
+ * that took gains, the one in which no pair competed included; each makes its launches for the gains with one wait apiece and, where
+ * a pair won, one launch for the claim and one wait.  Host logic over the views' launches, like tsd_view_assign: the map source,
+ * the stream and the refusals are its, with n_frontiers in n_goals' place -- the claims image is left as it was on a refusal, and
+ * holds the claims of the cells given when the call returns. */
+int tsd_view_assign_fields(tsd_ctx* ctx, const void* map_dev, int width, int height, int stride, const tsd_view_params* params,
+                           const tsd_route_goal* goals /* [r * n_frontiers + f] */, int n_frontiers, int n_robots, uint32_t gain_weight,
+                           int32_t* goal_of_robot /* n_robots, -1: none */, tsd_view_gain* picked /* n_robots or NULL */, int* rounds);
 
 /* ---- the map's surface as an ordered point list --------------------------------------------------------------- */
 /* The `coords` array of RayCastAxisAligned2D::calcCoords (RayCastAxisAligned2D.cpp:13-105), point for point and in its serial order:
@@ -1128,7 +1207,9 @@ int tsd_fuse(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell_off_x
  * tsd_frontiers_dev: "frontier_tile", "frontier_seam", "frontier_flatten" (each once for the frontiers and once more for the regions
  * where seeds are given), "frontier_rank" (count, scan, emit), "frontier_stats" (with the min_size compaction), and those of
  * tsd_route_dev, tsd_route_goals and tsd_route_trace: "route_init", "route_relax" (a batch of rounds), "route_goals", "route_trace",
- * tsd_route_waypoints' launch behind its trace: "route_waypoints",
+ * tsd_route_waypoints' launch behind its trace: "route_waypoints" (tsd_route_fields_waypoints' as well),
+ * the same passes of tsd_route_fields_dev / _goals / _trace: "route_fields_init", "route_fields_relax", "route_fields_goals",
+ * "route_fields_trace",
  * and the launches of tsd_view_gains and tsd_view_claim on the context's stream: "view_gain", "view_claim". */
 int tsd_profile_enable(tsd_ctx* ctx, int on);
 /* restrict timing to a comma separated list of kernel names, or "all"; a "/n" suffix times every n-th

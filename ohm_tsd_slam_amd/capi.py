@@ -165,6 +165,18 @@ class RouteInfo(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class RouteFieldsInfo(C.Structure):
+    """tsd_route_fields_info"""
+    _fields_ = [("layers", C.c_int32), ("rounds", C.c_int32), ("converged", C.c_int32), ("seeds_used", C.c_int32),
+                ("used", C.c_uint8 * 16), ("reached", C.c_uint32 * 16)]
+
+    def as_dict(self):
+        d = {n: int(getattr(self, n)) for n in ("layers", "rounds", "converged", "seeds_used")}
+        d["used"] = [int(v) for v in self.used]
+        d["reached"] = [int(v) for v in self.reached]
+        return d
+
+
 class RouteGoal(C.Structure):
     """tsd_route_goal"""
     _fields_ = [("cell", C.c_uint32), ("dist", C.c_uint32), ("seed", C.c_int32), ("reserved", C.c_uint32)]
@@ -428,6 +440,16 @@ ABI = {
     "tsd_route_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _ip]),
     "tsd_debug_set_route_sweeps": (C.c_int, [C.c_void_p, C.c_int]),
     "tsd_route_waypoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(WaypointParams), C.c_void_p, C.c_void_p]),
+    "tsd_route_fields_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(RouteParams), C.POINTER(RouteFieldsInfo)]),
+    "tsd_route_fields_frame": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RouteParams), C.POINTER(RouteFieldsInfo)]),
+    "tsd_route_fields_goals": (C.c_int, [C.c_void_p, _ip]),
+    "tsd_route_fields_goals_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tsd_route_fields_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "tsd_route_fields_waypoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(WaypointParams), C.c_void_p, C.c_void_p]),
+    "tsd_route_fields_dev_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), _ip, _ip, _ip]),
+    "tsd_route_fields_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _ip]),
+    "tsd_view_assign_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_int,
+                                         C.c_uint32, C.c_void_p, C.c_void_p, _ip]),
     "tsd_view_gains": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_void_p]),
     "tsd_view_claim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int]),
     "tsd_view_claims_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -513,7 +535,7 @@ def load_library(path: str | None = None):
                           ("tsd_align_params", AlignParams), ("tsd_align_peak", AlignPeak), ("tsd_align_result", AlignResult),
                           ("tsd_costmap_params", CostmapParams), ("tsd_frontier", Frontier),
                           ("tsd_frontier_params", FrontierParams), ("tsd_route_params", RouteParams),
-                          ("tsd_route_info", RouteInfo), ("tsd_route_goal", RouteGoal),
+                          ("tsd_route_info", RouteInfo), ("tsd_route_goal", RouteGoal), ("tsd_route_fields_info", RouteFieldsInfo),
                           ("tsd_view_params", ViewParams), ("tsd_view_gain", ViewGain),
                           ("tsd_waypoint_params", WaypointParams), ("tsd_waypoint_info", WaypointInfo)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
@@ -1365,7 +1387,87 @@ class TsdGridDevice:
         self._check(rc, "tsd_route_waypoints")
         return [way[g, :min(max(int(n), 0), int(max_way))].copy() for g, n in enumerate(info["n_way"])], info
 
-    # ---- views (tsd_view_gains / _claim / _claims_reset / _claims_dev_ptr / _assign)
+    # ---- fields (tsd_route_fields_*): one key image per seed
+    def route_fields_dev_ptrs(self):
+        """tsd_route_fields_dev_ptrs: (keys_dev, width, height, layers) of the last fields call, valid until the next one; layer r
+        lies at keys_dev + 4 * r * width * height"""
+        k, w, h, l = C.c_void_p(), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self.lib.tsd_route_fields_dev_ptrs(self.h, C.byref(k), C.byref(w), C.byref(h), C.byref(l)), "tsd_route_fields_dev_ptrs")
+        return k.value, w.value, h.value, l.value
+
+    def route_fields_counts(self):
+        """tsd_route_fields_counts: (workgroups that found their tile active over all rounds and layers, host waits)"""
+        v, w = C.c_longlong(0), C.c_int(0)
+        self._check(self.lib.tsd_route_fields_counts(self.h, C.byref(v), C.byref(w)), "tsd_route_fields_counts")
+        return v.value, w.value
+
+    def route_fields_keys(self) -> np.ndarray:
+        """the key images of the last fields call, (layers, height, width) uint32, copied to the host"""
+        keys_dev, w, h, l = self.route_fields_dev_ptrs()
+        keys = np.zeros((l, h, w), dtype=np.uint32)
+        self._check(self.lib.tsd_dev_copy(self.h, keys.ctypes.data, keys_dev, keys.nbytes, 0), "tsd_dev_copy")
+        return keys
+
+    def route_fields_of(self, dev_ptr: int, width: int, height: int, stride: int, seeds, free_max=0, weights=None, limit=0, max_rounds=0):
+        """tsd_route_fields_dev on a device map: (keys (L, height, width) uint32 -- layer r the field of seed r alone, its index in
+        the low four bits --, info as a dict with used[] and reached[] per layer).  seeds: (x, y) cells, L of them."""
+        prm, keep = self._route_params(seeds, free_max, weights, limit, max_rounds)
+        info = RouteFieldsInfo()
+        rc = self.lib.tsd_route_fields_dev(self.h, C.c_void_p(dev_ptr), int(width), int(height), int(stride), C.byref(prm), C.byref(info))
+        self.last_rc = rc
+        self._check(rc, "tsd_route_fields_dev")
+        return self.route_fields_keys(), info.as_dict()
+
+    def route_fields(self, source="map", seeds=(), free_max=0, weights=None, limit=0, max_rounds=0):
+        """tsd_route_fields_frame: the same for the map ("map") of the frame or update taken last or for the cost map ("costmap")"""
+        prm, keep = self._route_params(seeds, free_max, weights, limit, max_rounds)
+        info = RouteFieldsInfo()
+        rc = self.lib.tsd_route_fields_frame(self.h, ROUTE_SOURCES[source], C.byref(prm), C.byref(info))
+        self.last_rc = rc
+        self._check(rc, "tsd_route_fields_frame")
+        return self.route_fields_keys(), info.as_dict()
+
+    def route_fields_goals(self) -> np.ndarray:
+        """tsd_route_fields_goals + _fetch: the goal matrix (L, n) of ROUTE_GOAL_DTYPE -- row r: for every record of the frontier
+        call made last robot r's cheapest cell of it on layer r of the fields call made last"""
+        n = C.c_int(0)
+        rc = self.lib.tsd_route_fields_goals(self.h, C.byref(n))
+        self.last_rc = rc
+        self._check(rc, "tsd_route_fields_goals")
+        layers = self.route_fields_dev_ptrs()[3]
+        out = np.zeros((layers, n.value), dtype=ROUTE_GOAL_DTYPE)
+        for r in range(layers):
+            self._check(self.lib.tsd_route_fields_goals_fetch(self.h, r, 0, n.value, out[r].ctypes.data), "tsd_route_fields_goals_fetch")
+        return out
+
+    def route_fields_paths(self, cells, layers, max_len=4096):
+        """tsd_route_fields_trace: route_paths with a layer per goal cell"""
+        cells = np.ascontiguousarray(cells, dtype=np.uint32).ravel()
+        layers = np.ascontiguousarray(layers, dtype=np.uint8).ravel()
+        assert layers.size == cells.size
+        paths = np.zeros((cells.size, int(max_len)), dtype=np.uint32)
+        lens = np.zeros(cells.size, dtype=np.int32)
+        rc = self.lib.tsd_route_fields_trace(self.h, cells.ctypes.data, layers.ctypes.data, int(cells.size), int(max_len), paths.ctypes.data,
+                                             lens.ctypes.data)
+        self.last_rc = rc
+        self._check(rc, "tsd_route_fields_trace")
+        return [paths[g, :min(max(int(n), 0), int(max_len))].copy() for g, n in enumerate(lens)], lens
+
+    def route_fields_waypoints(self, cells, layers, lookahead=128, slack=0, max_len=4096, max_way=256):
+        """tsd_route_fields_waypoints: route_waypoints with a layer per goal cell"""
+        cells = np.ascontiguousarray(cells, dtype=np.uint32).ravel()
+        layers = np.ascontiguousarray(layers, dtype=np.uint8).ravel()
+        assert layers.size == cells.size
+        way = np.zeros((cells.size, max(int(max_way), 1)), dtype=np.uint32)
+        info = np.zeros(cells.size, dtype=WAYPOINT_INFO_DTYPE)
+        prm = WaypointParams(int(lookahead), int(slack), int(max_len), int(max_way))
+        rc = self.lib.tsd_route_fields_waypoints(self.h, cells.ctypes.data, layers.ctypes.data, int(cells.size), C.byref(prm), way.ctypes.data,
+                                                 info.ctypes.data)
+        self.last_rc = rc
+        self._check(rc, "tsd_route_fields_waypoints")
+        return [way[g, :min(max(int(n), 0), int(max_way))].copy() for g, n in enumerate(info["n_way"])], info
+
+    # ---- views (tsd_view_gains / _claim / _claims_reset / _claims_dev_ptr / _assign / _assign_fields)
     def view_gains_of(self, dev_ptr, width: int, height: int, stride: int, cells, radius: int, free_max=0, unknown_depth=0,
                       use_claims=False) -> np.ndarray:
         """tsd_view_gains on a device map (``dev_ptr``: int8, ``height`` rows of ``stride`` bytes; None: the staged map of the frame
@@ -1435,6 +1537,29 @@ class TsdGridDevice:
     def view_assign(self, goals, n_robots: int, radius: int, gain_weight: int, free_max=0, unknown_depth=0):
         """the same for the map of the frame or update taken last"""
         return self.view_assign_of(None, 0, 0, 0, goals, n_robots, radius, gain_weight, free_max, unknown_depth)
+
+    def view_assign_fields_of(self, dev_ptr, width: int, height: int, stride: int, goals, radius: int, gain_weight: int, free_max=0,
+                              unknown_depth=0):
+        """tsd_view_assign_fields on the goal matrix of a fields plan (ROUTE_GOAL_DTYPE, shape (n_robots, n_frontiers)):
+        (goal_of_robot int32[n_robots] -- the frontier index each robot is given, -1 for none --, the picked cells' records as their
+        rounds saw them, the rounds)"""
+        goals = np.ascontiguousarray(goals, dtype=ROUTE_GOAL_DTYPE)
+        assert goals.ndim == 2
+        n_robots, n_frontiers = goals.shape
+        goal_of = np.full(n_robots, -7, dtype=np.int32)
+        picked = np.zeros(n_robots, dtype=VIEW_GAIN_DTYPE)
+        rounds = C.c_int(-1)
+        prm = ViewParams(int(free_max), int(radius), int(unknown_depth), 0)
+        rc = self.lib.tsd_view_assign_fields(self.h, None if dev_ptr is None else C.c_void_p(dev_ptr), int(width), int(height), int(stride),
+                                             C.byref(prm), goals.ctypes.data if goals.size else None, int(n_frontiers), int(n_robots),
+                                             int(gain_weight), goal_of.ctypes.data, picked.ctypes.data, C.byref(rounds))
+        self.last_rc = rc
+        self._check(rc, "tsd_view_assign_fields")
+        return goal_of, picked, rounds.value
+
+    def view_assign_fields(self, goals, radius: int, gain_weight: int, free_max=0, unknown_depth=0):
+        """the same for the map of the frame or update taken last"""
+        return self.view_assign_fields_of(None, 0, 0, 0, goals, radius, gain_weight, free_max, unknown_depth)
 
     def push_stats_total(self, reset=False):
         st = PushStats()

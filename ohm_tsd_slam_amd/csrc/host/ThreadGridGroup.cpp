@@ -169,7 +169,7 @@ int ThreadGridGroup::explorePlan(const double* gridXy, uint32_t minSize, int max
 // frontiers(); with `plan` also the routes from the same seeds on the same map (unit weights, free_max 0), under the same two locks:
 // the goals read the frontier result
 int ThreadGridGroup::frontiersAndPlan(const double* gridXy, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed, int32_t* seedsXy,
-                                      double* originCs, ExplorePlan* plan, int maxLen)
+                                      double* originCs, ExplorePlan* plan, int maxLen, ExploreDispatch* dispatch)
 {
   if(!gridXy || !out || _members.size() > (size_t)TSD_FRONTIER_MAX_SEEDS)
     return TSD_E_ARG;
@@ -237,12 +237,99 @@ int ThreadGridGroup::frontiersAndPlan(const double* gridXy, uint32_t minSize, st
       rp.max_rounds = 0;
       rc = routePlan(ctx, tsd_group_map_dev(_group), static_cast<int>(_width), static_cast<int>(_height), TSD_ROUTE_MAP, rp, maxLen, plan);
     }
+    if(rc == TSD_OK && dispatch)
+      rc = dispatchLocked(ctx, seeds, dispatch);
   }
+  if(dispatch)
+    dispatch->frames = rc == TSD_OK ? _frames : 0;
   if(seedsUsed)
     *seedsUsed = used;
   if(plan)
     _planFrames = rc == TSD_OK ? _frames : 0;
   return rc;
+}
+
+#pragma weak tsd_route_fields_dev
+#pragma weak tsd_route_fields_goals
+#pragma weak tsd_route_fields_goals_fetch
+#pragma weak tsd_route_fields_waypoints
+#pragma weak tsd_view_assign_fields
+
+int ThreadGridGroup::exploreDispatch(const double* gridXy, uint32_t minSize, ExploreDispatch* d, int32_t* seedsXy, double* originCs)
+{
+  if(!tsd_route_fields_dev || !tsd_route_fields_goals || !tsd_route_fields_goals_fetch || !tsd_route_fields_waypoints || !tsd_view_assign_fields ||
+     !d || d->unknownDepth < 0 || d->maxLen < 1 || d->maxWay < 1)
+    return TSD_E_ARG;
+  return frontiersAndPlan(gridXy, minSize, &d->frontiers, &d->seedsUsed, seedsXy, originCs, nullptr, 0, d);
+}
+
+// exploreDispatch behind the frontiers, on the same context and under the same locks: fields, matrix, assignment, waypoints
+int ThreadGridGroup::dispatchLocked(tsd_ctx* ctx, const std::vector<int32_t>& seeds, ExploreDispatch* d)
+{
+  const int L = static_cast<int>(_members.size()), W = static_cast<int>(_width), H = static_cast<int>(_height);
+  const double cs = static_cast<double>(_grid.getCellSize());
+  if(d->frontiers.size() > (size_t)TSD_VIEW_MAX_CELLS)
+    return TSD_E_ARG;
+  tsd_route_params rp;
+  rp.free_max = 0;
+  rp.n_seeds = L;
+  rp.seeds_xy = seeds.data();
+  rp.weights = nullptr;
+  rp.limit = 0;
+  rp.max_rounds = 0;
+  int rc = tsd_route_fields_dev(ctx, tsd_group_map_dev(_group), W, H, W, &rp, &d->fields);
+  if(rc != TSD_OK)
+    return rc;
+  int n = 0;
+  rc = tsd_route_fields_goals(ctx, &n);
+  if(rc != TSD_OK)
+    return rc;
+  d->goals.assign((size_t)L * n, tsd_route_goal{TSD_ROUTE_NONE, TSD_ROUTE_NONE, -1, 0u});
+  for(int r = 0; r < L && n > 0; r++)
+    if((rc = tsd_route_fields_goals_fetch(ctx, r, 0, n, d->goals.data() + (size_t)r * n)) != TSD_OK)
+      return rc;
+  tsd_view_params vp;
+  vp.free_max = 0;
+  vp.radius = viewRadiusCells(d->viewRadius, cs);
+  vp.unknown_depth = d->unknownDepth;
+  vp.use_claims = 0;
+  d->radiusCells = vp.radius;
+  d->goalOfRobot.assign((size_t)L, -1);
+  d->picked.assign((size_t)L, tsd_view_gain{TSD_ROUTE_NONE, 0u, 0u, 0u});
+  rc = tsd_view_assign_fields(ctx, tsd_group_map_dev(_group), W, H, W, &vp, d->goals.data(), n, L, d->gainWeight, d->goalOfRobot.data(),
+                              d->picked.data(), &d->rounds);
+  if(rc != TSD_OK)
+    return rc;
+  tsd_waypoint_params wp;
+  wp.lookahead = waypointLookaheadCells(d->lookahead, cs);
+  wp.slack = d->slack;
+  wp.max_len = d->maxLen;
+  wp.max_way = d->maxWay;
+  d->lookaheadCells = wp.lookahead;
+  d->way.assign((size_t)L * d->maxWay, 0u);
+  d->wayInfo.assign((size_t)L, tsd_waypoint_info{0, 0, 0u, TSD_ROUTE_NONE});
+  // the members with a goal, each on its own layer, in one call
+  std::vector<uint32_t> cells, way;
+  std::vector<uint8_t> layers;
+  for(int r = 0; r < L; r++)
+    if(d->goalOfRobot[r] >= 0)
+    {
+      cells.push_back(d->goals[(size_t)r * n + d->goalOfRobot[r]].cell);
+      layers.push_back(static_cast<uint8_t>(r));
+    }
+  if(cells.empty())
+    return TSD_OK;
+  way.assign(cells.size() * d->maxWay, 0u);
+  std::vector<tsd_waypoint_info> info(cells.size());
+  rc = tsd_route_fields_waypoints(ctx, cells.data(), layers.data(), static_cast<int>(cells.size()), &wp, way.data(), info.data());
+  if(rc != TSD_OK)
+    return rc;
+  for(size_t k = 0; k < cells.size(); k++)
+  {
+    d->wayInfo[layers[k]] = info[k];
+    std::memcpy(d->way.data() + (size_t)layers[k] * d->maxWay, way.data() + k * d->maxWay, (size_t)d->maxWay * sizeof(uint32_t));
+  }
+  return TSD_OK;
 }
 
 #pragma weak tsd_view_assign

@@ -19,6 +19,26 @@ namespace ohm_tsd_slam
 
 struct ExplorePlan;      // ThreadGrid.h
 
+/** What ThreadGridGroup::exploreDispatch is asked and what it answers. */
+struct ExploreDispatch
+{
+  // the request
+  double viewRadius = 0.0, lookahead = 0.0;  // [m]
+  uint32_t gainWeight = 0, slack = 0;
+  int unknownDepth = 0, maxLen = 4096, maxWay = 256;
+  // the answer
+  std::vector<tsd_frontier> frontiers;
+  int seedsUsed = 0;
+  tsd_route_fields_info fields = {};
+  std::vector<tsd_route_goal> goals;         // the matrix, [member * frontiers + frontier]
+  std::vector<int32_t> goalOfRobot;          // per member a frontier index, -1: none
+  std::vector<tsd_view_gain> picked;
+  int rounds = 0, radiusCells = 0, lookaheadCells = 0;
+  std::vector<uint32_t> way;                 // [member * maxWay + i]
+  std::vector<tsd_waypoint_info> wayInfo;    // per member
+  uint64_t frames = 0;                       // the publication it was made on (0: none)
+};
+
 class ThreadGridGroup : public ThreadSLAM
 {
 public:
@@ -73,7 +93,8 @@ public:
   /** Which member drives to which goal of the plan made last (tsd_view_assign on the merged map, free_max 0, one robot per member):
    *  a goal's worth is the unknown cells a scanner there would see within viewRadius [m] (rounded to cells, at least 1 and at most
    *  TSD_VIEW_MAX_RADIUS, returned in *radiusCells), and what one member is about to see is no longer worth a visit by another.
-   *  goalOfRobot and picked hold one entry per member.  A member is only ever offered the goals it is nearest to.  Holds the publish
+   *  goalOfRobot and picked hold one entry per member.  A member is only ever offered the goals it is nearest to (exploreDispatch
+   *  plans on a field per member and lifts that).  Holds the publish
    *  mutex and member 0's frontierMutex and grid mutex.  TSD_E_ARG without a plan, where the merged map has been published again or
    *  re-placed since the plan was made, and where the device library has no views. */
   int exploreAssign(const tsd_route_goal* goals, size_t n, double viewRadius, uint32_t gainWeight, int unknownDepth, int32_t* goalOfRobot,
@@ -84,6 +105,16 @@ public:
    *  was made, and where the device library has no waypoints. */
   int exploreWaypoints(const tsd_route_goal* goals, size_t n, double lookahead, uint32_t slack, int maxLen, int maxWay, uint32_t* way,
                        tsd_waypoint_info* info, int* lookaheadCells);
+  /** One call from the merged map to every member's way: the frontiers of the merged map published last with one seed per member
+   *  (frontiers()), a cost-to-go field PER MEMBER on the same map (tsd_route_fields_dev: unit weights, free_max 0), the goal matrix
+   *  (member r's cheapest cell of frontier f), the assignment across members (tsd_view_assign_fields: a member may be given a frontier
+   *  another member is nearer to) and the waypoints of each member's goal on that member's own field (tsd_route_fields_waypoints).
+   *  d's request fields are read, its results filled: goals[r * n + f]; goalOfRobot[r] a frontier index or -1; way[r * maxWay + i],
+   *  i < min(wayInfo[r].n_way, maxWay), seed first -- a member without a goal has a record of len 0 and n_way 0.  Holds the locks
+   *  explorePlan holds, from the frontiers to the last fetch.  Refuses as exploreAssign refuses: TSD_E_ARG before the first
+   *  publication, for a negative unknownDepth, for more than TSD_FRONTIER_MAX_SEEDS members or TSD_VIEW_MAX_CELLS frontiers, and where
+   *  the device library has no fields. */
+  int exploreDispatch(const double* gridXy, uint32_t minSize, ExploreDispatch* d, int32_t* seedsXy, double* originCs);
   size_t members(void) const { return _members.size(); }
 
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }
@@ -96,7 +127,8 @@ protected:
 
 private:
   int frontiersAndPlan(const double* gridXy, uint32_t minSize, std::vector<tsd_frontier>* out, int* seedsUsed, int32_t* seedsXy, double* originCs,
-                       ExplorePlan* plan, int maxLen);
+                       ExplorePlan* plan, int maxLen, ExploreDispatch* dispatch = nullptr);
+  int dispatchLocked(tsd_ctx* ctx, const std::vector<int32_t>& seeds, ExploreDispatch* d);
 
   std::shared_ptr<rclcpp::Node> _node;
   std::vector<Member> _members;

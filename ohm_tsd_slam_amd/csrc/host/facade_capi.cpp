@@ -30,6 +30,7 @@ struct tsd_fleet
   std::vector<tsd_node*> nodes;
   std::vector<tsd_frontier> frontiers;    // the last tsd_fleet_frontiers
   ExplorePlan plan;                       // the last tsd_fleet_explore_plan
+  ExploreDispatch dispatch;               // the last tsd_fleet_explore_dispatch
   ThreadGridGroup* group = nullptr;
   obvious::TsdGrid* fused = nullptr;      // the fleet's own grid: the TSD-level fusion of the nodes' grids (created by the first fusion)
 };
@@ -857,6 +858,57 @@ int tsd_fleet_explore_assign(tsd_fleet* f, double view_radius_m, unsigned gain_w
     return TSD_E_ARG;
   return f->group->exploreAssign(f->plan.goals.data(), f->plan.goals.size(), view_radius_m, gain_weight, unknown_depth, goal_of_robot, picked,
                                  rounds, radius_cells);
+}
+
+// Frontiers, a field per node, the goal matrix, the assignment across nodes and each node's waypoints in one call on the merged map
+// published last (ThreadGridGroup::exploreDispatch), kept for tsd_fleet_explore_dispatch_fetch.  counts: the frontiers, the nodes, the
+// rounds, the view radius and the look-ahead in cells, the seeds used; seeds_out: 2 int32 per node; origin_cs as tsd_fleet_frontiers.
+int tsd_fleet_explore_dispatch(tsd_fleet* f, unsigned min_size, double view_radius_m, unsigned gain_weight, int unknown_depth, double lookahead_m,
+                               unsigned slack, int max_len, int max_way, int* counts, tsd_route_fields_info* info, int32_t* seeds_out, double* origin_cs)
+{
+  if(!f || !f->group || !counts || !info)
+    return TSD_E_ARG;
+  ExploreDispatch& d = f->dispatch;
+  d.frames = 0;
+  d.viewRadius = view_radius_m;
+  d.lookahead = lookahead_m;
+  d.gainWeight = gain_weight;
+  d.slack = slack;
+  d.unknownDepth = unknown_depth;
+  d.maxLen = max_len;
+  d.maxWay = max_way;
+  const std::vector<double> xy = fleet_grid_xy(f);
+  const int rc = f->group->exploreDispatch(xy.data(), min_size ? min_size : 1u, &d, seeds_out, origin_cs);
+  if(rc != TSD_OK)
+    return rc;
+  counts[0] = static_cast<int>(d.frontiers.size());
+  counts[1] = static_cast<int>(f->nodes.size());
+  counts[2] = d.rounds;
+  counts[3] = d.radiusCells;
+  counts[4] = d.lookaheadCells;
+  counts[5] = d.seedsUsed;
+  *info = d.fields;
+  return TSD_OK;
+}
+
+// The result of the last tsd_fleet_explore_dispatch: rec [frontiers], goals [nodes * frontiers], goal_of_robot and picked [nodes],
+// way [nodes * max_way], way_info [nodes]; each pointer may be NULL.  TSD_E_ARG without a result and once the merged map has been
+// published again: the result is then of a map that is no longer the published one.
+int tsd_fleet_explore_dispatch_fetch(tsd_fleet* f, tsd_frontier* rec, tsd_route_goal* goals, int32_t* goal_of_robot, tsd_view_gain* picked,
+                                     uint32_t* way, tsd_waypoint_info* way_info)
+{
+  if(!f || !f->group)
+    return TSD_E_ARG;
+  const ExploreDispatch& d = f->dispatch;
+  if(d.frames == 0 || d.frames != f->group->frames())
+    return TSD_E_ARG;
+  if(rec && !d.frontiers.empty()) std::memcpy(rec, d.frontiers.data(), d.frontiers.size() * sizeof(tsd_frontier));
+  if(goals && !d.goals.empty()) std::memcpy(goals, d.goals.data(), d.goals.size() * sizeof(tsd_route_goal));
+  if(goal_of_robot) std::memcpy(goal_of_robot, d.goalOfRobot.data(), d.goalOfRobot.size() * sizeof(int32_t));
+  if(picked) std::memcpy(picked, d.picked.data(), d.picked.size() * sizeof(tsd_view_gain));
+  if(way) std::memcpy(way, d.way.data(), d.way.size() * sizeof(uint32_t));
+  if(way_info) std::memcpy(way_info, d.wayInfo.data(), d.wayInfo.size() * sizeof(tsd_waypoint_info));
+  return TSD_OK;
 }
 
 // The merged plan's paths straightened into waypoints (ThreadGridGroup::exploreWaypoints), as tsd_node_explore_waypoints.

@@ -323,8 +323,9 @@ struct tsd_ctx {
   // routes (route.hip: tsd_route_dev / _frame / _goals / _trace / _dev_ptrs).  Scratch of the kernels and the last result, allocated on
   // first use, grown on demand and kept.  Every call waits for its own work, so nothing of this is ever in flight between calls
   struct Route {
-    uint32_t* d_key = nullptr; uint8_t* d_w = nullptr; size_t cells = 0;          // the key image; the cells' weights (0: not traversable)
-    uint8_t* d_act = nullptr; size_t tiles = 0;                                   // [2][tiles]: a tile works in the even / odd rounds
+    uint32_t* d_key = nullptr; size_t keys = 0;                                   // the key images, [layers][cells of the call]
+    uint8_t* d_w = nullptr; size_t cells = 0;                                     // the cells' weights (0: not traversable)
+    uint8_t* d_act = nullptr; size_t tiles = 0;                                   // [2][layers][tiles of the call]: a tile works in the even / odd rounds
     tsd_route_goal* d_goal = nullptr; size_t goals = 0;
     uint32_t* d_path = nullptr; uint32_t* h_path = nullptr; size_t path_words = 0, h_path_words = 0;   // goal cells, lengths, paths; h_path pinned
     uint32_t* d_res = nullptr; uint32_t* h_res = nullptr;                         // the call's counters; h_res pinned
@@ -332,9 +333,14 @@ struct tsd_ctx {
     hipStream_t stream = nullptr;                                                 // the stream the result was made on: goals and paths follow it
     bool valid = false;                                                           // the last result (false: none)
     int W = 0, H = 0, n_goals = -1;
-    int sweeps = 0;                                                               // tsd_debug_set_route_sweeps (0: the default)
+    int layers = 1;                                                               // key images in d_key, `cells` apart (route: always 1)
+    int sweeps = 0;                                                               // tsd_debug_set_route_sweeps (0: the default; route's holds for both)
     long long tile_visits = 0; int host_waits = 0;
   } route;
+  // fields (route.hip: tsd_route_fields_*): a second instance of the same result with one key image per seed.  d_key holds `layers`
+  // images (capacity `keys`, in keys), d_act [2][layers][tiles] (capacity `tiles`, in bytes), d_w one weight image (capacity
+  // `cells`), d_goal the goal matrix [layers][n_goals].  Neither instance touches the other's buffers
+  Route fields;
   // views (view.hip: tsd_view_gains / _claim / _claims_reset / _assign).  The candidates, their records and the pinned copies of both
   // (one capacity), and the claims image with the size it was reset at (cW == 0: none).  Allocated on first use, grown on demand and
   // kept.  Every call waits for its own work, so nothing of this is ever in flight between calls
@@ -384,7 +390,7 @@ struct tsd_ctx {
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;
   unsigned profile_every = 1;   // time every n-th launch of a selected kernel ("name/n" in tsd_profile_select)
-  unsigned profile_every_k[21] = {};   // a kernel's own period ("name:m"), 0 = the list's
+  unsigned profile_every_k[25] = {};   // a kernel's own period ("name:m"), 0 = the list's
   bool profile = false;
   std::map<std::string, tsd::KernelTimer> timers;
   std::vector<hipEvent_t> event_pool;
@@ -621,11 +627,13 @@ void surface_free(tsd_ctx* ctx);             // surface.hip: releases tsd_ctx::s
 void align_free(tsd_ctx* ctx);               // align.hip: releases tsd_ctx::align (tsd_destroy)
 void clearance_free(tsd_ctx* ctx);           // clearance.hip: releases tsd_ctx::clearance (tsd_destroy)
 void frontier_free(tsd_ctx* ctx);            // frontier.hip: releases tsd_ctx::frontier (tsd_destroy)
-void route_free(tsd_ctx* ctx);               // route.hip: releases tsd_ctx::route (tsd_destroy)
+void route_free(tsd_ctx* ctx);               // route.hip: releases tsd_ctx::route and ::fields (tsd_destroy)
 // route.hip: k_route_trace enqueued on the route result's stream, not waited for; where it leaves the goal cells, the lengths and the
 // paths ([g * max_len + j], goal first) in tsd_ctx::route's scratch
-struct RouteTrace { const uint32_t* d_goals; const int32_t* d_len; const uint32_t* d_paths; };
-int route_trace_enqueue(tsd_ctx* ctx, const uint32_t* goal_cells, int n_goals, int max_len, RouteTrace* out);
+const char* route_goal_layers_wrong(const tsd_ctx::Route& r, const uint8_t* goal_layers, int n_goals);   // nullptr, or why they are refused
+struct RouteTrace { const uint32_t* d_goals; const int32_t* d_len; const uint32_t* d_paths; const uint8_t* d_layers; };
+int route_trace_enqueue(tsd_ctx* ctx, tsd_ctx::Route& r, const uint32_t* goal_cells, const uint8_t* goal_layers, int n_goals, int max_len,
+                        RouteTrace* out);
 void view_free(tsd_ctx* ctx);                // view.hip: releases tsd_ctx::view (tsd_destroy)
 int8_t* frame_staged_map(const tsd_ctx* ctx);   // map_publish.hip: the frame staging's map (cells * cells int8), nullptr without a staging
 int launch_calibrate(tsd_ctx* ctx, double* t, double* w, size_t n);

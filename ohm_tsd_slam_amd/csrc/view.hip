@@ -358,4 +358,71 @@ int tsd_view_assign(tsd_ctx* ctx, const void* map_dev, int width, int height, in
   return TSD_OK;
 }
 
+int tsd_view_assign_fields(tsd_ctx* ctx, const void* map_dev, int width, int height, int stride, const tsd_view_params* params,
+                           const tsd_route_goal* goals, int n_frontiers, int n_robots, uint32_t gain_weight, int32_t* goal_of_robot,
+                           tsd_view_gain* picked, int* rounds)
+{
+  if (!ctx) return TSD_E_ARG;
+  if (const char* why = vw_params_wrong(params)) return set_error(ctx, TSD_E_ARG, (std::string("tsd_view_assign_fields: ") + why).c_str(), hipSuccess);
+  if (n_frontiers < 0 || n_frontiers > TSD_VIEW_MAX_CELLS || (n_frontiers > 0 && !goals) || n_robots < 1 || n_robots > TSD_FRONTIER_MAX_SEEDS ||
+      !goal_of_robot || !rounds)
+    return set_error(ctx, TSD_E_ARG, "tsd_view_assign_fields: n_frontiers outside 0 .. TSD_VIEW_MAX_CELLS, goals NULL, n_robots outside 1 .. "
+                                     "TSD_FRONTIER_MAX_SEEDS, or a NULL output", hipSuccess);
+  MapSource src{};
+  if (int rc = vw_map_source(ctx, "tsd_view_assign_fields", map_dev, width, height, stride, &src)) return rc;
+  if (int rc = map_source_enter(ctx, src)) return rc;
+  if (int rc = vw_claims_reset(ctx, src.stream, src.m.W, src.m.H)) return rc;        // (the round's first launch runs behind it)
+  tsd_view_params prm = *params;
+  prm.use_claims = 1;
+  for (int r = 0; r < n_robots; r++) {
+    goal_of_robot[r] = -1;
+    if (picked) picked[r] = tsd_view_gain{TSD_ROUTE_NONE, 0u, 0u, 0u};
+  }
+  struct Pair { int f, r; };
+  std::vector<Pair> remaining;                                                     // in ascending (f, r): the order of the tie
+  for (int f = 0; f < n_frontiers; f++)
+    for (int r = 0; r < n_robots; r++)
+      if (goals[(size_t)r * n_frontiers + f].cell != TSD_ROUTE_NONE) remaining.push_back(Pair{f, r});
+  std::vector<uint32_t> cells;
+  std::vector<tsd_view_gain> rec;
+  int n_rounds = 0;
+  while (!remaining.empty()) {
+    n_rounds++;
+    // every distinct cell of the remaining pairs once, in launches of at most TSD_VIEW_MAX_CELLS candidates
+    cells.clear();
+    for (const Pair& p : remaining) cells.push_back(goals[(size_t)p.r * n_frontiers + p.f].cell);
+    std::sort(cells.begin(), cells.end());
+    cells.erase(std::unique(cells.begin(), cells.end()), cells.end());
+    rec.resize(cells.size());
+    for (size_t at = 0; at < cells.size(); at += TSD_VIEW_MAX_CELLS) {
+      const int n = (int)std::min<size_t>(cells.size() - at, TSD_VIEW_MAX_CELLS);
+      if (int rc = vw_stage(ctx, cells.data() + at, n)) return rc;
+      if (int rc = vw_run(ctx, src, &prm, ctx->view.d_cells, n, true, false)) return rc;
+      std::memcpy(rec.data() + at, ctx->view.h_rec, (size_t)n * sizeof(tsd_view_gain));
+    }
+    const Pair* best = nullptr;
+    long long best_score = 0;
+    tsd_view_gain best_rec{};
+    for (const Pair& p : remaining) {                                              // (ascending (f, r): the first of a tie stays)
+      const tsd_route_goal& g = goals[(size_t)p.r * n_frontiers + p.f];
+      const tsd_view_gain& v = rec[(size_t)(std::lower_bound(cells.begin(), cells.end(), g.cell) - cells.begin())];
+      if (v.gain == 0) continue;                                                   // only pairs with a gain compete
+      const long long score = (long long)v.gain * (long long)gain_weight - (long long)g.dist;
+      if (!best || score > best_score) { best = &p; best_score = score; best_rec = v; }
+    }
+    if (!best) break;
+    const int f = best->f, r = best->r;
+    goal_of_robot[r] = f;
+    if (picked) picked[r] = best_rec;
+    // the claim uploads its one cell; it is waited for, so that the next round's staging does not write under the copy
+    if (int rc = vw_stage(ctx, &best_rec.cell, 1)) return rc;
+    if (int rc = vw_run(ctx, src, &prm, ctx->view.d_cells, 1, true, true)) return rc;
+    TSD_HIP_CHECK(ctx, hipStreamSynchronize(src.stream));
+    remaining.erase(std::remove_if(remaining.begin(), remaining.end(), [&](const Pair& q) { return q.r == r || q.f == f; }), remaining.end());
+  }
+  TSD_HIP_CHECK(ctx, hipStreamSynchronize(src.stream));                            // (the reset, where no round ran)
+  *rounds = n_rounds;
+  return TSD_OK;
+}
+
 }  // extern "C"

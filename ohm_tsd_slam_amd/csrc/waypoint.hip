@@ -1,8 +1,9 @@
-// waypoint.hip -- a traced path straightened into waypoints joined by straight drivable segments (tsd_route_waypoints of
-// include/tsd_hip.h, where the rule is written out).  All in integers.
+// waypoint.hip -- a traced path straightened into waypoints joined by straight drivable segments (tsd_route_waypoints and
+// tsd_route_fields_waypoints of include/tsd_hip.h, where the rule is written out).  All in integers.
 //
 // k_route_waypoints  one workgroup of 256 threads (four waves) per goal, launched behind k_route_trace on the same stream; it reads
-//                    the trace's path where the trace left it (goal first: driving index i is path word len - 1 - i).
+//                    the trace's path where the trace left it (goal first: driving index i is path word len - 1 - i), and the keys
+//                    of the layer the trace walked (layer_of_goal[g]; nullptr: layer 0 for every goal).
 //   window     Per anchor p_a the cells p_a .. p_hi (hi = min(a + lookahead, len - 1)) go into LDS as x | y << 16 (a side is at most
 //              32768) together with their d: 8 bytes per path cell, 8200 B at lookahead 1024.
 //   pairs      A step's cell is a closed form of the step's number, so every (candidate, step) pair is independent: a lane loads the
@@ -34,7 +35,6 @@ namespace tsd {
 
 constexpr int WP_THREADS = 256, WP_WAVES = WP_THREADS / 64;
 constexpr int WP_MAX = TSD_WAYPOINT_MAX_LOOKAHEAD;
-constexpr const char* WP_WHO = "tsd_route_waypoints";
 
 struct WpArgs {
   int W;                                             // the key image's width
@@ -80,11 +80,13 @@ __device__ __forceinline__ bool wp_step(const uint8_t* __restrict__ wimg, int W,
   return bad;
 }
 
+template <bool LAYERS>                                         // (false: layer 0 for every goal, layer_of_goal is not read)
 __global__ void __launch_bounds__(WP_THREADS)
 k_route_waypoints(const uint32_t* __restrict__ key, const uint8_t* __restrict__ wimg, WpArgs a, const uint32_t* __restrict__ goals,
-                  const int32_t* __restrict__ len, const uint32_t* __restrict__ paths, uint32_t* __restrict__ way,
-                  tsd_waypoint_info* __restrict__ info)
+                  const uint8_t* __restrict__ layer_of_goal, const int32_t* __restrict__ len, const uint32_t* __restrict__ paths,
+                  uint32_t* __restrict__ way, tsd_waypoint_info* __restrict__ info)
 {
+  if constexpr (LAYERS) key += (size_t)__builtin_amdgcn_readfirstlane((int)layer_of_goal[blockIdx.x]) * a.cells;   // (one value per workgroup: kept scalar)
   __shared__ uint32_t s_xy[WP_MAX + 1], s_d[WP_MAX + 1];       // the window: entry i is p_{a + i}
   __shared__ uint32_t s_recip[WP_MAX + 1];                     // by N
   __shared__ int s_best[2][WP_WAVES];                          // per wave its largest passing candidate (1: the traced step) ...
@@ -197,35 +199,30 @@ static const char* wp_args_wrong(const uint32_t* goal_cells, int n_goals, const 
   return nullptr;
 }
 
-}  // namespace tsd
-
-using namespace tsd;
-
-extern "C" {
-
-int tsd_route_waypoints(tsd_ctx* ctx, const uint32_t* goal_cells, int n_goals, const tsd_waypoint_params* params, uint32_t* way_host,
-                        tsd_waypoint_info* info_host)
+// The waypoints on instance r of the route result (tsd_ctx::route or ::fields); goal_layers: nullptr for the route entry.
+static int route_waypoints(tsd_ctx* ctx, tsd_ctx::Route& r, const char* who, const uint32_t* goal_cells, const uint8_t* goal_layers, int n_goals,
+                           const tsd_waypoint_params* params, uint32_t* way_host, tsd_waypoint_info* info_host)
 {
-  if (!ctx) return TSD_E_ARG;
-  tsd_ctx::Route& r = ctx->route;
-  if (const char* why = wp_args_wrong(goal_cells, n_goals, params, way_host, info_host)) return map_refused(ctx, WP_WHO, why);
-  if (!r.valid) return map_refused(ctx, WP_WHO, "no route result");
+  if (const char* why = wp_args_wrong(goal_cells, n_goals, params, way_host, info_host)) return map_refused(ctx, who, why);
+  if (!r.valid) return map_refused(ctx, who, "no route result");
+  if (&r == &ctx->fields)
+    if (const char* why = route_goal_layers_wrong(r, goal_layers, n_goals)) return map_refused(ctx, who, why);
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   // d_way / h_way: the records (four words each), then the waypoints
   const size_t ng = (size_t)n_goals, rec_words = ng * (sizeof(tsd_waypoint_info) / sizeof(uint32_t)), words = rec_words + ng * (size_t)params->max_way;
-  int rc = scratch_grow(ctx, WP_WHO, &r.d_way, &r.way_words, words, "the waypoints");
-  if (!rc) rc = scratch_grow(ctx, WP_WHO, &r.h_way, &r.h_way_words, words, "the waypoints' pinned copy", true);
+  int rc = scratch_grow(ctx, who, &r.d_way, &r.way_words, words, "the waypoints");
+  if (!rc) rc = scratch_grow(ctx, who, &r.h_way, &r.h_way_words, words, "the waypoints' pinned copy", true);
   if (rc == TSD_E_NOMEM) { r.valid = false; r.n_goals = -1; }        // out of memory takes the route result and its goals along, like the trace's
   if (rc) return rc;
   RouteTrace tr{};
-  if (int rc2 = route_trace_enqueue(ctx, goal_cells, n_goals, params->max_len, &tr)) return rc2;
+  if (int rc2 = route_trace_enqueue(ctx, r, goal_cells, goal_layers, n_goals, params->max_len, &tr)) return rc2;
   tsd_waypoint_info* d_info = reinterpret_cast<tsd_waypoint_info*>(r.d_way);
   uint32_t* d_ways = r.d_way + rec_words;
   const WpArgs a{r.W, (uint32_t)r.W * (uint32_t)r.H, params->lookahead, params->max_len, params->max_way, params->slack};
   {
     ScopedKernelTimer t(ctx, r.stream == ctx->stream ? "route_waypoints" : "", true);
-    hipLaunchKernelGGL(k_route_waypoints, dim3((unsigned)n_goals), dim3(WP_THREADS), 0, r.stream, r.d_key, r.d_w, a, tr.d_goals, tr.d_len, tr.d_paths,
-                       d_ways, d_info);
+    hipLaunchKernelGGL(tr.d_layers ? k_route_waypoints<true> : k_route_waypoints<false>, dim3((unsigned)n_goals), dim3(WP_THREADS), 0, r.stream,
+                       r.d_key, r.d_w, a, tr.d_goals, tr.d_layers, tr.d_len, tr.d_paths, d_ways, d_info);
   }
   TSD_HIP_CHECK(ctx, hipGetLastError());
   TSD_HIP_CHECK(ctx, hipMemcpyAsync(r.h_way, r.d_way, words * sizeof(uint32_t), hipMemcpyDeviceToHost, r.stream));
@@ -237,6 +234,26 @@ int tsd_route_waypoints(tsd_ctx* ctx, const uint32_t* goal_cells, int n_goals, c
     if (n) std::memcpy(way_host + g * (size_t)params->max_way, r.h_way + rec_words + g * (size_t)params->max_way, n * sizeof(uint32_t));
   }
   return TSD_OK;
+}
+
+}  // namespace tsd
+
+using namespace tsd;
+
+extern "C" {
+
+int tsd_route_waypoints(tsd_ctx* ctx, const uint32_t* goal_cells, int n_goals, const tsd_waypoint_params* params, uint32_t* way_host,
+                        tsd_waypoint_info* info_host)
+{
+  if (!ctx) return TSD_E_ARG;
+  return route_waypoints(ctx, ctx->route, "tsd_route_waypoints", goal_cells, nullptr, n_goals, params, way_host, info_host);
+}
+
+int tsd_route_fields_waypoints(tsd_ctx* ctx, const uint32_t* goal_cells, const uint8_t* goal_layers, int n_goals, const tsd_waypoint_params* params,
+                               uint32_t* way_host, tsd_waypoint_info* info_host)
+{
+  if (!ctx) return TSD_E_ARG;
+  return route_waypoints(ctx, ctx->fields, "tsd_route_fields_waypoints", goal_cells, goal_layers, n_goals, params, way_host, info_host);
 }
 
 }  // extern "C"

@@ -69,6 +69,9 @@ HOST_ABI = {
     "tsd_fleet_explore_assign": (C.c_int, [C.c_void_p, C.c_double, C.c_uint, C.c_int, C.c_void_p, C.c_void_p, _ip, _ip]),
     "tsd_node_explore_waypoints": (C.c_int, [C.c_void_p, C.c_double, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _ip]),
     "tsd_fleet_explore_waypoints": (C.c_int, [C.c_void_p, C.c_double, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _ip]),
+    "tsd_fleet_explore_dispatch": (C.c_int, [C.c_void_p, C.c_uint, C.c_double, C.c_uint, C.c_int, C.c_double, C.c_uint, C.c_int, C.c_int, _ip,
+                                             C.POINTER(capi.RouteFieldsInfo), C.c_void_p, _dp]),
+    "tsd_fleet_explore_dispatch_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_grid_lock": (None, [C.c_void_p]),
@@ -663,6 +666,60 @@ class SlamFleet:
             raise capi.TsdError(f"tsd_fleet_explore_assign failed ({rc})")
         return {"goal_of_robot": goal_of, "picked": picked, "rounds": rounds.value, "radius_cells": radius.value}
 
+    def explore_dispatch(self, view_radius_m: float, gain_weight: int, lookahead_m: float, slack=0, unknown_depth=0, min_size=1,
+                         max_len=4096, max_way=256) -> dict:
+        """Every node's next goal and the way to it in one call on the merged map published last, with one seed per node
+        (``frontiers()``'s seeds) and a cost-to-go field PER NODE: ``frontiers`` (as ``frontiers()`` returns them), ``goals`` (the
+        matrix, capi.ROUTE_GOAL_DTYPE of shape (nodes, frontiers): node r's cheapest cell of frontier f), ``goal_of_robot`` (a
+        frontier index per node, -1 for a node that gets none), ``goal`` (capi.ROUTE_GOAL_DTYPE per node: its row's entry of that
+        frontier, cell ROUTE_NONE for -1), ``picked`` (capi.VIEW_GAIN_DTYPE per node), ``rounds``, ``waypoints`` (per node an (n, 2)
+        array in metres, the node's own cell first and the goal last; empty for -1), ``waypoint_cells`` and ``waypoint_info``
+        (capi.WAYPOINT_INFO_DTYPE per node), ``fields`` (tsd_route_fields_info as a dict), ``radius_cells``, ``lookahead_cells``,
+        ``origin`` and ``resolution``.  The pair of node and frontier with the best gain * ``gain_weight`` - dist wins, node and
+        frontier leave, what the node will see is claimed; unlike ``explore_assign`` a node may be given a frontier another node is
+        nearer to.  Refused before the first merged map."""
+        n = len(self.nodes)
+        counts = (C.c_int * 6)()
+        info = capi.RouteFieldsInfo()
+        seeds = np.zeros(2 * capi.FRONTIER_MAX_SEEDS, dtype=np.int32)
+        origin_cs = np.zeros(3)
+        max_len, max_way = int(max_len), int(max_way)
+        rc = self.lib.tsd_fleet_explore_dispatch(self.h, int(min_size), float(view_radius_m), int(gain_weight), int(unknown_depth),
+                                                 float(lookahead_m), int(slack), max_len, max_way, counts, C.byref(info), seeds.ctypes.data,
+                                                 origin_cs.ctypes.data_as(_dp))
+        if rc != 0:
+            raise capi.TsdError(f"tsd_fleet_explore_dispatch failed ({rc}): no merged map published yet, or max_len / max_way < 1?")
+        nf = counts[0]
+        rec = np.zeros(nf, dtype=capi.FRONTIER_DTYPE)
+        goals = np.zeros((n, nf), dtype=capi.ROUTE_GOAL_DTYPE)
+        goal_of = np.full(n, -1, dtype=np.int32)
+        picked = np.zeros(n, dtype=capi.VIEW_GAIN_DTYPE)
+        way = np.zeros((n, max_way), dtype=np.uint32)
+        winfo = np.zeros(n, dtype=capi.WAYPOINT_INFO_DTYPE)
+        rc = self.lib.tsd_fleet_explore_dispatch_fetch(self.h, rec.ctypes.data, goals.ctypes.data, goal_of.ctypes.data, picked.ctypes.data,
+                                                       way.ctypes.data, winfo.ctypes.data)
+        if rc != 0:
+            raise capi.TsdError(f"tsd_fleet_explore_dispatch_fetch failed ({rc}): the merged map has been published again")
+        res, origin = float(origin_cs[2]), origin_cs[:2].copy()
+        width = self.merged_map_msg()["width"]
+        size = rec["size"].astype(np.float64)
+        cen = np.stack([(rec["sum_x"].astype(np.float64) / size + 0.5) * res + origin[0],
+                        (rec["sum_y"].astype(np.float64) / size + 0.5) * res + origin[1]], axis=1)
+        frontiers = {"records": rec, "centroids": cen, "seeds": [tuple(int(v) for v in seeds[2 * k:2 * k + 2]) for k in range(n)],
+                     "seeds_used": counts[5], "origin": origin, "resolution": res}
+        goal = np.zeros(n, dtype=capi.ROUTE_GOAL_DTYPE)
+        goal["cell"], goal["dist"], goal["seed"] = capi.ROUTE_NONE, capi.ROUTE_NONE, -1
+        cells, metres = [], []
+        for r in range(n):
+            if goal_of[r] >= 0:
+                goal[r] = goals[r, goal_of[r]]
+            c = way[r, :min(max(int(winfo["n_way"][r]), 0), max_way)].astype(np.int64)
+            cells.append(c.astype(np.uint32))
+            metres.append(np.stack([((c % width) + 0.5) * res + origin[0], ((c // width) + 0.5) * res + origin[1]], axis=-1).reshape(-1, 2))
+        return {"frontiers": frontiers, "goals": goals, "goal_of_robot": goal_of, "goal": goal, "picked": picked, "rounds": counts[2],
+                "waypoints": metres, "waypoint_cells": cells, "waypoint_info": winfo, "fields": info.as_dict(), "radius_cells": counts[3],
+                "lookahead_cells": counts[4], "origin": origin, "resolution": res}
+
     def merged_frames(self) -> int:
         return int(self.lib.tsd_fleet_merged_frames(self.h))
 
@@ -765,7 +822,8 @@ class GridView(capi.TsdGridDevice):
                "load_text", "color_image", "push_stats_total", "profile_reset", "profile_get", "profile_spread", "profile_samples", "tsdpdf_match",
                "relocalize", "debug_reloc_scores", "debug_reloc_peaks", "surface_extract", "surface_fetch", "surface_points",
                "surface_dev", "align_points", "debug_align_scores", "debug_align_peaks", "debug_align_sums",
-               "clearance_of", "costmap_begin", "frontiers_of", "frontiers", "route_of", "route", "route_goals", "route_paths")
+               "clearance_of", "costmap_begin", "frontiers_of", "frontiers", "route_of", "route", "route_goals", "route_paths",
+               "route_fields_of", "route_fields", "route_fields_goals", "route_fields_paths", "route_fields_waypoints")
 
     def __init__(self, ctx, node=None):  # noqa: D401 - does not call the base constructor on purpose
         self.lib = capi.load_library()
@@ -780,7 +838,8 @@ class GridView(capi.TsdGridDevice):
 
     # these also use the context's frontier scratch, which the node's ThreadGrid (and a fleet's group) use: the grid's frontierMutex
     # is taken first and held until the records and labels are fetched
-    _FRONTIER = ("frontiers_of", "frontiers", "route_of", "route", "route_goals", "route_paths")      # (the goals read the frontier result)
+    _FRONTIER = ("frontiers_of", "frontiers", "route_of", "route", "route_goals", "route_paths",      # (the goals read the frontier result)
+                 "route_fields_of", "route_fields", "route_fields_goals", "route_fields_paths", "route_fields_waypoints")
 
     def __getattribute__(self, name):
         attr = object.__getattribute__(self, name)
