@@ -857,6 +857,111 @@ int tsd_route_fields_dev_ptrs(tsd_ctx* ctx, const void** keys_dev, int* width, i
 /* As tsd_route_counts, over all layers: the workgroups that found their tile active, and the host's waits. */
 int tsd_route_fields_counts(tsd_ctx* ctx, long long* tile_visits, int* host_waits);
 
+/* ---- drive: the velocity of the next step -- arcs rolled out on the weight image and rated on a goal field --------- */
+/* For each robot a grid of (speed, turn) samples is rolled forward T time steps from the robot's pose; a sample whose arc leaves the
+ * traversable cells is refused, the others are rated by the cost-to-go at their end, and the best one is the command.  It works on
+ * the route result the context holds (tsd_drive_rollout) or on a layer of the fields result (tsd_drive_fields_rollout): the weight
+ * image w (0: not traversable) and the key image, d = key >> 4.  A key image holds the cost FROM its seeds, so to drive towards a
+ * goal the result must have been seeded AT the goal (the navigation potential).  In integers throughout (the kernel does no floating
+ * point), so a restatement agrees to the byte (tests/drive_ref.py).
+ *   directions     D[h] = (cx, cy), int32 Q16, h = 0 .. H - 1, H = TSD_DRIVE_HEADINGS, from tsd_drive_table: for h = 0 .. H/8
+ *                  cx = lrint(65536 cos(2 pi h / H)), cy = lrint(65536 sin(2 pi h / H)); every other entry follows from those by the
+ *                  octant symmetries -- D[h] = (cy, cx)[H/4 - h] for H/8 < h <= H/4, D[h] = (-cx, cy)[H/2 - h] for H/4 < h <= H/2,
+ *                  D[h] = -D[h - H/2] above -- so D[h + H/2] = -D[h], D[H/4] = (0, 65536) exactly, and only the first octant
+ *                  depends on libm.  Heading 0 looks along +x, H/4 along +y of the image
+ *   pose           the cell (x0, y0), the offset (fx, fy) inside it in Q16, each 0 .. 65535, the heading index h0 in 0 .. H - 1,
+ *                  and a layer (the route form ignores it)
+ *   samples        step_q16[V]: the step length per time step, 0 .. 65536 (at most one cell, so consecutive centre cells are
+ *                  neighbours or the same); turn[Wn]: the heading increment per time step, |t| <= H/8; T steps, 1 .. 256.  Sample
+ *                  (i, j) has the index i * Wn + j
+ *   trajectory     of sample (i, j) with s = step_q16[i], t = turn[j], for k = 1 .. T, products in 64 bits, >> arithmetic:
+ *                    h_k = (h0 + k t) mod H, non-negative
+ *                    X_k = X_{k-1} + ((s cx[h_k] + 32768) >> 16), X_0 = fx;   Y_k likewise with cy[h_k], Y_0 = fy
+ *                    the centre cell c_k = (x0 + (X_k >> 16), y0 + (Y_k >> 16));  c_0 = (x0, y0)
+ *   body           B points (bx, by) in Q16 cells in the robot's frame, x forward; 0 <= B <= 64, |bx|, |by| <= 64 * 65536.  Point b at
+ *                  step k lies at (X_k + ((bx cx[h_k] - by cy[h_k] + 32768) >> 16), Y_k + ((bx cy[h_k] + by cx[h_k] + 32768) >> 16));
+ *                  its cell is taken like the centre's
+ *   step k is refused   by the first of these that holds, in this order:
+ *                    1  c_k lies outside the map
+ *                    2  w[c_k] == 0
+ *                    3  c_k differs from c_{k-1} in x AND in y, and one of the two cells the step cuts, (c_{k-1}.x, c_k.y) and
+ *                       (c_k.x, c_{k-1}.y), has w == 0 (the routes' rule: ONE blocked corner refuses)
+ *                    4  for the lowest b whose cell lies outside the map or has w == 0
+ *                  and after step T:  5  key[c_T] == TSD_ROUTE_NONE on the sample's key image.
+ *                  The start pose itself is not tested (but c_1 is, also where it is the start's cell)
+ *   why            uint16 per sample: 0 where it is admissible, else (reason << 12) | k for the smallest refusing k with its first
+ *                  reason; k = T for reason 5
+ *   score          of an admissible sample, uint64: a_end d_end + a_nose d_nose + a_cost cost + a_turn |t|, with d_end = key[c_T] >> 4,
+ *                  cost = the sum over k = 1 .. T of w[c_k], and d_nose = key >> 4 at the cell of
+ *                  (X_T + ((nose_q16 cx[h_T] + 32768) >> 16), Y_T + ((nose_q16 cy[h_T] + 32768) >> 16)) where that cell lies inside
+ *                  the map and has a key, d_end + nose_miss otherwise.  nose_q16 in 0 .. 64 * 65536, the coefficients in 0 .. 255,
+ *                  nose_miss <= TSD_ROUTE_MAX_DIST.  The nose term makes a robot that faces away from its way turn on the spot:
+ *                  d_end alone cannot tell two rotations apart
+ *   choice         the minimum of (score << 16) | index over the admissible samples: the best score, among ties the lowest index
+ *                  -- the caller orders its lists by preference.  Without an admissible sample speed = turn = -1, score =
+ *                  TSD_DRIVE_NONE, end_cell = d_end = d_nose = TSD_ROUTE_NONE, cost = 0
+ * The result is defined by a minimum, not by a search order: it does not depend on how the work is scheduled. */
+#define TSD_DRIVE_HEADINGS   4096
+#define TSD_DRIVE_MAX_STEPS  256
+#define TSD_DRIVE_MAX_SPEEDS 64
+#define TSD_DRIVE_MAX_TURNS  129
+#define TSD_DRIVE_MAX_BODY   64
+#define TSD_DRIVE_MAX_ROBOTS 16
+#define TSD_DRIVE_NONE       0xFFFFFFFFFFFFFFFFull
+typedef struct {
+  int32_t  steps;               /* T: 1 .. TSD_DRIVE_MAX_STEPS */
+  int32_t  n_speeds;            /* V: 1 .. TSD_DRIVE_MAX_SPEEDS */
+  int32_t  n_turns;             /* Wn: 1 .. TSD_DRIVE_MAX_TURNS */
+  int32_t  n_body;              /* B: 0 .. TSD_DRIVE_MAX_BODY */
+  const int32_t* step_q16;      /* [V], host memory, each 0 .. 65536 */
+  const int32_t* turn;          /* [Wn], host memory, each |t| <= TSD_DRIVE_HEADINGS / 8 */
+  const int32_t* body_q16;      /* [B] pairs (bx, by), host memory; may be NULL where B == 0 */
+  int32_t  a_end, a_nose, a_cost, a_turn;      /* each 0 .. 255 */
+  int32_t  nose_q16;            /* 0 .. 64 * 65536 */
+  uint32_t nose_miss;           /* <= TSD_ROUTE_MAX_DIST */
+} tsd_drive_params;             /* 64 bytes */
+typedef struct {
+  int32_t x, y;                 /* the cell */
+  int32_t fx, fy;               /* the offset inside it, Q16: 0 .. 65535 */
+  int32_t heading;              /* 0 .. TSD_DRIVE_HEADINGS - 1 */
+  int32_t layer;                /* the fields form: 0 .. layers - 1; the route form ignores it */
+} tsd_drive_pose;               /* 24 bytes */
+typedef struct {
+  int32_t  speed, turn;         /* the chosen sample's indices i, j; -1 without an admissible sample */
+  int32_t  admissible;          /* the number of admissible samples */
+  uint32_t end_cell;            /* c_T as a linear index y * width + x */
+  uint32_t d_end, d_nose, cost;
+  uint32_t reserved;
+  uint64_t score;
+} tsd_drive_choice;             /* 40 bytes */
+/* The direction table, 2 * TSD_DRIVE_HEADINGS words: cx of heading h at table[2 h], cy at table[2 h + 1].  Host code, no GPU.
+ * TSD_E_ARG for a NULL table. */
+int tsd_drive_table(int32_t* table);
+/* The pose after n_steps steps of the rule's trajectory at step length step_q16 and heading increment `turn`, cell and offset
+ * renormalised (x = x0 + (X_n >> 16), fx = X_n & 65535), the heading h_n of the rule, the layer kept: the pose a controller should
+ * expect after it has executed the first steps of its arc.  out may be p.  Host code, no GPU.  TSD_E_ARG for a NULL pointer, an
+ * offset outside 0 .. 65535, a heading outside 0 .. TSD_DRIVE_HEADINGS - 1, |x| or |y| above 1 << 30, step_q16 outside 0 .. 65536,
+ * |turn| above TSD_DRIVE_HEADINGS / 8, n_steps outside 0 .. TSD_DRIVE_MAX_STEPS. */
+int tsd_drive_advance(const tsd_drive_pose* p, int step_q16, int turn, int n_steps, tsd_drive_pose* out);
+/* The choice of n_robots robots on the route result the context holds: choice_host[r]; where given, scores_host[r * V * Wn + index]
+ * (TSD_DRIVE_NONE where the sample is refused) and why_host[r * V * Wn + index]; nothing else is written.  One launch for all robots
+ * ("drive_rollout": one wave per sample, its lanes over 64 consecutive steps; the re-roll of each robot's winner for its record runs
+ * right behind it under the same name) on the stream of the route result, waited for, under the same lock as the frontier, route and
+ * view calls.  Scratch stays with the context and grows on demand: a repeated call of the same shape allocates nothing.  TSD_E_ARG,
+ * with the outputs and the context's results left as they were: no route result, a NULL params, poses, choice_host or list, a count
+ * or value outside the ranges above, a pose with its cell outside the map (a cell with w == 0 is legal), an offset outside
+ * 0 .. 65535 or a heading outside 0 .. TSD_DRIVE_HEADINGS - 1, n_robots outside 1 .. TSD_DRIVE_MAX_ROBOTS. */
+int tsd_drive_rollout(tsd_ctx* ctx, const tsd_drive_params* params, const tsd_drive_pose* poses, int n_robots,
+                      tsd_drive_choice* choice_host, uint64_t* scores_host /* or NULL */, uint16_t* why_host /* or NULL */);
+/* The same on the fields result: robot r reads the keys of layer poses[r].layer.  TSD_E_ARG also without a fields result and for a
+ * layer outside 0 .. layers - 1. */
+int tsd_drive_fields_rollout(tsd_ctx* ctx, const tsd_drive_params* params, const tsd_drive_pose* poses, int n_robots,
+                             tsd_drive_choice* choice_host, uint64_t* scores_host /* or NULL */, uint16_t* why_host /* or NULL */);
+/* The context's drive block on the device and its capacity in 32-bit words: the direction table in its first 2 * TSD_DRIVE_HEADINGS
+ * words, the last call's samples behind it.  Valid until a drive call that needs a larger block or tsd_destroy; a repeated call of
+ * the same shape leaves both as they are.  Each pointer may be NULL.  TSD_E_ARG before the first drive call. */
+int tsd_drive_dev_ptrs(tsd_ctx* ctx, const void** block_dev, unsigned long long* words);
+
 /* ---- views: what a scan from a cell would uncover, and who is about to see it ------------------------------------ */
 /* The expected information gain of candidate cells (exploration goals) and the coordination rule on top of it: what one robot is
  * about to see is no longer worth a visit by another.  Input: an int8 map on the context's device as for the frontiers and routes --
@@ -1210,6 +1315,7 @@ int tsd_fuse(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell_off_x
  * tsd_route_waypoints' launch behind its trace: "route_waypoints" (tsd_route_fields_waypoints' as well),
  * the same passes of tsd_route_fields_dev / _goals / _trace: "route_fields_init", "route_fields_relax", "route_fields_goals",
  * "route_fields_trace",
+ * tsd_drive_rollout's and tsd_drive_fields_rollout's launch: "drive_rollout",
  * and the launches of tsd_view_gains and tsd_view_claim on the context's stream: "view_gain", "view_claim". */
 int tsd_profile_enable(tsd_ctx* ctx, int on);
 /* restrict timing to a comma separated list of kernel names, or "all"; a "/n" suffix times every n-th

@@ -204,6 +204,36 @@ WAYPOINT_INFO_DTYPE = np.dtype([("len", "<i4"), ("n_way", "<i4"), ("cost", "<u4"
 assert WAYPOINT_INFO_DTYPE.itemsize == C.sizeof(WaypointInfo) == C.sizeof(WaypointParams) == 16
 
 
+DRIVE_HEADINGS = 4096
+DRIVE_MAX_STEPS = 256
+DRIVE_MAX_SPEEDS = 64
+DRIVE_MAX_TURNS = 129
+DRIVE_MAX_BODY = 64
+DRIVE_MAX_ROBOTS = 16
+DRIVE_NONE = 0xFFFFFFFFFFFFFFFF   # the score of a refused sample, and of a choice without an admissible one
+
+
+class DriveParams(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("n_speeds", C.c_int32), ("n_turns", C.c_int32), ("n_body", C.c_int32),
+                ("step_q16", C.POINTER(C.c_int32)), ("turn", C.POINTER(C.c_int32)), ("body_q16", C.POINTER(C.c_int32)),
+                ("a_end", C.c_int32), ("a_nose", C.c_int32), ("a_cost", C.c_int32), ("a_turn", C.c_int32),
+                ("nose_q16", C.c_int32), ("nose_miss", C.c_uint32)]
+
+
+class DrivePose(C.Structure):
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("fx", C.c_int32), ("fy", C.c_int32), ("heading", C.c_int32), ("layer", C.c_int32)]
+
+
+class DriveChoice(C.Structure):
+    _fields_ = [("speed", C.c_int32), ("turn", C.c_int32), ("admissible", C.c_int32), ("end_cell", C.c_uint32), ("d_end", C.c_uint32),
+                ("d_nose", C.c_uint32), ("cost", C.c_uint32), ("reserved", C.c_uint32), ("score", C.c_uint64)]
+
+
+DRIVE_POSE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("fx", "<i4"), ("fy", "<i4"), ("heading", "<i4"), ("layer", "<i4")])
+DRIVE_CHOICE_DTYPE = np.dtype([("speed", "<i4"), ("turn", "<i4"), ("admissible", "<i4"), ("end_cell", "<u4"), ("d_end", "<u4"),
+                               ("d_nose", "<u4"), ("cost", "<u4"), ("reserved", "<u4"), ("score", "<u8")])
+
+
 VIEW_MAX_RADIUS = 511
 VIEW_MAX_CELLS = 4096
 
@@ -448,6 +478,11 @@ ABI = {
     "tsd_route_fields_waypoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(WaypointParams), C.c_void_p, C.c_void_p]),
     "tsd_route_fields_dev_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), _ip, _ip, _ip]),
     "tsd_route_fields_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _ip]),
+    "tsd_drive_table": (C.c_int, [C.c_void_p]),
+    "tsd_drive_advance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tsd_drive_rollout": (C.c_int, [C.c_void_p, C.POINTER(DriveParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsd_drive_fields_rollout": (C.c_int, [C.c_void_p, C.POINTER(DriveParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsd_drive_dev_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong)]),
     "tsd_view_assign_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_int,
                                          C.c_uint32, C.c_void_p, C.c_void_p, _ip]),
     "tsd_view_gains": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_void_p]),
@@ -537,7 +572,8 @@ def load_library(path: str | None = None):
                           ("tsd_frontier_params", FrontierParams), ("tsd_route_params", RouteParams),
                           ("tsd_route_info", RouteInfo), ("tsd_route_goal", RouteGoal), ("tsd_route_fields_info", RouteFieldsInfo),
                           ("tsd_view_params", ViewParams), ("tsd_view_gain", ViewGain),
-                          ("tsd_waypoint_params", WaypointParams), ("tsd_waypoint_info", WaypointInfo)):
+                          ("tsd_waypoint_params", WaypointParams), ("tsd_waypoint_info", WaypointInfo),
+                          ("tsd_drive_params", DriveParams), ("tsd_drive_pose", DrivePose), ("tsd_drive_choice", DriveChoice)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -563,6 +599,38 @@ def route_weights(free_max=0, max_weight=1) -> np.ndarray:
     if rc != 0:
         raise TsdError(f"tsd_route_weights refused (rc {rc}): free_max {free_max}, max_weight {max_weight}")
     return tab
+
+
+def drive_table() -> np.ndarray:
+    """tsd_drive_table: the direction table int32 (DRIVE_HEADINGS, 2), row h = (cx, cy) in Q16 (host code: no GPU)"""
+    lib = load_library()
+    tab = np.zeros((DRIVE_HEADINGS, 2), dtype=np.int32)
+    if lib.tsd_drive_table(tab.ctypes.data) != 0:
+        raise TsdError("tsd_drive_table refused")
+    return tab
+
+
+def drive_poses(poses) -> np.ndarray:
+    """poses as a DRIVE_POSE_DTYPE array: a structured array, or rows (x, y, fx, fy, heading[, layer])"""
+    if isinstance(poses, np.ndarray) and poses.dtype == DRIVE_POSE_DTYPE:
+        return np.ascontiguousarray(poses).ravel()
+    rows = np.asarray(list(poses), dtype=np.int64).reshape(len(poses), -1)
+    out = np.zeros(rows.shape[0], dtype=DRIVE_POSE_DTYPE)
+    for k, name in enumerate(DRIVE_POSE_DTYPE.names[:rows.shape[1]]):
+        out[name] = rows[:, k]
+    return out
+
+
+def drive_advance(pose, step_q16: int, turn: int, n_steps: int = 1) -> np.ndarray:
+    """tsd_drive_advance: the pose (one DRIVE_POSE_DTYPE record) after ``n_steps`` steps of the rule's trajectory (host code: no GPU)"""
+    lib = load_library()
+    p = drive_poses([pose] if not isinstance(pose, np.ndarray) else pose)
+    assert p.size == 1
+    out = np.zeros(1, dtype=DRIVE_POSE_DTYPE)
+    rc = lib.tsd_drive_advance(p.ctypes.data, int(step_q16), int(turn), int(n_steps), out.ctypes.data)
+    if rc != 0:
+        raise TsdError(f"tsd_drive_advance refused (rc {rc}): pose {p[0]}, step {step_q16}, turn {turn}, n_steps {n_steps}")
+    return out[0]
 
 
 def costmap_table(cell_size, radius, inscribed_radius_m=0.25, cost_scaling=10.0) -> np.ndarray:
@@ -1386,6 +1454,61 @@ class TsdGridDevice:
         self.last_rc = rc
         self._check(rc, "tsd_route_waypoints")
         return [way[g, :min(max(int(n), 0), int(max_way))].copy() for g, n in enumerate(info["n_way"])], info
+
+    # ---- drive (tsd_drive_*): the next step's velocity from arcs rolled out on a route or fields result
+    @staticmethod
+    def drive_table() -> np.ndarray:
+        """tsd_drive_table: int32 (DRIVE_HEADINGS, 2)"""
+        return drive_table()
+
+    @staticmethod
+    def drive_advance(pose, step_q16: int, turn: int, n_steps: int = 1) -> np.ndarray:
+        """tsd_drive_advance: the pose after ``n_steps`` steps"""
+        return drive_advance(pose, step_q16, turn, n_steps)
+
+    def drive_dev_ptrs(self):
+        """tsd_drive_dev_ptrs: (the drive block on the device, its capacity in 32-bit words); the table is its first 8192 words"""
+        b, n = C.c_void_p(), C.c_ulonglong(0)
+        self._check(self.lib.tsd_drive_dev_ptrs(self.h, C.byref(b), C.byref(n)), "tsd_drive_dev_ptrs")
+        return b.value, n.value
+
+    @staticmethod
+    def _drive_params(steps, step_q16, turn, body, weights, nose_q16, nose_miss):
+        """(tsd_drive_params, the arrays it points into -- to be kept alive over the call)"""
+        s = np.ascontiguousarray(step_q16, dtype=np.int32).ravel()
+        t = np.ascontiguousarray(turn, dtype=np.int32).ravel()
+        b = np.zeros((0, 2), dtype=np.int32) if body is None else np.ascontiguousarray(body, dtype=np.int32).reshape(-1, 2)
+        p32 = C.POINTER(C.c_int32)
+        prm = DriveParams(int(steps), int(s.size), int(t.size), int(b.shape[0]), s.ctypes.data_as(p32), t.ctypes.data_as(p32),
+                          b.ctypes.data_as(p32) if b.shape[0] else None, *[int(w) for w in weights], int(nose_q16), int(nose_miss))
+        return prm, (s, t, b)
+
+    def _drive(self, fn, name, poses, steps, step_q16, turn, body, weights, nose_q16, nose_miss, want_scores):
+        prm, keep = self._drive_params(steps, step_q16, turn, body, weights, nose_q16, nose_miss)
+        p = drive_poses(poses)
+        n = prm.n_speeds * prm.n_turns
+        choice = np.zeros(p.size, dtype=DRIVE_CHOICE_DTYPE)
+        scores = np.zeros((p.size, prm.n_speeds, prm.n_turns), dtype=np.uint64) if want_scores else None
+        why = np.zeros((p.size, prm.n_speeds, prm.n_turns), dtype=np.uint16) if want_scores else None
+        rc = fn(self.h, C.byref(prm), p.ctypes.data, int(p.size), choice.ctypes.data, scores.ctypes.data if want_scores else None,
+                why.ctypes.data if want_scores else None)
+        self.last_rc = rc
+        self._check(rc, name)
+        return (choice, scores, why) if want_scores else choice
+
+    def drive_rollout(self, poses, steps, step_q16, turn, body=None, weights=(1, 1, 0, 0), nose_q16=0, nose_miss=0, want_scores=False):
+        """tsd_drive_rollout on the route result the context holds: per pose (x, y, fx, fy, heading) the best of the
+        len(step_q16) x len(turn) arcs of ``steps`` steps, as a structured array of DRIVE_CHOICE_DTYPE (speed and turn: indices into
+        the lists, -1 without an admissible arc).  weights: (a_end, a_nose, a_cost, a_turn); body: (bx, by) pairs in Q16 cells.
+        want_scores: (choice, scores uint64 (n, V, Wn) -- DRIVE_NONE where refused --, why uint16 (n, V, Wn))."""
+        return self._drive(self.lib.tsd_drive_rollout, "tsd_drive_rollout", poses, steps, step_q16, turn, body, weights, nose_q16, nose_miss,
+                           want_scores)
+
+    def drive_fields_rollout(self, poses, steps, step_q16, turn, body=None, weights=(1, 1, 0, 0), nose_q16=0, nose_miss=0,
+                             want_scores=False):
+        """tsd_drive_fields_rollout: the same on the fields result, pose r (x, y, fx, fy, heading, layer) on its layer's keys"""
+        return self._drive(self.lib.tsd_drive_fields_rollout, "tsd_drive_fields_rollout", poses, steps, step_q16, turn, body, weights,
+                           nose_q16, nose_miss, want_scores)
 
     # ---- fields (tsd_route_fields_*): one key image per seed
     def route_fields_dev_ptrs(self):

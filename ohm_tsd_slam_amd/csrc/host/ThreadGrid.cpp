@@ -27,6 +27,9 @@ ThreadGrid::ThreadGrid(obvious::TsdGrid* grid, const std::shared_ptr<rclcpp::Nod
     _frames(0),
     _updates(0),
     _planStamp(~(uint64_t)0),
+    _planSource(TSD_ROUTE_MAP),
+    _planMaxWeight(1),
+    _planRouteReplaced(false),
     _surfaces(0)
 {
   // (ThreadGrid.cpp:16-40)
@@ -412,7 +415,12 @@ int ThreadGrid::explorePlan(const int32_t* seedsXy, int n, uint32_t minSize, int
   _planStamp = ~(uint64_t)0;
   rc = routePlan(_grid.context(), nullptr, 0, 0, source, prm, maxLen, out);
   if(rc == TSD_OK)
+  {
     _planStamp = _frames + _updates;
+    _planSource = source;
+    _planMaxWeight = maxWeight;
+    _planRouteReplaced = false;
+  }
   return rc;
 }
 
@@ -490,8 +498,8 @@ int ThreadGrid::exploreWaypoints(const tsd_route_goal* goals, size_t n, double l
                                  tsd_waypoint_info* info, int* lookaheadCells)
 {
   std::lock_guard<std::mutex> lk(_publishMutex);
-  if(_planStamp != _frames + _updates)
-    return TSD_E_ARG;                  // no plan, or one of a map that has been published over
+  if(_planStamp != _frames + _updates || _planRouteReplaced)
+    return TSD_E_ARG;                  // no plan, one of a map that has been published over, or its field replaced by exploreDrive's
   tsd_waypoint_params prm;
   prm.lookahead = waypointLookaheadCells(lookahead, static_cast<double>(_grid.getCellSize()));
   prm.slack = slack;
@@ -501,6 +509,152 @@ int ThreadGrid::exploreWaypoints(const tsd_route_goal* goals, size_t n, double l
     *lookaheadCells = prm.lookahead;
   std::lock_guard<std::mutex> fl(_grid.frontierMutex());
   return routeWaypoints(_grid.context(), goals, n, prm, way, info);
+}
+
+// The rollout entry points are weak references like the routes'.
+#pragma weak tsd_drive_rollout
+#pragma weak tsd_drive_advance
+
+static const double kTwoPi = 6.283185307179586476925286766559;
+
+int driveSamples(double cellSize, const DriveRequest& q, DriveSamples* s)
+{
+  if(!s || !(cellSize > 0.0) || !(q.vMax > 0.0) || !(q.wMax >= 0.0) || !(q.horizon > 0.0) || !std::isfinite(q.vMax) || !std::isfinite(q.wMax) ||
+     !std::isfinite(q.horizon) || q.nSpeeds < 2 || q.nSpeeds > TSD_DRIVE_MAX_SPEEDS || (q.footprint.size() & 1u) ||
+     q.footprint.size() > 2u * TSD_DRIVE_MAX_BODY || !(q.nose >= 0.0) || q.noseMiss > TSD_ROUTE_MAX_DIST)
+    return TSD_E_ARG;
+  for(const int c : {q.aEnd, q.aNose, q.aCost, q.aTurn})
+    if(c < 0 || c > 255)
+      return TSD_E_ARG;
+  s->dt = cellSize / q.vMax;
+  const double steps = std::ceil(q.horizon / s->dt);
+  const int T = steps < 1.0 ? 1 : steps > (double)TSD_DRIVE_MAX_STEPS ? TSD_DRIVE_MAX_STEPS : static_cast<int>(steps);
+  const double turns = std::floor(q.wMax * s->dt * (double)TSD_DRIVE_HEADINGS / kTwoPi + 0.5);
+  if(turns > (double)(TSD_DRIVE_HEADINGS / 8) || 2.0 * turns + 1.0 > (double)TSD_DRIVE_MAX_TURNS)
+    return TSD_E_ARG;
+  s->step.clear();
+  for(int i = 0; i < q.nSpeeds; i++)
+    s->step.push_back(static_cast<int32_t>(std::lrint(65536.0 * (double)(q.nSpeeds - 1 - i) / (double)(q.nSpeeds - 1))));
+  s->turn.assign(1, 0);
+  for(int m = 1; m <= static_cast<int>(turns); m++)
+  {
+    s->turn.push_back(m);
+    s->turn.push_back(-m);
+  }
+  s->body.clear();
+  for(const double v : q.footprint)
+  {
+    const double cells = v / cellSize;
+    if(!(std::fabs(cells) <= 64.0))
+      return TSD_E_ARG;
+    s->body.push_back(static_cast<int32_t>(std::lrint(cells * 65536.0)));
+  }
+  const double nose = q.nose / cellSize;
+  if(!(nose <= 64.0))
+    return TSD_E_ARG;
+  tsd_drive_params& p = s->prm;
+  p.steps = T;
+  p.n_speeds = q.nSpeeds;
+  p.n_turns = static_cast<int32_t>(s->turn.size());
+  p.n_body = static_cast<int32_t>(s->body.size() / 2);
+  p.step_q16 = s->step.data();
+  p.turn = s->turn.data();
+  p.body_q16 = s->body.empty() ? nullptr : s->body.data();
+  p.a_end = q.aEnd; p.a_nose = q.aNose; p.a_cost = q.aCost; p.a_turn = q.aTurn;
+  p.nose_q16 = static_cast<int32_t>(std::lrint(nose * 65536.0));
+  p.nose_miss = q.noseMiss;
+  return TSD_OK;
+}
+
+bool drivePose(const double* originRes, const double* xyt, int width, int height, int layer, tsd_drive_pose* p)
+{
+  if(!std::isfinite(xyt[0]) || !std::isfinite(xyt[1]) || !std::isfinite(xyt[2]))
+    return false;
+  const double ux = (xyt[0] - originRes[0]) / originRes[2], uy = (xyt[1] - originRes[1]) / originRes[2];
+  const double cx = std::floor(ux), cy = std::floor(uy);
+  if(!(cx >= 0.0 && cx < (double)width && cy >= 0.0 && cy < (double)height))
+    return false;
+  p->x = static_cast<int32_t>(cx);
+  p->y = static_cast<int32_t>(cy);
+  p->fx = std::min(65535, std::max(0, static_cast<int>(std::floor((ux - cx) * 65536.0))));
+  p->fy = std::min(65535, std::max(0, static_cast<int>(std::floor((uy - cy) * 65536.0))));
+  const long long h = std::llrint(std::remainder(xyt[2], kTwoPi) * (double)TSD_DRIVE_HEADINGS / kTwoPi);
+  p->heading = static_cast<int32_t>(((h % TSD_DRIVE_HEADINGS) + TSD_DRIVE_HEADINGS) % TSD_DRIVE_HEADINGS);
+  p->layer = layer;
+  return true;
+}
+
+int driveAnswer(const DriveSamples& s, const double* originRes, int width, const tsd_drive_pose& pose, const tsd_drive_choice& c, DriveAnswer* out)
+{
+  if(!tsd_drive_advance || !out)
+    return TSD_E_ARG;
+  const double res = originRes[2];
+  out->choice = c;
+  tsd_drive_pose next = pose;
+  if(c.speed >= 0 && c.turn >= 0)
+  {
+    // host arithmetic on the chosen indices: a step of s cells takes dt, a turn of t headings per step likewise
+    out->v = (double)s.step[(size_t)c.speed] / 65536.0 * res / s.dt;
+    out->w = (double)s.turn[(size_t)c.turn] * kTwoPi / ((double)TSD_DRIVE_HEADINGS * s.dt);
+    out->endXy[0] = ((double)(c.end_cell % (uint32_t)width) + 0.5) * res + originRes[0];
+    out->endXy[1] = ((double)(c.end_cell / (uint32_t)width) + 0.5) * res + originRes[1];
+    if(tsd_drive_advance(&pose, s.step[(size_t)c.speed], s.turn[(size_t)c.turn], 1, &next) != TSD_OK)
+      return TSD_E_ARG;
+  }
+  else
+  {
+    out->v = out->w = 0.0;
+    out->endXy[0] = out->endXy[1] = std::nan("");
+  }
+  out->next[0] = ((double)next.x + (double)next.fx / 65536.0) * res + originRes[0];
+  out->next[1] = ((double)next.y + (double)next.fy / 65536.0) * res + originRes[1];
+  out->next[2] = (double)next.heading * kTwoPi / (double)TSD_DRIVE_HEADINGS;
+  return TSD_OK;
+}
+
+int ThreadGrid::exploreDrive(const tsd_route_goal& goal, const double* poseXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples)
+{
+  if(!tsd_drive_rollout || !tsd_drive_advance || !tsd_route_frame || !tsd_route_weights || !poseXyt || !out || !samples ||
+     goal.cell == TSD_ROUTE_NONE || goal.dist == TSD_ROUTE_NONE)
+    return TSD_E_ARG;
+  std::lock_guard<std::mutex> lk(_publishMutex);
+  if(_planStamp != _frames + _updates)
+    return TSD_E_ARG;                  // no plan, or one of a map that has been published over
+  double place[3];
+  mapPlacement(place);
+  const int W = static_cast<int>(_width), H = static_cast<int>(_height);
+  if(goal.cell >= (uint32_t)W * (uint32_t)H)
+    return TSD_E_ARG;
+  int rc = driveSamples(place[2], q, samples);
+  if(rc != TSD_OK)
+    return rc;
+  tsd_drive_pose pose;
+  if(!drivePose(place, poseXyt, W, H, 0, &pose))
+    return TSD_E_ARG;
+  uint8_t weights[100];
+  const int freeMax = _planSource == TSD_ROUTE_COSTMAP ? 98 : 0;
+  if(tsd_route_weights(freeMax, _planSource == TSD_ROUTE_COSTMAP ? _planMaxWeight : 1, weights) != TSD_OK)
+    return TSD_E_ARG;
+  const int32_t seed[2] = {static_cast<int32_t>(goal.cell % (uint32_t)W), static_cast<int32_t>(goal.cell / (uint32_t)W)};
+  tsd_route_params prm;
+  prm.free_max = freeMax;
+  prm.n_seeds = 1;
+  prm.seeds_xy = seed;
+  prm.weights = weights;
+  prm.limit = static_cast<uint32_t>(std::min<uint64_t>(TSD_ROUTE_MAX_DIST, (uint64_t)goal.dist + q.margin));
+  prm.max_rounds = 0;
+  std::lock_guard<std::mutex> fl(_grid.frontierMutex());
+  // the field seeded AT the goal (the navigation potential) takes the place of the plan's robot-seeded route result
+  _planRouteReplaced = true;
+  tsd_route_info info;
+  rc = tsd_route_frame(_grid.context(), _planSource, &prm, &info);
+  if(rc != TSD_OK)
+    return rc;
+  tsd_drive_choice choice;
+  rc = tsd_drive_rollout(_grid.context(), &samples->prm, &pose, 1, &choice, nullptr, nullptr);
+  if(rc != TSD_OK)
+    return rc;
+  return driveAnswer(*samples, place, W, pose, choice, out);
 }
 
 void ThreadGrid::mapPlacement(double* originRes)

@@ -52,6 +52,44 @@ int waypointLookaheadCells(double lookahead, double cellSize);
  *  TSD_E_ARG where the device library has no waypoints. */
 int routeWaypoints(tsd_ctx* ctx, const tsd_route_goal* goals, size_t n, const tsd_waypoint_params& prm, uint32_t* way, tsd_waypoint_info* info);
 
+/** What exploreDrive is asked (ThreadGrid::exploreDrive, ThreadGridGroup::exploreDrive): the robot's limits, its footprint and the
+ *  rollout's coefficients. */
+struct DriveRequest
+{
+  double vMax = 0.0, wMax = 0.0, horizon = 0.0;   // [m/s], [rad/s], [s]
+  int nSpeeds = 5;                                // V: v_max * i / (V - 1), the fastest first
+  std::vector<double> footprint;                  // pairs (x, y) [m] in the robot's frame, x forward; empty: the centre alone
+  int aEnd = 1, aNose = 1, aCost = 0, aTurn = 0;  // tsd_drive_params' coefficients
+  double nose = 0.0;                              // [m]
+  uint32_t noseMiss = 0;
+  uint32_t margin = 0;                            // added to the goal's dist for the field's limit
+};
+/** The sample lists made of a request at a cell size: dt = cellSize / vMax (the top speed is one cell per step), T = min(256,
+ *  ceil(horizon / dt)), the speeds vMax * i / (V - 1) fastest first, the turns 0, 1, -1, .. n, -n with n = round(wMax * dt * H / 2 pi). */
+struct DriveSamples
+{
+  std::vector<int32_t> step, turn, body;
+  tsd_drive_params prm;                           // points into the vectors
+  double dt = 0.0;
+};
+/** What exploreDrive answers per robot: the command, where its arc ends and the pose to expect after one step, in the map's frame. */
+struct DriveAnswer
+{
+  double v = 0.0, w = 0.0;                        // [m/s], [rad/s]; 0 without an admissible sample
+  double endXy[2] = {0.0, 0.0};                   // the end cell's centre [m]; NaN without an admissible sample
+  double next[3] = {0.0, 0.0, 0.0};               // x, y [m] and yaw [rad] after one step of the chosen arc (the pose itself without one)
+  tsd_drive_choice choice;
+};
+/** TSD_E_ARG for limits that are not positive and finite, V outside 2 .. TSD_DRIVE_MAX_SPEEDS, a turn list beyond TSD_DRIVE_HEADINGS / 8
+ *  or TSD_DRIVE_MAX_TURNS entries, more than TSD_DRIVE_MAX_BODY footprint points, a point or the nose beyond 64 cells, a coefficient
+ *  outside 0 .. 255. */
+int driveSamples(double cellSize, const DriveRequest& q, DriveSamples* s);
+/** A pose x, y [m], yaw [rad] in the map's frame (origin, resolution) as cell, Q16 offset and heading index; false for a pose that is
+ *  not finite or outside width x height. */
+bool drivePose(const double* originRes, const double* xyt, int width, int height, int layer, tsd_drive_pose* p);
+/** The answer of one robot from its choice: velocities from the chosen indices, the end cell in metres, tsd_drive_advance by one step. */
+int driveAnswer(const DriveSamples& s, const double* originRes, int width, const tsd_drive_pose& pose, const tsd_drive_choice& c, DriveAnswer* out);
+
 class ThreadGrid : public ThreadSLAM
 {
 public:
@@ -116,6 +154,14 @@ public:
    *  library has no waypoints. */
   int exploreWaypoints(const tsd_route_goal* goals, size_t n, double lookahead, uint32_t slack, int maxLen, int maxWay, uint32_t* way,
                        tsd_waypoint_info* info, int* lookaheadCells);
+  /** The velocity of the next step towards `goal` of the plan made last, for a robot at poseXyt (x, y [m], yaw [rad] in the map's
+   *  frame): a route call seeded at the goal's cell on the plan's source with the plan's weights (tsd_route_frame; limit: the goal's
+   *  dist plus q.margin), then tsd_drive_rollout with the lists of driveSamples.  The goal-seeded field REPLACES the plan's route
+   *  result on the context, so exploreWaypoints is refused from then on until the next explorePlan (the plan's goals and paths have
+   *  been fetched by then); exploreDrive itself may be called again.  Holds the locks explorePlan holds.  TSD_E_ARG without a plan,
+   *  once the map has been published again, for a goal without a cell, a pose outside the map, what driveSamples refuses, and where
+   *  the device library has no rollout. */
+  int exploreDrive(const tsd_route_goal& goal, const double* poseXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples);
   /** origin x, y and resolution of <node>/map: fixed by the parameters at construction, the same before and after a publication */
   void mapPlacement(double* originRes);
 
@@ -170,6 +216,8 @@ private:
   uint64_t _frames;
   uint64_t _updates;
   uint64_t _planStamp;           // _frames + _updates when explorePlan last succeeded (under _publishMutex; ~0: no plan)
+  int _planSource, _planMaxWeight;   // what the plan was made on: exploreDrive's field is made on the same
+  bool _planRouteReplaced;       // exploreDrive has put a goal-seeded field in the place of the plan's route result
   uint64_t _surfaces;
 };
 

@@ -332,6 +332,69 @@ int ThreadGridGroup::dispatchLocked(tsd_ctx* ctx, const std::vector<int32_t>& se
   return TSD_OK;
 }
 
+#pragma weak tsd_drive_fields_rollout
+
+int ThreadGridGroup::exploreDrive(const ExploreDispatch& d, const double* posesXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples)
+{
+  const size_t L = _members.size();
+  if(!tsd_drive_fields_rollout || !tsd_route_fields_dev || !posesXyt || !out || !samples || L < 1 || L > (size_t)TSD_DRIVE_MAX_ROBOTS ||
+     d.goalOfRobot.size() != L)
+    return TSD_E_ARG;
+  std::lock_guard<std::mutex> lk(_publishMutex);
+  if(d.frames == 0 || d.frames != _frames)
+    return TSD_E_ARG;                  // no dispatch, or one of a merged map that has been published over
+  double place[3];
+  {
+    std::lock_guard<std::mutex> m(_msgMutex);
+    place[0] = _occGrid->info.origin.position.x;
+    place[1] = _occGrid->info.origin.position.y;
+    place[2] = static_cast<double>(_occGrid->info.resolution);
+  }
+  const int W = static_cast<int>(_width), H = static_cast<int>(_height);
+  int rc = driveSamples(place[2], q, samples);
+  if(rc != TSD_OK)
+    return rc;
+  const size_t n = d.goals.size() / L;
+  std::vector<int32_t> seeds(2 * L, -1);
+  std::vector<tsd_drive_pose> poses(L);
+  uint32_t far = 0;
+  for(size_t r = 0; r < L; r++)
+  {
+    if(!drivePose(place, posesXyt + 3 * r, W, H, static_cast<int>(r), &poses[r]))
+      return TSD_E_ARG;
+    if(d.goalOfRobot[r] < 0 || (size_t)d.goalOfRobot[r] >= n)
+      continue;
+    const tsd_route_goal& g = d.goals[r * n + (size_t)d.goalOfRobot[r]];
+    if(g.cell == TSD_ROUTE_NONE || g.cell >= (uint32_t)W * (uint32_t)H)
+      continue;
+    seeds[2 * r] = static_cast<int32_t>(g.cell % (uint32_t)W);
+    seeds[2 * r + 1] = static_cast<int32_t>(g.cell / (uint32_t)W);
+    far = std::max(far, g.dist);
+  }
+  tsd_route_params rp;
+  rp.free_max = 0;
+  rp.n_seeds = static_cast<int32_t>(L);
+  rp.seeds_xy = seeds.data();
+  rp.weights = nullptr;
+  rp.limit = static_cast<uint32_t>(std::min<uint64_t>(TSD_ROUTE_MAX_DIST, (uint64_t)far + q.margin));
+  rp.max_rounds = 0;
+  std::vector<tsd_drive_choice> choice(L);
+  {
+    // as for the dispatch: member 0's context and stream carry the call
+    std::lock_guard<std::mutex> fl(_members[0].grid->frontierMutex());
+    std::lock_guard<std::mutex> g(_members[0].grid->mutex());
+    tsd_ctx* ctx = _members[0].grid->context();
+    tsd_route_fields_info info;
+    // layer r seeded AT member r's goal: this replaces the dispatch's robot-seeded fields result, whose answers have been fetched
+    rc = tsd_route_fields_dev(ctx, tsd_group_map_dev(_group), W, H, W, &rp, &info);
+    if(rc == TSD_OK)
+      rc = tsd_drive_fields_rollout(ctx, &samples->prm, poses.data(), static_cast<int>(L), choice.data(), nullptr, nullptr);
+  }
+  for(size_t r = 0; r < L && rc == TSD_OK; r++)
+    rc = driveAnswer(*samples, place, W, poses[r], choice[r], out + r);
+  return rc;
+}
+
 #pragma weak tsd_view_assign
 
 int ThreadGridGroup::exploreAssign(const tsd_route_goal* goals, size_t n, double viewRadius, uint32_t gainWeight, int unknownDepth,

@@ -18,6 +18,9 @@ namespace ohm_tsd_slam
 {
 
 struct ExplorePlan;      // ThreadGrid.h
+struct DriveRequest;
+struct DriveSamples;
+struct DriveAnswer;
 
 /** What ThreadGridGroup::exploreDispatch is asked and what it answers. */
 struct ExploreDispatch
@@ -115,6 +118,14 @@ public:
    *  publication, for a negative unknownDepth, for more than TSD_FRONTIER_MAX_SEEDS members or TSD_VIEW_MAX_CELLS frontiers, and where
    *  the device library has no fields. */
   int exploreDispatch(const double* gridXy, uint32_t minSize, ExploreDispatch* d, int32_t* seedsXy, double* originCs);
+  /** The velocity of every member's next step towards the goal the dispatch `d` gave it, for members at posesXyt (x, y [m], yaw [rad]
+   *  per member in the merged map's frame): one fields call on the merged map seeded at the members' goal cells (tsd_route_fields_dev:
+   *  unit weights, free_max 0 as exploreDispatch plans; limit: the largest goal dist plus q.margin; a member without a goal gets a
+   *  seed outside the map, a layer without keys and no command), then one tsd_drive_fields_rollout, member r on layer r.  The
+   *  goal-seeded layers REPLACE the robot-seeded fields result of the dispatch on member 0's context; the dispatch's answers have been
+   *  fetched by then.  Holds the locks explorePlan holds.  TSD_E_ARG for a dispatch of another publication, a pose outside the map,
+   *  what driveSamples refuses, and where the device library has no rollout. */
+  int exploreDrive(const ExploreDispatch& d, const double* posesXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples);
   size_t members(void) const { return _members.size(); }
 
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }

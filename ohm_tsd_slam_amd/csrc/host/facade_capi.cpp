@@ -655,6 +655,61 @@ int tsd_node_explore_waypoints(tsd_node* n, double lookahead_m, unsigned slack, 
                                          lookahead_cells);
 }
 
+// what the drive entries take beside the poses: limits [v_max, w_max, horizon_s, nose_m], ints [n_speeds, a_end, a_nose, a_cost,
+// a_turn, nose_miss, margin], the footprint as n_foot pairs (x, y) [m]
+static bool drive_request(const double* limits, const int* ints, const double* footprint_xy, int n_foot, DriveRequest* q)
+{
+  if(!limits || !ints || n_foot < 0 || (n_foot > 0 && !footprint_xy) || ints[5] < 0 || ints[6] < 0)
+    return false;
+  q->vMax = limits[0]; q->wMax = limits[1]; q->horizon = limits[2]; q->nose = limits[3];
+  q->nSpeeds = ints[0];
+  q->aEnd = ints[1]; q->aNose = ints[2]; q->aCost = ints[3]; q->aTurn = ints[4];
+  q->noseMiss = static_cast<uint32_t>(ints[5]);
+  q->margin = static_cast<uint32_t>(ints[6]);
+  q->footprint.assign(footprint_xy, footprint_xy + 2 * (size_t)n_foot);
+  return true;
+}
+
+// one robot's answer as eight doubles -- v, w, end x, end y, admissible, next x, next y, next yaw; the record itself goes to
+// `choice` --, and the call's shape as [T, V, Wn, B] with dt
+static void drive_answer(const DriveAnswer& a, double* out8, tsd_drive_choice* choice)
+{
+  out8[0] = a.v; out8[1] = a.w; out8[2] = a.endXy[0]; out8[3] = a.endXy[1]; out8[4] = (double)a.choice.admissible;
+  out8[5] = a.next[0]; out8[6] = a.next[1]; out8[7] = a.next[2];
+  if(choice)
+    *choice = a.choice;
+}
+
+static void drive_shape(const DriveSamples& s, int* shape4, double* dt)
+{
+  if(shape4)
+  {
+    shape4[0] = s.prm.steps; shape4[1] = s.prm.n_speeds; shape4[2] = s.prm.n_turns; shape4[3] = s.prm.n_body;
+  }
+  if(dt)
+    *dt = s.dt;
+}
+
+// The velocity of the next step towards goal `goal` of the plan made last (ThreadGrid::exploreDrive): pose_xyt x, y [m], yaw [rad] in
+// the map's frame; out8: v [m/s], w [rad/s], the end cell's centre x, y [m], the admissible samples, the pose after one step x, y,
+// yaw; choice, shape4 [T, V, Wn, B] and dt may be NULL.
+int tsd_node_explore_drive(tsd_node* n, int goal, const double* pose_xyt, const double* limits, const int* ints, const double* footprint_xy,
+                           int n_foot, double* out8, tsd_drive_choice* choice, int* shape4, double* dt)
+{
+  DriveRequest q;
+  if(!n || !n->gridThread || !pose_xyt || !out8 || goal < 0 || (size_t)goal >= n->plan.goals.size() ||
+     !drive_request(limits, ints, footprint_xy, n_foot, &q))
+    return TSD_E_ARG;
+  DriveAnswer a;
+  DriveSamples s;
+  const int rc = n->gridThread->exploreDrive(n->plan.goals[(size_t)goal], pose_xyt, q, &a, &s);
+  if(rc != TSD_OK)
+    return rc;
+  drive_answer(a, out8, choice);
+  drive_shape(s, shape4, dt);
+  return TSD_OK;
+}
+
 // <node>/get_map (ThreadGrid::getMapServCallBack): the last map with a fresh stamp (map_out layout); 1 if the service answered
 int tsd_node_get_map(tsd_node* n, int8_t* data_out, double* out12, char* frame_id, int cap)
 {
@@ -908,6 +963,25 @@ int tsd_fleet_explore_dispatch_fetch(tsd_fleet* f, tsd_frontier* rec, tsd_route_
   if(picked) std::memcpy(picked, d.picked.data(), d.picked.size() * sizeof(tsd_view_gain));
   if(way) std::memcpy(way, d.way.data(), d.way.size() * sizeof(uint32_t));
   if(way_info) std::memcpy(way_info, d.wayInfo.data(), d.wayInfo.size() * sizeof(tsd_waypoint_info));
+  return TSD_OK;
+}
+
+// Every node's next velocity towards the goal the last tsd_fleet_explore_dispatch gave it (ThreadGridGroup::exploreDrive): poses_xyt
+// three doubles per node in the merged map's frame; out8 eight doubles per node as tsd_node_explore_drive, choice one record per node.
+int tsd_fleet_explore_drive(tsd_fleet* f, const double* poses_xyt, const double* limits, const int* ints, const double* footprint_xy, int n_foot,
+                            double* out8, tsd_drive_choice* choice, int* shape4, double* dt)
+{
+  DriveRequest q;
+  if(!f || !f->group || !poses_xyt || !out8 || !drive_request(limits, ints, footprint_xy, n_foot, &q))
+    return TSD_E_ARG;
+  std::vector<DriveAnswer> a(f->nodes.size());
+  DriveSamples s;
+  const int rc = f->group->exploreDrive(f->dispatch, poses_xyt, q, a.data(), &s);
+  if(rc != TSD_OK)
+    return rc;
+  for(size_t r = 0; r < a.size(); r++)
+    drive_answer(a[r], out8 + 8 * r, choice ? choice + r : nullptr);
+  drive_shape(s, shape4, dt);
   return TSD_OK;
 }
 

@@ -341,6 +341,13 @@ struct tsd_ctx {
   // images (capacity `keys`, in keys), d_act [2][layers][tiles] (capacity `tiles`, in bytes), d_w one weight image (capacity
   // `cells`), d_goal the goal matrix [layers][n_goals].  Neither instance touches the other's buffers
   Route fields;
+  // drive (drive.hip: tsd_drive_rollout / tsd_drive_fields_rollout): one device block -- the direction table (uploaded when the block
+  // is made), then the call's inputs and outputs -- and its pinned copy without the table.  Grown on demand and kept; every call
+  // waits for its own work
+  struct Drive {
+    uint32_t* d_buf = nullptr; uint32_t* h_buf = nullptr; size_t words = 0, h_words = 0;
+    bool table_ready = false;                // the table has been uploaded into d_buf (cleared whenever d_buf is replaced)
+  } drive;
   // views (view.hip: tsd_view_gains / _claim / _claims_reset / _assign).  The candidates, their records and the pinned copies of both
   // (one capacity), and the claims image with the size it was reset at (cW == 0: none).  Allocated on first use, grown on demand and
   // kept.  Every call waits for its own work, so nothing of this is ever in flight between calls
@@ -390,7 +397,7 @@ struct tsd_ctx {
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;
   unsigned profile_every = 1;   // time every n-th launch of a selected kernel ("name/n" in tsd_profile_select)
-  unsigned profile_every_k[25] = {};   // a kernel's own period ("name:m"), 0 = the list's
+  unsigned profile_every_k[26] = {};   // a kernel's own period ("name:m"), 0 = the list's
   bool profile = false;
   std::map<std::string, tsd::KernelTimer> timers;
   std::vector<hipEvent_t> event_pool;
@@ -634,6 +641,7 @@ const char* route_goal_layers_wrong(const tsd_ctx::Route& r, const uint8_t* goal
 struct RouteTrace { const uint32_t* d_goals; const int32_t* d_len; const uint32_t* d_paths; const uint8_t* d_layers; };
 int route_trace_enqueue(tsd_ctx* ctx, tsd_ctx::Route& r, const uint32_t* goal_cells, const uint8_t* goal_layers, int n_goals, int max_len,
                         RouteTrace* out);
+void drive_free(tsd_ctx* ctx);               // drive.hip: releases tsd_ctx::drive (tsd_destroy)
 void view_free(tsd_ctx* ctx);                // view.hip: releases tsd_ctx::view (tsd_destroy)
 int8_t* frame_staged_map(const tsd_ctx* ctx);   // map_publish.hip: the frame staging's map (cells * cells int8), nullptr without a staging
 int launch_calibrate(tsd_ctx* ctx, double* t, double* w, size_t n);

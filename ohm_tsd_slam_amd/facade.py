@@ -72,6 +72,8 @@ HOST_ABI = {
     "tsd_fleet_explore_dispatch": (C.c_int, [C.c_void_p, C.c_uint, C.c_double, C.c_uint, C.c_int, C.c_double, C.c_uint, C.c_int, C.c_int, _ip,
                                              C.POINTER(capi.RouteFieldsInfo), C.c_void_p, _dp]),
     "tsd_fleet_explore_dispatch_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsd_node_explore_drive": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, C.c_int, _dp, C.c_void_p, _ip, _dp]),
+    "tsd_fleet_explore_drive": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, C.c_int, _dp, C.c_void_p, _ip, _dp]),
     "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_grid_lock": (None, [C.c_void_p]),
@@ -468,6 +470,24 @@ class SlamNode:
         return _waypoint_dict(lambda *a: self.lib.tsd_node_explore_waypoints(self.h, *a), self._plan_goals, self._plan_frame, lookahead_m,
                               slack, max_way, "tsd_node_explore_waypoints")
 
+    def explore_drive(self, goal: int, pose, v_max: float, w_max: float, horizon_s: float, footprint=None, n_speeds=5,
+                      weights=(1, 1, 0, 0), nose_m=0.0, nose_miss=0, margin=2000) -> dict:
+        """The velocity of the next step towards goal ``goal`` (an index into the goals of the plan made last) for a robot at
+        ``pose`` = (x, y [m], yaw [rad]) in the map's frame: a cost-to-go field seeded AT the goal's cell on the plan's source
+        (tsd_route_frame, limit: the goal's dist + ``margin``), then tsd_drive_rollout -- ``n_speeds`` speeds v_max * i / (V - 1) by
+        the turns 0, +-1 .. +-round(w_max * dt * 4096 / 2 pi) headings per step of dt = resolution / v_max, over
+        T = min(256, ceil(horizon_s / dt)) steps, every arc tested cell by cell with the ``footprint`` points ((x, y) [m] in the
+        robot's frame, x forward) and rated by ``weights`` = (a_end, a_nose, a_cost, a_turn) on the field at its end and ``nose_m``
+        ahead of it.  Returns ``v`` [m/s] and ``w`` [rad/s] (0 without an admissible arc: ``admissible`` == 0), ``end_xy`` (the arc's
+        end cell [m], NaN without one), ``next_pose`` (x, y, yaw after one step), ``choice`` (capi.DRIVE_CHOICE_DTYPE), ``steps``,
+        ``n_speeds``, ``n_turns``, ``n_body`` and ``dt``.  The goal-seeded field replaces the plan's route result on the device:
+        ``explore_waypoints`` is refused from then on until the next ``explore_plan``.  Refused without a plan, once the map has been
+        published again, for a goal without a cell, and where the turn list would exceed 129 entries."""
+        if getattr(self, "_plan_goals", None) is None:
+            raise capi.TsdError("explore_drive: no plan (explore_plan first)")
+        return _drive(lambda *a: self.lib.tsd_node_explore_drive(self.h, int(goal), *a), [pose], v_max, w_max, horizon_s, footprint, n_speeds,
+                      weights, nose_m, nose_miss, margin, "tsd_node_explore_drive")[0]
+
     def explore_gains(self, view_radius_m: float, unknown_depth=0) -> np.ndarray:
         """What each goal of the plan made last is worth: the capi.VIEW_GAIN_DTYPE records (cell, gain, unknown, visible), one per
         goal and in the goals' order, of a scanner standing on the goal and seeing ``view_radius_m`` far all around on the map the
@@ -572,6 +592,26 @@ def _plan_dict(call, fetch, width, max_len, what):
     return {"records": rec, "centroids": cen, "goals": goals, "goal_xy": goal_xy, "paths": paths, "path_lens": lens,
             "route": info.as_dict(), "seeds": [tuple(int(v) for v in seeds[2 * k:2 * k + 2]) for k in range(n_seeds.value)],
             "seeds_used": counts[2], "origin": origin, "resolution": res}
+
+
+def _drive(call, poses, v_max, w_max, horizon_s, footprint, n_speeds, weights, nose_m, nose_miss, margin, what):
+    """one explore_drive call for len(poses) robots: per robot a dict, the call's shape and dt shared by all"""
+    poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 3))
+    n = poses.shape[0]
+    limits = np.array([v_max, w_max, horizon_s, nose_m], dtype=np.float64)
+    ints = (C.c_int * 7)(int(n_speeds), *[int(w) for w in weights], int(nose_miss), int(margin))
+    foot = np.zeros((0, 2)) if footprint is None else np.ascontiguousarray(np.asarray(footprint, dtype=np.float64).reshape(-1, 2))
+    out = np.zeros((n, 8))
+    choice = np.zeros(n, dtype=capi.DRIVE_CHOICE_DTYPE)
+    shape, dt = (C.c_int * 4)(), C.c_double(0.0)
+    rc = call(poses.ctypes.data_as(_dp), limits.ctypes.data_as(_dp), ints, foot.ctypes.data_as(_dp) if foot.shape[0] else None,
+              int(foot.shape[0]), out.ctypes.data_as(_dp), choice.ctypes.data, shape, C.byref(dt))
+    if rc != 0:
+        raise capi.TsdError(f"{what} failed ({rc}): no plan or dispatch of the map published last, a pose outside the map, limits that are "
+                            "not positive, or a turn list beyond 129 entries (w_max * cell_size / v_max too large)?")
+    return [{"v": float(out[r, 0]), "w": float(out[r, 1]), "end_xy": out[r, 2:4].copy(), "admissible": int(out[r, 4]),
+             "next_pose": out[r, 5:8].copy(), "choice": choice[r], "steps": shape[0], "n_speeds": shape[1], "n_turns": shape[2],
+             "n_body": shape[3], "dt": dt.value} for r in range(n)]
 
 
 def _waypoint_dict(call, n, frame, lookahead_m, slack, max_way, what):
@@ -719,6 +759,18 @@ class SlamFleet:
         return {"frontiers": frontiers, "goals": goals, "goal_of_robot": goal_of, "goal": goal, "picked": picked, "rounds": counts[2],
                 "waypoints": metres, "waypoint_cells": cells, "waypoint_info": winfo, "fields": info.as_dict(), "radius_cells": counts[3],
                 "lookahead_cells": counts[4], "origin": origin, "resolution": res}
+
+    def explore_drive(self, poses, v_max: float, w_max: float, horizon_s: float, footprint=None, n_speeds=5, weights=(1, 1, 0, 0),
+                      nose_m=0.0, nose_miss=0, margin=2000) -> list:
+        """``SlamNode.explore_drive`` for every node at once, towards the goal the last ``explore_dispatch`` gave it: ``poses`` one
+        (x, y [m], yaw [rad]) per node in the merged map's frame; one fields call on the merged map seeded at the nodes' goal cells
+        (unit weights, as the dispatch plans), then one tsd_drive_fields_rollout, node r on layer r.  A list of one dict per node; a
+        node without a goal gets ``v`` = ``w`` = 0 and ``admissible`` == 0.  The goal-seeded layers replace the dispatch's fields
+        result on the device.  Refused without a dispatch and once the merged map has been published again."""
+        if len(poses) != len(self.nodes):
+            raise capi.TsdError("explore_drive: one pose per node")
+        return _drive(lambda *a: self.lib.tsd_fleet_explore_drive(self.h, *a), poses, v_max, w_max, horizon_s, footprint, n_speeds, weights,
+                      nose_m, nose_miss, margin, "tsd_fleet_explore_drive")
 
     def merged_frames(self) -> int:
         return int(self.lib.tsd_fleet_merged_frames(self.h))
