@@ -961,6 +961,50 @@ int tsd_drive_fields_rollout(tsd_ctx* ctx, const tsd_drive_params* params, const
  * words, the last call's samples behind it.  Valid until a drive call that needs a larger block or tsd_destroy; a repeated call of
  * the same shape leaves both as they are.  Each pointer may be NULL.  TSD_E_ARG before the first drive call. */
 int tsd_drive_dev_ptrs(tsd_ctx* ctx, const void** block_dev, unsigned long long* words);
+/* The fleet form: the choice of n_robots robots on the fields result as tsd_drive_fields_rollout makes it, but the robots decide one
+ * after the other and each one's arcs are rated against the arcs CHOSEN by those that decided before it (prioritised planning in
+ * space-time).  The trajectory, the reasons 1 .. 5, the score and the minimum are those of the rule above; one reason is added.
+ *   order          order[n_robots], a permutation of 0 .. n_robots - 1: order[0] decides first (rank 0)
+ *   parked         a pose with layer == -1: the robot takes no samples; its choice is the record without an admissible sample, its
+ *                  scores are TSD_DRIVE_NONE and its `why` 0; it stands at its pose for every k and counts as decided before
+ *                  order[0], whatever its place in `order`
+ *   positions      P_r(k) = ((x0 << 16) + X_k, (y0 << 16) + Y_k), int64, k = 0 .. T: the absolute Q16 position of robot r at step k of
+ *                  an arc; of a decided robot: of the arc it chose, its pose ((x0 << 16) + fx, (y0 << 16) + fy) for every k where
+ *                  it is parked or found no admissible sample.  All robots share T and the lists, so step k is one instant for all
+ *   distance       against a robot q decided before r (a parked one, or one of a lower rank), dx, dy = P_r(k) - P_q(k):
+ *                  D_k = dx^2 + dy^2 where |dx| < sep_q16 and |dy| < sep_q16, "far" otherwise -- larger than any number; the
+ *                  products stay below 2^47
+ *   step k is refused   (1 <= k <= T) by the first of 1, 2, 3, 4 above, and then by
+ *                    6  for some such q: D_k is not far, D_k < sep_q16^2, and D_k <= D_{k-1} (D_0 from the two poses).  The last
+ *                       clause is the way out: two robots that stand closer than the separation may still take arcs on which every
+ *                       step takes them further apart; without it neither could ever move
+ *                  and reason 5 stays behind step T.  The smallest refusing k wins with its first reason: why = (6 << 12) | k
+ *   tracks         where given, tracks_host[(r * (T + 1) + k) * 2 + {0, 1}] = P_r(k) of the arc robot r chose (its pose in every slot
+ *                  without one)
+ * With sep_q16 == 0, or with one robot, choices, scores and `why` equal tsd_drive_fields_rollout's byte for byte.  The robot of
+ * rank 0 depends on no other robot but the parked ones.  Every rank's choice is a minimum over its samples: the result does not
+ * depend on how the work is scheduled.  One launch rates every robot's arcs on the map as tsd_drive_fields_rollout does; then each
+ * rank takes two small launches on the same stream -- its samples against the tracks decided so far (a table read, a 64-bit product
+ * and the in-wave scan per lane, no map bytes) and the winner's record and track -- so ranks are ordered by kernel boundaries: no
+ * workgroup waits for another and the host waits once, at the end.  All of it is timed as "drive_fleet".  The block of
+ * tsd_drive_dev_ptrs serves this call too (it holds the map pass's per-sample results as well, so it is larger at the same shape).
+ * TSD_E_ARG, with the outputs and the context's results left as they were: what tsd_drive_fields_rollout refuses (but layer -1), a
+ * layer below -1, a NULL fleet or order, an order that is no permutation, sep_q16 outside 0 .. TSD_DRIVE_MAX_SEP. */
+#define TSD_DRIVE_MAX_SEP (128 * 65536)
+/* The key under each robot's pose on the fields result, for a priority by cost-to-go: togo_host[r] = the key of layer
+ * poses[r].layer at the cell (poses[r].x, poses[r].y) -- d = key >> 4, and the low bits hold the layer's seed index, so keys of
+ * different layers never tie --, TSD_ROUTE_NONE where the cell has no key and for a parked robot (layer -1).  One small launch and
+ * one copy back on the fields result's stream, waited for; offsets and headings are not read.  TSD_E_ARG: no fields result, a NULL
+ * pointer, n_robots outside 1 .. TSD_DRIVE_MAX_ROBOTS, a cell outside the map, a layer outside -1 .. layers - 1. */
+int tsd_drive_fields_togo(tsd_ctx* ctx, const tsd_drive_pose* poses, int n_robots, uint32_t* togo_host);
+typedef struct {
+  const int32_t* order;         /* [n_robots], host memory */
+  int32_t sep_q16;              /* 0 .. TSD_DRIVE_MAX_SEP */
+  int32_t reserved;
+} tsd_drive_fleet_params;       /* 16 bytes */
+int tsd_drive_fleet_rollout(tsd_ctx* ctx, const tsd_drive_params* params, const tsd_drive_fleet_params* fleet, const tsd_drive_pose* poses,
+                            int n_robots, tsd_drive_choice* choice_host, uint64_t* scores_host /* or NULL */, uint16_t* why_host /* or NULL */,
+                            int64_t* tracks_host /* or NULL */);
 
 /* ---- views: what a scan from a cell would uncover, and who is about to see it ------------------------------------ */
 /* The expected information gain of candidate cells (exploration goals) and the coordination rule on top of it: what one robot is
@@ -1315,7 +1359,7 @@ int tsd_fuse(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell_off_x
  * tsd_route_waypoints' launch behind its trace: "route_waypoints" (tsd_route_fields_waypoints' as well),
  * the same passes of tsd_route_fields_dev / _goals / _trace: "route_fields_init", "route_fields_relax", "route_fields_goals",
  * "route_fields_trace",
- * tsd_drive_rollout's and tsd_drive_fields_rollout's launch: "drive_rollout",
+ * tsd_drive_rollout's and tsd_drive_fields_rollout's launch: "drive_rollout", tsd_drive_fleet_rollout's launches: "drive_fleet",
  * and the launches of tsd_view_gains and tsd_view_claim on the context's stream: "view_gain", "view_claim". */
 int tsd_profile_enable(tsd_ctx* ctx, int on);
 /* restrict timing to a comma separated list of kernel names, or "all"; a "/n" suffix times every n-th

@@ -229,6 +229,12 @@ class DriveChoice(C.Structure):
                 ("d_nose", C.c_uint32), ("cost", C.c_uint32), ("reserved", C.c_uint32), ("score", C.c_uint64)]
 
 
+class DriveFleetParams(C.Structure):
+    """tsd_drive_fleet_params"""
+    _fields_ = [("order", C.POINTER(C.c_int32)), ("sep_q16", C.c_int32), ("reserved", C.c_int32)]
+
+
+DRIVE_MAX_SEP = 128 * 65536       # tsd_drive_fleet_rollout's largest separation, Q16 cells
 DRIVE_POSE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("fx", "<i4"), ("fy", "<i4"), ("heading", "<i4"), ("layer", "<i4")])
 DRIVE_CHOICE_DTYPE = np.dtype([("speed", "<i4"), ("turn", "<i4"), ("admissible", "<i4"), ("end_cell", "<u4"), ("d_end", "<u4"),
                                ("d_nose", "<u4"), ("cost", "<u4"), ("reserved", "<u4"), ("score", "<u8")])
@@ -482,6 +488,9 @@ ABI = {
     "tsd_drive_advance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tsd_drive_rollout": (C.c_int, [C.c_void_p, C.POINTER(DriveParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsd_drive_fields_rollout": (C.c_int, [C.c_void_p, C.POINTER(DriveParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsd_drive_fleet_rollout": (C.c_int, [C.c_void_p, C.POINTER(DriveParams), C.POINTER(DriveFleetParams), C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tsd_drive_fields_togo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tsd_drive_dev_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong)]),
     "tsd_view_assign_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_int,
                                          C.c_uint32, C.c_void_p, C.c_void_p, _ip]),
@@ -573,7 +582,8 @@ def load_library(path: str | None = None):
                           ("tsd_route_info", RouteInfo), ("tsd_route_goal", RouteGoal), ("tsd_route_fields_info", RouteFieldsInfo),
                           ("tsd_view_params", ViewParams), ("tsd_view_gain", ViewGain),
                           ("tsd_waypoint_params", WaypointParams), ("tsd_waypoint_info", WaypointInfo),
-                          ("tsd_drive_params", DriveParams), ("tsd_drive_pose", DrivePose), ("tsd_drive_choice", DriveChoice)):
+                          ("tsd_drive_params", DriveParams), ("tsd_drive_pose", DrivePose), ("tsd_drive_choice", DriveChoice),
+                          ("tsd_drive_fleet_params", DriveFleetParams)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -1509,6 +1519,39 @@ class TsdGridDevice:
         """tsd_drive_fields_rollout: the same on the fields result, pose r (x, y, fx, fy, heading, layer) on its layer's keys"""
         return self._drive(self.lib.tsd_drive_fields_rollout, "tsd_drive_fields_rollout", poses, steps, step_q16, turn, body, weights,
                            nose_q16, nose_miss, want_scores)
+
+    def drive_fleet_rollout(self, poses, steps, step_q16, turn, order, sep_q16, body=None, weights=(1, 1, 0, 0), nose_q16=0, nose_miss=0,
+                            want_scores=False, want_tracks=False):
+        """tsd_drive_fleet_rollout: tsd_drive_fields_rollout with the robots deciding in the order ``order`` (a permutation of their
+        indices, order[0] first), each against the arcs chosen before it: an arc that comes within ``sep_q16`` (Q16 cells, centre to
+        centre) of one of them without moving away from it is refused by reason 6.  A pose with layer -1 is a parked robot.  Returns
+        the choices, then (scores, why) with want_scores, then tracks int64 (n, steps + 1, 2) -- the absolute Q16 positions of each
+        robot's chosen arc, its pose in every slot without one -- with want_tracks."""
+        prm, keep = self._drive_params(steps, step_q16, turn, body, weights, nose_q16, nose_miss)
+        p = drive_poses(poses)
+        o = np.ascontiguousarray(order, dtype=np.int32).ravel()
+        if o.size != p.size:
+            raise TsdError(f"tsd_drive_fleet_rollout: {o.size} ranks for {p.size} robots")
+        fleet = DriveFleetParams(o.ctypes.data_as(C.POINTER(C.c_int32)), int(sep_q16), 0)
+        choice = np.zeros(p.size, dtype=DRIVE_CHOICE_DTYPE)
+        scores = np.zeros((p.size, prm.n_speeds, prm.n_turns), dtype=np.uint64) if want_scores else None
+        why = np.zeros((p.size, prm.n_speeds, prm.n_turns), dtype=np.uint16) if want_scores else None
+        tracks = np.zeros((p.size, int(steps) + 1, 2), dtype=np.int64) if want_tracks else None
+        rc = self.lib.tsd_drive_fleet_rollout(self.h, C.byref(prm), C.byref(fleet), p.ctypes.data, int(p.size), choice.ctypes.data,
+                                              scores.ctypes.data if want_scores else None, why.ctypes.data if want_scores else None,
+                                              tracks.ctypes.data if want_tracks else None)
+        self.last_rc = rc
+        self._check(rc, "tsd_drive_fleet_rollout")
+        out = (choice,) + ((scores, why) if want_scores else ()) + ((tracks,) if want_tracks else ())
+        return out if len(out) > 1 else choice
+
+    def drive_fields_togo(self, poses) -> np.ndarray:
+        """tsd_drive_fields_togo: uint32 per pose, the key of its layer of the fields result at its cell (ROUTE_NONE without one and
+        for a parked robot, layer -1) -- what a priority by cost-to-go sorts by"""
+        p = drive_poses(poses)
+        togo = np.zeros(p.size, dtype=np.uint32)
+        self._check(self.lib.tsd_drive_fields_togo(self.h, p.ctypes.data, int(p.size), togo.ctypes.data), "tsd_drive_fields_togo")
+        return togo
 
     # ---- fields (tsd_route_fields_*): one key image per seed
     def route_fields_dev_ptrs(self):

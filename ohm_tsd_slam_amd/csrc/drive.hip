@@ -169,6 +169,163 @@ k_drive_pick(const uint32_t* __restrict__ key, const uint8_t* __restrict__ wimg,
   if (lane == 0) choice[r] = tsd_drive_choice{i, j, (int32_t)count[r], o.end_cell, o.d_end, o.d_nose, o.cost, 0u, o.score};
 }
 
+// ---- the fleet form (tsd_drive_fleet_rollout): the ranks decide one after the other, ordered by kernel boundaries on one stream
+// k_drive_rollout    as above for the robots that are not parked (a compact pose list), into the block's map rows: every sample's
+//                    score and `why` by reasons 1 .. 5.  Its minimum and count go to words nobody reads.
+// k_fleet_init       one workgroup per robot: the robot's pose into every slot of its track; a parked robot's scores, `why` and choice.
+// k_fleet_sample     per rank: one wave per sample, the lanes over 64 consecutive steps as in dr_sample, but on the trajectory alone --
+//                    the table read, the product and the scan; no map byte.  It runs the steps before the map's first refusal (all T
+//                    for an admissible sample and for reason 5): per lane P(k) and P(k-1) (the lane below, or the carry) against
+//                    the tracks of the robots decided so far, which are read from the block (at most 16 x 257 x 16 bytes, read-only
+//                    in this launch and coalesced over the lanes: they stay in the caches, and a copy in LDS per workgroup of four
+//                    samples would read as much and add a barrier).  One ballot gives the round's first conflict.  Lane 0 stores the
+//                    final score and `why` and lowers the robot's minimum as k_drive_rollout does.
+// k_fleet_pick       per rank, one wave: the winner's record and its track over the pose's -- the trajectory, w at the centre cells and
+//                    the two keys; the winner is admissible, so no test is repeated and no body point walked.
+// `decided` is a bit per robot and a kernel argument, so a launch reads only tracks that launches before it have finished.
+constexpr long long DR_FAR = 1ll << 62;
+
+struct DrFleet { int R, sep; unsigned decided; };
+
+// D of the rule: far unless both differences are below sep in magnitude (so the products stay below 2^47)
+__device__ __forceinline__ long long dr_dist(long long ax, long long ay, longlong2 b, long long sep)
+{
+  const long long dx = ax - b.x, dy = ay - b.y;
+  return (dx > -sep && dx < sep && dy > -sep && dy < sep) ? dx * dx + dy * dy : DR_FAR;
+}
+
+// X_k, Y_k of the round's steps k = k0 + lane + 1 <= T (the carry cX, cY in a lane beyond T)
+__device__ __forceinline__ int2 dr_round(const int2* __restrict__ tab, const tsd_drive_pose& p, int s, int t, int T, int k0, int cX, int cY, int lane)
+{
+  const int k = k0 + lane + 1;
+  const bool act = k <= T;
+  const int2 d = tab[(p.heading + k * t) & (DR_H - 1)];
+  return make_int2(cX + dr_scan(act ? dr_q16((long long)s * d.x) : 0, lane), cY + dr_scan(act ? dr_q16((long long)s * d.y) : 0, lane));
+}
+
+__global__ void __launch_bounds__(DR_THREADS)
+k_fleet_init(DrArgs a, const tsd_drive_pose* __restrict__ poses, longlong2* __restrict__ tracks, unsigned long long* __restrict__ scores,
+             uint16_t* __restrict__ why, tsd_drive_choice* __restrict__ choice)
+{
+  const int r = (int)blockIdx.x, tid = (int)threadIdx.x, S = a.V * a.Wn;
+  const tsd_drive_pose p = poses[r];
+  const longlong2 at = make_longlong2(((long long)p.x << 16) + p.fx, ((long long)p.y << 16) + p.fy);
+  for (int k = tid; k <= a.T; k += DR_THREADS) tracks[(size_t)r * (a.T + 1) + k] = at;
+  if (p.layer >= 0) return;
+  for (int i = tid; i < S; i += DR_THREADS) { scores[(size_t)r * S + i] = DR_NONE; why[(size_t)r * S + i] = 0; }
+  if (tid == 0) choice[r] = tsd_drive_choice{-1, -1, 0, TSD_ROUTE_NONE, TSD_ROUTE_NONE, TSD_ROUTE_NONE, 0u, 0u, DR_NONE};
+}
+
+// Robot r (row c of the map pass) against the tracks of the robots in f.decided.
+__global__ void __launch_bounds__(DR_THREADS)
+k_fleet_sample(const int2* __restrict__ tab, DrArgs a, DrFleet f, int r, int c, const tsd_drive_pose* __restrict__ poses,
+               const int32_t* __restrict__ step, const int32_t* __restrict__ turn, const longlong2* __restrict__ tracks,
+               const unsigned long long* __restrict__ map_scores, const uint16_t* __restrict__ map_why, unsigned long long* __restrict__ best,
+               uint32_t* __restrict__ count, unsigned long long* __restrict__ scores, uint16_t* __restrict__ why)
+{
+  const int tid = (int)threadIdx.x, lane = tid & 63, S = a.V * a.Wn;
+  const int idx = (int)blockIdx.x * DR_WAVES + __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (idx >= S) return;
+  uint32_t w = map_why[(size_t)c * S + idx];
+  unsigned long long score = map_scores[(size_t)c * S + idx];
+  const uint32_t reason = w >> 12;
+  const int last = (reason >= 1 && reason <= 4) ? min((int)(w & 0xFFFu) - 1, a.T) : a.T;       // at the map's own step the map's reason goes first
+  if (f.decided != 0 && f.sep > 0) {
+    const tsd_drive_pose p = poses[r];
+    const int s = step[idx / a.Wn], t = turn[idx % a.Wn];
+    const long long bx = (long long)p.x << 16, by = (long long)p.y << 16, sep = f.sep, sep2 = sep * sep;
+    int cX = p.fx, cY = p.fy;
+    for (int k0 = 0; k0 < last; k0 += 64) {
+      const int k = k0 + lane + 1;
+      const int2 xy = dr_round(tab, p, s, t, last, k0, cX, cY, lane);
+      int qX = __shfl_up(xy.x, 1, 64), qY = __shfl_up(xy.y, 1, 64);                   // X_{k-1}, Y_{k-1}
+      if (lane == 0) { qX = cX; qY = cY; }
+      bool hit = false;
+      if (k <= last) {                                                                // (k <= T: slots k - 1 and k of a track exist)
+        for (unsigned m = f.decided & ((1u << f.R) - 1u); m != 0; m &= m - 1) {
+          const longlong2* tr = tracks + (size_t)__builtin_ctz(m) * (a.T + 1);
+          const long long dk = dr_dist(bx + xy.x, by + xy.y, tr[k], sep);
+          hit |= dk < sep2 && dk <= dr_dist(bx + qX, by + qY, tr[k - 1], sep);        // (far is above sep^2)
+        }
+      }
+      const unsigned long long bad = __ballot(hit);
+      if (bad) { w = (6u << 12) | (uint32_t)(k0 + __builtin_ctzll(bad) + 1); score = DR_NONE; break; }
+      const int e = min(last - k0, 64) - 1;
+      cX = __shfl(xy.x, e, 64); cY = __shfl(xy.y, e, 64);
+    }
+  }
+  if (lane == 0) {
+    scores[(size_t)r * S + idx] = score;
+    why[(size_t)r * S + idx] = (uint16_t)w;
+    if (w == 0) {
+      atomicMin(&best[r], (score << 16) | (unsigned long long)idx);
+      atomicAdd(&count[r], 1u);
+    }
+  }
+}
+
+// The winner of robot r: its record and its track.  The winner is admissible -- every step has passed every test in the map pass --
+// so nothing is tested again: the trajectory, w at the centre cells for the cost, the two keys.  (k_drive_pick's re-roll with dr_sample
+// walks the body points once more, a serial loop per lane; 16 of those one after the other were most of the chain's time at the limits.)
+__global__ void __launch_bounds__(64)
+k_fleet_pick(const uint32_t* __restrict__ key, const uint8_t* __restrict__ wimg, const int2* __restrict__ tab, DrArgs a, int r,
+             const tsd_drive_pose* __restrict__ poses, const int32_t* __restrict__ step, const int32_t* __restrict__ turn,
+             const unsigned long long* __restrict__ best, const uint32_t* __restrict__ count, tsd_drive_choice* __restrict__ choice,
+             longlong2* __restrict__ tracks)
+{
+  const int lane = (int)threadIdx.x;
+  const unsigned long long b = best[r];
+  const int idx = (int)(b & 0xFFFFull);
+  if (b == DR_NONE || idx >= a.V * a.Wn) {                     // (the same for every lane; the track stays the pose's)
+    if (lane == 0) choice[r] = tsd_drive_choice{-1, -1, 0, TSD_ROUTE_NONE, TSD_ROUTE_NONE, TSD_ROUTE_NONE, 0u, 0u, DR_NONE};
+    return;
+  }
+  const int i = idx / a.Wn, j = idx % a.Wn;
+  const tsd_drive_pose p = poses[r];
+  const int s = step[i], t = turn[j];
+  int cX = p.fx, cY = p.fy, wsum = 0;
+  for (int k0 = 0; k0 < a.T; k0 += 64) {
+    const int k = k0 + lane + 1;
+    const int2 xy = dr_round(tab, p, s, t, a.T, k0, cX, cY, lane);
+    if (k <= a.T) {
+      tracks[(size_t)r * (a.T + 1) + k] = make_longlong2(((long long)p.x << 16) + xy.x, ((long long)p.y << 16) + xy.y);
+      wsum += dr_w(wimg, a.W, a.H, p.x + (xy.x >> 16), p.y + (xy.y >> 16));
+    }
+    const int e = min(a.T - k0, 64) - 1;
+    cX = __shfl(xy.x, e, 64); cY = __shfl(xy.y, e, 64);
+  }
+  const uint32_t cost = (uint32_t)__shfl(wave_sum_i(wsum), 0, 64);
+  if (lane != 0) return;
+  // From here on this restates the end of dr_sample -- c_T's key, the nose cell, the d_nose fallback, the score -- and must change with
+  // it: dr_sample itself is left as it is so that the two older entries keep their code; tests/test_gpu_drive_fleet.py holds the two
+  // copies together byte for byte (sep 0 against tsd_drive_fields_rollout's choices).
+  const uint32_t* lkey = key + (size_t)p.layer * a.cells;
+  const int ex = p.x + (cX >> 16), ey = p.y + (cY >> 16);      // c_T: inside the map and with a key, or the sample were not admissible
+  const uint32_t end = (uint32_t)ey * (uint32_t)a.W + (uint32_t)ex;
+  const uint32_t ke = ((unsigned)ex < (unsigned)a.W && (unsigned)ey < (unsigned)a.H) ? lkey[end] : TSD_ROUTE_NONE;
+  const uint32_t d_end = ke >> 4;
+  const int2 d = tab[(p.heading + a.T * t) & (DR_H - 1)];
+  const int nx = p.x + ((cX + dr_q16((long long)a.nose * d.x)) >> 16), ny = p.y + ((cY + dr_q16((long long)a.nose * d.y)) >> 16);
+  uint32_t kn = TSD_ROUTE_NONE;
+  if ((unsigned)nx < (unsigned)a.W && (unsigned)ny < (unsigned)a.H) kn = lkey[(uint32_t)ny * (uint32_t)a.W + (uint32_t)nx];
+  const uint32_t d_nose = kn != TSD_ROUTE_NONE ? kn >> 4 : d_end + a.nose_miss;
+  const unsigned long long score = (unsigned long long)a.a_end * d_end + (unsigned long long)a.a_nose * d_nose +
+                                   (unsigned long long)a.a_cost * cost + (unsigned long long)a.a_turn * (uint32_t)abs(t);
+  choice[r] = tsd_drive_choice{i, j, (int32_t)count[r], end, d_end, d_nose, cost, 0u, score};
+}
+
+// The key under each robot's pose on its own layer (tsd_drive_fields_togo): one thread per robot; a parked robot has none.
+__global__ void __launch_bounds__(64)
+k_drive_togo(const uint32_t* __restrict__ key, int W, int H, uint32_t cells, int layers, int R, const tsd_drive_pose* __restrict__ poses,
+             uint32_t* __restrict__ togo)
+{
+  const int r = (int)threadIdx.x;
+  if (r >= R) return;
+  const tsd_drive_pose p = poses[r];
+  const bool in = (unsigned)p.x < (unsigned)W && (unsigned)p.y < (unsigned)H && (unsigned)p.layer < (unsigned)layers;
+  togo[r] = in ? key[(size_t)p.layer * cells + (uint32_t)p.y * (uint32_t)W + (uint32_t)p.x] : TSD_ROUTE_NONE;
+}
+
 // ---- the host's side of the rule
 static const int32_t* drive_table()
 {
@@ -194,7 +351,7 @@ static bool drive_pose_wrong(const tsd_drive_pose& p)
 }
 
 static const char* drive_args_wrong(const tsd_ctx::Route& r, bool layered, const tsd_drive_params* p, const tsd_drive_pose* poses, int n_robots,
-                                    const tsd_drive_choice* choice)
+                                    const tsd_drive_choice* choice, bool parked_ok = false)
 {
   if (!p) return "params is NULL";
   if (!poses) return "poses is NULL";
@@ -222,7 +379,8 @@ static const char* drive_args_wrong(const tsd_ctx::Route& r, bool layered, const
     const tsd_drive_pose& q = poses[i];
     if (q.x < 0 || q.x >= r.W || q.y < 0 || q.y >= r.H) return "a pose's cell lies outside the map";
     if (drive_pose_wrong(q)) return "a pose's offset is outside 0 .. 65535 or its heading outside 0 .. TSD_DRIVE_HEADINGS - 1";
-    if (layered && (q.layer < 0 || q.layer >= r.layers)) return "a pose's layer is outside 0 .. layers - 1";
+    if (layered && (q.layer < (parked_ok ? -1 : 0) || q.layer >= r.layers))
+      return parked_ok ? "a pose's layer is outside -1 .. layers - 1" : "a pose's layer is outside 0 .. layers - 1";
   }
   return nullptr;
 }
@@ -288,6 +446,137 @@ static int drive_rollout(tsd_ctx* ctx, tsd_ctx::Route& r, const char* who, const
   return TSD_OK;
 }
 
+// The fleet form on the fields result: the map pass for the robots that are not parked, then a launch pair per rank.
+static int drive_fleet_rollout(tsd_ctx* ctx, const tsd_drive_params* p, const tsd_drive_fleet_params* fl, const tsd_drive_pose* poses, int n_robots,
+                               tsd_drive_choice* choice_host, uint64_t* scores_host, uint16_t* why_host, int64_t* tracks_host)
+{
+  const char* who = "tsd_drive_fleet_rollout";
+  tsd_ctx::Route& r = ctx->fields;
+  if (const char* why = drive_args_wrong(r, true, p, poses, n_robots, choice_host, true)) return map_refused(ctx, who, why);
+  if (!fl) return map_refused(ctx, who, "fleet is NULL");
+  if (!fl->order) return map_refused(ctx, who, "order is NULL");
+  if (fl->sep_q16 < 0 || fl->sep_q16 > TSD_DRIVE_MAX_SEP) return map_refused(ctx, who, "sep_q16 is outside 0 .. TSD_DRIVE_MAX_SEP");
+  unsigned seen = 0;
+  for (int m = 0; m < n_robots; m++) {
+    const int32_t q = fl->order[m];
+    if (q < 0 || q >= n_robots || ((seen >> q) & 1u)) return map_refused(ctx, who, "order is no permutation of 0 .. n_robots - 1");
+    seen |= 1u << q;
+  }
+  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  // the block as drive_rollout's, with the compact poses of the robots that are not parked among the inputs, the tracks among the
+  // outputs, and behind the outputs what only the device reads: the map pass's scores and `why` per compact row, and the words its
+  // minimum and count go to
+  const size_t R = (size_t)n_robots, S = (size_t)p->n_speeds * p->n_turns, B = (size_t)p->n_body, T1 = (size_t)p->steps + 1;
+  const size_t tab_words = 2 * DR_H;
+  const size_t o_pose = 0, o_apose = o_pose + 6 * R, o_step = o_apose + 6 * R, o_turn = o_step + p->n_speeds;
+  const size_t o_body = (o_turn + p->n_turns + 1) & ~(size_t)1, o_best = (o_body + 2 * B + 1) & ~(size_t)1, o_count = o_best + 2 * R;
+  const size_t in_words = (o_count + R + 3) & ~(size_t)3;
+  const size_t o_choice = in_words, o_tracks = (o_choice + R * (sizeof(tsd_drive_choice) / 4) + 3) & ~(size_t)3;       // (16 bytes per slot)
+  const size_t o_scores = o_tracks + 4 * R * T1, o_why = o_scores + 2 * R * S, io_words = (o_why + (R * S + 1) / 2 + 1) & ~(size_t)1;
+  const size_t o_mscores = io_words, o_mwhy = o_mscores + 2 * R * S, o_mbest = (o_mwhy + (R * S + 1) / 2 + 1) & ~(size_t)1;
+  const size_t words = o_mbest + 2 * R + R;
+  tsd_ctx::Drive& dr = ctx->drive;
+  if (dr.words < tab_words + words) dr.table_ready = false;
+  int rc = scratch_grow(ctx, who, &dr.d_buf, &dr.words, tab_words + words, "the fleet rollout's samples");
+  if (!rc) rc = scratch_grow(ctx, who, &dr.h_buf, &dr.h_words, io_words, "the fleet rollout's pinned copy", true);
+  if (rc) return rc;
+  if (!dr.table_ready) {
+    TSD_HIP_CHECK(ctx, hipMemcpyAsync(dr.d_buf, drive_table(), tab_words * 4, hipMemcpyHostToDevice, r.stream));
+    dr.table_ready = true;
+  }
+  uint32_t* h = dr.h_buf;
+  std::memcpy(h + o_pose, poses, R * sizeof(tsd_drive_pose));
+  int row[TSD_DRIVE_MAX_ROBOTS], A = 0;                                // a robot's row in the map pass, -1: parked
+  unsigned parked = 0;
+  for (size_t i = 0; i < R; i++) {
+    if (poses[i].layer < 0) { row[i] = -1; parked |= 1u << i; continue; }
+    std::memcpy(h + o_apose + 6 * (size_t)A, poses + i, sizeof(tsd_drive_pose));
+    row[i] = A++;
+  }
+  std::memcpy(h + o_step, p->step_q16, (size_t)p->n_speeds * 4);
+  std::memcpy(h + o_turn, p->turn, (size_t)p->n_turns * 4);
+  if (B) std::memcpy(h + o_body, p->body_q16, 2 * B * 4);
+  std::memset(h + o_best, 0xFF, 2 * R * 4);
+  std::memset(h + o_count, 0, R * 4);
+  uint32_t* d = dr.d_buf + tab_words;
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d, h, in_words * 4, hipMemcpyHostToDevice, r.stream));
+  const DrArgs a{r.W, r.H, (uint32_t)r.W * (uint32_t)r.H, p->steps, p->n_speeds, p->n_turns, p->n_body,
+                 (uint32_t)p->a_end, (uint32_t)p->a_nose, (uint32_t)p->a_cost, (uint32_t)p->a_turn, p->nose_q16, p->nose_miss};
+  const int2* d_tab = reinterpret_cast<const int2*>(dr.d_buf);
+  const tsd_drive_pose* d_pose = reinterpret_cast<const tsd_drive_pose*>(d + o_pose);
+  const int32_t* d_step = reinterpret_cast<const int32_t*>(d + o_step);
+  const int32_t* d_turn = reinterpret_cast<const int32_t*>(d + o_turn);
+  const int2* d_body = reinterpret_cast<const int2*>(d + o_body);
+  unsigned long long* d_best = reinterpret_cast<unsigned long long*>(d + o_best);
+  unsigned long long* d_scores = reinterpret_cast<unsigned long long*>(d + o_scores);
+  unsigned long long* d_mscores = reinterpret_cast<unsigned long long*>(d + o_mscores);
+  uint16_t* d_why = reinterpret_cast<uint16_t*>(d + o_why);
+  uint16_t* d_mwhy = reinterpret_cast<uint16_t*>(d + o_mwhy);
+  tsd_drive_choice* d_choice = reinterpret_cast<tsd_drive_choice*>(d + o_choice);
+  longlong2* d_tracks = reinterpret_cast<longlong2*>(d + o_tracks);
+  const unsigned groups = (unsigned)((S + DR_WAVES - 1) / DR_WAVES);
+  {
+    ScopedKernelTimer t(ctx, r.stream == ctx->stream ? "drive_fleet" : "", true);
+    hipLaunchKernelGGL(k_fleet_init, dim3((unsigned)n_robots), dim3(DR_THREADS), 0, r.stream, a, d_pose, d_tracks, d_scores, d_why, d_choice);
+    if (A > 0)
+      hipLaunchKernelGGL(k_drive_rollout, dim3(groups, (unsigned)A), dim3(DR_THREADS), 0, r.stream, r.d_key, r.d_w, d_tab, a,
+                         reinterpret_cast<const tsd_drive_pose*>(d + o_apose), d_step, d_turn, d_body,
+                         reinterpret_cast<unsigned long long*>(d + o_mbest), d + o_mbest + 2 * R, d_mscores, d_mwhy);
+    DrFleet f{n_robots, fl->sep_q16, parked};
+    for (int m = 0; m < n_robots; m++) {
+      const int q = fl->order[m];
+      if (row[q] < 0) continue;
+      hipLaunchKernelGGL(k_fleet_sample, dim3(groups), dim3(DR_THREADS), 0, r.stream, d_tab, a, f, q, row[q], d_pose, d_step, d_turn, d_tracks,
+                         d_mscores, d_mwhy, d_best, d + o_count, d_scores, d_why);
+      hipLaunchKernelGGL(k_fleet_pick, dim3(1), dim3(64), 0, r.stream, r.d_key, r.d_w, d_tab, a, q, d_pose, d_step, d_turn, d_best, d + o_count,
+                         d_choice, d_tracks);
+      f.decided |= 1u << q;
+    }
+  }
+  TSD_HIP_CHECK(ctx, hipGetLastError());
+  const size_t back = (why_host ? io_words : scores_host ? o_why : tracks_host ? o_scores : o_tracks) - o_choice;
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(h + o_choice, d + o_choice, back * 4, hipMemcpyDeviceToHost, r.stream));
+  TSD_HIP_CHECK(ctx, hipStreamSynchronize(r.stream));
+  std::memcpy(choice_host, h + o_choice, R * sizeof(tsd_drive_choice));
+  if (tracks_host) std::memcpy(tracks_host, h + o_tracks, R * T1 * 2 * sizeof(int64_t));
+  if (scores_host) std::memcpy(scores_host, h + o_scores, R * S * sizeof(uint64_t));
+  if (why_host) std::memcpy(why_host, h + o_why, R * S * sizeof(uint16_t));
+  return TSD_OK;
+}
+
+// The keys under the poses, fetched in one round trip.
+static int drive_fields_togo(tsd_ctx* ctx, const tsd_drive_pose* poses, int n_robots, uint32_t* togo_host)
+{
+  const char* who = "tsd_drive_fields_togo";
+  tsd_ctx::Route& r = ctx->fields;
+  if (!poses) return map_refused(ctx, who, "poses is NULL");
+  if (!togo_host) return map_refused(ctx, who, "togo_host is NULL");
+  if (n_robots < 1 || n_robots > TSD_DRIVE_MAX_ROBOTS) return map_refused(ctx, who, "n_robots is outside 1 .. TSD_DRIVE_MAX_ROBOTS");
+  if (!r.valid) return map_refused(ctx, who, "no fields result");
+  for (int i = 0; i < n_robots; i++) {
+    if (poses[i].x < 0 || poses[i].x >= r.W || poses[i].y < 0 || poses[i].y >= r.H) return map_refused(ctx, who, "a pose's cell lies outside the map");
+    if (poses[i].layer < -1 || poses[i].layer >= r.layers) return map_refused(ctx, who, "a pose's layer is outside -1 .. layers - 1");
+  }
+  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t R = (size_t)n_robots, tab_words = 2 * DR_H, words = 7 * R;        // the poses | the keys
+  tsd_ctx::Drive& dr = ctx->drive;
+  if (dr.words < tab_words + words) dr.table_ready = false;
+  int rc = scratch_grow(ctx, who, &dr.d_buf, &dr.words, tab_words + words, "the poses' keys");
+  if (!rc) rc = scratch_grow(ctx, who, &dr.h_buf, &dr.h_words, words, "the poses' keys, pinned", true);
+  if (rc) return rc;
+  uint32_t* h = dr.h_buf;
+  uint32_t* d = dr.d_buf + tab_words;
+  std::memcpy(h, poses, R * sizeof(tsd_drive_pose));
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d, h, 6 * R * 4, hipMemcpyHostToDevice, r.stream));
+  hipLaunchKernelGGL(k_drive_togo, dim3(1), dim3(64), 0, r.stream, r.d_key, r.W, r.H, (uint32_t)r.W * (uint32_t)r.H, r.layers, n_robots,
+                     reinterpret_cast<const tsd_drive_pose*>(d), d + 6 * R);
+  TSD_HIP_CHECK(ctx, hipGetLastError());
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(h + 6 * R, d + 6 * R, R * 4, hipMemcpyDeviceToHost, r.stream));
+  TSD_HIP_CHECK(ctx, hipStreamSynchronize(r.stream));
+  std::memcpy(togo_host, h + 6 * R, R * 4);
+  return TSD_OK;
+}
+
 void drive_free(tsd_ctx* ctx)
 {
   hipFree(ctx->drive.d_buf);
@@ -338,6 +627,19 @@ int tsd_drive_fields_rollout(tsd_ctx* ctx, const tsd_drive_params* params, const
 {
   if (!ctx) return TSD_E_ARG;
   return drive_rollout(ctx, ctx->fields, "tsd_drive_fields_rollout", params, poses, n_robots, choice_host, scores_host, why_host);
+}
+
+int tsd_drive_fleet_rollout(tsd_ctx* ctx, const tsd_drive_params* params, const tsd_drive_fleet_params* fleet, const tsd_drive_pose* poses,
+                            int n_robots, tsd_drive_choice* choice_host, uint64_t* scores_host, uint16_t* why_host, int64_t* tracks_host)
+{
+  if (!ctx) return TSD_E_ARG;
+  return drive_fleet_rollout(ctx, params, fleet, poses, n_robots, choice_host, scores_host, why_host, tracks_host);
+}
+
+int tsd_drive_fields_togo(tsd_ctx* ctx, const tsd_drive_pose* poses, int n_robots, uint32_t* togo_host)
+{
+  if (!ctx) return TSD_E_ARG;
+  return drive_fields_togo(ctx, poses, n_robots, togo_host);
 }
 
 int tsd_drive_dev_ptrs(tsd_ctx* ctx, const void** block_dev, unsigned long long* words)

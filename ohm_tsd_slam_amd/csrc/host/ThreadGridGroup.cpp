@@ -1,6 +1,7 @@
 #include "ThreadGridGroup.h"
 #include "ThreadGrid.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -333,12 +334,19 @@ int ThreadGridGroup::dispatchLocked(tsd_ctx* ctx, const std::vector<int32_t>& se
 }
 
 #pragma weak tsd_drive_fields_rollout
+#pragma weak tsd_drive_fleet_rollout
+#pragma weak tsd_drive_fields_togo
 
-int ThreadGridGroup::exploreDrive(const ExploreDispatch& d, const double* posesXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples)
+int ThreadGridGroup::exploreDrive(const ExploreDispatch& d, const double* posesXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples,
+                                  const FleetDriveRequest* fleet, FleetDriveAnswer* fleetOut)
 {
   const size_t L = _members.size();
   if(!tsd_drive_fields_rollout || !tsd_route_fields_dev || !posesXyt || !out || !samples || L < 1 || L > (size_t)TSD_DRIVE_MAX_ROBOTS ||
      d.goalOfRobot.size() != L)
+    return TSD_E_ARG;
+  const bool apart = fleet && fleet->separation > 0.0;
+  if(apart && (!tsd_drive_fleet_rollout || !tsd_drive_fields_togo || !fleetOut || !std::isfinite(fleet->separation) ||
+               (!fleet->priority.empty() && fleet->priority.size() != L)))
     return TSD_E_ARG;
   std::lock_guard<std::mutex> lk(_publishMutex);
   if(d.frames == 0 || d.frames != _frames)
@@ -379,6 +387,32 @@ int ThreadGridGroup::exploreDrive(const ExploreDispatch& d, const double* posesX
   rp.limit = static_cast<uint32_t>(std::min<uint64_t>(TSD_ROUTE_MAX_DIST, (uint64_t)far + q.margin));
   rp.max_rounds = 0;
   std::vector<tsd_drive_choice> choice(L);
+  tsd_drive_fleet_params fp;
+  std::vector<int32_t> order;
+  std::vector<uint16_t> why;
+  std::vector<int64_t> tracks;
+  const size_t S = (size_t)samples->prm.n_speeds * samples->prm.n_turns, T1 = (size_t)samples->prm.steps + 1;
+  if(apart)
+  {
+    const double sep = std::floor(fleet->separation / place[2] * 65536.0 + 0.5);
+    if(!(sep <= (double)TSD_DRIVE_MAX_SEP))
+      return TSD_E_ARG;
+    fp.sep_q16 = static_cast<int32_t>(sep);
+    fp.reserved = 0;
+    order = fleet->priority;
+    std::vector<bool> seen(L, false);
+    for(const int32_t r : order)
+    {
+      if(r < 0 || (size_t)r >= L || seen[(size_t)r])
+        return TSD_E_ARG;
+      seen[(size_t)r] = true;
+    }
+    for(size_t r = 0; r < L; r++)
+      if(seeds[2 * r] < 0)
+        poses[r].layer = -1;             // no goal: parked where it stands
+    why.resize(L * S);
+    tracks.resize(L * T1 * 2);
+  }
   {
     // as for the dispatch: member 0's context and stream carry the call
     std::lock_guard<std::mutex> fl(_members[0].grid->frontierMutex());
@@ -387,11 +421,41 @@ int ThreadGridGroup::exploreDrive(const ExploreDispatch& d, const double* posesX
     tsd_route_fields_info info;
     // layer r seeded AT member r's goal: this replaces the dispatch's robot-seeded fields result, whose answers have been fetched
     rc = tsd_route_fields_dev(ctx, tsd_group_map_dev(_group), W, H, W, &rp, &info);
-    if(rc == TSD_OK)
+    if(rc == TSD_OK && !apart)
       rc = tsd_drive_fields_rollout(ctx, &samples->prm, poses.data(), static_cast<int>(L), choice.data(), nullptr, nullptr);
+    if(rc == TSD_OK && apart && order.empty())
+    {
+      // the cost-to-go of each member at its pose, from its own layer, in one round trip: 0xFFFFFFFF (no key, or no goal) sorts
+      // last.  Two members' keys never tie -- the low bits of layer r's keys hold the seed index r --, so equal cost goes to the lower
+      // index by the keys themselves; the stable sort settles the members without a key.
+      std::vector<uint32_t> togo(L, TSD_ROUTE_NONE);
+      rc = tsd_drive_fields_togo(ctx, poses.data(), static_cast<int>(L), togo.data());
+      order.resize(L);
+      for(size_t r = 0; r < L; r++)
+        order[r] = static_cast<int32_t>(r);
+      std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return togo[(size_t)a] < togo[(size_t)b]; });
+    }
+    if(rc == TSD_OK && apart)
+    {
+      fp.order = order.data();
+      rc = tsd_drive_fleet_rollout(ctx, &samples->prm, &fp, poses.data(), static_cast<int>(L), choice.data(), nullptr, why.data(), tracks.data());
+    }
   }
   for(size_t r = 0; r < L && rc == TSD_OK; r++)
     rc = driveAnswer(*samples, place, W, poses[r], choice[r], out + r);
+  if(rc == TSD_OK && apart)
+  {
+    fleetOut->order = order;
+    fleetOut->steps = samples->prm.steps;
+    fleetOut->blocked.assign(L, 0);
+    for(size_t r = 0; r < L; r++)
+      for(size_t i = 0; i < S; i++)
+        fleetOut->blocked[r] += (why[r * S + i] >> 12) == 6;
+    fleetOut->tracks.resize(L * T1 * 2);
+    for(size_t i = 0; i < L * T1; i++)
+      for(size_t a = 0; a < 2; a++)
+        fleetOut->tracks[2 * i + a] = static_cast<double>(tracks[2 * i + a]) / 65536.0 * place[2] + place[a];
+  }
   return rc;
 }
 

@@ -22,6 +22,21 @@ struct DriveRequest;
 struct DriveSamples;
 struct DriveAnswer;
 
+/** What ThreadGridGroup::exploreDrive is asked beside the DriveRequest where the members have to keep off each other, and what it
+ *  answers beside the DriveAnswers. */
+struct FleetDriveRequest
+{
+  double separation = 0.0;             // [m] centre to centre; 0: every member is rolled out as if it were alone on the map
+  std::vector<int32_t> priority;       // a permutation of the members' indices, the first decides first; empty: see exploreDrive
+};
+struct FleetDriveAnswer
+{
+  std::vector<int32_t> order;          // the priority used
+  std::vector<int32_t> blocked;        // per member: the samples refused because of another member's arc (reason 6)
+  std::vector<double> tracks;          // per member T + 1 pairs (x, y) [m]: the chosen arc step by step, the pose itself without one
+  int steps = 0;                       // T
+};
+
 /** What ThreadGridGroup::exploreDispatch is asked and what it answers. */
 struct ExploreDispatch
 {
@@ -124,8 +139,15 @@ public:
    *  seed outside the map, a layer without keys and no command), then one tsd_drive_fields_rollout, member r on layer r.  The
    *  goal-seeded layers REPLACE the robot-seeded fields result of the dispatch on member 0's context; the dispatch's answers have been
    *  fetched by then.  Holds the locks explorePlan holds.  TSD_E_ARG for a dispatch of another publication, a pose outside the map,
-   *  what driveSamples refuses, and where the device library has no rollout. */
-  int exploreDrive(const ExploreDispatch& d, const double* posesXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples);
+   *  what driveSamples refuses, and where the device library has no rollout.
+   *  With fleet->separation > 0 the members keep off each other (tsd_drive_fleet_rollout instead): they decide in the order
+   *  fleet->priority, each against the arcs chosen before it, and a member without a goal goes in as a parked robot the others keep
+   *  clear of.  Without a priority list: the members with a goal in ascending cost-to-go at their pose (the one nearer its goal
+   *  decides first; read from the goal-seeded layers), ties by index, then the others.  fleetOut gets the order used, the samples
+   *  each member lost to the others and the chosen arcs in metres.  TSD_E_ARG also for a priority that is no permutation, a
+   *  separation beyond TSD_DRIVE_MAX_SEP cells, a NULL fleetOut and where the device library has no fleet rollout. */
+  int exploreDrive(const ExploreDispatch& d, const double* posesXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples,
+                   const FleetDriveRequest* fleet = nullptr, FleetDriveAnswer* fleetOut = nullptr);
   size_t members(void) const { return _members.size(); }
 
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }

@@ -985,6 +985,37 @@ int tsd_fleet_explore_drive(tsd_fleet* f, const double* poses_xyt, const double*
   return TSD_OK;
 }
 
+// tsd_fleet_explore_drive with the nodes keeping `separation_m` [m] off each other (ThreadGridGroup::exploreDrive with a
+// FleetDriveRequest): priority n_priority node indices, the first decides first, or NULL / 0 for the default; order_out and
+// blocked_out one int per node, tracks_out (steps + 1) pairs (x, y) [m] per node, node after node, where tracks_cap doubles hold them.
+int tsd_fleet_explore_drive_apart(tsd_fleet* f, const double* poses_xyt, const double* limits, const int* ints, const double* footprint_xy, int n_foot,
+                                  double separation_m, const int32_t* priority, int n_priority, double* out8, tsd_drive_choice* choice, int* shape4,
+                                  double* dt, int32_t* order_out, int32_t* blocked_out, double* tracks_out, int tracks_cap)
+{
+  DriveRequest q;
+  if(!f || !f->group || !poses_xyt || !out8 || !drive_request(limits, ints, footprint_xy, n_foot, &q) || !(separation_m > 0.0) || n_priority < 0 ||
+     (n_priority > 0 && !priority))
+    return TSD_E_ARG;
+  FleetDriveRequest fq;
+  fq.separation = separation_m;
+  fq.priority.assign(priority, priority + n_priority);
+  FleetDriveAnswer fa;
+  std::vector<DriveAnswer> a(f->nodes.size());
+  DriveSamples s;
+  const int rc = f->group->exploreDrive(f->dispatch, poses_xyt, q, a.data(), &s, &fq, &fa);
+  if(rc != TSD_OK)
+    return rc;
+  if(tracks_out && (size_t)std::max(tracks_cap, 0) < fa.tracks.size())
+    return TSD_E_ARG;
+  for(size_t r = 0; r < a.size(); r++)
+    drive_answer(a[r], out8 + 8 * r, choice ? choice + r : nullptr);
+  drive_shape(s, shape4, dt);
+  if(order_out) std::memcpy(order_out, fa.order.data(), fa.order.size() * sizeof(int32_t));
+  if(blocked_out) std::memcpy(blocked_out, fa.blocked.data(), fa.blocked.size() * sizeof(int32_t));
+  if(tracks_out) std::memcpy(tracks_out, fa.tracks.data(), fa.tracks.size() * sizeof(double));
+  return TSD_OK;
+}
+
 // The merged plan's paths straightened into waypoints (ThreadGridGroup::exploreWaypoints), as tsd_node_explore_waypoints.
 int tsd_fleet_explore_waypoints(tsd_fleet* f, double lookahead_m, unsigned slack, int max_len, int max_way, uint32_t* way, tsd_waypoint_info* info,
                                 int* lookahead_cells)

@@ -342,7 +342,8 @@ struct tsd_ctx {
   // `cells`), d_goal the goal matrix [layers][n_goals].  Neither instance touches the other's buffers
   Route fields;
   // drive (drive.hip: tsd_drive_rollout / tsd_drive_fields_rollout): one device block -- the direction table (uploaded when the block
-  // is made), then the call's inputs and outputs -- and its pinned copy without the table.  Grown on demand and kept; every call
+  // is made), then the call's inputs and outputs (tsd_drive_fleet_rollout: the tracks among them, and behind them the map pass's
+  // per-sample rows, which only the device reads) -- and its pinned copy without the table.  Grown on demand and kept; every call
   // waits for its own work
   struct Drive {
     uint32_t* d_buf = nullptr; uint32_t* h_buf = nullptr; size_t words = 0, h_words = 0;
@@ -397,7 +398,7 @@ struct tsd_ctx {
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;
   unsigned profile_every = 1;   // time every n-th launch of a selected kernel ("name/n" in tsd_profile_select)
-  unsigned profile_every_k[26] = {};   // a kernel's own period ("name:m"), 0 = the list's
+  unsigned profile_every_k[27] = {};   // a kernel's own period ("name:m"), 0 = the list's
   bool profile = false;
   std::map<std::string, tsd::KernelTimer> timers;
   std::vector<hipEvent_t> event_pool;

@@ -74,6 +74,8 @@ HOST_ABI = {
     "tsd_fleet_explore_dispatch_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsd_node_explore_drive": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, C.c_int, _dp, C.c_void_p, _ip, _dp]),
     "tsd_fleet_explore_drive": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, C.c_int, _dp, C.c_void_p, _ip, _dp]),
+    "tsd_fleet_explore_drive_apart": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, C.c_int, C.c_double, C.c_void_p, C.c_int, _dp, C.c_void_p, _ip, _dp,
+                                                C.c_void_p, C.c_void_p, _dp, C.c_int]),
     "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_grid_lock": (None, [C.c_void_p]),
@@ -761,16 +763,42 @@ class SlamFleet:
                 "lookahead_cells": counts[4], "origin": origin, "resolution": res}
 
     def explore_drive(self, poses, v_max: float, w_max: float, horizon_s: float, footprint=None, n_speeds=5, weights=(1, 1, 0, 0),
-                      nose_m=0.0, nose_miss=0, margin=2000) -> list:
+                      nose_m=0.0, nose_miss=0, margin=2000, separation_m=0.0, priority=None) -> list:
         """``SlamNode.explore_drive`` for every node at once, towards the goal the last ``explore_dispatch`` gave it: ``poses`` one
         (x, y [m], yaw [rad]) per node in the merged map's frame; one fields call on the merged map seeded at the nodes' goal cells
         (unit weights, as the dispatch plans), then one tsd_drive_fields_rollout, node r on layer r.  A list of one dict per node; a
         node without a goal gets ``v`` = ``w`` = 0 and ``admissible`` == 0.  The goal-seeded layers replace the dispatch's fields
-        result on the device.  Refused without a dispatch and once the merged map has been published again."""
+        result on the device.  Refused without a dispatch and once the merged map has been published again.
+
+        ``separation_m`` > 0 keeps the nodes off each other (tsd_drive_fleet_rollout): they decide one after the other, and an arc
+        that comes within ``separation_m`` (centre to centre) of an arc chosen before it, at the same time step and without moving
+        away from it, is refused; a node without a goal is a parked robot the others keep clear of.  ``priority``: the nodes'
+        indices, the first decides first.  By default the nodes with a goal go in ascending cost-to-go at their pose -- the one
+        nearer its goal first --, ties by index, the others behind them.  Each dict then also holds ``blocked`` (the samples the node
+        lost to the others), ``tracks`` (the chosen arc, ``steps`` + 1 points (x, y) [m]; the pose itself without one) and ``rank``
+        (its place in the order used).  With 0.0 the call is the one above, unchanged."""
         if len(poses) != len(self.nodes):
             raise capi.TsdError("explore_drive: one pose per node")
-        return _drive(lambda *a: self.lib.tsd_fleet_explore_drive(self.h, *a), poses, v_max, w_max, horizon_s, footprint, n_speeds, weights,
-                      nose_m, nose_miss, margin, "tsd_fleet_explore_drive")
+        if not separation_m > 0.0:
+            if separation_m != 0.0 or priority is not None:
+                raise capi.TsdError("explore_drive: separation_m must be 0 or positive, and a priority needs a separation")
+            return _drive(lambda *a: self.lib.tsd_fleet_explore_drive(self.h, *a), poses, v_max, w_max, horizon_s, footprint, n_speeds, weights,
+                          nose_m, nose_miss, margin, "tsd_fleet_explore_drive")
+        n = len(self.nodes)
+        prio = np.zeros(0, dtype=np.int32) if priority is None else np.ascontiguousarray(priority, dtype=np.int32).ravel()
+        order, blocked = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        tracks = np.zeros((n * (capi.DRIVE_MAX_STEPS + 1), 2))
+
+        def call(poses_p, limits, ints, foot, n_foot, out, choice, shape, dt):
+            return self.lib.tsd_fleet_explore_drive_apart(self.h, poses_p, limits, ints, foot, n_foot, float(separation_m),
+                                                          prio.ctypes.data if prio.size else None, int(prio.size), out, choice, shape, dt,
+                                                          order.ctypes.data, blocked.ctypes.data, tracks.ctypes.data_as(_dp), int(tracks.size))
+
+        out = _drive(call, poses, v_max, w_max, horizon_s, footprint, n_speeds, weights, nose_m, nose_miss, margin, "tsd_fleet_explore_drive_apart")
+        t1 = out[0]["steps"] + 1
+        for r in range(n):
+            out[r].update(blocked=int(blocked[r]), tracks=tracks[r * t1:(r + 1) * t1].copy(), rank=int(np.nonzero(order == r)[0][0]))
+        return out
 
     def merged_frames(self) -> int:
         return int(self.lib.tsd_fleet_merged_frames(self.h))
