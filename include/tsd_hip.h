@@ -1005,6 +1005,60 @@ typedef struct {
 int tsd_drive_fleet_rollout(tsd_ctx* ctx, const tsd_drive_params* params, const tsd_drive_fleet_params* fleet, const tsd_drive_pose* poses,
                             int n_robots, tsd_drive_choice* choice_host, uint64_t* scores_host /* or NULL */, uint16_t* why_host /* or NULL */,
                             int64_t* tracks_host /* or NULL */);
+/* The live layer: what a scanner sees this instant, kept off the arcs.  The three rollouts above read the weight image of a route or
+ * fields result, which was made from a map published some time ago; a context may hold beside it at most one live layer, made from
+ * the end points of the current scans, and while one is set the rollouts refuse every arc that enters it.
+ *   the layer      a bit per cell of a width x height image, rows padded to 32-bit words: bit x & 31 of word
+ *                  y * stride_words + (x >> 5) is the cell (x, y), stride_words = (width + 31) / 32; the tail bits of a row's last
+ *                  word are always 0
+ *   points         n pairs (px, py), int32: the map cell of a scan end point, |px|, |py| <= 1 << 30 -- a point may lie outside the
+ *                  map --, 0 <= n <= TSD_DRIVE_LIVE_MAX_POINTS; n == 0 is legal and gives an empty layer that is set
+ *   skip discs     n_skip <= TSD_DRIVE_LIVE_MAX_SKIP triples (ox, oy, ro), |ox|, |oy| <= 1 << 30, 0 <= ro <= 1 << 15: a point is
+ *                  dropped where (px - ox)^2 + (py - oy)^2 <= ro^2 for some disc (products in 64 bits; a point further than ro from
+ *                  the centre along one axis is outside without a product).  The discs are the robots themselves: one robot's
+ *                  scanner sees another robot's body, and a robot that stands inside a stamped disc could not move
+ *   radius         r in 0 .. TSD_DRIVE_LIVE_MAX_RADIUS cells
+ *   the live set   L: every cell (x, y) inside the map with (x - px)^2 + (y - py)^2 <= r^2 for some point that was not dropped
+ * Every set rebuilds the layer whole from its own points: no ray clearing, no decay, and no bit of the set before it survives.
+ * While a layer is set, tsd_drive_rollout, tsd_drive_fields_rollout and tsd_drive_fleet_rollout refuse step k by the first of 1, 2,
+ * 3, 4 as above, and then by
+ *                    7  c_k lies in L or, failing that, for the lowest body point b whose cell lies in L (every such cell lies
+ *                       inside the map: 4 has passed)
+ * and in the fleet form reason 6 follows: at one step the order is 1, 2, 3, 4, 7, 6.  The smallest refusing k wins with its first
+ * reason, reason 5 stays behind step T; why = (7 << 12) | k.  The layer refuses and never rates: score, choice, tie order, tracks and
+ * the winner's record are those of the rule above over the samples that are left.  c_1 is tested also where it is the start's
+ * cell, as for w == 0: a robot that stands on a live cell cannot move, and the skip discs are the caller's way out.  The corner rule
+ * (3) is NOT restated for live cells: a disc of r >= 1 is 4-connected, so no centre passes diagonally between two of its cells, but
+ * at r == 0 a centre can slip diagonally between two live cells.  A layer whose width or height differ from the result's image
+ * makes the three rollouts return TSD_E_ARG, outputs and results left as they were.  Without a layer -- the state of a new context
+ * and after tsd_drive_live_clear -- the three rollouts answer byte for byte as they do without this section (the kernels keep an
+ * instantiation without the test).  The route and fields calls do not read the layer: plans still lead through live cells.
+ * The calls below take no lock of their own: like the other drive calls they run under the lock the caller holds for the frontier,
+ * route and view calls (one thread per context at a time). */
+#define TSD_DRIVE_LIVE_MAX_POINTS 32768
+#define TSD_DRIVE_LIVE_MAX_SKIP   16
+#define TSD_DRIVE_LIVE_MAX_RADIUS 64
+typedef struct {
+  int32_t radius;               /* r: 0 .. TSD_DRIVE_LIVE_MAX_RADIUS */
+  int32_t n_skip;               /* 0 .. TSD_DRIVE_LIVE_MAX_SKIP */
+  const int32_t* skip;          /* [3 n_skip] triples (ox, oy, ro), host memory; may be NULL where n_skip == 0 */
+} tsd_drive_live_params;        /* 16 bytes */
+/* Sets the layer from n points for a width x height image, sides 1 .. TSD_FRONTIER_MAX_SIDE; *n_kept, where given, is the number of
+ * points no disc dropped.  The old layer is emptied (one memset of the bit image), then one launch
+ * ("drive_live": a thread per (point, row of its disc): the skip test, the row's half-width floor(sqrt(r^2 - dy^2)) from a table the
+ * host builds per call with integer arithmetic, the span clipped to the map and written as word masks with atomic ORs) on the
+ * context's stream, waited for.  Scratch -- the bit image, a block for the points -- stays with the context and grows on demand: a
+ * repeated set of the same shape allocates nothing.  TSD_E_ARG, with the previous layer left in place: a NULL params, a NULL
+ * points_xy where n > 0, a NULL skip where n_skip > 0, a count, radius, coordinate or side outside the ranges above. */
+int tsd_drive_live_set(tsd_ctx* ctx, const tsd_drive_live_params* params, const int32_t* points_xy /* [2 n], host */, int n,
+                       int width, int height, int* n_kept /* or NULL */);
+/* No layer: the rollouts are those of the rule without the layer again.  Legal without a layer. */
+int tsd_drive_live_clear(tsd_ctx* ctx);
+/* The layer's words, stride_words * height of them, into words_host (cap_words: its capacity in words), and its shape; each pointer
+ * may be NULL (words_host NULL: the shape alone).  TSD_E_ARG without a layer, or where cap_words is too small. */
+int tsd_drive_live_fetch(tsd_ctx* ctx, uint32_t* words_host, long long cap_words, int* width, int* height, int* stride_words);
+/* The layer on the device.  Valid until a set that needs a larger image or tsd_destroy.  TSD_E_ARG without a layer. */
+int tsd_drive_live_dev_ptr(tsd_ctx* ctx, const void** words_dev, int* width, int* height, int* stride_words);
 
 /* ---- views: what a scan from a cell would uncover, and who is about to see it ------------------------------------ */
 /* The expected information gain of candidate cells (exploration goals) and the coordination rule on top of it: what one robot is
@@ -1360,6 +1414,7 @@ int tsd_fuse(tsd_ctx* dst, int n, tsd_ctx* const* src, const int32_t* cell_off_x
  * the same passes of tsd_route_fields_dev / _goals / _trace: "route_fields_init", "route_fields_relax", "route_fields_goals",
  * "route_fields_trace",
  * tsd_drive_rollout's and tsd_drive_fields_rollout's launch: "drive_rollout", tsd_drive_fleet_rollout's launches: "drive_fleet",
+ * tsd_drive_live_set's emptying and stamp: "drive_live",
  * and the launches of tsd_view_gains and tsd_view_claim on the context's stream: "view_gain", "view_claim". */
 int tsd_profile_enable(tsd_ctx* ctx, int on);
 /* restrict timing to a comma separated list of kernel names, or "all"; a "/n" suffix times every n-th

@@ -234,6 +234,14 @@ class DriveFleetParams(C.Structure):
     _fields_ = [("order", C.POINTER(C.c_int32)), ("sep_q16", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DriveLiveParams(C.Structure):
+    """tsd_drive_live_params"""
+    _fields_ = [("radius", C.c_int32), ("n_skip", C.c_int32), ("skip", C.POINTER(C.c_int32))]
+
+
+DRIVE_LIVE_MAX_POINTS = 32768     # tsd_drive_live_set's limits: points, skip discs, the radius in cells
+DRIVE_LIVE_MAX_SKIP = 16
+DRIVE_LIVE_MAX_RADIUS = 64
 DRIVE_MAX_SEP = 128 * 65536       # tsd_drive_fleet_rollout's largest separation, Q16 cells
 DRIVE_POSE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("fx", "<i4"), ("fy", "<i4"), ("heading", "<i4"), ("layer", "<i4")])
 DRIVE_CHOICE_DTYPE = np.dtype([("speed", "<i4"), ("turn", "<i4"), ("admissible", "<i4"), ("end_cell", "<u4"), ("d_end", "<u4"),
@@ -492,6 +500,10 @@ ABI = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "tsd_drive_fields_togo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tsd_drive_dev_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong)]),
+    "tsd_drive_live_set": (C.c_int, [C.c_void_p, C.POINTER(DriveLiveParams), C.c_void_p, C.c_int, C.c_int, C.c_int, _ip]),
+    "tsd_drive_live_clear": (C.c_int, [C.c_void_p]),
+    "tsd_drive_live_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, _ip, _ip, _ip]),
+    "tsd_drive_live_dev_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), _ip, _ip, _ip]),
     "tsd_view_assign_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_int,
                                          C.c_uint32, C.c_void_p, C.c_void_p, _ip]),
     "tsd_view_gains": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ViewParams), C.c_void_p, C.c_int, C.c_void_p]),
@@ -583,7 +595,7 @@ def load_library(path: str | None = None):
                           ("tsd_view_params", ViewParams), ("tsd_view_gain", ViewGain),
                           ("tsd_waypoint_params", WaypointParams), ("tsd_waypoint_info", WaypointInfo),
                           ("tsd_drive_params", DriveParams), ("tsd_drive_pose", DrivePose), ("tsd_drive_choice", DriveChoice),
-                          ("tsd_drive_fleet_params", DriveFleetParams)):
+                          ("tsd_drive_fleet_params", DriveFleetParams), ("tsd_drive_live_params", DriveLiveParams)):
         if lib.tsd_abi_sizeof(cname.encode()) != C.sizeof(mirror):
             raise TsdError(f"ABI mismatch: sizeof({cname}) = {lib.tsd_abi_sizeof(cname.encode())} in {p}, {C.sizeof(mirror)} in capi.py")
     if path is None:
@@ -1552,6 +1564,40 @@ class TsdGridDevice:
         togo = np.zeros(p.size, dtype=np.uint32)
         self._check(self.lib.tsd_drive_fields_togo(self.h, p.ctypes.data, int(p.size), togo.ctypes.data), "tsd_drive_fields_togo")
         return togo
+
+    # ---- the live layer (tsd_drive_live_*): the current scans' end points, kept off the arcs of the three rollouts
+    def drive_live_set(self, points_cells, radius: int, skip=None, size=None) -> int:
+        """tsd_drive_live_set: the layer of the int32 (n, 2) map cells ``points_cells`` (they may lie outside the map), each a disc of
+        ``radius`` cells; ``skip``: up to 16 discs (ox, oy, ro) whose points are dropped -- the robots themselves; ``size``: (width,
+        height), by default the image of the route result, else of the fields result.  Returns the number of points not dropped.
+        While the layer is set the rollouts refuse every arc that enters it (reason 7)."""
+        pts = np.ascontiguousarray(points_cells if points_cells is not None else [], dtype=np.int32).reshape(-1, 2)
+        sk = np.ascontiguousarray(skip if skip is not None else [], dtype=np.int32).reshape(-1, 3)
+        if size is None:
+            k, w, h = C.c_void_p(), C.c_int(0), C.c_int(0)
+            if self.lib.tsd_route_dev_ptrs(self.h, C.byref(k), C.byref(w), C.byref(h)) != 0:
+                w, h = (C.c_int(v) for v in self.route_fields_dev_ptrs()[1:3])
+            size = (w.value, h.value)
+        prm = DriveLiveParams(int(radius), int(sk.shape[0]), sk.ctypes.data_as(C.POINTER(C.c_int32)) if sk.shape[0] else None)
+        kept = C.c_int(-1)
+        rc = self.lib.tsd_drive_live_set(self.h, C.byref(prm), pts.ctypes.data if pts.shape[0] else None, int(pts.shape[0]), int(size[0]),
+                                         int(size[1]), C.byref(kept))
+        self.last_rc = rc
+        self._check(rc, "tsd_drive_live_set")
+        return kept.value
+
+    def drive_live_clear(self) -> None:
+        """tsd_drive_live_clear: no layer -- the rollouts are those without one again"""
+        self._check(self.lib.tsd_drive_live_clear(self.h), "tsd_drive_live_clear")
+
+    def drive_live(self):
+        """the layer as a bool (height, width) image (tsd_drive_live_fetch, unpacked), None where none is set"""
+        w, h, s = C.c_int(0), C.c_int(0), C.c_int(0)
+        if self.lib.tsd_drive_live_dev_ptr(self.h, None, C.byref(w), C.byref(h), C.byref(s)) != 0:
+            return None
+        words = np.zeros((h.value, s.value), dtype="<u4")
+        self._check(self.lib.tsd_drive_live_fetch(self.h, words.ctypes.data, words.size, None, None, None), "tsd_drive_live_fetch")
+        return np.unpackbits(words.view(np.uint8).reshape(h.value, -1), axis=1, bitorder="little")[:, :w.value].astype(bool)
 
     # ---- fields (tsd_route_fields_*): one key image per seed
     def route_fields_dev_ptrs(self):

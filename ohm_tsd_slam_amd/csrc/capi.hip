@@ -30,7 +30,8 @@ int set_error(tsd_ctx* ctx, int code, const char* what, hipError_t e)
 const char* const kKernelNames[] = {"push_classify", "push_update", "push_halo", "raycast", "icp", "occupancy", "tsdpdf", "fuse", "clearance",
                                    "frontier_tile", "frontier_seam", "frontier_flatten", "frontier_rank", "frontier_stats",
                                    "route_init", "route_relax", "route_goals", "route_trace", "view_gain", "view_claim", "route_waypoints",
-                                   "route_fields_init", "route_fields_relax", "route_fields_goals", "route_fields_trace", "drive_rollout", "drive_fleet"};
+                                   "route_fields_init", "route_fields_relax", "route_fields_goals", "route_fields_trace", "drive_rollout", "drive_fleet",
+                                   "drive_live"};
 
 bool kernel_is_timed(const tsd_ctx* ctx, const char* name)
 {

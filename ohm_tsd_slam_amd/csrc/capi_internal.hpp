@@ -16,7 +16,7 @@
 
 namespace tsd {
 
-extern const char* const kKernelNames[27];         // the kernels tsd_profile_select knows, in profile_mask's bit order
+extern const char* const kKernelNames[28];         // the kernels tsd_profile_select knows, in profile_mask's bit order
 hipEvent_t pool_get(tsd_ctx* ctx);                  // a timing event from the context's pool
 char* stage_acquire(tsd_ctx* ctx, int* slot_out);   // next pinned staging slot; waits for the copy that last used it
 double distance_filter_multiplier(double maxdist, double mindist, int icp_iterations);

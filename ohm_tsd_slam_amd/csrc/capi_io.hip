@@ -142,6 +142,7 @@ int tsd_abi_sizeof(const char* n)
   TSD_SZ(tsd_frontier); TSD_SZ(tsd_frontier_params); TSD_SZ(tsd_route_params); TSD_SZ(tsd_route_info); TSD_SZ(tsd_route_goal);
   TSD_SZ(tsd_view_params); TSD_SZ(tsd_view_gain); TSD_SZ(tsd_waypoint_params); TSD_SZ(tsd_waypoint_info); TSD_SZ(tsd_route_fields_info);
   TSD_SZ(tsd_drive_params); TSD_SZ(tsd_drive_pose); TSD_SZ(tsd_drive_choice); TSD_SZ(tsd_drive_fleet_params);
+  TSD_SZ(tsd_drive_live_params);
 #undef TSD_SZ
   return 0;
 }

@@ -21,6 +21,8 @@
 // k_drive_pick       one wave per robot right behind it on the same stream: it rolls the winner out once more with the same device
 //                    function and writes the robot's tsd_drive_choice; no per-sample record has to be kept for it.
 // No workgroup waits for another; the two launches are ordered by the stream.
+// Both kernels come in two instantiations: <false>, the code of a context without a live layer, and <true>, which also refuses a step
+// whose centre or body point lies in the layer of tsd_drive_live_set (reason 7; k_live_stamp further down makes the layer).
 #include "map_product.hpp"
 
 #include <cmath>
@@ -61,9 +63,20 @@ __device__ __forceinline__ int dr_scan(int v, int lane)       // the inclusive s
   return v;
 }
 
-// Sample (s, t) of pose p, by the whole wave.  key: the sample's key image; s_body: the body points (LDS).
+// the live layer of a launch (tsd_drive_live_set): a bit per cell, `stride` words per row
+struct DrLive { const uint32_t* words; int stride; };
+
+// the bit of the cell (x, y), which lies inside the map
+__device__ __forceinline__ bool dr_live(const DrLive& lv, int x, int y)
+{
+  return (lv.words[(size_t)(uint32_t)y * (uint32_t)lv.stride + ((uint32_t)x >> 5)] >> (x & 31)) & 1u;
+}
+
+// Sample (s, t) of pose p, by the whole wave.  key: the sample's key image; s_body: the body points (LDS).  LIVE: reason 7 behind
+// reason 4 -- the centre's bit and, beside each body point's byte, its bit; a launch without a layer takes the instantiation without.
+template <bool LIVE>
 __device__ DrSample dr_sample(const uint32_t* __restrict__ key, const uint8_t* __restrict__ wimg, const int2* __restrict__ tab, const DrArgs& a,
-                              const tsd_drive_pose& p, int s, int t, const int2* s_body, int lane)
+                              const DrLive& lv, const tsd_drive_pose& p, int s, int t, const int2* s_body, int lane)
 {
   int cX = p.fx, cY = p.fy;                          // X, Y and the centre cell of the last step done (step 0: the pose)
   int px = p.x, py = p.y, hT = p.heading;
@@ -90,11 +103,29 @@ __device__ DrSample dr_sample(const uint32_t* __restrict__ key, const uint8_t* _
     unsigned long long bad = __ballot(reason != 0);
     const int first = bad ? __builtin_ctzll(bad) : 64;
     if (act && lane < first) {                                 // (a lane behind a refused step has nothing to add)
+      bool seven = false;
+      if constexpr (LIVE) seven = dr_live(lv, x, y);           // (c_k lies inside the map: 1 has passed)
       for (int b = 0; b < a.B; b++) {
         const long long bx = s_body[b].x, by = s_body[b].y;
         const int ux = X + dr_q16(bx * d.x - by * d.y), uy = Y + dr_q16(bx * d.y + by * d.x);
-        if (dr_w(wimg, a.W, a.H, p.x + (ux >> 16), p.y + (uy >> 16)) == 0) { reason = 4; break; }
+        const int vx = p.x + (ux >> 16), vy = p.y + (uy >> 16);
+        if constexpr (LIVE) {                                  // the byte and the bit in flight together, in front of the test
+          const bool in = (unsigned)vx < (unsigned)a.W && (unsigned)vy < (unsigned)a.H;
+          int wv = 0;
+          uint32_t lw = 0u;
+          if (in) {
+            wv = wimg[(uint32_t)vy * (uint32_t)a.W + (uint32_t)vx];
+            lw = lv.words[(size_t)(uint32_t)vy * (uint32_t)lv.stride + ((uint32_t)vx >> 5)];
+          }
+          asm volatile("" : "+v"(lw));                         // (keeps the word's load in front of the test: it would sink behind the break)
+          if (wv == 0) { reason = 4; break; }
+          seven |= (lw >> (vx & 31)) & 1u;
+        } else {
+          if (dr_w(wimg, a.W, a.H, vx, vy) == 0) { reason = 4; break; }
+        }
       }
+      if constexpr (LIVE)
+        if (reason == 0 && seven) reason = 7;                  // 4 goes first at one step, whichever point it is
     }
     bad = __ballot(reason != 0);
     if (bad) {
@@ -122,11 +153,12 @@ __device__ DrSample dr_sample(const uint32_t* __restrict__ key, const uint8_t* _
   return DrSample{0u, end, d_end, d_nose, cost, score};
 }
 
+template <bool LIVE>
 __global__ void __launch_bounds__(DR_THREADS)
 k_drive_rollout(const uint32_t* __restrict__ key, const uint8_t* __restrict__ wimg, const int2* __restrict__ tab, DrArgs a,
                 const tsd_drive_pose* __restrict__ poses, const int32_t* __restrict__ step, const int32_t* __restrict__ turn,
                 const int2* __restrict__ body, unsigned long long* __restrict__ best, uint32_t* __restrict__ count,
-                unsigned long long* __restrict__ scores, uint16_t* __restrict__ why)
+                unsigned long long* __restrict__ scores, uint16_t* __restrict__ why, DrLive lv)
 {
   __shared__ int2 s_body[TSD_DRIVE_MAX_BODY];
   const int tid = (int)threadIdx.x, lane = tid & 63;
@@ -137,7 +169,7 @@ k_drive_rollout(const uint32_t* __restrict__ key, const uint8_t* __restrict__ wi
   if (idx >= S) return;
   const tsd_drive_pose p = poses[r];
   const int t = turn[idx % a.Wn];
-  const DrSample o = dr_sample(key + (size_t)p.layer * a.cells, wimg, tab, a, p, step[idx / a.Wn], t, s_body, lane);
+  const DrSample o = dr_sample<LIVE>(key + (size_t)p.layer * a.cells, wimg, tab, a, lv, p, step[idx / a.Wn], t, s_body, lane);
   if (lane == 0) {
     scores[(size_t)r * S + idx] = o.score;
     why[(size_t)r * S + idx] = (uint16_t)o.why;
@@ -148,11 +180,12 @@ k_drive_rollout(const uint32_t* __restrict__ key, const uint8_t* __restrict__ wi
   }
 }
 
+template <bool LIVE>
 __global__ void __launch_bounds__(64)
 k_drive_pick(const uint32_t* __restrict__ key, const uint8_t* __restrict__ wimg, const int2* __restrict__ tab, DrArgs a,
              const tsd_drive_pose* __restrict__ poses, const int32_t* __restrict__ step, const int32_t* __restrict__ turn,
              const int2* __restrict__ body, const unsigned long long* __restrict__ best, const uint32_t* __restrict__ count,
-             tsd_drive_choice* __restrict__ choice)
+             tsd_drive_choice* __restrict__ choice, DrLive lv)
 {
   __shared__ int2 s_body[TSD_DRIVE_MAX_BODY];
   const int lane = (int)threadIdx.x, r = (int)blockIdx.x;
@@ -165,7 +198,7 @@ k_drive_pick(const uint32_t* __restrict__ key, const uint8_t* __restrict__ wimg,
   }
   const int idx = (int)(b & 0xFFFFull), i = idx / a.Wn, j = idx % a.Wn;
   const tsd_drive_pose p = poses[r];
-  const DrSample o = dr_sample(key + (size_t)p.layer * a.cells, wimg, tab, a, p, step[i], turn[j], s_body, lane);
+  const DrSample o = dr_sample<LIVE>(key + (size_t)p.layer * a.cells, wimg, tab, a, lv, p, step[i], turn[j], s_body, lane);
   if (lane == 0) choice[r] = tsd_drive_choice{i, j, (int32_t)count[r], o.end_cell, o.d_end, o.d_nose, o.cost, 0u, o.score};
 }
 
@@ -229,7 +262,8 @@ k_fleet_sample(const int2* __restrict__ tab, DrArgs a, DrFleet f, int r, int c, 
   uint32_t w = map_why[(size_t)c * S + idx];
   unsigned long long score = map_scores[(size_t)c * S + idx];
   const uint32_t reason = w >> 12;
-  const int last = (reason >= 1 && reason <= 4) ? min((int)(w & 0xFFFu) - 1, a.T) : a.T;       // at the map's own step the map's reason goes first
+  // at the map's own step the map's reason goes first: 1 .. 4, and 7 where the map pass ran with a live layer
+  const int last = ((reason >= 1 && reason <= 4) || reason == 7) ? min((int)(w & 0xFFFu) - 1, a.T) : a.T;
   if (f.decided != 0 && f.sep > 0) {
     const tsd_drive_pose p = poses[r];
     const int s = step[idx / a.Wn], t = turn[idx % a.Wn];
@@ -326,6 +360,120 @@ k_drive_togo(const uint32_t* __restrict__ key, int W, int H, uint32_t cells, int
   togo[r] = in ? key[(size_t)p.layer * cells + (uint32_t)p.y * (uint32_t)W + (uint32_t)p.x] : TSD_ROUTE_NONE;
 }
 
+// ---- the live layer (tsd_drive_live_set): the discs of a scan's end points as bits
+// k_live_stamp       one thread per (point, row of its disc), 256 per workgroup, the row the fast index: a wave holds the rows of one or
+//                    a few discs whatever the radius (at r = 8 a wave per point would leave 47 of 64 lanes idle, and a thread per point
+//                    would walk up to 129 rows one after the other).  The skip discs and the half-width table come into LDS once per
+//                    workgroup; each thread tests its point against the discs, takes the row's half-width from the table (built by
+//                    the host in integers), clips the span to the map and ORs its word masks into the image -- at most five words at
+//                    r = 64.  Every word address is bounded by y < H and x1 <= W - 1, so x1 >> 5 < stride.  The thread of a point's
+//                    first row counts the point as kept: one atomic add per wave.
+// The old layer is emptied by a memset of the bit image.  (A pass over the previous set's points that zeroes the words they wrote was
+// built and measured beside it -- profiles/drive_live.txt: 3 us cheaper on a 32 MB image for one scan's points, up to 80 us dearer at
+// 32 768 points -- and taken out again.)
+// The points' block, in int32 words: the discs (3 * 16), the table (65), the kept count, padding up to 128, then the points.
+constexpr int LV_THREADS = 256, LV_DISC = 0, LV_TABLE = 3 * TSD_DRIVE_LIVE_MAX_SKIP, LV_KEPT = LV_TABLE + TSD_DRIVE_LIVE_MAX_RADIUS + 1, LV_POINTS = 128;
+constexpr size_t LV_BLOCK = LV_POINTS + 2 * (size_t)TSD_DRIVE_LIVE_MAX_POINTS;
+static_assert(LV_KEPT < LV_POINTS, "the head of the block holds the discs, the table and the count");
+
+struct LvArgs { int W, H, stride, r, n, n_skip; };
+
+__global__ void __launch_bounds__(LV_THREADS)
+k_live_stamp(int32_t* __restrict__ block, LvArgs a, uint32_t* __restrict__ words)
+{
+  __shared__ int s_disc[3 * TSD_DRIVE_LIVE_MAX_SKIP];
+  __shared__ int s_hw[TSD_DRIVE_LIVE_MAX_RADIUS + 1];
+  const int tid = (int)threadIdx.x;
+  if (tid < 3 * a.n_skip) s_disc[tid] = block[LV_DISC + tid];
+  if (tid <= a.r) s_hw[tid] = block[LV_TABLE + tid];
+  __syncthreads();
+  const int rows = 2 * a.r + 1;
+  const int id = (int)blockIdx.x * LV_THREADS + tid;           // (at most 32 768 * 129 + 255)
+  const int i = id / rows, row = id - i * rows;
+  bool keep = i < a.n;
+  int px = 0, py = 0;
+  if (keep) {
+    px = block[LV_POINTS + 2 * i]; py = block[LV_POINTS + 2 * i + 1];
+    for (int q = 0; q < a.n_skip; q++) {
+      const long long dx = (long long)px - s_disc[3 * q], dy = (long long)py - s_disc[3 * q + 1], ro = s_disc[3 * q + 2];
+      if (dx >= -ro && dx <= ro && dy >= -ro && dy <= ro && dx * dx + dy * dy <= ro * ro) keep = false;
+    }
+  }
+  const unsigned long long first_rows = __ballot(keep && row == 0);
+  if ((tid & 63) == 0 && first_rows) atomicAdd(reinterpret_cast<unsigned*>(block + LV_KEPT), (unsigned)__popcll(first_rows));
+  if (!keep) return;
+  const int dy = row - a.r, y = py + dy;
+  if ((unsigned)y >= (unsigned)a.H) return;
+  const int hw = s_hw[dy < 0 ? -dy : dy];
+  const int x0 = max(px - hw, 0), x1 = min(px + hw, a.W - 1);
+  if (x0 > x1) return;
+  uint32_t* line = words + (size_t)y * (size_t)a.stride;
+  for (int w = x0 >> 5; w <= (x1 >> 5); w++) {                 // (x1 < W: w < stride)
+    const int lo = max(x0, w << 5), hi = min(x1, (w << 5) + 31);
+    atomicOr(&line[w], (0xFFFFFFFFu >> (31 - (hi - lo))) << (lo & 31));
+  }
+}
+
+static const char* live_args_wrong(const tsd_drive_live_params* p, const int32_t* pts, int n, int width, int height)
+{
+  if (!p) return "params is NULL";
+  if (p->radius < 0 || p->radius > TSD_DRIVE_LIVE_MAX_RADIUS) return "radius is outside 0 .. TSD_DRIVE_LIVE_MAX_RADIUS";
+  if (p->n_skip < 0 || p->n_skip > TSD_DRIVE_LIVE_MAX_SKIP) return "n_skip is outside 0 .. TSD_DRIVE_LIVE_MAX_SKIP";
+  if (p->n_skip > 0 && !p->skip) return "skip is NULL";
+  if (n < 0 || n > TSD_DRIVE_LIVE_MAX_POINTS) return "n is outside 0 .. TSD_DRIVE_LIVE_MAX_POINTS";
+  if (n > 0 && !pts) return "points_xy is NULL";
+  if (width < 1 || height < 1 || width > TSD_FRONTIER_MAX_SIDE || height > TSD_FRONTIER_MAX_SIDE) return "a side outside 1 .. TSD_FRONTIER_MAX_SIDE";
+  constexpr int32_t far = 1 << 30;
+  for (int q = 0; q < p->n_skip; q++) {
+    if (p->skip[3 * q] < -far || p->skip[3 * q] > far || p->skip[3 * q + 1] < -far || p->skip[3 * q + 1] > far) return "a skip disc's centre is beyond 1 << 30";
+    if (p->skip[3 * q + 2] < 0 || p->skip[3 * q + 2] > (1 << 15)) return "a skip disc's radius is outside 0 .. 1 << 15";
+  }
+  for (int i = 0; i < 2 * n; i++)
+    if (pts[i] < -far || pts[i] > far) return "a point's coordinate is beyond 1 << 30";
+  return nullptr;
+}
+
+static int drive_live_set(tsd_ctx* ctx, const tsd_drive_live_params* p, const int32_t* pts, int n, int width, int height, int* n_kept)
+{
+  const char* who = "tsd_drive_live_set";
+  if (const char* why = live_args_wrong(p, pts, n, width, height)) return map_refused(ctx, who, why);
+  TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  tsd_ctx::Drive::Live& l = ctx->drive.live;
+  const int stride = (width + 31) / 32;
+  const size_t words = (size_t)stride * (size_t)height;
+  if (l.words < words) l.set = false;                                  // a new image holds nothing, whatever becomes of this call
+  int rc = scratch_grow(ctx, who, &l.d_words, &l.words, words, "the live layer");
+  if (!rc) rc = scratch_grow(ctx, who, &l.d_pts, &l.pts_words, LV_BLOCK, "the live layer's points");
+  if (!rc) rc = scratch_grow(ctx, who, &l.h_pts, &l.h_pts_words, LV_BLOCK, "the live layer's points, pinned", true);
+  if (rc) { l.set = false; return rc; }
+  hipStream_t stream = ctx->stream;
+  int32_t* d_new = l.d_pts;
+  l.set = false;                                                       // until the new one stands
+  int32_t* h = l.h_pts;
+  std::memset(h, 0, LV_POINTS * sizeof(int32_t));
+  if (p->n_skip) std::memcpy(h + LV_DISC, p->skip, 3 * (size_t)p->n_skip * sizeof(int32_t));
+  for (int d = 0, hw = p->radius; d <= p->radius; d++) {               // floor(sqrt(r^2 - d^2)): it falls as d grows
+    while (hw * hw > p->radius * p->radius - d * d) hw--;
+    h[LV_TABLE + d] = hw;
+  }
+  if (n) std::memcpy(h + LV_POINTS, pts, 2 * (size_t)n * sizeof(int32_t));
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(d_new, h, (LV_POINTS + 2 * (size_t)n) * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  {
+    ScopedKernelTimer t(ctx, "drive_live", true);
+    TSD_HIP_CHECK(ctx, hipMemsetAsync(l.d_words, 0, words * sizeof(uint32_t), stream));
+    const long long threads = (long long)n * (2 * p->radius + 1);
+    if (threads > 0)
+      hipLaunchKernelGGL(k_live_stamp, dim3((unsigned)((threads + LV_THREADS - 1) / LV_THREADS)), dim3(LV_THREADS), 0, stream, d_new,
+                         LvArgs{width, height, stride, p->radius, n, p->n_skip}, l.d_words);
+  }
+  TSD_HIP_CHECK(ctx, hipGetLastError());
+  TSD_HIP_CHECK(ctx, hipMemcpyAsync(h + LV_KEPT, d_new + LV_KEPT, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  TSD_HIP_CHECK(ctx, hipStreamSynchronize(stream));
+  l.set = true; l.W = width; l.H = height; l.stride = stride;
+  if (n_kept) *n_kept = h[LV_KEPT];
+  return TSD_OK;
+}
+
 // ---- the host's side of the rule
 static const int32_t* drive_table()
 {
@@ -385,12 +533,21 @@ static const char* drive_args_wrong(const tsd_ctx::Route& r, bool layered, const
   return nullptr;
 }
 
+// a layer that is set has the sides of the result's image
+static const char* drive_live_wrong(const tsd_ctx* ctx, const tsd_ctx::Route& r)
+{
+  const tsd_ctx::Drive::Live& l = ctx->drive.live;
+  return l.set && (l.W != r.W || l.H != r.H) ? "the live layer's width or height differ from the result's image" : nullptr;
+}
+
 // The rollout on instance r of the route result (tsd_ctx::route or ::fields).
 static int drive_rollout(tsd_ctx* ctx, tsd_ctx::Route& r, const char* who, const tsd_drive_params* p, const tsd_drive_pose* poses, int n_robots,
                          tsd_drive_choice* choice_host, uint64_t* scores_host, uint16_t* why_host)
 {
   const bool layered = &r == &ctx->fields;
   if (const char* why = drive_args_wrong(r, layered, p, poses, n_robots, choice_host)) return map_refused(ctx, who, why);
+  if (const char* why = drive_live_wrong(ctx, r)) return map_refused(ctx, who, why);
+  const DrLive lv{ctx->drive.live.d_words, ctx->drive.live.stride};
   TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   // the block in 32-bit words: the table | the inputs: poses, steps, turns, (even) body, (even) best, count | (even) the outputs: choices,
   // scores, why.  The pinned copy holds the inputs and the outputs.
@@ -430,11 +587,21 @@ static int drive_rollout(tsd_ctx* ctx, tsd_ctx::Route& r, const char* who, const
   unsigned long long* d_best = reinterpret_cast<unsigned long long*>(d + o_best);
   {
     ScopedKernelTimer t(ctx, r.stream == ctx->stream ? "drive_rollout" : "", true);
-    hipLaunchKernelGGL(k_drive_rollout, dim3((unsigned)((S + DR_WAVES - 1) / DR_WAVES), (unsigned)n_robots), dim3(DR_THREADS), 0, r.stream, r.d_key, r.d_w,
-                       d_tab, a, d_pose, d_step, d_turn, d_body, d_best, d + o_count, reinterpret_cast<unsigned long long*>(d + o_scores),
-                       reinterpret_cast<uint16_t*>(d + o_why));
-    hipLaunchKernelGGL(k_drive_pick, dim3((unsigned)n_robots), dim3(64), 0, r.stream, r.d_key, r.d_w, d_tab, a, d_pose, d_step, d_turn, d_body, d_best,
-                       d + o_count, reinterpret_cast<tsd_drive_choice*>(d + o_choice));
+    const dim3 groups((unsigned)((S + DR_WAVES - 1) / DR_WAVES), (unsigned)n_robots);
+    unsigned long long* d_scores = reinterpret_cast<unsigned long long*>(d + o_scores);
+    uint16_t* d_why = reinterpret_cast<uint16_t*>(d + o_why);
+    tsd_drive_choice* d_choice = reinterpret_cast<tsd_drive_choice*>(d + o_choice);
+    if (dr.live.set) {
+      hipLaunchKernelGGL(k_drive_rollout<true>, groups, dim3(DR_THREADS), 0, r.stream, r.d_key, r.d_w, d_tab, a, d_pose, d_step, d_turn, d_body, d_best,
+                         d + o_count, d_scores, d_why, lv);
+      hipLaunchKernelGGL(k_drive_pick<true>, dim3((unsigned)n_robots), dim3(64), 0, r.stream, r.d_key, r.d_w, d_tab, a, d_pose, d_step, d_turn, d_body,
+                         d_best, d + o_count, d_choice, lv);
+    } else {
+      hipLaunchKernelGGL(k_drive_rollout<false>, groups, dim3(DR_THREADS), 0, r.stream, r.d_key, r.d_w, d_tab, a, d_pose, d_step, d_turn, d_body, d_best,
+                         d + o_count, d_scores, d_why, lv);
+      hipLaunchKernelGGL(k_drive_pick<false>, dim3((unsigned)n_robots), dim3(64), 0, r.stream, r.d_key, r.d_w, d_tab, a, d_pose, d_step, d_turn, d_body,
+                         d_best, d + o_count, d_choice, lv);
+    }
   }
   TSD_HIP_CHECK(ctx, hipGetLastError());
   const size_t back = (why_host ? words : scores_host ? o_why : o_scores) - o_choice;
@@ -456,6 +623,8 @@ static int drive_fleet_rollout(tsd_ctx* ctx, const tsd_drive_params* p, const ts
   if (!fl) return map_refused(ctx, who, "fleet is NULL");
   if (!fl->order) return map_refused(ctx, who, "order is NULL");
   if (fl->sep_q16 < 0 || fl->sep_q16 > TSD_DRIVE_MAX_SEP) return map_refused(ctx, who, "sep_q16 is outside 0 .. TSD_DRIVE_MAX_SEP");
+  if (const char* why = drive_live_wrong(ctx, r)) return map_refused(ctx, who, why);
+  const DrLive lv{ctx->drive.live.d_words, ctx->drive.live.stride};
   unsigned seen = 0;
   for (int m = 0; m < n_robots; m++) {
     const int32_t q = fl->order[m];
@@ -518,10 +687,16 @@ static int drive_fleet_rollout(tsd_ctx* ctx, const tsd_drive_params* p, const ts
   {
     ScopedKernelTimer t(ctx, r.stream == ctx->stream ? "drive_fleet" : "", true);
     hipLaunchKernelGGL(k_fleet_init, dim3((unsigned)n_robots), dim3(DR_THREADS), 0, r.stream, a, d_pose, d_tracks, d_scores, d_why, d_choice);
-    if (A > 0)
-      hipLaunchKernelGGL(k_drive_rollout, dim3(groups, (unsigned)A), dim3(DR_THREADS), 0, r.stream, r.d_key, r.d_w, d_tab, a,
-                         reinterpret_cast<const tsd_drive_pose*>(d + o_apose), d_step, d_turn, d_body,
-                         reinterpret_cast<unsigned long long*>(d + o_mbest), d + o_mbest + 2 * R, d_mscores, d_mwhy);
+    if (A > 0) {                                                       // the map rows carry reason 7: the rank launches need nothing
+      const tsd_drive_pose* d_apose = reinterpret_cast<const tsd_drive_pose*>(d + o_apose);
+      unsigned long long* d_mbest = reinterpret_cast<unsigned long long*>(d + o_mbest);
+      if (dr.live.set)
+        hipLaunchKernelGGL(k_drive_rollout<true>, dim3(groups, (unsigned)A), dim3(DR_THREADS), 0, r.stream, r.d_key, r.d_w, d_tab, a, d_apose, d_step,
+                           d_turn, d_body, d_mbest, d + o_mbest + 2 * R, d_mscores, d_mwhy, lv);
+      else
+        hipLaunchKernelGGL(k_drive_rollout<false>, dim3(groups, (unsigned)A), dim3(DR_THREADS), 0, r.stream, r.d_key, r.d_w, d_tab, a, d_apose, d_step,
+                           d_turn, d_body, d_mbest, d + o_mbest + 2 * R, d_mscores, d_mwhy, lv);
+    }
     DrFleet f{n_robots, fl->sep_q16, parked};
     for (int m = 0; m < n_robots; m++) {
       const int q = fl->order[m];
@@ -581,6 +756,9 @@ void drive_free(tsd_ctx* ctx)
 {
   hipFree(ctx->drive.d_buf);
   if (ctx->drive.h_buf) hipHostFree(ctx->drive.h_buf);
+  hipFree(ctx->drive.live.d_words);
+  hipFree(ctx->drive.live.d_pts);
+  if (ctx->drive.live.h_pts) hipHostFree(ctx->drive.live.h_pts);
   ctx->drive = tsd_ctx::Drive{};
 }
 
@@ -640,6 +818,48 @@ int tsd_drive_fields_togo(tsd_ctx* ctx, const tsd_drive_pose* poses, int n_robot
 {
   if (!ctx) return TSD_E_ARG;
   return drive_fields_togo(ctx, poses, n_robots, togo_host);
+}
+
+int tsd_drive_live_set(tsd_ctx* ctx, const tsd_drive_live_params* params, const int32_t* points_xy, int n, int width, int height, int* n_kept)
+{
+  if (!ctx) return TSD_E_ARG;
+  return drive_live_set(ctx, params, points_xy, n, width, height, n_kept);
+}
+
+int tsd_drive_live_clear(tsd_ctx* ctx)
+{
+  if (!ctx) return TSD_E_ARG;
+  ctx->drive.live.set = false;                                 // (the image keeps its bits: the next set empties it first)
+  return TSD_OK;
+}
+
+int tsd_drive_live_fetch(tsd_ctx* ctx, uint32_t* words_host, long long cap_words, int* width, int* height, int* stride_words)
+{
+  if (!ctx) return TSD_E_ARG;
+  const tsd_ctx::Drive::Live& l = ctx->drive.live;
+  if (!l.set) return map_refused(ctx, "tsd_drive_live_fetch", "no live layer");
+  const long long words = (long long)l.stride * l.H;
+  if (words_host && cap_words < words) return map_refused(ctx, "tsd_drive_live_fetch", "cap_words is below stride_words * height");
+  if (words_host) {
+    TSD_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    TSD_HIP_CHECK(ctx, hipMemcpy(words_host, l.d_words, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  if (width) *width = l.W;
+  if (height) *height = l.H;
+  if (stride_words) *stride_words = l.stride;
+  return TSD_OK;
+}
+
+int tsd_drive_live_dev_ptr(tsd_ctx* ctx, const void** words_dev, int* width, int* height, int* stride_words)
+{
+  if (!ctx) return TSD_E_ARG;
+  const tsd_ctx::Drive::Live& l = ctx->drive.live;
+  if (!l.set) return map_refused(ctx, "tsd_drive_live_dev_ptr", "no live layer");
+  if (words_dev) *words_dev = l.d_words;
+  if (width) *width = l.W;
+  if (height) *height = l.H;
+  if (stride_words) *stride_words = l.stride;
+  return TSD_OK;
 }
 
 int tsd_drive_dev_ptrs(tsd_ctx* ctx, const void** block_dev, unsigned long long* words)

@@ -612,10 +612,56 @@ int driveAnswer(const DriveSamples& s, const double* originRes, int width, const
   return TSD_OK;
 }
 
-int ThreadGrid::exploreDrive(const tsd_route_goal& goal, const double* poseXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples)
+// The live layer's entry points are weak references too: a device library without them answers TSD_E_ARG.
+#pragma weak tsd_drive_live_set
+#pragma weak tsd_drive_live_clear
+
+int liveSet(tsd_ctx* ctx, const double* originRes, const LiveRequest& live, const tsd_drive_pose* poses, size_t nPoses, int width, int height,
+            int* kept)
+{
+  if(!tsd_drive_live_set || !tsd_drive_live_clear || !poses || nPoses > (size_t)TSD_DRIVE_LIVE_MAX_SKIP || (live.points.size() & 1u) ||
+     live.points.size() > 2u * TSD_DRIVE_LIVE_MAX_POINTS || !(live.radius >= 0.0) || !(live.skipRadius >= 0.0) || !std::isfinite(live.radius) ||
+     !std::isfinite(live.skipRadius))
+    return TSD_E_ARG;
+  const double radius = std::floor(live.radius / originRes[2] + 0.5), skipRadius = std::ceil(live.skipRadius / originRes[2]);
+  if(!(radius <= (double)TSD_DRIVE_LIVE_MAX_RADIUS) || !(skipRadius <= 32768.0))
+    return TSD_E_ARG;
+  std::vector<int32_t> cells(live.points.size());
+  for(size_t i = 0; i < live.points.size(); i++)
+  {
+    const double c = std::floor((live.points[i] - originRes[i & 1u]) / originRes[2]);      // (as drivePose takes a pose's cell)
+    if(!(std::fabs(c) <= 1073741824.0))
+      return TSD_E_ARG;                  // not finite, or beyond 1 << 30 cells
+    cells[i] = static_cast<int32_t>(c);
+  }
+  std::vector<int32_t> skip;
+  for(size_t r = 0; r < nPoses; r++)
+  {
+    skip.push_back(poses[r].x);
+    skip.push_back(poses[r].y);
+    skip.push_back(static_cast<int32_t>(skipRadius));
+  }
+  tsd_drive_live_params prm;
+  prm.radius = static_cast<int32_t>(radius);
+  prm.n_skip = static_cast<int32_t>(nPoses);
+  prm.skip = skip.empty() ? nullptr : skip.data();
+  return tsd_drive_live_set(ctx, &prm, cells.empty() ? nullptr : cells.data(), static_cast<int>(cells.size() / 2), width, height, kept);
+}
+
+void liveDone(tsd_ctx* ctx, const uint16_t* why, size_t nRobots, size_t samples, std::vector<int32_t>* blocked)
+{
+  tsd_drive_live_clear(ctx);
+  blocked->assign(nRobots, 0);
+  for(size_t r = 0; r < nRobots; r++)
+    for(size_t i = 0; i < samples; i++)
+      (*blocked)[r] += (why[r * samples + i] >> 12) == 7;
+}
+
+int ThreadGrid::exploreDrive(const tsd_route_goal& goal, const double* poseXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples,
+                             const LiveRequest* live, LiveAnswer* liveOut)
 {
   if(!tsd_drive_rollout || !tsd_drive_advance || !tsd_route_frame || !tsd_route_weights || !poseXyt || !out || !samples ||
-     goal.cell == TSD_ROUTE_NONE || goal.dist == TSD_ROUTE_NONE)
+     goal.cell == TSD_ROUTE_NONE || goal.dist == TSD_ROUTE_NONE || (live && (!liveOut || !tsd_drive_live_set || !tsd_drive_live_clear)))
     return TSD_E_ARG;
   std::lock_guard<std::mutex> lk(_publishMutex);
   if(_planStamp != _frames + _updates)
@@ -651,7 +697,17 @@ int ThreadGrid::exploreDrive(const tsd_route_goal& goal, const double* poseXyt, 
   if(rc != TSD_OK)
     return rc;
   tsd_drive_choice choice;
-  rc = tsd_drive_rollout(_grid.context(), &samples->prm, &pose, 1, &choice, nullptr, nullptr);
+  if(!live)
+    rc = tsd_drive_rollout(_grid.context(), &samples->prm, &pose, 1, &choice, nullptr, nullptr);
+  else
+  {
+    rc = liveSet(_grid.context(), place, *live, &pose, 1, W, H, &liveOut->kept);
+    if(rc != TSD_OK)
+      return rc;                         // (the layer before it, if any, was nobody's: none outlives a call)
+    std::vector<uint16_t> why((size_t)samples->prm.n_speeds * samples->prm.n_turns, 0);
+    rc = tsd_drive_rollout(_grid.context(), &samples->prm, &pose, 1, &choice, nullptr, why.data());
+    liveDone(_grid.context(), why.data(), 1, why.size(), &liveOut->blocked);
+  }
   if(rc != TSD_OK)
     return rc;
   return driveAnswer(*samples, place, W, pose, choice, out);

@@ -90,6 +90,29 @@ bool drivePose(const double* originRes, const double* xyt, int width, int height
 /** The answer of one robot from its choice: velocities from the chosen indices, the end cell in metres, tsd_drive_advance by one step. */
 int driveAnswer(const DriveSamples& s, const double* originRes, int width, const tsd_drive_pose& pose, const tsd_drive_choice& c, DriveAnswer* out);
 
+/** What exploreDrive is asked beside the DriveRequest where the current scans are to keep the arcs off what is not on the map yet
+ *  (tsd_drive_live_set): the scans' end points and how far to stay away from them. */
+struct LiveRequest
+{
+  std::vector<double> points;                     // pairs (x, y) [m] in the map's frame
+  double radius = 0.0;                            // [m], to the nearest cell: every cell that close to a point refuses an arc
+  double skipRadius = 0.0;                        // [m], rounded up to cells: points that close to a robot's own pose are dropped
+};
+/** ... and what it answers beside the DriveAnswers: the points no robot's disc dropped, and per robot the samples refused by reason 7. */
+struct LiveAnswer
+{
+  int kept = 0;
+  std::vector<int32_t> blocked;
+};
+/** The request in cells of the map (origin, resolution) -- a point's cell is taken as a pose's, floor((x - origin) / resolution) --
+ *  with a skip disc at every pose of `poses`, and the layer set on `ctx` for a width x height image.  TSD_E_ARG where the device
+ *  library has no live layer, for a point, radius or skip radius that is not finite or negative, and for what tsd_drive_live_set
+ *  refuses. */
+int liveSet(tsd_ctx* ctx, const double* originRes, const LiveRequest& live, const tsd_drive_pose* poses, size_t nPoses, int width, int height,
+            int* kept);
+/** tsd_drive_live_clear, and the samples of each of n robots whose `why` holds reason 7. */
+void liveDone(tsd_ctx* ctx, const uint16_t* why, size_t nRobots, size_t samples, std::vector<int32_t>* blocked);
+
 class ThreadGrid : public ThreadSLAM
 {
 public:
@@ -160,8 +183,13 @@ public:
    *  result on the context, so exploreWaypoints is refused from then on until the next explorePlan (the plan's goals and paths have
    *  been fetched by then); exploreDrive itself may be called again.  Holds the locks explorePlan holds.  TSD_E_ARG without a plan,
    *  once the map has been published again, for a goal without a cell, a pose outside the map, what driveSamples refuses, and where
-   *  the device library has no rollout. */
-  int exploreDrive(const tsd_route_goal& goal, const double* poseXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples);
+   *  the device library has no rollout.
+   *  With `live` the current scans' end points refuse arcs as well (reason 7 of the rule): the layer is set behind the route call --
+   *  the skip disc is the robot's own pose --, the rollout runs with it and it is cleared again before the locks are given up, so no
+   *  other caller of the context ever meets it.  liveOut gets the points kept and the samples the layer refused.  TSD_E_ARG also
+   *  for a NULL liveOut, what liveSet refuses and where the device library has no live layer. */
+  int exploreDrive(const tsd_route_goal& goal, const double* poseXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples,
+                   const LiveRequest* live = nullptr, LiveAnswer* liveOut = nullptr);
   /** origin x, y and resolution of <node>/map: fixed by the parameters at construction, the same before and after a publication */
   void mapPlacement(double* originRes);
 

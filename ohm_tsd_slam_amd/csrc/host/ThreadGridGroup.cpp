@@ -336,9 +336,11 @@ int ThreadGridGroup::dispatchLocked(tsd_ctx* ctx, const std::vector<int32_t>& se
 #pragma weak tsd_drive_fields_rollout
 #pragma weak tsd_drive_fleet_rollout
 #pragma weak tsd_drive_fields_togo
+#pragma weak tsd_drive_live_set
+#pragma weak tsd_drive_live_clear
 
 int ThreadGridGroup::exploreDrive(const ExploreDispatch& d, const double* posesXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples,
-                                  const FleetDriveRequest* fleet, FleetDriveAnswer* fleetOut)
+                                  const FleetDriveRequest* fleet, FleetDriveAnswer* fleetOut, const LiveRequest* live, LiveAnswer* liveOut)
 {
   const size_t L = _members.size();
   if(!tsd_drive_fields_rollout || !tsd_route_fields_dev || !posesXyt || !out || !samples || L < 1 || L > (size_t)TSD_DRIVE_MAX_ROBOTS ||
@@ -347,6 +349,8 @@ int ThreadGridGroup::exploreDrive(const ExploreDispatch& d, const double* posesX
   const bool apart = fleet && fleet->separation > 0.0;
   if(apart && (!tsd_drive_fleet_rollout || !tsd_drive_fields_togo || !fleetOut || !std::isfinite(fleet->separation) ||
                (!fleet->priority.empty() && fleet->priority.size() != L)))
+    return TSD_E_ARG;
+  if(live && (!liveOut || !tsd_drive_live_set || !tsd_drive_live_clear))
     return TSD_E_ARG;
   std::lock_guard<std::mutex> lk(_publishMutex);
   if(d.frames == 0 || d.frames != _frames)
@@ -410,9 +414,10 @@ int ThreadGridGroup::exploreDrive(const ExploreDispatch& d, const double* posesX
     for(size_t r = 0; r < L; r++)
       if(seeds[2 * r] < 0)
         poses[r].layer = -1;             // no goal: parked where it stands
-    why.resize(L * S);
     tracks.resize(L * T1 * 2);
   }
+  if(apart || live)
+    why.resize(L * S);
   {
     // as for the dispatch: member 0's context and stream carry the call
     std::lock_guard<std::mutex> fl(_members[0].grid->frontierMutex());
@@ -421,8 +426,14 @@ int ThreadGridGroup::exploreDrive(const ExploreDispatch& d, const double* posesX
     tsd_route_fields_info info;
     // layer r seeded AT member r's goal: this replaces the dispatch's robot-seeded fields result, whose answers have been fetched
     rc = tsd_route_fields_dev(ctx, tsd_group_map_dev(_group), W, H, W, &rp, &info);
+    bool layer = false;                  // the live layer stands: it goes before the locks do
+    if(rc == TSD_OK && live)
+    {
+      rc = liveSet(ctx, place, *live, poses.data(), L, W, H, &liveOut->kept);
+      layer = rc == TSD_OK;
+    }
     if(rc == TSD_OK && !apart)
-      rc = tsd_drive_fields_rollout(ctx, &samples->prm, poses.data(), static_cast<int>(L), choice.data(), nullptr, nullptr);
+      rc = tsd_drive_fields_rollout(ctx, &samples->prm, poses.data(), static_cast<int>(L), choice.data(), nullptr, live ? why.data() : nullptr);
     if(rc == TSD_OK && apart && order.empty())
     {
       // the cost-to-go of each member at its pose, from its own layer, in one round trip: 0xFFFFFFFF (no key, or no goal) sorts
@@ -440,6 +451,8 @@ int ThreadGridGroup::exploreDrive(const ExploreDispatch& d, const double* posesX
       fp.order = order.data();
       rc = tsd_drive_fleet_rollout(ctx, &samples->prm, &fp, poses.data(), static_cast<int>(L), choice.data(), nullptr, why.data(), tracks.data());
     }
+    if(layer)
+      liveDone(ctx, why.data(), L, S, &liveOut->blocked);
   }
   for(size_t r = 0; r < L && rc == TSD_OK; r++)
     rc = driveAnswer(*samples, place, W, poses[r], choice[r], out + r);

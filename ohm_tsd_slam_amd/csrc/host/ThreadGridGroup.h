@@ -21,6 +21,8 @@ struct ExplorePlan;      // ThreadGrid.h
 struct DriveRequest;
 struct DriveSamples;
 struct DriveAnswer;
+struct LiveRequest;
+struct LiveAnswer;
 
 /** What ThreadGridGroup::exploreDrive is asked beside the DriveRequest where the members have to keep off each other, and what it
  *  answers beside the DriveAnswers. */
@@ -145,9 +147,13 @@ public:
    *  clear of.  Without a priority list: the members with a goal in ascending cost-to-go at their pose (the one nearer its goal
    *  decides first; read from the goal-seeded layers), ties by index, then the others.  fleetOut gets the order used, the samples
    *  each member lost to the others and the chosen arcs in metres.  TSD_E_ARG also for a priority that is no permutation, a
-   *  separation beyond TSD_DRIVE_MAX_SEP cells, a NULL fleetOut and where the device library has no fleet rollout. */
+   *  separation beyond TSD_DRIVE_MAX_SEP cells, a NULL fleetOut and where the device library has no fleet rollout.
+   *  With `live` the current scans' end points refuse arcs as well, as in ThreadGrid::exploreDrive: one layer for all members, a
+   *  skip disc at every member's pose (one member's scanner sees the other's body), set behind the fields call and cleared before
+   *  the locks are given up. */
   int exploreDrive(const ExploreDispatch& d, const double* posesXyt, const DriveRequest& q, DriveAnswer* out, DriveSamples* samples,
-                   const FleetDriveRequest* fleet = nullptr, FleetDriveAnswer* fleetOut = nullptr);
+                   const FleetDriveRequest* fleet = nullptr, FleetDriveAnswer* fleetOut = nullptr, const LiveRequest* live = nullptr,
+                   LiveAnswer* liveOut = nullptr);
   size_t members(void) const { return _members.size(); }
 
   std::shared_ptr<rclcpp::Publisher<nav_msgs::msg::OccupancyGrid>> gridPublisher() { return _gridPub; }

@@ -710,6 +710,43 @@ int tsd_node_explore_drive(tsd_node* n, int goal, const double* pose_xyt, const 
   return TSD_OK;
 }
 
+// what the live entries take beside that: n_live scan end points as pairs (x, y) [m] in the map's frame, the radius round each [m]
+// and the radius round a robot's own pose inside which points are dropped [m]
+static bool live_request(const double* live_xy, int n_live, double radius_m, double skip_m, LiveRequest* l)
+{
+  if(n_live < 0 || (n_live > 0 && !live_xy))
+    return false;
+  l->points.assign(live_xy, live_xy + 2 * (size_t)n_live);
+  l->radius = radius_m;
+  l->skipRadius = skip_m;
+  return true;
+}
+
+// tsd_node_explore_drive with the current scans' end points keeping the arcs off what is not on the map yet (ThreadGrid::exploreDrive
+// with a LiveRequest): live_kept the points the node's own disc did not drop, blocked_live the samples refused by reason 7; both may
+// be NULL.
+int tsd_node_explore_drive_live(tsd_node* n, int goal, const double* pose_xyt, const double* limits, const int* ints, const double* footprint_xy,
+                                int n_foot, const double* live_xy, int n_live, double live_radius_m, double live_skip_m, double* out8,
+                                tsd_drive_choice* choice, int* shape4, double* dt, int* live_kept, int32_t* blocked_live)
+{
+  DriveRequest q;
+  LiveRequest l;
+  if(!n || !n->gridThread || !pose_xyt || !out8 || goal < 0 || (size_t)goal >= n->plan.goals.size() ||
+     !drive_request(limits, ints, footprint_xy, n_foot, &q) || !live_request(live_xy, n_live, live_radius_m, live_skip_m, &l))
+    return TSD_E_ARG;
+  DriveAnswer a;
+  DriveSamples s;
+  LiveAnswer la;
+  const int rc = n->gridThread->exploreDrive(n->plan.goals[(size_t)goal], pose_xyt, q, &a, &s, &l, &la);
+  if(rc != TSD_OK)
+    return rc;
+  drive_answer(a, out8, choice);
+  drive_shape(s, shape4, dt);
+  if(live_kept) *live_kept = la.kept;
+  if(blocked_live) *blocked_live = la.blocked.empty() ? 0 : la.blocked[0];
+  return TSD_OK;
+}
+
 // <node>/get_map (ThreadGrid::getMapServCallBack): the last map with a fresh stamp (map_out layout); 1 if the service answered
 int tsd_node_get_map(tsd_node* n, int8_t* data_out, double* out12, char* frame_id, int cap)
 {
@@ -1013,6 +1050,45 @@ int tsd_fleet_explore_drive_apart(tsd_fleet* f, const double* poses_xyt, const d
   if(order_out) std::memcpy(order_out, fa.order.data(), fa.order.size() * sizeof(int32_t));
   if(blocked_out) std::memcpy(blocked_out, fa.blocked.data(), fa.blocked.size() * sizeof(int32_t));
   if(tracks_out) std::memcpy(tracks_out, fa.tracks.data(), fa.tracks.size() * sizeof(double));
+  return TSD_OK;
+}
+
+// tsd_fleet_explore_drive (separation_m == 0) or tsd_fleet_explore_drive_apart (separation_m > 0) with the current scans' end points of
+// all nodes as one live layer (ThreadGridGroup::exploreDrive with a LiveRequest; a skip disc at every node's pose): live_kept the
+// points no disc dropped, blocked_live_out one int per node, the samples refused by reason 7.  order_out, blocked_out and tracks_out
+// are written with a separation only.
+int tsd_fleet_explore_drive_live(tsd_fleet* f, const double* poses_xyt, const double* limits, const int* ints, const double* footprint_xy, int n_foot,
+                                 double separation_m, const int32_t* priority, int n_priority, const double* live_xy, int n_live,
+                                 double live_radius_m, double live_skip_m, double* out8, tsd_drive_choice* choice, int* shape4, double* dt,
+                                 int32_t* order_out, int32_t* blocked_out, double* tracks_out, int tracks_cap, int* live_kept,
+                                 int32_t* blocked_live_out)
+{
+  DriveRequest q;
+  LiveRequest l;
+  if(!f || !f->group || !poses_xyt || !out8 || !drive_request(limits, ints, footprint_xy, n_foot, &q) || !(separation_m >= 0.0) || n_priority < 0 ||
+     (n_priority > 0 && (!priority || !(separation_m > 0.0))) || !live_request(live_xy, n_live, live_radius_m, live_skip_m, &l))
+    return TSD_E_ARG;
+  const bool apart = separation_m > 0.0;
+  FleetDriveRequest fq;
+  fq.separation = separation_m;
+  fq.priority.assign(priority, priority + n_priority);
+  FleetDriveAnswer fa;
+  LiveAnswer la;
+  std::vector<DriveAnswer> a(f->nodes.size());
+  DriveSamples s;
+  const int rc = f->group->exploreDrive(f->dispatch, poses_xyt, q, a.data(), &s, apart ? &fq : nullptr, apart ? &fa : nullptr, &l, &la);
+  if(rc != TSD_OK)
+    return rc;
+  if(apart && tracks_out && (size_t)std::max(tracks_cap, 0) < fa.tracks.size())
+    return TSD_E_ARG;
+  for(size_t r = 0; r < a.size(); r++)
+    drive_answer(a[r], out8 + 8 * r, choice ? choice + r : nullptr);
+  drive_shape(s, shape4, dt);
+  if(apart && order_out) std::memcpy(order_out, fa.order.data(), fa.order.size() * sizeof(int32_t));
+  if(apart && blocked_out) std::memcpy(blocked_out, fa.blocked.data(), fa.blocked.size() * sizeof(int32_t));
+  if(apart && tracks_out) std::memcpy(tracks_out, fa.tracks.data(), fa.tracks.size() * sizeof(double));
+  if(live_kept) *live_kept = la.kept;
+  if(blocked_live_out) std::memcpy(blocked_live_out, la.blocked.data(), la.blocked.size() * sizeof(int32_t));
   return TSD_OK;
 }
 

@@ -348,6 +348,14 @@ struct tsd_ctx {
   struct Drive {
     uint32_t* d_buf = nullptr; uint32_t* h_buf = nullptr; size_t words = 0, h_words = 0;
     bool table_ready = false;                // the table has been uploaded into d_buf (cleared whenever d_buf is replaced)
+    // the live layer (tsd_drive_live_*): the bit image, and the block of a set's skip discs, half-width table, kept count and points
+    // with its pinned copy.  Every call waits for its own work
+    struct Live {
+      uint32_t* d_words = nullptr; size_t words = 0;
+      int32_t* d_pts = nullptr; int32_t* h_pts = nullptr; size_t pts_words = 0, h_pts_words = 0;
+      bool set = false;                      // a layer is set: the rollouts test it
+      int W = 0, H = 0, stride = 0;
+    } live;
   } drive;
   // views (view.hip: tsd_view_gains / _claim / _claims_reset / _assign).  The candidates, their records and the pinned copies of both
   // (one capacity), and the claims image with the size it was reset at (cW == 0: none).  Allocated on first use, grown on demand and
@@ -398,7 +406,7 @@ struct tsd_ctx {
   // profiling: bit i of profile_mask times kernel i (names in capi.hip: kKernelNames)
   unsigned profile_mask = 0;
   unsigned profile_every = 1;   // time every n-th launch of a selected kernel ("name/n" in tsd_profile_select)
-  unsigned profile_every_k[27] = {};   // a kernel's own period ("name:m"), 0 = the list's
+  unsigned profile_every_k[28] = {};   // a kernel's own period ("name:m"), 0 = the list's
   bool profile = false;
   std::map<std::string, tsd::KernelTimer> timers;
   std::vector<hipEvent_t> event_pool;

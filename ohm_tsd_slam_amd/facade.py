@@ -76,6 +76,10 @@ HOST_ABI = {
     "tsd_fleet_explore_drive": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, C.c_int, _dp, C.c_void_p, _ip, _dp]),
     "tsd_fleet_explore_drive_apart": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, C.c_int, C.c_double, C.c_void_p, C.c_int, _dp, C.c_void_p, _ip, _dp,
                                                 C.c_void_p, C.c_void_p, _dp, C.c_int]),
+    "tsd_node_explore_drive_live": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _dp,
+                                              C.c_void_p, _ip, _dp, _ip, _ip]),
+    "tsd_fleet_explore_drive_live": (C.c_int, [C.c_void_p, _dp, _dp, _ip, _dp, C.c_int, C.c_double, C.c_void_p, C.c_int, _dp, C.c_int, C.c_double,
+                                               C.c_double, _dp, C.c_void_p, _ip, _dp, C.c_void_p, C.c_void_p, _dp, C.c_int, _ip, C.c_void_p]),
     "tsd_node_get_map": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_map_image_msg": (C.c_ulonglong, [C.c_void_p, C.c_void_p, _dp, C.c_char_p, C.c_int]),
     "tsd_node_grid_lock": (None, [C.c_void_p]),
@@ -473,7 +477,7 @@ class SlamNode:
                               slack, max_way, "tsd_node_explore_waypoints")
 
     def explore_drive(self, goal: int, pose, v_max: float, w_max: float, horizon_s: float, footprint=None, n_speeds=5,
-                      weights=(1, 1, 0, 0), nose_m=0.0, nose_miss=0, margin=2000) -> dict:
+                      weights=(1, 1, 0, 0), nose_m=0.0, nose_miss=0, margin=2000, live_points=None, live_radius_m=0.0, live_skip_m=0.0) -> dict:
         """The velocity of the next step towards goal ``goal`` (an index into the goals of the plan made last) for a robot at
         ``pose`` = (x, y [m], yaw [rad]) in the map's frame: a cost-to-go field seeded AT the goal's cell on the plan's source
         (tsd_route_frame, limit: the goal's dist + ``margin``), then tsd_drive_rollout -- ``n_speeds`` speeds v_max * i / (V - 1) by
@@ -484,9 +488,31 @@ class SlamNode:
         end cell [m], NaN without one), ``next_pose`` (x, y, yaw after one step), ``choice`` (capi.DRIVE_CHOICE_DTYPE), ``steps``,
         ``n_speeds``, ``n_turns``, ``n_body`` and ``dt``.  The goal-seeded field replaces the plan's route result on the device:
         ``explore_waypoints`` is refused from then on until the next ``explore_plan``.  Refused without a plan, once the map has been
-        published again, for a goal without a cell, and where the turn list would exceed 129 entries."""
+        published again, for a goal without a cell, and where the turn list would exceed 129 entries.
+
+        ``live_points``: the end points of the current scans, (N, 2) [m] in the map's frame (``scan_points``).  What the scanner sees
+        this instant is on the published map only after the next publication; with the points given every arc that comes within
+        ``live_radius_m`` (to the nearest cell) of one of them is refused as well (tsd_drive_live_set, reason 7 of the rule), but
+        for the points within ``live_skip_m`` (rounded up to cells) of the robot's own pose, which are dropped.  The layer lives for
+        this call only.  The answer then also holds ``live_kept`` (the points not dropped) and ``blocked_live`` (the samples the
+        layer refused).  The field is still planned on the published map: a closed door stalls the robot in front of it until the
+        map catches up.  ``None`` is the call above, unchanged."""
         if getattr(self, "_plan_goals", None) is None:
             raise capi.TsdError("explore_drive: no plan (explore_plan first)")
+        if live_points is not None:
+            pts = _live_points(live_points)
+            kept, blocked = C.c_int(0), C.c_int(0)
+
+            def call(pose_p, limits, ints, foot, n_foot, out, choice, shape, dt):
+                return self.lib.tsd_node_explore_drive_live(self.h, int(goal), pose_p, limits, ints, foot, n_foot,
+                                                            pts.ctypes.data_as(_dp) if pts.shape[0] else None, int(pts.shape[0]),
+                                                            float(live_radius_m), float(live_skip_m), out, choice, shape, dt, C.byref(kept),
+                                                            C.byref(blocked))
+
+            out = _drive(call, [pose], v_max, w_max, horizon_s, footprint, n_speeds, weights, nose_m, nose_miss, margin,
+                         "tsd_node_explore_drive_live")[0]
+            out.update(live_kept=kept.value, blocked_live=blocked.value)
+            return out
         return _drive(lambda *a: self.lib.tsd_node_explore_drive(self.h, int(goal), *a), [pose], v_max, w_max, horizon_s, footprint, n_speeds,
                       weights, nose_m, nose_miss, margin, "tsd_node_explore_drive")[0]
 
@@ -594,6 +620,24 @@ def _plan_dict(call, fetch, width, max_len, what):
     return {"records": rec, "centroids": cen, "goals": goals, "goal_xy": goal_xy, "paths": paths, "path_lens": lens,
             "route": info.as_dict(), "seeds": [tuple(int(v) for v in seeds[2 * k:2 * k + 2]) for k in range(n_seeds.value)],
             "seeds_used": counts[2], "origin": origin, "resolution": res}
+
+
+def scan_points(pose, ranges, angle_min: float, angle_increment: float, max_range: float) -> np.ndarray:
+    """The end points of a scan taken at ``pose`` = (x, y [m], yaw [rad]) in the map's frame, float64 (N, 2): beam i ends at
+    pose + ranges[i] * (cos, sin)(yaw + angle_min + i * angle_increment).  Readings that are not finite or beyond ``max_range`` are dropped -- they
+    ended on nothing.  What ``explore_drive`` takes as ``live_points``."""
+    r = np.asarray(ranges, dtype=np.float64).ravel()
+    a = float(pose[2]) + float(angle_min) + float(angle_increment) * np.arange(r.size, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(r) & (r <= float(max_range))
+    return np.stack([float(pose[0]) + r[ok] * np.cos(a[ok]), float(pose[1]) + r[ok] * np.sin(a[ok])], axis=1)
+
+
+def _live_points(points) -> np.ndarray:
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 2))
+    if pts.shape[0] > capi.DRIVE_LIVE_MAX_POINTS:
+        raise capi.TsdError(f"explore_drive: {pts.shape[0]} live points, at most {capi.DRIVE_LIVE_MAX_POINTS}")
+    return pts
 
 
 def _drive(call, poses, v_max, w_max, horizon_s, footprint, n_speeds, weights, nose_m, nose_miss, margin, what):
@@ -763,7 +807,8 @@ class SlamFleet:
                 "lookahead_cells": counts[4], "origin": origin, "resolution": res}
 
     def explore_drive(self, poses, v_max: float, w_max: float, horizon_s: float, footprint=None, n_speeds=5, weights=(1, 1, 0, 0),
-                      nose_m=0.0, nose_miss=0, margin=2000, separation_m=0.0, priority=None) -> list:
+                      nose_m=0.0, nose_miss=0, margin=2000, separation_m=0.0, priority=None, live_points=None, live_radius_m=0.0,
+                      live_skip_m=0.0) -> list:
         """``SlamNode.explore_drive`` for every node at once, towards the goal the last ``explore_dispatch`` gave it: ``poses`` one
         (x, y [m], yaw [rad]) per node in the merged map's frame; one fields call on the merged map seeded at the nodes' goal cells
         (unit weights, as the dispatch plans), then one tsd_drive_fields_rollout, node r on layer r.  A list of one dict per node; a
@@ -776,12 +821,20 @@ class SlamFleet:
         indices, the first decides first.  By default the nodes with a goal go in ascending cost-to-go at their pose -- the one
         nearer its goal first --, ties by index, the others behind them.  Each dict then also holds ``blocked`` (the samples the node
         lost to the others), ``tracks`` (the chosen arc, ``steps`` + 1 points (x, y) [m]; the pose itself without one) and ``rank``
-        (its place in the order used).  With 0.0 the call is the one above, unchanged."""
+        (its place in the order used).  With 0.0 the call is the one above, unchanged.
+
+        ``live_points``, ``live_radius_m``, ``live_skip_m``: as for ``SlamNode.explore_drive`` -- the end points of all nodes' current
+        scans in the merged map's frame as ONE layer for all nodes, with the points within ``live_skip_m`` of ANY node's pose dropped
+        (one node's scanner sees the other's body).  Every dict then also holds ``live_kept`` and the node's ``blocked_live``.
+        ``None`` is the call above, unchanged."""
         if len(poses) != len(self.nodes):
             raise capi.TsdError("explore_drive: one pose per node")
+        if not separation_m > 0.0 and (separation_m != 0.0 or priority is not None):
+            raise capi.TsdError("explore_drive: separation_m must be 0 or positive, and a priority needs a separation")
+        if live_points is not None:
+            return self._explore_drive_live(poses, v_max, w_max, horizon_s, footprint, n_speeds, weights, nose_m, nose_miss, margin,
+                                            float(separation_m), priority, _live_points(live_points), float(live_radius_m), float(live_skip_m))
         if not separation_m > 0.0:
-            if separation_m != 0.0 or priority is not None:
-                raise capi.TsdError("explore_drive: separation_m must be 0 or positive, and a priority needs a separation")
             return _drive(lambda *a: self.lib.tsd_fleet_explore_drive(self.h, *a), poses, v_max, w_max, horizon_s, footprint, n_speeds, weights,
                           nose_m, nose_miss, margin, "tsd_fleet_explore_drive")
         n = len(self.nodes)
@@ -798,6 +851,30 @@ class SlamFleet:
         t1 = out[0]["steps"] + 1
         for r in range(n):
             out[r].update(blocked=int(blocked[r]), tracks=tracks[r * t1:(r + 1) * t1].copy(), rank=int(np.nonzero(order == r)[0][0]))
+        return out
+
+    def _explore_drive_live(self, poses, v_max, w_max, horizon_s, footprint, n_speeds, weights, nose_m, nose_miss, margin, separation_m, priority,
+                            pts, radius_m, skip_m):
+        """explore_drive with live points (tsd_fleet_explore_drive_live), with or without a separation"""
+        n = len(self.nodes)
+        prio = np.zeros(0, dtype=np.int32) if priority is None else np.ascontiguousarray(priority, dtype=np.int32).ravel()
+        order, blocked, blocked_live = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        tracks = np.zeros((n * (capi.DRIVE_MAX_STEPS + 1), 2))
+        kept = C.c_int(0)
+
+        def call(poses_p, limits, ints, foot, n_foot, out, choice, shape, dt):
+            return self.lib.tsd_fleet_explore_drive_live(self.h, poses_p, limits, ints, foot, n_foot, separation_m,
+                                                         prio.ctypes.data if prio.size else None, int(prio.size),
+                                                         pts.ctypes.data_as(_dp) if pts.shape[0] else None, int(pts.shape[0]), radius_m, skip_m,
+                                                         out, choice, shape, dt, order.ctypes.data, blocked.ctypes.data,
+                                                         tracks.ctypes.data_as(_dp), int(tracks.size), C.byref(kept), blocked_live.ctypes.data)
+
+        out = _drive(call, poses, v_max, w_max, horizon_s, footprint, n_speeds, weights, nose_m, nose_miss, margin, "tsd_fleet_explore_drive_live")
+        t1 = out[0]["steps"] + 1
+        for r in range(n):
+            out[r].update(live_kept=kept.value, blocked_live=int(blocked_live[r]))
+            if separation_m > 0.0:
+                out[r].update(blocked=int(blocked[r]), tracks=tracks[r * t1:(r + 1) * t1].copy(), rank=int(np.nonzero(order == r)[0][0]))
         return out
 
     def merged_frames(self) -> int:
